@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- node-label MH updates/s of the sweep engine on BASELINE.json's headline workload.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no launcher in the environment (RANK / WORLD_SIZE unset) this process starts the N ranks itself
 -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...` as a
@@ -16,9 +16,21 @@ launch.  Inputs (CSR, labels, tables) are resident in HBM before the timed regio
 Chains shard over GPUs with no collective in the sweep path (scaling = "weak": 1024 chains per GPU);
 the RCCL pooling of per-chain sums and of the marginal histogram runs after the timed region.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel: sweep_fast_kernel; the HBM figure SURVEY 8(d)
-defines, the instruction-issue ceiling the counters support, and the measured HBM traffic) and `cpu_baseline` (the
-oracle restatement timed on the host cores on a bounded sample of the same workload; N = 1 only).
+A plain run sets up, runs --spinup throw-away sweeps and the W warm-up sweeps, times the K steps, writes the outputs
+of the last timed step when --dump-outputs DIR is given, and prints ONE JSON line on rank 0: `value` = updates/s over
+the K steps, `ms_per_step` = wall milliseconds per timed step, and `roofline` (dominant kernel: sweep_fast_kernel; the
+HBM figure SURVEY 8(d) defines, from the timed launches and the profile summaries committed under profiles/).
+
+--full adds what the headline figure does not need, after the timed region: the pooling epilogue (with N > 1 its
+timings), `equilibrated_start`, `steady_state.live` (the same chains after 150 sweeps, default workload, N = 1) and
+`cpu_baseline` (the oracle restatement timed on the host cores on a bounded sample of the same workload; N = 1 only);
+--no-extras / --no-cpu-baseline leave parts of it out.
+
+--dump-outputs DIR: what the caller of the timed path holds after the last timed step, as DIR/<name>.npy (rank 0's
+chains): acceptance_rate (what anneal() returned), accepted_moves and cum_dS (per chain, float64), m (block edge counts
+of a fixed, evenly spaced sample of the chains, float64) and memberships (labels of a fixed sample of the chains,
+float32), 48 MB and 24 bytes per chain at most.  The graph, the chains' seeds and the number of sweeps before every step are fixed by the
+arguments, so two runs with the same arguments compute the same outputs.
 """
 import argparse
 import importlib
@@ -65,9 +77,10 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--spinup", type=int, default=4,
-                    help="throw-away sweeps before the warm-up (four: the library launches every pass depth twice before it "
-                         "trusts a measurement); up to 6 more while launch times still settle")
+    ap.add_argument("--spinup", type=int, default=6,
+                    help="throw-away sweeps before the warm-up, exactly this many (six: the library's start-up walk launches every "
+                         "pass depth it tries twice, at most six launches, so the warm-up runs the depth it settled on; a fixed "
+                         "count keeps the chains' history, and with it what the timed steps compute, the same from run to run)")
     ap.add_argument("--chains", type=int, default=None, help="chains per GPU (default 1024; 256 for --edgelist n_1000)")
     ap.add_argument("--na", type=int, default=500_000)
     ap.add_argument("--nb", type=int, default=500_000)
@@ -79,16 +92,23 @@ def parse_args(argv=None):
                          "blocks of the contiguous initial partition); --edgelist n_1000 = the reference's shipped 1000-node data "
                          "set as BASELINE configs[1] runs it (Ka = 4, Kb = 6, 256 chains, 2000 sweeps per step)")
     ap.add_argument("--steady-sweeps", type=int, default=None,
-                    help="after the timed region let the chains run on until they have done this many sweeps in all, then time "
-                         "three more: the steady-state figure, measured live.  Default: 150 on the default workload with one GPU "
-                         "(~1.5 min; --no-extras skips it), 0 otherwise")
+                    help="with --full: after the timed region let the chains run on until they have done this many sweeps in all, "
+                         "then time three more: the steady-state figure, measured live.  Default: 150 on the default workload "
+                         "with one GPU (~1.5 min; --no-extras skips it), 0 otherwise")
     ap.add_argument("--sweeps-per-step", type=int, default=1, help="sweeps of every chain per timed step (small graphs: one launch should last milliseconds)")
     ap.add_argument("--rng", choices=["philox", "compat"], default="philox",
                     help="compat: the mt19937-compat path (the reference's own random streams, draw order and summation order -- the "
                          "only path that is bit-exact with the reference; a verification mode, one generic-kernel wave per chain)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: the pooling epilogue, the "
+                         "equilibrated-start and live after-150-sweeps figures, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's chains) as DIR/<name>.npy, float32 / float64, "
+                         "48 MB and 24 bytes per chain at most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra legs after the timed region (equilibrated-start figure, pooling timings)")
+                    help="with --full: skip the extra legs after the timed region (equilibrated-start and after-150-sweeps "
+                         "figures, pooling timings)")
     ap.add_argument("--shuffle-ids", action="store_true",
                     help="custom workload: renumber the nodes of each type at random (ids that carry no structure)")
     ap.add_argument("--planted-start", action="store_true",
@@ -96,7 +116,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-reorder", action="store_true",
                     help="with --shuffle-ids: do not run the ingest-time locality reordering pass")
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)  # internal: one CPU-baseline process
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steady_sweeps is not None and not args.full:
+        ap.error("--steady-sweeps is one of the --full legs")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------- launcher
@@ -338,6 +363,41 @@ def cpu_baseline(n, n_edges, seconds_budget=18.0, probe=None):
                                          "probe": pr}}
 
 
+# ----------------------------------------------------------------------------------------------- outputs
+DUMP_M_BYTES = 16 << 20       # --dump-outputs: block edge counts of a sample of the chains
+DUMP_LABEL_BYTES = 32 << 20   # ... and labels of a (smaller) sample
+
+
+def _evenly_spaced(count, k):
+    """k indices out of range(count), evenly spaced, first and last included (all of them when k >= count)."""
+    k = max(1, min(count, k))
+    return np.unique(np.linspace(0, count - 1, k).round().astype(np.int64))
+
+
+def dump_outputs(out_dir, model, rates):
+    """What the caller of the timed path holds after the last timed step, as out_dir/<name>.npy.  Per chain: `rates` (what
+    anneal() returned), the step's accepted moves and the running sum of accepted dS; for a fixed sample of the chains the
+    block edge counts m (K x K; left out when one chain's alone exceed the budget) and the labels -- of every node, or of a
+    fixed seeded sample of the nodes when one chain's labels alone exceed the budget.  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    nc, n, K = model.n_chains, model.n, model.K
+    out = {"acceptance_rate": np.atleast_1d(np.asarray(rates, dtype=np.float64)),
+           "accepted_moves": model.last_counts()[0].astype(np.float64),
+           "cum_dS": model.get_entropy().astype(np.float64)}
+    if K * K * 8 <= DUMP_M_BYTES:
+        chains = _evenly_spaced(nc, DUMP_M_BYTES // (K * K * 8))
+        out["m"] = np.stack([model.get_m(int(c)) for c in chains]).astype(np.float64)
+    chains = _evenly_spaced(nc, DUMP_LABEL_BYTES // (n * 4))
+    nodes = None
+    if n * 4 > DUMP_LABEL_BYTES:
+        nodes = np.sort(np.random.default_rng(0).choice(n, DUMP_LABEL_BYTES // 4, replace=False))
+    out["memberships"] = np.stack([model.get_memberships(int(c)) if nodes is None else model.get_memberships(int(c))[nodes]
+                                   for c in chains]).astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 # ----------------------------------------------------------------------------------------------- main
 def profile_json(name):
     path = os.path.join(ROOT, "profiles", name)
@@ -433,10 +493,10 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # Spin-up, not part of the protocol's W + K steps: the chains simply run on through a few throw-away sweeps -- at
-    # least --spinup of them, then until two launches in a row are within 5 % of the fastest one seen -- so the warm-up
-    # and timed sweeps are later sweeps of the same chains (slightly slower ones: the accepted fraction and with it
-    # the speed drift down by ~0.5 % per sweep).
+    # Spin-up, not part of the protocol's W + K steps: the chains simply run on through --spinup throw-away sweeps, so
+    # the warm-up and timed sweeps are later sweeps of the same chains (slightly slower ones: the accepted fraction and
+    # with it the speed drift down by ~0.5 % per sweep).  Always the same number of them: the chains, and what the timed
+    # steps compute, do not depend on how fast a launch happened to be.
     verbose = bool(os.environ.get("BISBM_BENCH_VERBOSE"))
 
     def note(what):
@@ -446,15 +506,13 @@ def main():
                 time.time()), file=sys.stderr, flush=True)
 
     def sweep():  # one timed step: --sweeps-per-step sweeps of every chain in one launch
-        mh.anneal(model, pkg.constant_schedule, [1.0], n * args.sweeps_per_step, 1 << 60)  # blocks until the sweep kernel is done
+        return mh.anneal(model, pkg.constant_schedule, [1.0], n * args.sweeps_per_step, 1 << 60)  # blocks until the sweep kernel is done
 
     spin_ms = []
-    while args.spinup and len(spin_ms) < args.spinup + 6:
+    for _ in range(args.spinup):
         sweep()
         note("spin-up")
         spin_ms.append(model.last_sweep_timing()[0])
-        if len(spin_ms) >= max(args.spinup, 2) and max(spin_ms[-2:]) <= 1.05 * min(spin_ms):
-            break
     for _ in range(args.warmup):
         sweep()
         note("warm-up")
@@ -463,8 +521,9 @@ def main():
     kernel_ms, updates = 0.0, 0
     pass_steps = []  # steps per pass of each timed launch (chosen per launch by the library; the chain does not depend on it)
     launch_ms, launch_acc = [], []  # ... its kernel time and the fraction of its steps that were accepted
+    rates = None
     for _ in range(args.steps):
-        sweep()
+        rates = sweep()
         ms, upd = model.last_sweep_timing()
         pass_steps.append(model.last_pass_steps())
         launch_ms.append(round(ms, 2))
@@ -486,40 +545,44 @@ def main():
         total_updates = updates
 
     # ---- after the timed region -------------------------------------------------------------------------------------
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before the --full legs move the chains on
+        dumped = dump_outputs(args.dump_outputs, model, rates)
     extras = {}
-    # pooling epilogue: RCCL all_gather of the per-chain sums
-    cum = torch.from_numpy(model.get_entropy()).to(coll_device).reshape(-1, 1)
-    sync()
-    t1 = time.perf_counter()
-    allcum = shard.all_gather_chain_values(cum)
-    torch.cuda.synchronize()
-    pool_ms = (time.perf_counter() - t1) * 1e3
-    assert allcum.shape[0] == args.chains * world and bool(torch.isfinite(allcum).all())
-    if world > 1 and not args.no_extras:
-        extras["pool_all_gather_ms"] = pool_ms
-        # marginals: one sample of every chain into a device histogram, pooled by reduce_scatter over node ranges
-        # (128 MB of counts at this workload, 1 GB at config 5's)
-        dev = torch.device("cuda", device_index)
-        counts = torch.zeros((n, model.kmax), dtype=torch.int32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()  # (the zero fill is torch's stream, the histogram kernel the library's)
-        model.marginals_accumulate(counts.data_ptr())
-        torch.cuda.synchronize()
-        send = counts if backend == "nccl" else counts.cpu()
+    if args.full:
+        # pooling epilogue: RCCL all_gather of the per-chain sums
+        cum = torch.from_numpy(model.get_entropy()).to(coll_device).reshape(-1, 1)
         sync()
         t1 = time.perf_counter()
-        lab = shard.map_labels(send, na, ka)
-        if backend == "nccl":
+        allcum = shard.all_gather_chain_values(cum)
+        torch.cuda.synchronize()
+        pool_ms = (time.perf_counter() - t1) * 1e3
+        assert allcum.shape[0] == args.chains * world and bool(torch.isfinite(allcum).all())
+        if world > 1 and not args.no_extras:
+            extras["pool_all_gather_ms"] = pool_ms
+            # marginals: one sample of every chain into a device histogram, pooled by reduce_scatter over node ranges
+            # (128 MB of counts at this workload, 1 GB at config 5's)
+            dev = torch.device("cuda", device_index)
+            counts = torch.zeros((n, model.kmax), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()  # (the zero fill is torch's stream, the histogram kernel the library's)
+            model.marginals_accumulate(counts.data_ptr())
             torch.cuda.synchronize()
-        extras["pool_marginals_reduce_scatter_argmax_all_gather_ms"] = (time.perf_counter() - t1) * 1e3
-        extras["pool_marginals_bytes"] = int(counts.numel() * 4)
-        assert lab.shape[0] == n
-        del counts, send
+            send = counts if backend == "nccl" else counts.cpu()
+            sync()
+            t1 = time.perf_counter()
+            lab = shard.map_labels(send, na, ka)
+            if backend == "nccl":
+                torch.cuda.synchronize()
+            extras["pool_marginals_reduce_scatter_argmax_all_gather_ms"] = (time.perf_counter() - t1) * 1e3
+            extras["pool_marginals_bytes"] = int(counts.numel() * 4)
+            assert lab.shape[0] == n
+            del counts, send
 
     # the same chains further along (a marginalize run lives there, not in the burn-in the protocol's sweeps see)
     if args.steady_sweeps is None:
         is_default = ((na, nb, args.edges, ka, kb, args.chains) == (500_000, 500_000, 10_000_000, 32, 32, 1024) and not args.edgelist
                       and not args.shuffle_ids and not args.planted_start and args.rng == "philox" and args.sweeps_per_step == 1)
-        args.steady_sweeps = 150 if (is_default and world == 1 and not args.no_extras) else 0
+        args.steady_sweeps = 150 if (args.full and is_default and world == 1 and not args.no_extras) else 0
     steady_live = None
     sweeps_so_far = (len(spin_ms) + args.warmup + args.steps) * args.sweeps_per_step
     if args.steady_sweeps > sweeps_so_far:
@@ -542,7 +605,7 @@ def main():
     # the same workload from an equilibrated start: every chain on the planted partition (the posterior mode of this
     # generator), a few sweeps to settle, then timed -- the regime a long marginalize run lives in
     equil = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         model.set_memberships(planted)
         model.init_bisbm()
         for _ in range(3):
@@ -654,7 +717,9 @@ def main():
             "steady_state": steady,
         }
         out.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             del model
             out["cpu_baseline"] = cpu_baseline(n, E, probe=REF_PROBE_N1000 if args.preset == "BASELINE configs[1]" else None)
         print(json.dumps(out), flush=True)

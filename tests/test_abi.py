@@ -271,3 +271,56 @@ def test_bench_host_helpers():
     for name in ("r04_traffic.json", "r04_issue.json", "r04_steady_state.json"):
         j = bench.profile_json(name)
         assert j is not None and len(j.get("build", "")) == 12, name
+
+
+def test_bench_options_and_output_dump(tmp_path):
+    """bench.py without a GPU: a plain run leaves every leg beyond the headline figure to --full, and --dump-outputs writes
+    what a caller of the timed path holds (a stand-in model here) as float32 / float64 arrays within the byte budget, with
+    the same chains and nodes sampled on every call."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.spinup, a.full, a.dump_outputs, a.steady_sweeps) == (7, 2, 6, False, None, None)
+    assert bench.parse_args(["--full", "--steady-sweeps", "40"]).steady_sweeps == 40
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steady-sweeps", "40"])  # a --full leg
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0", "--dump-outputs", str(tmp_path)])
+
+    class Model:  # the getters dump_outputs uses, with labels / counts that tell the chains apart
+        def __init__(self, n_chains, n, K):
+            self.n_chains, self.n, self.K = n_chains, n, K
+
+        def last_counts(self):
+            return np.arange(self.n_chains, dtype=np.uint64) * 3, np.ones(self.n_chains, dtype=np.uint64)
+
+        def get_entropy(self):
+            return -np.arange(self.n_chains, dtype=np.float64)
+
+        def get_m(self, c):
+            return np.full((self.K, self.K), c, dtype=np.int32)
+
+        def get_memberships(self, c):
+            return (np.arange(self.n, dtype=np.uint32) + c) % self.K
+
+    for n_chains, n, K in ((1024, 1_000_000, 64), (3, 1000, 10), (2, 9_000_000, 4)):
+        shapes = {}
+        for run in ("a", "b"):
+            d = tmp_path / ("%d_%s" % (n_chains, run))
+            rates = np.linspace(0, 1, n_chains)
+            shapes[run] = bench.dump_outputs(str(d), Model(n_chains, n, K), rates if n_chains > 1 else float(rates[0]))
+            arrays = {p.stem: np.load(str(p)) for p in d.iterdir()}
+            assert set(arrays) == {"acceptance_rate", "accepted_moves", "cum_dS", "m", "memberships"}
+            assert all(x.dtype in (np.float32, np.float64) for x in arrays.values())
+            assert sum(x.nbytes for x in arrays.values()) <= (48 << 20) + 24 * n_chains
+            assert (arrays["acceptance_rate"] == rates).all() and (arrays["accepted_moves"] == 3 * np.arange(n_chains)).all()
+            m, lab = arrays["m"], arrays["memberships"]
+            assert m.shape[1:] == (K, K) and m[0, 0, 0] == 0 and m[-1, 0, 0] == n_chains - 1  # first and last chain
+            last = n_chains - 1 if n * 4 <= (32 << 20) else 0  # (a larger graph: one chain, a sample of its nodes)
+            assert lab.shape[1] == min(n, (32 << 20) // 4) and (lab[-1, 0] - lab[0, 0]) % K == last % K
+            if run == "b":
+                for name, x in arrays.items():
+                    assert (np.load(str(tmp_path / ("%d_a" % n_chains) / (name + ".npy"))) == x).all(), name
+        assert shapes["a"] == shapes["b"]

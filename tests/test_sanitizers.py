@@ -6,6 +6,7 @@ sanitizer support; the kernels are covered by the parity tests instead):
 CPU only; g++/gcc from the image."""
 import os
 import random
+import shutil
 import subprocess
 import sys
 
@@ -52,7 +53,9 @@ def test_cli_argument_handling_under_sanitizers(san_dir):
     exe = os.path.join(san_dir, "mcmc_san")
     subprocess.run(["g++", "-std=c++17", *SAN, "-o", exe, os.path.join(PKG, "host", "mcmc_main.cpp"), "-L" + PKG, "-lbisbm_hip",
                     "-Wl,-rpath," + PKG], check=True, capture_output=True)
-    el = os.path.join(ROOT, "tests", "golden", "southernWomen.edgelist")
+    # a copy: --csr_cache writes <edge list>.bisbm_csr beside the file it reads
+    el = os.path.join(san_dir, "southernWomen.edgelist")
+    shutil.copy(os.path.join(ROOT, "tests", "golden", "southernWomen.edgelist"), el)
     good = ["-e", el, "-y", "18", "14", "-n", "4", "4", "4", "3", "3", "3", "3", "3", "3", "2", "-z", "5", "5", "-t", "3200", "-x", "100",
             "-c", "exponential", "-a", "10", "0.1", "-E", "0.001", "--randomize", "-d", "1"]
     cases = [good, [], ["-h"], ["--help"], ["-e"], ["-e", "/nonexistent"], ["-y"], ["-y", "18"], ["-n"], ["-z", "5"],
