@@ -32,6 +32,8 @@ BISBM_ERR_UNSUPPORTED = 3
 BISBM_ERR_NO_DEVICE = 4
 BISBM_ERR_HIP = 5
 BISBM_ERR_STATE = 6
+ALIGN_NONE = 0
+ALIGN_REFERENCE = 1
 RNG_PHILOX = 0
 RNG_MT19937_COMPAT = 1
 ALL_CHAINS = -1
@@ -68,6 +70,11 @@ ABI = {
     "bisbm_marginals_accumulate": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bisbm_marginals_reset": (C.c_int, [C.c_void_p]),
     "bisbm_marginals_get": (C.c_int, [C.c_void_p, _u32p]),
+    "bisbm_marginals_set_alignment": (C.c_int, [C.c_void_p, C.c_int]),
+    "bisbm_marginals_set_reference": (C.c_int, [C.c_void_p, _u32p]),
+    "bisbm_marginals_get_reference": (C.c_int, [C.c_void_p, _u32p, C.POINTER(C.c_int64)]),
+    "bisbm_marginals_get_alignment": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u64p]),
+    "bisbm_align_assignment": (C.c_int, [C.c_uint32, _u32p, _u32p, _u64p]),
     "bisbm_get_ka_kb": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bisbm_get_ka_kb_chain": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "bisbm_agg_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -300,6 +307,7 @@ class BlockModel:
         self.n = self.na + self.nb
         self.KA, self.KB = int(KA), int(KB)
         self.K = self.KA + self.KB
+        self.alignment = ALIGN_NONE  # marginals_set_alignment
         self.mixed_shapes = False  # True once a one-argument agg_merge left the chains with different block counts
         self.epsilon = float(epsilon)
         self.n_chains = int(n_chains)
@@ -502,6 +510,40 @@ class BlockModel:
         self._check(self._L.bisbm_marginals_get(self._h, _p(out, _u32p)))
         return out
 
+    def marginals_set_alignment(self, mode):
+        """ALIGN_REFERENCE (or True): every chain's labels are counted through its permutation onto the reference partition
+        (include/bisbm.h, "Label alignment before pooling"); ALIGN_NONE (False, the default): raw labels.  Holds across resets;
+        refused while the internal histogram holds samples of the other mode."""
+        self._check(self._L.bisbm_marginals_set_alignment(self._h, int(mode)))
+        self.alignment = int(mode)
+
+    def marginals_set_reference(self, labels=None):
+        """n labels of the present block counts as the reference of the alignment; None: the lowest-description-length chain,
+        taken at the next aligned sample."""
+        if labels is None:
+            self._check(self._L.bisbm_marginals_set_reference(self._h, None))
+            return
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        if len(lab) != self.n:
+            raise ValueError("reference has %d labels, graph has %d nodes" % (len(lab), self.n))
+        self._check(self._L.bisbm_marginals_set_reference(self._h, _p(lab, _u32p)))
+
+    def marginals_reference(self):
+        """(labels uint32 [n], chain): the reference of the alignment and the chain it came from (-1: set by the caller)."""
+        out = np.zeros(self.n, dtype=np.uint32)
+        chain = C.c_int64()
+        self._check(self._L.bisbm_marginals_get_reference(self._h, _p(out, _u32p), C.byref(chain)))
+        return out, chain.value
+
+    def marginals_alignment(self, chain):
+        """(perm uint32 [KA + KB], overlap): chain's permutation of the last aligned sample in global-label form (label r was
+        counted as perm[r]) and its overlap with the reference."""
+        ka, kb = self.ka_kb(chain)
+        perm = np.zeros(ka + kb, dtype=np.uint32)
+        tot = C.c_uint64()
+        self._check(self._L.bisbm_marginals_get_alignment(self._h, int(chain), _p(perm, _u32p), C.byref(tot)))
+        return perm, tot.value
+
     def marginals_map(self):
         """MAP block of every node from the internal histogram (most frequent block, ties -> the lowest), pooled over the
         handle's devices on the devices (``bisbm_marginals_map``: reduce-scatter -> argmax -> all-gather)."""
@@ -524,6 +566,20 @@ class BlockModel:
         self._check(self._L.bisbm_debug_log_q(self._h, _p(n, _i32p), _p(k, _i32p), len(n), int(bool(fast)),
                                               _p(out, _f64p)))
         return out
+
+
+def align_assignment(table):
+    """The alignment's assignment solver on the host (bisbm_align_assignment): table [k, k] of overlaps C[r][s] ->
+    (perm uint32 [k] maximising sum_r C[r][perm[r]], that sum).  Needs no device."""
+    t = np.ascontiguousarray(table, dtype=np.uint32)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or t.shape[0] == 0:
+        raise ValueError("table must be a non-empty square matrix")
+    perm = np.zeros(t.shape[0], dtype=np.uint32)
+    tot = C.c_uint64()
+    rc = lib().bisbm_align_assignment(t.shape[0], _p(t, _u32p), _p(perm, _u32p), C.byref(tot))
+    if rc != BISBM_OK:
+        raise BisbmError(rc, (lib().bisbm_last_error(None) or b"").decode())
+    return perm, tot.value
 
 
 def _fmt_g6(x):

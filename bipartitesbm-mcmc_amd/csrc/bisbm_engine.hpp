@@ -8,6 +8,7 @@
 //   bisbm_marginals.hip  per-node label histogram, MAP labels of one engine
 //   bisbm_multi.hip      several devices behind one handle: creation, dispatch, pooling (RCCL / peer copies)
 //   bisbm_merge.hip      agg_merge / agg_split between anneals, chains of one handle in different shapes
+//   bisbm_align.hip      label alignment of the chains to a reference partition before their samples are pooled
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -55,6 +56,28 @@ double h_lgamma_fast(const HostTables& t, uint64_t x);                // cache.h
 double h_lbinom_fast(const HostTables& t, uint64_t N, uint64_t k);    // util.hh:41-47
 // metropolis_hasting.cc:10-13,20-23 with the host libm for steps t0 .. t0 + len - 1 of a call
 std::vector<double> schedule_table(int schedule, float kw0, float kw1, uint64_t t0, uint64_t len, int* zero_after);
+
+// Label alignment of the marginal histogram (bisbm_align.hip).  The mode, the reference and `samples` belong to the handle
+// the caller holds; the buffers and the last permutations belong to the engines that run the kernels (a plain handle, a
+// group, a device entry).
+struct AlignState {
+    int mode = 0;                 // BISBM_ALIGN_NONE / BISBM_ALIGN_REFERENCE
+    bool samples = false;         // the internal histogram holds samples (a mode change is refused then)
+    bool has_ref = false;
+    int64_t ref_chain = -1;       // chain the reference came from; -1: set by the caller
+    uint32_t ref_ka = 0, ref_kb = 0;
+    std::vector<uint32_t> ref;    // n labels
+    uint64_t serial = 0;          // bumped whenever the reference changes
+    // kernel-running engine
+    uint64_t uploaded = 0;        // serial of the reference in d_ref
+    uint8_t* d_ref = nullptr;     // label_stride bytes
+    uint32_t* d_tab = nullptr;    // [chain][ka*ka + kb*kb] overlap tables
+    uint8_t* d_perm = nullptr;    // [chain][ka + kb] permutation, global-label form
+    uint64_t* d_tot = nullptr;    // [chain][2] overlap totals per type
+    size_t tab_cap = 0, perm_cap = 0, tot_cap = 0;
+    bool have_perm = false;
+    uint32_t perm_ka = 0, perm_kb = 0;
+};
 
 }  // namespace bisbm
 
@@ -143,6 +166,7 @@ struct bisbm_engine {
     std::vector<uint32_t> dev_first;
     struct DevicePool* pool = nullptr;
     uint64_t counts_rows = 0;  // rows of the internal marginal buffer (n, or n rounded up to a multiple of the device count)
+    bisbm::AlignState align;
 };
 
 namespace bisbm {
@@ -278,5 +302,8 @@ int multi_marginals_map(bisbm_engine* h, uint32_t* labels_out);
 void multi_free(bisbm_engine* h);
 // MAP labels from the internal histogram of one engine (no pooling); bisbm_marginals.hip
 int single_marginals_map(bisbm_engine* h, uint32_t* labels_out);
+// bisbm_marginals_accumulate with the alignment on; the buffers of alignment (bisbm_destroy); bisbm_align.hip
+int align_accumulate(bisbm_engine* h, uint32_t* device_counts);
+void align_free(bisbm_engine* h);
 
 }  // namespace bisbm

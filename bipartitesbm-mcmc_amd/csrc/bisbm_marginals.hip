@@ -30,6 +30,8 @@ extern "C" {
 
 int bisbm_marginals_reset(bisbm_handle h) {
     if (!h) return BISBM_ERR_INVALID_ARG;
+    h->align.samples = false;
+    if (h->align.has_ref && h->align.ref_chain >= 0) h->align.has_ref = false;  // (a caller's reference stays)
     if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_marginals_reset(d); });
     if (!h->groups.empty() && !common_shape(h))
         return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: no common marginal histogram");
@@ -50,8 +52,11 @@ int bisbm_marginals_reset(bisbm_handle h) {
     return BISBM_OK;
 }
 
-int bisbm_marginals_accumulate(bisbm_handle h, uint32_t* device_counts) {
-    if (!h) return BISBM_ERR_INVALID_ARG;
+}  // extern "C"
+
+namespace {
+
+int accumulate_plain(bisbm_engine* h, uint32_t* device_counts) {
     if (!h->devs.empty()) {
         if (device_counts) return fail(h, BISBM_ERR_UNSUPPORTED, "a handle over several devices accumulates into its own buffers (device_counts must be NULL); bisbm_marginals_map pools them");
         if (int rc = multi_common_shape(h, nullptr, nullptr)) return rc;
@@ -83,6 +88,17 @@ int bisbm_marginals_accumulate(bisbm_handle h, uint32_t* device_counts) {
     HIPCHK(h, launch_marginals(mp, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bisbm_marginals_accumulate(bisbm_handle h, uint32_t* device_counts) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    const int rc = h->align.mode == BISBM_ALIGN_REFERENCE ? align_accumulate(h, device_counts) : accumulate_plain(h, device_counts);
+    if (rc == BISBM_OK && !device_counts) h->align.samples = true;
+    return rc;
 }
 
 int bisbm_marginals_get(bisbm_handle h, uint32_t* counts_out) {

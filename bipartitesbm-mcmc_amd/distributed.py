@@ -66,6 +66,26 @@ class ChainShard:
         return torch.cat([o[:c] for o, c in zip(out, self.counts)], dim=0)
 
     # -- marginals --------------------------------------------------------------------------
+    def lowest_chain_labels(self, model):
+        """(global chain id, labels uint32 [n]) of the chain of the lowest description length over all ranks (ties -> the
+        lowest global chain id): the reference partition of an aligned marginalisation.  The description lengths are
+        all-gathered, the owning rank broadcasts the chain's labels."""
+        import torch
+        dist = _dist()
+        dev = _collective_device(self)
+        local = torch.as_tensor(np.asarray(model.entropy(), dtype=np.float64)).reshape(-1)
+        allv = self.all_gather_chain_values(local.to(dev)).cpu().numpy()
+        best = int(np.argmin(allv))  # (the first minimum: the lowest global chain id among ties)
+        owner = next(r for r in range(self.world_size) if best < sum(self.counts[: r + 1]))
+        if owner == self.rank:
+            lab = torch.as_tensor(np.asarray(model.get_memberships(best - self.first_chain_id), dtype=np.int64)).to(dev)
+        else:
+            lab = torch.zeros(model.n, dtype=torch.int64, device=dev)
+        if self.world_size > 1:
+            src = dist.get_global_rank(self.group, owner) if self.group is not None else owner
+            dist.broadcast(lab, src=src, group=self.group)
+        return best, lab.cpu().numpy().astype(np.uint32)
+
     def node_range(self, n, rank=None):
         """Node rows [lo, hi) of the pooled histogram that `rank` reduces in map_labels (the n % world last rows are
         summed on every rank)."""
@@ -115,6 +135,15 @@ class ChainShard:
             dist.all_reduce(tail, op=dist.ReduceOp.SUM, group=self.group)
             parts.append(label_rows(tail, n_main))
         return torch.cat(parts) if len(parts) > 1 else parts[0]
+
+
+def _collective_device(shard):
+    """where the tensors of a collective live: the current GPU for nccl, the host for gloo (and without a process group)"""
+    import torch
+    dist = _dist()
+    if dist.is_initialized() and dist.get_backend(shard.group) == "nccl":
+        return torch.device("cuda", torch.cuda.current_device())
+    return torch.device("cpu")
 
 
 def _argmax_first(counts):

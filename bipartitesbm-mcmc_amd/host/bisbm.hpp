@@ -246,6 +246,13 @@ public:
     // (most frequent block, ties -> lowest index) in the reference's block numbering.
     void marginals_reset() { check(bisbm_marginals_reset(h_)); }
     void marginals_accumulate() { check(bisbm_marginals_accumulate(h_, nullptr)); }
+    // label alignment before pooling (include/bisbm.h): on / off, and the chain the reference was taken from (-1: the caller's)
+    void marginals_set_alignment(bool on) { check(bisbm_marginals_set_alignment(h_, on ? BISBM_ALIGN_REFERENCE : BISBM_ALIGN_NONE)); }
+    int64_t marginals_reference_chain() {
+        int64_t chain = -1;
+        check(bisbm_marginals_get_reference(h_, nullptr, &chain));
+        return chain;
+    }
     // the marginal estimate of README.md:49-53: every node's most frequent block, pooled over the handle's devices on the
     // devices (bisbm_marginals_map)
     uint_vec_t marginal_map_labels(size_t /*NA*/) {

@@ -4,7 +4,7 @@
 // partition rules (:241-326), same stdout contract: the label vector through output_vec (trailing blank,
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
-// Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize.
+// Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -44,7 +44,7 @@ const option_spec kOptions[] = {
     {"seed", 'd', 1},           {"help", 'h', 0},
     // engine extras
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
-    {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},
+    {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -168,6 +168,8 @@ void print_help(const char* argv0) {
                  "                                        -f and drops them): T = 1, -b burn-in steps, then -t steps with a\n"
                  "                                        sample every -f steps (whole sweeps, at least one between samples);\n"
                  "                                        prints every node's most frequent block over samples and chains.\n"
+                 "  --align                               With --marginalize: match every chain's block labels to those of the\n"
+                 "                                        lowest-description-length chain before pooling (needed for --chains > 1).\n"
                  "  --csr_cache                           Keep a binary CSR beside the edge list (<path>.bisbm_csr, checked\n"
                  "                                        against the file's size and mtime); the text file stays the input.\n";
 }
@@ -187,6 +189,10 @@ int main(int argc, char const* argv[]) {
     if (count("help") > 0 || argc == 1) {  // mcmc_main.cc:99-105
         print_help(argv[0]);
         return 0;
+    }
+    if (count("align") && !count("marginalize")) {
+        std::cerr << "--align aligns the chains' block labels before pooling: it needs --marginalize.\n";
+        return 1;
     }
     if (count("edge_list_path") == 0) {
         std::cerr << "edge_list_path is required (-e flag)\n";
@@ -634,6 +640,7 @@ int main(int argc, char const* argv[]) {
             const size_t never = std::numeric_limits<size_t>::max();
             if (burn_in >= N) algorithm.anneal(blockmodel, &constant_schedule, t1, burn_in, never);
             blockmodel.marginals_reset();
+            if (count("align")) blockmodel.marginals_set_alignment(true);
             for (size_t sample = 0; sample < n_samples; ++sample) {
                 algorithm.anneal(blockmodel, &constant_schedule, t1, sweeps_between * N, never);
                 blockmodel.marginals_accumulate();
@@ -645,6 +652,8 @@ int main(int argc, char const* argv[]) {
                           << " steps per sample)\n";
                 return 1;
             }
+            if (count("align"))
+                std::clog << "align: labels matched to chain " << blockmodel.marginals_reference_chain() << " (lowest description length)\n";
             emit_labels(blockmodel.marginal_map_labels(NA));
         } catch (const std::exception& e) {
             std::cerr << e.what() << "\n";

@@ -17,7 +17,7 @@ import numpy as np
 
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
-                return_counts=None):
+                return_counts=None, align=False):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -30,7 +30,12 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     add to what it holds); by default one is allocated when pooling over ranks, and the library's internal buffer is
     used for a single rank.  The library's kernels run on the handle's own (non-blocking) stream, so whatever torch
     still has in flight on the tensor (its zero fill, a caller's writes) is waited for here before the first sample
-    is added -- the stream contract include/bisbm.h states for `device_counts`."""
+    is added -- the stream contract include/bisbm.h states for `device_counts`.
+    `align`: count every chain's labels through its permutation onto a reference partition (include/bisbm.h, "Label
+    alignment before pooling"); pooling more than one chain gives a marginal only then.  The mode is turned on for the run and
+    stays on.  The reference: one the caller set (model.marginals_set_reference), or else the lowest-description-length chain
+    at the first sample -- over all ranks when the chains are spread (all-gathered description lengths, ties -> the lowest
+    global chain id; the owning rank broadcasts its labels and every rank sets them before the first sample)."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
@@ -40,6 +45,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     if device_counts is None and not multi:
         # one rank, no caller buffer: the library's own histogram
         model.marginals_reset()
+        if align:
+            model.marginals_set_alignment(True)
         for _ in range(int(n_samples)):
             if sampling_frequency_sweeps > 0:
                 model.run_sweeps(sampling_frequency_sweeps)
@@ -59,6 +66,12 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         # read-modify-writes on the library's stream: order the two before the first sample.  (The other direction needs
         # nothing: bisbm_marginals_accumulate returns after its kernel has finished.)
         torch.cuda.current_stream(device_counts.device).synchronize()
+    if align:
+        model.marginals_set_alignment(True)
+        if multi:
+            model.marginals_set_reference(shard.lowest_chain_labels(model)[1])
+        else:
+            _drop_library_reference(model)
     for _ in range(int(n_samples)):
         if sampling_frequency_sweeps > 0:
             model.run_sweeps(sampling_frequency_sweeps)
@@ -73,6 +86,17 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     labels = shard.map_labels(send, model.na, model.KA).cpu().numpy().astype(np.uint32)
     counts = shard.pooled_marginals(send).cpu().numpy().astype(np.int64) if return_counts else None
     return labels, counts
+
+
+def _drop_library_reference(model):
+    """A reference the library took at an earlier run (no reset since) is taken afresh; a caller's stays."""
+    from . import BisbmError
+    try:
+        chain = model.marginals_reference()[1]
+    except BisbmError:
+        return
+    if chain >= 0:
+        model.marginals_set_reference(None)
 
 
 def _uses_cuda_backend(shard):

@@ -158,10 +158,49 @@ int bisbm_get_last_counts(bisbm_handle h, uint64_t *accepted, uint64_t *sweeps);
  * Stream contract: the histogram kernel runs on the handle's own non-blocking stream and adds with
  * plain read-modify-writes, so everything the caller has in flight on device_counts (its zero fill,
  * its own kernels) must have COMPLETED before the call (synchronise the stream that wrote it); the
- * call returns after its kernel has finished, so the caller may read the buffer right away. */
+ * call returns after its kernel has finished, so the caller may read the buffer right away.
+ * With the alignment on (bisbm_marginals_set_alignment) every chain's labels are counted through that chain's permutation onto
+ * the reference partition, into the internal buffer and into a caller's device_counts alike; without it (the default) the raw
+ * labels are counted.  A block label means something only inside one chain, so a histogram of more than one chain is a
+ * marginal only when aligned.  bisbm_marginals_reset empties the histogram and drops a library-chosen reference (the
+ * alignment mode and a caller's reference stay). */
 int bisbm_marginals_accumulate(bisbm_handle h, uint32_t *device_counts);
 int bisbm_marginals_reset(bisbm_handle h);
 int bisbm_marginals_get(bisbm_handle h, uint32_t *counts_out /* n*kmax, host */);
+
+/* Label alignment before pooling (no reference counterpart: one chain needs none).  Chains start from independent shuffles and
+ * each settles on its own numbering of the blocks, so before a sample is added every chain's blocks are matched to a REFERENCE
+ * partition, per node type: C[r][s] = nodes of the type with the chain's label r and reference label s (the overlap table);
+ * the permutation pi maximises sum_r C[r][pi(r)], found exactly by a shortest-augmenting-path assignment in int64 with cost
+ * max(C) - C[r][s], rows inserted in order 0..K-1, and in every Dijkstra step the unvisited column of least reduced
+ * distance, ties -> the lowest column (bisbm_align_assignment is the same solver on the host: both give the same permutation
+ * for the same table).  A fresh permutation is computed at every aligned sample; the chains' own state (labels, block state,
+ * random streams, sum dS) is never touched.
+ * The reference: the caller's (bisbm_marginals_set_reference), or else -- taken at the first aligned sample after a reset --
+ * the labels of the chain of the lowest description length (bisbm_entropy; ties -> the lowest global chain id), over every
+ * device of the handle.
+ * Refused: byte labels only (a wide handle, more than 256 blocks: BISBM_ERR_UNSUPPORTED at the accumulate); chains of different
+ * shapes (BISBM_ERR_STATE, as the histogram itself); a caller's reference made for other block counts than the chains have
+ * now, after a merge or split (BISBM_ERR_STATE at the next accumulate; a library-chosen one is taken afresh). */
+#define BISBM_ALIGN_NONE 0      /* raw labels are pooled (the default) */
+#define BISBM_ALIGN_REFERENCE 1 /* labels are counted through each chain's permutation onto the reference */
+
+/* Sets the mode; it holds across resets.  BISBM_ERR_STATE when it would change while the internal histogram holds samples. */
+int bisbm_marginals_set_alignment(bisbm_handle h, int mode);
+/* A reference partition of the caller: n labels of the present block counts (type-b offset by ka); a label outside its node's
+ * type range is BISBM_ERR_INVALID_ARG.  It stays until it is replaced or cleared.  NULL clears any reference: the next aligned
+ * sample takes the lowest-description-length chain's labels. */
+int bisbm_marginals_set_reference(bisbm_handle h, const uint32_t *labels);
+/* The reference (n labels) and the chain it came from (-1: set by the caller); either pointer may be NULL.  BISBM_ERR_STATE
+ * while there is none. */
+int bisbm_marginals_get_reference(bisbm_handle h, uint32_t *labels_out, int64_t *chain_out);
+/* One chain's permutation of the last aligned sample, in global-label form (perm_out[r] = the reference block chain label r is
+ * counted as, ka + kb entries) and its overlap sum_r C[r][pi(r)] over both types; either pointer may be NULL.
+ * BISBM_ERR_STATE before the chain's first aligned sample or when its block counts changed since. */
+int bisbm_marginals_get_alignment(bisbm_handle h, uint32_t chain, uint32_t *perm_out, uint64_t *overlap_out);
+/* The assignment solver of the alignment on the host, without a device: table is k x k (row-major, C[r][s]), perm_out[k]
+ * receives pi(r) in 0..k-1, total_out (may be NULL) sum_r C[r][pi(r)]. */
+int bisbm_align_assignment(uint32_t k, const uint32_t *table, uint32_t *perm_out, uint64_t *total_out);
 
 /* The marginal estimate README.md:49-53 asks for: the most frequent block of every node over all samples of all chains (ties ->
  * the lowest block), n labels in the reference's numbering, from the internal histogram.  Over several devices this is the
