@@ -75,6 +75,10 @@ ABI = {
     "bisbm_marginals_get_reference": (C.c_int, [C.c_void_p, _u32p, C.POINTER(C.c_int64)]),
     "bisbm_marginals_get_alignment": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u64p]),
     "bisbm_align_assignment": (C.c_int, [C.c_uint32, _u32p, _u32p, _u64p]),
+    "bisbm_tempering_set": (C.c_int, [C.c_void_p, C.c_uint32, _f32p]),
+    "bisbm_tempering_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, _f64p]),
+    "bisbm_tempering_get": (C.c_int, [C.c_void_p, _u32p, _f32p]),
+    "bisbm_tempering_stats": (C.c_int, [C.c_void_p, _u64p, _u64p, _u64p]),
     "bisbm_get_ka_kb": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bisbm_get_ka_kb_chain": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "bisbm_agg_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -308,6 +312,7 @@ class BlockModel:
         self.KA, self.KB = int(KA), int(KB)
         self.K = self.KA + self.KB
         self.alignment = ALIGN_NONE  # marginals_set_alignment
+        self.tempering_L = 0  # rungs of the replica-exchange ladder (set_tempering); 0: off
         self.mixed_shapes = False  # True once a one-argument agg_merge left the chains with different block counts
         self.epsilon = float(epsilon)
         self.n_chains = int(n_chains)
@@ -492,6 +497,43 @@ class BlockModel:
         """`sweeps` sweeps at constant temperature (the "marginalize" regime: -c constant -a 1)."""
         return MetropolisHasting().anneal(self, constant_schedule, [temperature], int(sweeps) * self.n, 1 << 60)
 
+    # -- replica exchange (include/bisbm.h, "Replica exchange")
+    def set_tempering(self, ladder):
+        """Replica exchange over ensembles of L = len(ladder) consecutive chains (chain g L + i starts on rung i); ``None`` or
+        an empty ladder turns it off.  The ladder is checked here first (validate_ladder), the chain count too."""
+        if ladder is None or len(ladder) == 0:
+            self._check(self._L.bisbm_tempering_set(self._h, 0, None))
+            self.tempering_L = 0
+            return
+        lad = validate_ladder(ladder)
+        if self.n_chains % len(lad):
+            raise ValueError("%d chains are not a multiple of the ladder's %d rungs" % (self.n_chains, len(lad)))
+        self._check(self._L.bisbm_tempering_set(self._h, len(lad), _p(lad, _f32p)))
+        self.tempering_L = len(lad)
+
+    def tempering_run(self, sweeps, exchange_every=1):
+        """`sweeps` sweeps of every chain at its rung's temperature, an exchange round after every complete block of
+        `exchange_every` sweeps (0: none).  Returns the acceptance rate per chain (a float for one chain)."""
+        rates = np.zeros(self.n_chains, dtype=np.float64)
+        self._check(self._L.bisbm_tempering_run(self._h, int(sweeps), int(exchange_every), _p(rates, _f64p)))
+        return float(rates[0]) if self.n_chains == 1 else rates
+
+    def tempering_state(self):
+        """(rung uint32 [n_chains], temperature float32 [n_chains]) of every chain."""
+        rung = np.zeros(self.n_chains, dtype=np.uint32)
+        T = np.zeros(self.n_chains, dtype=np.float32)
+        self._check(self._L.bisbm_tempering_get(self._h, _p(rung, _u32p), _p(T, _f32p)))
+        return rung, T
+
+    def tempering_stats(self):
+        """(attempted uint64 [L - 1], accepted uint64 [L - 1], rounds): exchanges per rung pair (i, i + 1) since set_tempering."""
+        P = max(self.tempering_L - 1, 1)
+        att = np.zeros(P, dtype=np.uint64)
+        acc = np.zeros(P, dtype=np.uint64)
+        rounds = C.c_uint64()
+        self._check(self._L.bisbm_tempering_stats(self._h, _p(att, _u64p), _p(acc, _u64p), C.byref(rounds)))
+        return att, acc, rounds.value
+
     def counts_device(self):
         """torch device a caller-owned marginal histogram must live on."""
         import torch
@@ -580,6 +622,25 @@ def align_assignment(table):
     if rc != BISBM_OK:
         raise BisbmError(rc, (lib().bisbm_last_error(None) or b"").decode())
     return perm, tot.value
+
+
+def validate_ladder(ladder):
+    """A replica-exchange ladder as float32 (what the library runs), or ValueError: at least 2 temperatures, each finite and
+    > 0 as a float32, non-decreasing."""
+    try:
+        vals = [float(x) for x in ladder]
+    except (TypeError, ValueError):
+        raise ValueError("the temperature ladder must be a sequence of numbers")
+    if len(vals) < 2:
+        raise ValueError("a temperature ladder needs at least 2 rungs, got %d" % len(vals))
+    with np.errstate(over="ignore"):
+        lad = np.asarray(vals, dtype=np.float32)
+    for i, t in enumerate(lad):
+        if not (np.isfinite(t) and t > 0):
+            raise ValueError("ladder[%d] = %s: every temperature must be finite and > 0" % (i, vals[i]))
+        if i and t < lad[i - 1]:
+            raise ValueError("ladder[%d] = %s < ladder[%d] = %s: the ladder must be non-decreasing" % (i, vals[i], i - 1, vals[i - 1]))
+    return lad
 
 
 def _fmt_g6(x):

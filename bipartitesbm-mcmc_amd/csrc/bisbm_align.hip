@@ -199,7 +199,8 @@ __global__ __launch_bounds__(256) void marginals_aligned_kernel(MarginalParams p
         for (uint32_t i = threadIdx.x; i < nc * K; i += 256) pm[i] = perm[(size_t)c0 * K + i];
         __syncthreads();
         if (live)
-            for (uint32_t c = 0; c < nc; ++c) row[(uint32_t)pm[c * K + p.labels[(size_t)(c0 + c) * p.label_stride + v]] - base] += 1;
+            for (uint32_t c = 0; c < nc; ++c)
+                if (!p.rung || p.rung[c0 + c] == 0u) row[(uint32_t)pm[c * K + p.labels[(size_t)(c0 + c) * p.label_stride + v]] - base] += 1;
     }
     if (IN_LDS && live) {
         uint32_t* out = p.counts + (size_t)v * p.kmax;
@@ -338,6 +339,7 @@ int align_leaf(bisbm_engine* e, const AlignState& top, uint32_t* counts) {
     mp.labels = e->d_labels;
     mp.label_stride = e->label_stride;
     mp.counts = counts;
+    mp.rung = e->temper.L ? e->temper.d_rung : nullptr;  // replica exchange: the cold chains only
     HIPCHK(e, launch_marginals_aligned(mp, a.d_perm, K, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     a.have_perm = true, a.perm_ka = ka, a.perm_kb = kb;
@@ -345,15 +347,19 @@ int align_leaf(bisbm_engine* e, const AlignState& top, uint32_t* counts) {
 }
 
 // the library's reference: the labels of the lowest-description-length chain (ties -> the lowest global chain id, which is
-// the lowest chain index of the handle)
+// the lowest chain index of the handle); with replica exchange on, among the chains on rung 0
 int pick_reference(bisbm_engine* h, uint32_t ka, uint32_t kb) {
     uint32_t n_chains = 0;
     if (int rc = bisbm_get_sizes(h, nullptr, nullptr, nullptr, &n_chains)) return rc;
     std::vector<double> S(n_chains);
     if (int rc = bisbm_entropy(h, S.data())) return rc;
-    uint32_t best = 0;
-    for (uint32_t c = 1; c < n_chains; ++c)
-        if (S[c] < S[best]) best = c;
+    std::vector<uint32_t> rung(n_chains, 0);
+    if (h->temper.L)
+        if (int rc = bisbm_tempering_get(h, rung.data(), nullptr)) return rc;
+    int64_t pick = -1;
+    for (uint32_t c = 0; c < n_chains; ++c)
+        if (rung[c] == 0u && (pick < 0 || S[c] < S[pick])) pick = c;
+    const uint32_t best = (uint32_t)pick;  // (rung 0 holds n_chains / L >= 1 chains)
     std::vector<uint32_t> lab((size_t)h->n);
     if (int rc = bisbm_get_memberships(h, best, lab.data())) return rc;
     AlignState& a = h->align;

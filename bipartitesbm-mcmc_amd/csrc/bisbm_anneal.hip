@@ -13,6 +13,15 @@ extern "C" {
 int bisbm_anneal(bisbm_handle h, int schedule, const float kwargs[2], uint64_t duration_steps,
                  uint64_t steps_await, double* acc_rate_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
+    if (h->temper.L)
+        return fail(h, BISBM_ERR_STATE, "replica exchange is on: sweeps run through bisbm_tempering_run (bisbm_tempering_set(h, 0, NULL) turns it off)");
+    return anneal_engine(h, schedule, kwargs, duration_steps, steps_await, acc_rate_out, nullptr);
+}
+
+}  // extern "C"
+
+int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t duration_steps, uint64_t steps_await,
+                         double* acc_rate_out, const float* T_chain) {
     if (!kwargs) return fail(h, BISBM_ERR_INVALID_ARG, "kwargs is NULL");
     if (schedule < BISBM_SCHED_EXPONENTIAL || schedule > BISBM_SCHED_ABRUPT_COOL)
         return fail(h, BISBM_ERR_INVALID_ARG, "unknown schedule %d", schedule);
@@ -77,12 +86,13 @@ int bisbm_anneal(bisbm_handle h, int schedule, const float kwargs[2], uint64_t d
     p.q_tab = h->d_q;
     p.q_stride = h->q_stride;
     p.log_tab = h->d_logtab;
-    p.schedule = schedule;
+    p.schedule = T_chain ? SCHED_PER_CHAIN : schedule;  // (T_chain: a constant schedule per chain; the host's choices below see `schedule`)
     p.kw0 = kwargs[0];
     p.kw1 = kwargs[1];
     p.duration = duration_steps;
     p.steps_await = steps_await;
     p.seed = h->seed;
+    p.T_chain = T_chain;
 
     p.t_base = 0;
     p.call_duration = duration_steps;
@@ -367,5 +377,3 @@ int bisbm_anneal(bisbm_handle h, int schedule, const float kwargs[2], uint64_t d
     }
     return BISBM_OK;
 }
-
-}  // extern "C"

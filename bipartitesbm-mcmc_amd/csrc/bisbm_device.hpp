@@ -16,7 +16,11 @@ constexpr int kWave = 64;
 constexpr int kQNmax = 10000;  // blockmodel.cc:48 init_q_cache(10000)
 
 enum : int { RNG_PHILOX = 0, RNG_COMPAT = 1 };
-enum : int { SCHED_EXPONENTIAL = 0, SCHED_LINEAR = 1, SCHED_LOGARITHMIC = 2, SCHED_CONSTANT = 3, SCHED_ABRUPT = 4 };
+// SCHED_PER_CHAIN (internal, not in the C ABI): every chain at its own constant temperature, SweepParams::T_chain -- replica
+// exchange.  The production kernel runs it in its cooling-schedule variants, which take a temperature per step anyway; reading a
+// per-chain value in the constant-schedule variants cost the default path 1.6 % (loaded once) or 2.1 % (kept in LDS) per sweep
+// (profiles/tempering_ab_constant_path.txt)
+enum : int { SCHED_EXPONENTIAL = 0, SCHED_LINEAR = 1, SCHED_LOGARITHMIC = 2, SCHED_CONSTANT = 3, SCHED_ABRUPT = 4, SCHED_PER_CHAIN = 5 };
 enum : uint32_t { PHX_STEP_A = 0, PHX_STEP_B = 1, PHX_SWEEP_KEY = 2, PHX_INIT_SHUFFLE = 3 };
 
 // ------------------------------------------------------------------------------------------

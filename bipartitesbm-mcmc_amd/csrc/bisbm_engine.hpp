@@ -9,6 +9,7 @@
 //   bisbm_multi.hip      several devices behind one handle: creation, dispatch, pooling (RCCL / peer copies)
 //   bisbm_merge.hip      agg_merge / agg_split between anneals, chains of one handle in different shapes
 //   bisbm_align.hip      label alignment of the chains to a reference partition before their samples are pooled
+//   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -77,6 +78,21 @@ struct AlignState {
     size_t tab_cap = 0, perm_cap = 0, tot_cap = 0;
     bool have_perm = false;
     uint32_t perm_ka = 0, perm_kb = 0;
+};
+
+// Replica exchange (bisbm_tempering.hip).  The ladder and the round counter belong to the handle the caller holds and are
+// copied to every device entry; the buffers belong to the engines that run the kernels (a plain handle, a device entry).
+struct TemperState {
+    uint32_t L = 0;               // rungs per ensemble; 0: tempering off
+    std::vector<float> ladder;    // L temperatures, non-decreasing
+    uint64_t round = 0;           // exchange rounds since bisbm_tempering_set
+    // kernel-running engine
+    float* d_T = nullptr;               // [chain] temperature of the chain's rung (SweepParams::T_chain)
+    uint32_t* d_rung = nullptr;         // [chain] rung of the chain (MarginalParams::rung)
+    uint32_t* d_at = nullptr;           // [ensemble][L] the chain (index in the engine) on every rung
+    float* d_ladder = nullptr;          // L temperatures
+    unsigned long long* d_stats = nullptr;  // [2][L - 1] attempted, accepted exchanges per rung pair
+    size_t cap_chains = 0, cap_L = 0;
 };
 
 }  // namespace bisbm
@@ -167,6 +183,7 @@ struct bisbm_engine {
     struct DevicePool* pool = nullptr;
     uint64_t counts_rows = 0;  // rows of the internal marginal buffer (n, or n rounded up to a multiple of the device count)
     bisbm::AlignState align;
+    bisbm::TemperState temper;
 };
 
 namespace bisbm {
@@ -302,6 +319,13 @@ int multi_marginals_map(bisbm_engine* h, uint32_t* labels_out);
 void multi_free(bisbm_engine* h);
 // MAP labels from the internal histogram of one engine (no pooling); bisbm_marginals.hip
 int single_marginals_map(bisbm_engine* h, uint32_t* labels_out);
+// bisbm_entropy's full description length is t[0] + (block-state part) + t[1] + ... + t[7], added in that order (bisbm_handle.hip)
+void entropy_terms(const bisbm_engine* h, double t[8]);
+// bisbm_anneal on a kernel-running engine with a temperature per chain (T_chain: device pointer, NULL: none); bisbm_anneal.hip
+int anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t duration_steps, uint64_t steps_await,
+                  double* acc_rate_out, const float* T_chain);
+// the buffers of replica exchange (bisbm_destroy); bisbm_tempering.hip
+void temper_free(bisbm_engine* h);
 // bisbm_marginals_accumulate with the alignment on; the buffers of alignment (bisbm_destroy); bisbm_align.hip
 int align_accumulate(bisbm_engine* h, uint32_t* device_counts);
 void align_free(bisbm_engine* h);

@@ -46,6 +46,7 @@ void free_all(bisbm_engine* h) {
     h->groups.clear();
     free_chain_arrays(h);
     align_free(h);
+    temper_free(h);
     if (h->root) {  // a sub-engine: the graph and the tables belong to the handle it serves
         h->d_rowptr = nullptr, h->d_col = nullptr, h->d_lgamma = nullptr, h->d_logtab = nullptr, h->d_q = nullptr;
     }
@@ -100,6 +101,18 @@ size_t generic_lds_base_bytes(uint32_t ka, uint32_t kb, bool wide, int rng_mode)
     size_t lds = sizeof(int32_t) * ((wide ? 0 : (size_t)ka * S) + 2 * K + std::max<uint32_t>(std::max(ka, kb), 64)) + sizeof(uint32_t) * 64 * 64;
     if (rng_mode == BISBM_RNG_MT19937_COMPAT) lds += sizeof(uint32_t) * 624 * 4;
     return lds;
+}
+
+void entropy_terms(const bisbm_engine* h, double t[8]) {  // blockmodel.cc:753-787, statement order kept
+    const HostTables& tab = *h->tab;
+    t[0] = h->ent_deg;
+    t[1] = h->ent_multi;
+    t[2] = h_lbinom_fast(tab, (uint64_t)h->ka * h->kb + h->num_edges - 1, h->num_edges);
+    t[3] = h_lbinom_fast(tab, h->na - 1, h->ka - 1);
+    t[4] = h_lbinom_fast(tab, h->nb - 1, h->kb - 1);
+    t[5] = (h->na * h->nb == 0) ? 0. : std::log((double)(h->na * h->nb));  // safelog, without the na*nb table (F5)
+    t[6] = h_lgamma_fast(tab, h->na + 1);
+    t[7] = h_lgamma_fast(tab, h->nb + 1);
 }
 
 int launch_block_entropy(bisbm_engine* h, double* d_out) {
@@ -505,17 +518,12 @@ int bisbm_entropy(bisbm_handle h, double* out) {
     std::vector<double> part(h->n_chains);
     HIPCHK(h, hipMemcpyAsync(part.data(), h->d_tmp_f64, sizeof(double) * h->n_chains, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const HostTables& t = *h->tab;
-    for (uint32_t c = 0; c < h->n_chains; ++c) {  // blockmodel.cc:753-787, statement order kept
-        double ent = h->ent_deg;
+    double t[8];
+    entropy_terms(h, t);
+    for (uint32_t c = 0; c < h->n_chains; ++c) {
+        double ent = t[0];
         ent += part[c];
-        ent += h->ent_multi;
-        ent += h_lbinom_fast(t, (uint64_t)h->ka * h->kb + h->num_edges - 1, h->num_edges);
-        ent += h_lbinom_fast(t, h->na - 1, h->ka - 1);
-        ent += h_lbinom_fast(t, h->nb - 1, h->kb - 1);
-        ent += (h->na * h->nb == 0) ? 0. : std::log((double)(h->na * h->nb));  // safelog, without the na*nb table (F5)
-        ent += h_lgamma_fast(t, h->na + 1);
-        ent += h_lgamma_fast(t, h->nb + 1);
+        for (int i = 1; i < 8; ++i) ent += t[i];
         out[c] = ent;
     }
     return BISBM_OK;

@@ -893,7 +893,8 @@ __global__ __launch_bounds__(256) void marginals_kernel(MarginalParams p) {
         for (uint32_t j = 0; j < p.kmax; ++j) row[j] = 0;
         if (v < p.n) {
             const uint32_t base = v < p.na ? 0 : p.ka;
-            for (uint32_t c = 0; c < p.n_chains; ++c) row[(uint32_t)labels[(size_t)c * p.label_stride + v] - base] += 1;
+            for (uint32_t c = 0; c < p.n_chains; ++c)
+                if (!p.rung || p.rung[c] == 0u) row[(uint32_t)labels[(size_t)c * p.label_stride + v] - base] += 1;
             uint32_t* out = p.counts + (size_t)v * p.kmax;
             for (uint32_t j = 0; j < p.kmax; ++j)
                 if (row[j]) out[j] += row[j];
@@ -903,7 +904,8 @@ __global__ __launch_bounds__(256) void marginals_kernel(MarginalParams p) {
         // it can count straight into it
         const uint32_t base = v < p.na ? 0 : p.ka;
         uint32_t* out = p.counts + (size_t)v * p.kmax;
-        for (uint32_t c = 0; c < p.n_chains; ++c) out[(uint32_t)labels[(size_t)c * p.label_stride + v] - base] += 1;
+        for (uint32_t c = 0; c < p.n_chains; ++c)
+            if (!p.rung || p.rung[c] == 0u) out[(uint32_t)labels[(size_t)c * p.label_stride + v] - base] += 1;
     }
 }
 

@@ -97,6 +97,9 @@ struct SweepParams {
     // that cannot stop early -- BISBM_KEEP_SUM=1: the tests that check the sum of the kernel's own dS values against the change
     // of the description length, tools/soak.py
     uint32_t keep_sum;
+    // replica exchange (bisbm_tempering.hip), schedule SCHED_PER_CHAIN: the constant temperature of every chain of the launch (a
+    // float, like kw0: a chain at T runs exactly as a constant-schedule launch at kwargs {T, .}); NULL otherwise
+    const float* T_chain;
 };
 constexpr uint32_t kSimdClaims = 1u << 14;  // index: XCC_ID[3:0] | HW_ID se, sh, cu [15:8] | simd [5:4]
 
@@ -145,6 +148,7 @@ struct MarginalParams {
     size_t label_stride;
     uint32_t* counts;
     uint32_t wide;  // two-byte labels (see SweepParams::wide)
+    const uint32_t* rung;  // replica exchange: only chains with rung[c] == 0 are counted; NULL: every chain
 };
 
 // agg_split (blockmodel.cc:505-565): evaluation of `n_trials` random half-cuts of every block of one type, all chains
@@ -174,6 +178,7 @@ struct SplitParams {
     const uint32_t* block_off;
 };
 constexpr uint32_t PHX_SPLIT = 6;
+constexpr uint32_t PHX_EXCHANGE = 7;  // replica exchange: idx = round * L + lower rung, chain = the ensemble's first global id
 
 hipError_t launch_split_rank(const SplitParams& p, hipStream_t stream);
 hipError_t launch_split_eval(const SplitParams& p, hipStream_t stream);
@@ -192,6 +197,8 @@ __device__ __forceinline__ double temperature_of(const SweepParams& p, uint64_t 
     switch (p.schedule) {
         case SCHED_CONSTANT:
             return (double)p.kw0;
+        case SCHED_PER_CHAIN:  // (replica exchange; the sweep kernels run chain blockIdx.x)
+            return (double)p.T_chain[blockIdx.x];
         case SCHED_ABRUPT:
             return ((float)t < p.kw0) ? 1. : 0.;
         case SCHED_LINEAR:
@@ -220,6 +227,8 @@ __device__ __forceinline__ double temperature_tabled(const SweepParams& p, uint6
             return ((float)t < p.kw0) ? 1. : 0.;
         case SCHED_LINEAR:
             return (double)(p.kw0 - p.kw1 * (float)t);
+        case SCHED_PER_CHAIN:  // (replica exchange; the production kernel runs chain blockIdx.x)
+            return (double)p.T_chain[blockIdx.x];
         default: {  // SCHED_EXPONENTIAL, SCHED_LOGARITHMIC
             const uint64_t i = t - p.T_base;
             return i < p.T_len ? p.T_tab[i] : 0.;  // (past the table: the exponential schedule after it has underflowed to 0)

@@ -85,6 +85,7 @@ int accumulate_plain(bisbm_engine* h, uint32_t* device_counts) {
     mp.label_stride = h->label_stride;
     mp.wide = h->wide ? 1u : 0u;
     mp.counts = device_counts;
+    mp.rung = h->temper.L ? h->temper.d_rung : nullptr;  // replica exchange: the cold chains only
     HIPCHK(h, launch_marginals(mp, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
@@ -96,6 +97,12 @@ extern "C" {
 
 int bisbm_marginals_accumulate(bisbm_handle h, uint32_t* device_counts) {
     if (!h) return BISBM_ERR_INVALID_ARG;
+    if (h->temper.L) {  // (a group engine knows no rungs: refused wherever the chains are grouped, on any device entry, raw or aligned)
+        bool grouped = !h->groups.empty();
+        for (bisbm_engine* d : h->devs) grouped = grouped || !d->groups.empty();
+        if (grouped)
+            return fail(h, BISBM_ERR_STATE, "replica exchange is on and the chains of this handle are grouped by shape (after bisbm_agg_merge_total): no cold-chain histogram");
+    }
     const int rc = h->align.mode == BISBM_ALIGN_REFERENCE ? align_accumulate(h, device_counts) : accumulate_plain(h, device_counts);
     if (rc == BISBM_OK && !device_counts) h->align.samples = true;
     return rc;

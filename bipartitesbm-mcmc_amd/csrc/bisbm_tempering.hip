@@ -1,0 +1,284 @@
+// bisbm_tempering.hip -- replica exchange (parallel tempering) across the chains of a handle (no reference counterpart: the
+// reference runs one chain).  The chains form ensembles of L consecutive global ids; every chain of an ensemble runs the
+// constant-temperature chain at its rung's temperature (the sweep kernels read it per chain, SweepParams::T_chain), and every
+// `exchange_every` sweeps neighbouring rungs of every ensemble propose to swap temperatures -- one lane per (ensemble, pair) of
+// the exchange kernel below, on the device, with no host round trip per round.  include/bisbm.h states the definition.
+#include "bisbm_engine.hpp"
+
+using namespace bisbm;
+
+namespace {
+
+// What one exchange round of one engine reads and writes.  The description length of chain c is rebuilt from the block-state
+// part the entropy kernel left in part[c] and the terms of entropy_terms, added in bisbm_entropy's order: the same double.
+struct ExchangeParams {
+    const double* part;  // [chain] block-state part of the description length
+    double terms[8];     // entropy_terms
+    uint32_t n_ens, L, pairs;
+    uint32_t first_gid;  // global id of the engine's first chain (a multiple of L)
+    uint64_t seed, round;
+    const float* ladder;
+    float* T;                    // [chain] temperature of the chain's rung
+    uint32_t* rung;              // [chain] rung of the chain
+    uint32_t* at;                // [ensemble][L] chain on every rung
+    unsigned long long* stats;   // [2][L - 1] attempted, accepted
+};
+
+__device__ __forceinline__ double description_length(const ExchangeParams& p, uint32_t c) {
+    double s = p.terms[0];
+    s += p.part[c];
+    for (int i = 1; i < 8; ++i) s += p.terms[i];
+    return s;
+}
+
+// One lane per (ensemble, lower rung i of this round's parity).  The pairs of a round are disjoint, so every lane owns the
+// entries it swaps.
+__global__ __launch_bounds__(256) void tempering_exchange_kernel(ExchangeParams p) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= p.n_ens * p.pairs) return;
+    const uint32_t g = t / p.pairs;
+    const uint32_t i = (uint32_t)(p.round & 1u) + 2u * (t % p.pairs);  // i + 1 < L by the choice of `pairs`
+    uint32_t* at = p.at + (size_t)g * p.L;
+    const uint32_t a = at[i], b = at[i + 1];
+    const double delta = (1.0 / (double)p.ladder[i] - 1.0 / (double)p.ladder[i + 1]) * (description_length(p, a) - description_length(p, b));
+    const U4 U = phx_draw(p.seed, p.first_gid + g * p.L, PHX_EXCHANGE, p.round * p.L + i);
+    const bool accept = delta >= 0. || u53(U.x, U.y) < exp(delta);
+    atomicAdd(&p.stats[i], 1ull);
+    if (accept) {
+        atomicAdd(&p.stats[p.L - 1 + i], 1ull);
+        at[i] = b, at[i + 1] = a;
+        p.rung[a] = i + 1, p.rung[b] = i;
+        p.T[a] = p.ladder[i + 1], p.T[b] = p.ladder[i];
+    }
+}
+
+constexpr uint64_t kNoStop = 1ull << 60;  // steps_await of every segment: no early stop (as BlockModel.run_sweeps)
+
+// the engines that run kernels under a handle: a plain handle, or its device entries
+std::vector<bisbm_engine*> leaves(bisbm_engine* h) { return h->devs.empty() ? std::vector<bisbm_engine*>{h} : h->devs; }
+
+int mixed_shapes(bisbm_engine* h) {
+    for (bisbm_engine* e : leaves(h))
+        if (!e->groups.empty())
+            return fail(h, BISBM_ERR_STATE, "the chains of this handle are grouped by shape (a one-argument bisbm_agg_merge_total left different block counts): replica exchange needs one common shape");
+    return BISBM_OK;
+}
+
+template <class T>
+int grow(bisbm_engine* e, T** p, size_t count) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    HIPCHK(e, dalloc(p, count));
+    return BISBM_OK;
+}
+
+// rungs, temperatures, statistics of a kernel-running engine: chain c on rung c mod L
+int setup_leaf(bisbm_engine* e, uint32_t L, const float* ladder) {
+    TemperState& t = e->temper;
+    HIPCHK(e, hipSetDevice(e->device));
+    const uint32_t C = e->n_chains;
+    if (t.cap_chains < C || !t.d_T) {
+        if (int rc = grow(e, &t.d_T, C)) return rc;
+        if (int rc = grow(e, &t.d_rung, C)) return rc;
+        if (int rc = grow(e, &t.d_at, C)) return rc;
+        t.cap_chains = C;
+    }
+    if (t.cap_L < L || !t.d_ladder) {
+        if (int rc = grow(e, &t.d_ladder, L)) return rc;
+        if (int rc = grow(e, &t.d_stats, 2 * (size_t)L)) return rc;
+        t.cap_L = L;
+    }
+    std::vector<float> T(C);
+    std::vector<uint32_t> rung(C), at(C);
+    for (uint32_t c = 0; c < C; ++c) T[c] = ladder[c % L], rung[c] = c % L, at[c] = c;
+    HIPCHK(e, hipMemcpyAsync(t.d_T, T.data(), sizeof(float) * C, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(t.d_rung, rung.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(t.d_at, at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(t.d_ladder, ladder, sizeof(float) * L, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemsetAsync(t.d_stats, 0, sizeof(unsigned long long) * 2 * L, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    t.L = L;
+    t.ladder.assign(ladder, ladder + L);
+    t.round = 0;
+    return BISBM_OK;
+}
+
+// one exchange round of a kernel-running engine, on its stream
+int exchange_round(bisbm_engine* e) {
+    TemperState& t = e->temper;
+    // the block-state part of every chain's description length: the sweep call just before left it in d_ent_prev when it
+    // advanced the running sum of dS that way (bisbm_anneal); otherwise the entropy kernel runs
+    const double* part = e->d_ent_prev;
+    if (!e->ent_prev_valid) {
+        if (int rc = launch_block_entropy(e, e->d_tmp_f64)) return rc;
+        part = e->d_tmp_f64;
+    }
+    ExchangeParams p{};
+    p.part = part;
+    entropy_terms(e, p.terms);
+    p.L = t.L;
+    p.n_ens = e->n_chains / t.L;
+    p.pairs = (t.L - (uint32_t)(t.round & 1u)) / 2u;
+    p.first_gid = e->first_chain_id;
+    p.seed = e->seed;
+    p.round = t.round;
+    p.ladder = t.d_ladder;
+    p.T = t.d_T;
+    p.rung = t.d_rung;
+    p.at = t.d_at;
+    p.stats = t.d_stats;
+    const uint32_t lanes = p.n_ens * p.pairs;
+    if (lanes) {
+        hipLaunchKernelGGL(tempering_exchange_kernel, dim3((lanes + 255) / 256), dim3(256), 0, e->stream, p);
+        HIPCHK(e, hipGetLastError());
+    }
+    ++t.round;
+    return BISBM_OK;
+}
+
+int run_leaf(bisbm_engine* e, uint64_t sweeps, uint32_t every, double* acc_rate_out) {
+    TemperState& t = e->temper;
+    HIPCHK(e, hipSetDevice(e->device));
+    const float kw[2] = {t.ladder[0], 0.f};  // (the host's view of the call; every chain's own T comes from T_chain)
+    const uint64_t blocks = every ? sweeps / every : 0, rest = sweeps - blocks * every;
+    std::vector<double> rate(e->n_chains), acc(e->n_chains, 0.);
+    double ms = 0;
+    uint64_t updates = 0;
+    auto segment = [&](uint64_t k) -> int {
+        if (int rc = anneal_engine(e, BISBM_SCHED_CONSTANT, kw, k * e->n, kNoStop, rate.data(), t.d_T)) return rc;
+        for (uint32_t c = 0; c < e->n_chains; ++c) acc[c] += rate[c] * (double)k;  // (rate: accepted / steps of the segment)
+        ms += e->last_kernel_ms;
+        updates += e->last_updates;
+        return BISBM_OK;
+    };
+    for (uint64_t b = 0; b < blocks; ++b) {
+        if (int rc = segment(every)) return rc;
+        if (int rc = exchange_round(e)) return rc;
+    }
+    if (rest)
+        if (int rc = segment(rest)) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->last_kernel_ms = ms;
+    e->last_updates = updates;
+    if (acc_rate_out)
+        for (uint32_t c = 0; c < e->n_chains; ++c) acc_rate_out[c] = sweeps ? acc[c] / (double)sweeps : 0.;
+    return BISBM_OK;
+}
+
+}  // namespace
+
+namespace bisbm {
+
+void temper_free(bisbm_engine* h) {
+    TemperState& t = h->temper;
+    void* ptrs[] = {t.d_T, t.d_rung, t.d_at, t.d_ladder, t.d_stats};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    t.d_T = nullptr, t.d_rung = nullptr, t.d_at = nullptr, t.d_ladder = nullptr, t.d_stats = nullptr;
+    t.cap_chains = t.cap_L = 0;
+    t.L = 0;
+}
+
+}  // namespace bisbm
+
+extern "C" {
+
+int bisbm_tempering_set(bisbm_handle h, uint32_t L, const float* ladder) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (L == 0) {  // off: every call behaves as without tempering again
+        h->temper.L = 0;
+        h->temper.ladder.clear();
+        h->temper.round = 0;
+        for (bisbm_engine* d : h->devs) d->temper.L = 0, d->temper.ladder.clear(), d->temper.round = 0;
+        return BISBM_OK;
+    }
+    if (L < 2) return fail(h, BISBM_ERR_INVALID_ARG, "a temperature ladder needs at least 2 rungs (L = %u)", L);
+    if (!ladder) return fail(h, BISBM_ERR_INVALID_ARG, "ladder is NULL");
+    for (uint32_t i = 0; i < L; ++i) {
+        if (!std::isfinite(ladder[i]) || !(ladder[i] > 0.f))
+            return fail(h, BISBM_ERR_INVALID_ARG, "ladder[%u] = %g: every temperature must be finite and > 0", i, (double)ladder[i]);
+        if (i && ladder[i] < ladder[i - 1])
+            return fail(h, BISBM_ERR_INVALID_ARG, "ladder[%u] = %g < ladder[%u] = %g: the ladder must be non-decreasing", i, (double)ladder[i], i - 1,
+                        (double)ladder[i - 1]);
+    }
+    if (h->rng_mode == BISBM_RNG_MT19937_COMPAT)
+        return fail(h, BISBM_ERR_UNSUPPORTED, "replica exchange runs in Philox mode only (mt19937-compat mode is the reference's verification path)");
+    if (int rc = mixed_shapes(h)) return rc;
+    if (h->first_chain_id % L)
+        return fail(h, BISBM_ERR_INVALID_ARG, "the first global chain id %u is not a multiple of L = %u: ensembles are global ids [g L, (g + 1) L)",
+                    h->first_chain_id, L);
+    for (bisbm_engine* e : leaves(h))
+        if (e->n_chains % L)
+            return fail(h, BISBM_ERR_INVALID_ARG, "%s holds %u chains, not a multiple of L = %u: an ensemble may not straddle device entries",
+                        h->devs.empty() ? "the handle" : ("the entry of device " + std::to_string(e->device)).c_str(), e->n_chains, L);
+    h->temper.L = 0;
+    for (bisbm_engine* e : leaves(h)) {
+        if (int rc = setup_leaf(e, L, ladder)) {
+            if (e != h) h->err = e->err;
+            for (bisbm_engine* d : h->devs) d->temper.L = 0;
+            return rc;
+        }
+    }
+    h->temper.L = L;
+    h->temper.ladder.assign(ladder, ladder + L);
+    h->temper.round = 0;
+    return BISBM_OK;
+}
+
+int bisbm_tempering_run(bisbm_handle h, uint64_t sweeps, uint32_t exchange_every, double* acc_rate_out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->temper.L) return fail(h, BISBM_ERR_STATE, "replica exchange is off: call bisbm_tempering_set first");
+    if (int rc = mixed_shapes(h)) return rc;
+    if (h->devs.empty()) {
+        const int rc = run_leaf(h, sweeps, exchange_every, acc_rate_out);
+        return rc;
+    }
+    const int rc = on_devices(h, [&](bisbm_engine* d, size_t i) {
+        return run_leaf(d, sweeps, exchange_every, acc_rate_out ? acc_rate_out + h->dev_first[i] : nullptr);
+    });
+    h->last_kernel_ms = 0;
+    h->last_updates = 0;
+    for (bisbm_engine* d : h->devs) {  // (as multi_anneal: the devices run side by side)
+        h->last_kernel_ms = std::max(h->last_kernel_ms, d->last_kernel_ms);
+        h->last_updates += d->last_updates;
+        h->last_pass_steps = std::max(d == h->devs[0] ? 0u : h->last_pass_steps, d->last_pass_steps);
+    }
+    h->temper.round = h->devs[0]->temper.round;
+    return rc;
+}
+
+int bisbm_tempering_get(bisbm_handle h, uint32_t* rung_of_chain, float* T_of_chain) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->temper.L) return fail(h, BISBM_ERR_STATE, "replica exchange is off");
+    uint32_t first = 0;
+    for (bisbm_engine* e : leaves(h)) {
+        HIPCHK(h, hipSetDevice(e->device));
+        HIPCHK(h, hipStreamSynchronize(e->stream));
+        if (rung_of_chain)
+            HIPCHK(h, hipMemcpy(rung_of_chain + first, e->temper.d_rung, sizeof(uint32_t) * e->n_chains, hipMemcpyDeviceToHost));
+        if (T_of_chain) HIPCHK(h, hipMemcpy(T_of_chain + first, e->temper.d_T, sizeof(float) * e->n_chains, hipMemcpyDeviceToHost));
+        first += e->n_chains;
+    }
+    return BISBM_OK;
+}
+
+int bisbm_tempering_stats(bisbm_handle h, uint64_t* attempted, uint64_t* accepted, uint64_t* rounds) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->temper.L) return fail(h, BISBM_ERR_STATE, "replica exchange is off");
+    const uint32_t P = h->temper.L - 1;
+    std::vector<uint64_t> sum(2 * (size_t)P, 0), part(2 * (size_t)P);
+    for (bisbm_engine* e : leaves(h)) {
+        HIPCHK(h, hipSetDevice(e->device));
+        HIPCHK(h, hipStreamSynchronize(e->stream));
+        HIPCHK(h, hipMemcpy(part.data(), e->temper.d_stats, sizeof(uint64_t) * 2 * P, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < part.size(); ++i) sum[i] += part[i];
+    }
+    for (uint32_t i = 0; i < P; ++i) {
+        if (attempted) attempted[i] = sum[i];
+        if (accepted) accepted[i] = sum[P + i];
+    }
+    if (rounds) *rounds = h->temper.round;
+    return BISBM_OK;
+}
+
+}  // extern "C"

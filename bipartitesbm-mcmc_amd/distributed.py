@@ -69,11 +69,15 @@ class ChainShard:
     def lowest_chain_labels(self, model):
         """(global chain id, labels uint32 [n]) of the chain of the lowest description length over all ranks (ties -> the
         lowest global chain id): the reference partition of an aligned marginalisation.  The description lengths are
-        all-gathered, the owning rank broadcasts the chain's labels."""
+        all-gathered, the owning rank broadcasts the chain's labels.  With replica exchange on (model.set_tempering) only the
+        chains on rung 0 compete."""
         import torch
         dist = _dist()
         dev = _collective_device(self)
-        local = torch.as_tensor(np.asarray(model.entropy(), dtype=np.float64)).reshape(-1)
+        S = np.asarray(model.entropy(), dtype=np.float64).reshape(-1)
+        if getattr(model, "tempering_L", 0):
+            S = np.where(model.tempering_state()[0] == 0, S, np.inf)
+        local = torch.as_tensor(S)
         allv = self.all_gather_chain_values(local.to(dev)).cpu().numpy()
         best = int(np.argmin(allv))  # (the first minimum: the lowest global chain id among ties)
         owner = next(r for r in range(self.world_size) if best < sum(self.counts[: r + 1]))

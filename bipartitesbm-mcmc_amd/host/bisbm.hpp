@@ -253,6 +253,14 @@ public:
         check(bisbm_marginals_get_reference(h_, nullptr, &chain));
         return chain;
     }
+    // replica exchange (include/bisbm.h): the ladder, sweeps with an exchange round every `every` sweeps, swaps per rung pair
+    void tempering_set(const std::vector<float>& ladder) { check(bisbm_tempering_set(h_, (uint32_t)ladder.size(), ladder.data())); }
+    void tempering_run(uint64_t sweeps, uint32_t every) { check(bisbm_tempering_run(h_, sweeps, every, nullptr)); }
+    void tempering_stats(size_t L, std::vector<uint64_t>& attempted, std::vector<uint64_t>& accepted, uint64_t& rounds) {
+        attempted.assign(L - 1, 0);
+        accepted.assign(L - 1, 0);
+        check(bisbm_tempering_stats(h_, attempted.data(), accepted.data(), &rounds));
+    }
     // the marginal estimate of README.md:49-53: every node's most frequent block, pooled over the handle's devices on the
     // devices (bisbm_marginals_map)
     uint_vec_t marginal_map_labels(size_t /*NA*/) {

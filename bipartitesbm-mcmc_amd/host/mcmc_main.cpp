@@ -4,7 +4,8 @@
 // partition rules (:241-326), same stdout contract: the label vector through output_vec (trailing blank,
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
-// Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align.
+// Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
+// --tempering, --exchange_every.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -45,6 +46,7 @@ const option_spec kOptions[] = {
     // engine extras
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
+    {"tempering", 0, 2},        {"exchange_every", 0, 1},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -170,6 +172,12 @@ void print_help(const char* argv0) {
                  "                                        prints every node's most frequent block over samples and chains.\n"
                  "  --align                               With --marginalize: match every chain's block labels to those of the\n"
                  "                                        lowest-description-length chain before pooling (needed for --chains > 1).\n"
+                 "  --tempering arg                       With --marginalize: replica exchange over a ladder T0 <= ... <= T{L-1}\n"
+                 "                                        (L >= 2 temperatures > 0; --chains a multiple of L; Philox mode): the\n"
+                 "                                        chains run in ensembles of L, neighbouring rungs propose to swap\n"
+                 "                                        temperatures, and only the chains at T0 are sampled.  The swap\n"
+                 "                                        acceptance of every rung pair is reported on stderr.\n"
+                 "  --exchange_every arg (=1)             With --tempering: sweeps between exchange rounds.\n"
                  "  --csr_cache                           Keep a binary CSR beside the edge list (<path>.bisbm_csr, checked\n"
                  "                                        against the file's size and mtime); the text file stays the input.\n";
 }
@@ -193,6 +201,42 @@ int main(int argc, char const* argv[]) {
     if (count("align") && !count("marginalize")) {
         std::cerr << "--align aligns the chains' block labels before pooling: it needs --marginalize.\n";
         return 1;
+    }
+    // replica exchange: the ladder and the exchange period are checked before anything else runs
+    std::vector<float> ladder;
+    uint32_t exchange_every = 1;
+    if ((count("tempering") || count("exchange_every")) && !count("marginalize")) {
+        std::cerr << "--tempering runs replica exchange for the marginals of the coldest chains: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("exchange_every") && !count("tempering")) {
+        std::cerr << "--exchange_every sets the period of the exchange rounds: it needs --tempering.\n";
+        return 1;
+    }
+    if (count("tempering")) {
+        for (const std::string& tok : var_map["tempering"]) {
+            char* end = nullptr;
+            const float T = std::strtof(tok.c_str(), &end);
+            if (tok.empty() || *end != '\0' || !std::isfinite(T) || !(T > 0.f) || (!ladder.empty() && T < ladder.back())) {
+                std::cerr << "Invalid --tempering. A non-decreasing ladder of at least 2 finite temperatures > 0, e.g. --tempering 1 1.5 2.5 4.\n";
+                return 1;
+            }
+            ladder.push_back(T);
+        }
+        if (ladder.size() < 2) {
+            std::cerr << "Invalid --tempering. A non-decreasing ladder of at least 2 finite temperatures > 0, e.g. --tempering 1 1.5 2.5 4.\n";
+            return 1;
+        }
+        if (count("exchange_every")) {
+            const std::string v = single("exchange_every", "1");
+            char* end = nullptr;
+            const unsigned long k = std::strtoul(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || v[0] == '-' || k > 0xffffffffUL) {
+                std::cerr << "Invalid --exchange_every. Sweeps between exchange rounds: an integer >= 0 (0: no exchanges).\n";
+                return 1;
+            }
+            exchange_every = (uint32_t)k;
+        }
     }
     if (count("edge_list_path") == 0) {
         std::cerr << "edge_list_path is required (-e flag)\n";
@@ -444,6 +488,25 @@ int main(int argc, char const* argv[]) {
         return 1;
     }
     opt.rng_mode = rng == "philox" ? BISBM_RNG_PHILOX : BISBM_RNG_MT19937_COMPAT;
+    if (!ladder.empty()) {
+        if (opt.n_chains % ladder.size()) {
+            std::cerr << "--tempering with " << ladder.size() << " temperatures needs --chains a multiple of " << ladder.size() << " (got " << opt.n_chains
+                      << ").\n";
+            return 1;
+        }
+        // --devices: the chains are split into contiguous ranges, the first n_chains % devices one chain longer (bisbm_create_multi);
+        // every range must hold whole ensembles
+        const size_t nd = opt.devices.size();
+        if (nd > 1 && ((opt.n_chains / nd) % ladder.size() || (opt.n_chains % nd) != 0)) {
+            std::cerr << "--tempering with " << ladder.size() << " temperatures over " << nd << " devices needs --chains a multiple of "
+                      << ladder.size() * nd << " (every device's share a multiple of " << ladder.size() << "; got " << opt.n_chains << ").\n";
+            return 1;
+        }
+        if (opt.rng_mode != BISBM_RNG_PHILOX) {
+            std::cerr << "--tempering runs in Philox mode only (mt19937-compat is the reference's verification path): add --rng philox.\n";
+            return 1;
+        }
+    }
     opt.seed = seed;
     opt.gen_seed = count("gen_seed") ? std::strtoull(single("gen_seed", "0").c_str(), nullptr, 10) : seed + 1;
 
@@ -638,11 +701,19 @@ int main(int argc, char const* argv[]) {
             metropolis_hasting algorithm;
             const float_vec_t t1{1.f, 0.f};
             const size_t never = std::numeric_limits<size_t>::max();
-            if (burn_in >= N) algorithm.anneal(blockmodel, &constant_schedule, t1, burn_in, never);
+            // with --tempering every chain runs at its rung's temperature and the exchange rounds run between the sweeps
+            if (!ladder.empty()) blockmodel.tempering_set(ladder);
+            auto advance = [&](size_t sweeps) {
+                if (!ladder.empty())
+                    blockmodel.tempering_run(sweeps, exchange_every);
+                else
+                    algorithm.anneal(blockmodel, &constant_schedule, t1, sweeps * N, never);
+            };
+            if (burn_in >= N) advance(burn_in / N);
             blockmodel.marginals_reset();
             if (count("align")) blockmodel.marginals_set_alignment(true);
             for (size_t sample = 0; sample < n_samples; ++sample) {
-                algorithm.anneal(blockmodel, &constant_schedule, t1, sweeps_between * N, never);
+                advance(sweeps_between);
                 blockmodel.marginals_accumulate();
             }
             std::clog << "marginalize: burn-in " << burn_in / N << " sweeps, " << n_samples << " samples " << sweeps_between
@@ -651,6 +722,17 @@ int main(int argc, char const* argv[]) {
                 std::cerr << "[error] --marginalize: -t " << sampling_steps << " steps hold no sample (" << sweeps_between * N
                           << " steps per sample)\n";
                 return 1;
+            }
+            if (!ladder.empty()) {
+                std::vector<uint64_t> att, acc;
+                uint64_t rounds = 0;
+                blockmodel.tempering_stats(ladder.size(), att, acc, rounds);
+                std::clog << "tempering: " << opt.n_chains / ladder.size() << " ensemble(s) of " << ladder.size() << " rungs, " << rounds
+                          << " exchange round(s), " << opt.n_chains / ladder.size() << " chain(s) at T0 = " << ladder[0] << " sampled; swap acceptance:";
+                for (size_t i = 0; i + 1 < ladder.size(); ++i)
+                    std::clog << " " << ladder[i] << "<->" << ladder[i + 1] << " " << acc[i] << "/" << att[i] << " ("
+                              << (att[i] ? (double)acc[i] / (double)att[i] : 0.) << ")";
+                std::clog << "\n";
             }
             if (count("align"))
                 std::clog << "align: labels matched to chain " << blockmodel.marginals_reference_chain() << " (lowest description length)\n";

@@ -17,7 +17,7 @@ import numpy as np
 
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
-                return_counts=None, align=False):
+                return_counts=None, align=False, tempering=None, exchange_every=1):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -35,13 +35,25 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     alignment before pooling"); pooling more than one chain gives a marginal only then.  The mode is turned on for the run and
     stays on.  The reference: one the caller set (model.marginals_set_reference), or else the lowest-description-length chain
     at the first sample -- over all ranks when the chains are spread (all-gathered description lengths, ties -> the lowest
-    global chain id; the owning rank broadcasts its labels and every rank sets them before the first sample)."""
+    global chain id; the owning rank broadcasts its labels and every rank sets them before the first sample).
+    `tempering`: a temperature ladder T0 <= ... <= T{L-1} (include/bisbm.h, "Replica exchange"): the chains run in ensembles of L
+    consecutive global ids, burn-in and the gaps between samples run through model.tempering_run(sweeps, exchange_every), and
+    only the chains on rung 0 (T0) are counted -- over ranks each rank histograms its own cold chains, and the aligned reference
+    is the lowest-description-length rung-0 chain.  Tempering is turned on for the run (rungs and statistics reset) and stays
+    on: model.tempering_stats() reports the swaps afterwards."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
         return_counts = not multi
+    if tempering is not None:
+        model.set_tempering(tempering)
+
+        def advance(sweeps):
+            model.tempering_run(sweeps, exchange_every)
+    else:
+        advance = model.run_sweeps
     if burn_in_sweeps > 0:
-        model.run_sweeps(burn_in_sweeps)
+        advance(burn_in_sweeps)
     if device_counts is None and not multi:
         # one rank, no caller buffer: the library's own histogram
         model.marginals_reset()
@@ -49,7 +61,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             model.marginals_set_alignment(True)
         for _ in range(int(n_samples)):
             if sampling_frequency_sweeps > 0:
-                model.run_sweeps(sampling_frequency_sweeps)
+                advance(sampling_frequency_sweeps)
             model.marginals_accumulate(None)
         counts = model.marginals_get().astype(np.int64)
         base = np.where(np.arange(n) >= model.na, model.KA, 0)
@@ -74,7 +86,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             _drop_library_reference(model)
     for _ in range(int(n_samples)):
         if sampling_frequency_sweeps > 0:
-            model.run_sweeps(sampling_frequency_sweeps)
+            advance(sampling_frequency_sweeps)
         model.marginals_accumulate(device_counts.data_ptr())  # adds into the tensor, on the device
     if not multi:
         from .distributed import _argmax_first

@@ -22,7 +22,8 @@ extern "C" {
 #endif
 
 /* 2: bisbm_get_ka_kb_chain; KA + KB above 256 (wide mode); handles whose chains differ in shape.
- * 3: bisbm_check_shape; several devices behind one handle (bisbm_create_multi); bisbm_last_pass_steps.  Additions only. */
+ * 3: bisbm_check_shape; several devices behind one handle (bisbm_create_multi); bisbm_last_pass_steps; later additions: label
+ *    alignment (bisbm_marginals_set_alignment ...), replica exchange (bisbm_tempering_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -117,7 +118,7 @@ int bisbm_init(bisbm_handle h);
 int bisbm_shuffle(bisbm_handle h);
 
 /* metropolis_hasting::anneal (metropolis_hasting.hh:48-53, metropolis_hasting.cc:64-101) for
- * every chain: duration_steps / n sweeps of n node updates (step :42-62, transition_ratio
+ * every chain (BISBM_ERR_STATE while replica exchange is on: bisbm_tempering_run): duration_steps / n sweeps of n node updates (step :42-62, transition_ratio
  * :103-192, single_vertex_change blockmodel.cc:613-637, apply_mcmc_moves blockmodel.cc:461-503),
  * early stop per chain when the count of T<1 steps since the last new minimum reaches steps_await.
  * kwargs are the two float cooling parameters (mcmc_main.cc:49).  acc_rate_out[n_chains] receives
@@ -201,6 +202,35 @@ int bisbm_marginals_get_alignment(bisbm_handle h, uint32_t chain, uint32_t *perm
 /* The assignment solver of the alignment on the host, without a device: table is k x k (row-major, C[r][s]), perm_out[k]
  * receives pi(r) in 0..k-1, total_out (may be NULL) sum_r C[r][pi(r)]. */
 int bisbm_align_assignment(uint32_t k, const uint32_t *table, uint32_t *perm_out, uint64_t *total_out);
+
+/* Replica exchange (parallel tempering; no reference counterpart: the reference runs one chain at one temperature).
+ * Ladder: L >= 2 float temperatures, finite, > 0, non-decreasing (float, like the kwargs of bisbm_anneal: a chain at rung T runs
+ * bit-for-bit as bisbm_anneal(BISBM_SCHED_CONSTANT, {T, .}) would run it).  Ensemble g is the chains of global ids
+ * [g L, (g + 1) L); at the start chain g L + i sits on rung i.  The chain count of the handle and of every device entry, and the
+ * first global chain id, must be multiples of L (an ensemble never straddles a device or a rank: no collective), and all chains
+ * one shape.  Every chain runs the constant-temperature chain at its rung's temperature, its Philox streams keyed by its own
+ * global id as always, so its path is that of a one-chain run with a piecewise-constant T; there is no early stop.
+ * Exchange round r (r counts from 0 at bisbm_tempering_set): S = every chain's full description length (bisbm_entropy's value,
+ * f64); for every ensemble and every lower rung i with i = r (mod 2) and i + 1 < L, with a = the chain on rung i, b = the chain
+ * on rung i + 1: delta = (1/T_i - 1/T_{i+1}) (S_a - S_b); U = Philox(seed, counter (r L + i, global id of the ensemble's first
+ * chain, purpose 7 = exchange)), u = the 53-bit uniform of U's first two words (DESIGN.md "Philox-mode definition"); the two
+ * chains swap rungs iff delta >= 0 or u < exp(delta).  Chain states never move.  Attempted / accepted exchanges are counted per
+ * rung pair (L - 1 counters each, summed over ensembles and devices).
+ * While tempering is on, bisbm_anneal is refused (BISBM_ERR_STATE) and bisbm_marginals_accumulate counts only the chains on rung
+ * 0, raw or aligned; the library-chosen alignment reference is the lowest-description-length chain on rung 0. */
+
+/* On with the ladder (L temperatures), or off with L = 0 (ladder may be NULL then).  Resets the rungs, the round counter and the
+ * statistics.  Refused: a bad ladder or L that does not divide the chain counts (BISBM_ERR_INVALID_ARG), mt19937-compat mode
+ * (BISBM_ERR_UNSUPPORTED), chains grouped by shape after bisbm_agg_merge_total (BISBM_ERR_STATE). */
+int bisbm_tempering_set(bisbm_handle h, uint32_t L, const float *ladder);
+/* `sweeps` sweeps of every chain; after each complete block of exchange_every sweeps one exchange round (0: no exchange).
+ * acc_rate_out[n_chains] (may be NULL): accepted steps / steps of the call, per chain. */
+int bisbm_tempering_run(bisbm_handle h, uint64_t sweeps, uint32_t exchange_every, double *acc_rate_out);
+/* Rung and temperature of every chain (n_chains entries each; either pointer may be NULL). */
+int bisbm_tempering_get(bisbm_handle h, uint32_t *rung_of_chain, float *T_of_chain);
+/* attempted[L - 1] / accepted[L - 1] exchanges of rung pair (i, i + 1) and the rounds run since bisbm_tempering_set; any pointer
+ * may be NULL. */
+int bisbm_tempering_stats(bisbm_handle h, uint64_t *attempted, uint64_t *accepted, uint64_t *rounds);
 
 /* The marginal estimate README.md:49-53 asks for: the most frequent block of every node over all samples of all chains (ties ->
  * the lowest block), n labels in the reference's numbering, from the internal histogram.  Over several devices this is the
