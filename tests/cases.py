@@ -31,11 +31,13 @@ CASES = [
     # KA + KB > 256: the library's wide mode (two-byte labels, m read and updated in HBM) -- where a --merge run starts
     ("wide_labels", 400, 300, 6000, 200, 150, 1.0, 2, 0),
     ("big_m_r", 150, 150, 60000, 2, 3, 1.0, 0, 0),     # m_r > 10^4: log_q_approx on the device
-    # production kernel's hot step: m_r > 10^4 and k / sqrt(n) > 24 (closed-form log_q tier), K <= 32 ...
+    # production kernel's hot step: m_r > 10^4 and k / sqrt(n) > 18 (closed-form log_q tier), K <= 32 ...
     ("direct_tier", 20000, 20000, 100000, 2, 2, 1.0, 0, 0),
-    # ... the same with both block counts > 32 (six-level scans and sums) ...
+    # ... both block counts > 32 (six-level scans and sums) with every m_r <= 10^4: the K > 32 path on the q TABLE ...
     ("direct_tier_wide", 72000, 72000, 216000, 40, 33, 1.0, 0, 0),
-    # ... and k / sqrt(n) around 23: the hot step falls back to the iterated / literal log_q tiers
+    # ... both block counts > 32 in the closed-form tier (blocks of ~3000 nodes, m_r ~ 2 x 10^4, k / sqrt(n) ~ 22) ...
+    ("direct_tier_k40", 120000, 120000, 720000, 40, 33, 1.0, 0, 0),
+    # ... k / sqrt(n) around 23: the closed-form tier as well (the name is of the time the tier began at 24)
     ("mid_tier", 5300, 5300, 26500, 2, 2, 1.0, 0, 0),
     # ... k / sqrt(n) around 10 (blocks of ~1200 nodes): the converged log_q tier in the hot step
     ("mid_tier_low", 2400, 2400, 28800, 2, 2, 1.0, 0, 0),
@@ -56,6 +58,30 @@ CASES = [
     ("edgeless", 10, 8, 0, 2, 2, 1.0, 0, 0),
 ]
 CASE = {c[0]: c for c in CASES}
+
+# The log_q tier every block of a case reaches after shuffle_bisbm, for the cases whose name or comment claims one
+# (tests/test_oracle.py guards this, so that a case drifting into another tier fails instead of passing vacuously).
+CASE_TIERS = {"big_m_r": "literal", "direct_tier": "closed", "direct_tier_wide": "table", "direct_tier_k40": "closed",
+              "mid_tier": "closed", "mid_tier_low": "mid", "dense_low_tier": "low", "eps0_direct": "closed"}
+
+LOG_Q_TIERS = ("table", "closed", "closed2", "mid", "low", "literal")
+
+
+def log_q_tiers(m_r, n_r):
+    """The tier in which the Philox-mode log_q(n = m_r, k = n_r) is evaluated (bisbm_device.hpp log_q / log_q_approx<true>,
+    and the hot step's hot_log_q in bisbm_sweep_fast.hip), per block: n <= 10^4 the q table; k^4 < n the small-k sum; else by
+    u^2 = k^2 / n with k = min(k, n): > 18^2 log_q_closed, [13^2, 18^2] log_q_closed2, [8^2, 13^2) log_q_mid, [2.5^2, 8^2)
+    log_q_low, below the literal series ("literal" covers the small-k sum as well).  The same exact integer tests."""
+    n = np.asarray(m_r, dtype=np.int64)
+    k = np.minimum(np.asarray(n_r, dtype=np.int64), n)
+    k2 = k * k
+    return np.select([n <= 10000, (k < 256) & (k2 * k2 < n), k2 > 324 * n, k2 >= 169 * n, k2 >= 64 * n, 4 * k2 >= 25 * n],
+                     ["table", "literal", "closed", "closed2", "mid", "low"], "literal")
+
+
+def tier_counts(m_r, n_r):
+    t = log_q_tiers(m_r, n_r)
+    return {name: int((t == name).sum()) for name in LOG_Q_TIERS}
 
 
 # ------------------------------------------------------------------ a graph small enough to enumerate

@@ -247,9 +247,19 @@ def test_config5_shape_properties(chains, container, monkeypatch, capfd):
     monkeypatch.setenv("BISBM_POOL_LOG", "1")
     g = gpu_model(rowptr, col, na, nb, ka, kb, 1.0, labels, n_chains=chains, rng="philox", seed=5, **({"devices": [0] * container} if container else {}))
     g.shuffle_bisbm()
+    # the plain handle: chains 0 and 255 against their oracle runs after each sweep (an oracle model of this shape holds ~3.3 GB
+    # and takes ~20 s per sweep on one CPU core; the models run one after the other)
+    oracle_picks = (0, chains - 1) if not container else ()
+    snaps = []
+
+    def snap(rates):
+        snaps.append([(rates[c], g.get_memberships(c), g.get_m(c), g.get_m_r(c), g.get_n_r(c), g.get_eta_rk_(c),
+                       g.get_entropy()[c]) for c in oracle_picks])
+
     s0 = g.entropy()
     rates = B.MetropolisHasting().anneal(g, "constant", [1.0], na + nb, BIG)
     assert ((rates > 0.3) & (rates <= 1.0)).all()
+    snap(rates)
     s1 = g.entropy()
     cum = g.get_entropy()
     assert np.allclose(s1 - s0, cum, rtol=1e-9, atol=1e-6 * np.abs(cum).max())
@@ -257,9 +267,22 @@ def test_config5_shape_properties(chains, container, monkeypatch, capfd):
     labs_after_first = [g.get_memberships(c) for c in picks]
     rates = B.MetropolisHasting().anneal(g, "exponential", [1.5, 0.9999999], na + nb, BIG)  # (the cooling-schedule variant)
     assert ((rates > 0.2) & (rates <= 1.0)).all()
+    snap(rates)
     s2 = g.entropy()
     cum2 = g.get_entropy()
     assert np.allclose(s2 - s0, cum2, rtol=1e-9, atol=1e-6 * np.abs(cum2).max())
+    for i, c in enumerate(oracle_picks):
+        o = O.OracleModel(rowptr, col, na, nb, ka, kb, 1.0, labels)
+        o.seed_philox(5, c)
+        o.shuffle_bisbm()
+        for (sched, kw), sn in zip((("constant", [1.0]), ("exponential", [1.5, 0.9999999])), snaps):
+            rate, lab, m, m_r, n_r, eta, cum_c = sn[i]
+            assert o.anneal(sched, kw, na + nb, BIG) == rate, (sched, c)
+            assert (o.memberships() == lab).all() and (o.m() == m).all() and (o.m_r() == m_r).all(), (sched, c)
+            assert (o.n_r() == n_r).all() and (o.eta() == eta).all(), (sched, c)
+            assert abs(cum_c - o.get_entropy()) <= 1e-9 * abs(o.get_entropy()), (sched, c, cum_c, o.get_entropy())
+        del o
+    del snaps
     before = [(g.get_m(c), g.get_m_r(c), g.get_n_r(c), g.get_eta_rk_(c)) for c in picks]
     labs = [g.get_memberships(c) for c in picks]
     n_r_all = [g.get_n_r(c) for c in range(0, chains, 17)]

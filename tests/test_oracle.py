@@ -611,3 +611,24 @@ def test_agg_merge_with_negative_diffs_splits_first():
     assert b.agg_split(0, 10) == 0 and b.agg_merge(0, 1, 10) == 0
     assert (a.ka, a.kb) == (4, 4) == (b.ka, b.kb)
     assert (a.memberships() == b.memberships()).all()
+
+
+def test_cases_reach_the_log_q_tiers_they_claim():
+    """Every case of tests/cases.py whose name claims a log_q tier reaches it: after test_matches_oracle's shuffle (shuffling
+    keeps n_r; m_r follows the mean degree), every block's (m_r, n_r) lies in that tier.  A case whose sizes drift out of its tier
+    would otherwise go on passing the GPU comparison without ever evaluating the tier it is named for."""
+    import cases
+    assert {c[0] for c in cases.CASES if "tier" in c[0]} <= set(cases.CASE_TIERS)
+    for name, tier in cases.CASE_TIERS.items():
+        _, na, nb, ne, ka, kb, eps, hubs, iso = cases.CASE[name]
+        rowptr, col = cases.random_graph(11, na, nb, ne, ka, kb, hubs, iso)
+        o = O.OracleModel(rowptr, col, na, nb, ka, kb, eps, O.contiguous_labels(na, nb, ka, kb))
+        o.seed_philox(777, 3)
+        o.shuffle_bisbm()
+        got = cases.log_q_tiers(o.m_r(), o.n_r())
+        assert (got == tier).all(), (name, tier, cases.tier_counts(o.m_r(), o.n_r()))
+    # the classifier's edges: table up to n = 10^4; the exact u^2 boundaries 324 (exclusive) / 169 / 64 / 6.25 (inclusive)
+    m_r = np.array([10000, 10001, 10001, 40000, 40000, 40000, 40000, 40000, 40000, 40000, 40000, 10 ** 6, 40000])
+    n_r = np.array([9000, 1800, 1801, 3600, 3601, 2600, 2599, 1600, 1599, 500, 499, 31, 50000])
+    assert list(cases.log_q_tiers(m_r, n_r)) == ["table", "closed2", "closed", "closed2", "closed", "closed2", "mid", "mid",
+                                                 "low", "low", "literal", "literal", "closed"]
