@@ -92,10 +92,10 @@ def compile_library(out, extra=(), verbose=False, jobs=None):
     objdir = tempfile.mkdtemp(prefix="bisbm_obj_")
     try:
         # the production kernel's 20 variants: four units of five kernels + the dispatch (BISBM_FAST_PART, bisbm_sweep_fast.hip);
-        # a build with in-kernel stamps keeps them in one unit (its counters are one device symbol)
+        # a build with in-kernel stamps or pass counts keeps them in one unit (its counters are one device symbol)
         units = []
         for src in SOURCES:
-            if src == "bisbm_sweep_fast.hip" and not any("BISBM_STAMPS" in f for f in extra):
+            if src == "bisbm_sweep_fast.hip" and not any("BISBM_STAMPS" in f or "BISBM_PASS_COUNTS" in f for f in extra):
                 units += [(src, ["-DBISBM_FAST_PART=%d" % part], "%s.part%d.o" % (src, part)) for part in range(5)]
             else:
                 units.append((src, [], src + ".o"))

@@ -105,6 +105,44 @@ __device__ __forceinline__ uint32_t smin(uint32_t x, uint32_t y) {
     return r;
 }
 
+// A later step's inverse-CDF target s' (the first block whose running sum S exceeds its draw x) lies strictly between the
+// blocks r and s of an earlier step that moves k of the column's edges from row r to row s.  Both S_{s'-1} and S_{s'} then move
+// by k: down when r < s (down = 1, edge = S_{s'}), up when r > s (down = 0, edge = S_{s'-1}).  The margin is how far they may
+// move with s' still the target: S_{s'} - 1 - x = ~(x - S_{s'}), or x - S_{s'-1}; both >= 0, and the target holds iff k <= margin.
+__device__ __forceinline__ uint32_t target_margin(uint32_t down, uint32_t edge, uint32_t x) { return (x - edge) ^ (0u - down); }
+// k > margin as a 0 / 1 word (both < 2^31: column sums are edge counts)
+__device__ __forceinline__ uint32_t target_moves(uint32_t margin, uint32_t k) { return (margin - k) >> 31; }
+
+// Diagnostic: committed steps per pass, and what the stand rule did with the passes in which the first step moved
+// (BISBM_PASS_COUNTS, compiled out of the product build; one line on stderr per launch)
+//   0 passes, 1 steps they committed, 2 two-steps passes whose first step moves with a second step to stand or fall, of those:
+//   3 a shared block, 4 / 5 a target strictly between r and s (k > 0, no shared block) that holds / moves, 6 / 7 the same at the
+//   boundary (k == margin / k == margin + 1)
+#ifdef BISBM_PASS_COUNTS
+__device__ unsigned long long g_pass_counts[8];
+#define PCOUNT(i, v) (pc_acc[i] += (v))
+#define PASS_COUNTS_PAIR(paired)                                                          \
+    do {                                                                                  \
+        const uint32_t pm_ = (paired) & chA, colk_ = col & sflag(kAtB) & (set_clash ^ 1u); \
+        const uint32_t mv_ = target_moves(margin, kAtB);                                  \
+        pc_acc[0] += 1u;                                                                  \
+        pc_acc[1] += 1u + stands;                                                         \
+        pc_acc[2] += pm_;                                                                 \
+        pc_acc[3] += pm_ & set_clash;                                                     \
+        pc_acc[4] += pm_ & colk_ & (mv_ ^ 1u);                                            \
+        pc_acc[5] += pm_ & colk_ & mv_;                                                   \
+        pc_acc[6] += pm_ & colk_ & (margin == kAtB ? 1u : 0u);                            \
+        pc_acc[7] += pm_ & colk_ & (margin + 1u == kAtB ? 1u : 0u);                       \
+    } while (0)
+#else
+#define PCOUNT(i, v) \
+    do {             \
+    } while (0)
+#define PASS_COUNTS_PAIR(paired) \
+    do {                         \
+    } while (0)
+#endif
+
 // BISBM_PREDICT_TARGET=0 compiles the predicted target out of the two-steps passes (A/B builds)
 #ifndef BISBM_PREDICT_TARGET
 #define BISBM_PREDICT_TARGET 1
@@ -281,6 +319,9 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
 #ifdef BISBM_STAMPS
     unsigned long long st_prev, st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     __asm__ volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
+#endif
+#ifdef BISBM_PASS_COUNTS
+    unsigned long long pc_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
 
     for (uint64_t sweep = 0; sweep < all_sweeps; ++sweep) {
@@ -882,11 +923,13 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                 // ---- two steps per pass (K <= 32, constant T > 0, no early-stop bookkeeping) ----
                 // The hot step uses lanes 0..31 (one lane per block).  Here lanes 32..63 evaluate step q + 1 in the same
                 // instructions, against the same state, i.e. the state BEFORE step q.  That is step q + 1's true outcome
-                // unless step q moves its node (r -> s, r != s) AND touches something step q + 1 read:
+                // unless step q moves its node (r -> s, r != s) AND changes something step q + 1 used:
                 //   rows r, s of m, m_r / n_r / eta of r, s       <=>  {r', s'} meets {r, s};
-                //   column t' of m (it feeds the inverse CDF)      <=>  k_q[t'] != 0 -- and then only rows r and s of the
-                //     column change, by -k and +k: the running sums move only for blocks in [min(r,s), max(r,s)), so a
-                //     target s' outside (min, max) is still the first block whose sum exceeds x.
+                //   the target s' of the inverse CDF over column t' of m.  Only rows r and s of the column change, by -k and
+                //     +k (k = k_q[t']): the running sums S_j move by the same amount for every j in [min(r,s), max(r,s)) and
+                //     stay monotone, so a target outside (min, max) is still the first block whose sum exceeds x.  Inside, both
+                //     S_{s'-1} and S_{s'} move: with r < s they drop by k and s' holds iff k <= S_{s'} - 1 - x, with r > s they
+                //     rise by k and s' holds iff k <= x - S_{s'-1} (target_margin).
                 // In those cases step q + 1 is evaluated again as the first step of the next pass; otherwise both
                 // steps are committed (their writes touch different rows).  The chain is the serial chain, bit for
                 // bit: the CPU checker steps one node at a time and the parity tests compare against it (measured on the
@@ -996,6 +1039,8 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             if ((liveA & warmA) != 0u) new_minimum(q);
                             if ((liveB & warmB) != 0u) new_minimum(qB);
                         }
+                        PCOUNT(0, 1u);
+                        PCOUNT(1, 1u + pairable);
                         return 1u + pairable;
                     }
                     if constexpr (kPredictTarget) {
@@ -1018,7 +1063,13 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const uint32_t lo = min(r_locA, s_locA), hi = max(r_locA, s_locA);
                     const uint32_t between = ((1u << hi) - 1u) & ~((2u << lo) - 1u);  // blocks strictly between r and s
                     const uint32_t kAtB = readlane(kk, t_locB);                        // (lanes 0..31 hold k_q[.])
-                    const uint32_t clash = sflag(setA & setB) | (((between >> s_locB) & 1u) & sflag(kAtB));
+                    // a target strictly between r and s: does step q's move of column t' move it?  (step q + 1's running sums
+                    // are lanes 32.. of the scan -- the scan's target, not the prediction -- and its x is prop in lanes 32..)
+                    const uint32_t downA = (r_locA - s_locA) >> 31;
+                    const uint32_t margin = target_margin(downA, readlane((uint32_t)scan, 31u + s_locB + downA), readlane(prop, 32u));
+                    const uint32_t col = (between >> s_locB) & 1u;
+                    const uint32_t set_clash = sflag(setA & setB);
+                    const uint32_t clash = set_clash | (col & target_moves(margin, kAtB));
                     // what the verdicts will be combined with, in one word (the scalar file is full): bit 0 step q can
                     // move, bit 1 step q is an accepted r == s, bits 2, 3 the same for step q + 1, bit 4 the clash
                     const uint32_t flags = (liveA & (selfA ^ 1u)) | ((liveA & selfA & warmA) << 1) | ((liveB & (selfB ^ 1u)) << 2) |
@@ -1080,6 +1131,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const uint32_t chA = flags & yesA;                                  // step q moves its node
                     const uint32_t okA = chA | ((flags >> 1) & 1u);                     // ... counts as accepted
                     const uint32_t stands = pairable & ((chA & (flags >> 4)) ^ 1u);     // step q + 1's evaluation stands
+                    PASS_COUNTS_PAIR(pairable);
                     const uint32_t chB = stands & (flags >> 2) & yesB;
                     const uint32_t okB = chB | (stands & (flags >> 3) & 1u);
                     acc_chunk += okA + okB;
@@ -1209,6 +1261,8 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             if ((liveA & warmA) != 0u) new_minimum(q);
                             if ((liveB & warmB) != 0u) new_minimum(qB);
                         }
+                        PCOUNT(0, 1u);
+                        PCOUNT(1, 1u + pairable);
                         return 1u + pairable;
                     }
                     uint32_t pair_ok = pairable;  // step q + 1 is there and has been evaluated on its own target
@@ -1233,7 +1287,14 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const uint32_t kA0 = readlane(kk0, t_locB & 31u), kA1 = readlane(kk1, t_locB & 31u);
                     const uint32_t kAtB = kA0 + (t_locB >> 5) * (kA1 - kA0);
                     const unsigned long long common = setA & setB;
-                    const uint32_t clash = sflag((uint32_t)common | (uint32_t)(common >> 32)) | ((uint32_t)((between >> s_locB) & 1ull) & sflag(kAtB));
+                    // the exact target test of step_pair: block e = s' - 1 + down (S_{s'} or S_{s'-1}) is lane 32 + (e & 31) of
+                    // the lower (e < 32) or the upper scan
+                    const uint32_t downA = (r_locA - s_locA) >> 31, e_edge = s_locB - 1u + downA;
+                    const uint32_t S0 = readlane((uint32_t)scan0, 32u + (e_edge & 31u)), S1 = readlane((uint32_t)scan1, 32u + (e_edge & 31u));
+                    const uint32_t margin = target_margin(downA, S0 + (e_edge >> 5) * (S1 - S0), readlane(prop, 32u));
+                    const uint32_t col = (uint32_t)(between >> s_locB) & 1u;
+                    const uint32_t set_clash = sflag((uint32_t)common | (uint32_t)(common >> 32));
+                    const uint32_t clash = set_clash | (col & target_moves(margin, kAtB));
                     const uint32_t flags = (liveA & (selfA ^ 1u)) | ((liveA & selfA & warmA) << 1) | ((liveB & (selfB ^ 1u)) << 2) |
                                            ((liveB & selfB & warmB) << 3) | (clash << 4);
                     uint32_t flags_pin = flags;
@@ -1276,6 +1337,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const uint32_t chA = flags & yesA;
                     const uint32_t okA = chA | ((flags >> 1) & 1u);
                     const uint32_t stands = pair_ok & ((chA & (flags >> 4)) ^ 1u);
+                    PASS_COUNTS_PAIR(pair_ok);
                     const uint32_t chB = stands & (flags >> 2) & yesB;
                     const uint32_t okB = chB | (stands & (flags >> 3) & 1u);
                     acc_chunk += okA + okB;
@@ -1478,7 +1540,10 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             q += 1u;
                         } else {  // the steps up to the next one that needs the general path, or to the end of the chunk
                             const uint32_t nst = min(min((uint32_t)__builtin_ctz(four | 0x10u), 4u), cnt - q);
-                            q += step_quad(tm, q, nst);
+                            const uint32_t done = step_quad(tm, q, nst);
+                            PCOUNT(0, 1u);
+                            PCOUNT(1, done);
+                            q += done;
                         }
                     }
                     acc_l0 += (unsigned long long)acc_chunk;
@@ -1667,7 +1732,10 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             q += 1u;
                         } else {  // the steps up to the next one that needs the general path, or to the end of the chunk
                             const uint32_t nst = min(min((uint32_t)__builtin_ctz(four | 0x10u), 4u), cnt - q);
-                            q += step_quad32(tm, q, nst);
+                            const uint32_t done = step_quad32(tm, q, nst);
+                            PCOUNT(0, 1u);
+                            PCOUNT(1, done);
+                            q += done;
                         }
                     }
                     acc_l0 += (unsigned long long)acc_chunk;
@@ -1821,7 +1889,10 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             q += 1u;
                         } else {
                             const uint32_t nst = min(min((uint32_t)__builtin_ctz(eight | 0x100u), 8u), cnt - q);
-                            q += step_oct(tm, q, nst);
+                            const uint32_t done = step_oct(tm, q, nst);
+                            PCOUNT(0, 1u);
+                            PCOUNT(1, done);
+                            q += done;
                         }
                     }
                     acc_l0 += (unsigned long long)acc_chunk;
@@ -1950,6 +2021,10 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
     if (lane == 0)
         for (int i = 0; i < 12; ++i) atomicAdd(&g_fast_stamps[i], st_acc[i]);
 #endif
+#ifdef BISBM_PASS_COUNTS
+    if (lane == 0)
+        for (int i = 0; i < 8; ++i) atomicAdd(&g_pass_counts[i], pc_acc[i]);
+#endif
     if (lane == 0) {
         // (a launch without the early-stop bookkeeping has not kept the running sum: bisbm_anneal sets it from the change of the
         // description length, sweep_fast_sum_from_entropy)
@@ -2048,6 +2123,19 @@ hipError_t launch_sweep_fast(const SweepParams& p, size_t /*generic_lds_bytes*/,
         fprintf(stderr, "[stamps] %-20s %8.1f cyc/step\n", "total", tot / steps);
         unsigned long long z[16] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fast_stamps), z, sizeof(z));
+    }
+#endif
+#ifdef BISBM_PASS_COUNTS
+    if (e == hipSuccess) {
+        (void)hipStreamSynchronize(stream);
+        unsigned long long h[8] = {0};
+        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pass_counts), sizeof(h));
+        fprintf(stderr,
+                "[pass_counts] passes %llu steps %llu first_moves %llu shared_block %llu target_holds %llu target_moves %llu "
+                "holds_at_boundary %llu moves_at_boundary %llu\n",
+                h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
+        const unsigned long long z[8] = {0};
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pass_counts), z, sizeof(z));
     }
 #endif
     return e;
