@@ -79,6 +79,10 @@ ABI = {
     "bisbm_tempering_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, _f64p]),
     "bisbm_tempering_get": (C.c_int, [C.c_void_p, _u32p, _f32p]),
     "bisbm_tempering_stats": (C.c_int, [C.c_void_p, _u64p, _u64p, _u64p]),
+    "bisbm_pair_scores_set": (C.c_int, [C.c_void_p, C.c_uint64, _u32p, _u32p]),
+    "bisbm_pair_scores_accumulate": (C.c_int, [C.c_void_p]),
+    "bisbm_pair_scores_reset": (C.c_int, [C.c_void_p]),
+    "bisbm_pair_scores_get": (C.c_int, [C.c_void_p, _f64p, _u64p]),
     "bisbm_get_ka_kb": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bisbm_get_ka_kb_chain": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "bisbm_agg_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -593,6 +597,38 @@ class BlockModel:
         self._check(self._L.bisbm_marginals_map(self._h, _p(out, _u32p)))
         return out
 
+    # -- pair scores (include/bisbm.h, "Posterior-predictive pair scores")
+    def pair_scores_set(self, pairs):
+        """The pairs to score: an integer array [P, 2] of (type-a node, type-b node); replaces earlier pairs and zeroes the
+        sums.  An empty array frees everything."""
+        pr = np.asarray(pairs)
+        if pr.size == 0:
+            pr = np.zeros((0, 2), dtype=np.uint32)
+        if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+            raise ValueError("pairs must be an integer array of shape (P, 2)")
+        if len(pr) and (pr.min() < 0 or pr.max() > 0xFFFFFFFF):
+            raise ValueError("a node id of a pair is outside [0, 2^32)")
+        u = np.ascontiguousarray(pr[:, 0], dtype=np.uint32)
+        v = np.ascontiguousarray(pr[:, 1], dtype=np.uint32)
+        self._check(self._L.bisbm_pair_scores_set(self._h, len(u), _p(u, _u32p), _p(v, _u32p)))
+        self.n_pairs = len(u)
+
+    def pair_scores_accumulate(self):
+        """One sample: every counted chain's term lambda(u, v) is added to every pair's sum (with replica exchange on, the
+        chains on rung 0 only)."""
+        self._check(self._L.bisbm_pair_scores_accumulate(self._h))
+
+    def pair_scores_reset(self):
+        self._check(self._L.bisbm_pair_scores_reset(self._h))
+
+    def pair_scores(self):
+        """(sum float64 [P] in the order of pair_scores_set, terms): the estimate of a pair's expected edge count is
+        sum / terms."""
+        out = np.zeros(getattr(self, "n_pairs", 0), dtype=np.float64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_pair_scores_get(self._h, _p(out, _f64p), C.byref(terms)))
+        return out, terms.value
+
     def device_layout(self):
         """(device ordinals, first chain of each device) behind this handle."""
         nd = C.c_int()
@@ -667,5 +703,5 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import ChainShard, shard_chains  # noqa: E402,F401
+from .distributed import ChainShard, numpy_pair_scores, shard_chains  # noqa: E402,F401
 from .marginalize import marginalize  # noqa: E402,F401

@@ -10,6 +10,7 @@
 //   bisbm_merge.hip      agg_merge / agg_split between anneals, chains of one handle in different shapes
 //   bisbm_align.hip      label alignment of the chains to a reference partition before their samples are pooled
 //   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
+//   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -95,11 +96,23 @@ struct TemperState {
     size_t cap_chains = 0, cap_L = 0;
 };
 
+// Pair scores (bisbm_pair_scores.hip).  The buffers belong to the engine that owns the graph on a device (a plain handle, the
+// container of shape groups, a device entry); the container of device entries keeps only `n`.  The pairs are held sorted by
+// (u, v) -- the type-a gather of the kernel then walks the label array forwards --, `order` leads back to the caller's index.
+struct PairScoreState {
+    uint64_t n = 0;               // pairs set (0: none)
+    uint64_t terms = 0;           // chain terms added to every sum since the last set / reset
+    uint32_t* d_u = nullptr;      // [n] type-a node of every pair, sorted order
+    uint32_t* d_v = nullptr;      // [n] type-b node
+    double* d_dd = nullptr;       // [n] (double)d(u) * (double)d(v)
+    double* d_sum = nullptr;      // [n] running sums, sorted order
+    double* d_part = nullptr;     // [slabs][n] partial sums of one sample
+    size_t part_cap = 0;          // doubles d_part is allocated for
+    std::vector<uint32_t> order;  // sorted position -> index in the caller's arrays
+};
+
 }  // namespace bisbm
 
-// ------------------------------------------------------------------------------------------
-// the handle
-// ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
 // the handle
 // ------------------------------------------------------------------------------------------
@@ -184,6 +197,7 @@ struct bisbm_engine {
     uint64_t counts_rows = 0;  // rows of the internal marginal buffer (n, or n rounded up to a multiple of the device count)
     bisbm::AlignState align;
     bisbm::TemperState temper;
+    bisbm::PairScoreState pairs;
 };
 
 namespace bisbm {
@@ -329,5 +343,10 @@ void temper_free(bisbm_engine* h);
 // bisbm_marginals_accumulate with the alignment on; the buffers of alignment (bisbm_destroy); bisbm_align.hip
 int align_accumulate(bisbm_engine* h, uint32_t* device_counts);
 void align_free(bisbm_engine* h);
+// replica exchange is on and some engine under `h` keeps its chains grouped by shape: BISBM_ERR_STATE with the message of the
+// marginal histogram (a group engine knows no rungs), BISBM_OK otherwise; bisbm_marginals.hip
+int refuse_rungs_over_groups(bisbm_engine* h);
+// the buffers of the pair scores (bisbm_destroy); bisbm_pair_scores.hip
+void pair_scores_free(bisbm_engine* h);
 
 }  // namespace bisbm

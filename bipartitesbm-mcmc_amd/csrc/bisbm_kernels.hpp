@@ -151,6 +151,23 @@ struct MarginalParams {
     const uint32_t* rung;  // replica exchange: only chains with rung[c] == 0 are counted; NULL: every chain
 };
 
+// Pair scores (bisbm_pair_scores.hip): one sample of the chains of one engine.  Slab s of the launch adds the terms of its chains
+// (chain c belongs to slab c / ceil(n_chains / slabs)) into part[s][pair]; pair_scores_fold then adds the slabs to the running sums.
+struct PairScoreParams {
+    uint32_t n_pairs, na, ka, kb, n_chains, slabs;
+    const uint32_t* u;   // [n_pairs] type-a node
+    const uint32_t* v;   // [n_pairs] type-b node
+    const double* dd;    // [n_pairs] (double)d(u) * (double)d(v)
+    const uint8_t* labels;
+    size_t label_stride;
+    uint32_t wide;         // two-byte labels, m read from HBM (see SweepParams::wide)
+    const int32_t* m;      // [chain][ka*kb]
+    const int32_t* m_r;    // [chain][K]
+    const uint32_t* rung;  // replica exchange: only chains with rung[c] == 0 are counted; NULL: every chain
+    double* part;          // [slabs][n_pairs]
+};
+constexpr uint32_t kPairTile = 2048;  // pairs per workgroup: 256 lanes, 8 pairs each
+
 // agg_split (blockmodel.cc:505-565): evaluation of `n_trials` random half-cuts of every block of one type, all chains
 struct SplitParams {
     const uint32_t* rowptr;
@@ -270,6 +287,12 @@ hipError_t launch_marginals(const MarginalParams& p, hipStream_t stream);
 hipError_t launch_marginal_map(const uint32_t* counts, uint32_t rows, uint32_t kmax, uint32_t first, uint32_t n, uint32_t na,
                                uint32_t ka, uint16_t* labels_out, hipStream_t stream);
 hipError_t launch_counts_add(uint32_t* a, const uint32_t* b, size_t count, hipStream_t stream);
+// dd[i] = (double)d(u[i]) * (double)d(v[i]) from the CSR row lengths
+hipError_t launch_pair_degrees(const uint32_t* rowptr, const uint32_t* u, const uint32_t* v, uint32_t n_pairs, double* dd, hipStream_t stream);
+hipError_t launch_pair_scores(const PairScoreParams& p, hipStream_t stream);
+// sum[i] += part[0][i] + ... + part[slabs - 1][i], added in slab order
+hipError_t launch_pair_scores_fold(double* sum, const double* part, uint32_t slabs, uint32_t n_pairs, hipStream_t stream);
+uint32_t pair_score_slabs(uint64_t n_pairs, uint32_t n_chains);
 hipError_t launch_log_q_probe(const Tables& tab, const int32_t* n, const int32_t* k, size_t count, double* out,
                               int fast, hipStream_t stream);
 

@@ -24,6 +24,16 @@ int single_marginals_map(bisbm_engine* h, uint32_t* labels_out) {
     return BISBM_OK;
 }
 
+int refuse_rungs_over_groups(bisbm_engine* h) {
+    if (!h->temper.L) return BISBM_OK;
+    // (a group engine knows no rungs: refused wherever the chains are grouped, on any device entry, raw or aligned)
+    bool grouped = !h->groups.empty();
+    for (bisbm_engine* d : h->devs) grouped = grouped || !d->groups.empty();
+    if (grouped)
+        return fail(h, BISBM_ERR_STATE, "replica exchange is on and the chains of this handle are grouped by shape (after bisbm_agg_merge_total): no cold-chain histogram");
+    return BISBM_OK;
+}
+
 }  // namespace bisbm
 
 extern "C" {
@@ -97,12 +107,7 @@ extern "C" {
 
 int bisbm_marginals_accumulate(bisbm_handle h, uint32_t* device_counts) {
     if (!h) return BISBM_ERR_INVALID_ARG;
-    if (h->temper.L) {  // (a group engine knows no rungs: refused wherever the chains are grouped, on any device entry, raw or aligned)
-        bool grouped = !h->groups.empty();
-        for (bisbm_engine* d : h->devs) grouped = grouped || !d->groups.empty();
-        if (grouped)
-            return fail(h, BISBM_ERR_STATE, "replica exchange is on and the chains of this handle are grouped by shape (after bisbm_agg_merge_total): no cold-chain histogram");
-    }
+    if (int rc = refuse_rungs_over_groups(h)) return rc;
     const int rc = h->align.mode == BISBM_ALIGN_REFERENCE ? align_accumulate(h, device_counts) : accumulate_plain(h, device_counts);
     if (rc == BISBM_OK && !device_counts) h->align.samples = true;
     return rc;

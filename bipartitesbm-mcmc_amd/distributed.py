@@ -105,6 +105,21 @@ class ChainShard:
             dist.all_reduce(out, op=dist.ReduceOp.SUM, group=self.group)
         return out
 
+    def pooled_pair_scores(self, model):
+        """(sum float64 [P], terms) of the pair scores over all ranks: every rank's own sums (model.pair_scores(): the chains
+        it owns) and term counts are all-reduced.  Every rank must have set the same pairs."""
+        import torch
+        dist = _dist()
+        local, terms = model.pair_scores()
+        if self.world_size == 1:
+            return local, terms
+        dev = _collective_device(self)
+        s = torch.as_tensor(local).to(dev)
+        t = torch.tensor([terms], dtype=torch.int64, device=dev)
+        dist.all_reduce(s, op=dist.ReduceOp.SUM, group=self.group)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return s.cpu().numpy(), int(t.item())
+
     def map_labels(self, local_counts, na, ka):
         """MAP block of every node from the pooled histogram: reduce_scatter by node range, argmax on
         the owned rows (ties -> lowest block, like numpy), all_gather of the labels.  Returns a tensor [n] of
@@ -170,3 +185,25 @@ def numpy_marginals(labels_by_chain, na, ka, kb):
     for row in labels_by_chain:
         np.add.at(counts, (np.arange(n), row.astype(np.int64) - base), 1)
     return counts
+
+
+def numpy_pair_scores(labels_by_chain, m_by_chain, m_r_by_chain, deg, pairs):
+    """Host restatement of one sample of the pair scores (include/bisbm.h): for every pair (u, v) the sum over the given
+    chains of ((double)d(u) * (double)d(v)) * (double)m[b_u, b_v] / ((double)m_r[b_u] * (double)m_r[b_v]), 0.0 where a degree
+    is 0, in exactly this order of f64 operations -- one chain's term equals the device's bit for bit.  The arguments are what
+    get_memberships / get_m / get_m_r return per chain (global labels, the full K x K matrix), as lists: the chains may have
+    different shapes.  `deg`: the degree of every node (multi-edges count); `pairs`: integer array [P, 2]."""
+    pairs = np.asarray(pairs).reshape(-1, 2).astype(np.int64)
+    u, v = pairs[:, 0], pairs[:, 1]
+    deg = np.asarray(deg)
+    dd = deg[u].astype(np.float64) * deg[v].astype(np.float64)
+    live = dd != 0
+    total = np.zeros(len(pairs), dtype=np.float64)
+    for labels, m, m_r in zip(labels_by_chain, m_by_chain, m_r_by_chain):
+        labels = np.asarray(labels).astype(np.int64)
+        m, m_r = np.asarray(m), np.asarray(m_r)
+        bu, bv = labels[u][live], labels[v][live]
+        term = np.zeros(len(pairs), dtype=np.float64)
+        term[live] = (dd[live] * m[bu, bv].astype(np.float64)) / (m_r[bu].astype(np.float64) * m_r[bv].astype(np.float64))
+        total += term
+    return total

@@ -261,6 +261,20 @@ public:
         accepted.assign(L - 1, 0);
         check(bisbm_tempering_stats(h_, attempted.data(), accepted.data(), &rounds));
     }
+    // pair scores (include/bisbm.h): the pairs (u of type a, v of type b), a sample of every counted chain, the sums and the
+    // number of chain terms in them (the estimate of a pair is sum / terms)
+    void pair_scores_set(const std::vector<uint32_t>& u, const std::vector<uint32_t>& v) {
+        if (u.size() != v.size()) throw std::runtime_error("pair_scores_set: u and v differ in length");
+        check(bisbm_pair_scores_set(h_, u.size(), u.data(), v.data()));
+        n_pairs_ = u.size();
+    }
+    void pair_scores_accumulate() { check(bisbm_pair_scores_accumulate(h_)); }
+    void pair_scores_reset() { check(bisbm_pair_scores_reset(h_)); }
+    std::vector<double> pair_scores(uint64_t& terms) {
+        std::vector<double> sum(n_pairs_);
+        check(bisbm_pair_scores_get(h_, sum.data(), &terms));
+        return sum;
+    }
     // the marginal estimate of README.md:49-53: every node's most frequent block, pooled over the handle's devices on the
     // devices (bisbm_marginals_map)
     uint_vec_t marginal_map_labels(size_t /*NA*/) {
@@ -282,7 +296,7 @@ private:
         KB_ = kb;
     }
     bisbm_handle h_ = nullptr;
-    size_t KA_, KB_, n_ = 0;
+    size_t KA_, KB_, n_ = 0, n_pairs_ = 0;
     uint32_t n_chains_;
     uint_vec_t memberships_;
 };

@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every.
+// --tempering, --exchange_every, --score_pairs.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -14,7 +14,9 @@
 #include <cmath>
 #include <numeric>
 #include <cstdlib>
+#include <cstdio>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <map>
 #include <memory>
@@ -46,7 +48,7 @@ const option_spec kOptions[] = {
     // engine extras
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
-    {"tempering", 0, 2},        {"exchange_every", 0, 1},
+    {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -178,6 +180,10 @@ void print_help(const char* argv0) {
                  "                                        temperatures, and only the chains at T0 are sampled.  The swap\n"
                  "                                        acceptance of every rung pair is reported on stderr.\n"
                  "  --exchange_every arg (=1)             With --tempering: sweeps between exchange rounds.\n"
+                 "  --score_pairs IN OUT                  With --marginalize: IN holds one pair `u v` per line (u of type a, v of\n"
+                 "                                        type b); every sample adds every sampled chain's expected edge count\n"
+                 "                                        between the two, and OUT receives `u v score` per pair in input order\n"
+                 "                                        (score = the mean over samples and chains, printed with %.17g).\n"
                  "  --csr_cache                           Keep a binary CSR beside the edge list (<path>.bisbm_csr, checked\n"
                  "                                        against the file's size and mtime); the text file stays the input.\n";
 }
@@ -200,6 +206,14 @@ int main(int argc, char const* argv[]) {
     }
     if (count("align") && !count("marginalize")) {
         std::cerr << "--align aligns the chains' block labels before pooling: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("score_pairs") && !count("marginalize")) {
+        std::cerr << "--score_pairs scores pairs of nodes over the samples of the chains: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("score_pairs") && var_map["score_pairs"].size() != 2) {
+        std::cerr << "Invalid --score_pairs. Two paths: the file of pairs to read and the file of scores to write.\n";
         return 1;
     }
     // replica exchange: the ladder and the exchange period are checked before anything else runs
@@ -256,6 +270,21 @@ int main(int argc, char const* argv[]) {
         NB = y[1];
         types_init.assign(NA + NB, 0);
         for (size_t i = NA; i < NA + NB; ++i) types_init[i] = 1;
+    }
+    // --score_pairs: the pairs are read and checked before any device is touched (ids as in the edge list file)
+    edge_list_t score_pairs;
+    if (count("score_pairs")) {
+        const std::string in = var_map["score_pairs"][0];
+        if (!load_edge_list(score_pairs, in)) {
+            std::cerr << "[error] --score_pairs: cannot read " << in << "\n";
+            return 1;
+        }
+        for (size_t i = 0; i < score_pairs.size(); ++i)
+            if (score_pairs[i].first >= NA || score_pairs[i].second < NA || score_pairs[i].second >= NA + NB) {
+                std::cerr << "[error] --score_pairs: pair " << i << " (" << score_pairs[i].first << " " << score_pairs[i].second
+                          << ") must name a type-a node [0, " << NA << ") and a type-b node [" << NA << ", " << NA + NB << ")\n";
+                return 1;
+            }
     }
     const std::string cooling_schedule = single("cooling_schedule", "abrupt_cool");
     const size_t sampling_steps = std::strtoull(single("sampling_steps", "1000").c_str(), nullptr, 10);
@@ -712,9 +741,18 @@ int main(int argc, char const* argv[]) {
             if (burn_in >= N) advance(burn_in / N);
             blockmodel.marginals_reset();
             if (count("align")) blockmodel.marginals_set_alignment(true);
+            if (count("score_pairs")) {  // (--reorder: the engine knows the nodes by their new ids)
+                std::vector<uint32_t> pu, pv;
+                for (auto const& pr : score_pairs) {
+                    pu.push_back(new_id.empty() ? (uint32_t)pr.first : new_id[pr.first]);
+                    pv.push_back(new_id.empty() ? (uint32_t)pr.second : new_id[pr.second]);
+                }
+                blockmodel.pair_scores_set(pu, pv);
+            }
             for (size_t sample = 0; sample < n_samples; ++sample) {
                 advance(sweeps_between);
                 blockmodel.marginals_accumulate();
+                if (!score_pairs.empty()) blockmodel.pair_scores_accumulate();
             }
             std::clog << "marginalize: burn-in " << burn_in / N << " sweeps, " << n_samples << " samples " << sweeps_between
                       << " sweep(s) apart, " << opt.n_chains << " chain(s) pooled\n";
@@ -736,6 +774,23 @@ int main(int argc, char const* argv[]) {
             }
             if (count("align"))
                 std::clog << "align: labels matched to chain " << blockmodel.marginals_reference_chain() << " (lowest description length)\n";
+            if (count("score_pairs")) {
+                const std::string out_path = var_map["score_pairs"][1];
+                std::ofstream out(out_path);
+                uint64_t terms = 0;
+                const std::vector<double> sum = score_pairs.empty() ? std::vector<double>() : blockmodel.pair_scores(terms);
+                char line[128];
+                for (size_t i = 0; i < score_pairs.size(); ++i) {
+                    std::snprintf(line, sizeof(line), "%zu %zu %.17g\n", score_pairs[i].first, score_pairs[i].second, sum[i] / (double)terms);
+                    out << line;
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --score_pairs: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "score_pairs: " << score_pairs.size() << " pair(s), " << terms << " chain term(s) each -> " << out_path << "\n";
+            }
             emit_labels(blockmodel.marginal_map_labels(NA));
         } catch (const std::exception& e) {
             std::cerr << e.what() << "\n";

@@ -17,7 +17,7 @@ import numpy as np
 
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
-                return_counts=None, align=False, tempering=None, exchange_every=1):
+                return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -40,7 +40,11 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     consecutive global ids, burn-in and the gaps between samples run through model.tempering_run(sweeps, exchange_every), and
     only the chains on rung 0 (T0) are counted -- over ranks each rank histograms its own cold chains, and the aligned reference
     is the lowest-description-length rung-0 chain.  Tempering is turned on for the run (rungs and statistics reset) and stays
-    on: model.tempering_stats() reports the swaps afterwards."""
+    on: model.tempering_stats() reports the swaps afterwards.
+    `score_pairs`: an integer array [P, 2] of (type-a node, type-b node) pairs (include/bisbm.h, "Posterior-predictive pair
+    scores"): set, with zeroed sums, before the first sample, and every sample also adds every counted chain's term to every
+    pair's sum (with `tempering` the chains on rung 0 only).  The return value does not change: model.pair_scores() gives
+    (sum, terms) afterwards, shard.pooled_pair_scores(model) the same over ranks."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
@@ -54,6 +58,9 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         advance = model.run_sweeps
     if burn_in_sweeps > 0:
         advance(burn_in_sweeps)
+    if score_pairs is not None:
+        model.pair_scores_set(score_pairs)
+        model.pair_scores_reset()
     if device_counts is None and not multi:
         # one rank, no caller buffer: the library's own histogram
         model.marginals_reset()
@@ -63,6 +70,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             if sampling_frequency_sweeps > 0:
                 advance(sampling_frequency_sweeps)
             model.marginals_accumulate(None)
+            if score_pairs is not None:
+                model.pair_scores_accumulate()
         counts = model.marginals_get().astype(np.int64)
         base = np.where(np.arange(n) >= model.na, model.KA, 0)
         return (counts.argmax(axis=1) + base).astype(np.uint32), (counts if return_counts else None)
@@ -88,6 +97,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         if sampling_frequency_sweeps > 0:
             advance(sampling_frequency_sweeps)
         model.marginals_accumulate(device_counts.data_ptr())  # adds into the tensor, on the device
+        if score_pairs is not None:
+            model.pair_scores_accumulate()
     if not multi:
         from .distributed import _argmax_first
         arg = _argmax_first(device_counts)

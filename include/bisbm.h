@@ -23,7 +23,8 @@ extern "C" {
 
 /* 2: bisbm_get_ka_kb_chain; KA + KB above 256 (wide mode); handles whose chains differ in shape.
  * 3: bisbm_check_shape; several devices behind one handle (bisbm_create_multi); bisbm_last_pass_steps; later additions: label
- *    alignment (bisbm_marginals_set_alignment ...), replica exchange (bisbm_tempering_*).  Additions only. */
+ *    alignment (bisbm_marginals_set_alignment ...), replica exchange (bisbm_tempering_*), pair scores (bisbm_pair_scores_*).
+ *    Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -238,6 +239,31 @@ int bisbm_tempering_stats(bisbm_handle h, uint64_t *attempted, uint64_t *accepte
  * argmax on the owner of the range -> ncclAllGather of the labels; peer copies + an add kernel where RCCL cannot serve (a
  * device listed twice, librccl.so missing, BISBM_POOL=p2p). */
 int bisbm_marginals_map(bisbm_handle h, uint32_t *labels_out /* n, host */);
+
+/* Posterior-predictive pair scores pooled over chains (no reference counterpart: the reference keeps one partition and scores
+ * nothing).  For a pair (u, v), u of type a (u < na) and v of type b (na <= v < n), one chain with labels b, block matrix m and
+ * block degree sums m_r contributes the DC-SBM's expected number of edges between the two given its partition,
+ *     lambda(u, v) = ((double)d(u) * (double)d(v)) * (double)m[b_u][b_v] / ((double)m_r[b_u] * (double)m_r[b_v])
+ * (d = length of the node's CSR row, multi-edges count; f64, in exactly this order of operations), and 0.0 when d(u) or d(v)
+ * is 0.  Over all na * nb pairs the terms of one chain add up to the number of edges.  A SAMPLE (bisbm_pair_scores_accumulate)
+ * adds, for every pair, the term of every counted chain to a running f64 sum and the number of counted chains to `terms`;
+ * counted = every chain, or with replica exchange on only the chains on rung 0.  The estimate is sum / terms.  The term does
+ * not depend on how a chain numbers its blocks, so nothing is aligned and chains of different shapes (after
+ * bisbm_agg_merge_total), wide handles, both RNG modes and several devices are all served; replica exchange over chains grouped
+ * by shape is BISBM_ERR_STATE, as for the marginal histogram.  The sums are added without floating-point atomics, in an order
+ * fixed by the pairs, the chain count and the shapes: the same handle and the same calls give the same bits.  Sums and `terms`
+ * survive merges, splits, the switch between byte and two-byte labels and regrouping by shape.
+ * set: uploads n_pairs pairs (they may repeat and may be edges), replacing earlier ones and zeroing sums and terms; n_pairs = 0
+ *   frees everything.  A u outside [0, na) or a v outside [na, n) is BISBM_ERR_INVALID_ARG, bisbm_last_error names the first
+ *   offending index, and the earlier pairs stay in place.
+ * accumulate: one sample; BISBM_ERR_STATE before bisbm_init / bisbm_shuffle or without pairs.
+ * reset: zeroes sums and terms, keeps the pairs.
+ * get: sum_out[n_pairs] in the caller's order (over several devices: the per-device sums added on the host in device order) and
+ *   terms; either pointer may be NULL. */
+int bisbm_pair_scores_set(bisbm_handle h, uint64_t n_pairs, const uint32_t *u, const uint32_t *v);
+int bisbm_pair_scores_accumulate(bisbm_handle h);
+int bisbm_pair_scores_reset(bisbm_handle h);
+int bisbm_pair_scores_get(bisbm_handle h, double *sum_out /* n_pairs, host */, uint64_t *terms_out);
 
 /* blockmodel_t::agg_merge(engine, diff_a, diff_b, nm) (blockmodel.hh, blockmodel.cc:109-206; call sites
  * mcmc_main.cc:385,429,434,446): merge diff_a type-a and diff_b type-b blocks in every chain -- nm proposals per
