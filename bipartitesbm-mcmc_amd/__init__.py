@@ -83,6 +83,9 @@ ABI = {
     "bisbm_pair_scores_accumulate": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_reset": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_get": (C.c_int, [C.c_void_p, _f64p, _u64p]),
+    "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
+    "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
+    "bisbm_partition_modes": (C.c_int, [C.c_uint32, _f64p, C.c_double, _u32p, _u32p, _u32p]),
     "bisbm_get_ka_kb": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bisbm_get_ka_kb_chain": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "bisbm_agg_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -629,6 +632,49 @@ class BlockModel:
         self._check(self._L.bisbm_pair_scores_get(self._h, _p(out, _f64p), C.byref(terms)))
         return out, terms.value
 
+    # -- partition distances and posterior modes (include/bisbm.h, "Partition distances and posterior modes")
+    def partition_distances(self, chains=None):
+        """(vi float64 [m, m], H float64 [m]): the variation of information (nats) between every two of the selected chains'
+        partitions and each one's partition entropy, in the order of `chains` (None: all chains).  Reads labels only."""
+        if chains is None:
+            sel, m, ptr = None, self.n_chains, None
+        else:
+            sel = np.ascontiguousarray(chains, dtype=np.uint32).ravel()
+            m, ptr = len(sel), _p(sel, _u32p)
+        vi = np.zeros((m, m), dtype=np.float64)
+        H = np.zeros(m, dtype=np.float64)
+        self._check(self._L.bisbm_partition_distances(self._h, m, ptr, _p(vi, _f64p), _p(H, _f64p)))
+        return vi, H
+
+    def partition_contingency(self, c, d):
+        """uint32 [K_c, K_d]: how many nodes have label r in chain c and label s in chain d (global labels)."""
+        c, d = int(c), int(d)
+        for x in (c, d):
+            if not 0 <= x < self.n_chains:
+                raise BisbmError(BISBM_ERR_INVALID_ARG, "chain %d out of range: the model has %d chains" % (x, self.n_chains))
+        out = np.zeros((sum(self.ka_kb(c)), sum(self.ka_kb(d))), dtype=np.uint32)
+        self._check(self._L.bisbm_partition_contingency(self._h, int(c), int(d), _p(out, _u32p)))
+        return out
+
+    def partition_modes(self, threshold, chains=None):
+        """The selected chains grouped into modes: single linkage over VI <= threshold (the caller's resolution: no default).
+        `chains` None: all chains, or with replica exchange on the chains on rung 0.  Returns a dict: `chains` (the selection),
+        `mode` (per selected chain), `medoids` (chain index per mode), `weights` (each mode's share of the selection),
+        `lowest_entropy` (per mode the member chain of the least entropy()), `vi` (the matrix of the selection).
+        The chains of this model only: pooling over ranks (ChainShard) is not done here."""
+        if chains is None:
+            sel = np.arange(self.n_chains, dtype=np.uint32)
+            if self.tempering_L:
+                sel = sel[self.tempering_state()[0] == 0]
+        else:
+            sel = np.ascontiguousarray(chains, dtype=np.uint32).ravel()
+        vi, _ = self.partition_distances(sel)
+        mode, med = partition_modes(vi, threshold)
+        S = self.entropy()[sel]
+        low = np.array([sel[mode == k][np.argmin(S[mode == k])] for k in range(len(med))], dtype=np.uint32)
+        return {"chains": sel, "mode": mode, "medoids": sel[med], "weights": np.bincount(mode, minlength=len(med)) / len(sel),
+                "lowest_entropy": low, "vi": vi}
+
     def device_layout(self):
         """(device ordinals, first chain of each device) behind this handle."""
         nd = C.c_int()
@@ -658,6 +704,22 @@ def align_assignment(table):
     if rc != BISBM_OK:
         raise BisbmError(rc, (lib().bisbm_last_error(None) or b"").decode())
     return perm, tot.value
+
+
+def partition_modes(vi, threshold):
+    """Modes of a symmetric VI matrix [m, m] on the host (bisbm_partition_modes): single linkage over VI <= threshold ->
+    (mode uint32 [m], numbered by lowest member; medoids uint32 [n_modes], indices into the matrix).  Needs no device."""
+    v = np.ascontiguousarray(vi, dtype=np.float64)
+    if v.ndim != 2 or v.shape[0] != v.shape[1]:
+        raise ValueError("vi must be a square matrix")
+    m = v.shape[0]
+    mode = np.zeros(max(m, 1), dtype=np.uint32)
+    med = np.zeros(max(m, 1), dtype=np.uint32)
+    n_modes = C.c_uint32()
+    rc = lib().bisbm_partition_modes(m, _p(v, _f64p), float(threshold), _p(mode, _u32p), _p(med, _u32p), C.byref(n_modes))
+    if rc != BISBM_OK:
+        raise BisbmError(rc, (lib().bisbm_last_error(None) or b"").decode())
+    return mode[:m], med[: n_modes.value]
 
 
 def validate_ladder(ladder):

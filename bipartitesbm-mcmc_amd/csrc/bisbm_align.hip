@@ -369,20 +369,6 @@ int pick_reference(bisbm_engine* h, uint32_t ka, uint32_t kb) {
     return BISBM_OK;
 }
 
-// the engine that runs chain `chain` of the handle, and the chain's index there
-bisbm_engine* leaf_of_chain(bisbm_engine* h, uint32_t chain, uint32_t* local) {
-    if (!h->devs.empty()) {
-        bisbm_engine* d = h->devs[dev_of_chain(h, chain, &chain)];
-        return leaf_of_chain(d, chain, local);
-    }
-    if (!h->groups.empty()) {
-        *local = h->where[chain].second;
-        return h->groups[h->where[chain].first];
-    }
-    *local = chain;
-    return h;
-}
-
 // the host solver (include/bisbm.h): the Jonker-Volgenant / Hungarian shortest-augmenting-path form, 1-based with column 0 as
 // the virtual start; the device kernel above runs the same steps
 void solve_assignment(uint32_t K, const uint32_t* C, uint32_t* perm, uint64_t* total) {
@@ -431,6 +417,20 @@ void solve_assignment(uint32_t K, const uint32_t* C, uint32_t* perm, uint64_t* t
 }  // namespace
 
 namespace bisbm {
+
+// the engine that runs chain `chain` of the handle, and the chain's index there
+bisbm_engine* leaf_of_chain(bisbm_engine* h, uint32_t chain, uint32_t* local) {
+    if (!h->devs.empty()) {
+        bisbm_engine* d = h->devs[dev_of_chain(h, chain, &chain)];
+        return leaf_of_chain(d, chain, local);
+    }
+    if (!h->groups.empty()) {
+        *local = h->where[chain].second;
+        return h->groups[h->where[chain].first];
+    }
+    *local = chain;
+    return h;
+}
 
 int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     if (!h->devs.empty() && device_counts)

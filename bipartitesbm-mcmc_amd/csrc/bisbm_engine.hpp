@@ -11,6 +11,7 @@
 //   bisbm_align.hip      label alignment of the chains to a reference partition before their samples are pooled
 //   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
+//   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -111,6 +112,18 @@ struct PairScoreState {
     std::vector<uint32_t> order;  // sorted position -> index in the caller's arrays
 };
 
+// Partition distances (bisbm_partition.hip).  The scratch of the calls, on the engine whose device computes (a plain handle, the
+// container of shape groups, the first device entry); nothing of it outlives a call in meaning, it is only kept to be reused.
+struct PartitionState {
+    void* d_desc = nullptr;       // [selection] row pointer, ka, kb of every selected chain
+    void* d_tiles = nullptr;      // [tiles] (row tile, column tile)
+    double* d_A = nullptr;        // [selection] sum_r a_r ln a_r
+    double* d_snn = nullptr;      // [selection][selection] sum_rs n_rs ln n_rs of every pair i < j
+    uint32_t* d_tab = nullptr;    // few pairs: the integer tables of one launch
+    uint8_t* d_stage = nullptr;   // label rows of selected chains that live on another device
+    size_t desc_cap = 0, tiles_cap = 0, A_cap = 0, snn_cap = 0, tab_cap = 0, stage_cap = 0;  // bytes
+};
+
 }  // namespace bisbm
 
 // ------------------------------------------------------------------------------------------
@@ -198,6 +211,7 @@ struct bisbm_engine {
     bisbm::AlignState align;
     bisbm::TemperState temper;
     bisbm::PairScoreState pairs;
+    bisbm::PartitionState partition;
 };
 
 namespace bisbm {
@@ -348,5 +362,9 @@ void align_free(bisbm_engine* h);
 int refuse_rungs_over_groups(bisbm_engine* h);
 // the buffers of the pair scores (bisbm_destroy); bisbm_pair_scores.hip
 void pair_scores_free(bisbm_engine* h);
+// the scratch of the partition distances (bisbm_destroy); bisbm_partition.hip
+void partition_free(bisbm_engine* h);
+// the engine that runs chain `chain` of the handle, and the chain's index there; bisbm_align.hip
+bisbm_engine* leaf_of_chain(bisbm_engine* h, uint32_t chain, uint32_t* local);
 
 }  // namespace bisbm

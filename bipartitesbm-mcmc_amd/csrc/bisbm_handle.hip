@@ -48,6 +48,7 @@ void free_all(bisbm_engine* h) {
     align_free(h);
     temper_free(h);
     pair_scores_free(h);
+    partition_free(h);
     if (h->root) {  // a sub-engine: the graph and the tables belong to the handle it serves
         h->d_rowptr = nullptr, h->d_col = nullptr, h->d_lgamma = nullptr, h->d_logtab = nullptr, h->d_q = nullptr;
     }

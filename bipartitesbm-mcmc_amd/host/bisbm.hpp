@@ -275,6 +275,28 @@ public:
         check(bisbm_pair_scores_get(h_, sum.data(), &terms));
         return sum;
     }
+    // rung of every chain under replica exchange (bisbm_tempering_get)
+    std::vector<uint32_t> tempering_rungs() {
+        std::vector<uint32_t> rung(n_chains_);
+        check(bisbm_tempering_get(h_, rung.data(), nullptr));
+        return rung;
+    }
+    // partition distances and modes (include/bisbm.h): the VI matrix of the listed chains (row-major, in their order), and its
+    // grouping by single linkage at `threshold` -- mode per listed chain, medoid per mode (positions in the list)
+    std::vector<double> partition_distances(const std::vector<uint32_t>& chains) {
+        std::vector<double> vi(chains.size() * chains.size());
+        check(bisbm_partition_distances(h_, (uint32_t)chains.size(), chains.data(), vi.data(), nullptr));
+        return vi;
+    }
+    static void partition_modes(const std::vector<double>& vi, size_t m, double threshold, std::vector<uint32_t>& mode,
+                                std::vector<uint32_t>& medoids) {
+        mode.assign(m, 0);
+        medoids.assign(m, 0);
+        uint32_t n_modes = 0;
+        if (bisbm_partition_modes((uint32_t)m, vi.data(), threshold, mode.data(), medoids.data(), &n_modes) != BISBM_OK)
+            throw std::runtime_error(std::string("bisbm: ") + bisbm_last_error(nullptr));
+        medoids.resize(n_modes);
+    }
     // the marginal estimate of README.md:49-53: every node's most frequent block, pooled over the handle's devices on the
     // devices (bisbm_marginals_map)
     uint_vec_t marginal_map_labels(size_t /*NA*/) {

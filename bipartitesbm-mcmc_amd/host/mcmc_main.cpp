@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --score_pairs.
+// --tempering, --exchange_every, --score_pairs, --modes.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -49,6 +49,7 @@ const option_spec kOptions[] = {
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
     {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
+    {"modes", 0, 2},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -184,6 +185,11 @@ void print_help(const char* argv0) {
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
                  "                                        (score = the mean over samples and chains, printed with %.17g).\n"
+                 "  --modes OUT THRESHOLD                 With --marginalize: after the last sample the sampled chains' partitions\n"
+                 "                                        are compared (variation of information, nats) and grouped into modes:\n"
+                 "                                        chains joined by a path of pairs with VI <= THRESHOLD share a mode.  OUT\n"
+                 "                                        receives `chain mode VI-to-the-mode's-medoid` per sampled chain; the\n"
+                 "                                        modes' sizes, shares and medoids are reported on stderr.\n"
                  "  --csr_cache                           Keep a binary CSR beside the edge list (<path>.bisbm_csr, checked\n"
                  "                                        against the file's size and mtime); the text file stays the input.\n";
 }
@@ -215,6 +221,24 @@ int main(int argc, char const* argv[]) {
     if (count("score_pairs") && var_map["score_pairs"].size() != 2) {
         std::cerr << "Invalid --score_pairs. Two paths: the file of pairs to read and the file of scores to write.\n";
         return 1;
+    }
+    double modes_threshold = 0.;
+    if (var_map.count("modes") && !count("marginalize")) {
+        std::cerr << "--modes groups the sampled chains' partitions into modes: it needs --marginalize.\n";
+        return 1;
+    }
+    if (var_map.count("modes")) {
+        if (var_map["modes"].size() != 2) {
+            std::cerr << "Invalid --modes. Two arguments: the file to write and the VI threshold (nats) that joins two chains.\n";
+            return 1;
+        }
+        const std::string tok = var_map["modes"][1];
+        char* end = nullptr;
+        modes_threshold = std::strtod(tok.c_str(), &end);
+        if (tok.empty() || *end != '\0' || !std::isfinite(modes_threshold) || !(modes_threshold >= 0.)) {
+            std::cerr << "Invalid --modes. The threshold must be a finite number >= 0 (nats), e.g. --modes modes.txt 0.05.\n";
+            return 1;
+        }
     }
     // replica exchange: the ladder and the exchange period are checked before anything else runs
     std::vector<float> ladder;
@@ -790,6 +814,40 @@ int main(int argc, char const* argv[]) {
                     return 1;
                 }
                 std::clog << "score_pairs: " << score_pairs.size() << " pair(s), " << terms << " chain term(s) each -> " << out_path << "\n";
+            }
+            if (var_map.count("modes")) {  // (a partition's distance to another does not depend on the node numbering: --reorder is fine)
+                std::vector<uint32_t> sel;
+                const std::vector<uint32_t> rung = ladder.empty() ? std::vector<uint32_t>(opt.n_chains, 0) : blockmodel.tempering_rungs();
+                for (uint32_t c = 0; c < opt.n_chains; ++c)
+                    if (rung[c] == 0) sel.push_back(c);
+                const size_t m = sel.size();
+                const std::vector<double> vi = blockmodel.partition_distances(sel);
+                std::vector<uint32_t> mode, medoids;
+                blockmodel_t::partition_modes(vi, m, modes_threshold, mode, medoids);
+                const std::vector<double> dl = blockmodel.entropy_all();
+                const std::string out_path = var_map["modes"][0];
+                std::ofstream out(out_path);
+                char line[128];
+                for (size_t i = 0; i < m; ++i) {
+                    std::snprintf(line, sizeof(line), "%u %u %.17g\n", opt.first_chain_id + sel[i], mode[i], vi[i * m + medoids[mode[i]]]);
+                    out << line;
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --modes: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "modes: " << medoids.size() << "\n";
+                for (size_t k = 0; k < medoids.size(); ++k) {
+                    size_t size = 0, low = m;
+                    for (size_t i = 0; i < m; ++i)
+                        if (mode[i] == k) {
+                            ++size;
+                            if (low == m || dl[sel[i]] < dl[sel[low]]) low = i;
+                        }
+                    std::clog << "mode " << k << ": " << size << " chain(s), share " << (double)size / (double)m << ", medoid chain "
+                              << opt.first_chain_id + sel[medoids[k]] << ", lowest description length chain " << opt.first_chain_id + sel[low] << "\n";
+                }
             }
             emit_labels(blockmodel.marginal_map_labels(NA));
         } catch (const std::exception& e) {

@@ -1,0 +1,36 @@
+"""How many different answers did the chains find?  64 chains sample partitions of the shipped 1000-node data set from
+independent shuffles; their partitions are compared pair by pair on the device (variation of information, in nats: include/bisbm.h,
+"Partition distances and posterior modes") and grouped into modes: chains joined by a path of pairs with VI <= the threshold share
+a mode.  The threshold is the caller's resolution; here a tenth of the mean partition entropy."""
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+bisbm = importlib.import_module("bipartitesbm-mcmc_amd")
+
+a, b = bisbm.load_edge_list(os.path.join(ROOT, "tests", "golden", "bisbm-n_1000-ka_4-kb_6.edgelist"))
+na = nb = 500
+adj = bisbm.edge_to_adj((a, b), na + nb)
+start = np.concatenate([np.arange(na) * 4 // na, 4 + np.arange(nb) * 6 // nb])
+model = bisbm.BlockModel(start, [0] * na + [1] * nb, 10, 4, 6, 1.0, adj, n_chains=64, rng="philox", seed=1)
+model.shuffle_bisbm()
+model.run_sweeps(200)
+
+vi, H = model.partition_distances()
+threshold = 0.1 * H.mean()
+found = model.partition_modes(threshold)
+S = model.entropy()
+print("64 chains, mean partition entropy %.3f nats, VI between chains %.3f .. %.3f, threshold %.3f" % (H.mean(), vi[vi > 0].min() if (vi > 0).any() else 0.0, vi.max(), threshold))
+print("modes: %d" % len(found["medoids"]))
+for k, (medoid, weight, low) in enumerate(zip(found["medoids"], found["weights"], found["lowest_entropy"])):
+    print("mode %d: share %.3f, medoid chain %d, lowest description length chain %d (%.1f)" % (k, weight, medoid, low, S[low]))
+# the table behind one distance: how the blocks of the two most different chains overlap
+c, d = np.unravel_index(np.argmax(vi), vi.shape)
+print("chains %d and %d, VI %.3f, contingency table:" % (c, d, vi[c, d]))
+print(model.partition_contingency(c, d))
+assert (vi == vi.T).all() and (np.diag(vi) == 0).all() and abs(found["weights"].sum() - 1) < 1e-12
+assert model.partition_contingency(c, d).sum() == na + nb

@@ -265,6 +265,48 @@ int bisbm_pair_scores_accumulate(bisbm_handle h);
 int bisbm_pair_scores_reset(bisbm_handle h);
 int bisbm_pair_scores_get(bisbm_handle h, double *sum_out /* n_pairs, host */, uint64_t *terms_out);
 
+/* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
+ * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
+ * chains' partitions on the device, and a small deterministic grouping on the host.
+ * Labels: chains c and d have global labels over the n nodes, type-a blocks 0 .. ka-1, type-b blocks ka .. ka+kb-1, each chain
+ * with its own ka, kb (chains of different shapes are compared as they are).
+ * Contingency counts: n_rs = #{v : b^c_v = r and b^d_v = s}, a_r = sum_s n_rs, b_s = sum_r n_rs; cells that mix the two types
+ * are zero by construction.
+ * Variation of information, in nats: VI(c, d) = ( sum_r a_r ln a_r + sum_s b_s ln b_s - 2 sum_rs n_rs ln n_rs ) / n, with
+ * 0 ln 0 = 0, all arithmetic in f64; a rounding result below 0 is returned as 0.0; VI(c, c) is exactly 0.0; the matrix is
+ * exactly symmetric (each pair is computed once and mirrored).
+ * Partition entropy: H(c) = ln n - ( sum_r a_r ln a_r ) / n.  (NMI follows from VI and the two entropies.)
+ * The counts are integers and do not depend on the order of the adds; each of the three sums is added in an order fixed by the
+ * selection and the shapes (one wavefront per table: lane l adds cells l, l + 64, ... in turn, then a butterfly over the
+ * lanes), so the same handle and the same call give the same bits.
+ * Modes: a pure host function of a symmetric m x m matrix and a threshold tau >= 0.  i and j are in one mode when a path of
+ * pairs with VI <= tau joins them (single linkage); modes are numbered by their lowest selected index; the medoid of a mode is
+ * the member with the least sum of VI to the other members (ties -> the lowest index).  tau has no default: it is the caller's
+ * resolution.
+ *
+ * The calls read the chains' labels only: random streams, running sums, the marginal histogram and the pair scores are left
+ * untouched.  Served: both RNG modes, chains grouped by shape after bisbm_agg_merge_total, several devices behind one handle
+ * (the first device computes; the label rows of selected chains on other devices are copied to it, peer copy or through the
+ * host; the result equals a single-device handle's bit for bit), replica exchange on (every selected chain is compared
+ * whatever its rung).  Refused: byte labels only (a wide handle, more than 256 blocks: BISBM_ERR_UNSUPPORTED); BISBM_ERR_STATE
+ * before bisbm_init / bisbm_shuffle; BISBM_ERR_INVALID_ARG for a chain out of range or listed twice (bisbm_last_error names it).
+ * The tables of all pairs are never held together.  Device scratch of a call with m selected chains, the largest shape among
+ * them kaM + kbM: 16 m bytes of descriptors, 8 m^2 + 8 m bytes of sums, 8 bytes per tile of chain pairs (a tile is up to 4 x 4
+ * chains), n rounded up to 256 bytes per selected chain that lives on another device, and -- only when the pairs are too few to
+ * fill the device with one tile per workgroup, or a table does not fit the LDS -- integer tables of 4 (kaM^2 + kbM^2) bytes per
+ * pair for as many tiles as fit 256 MiB (at least one), run in as many launches as that takes.  Scratch that cannot be
+ * allocated is BISBM_ERR_HIP with the size in the message; nothing is skipped or subsampled.
+ *
+ * distances: chains = NULL selects all chains (n_sel must be n_chains).  vi_out[n_sel * n_sel] and h_out[n_sel] in the order
+ *   of the selection; either may be NULL.
+ * contingency: the table of one pair, (ka_c + kb_c) x (ka_d + kb_d), row-major, indexed by global labels.
+ * modes: mode_out[m]; medoid_out (may be NULL) m entries of which the first *n_modes_out are used, as indices 0 .. m-1.
+ *   BISBM_ERR_INVALID_ARG for m = 0, a negative or NaN threshold, a NaN or asymmetric entry.  Needs no device. */
+int bisbm_partition_distances(bisbm_handle h, uint32_t n_sel, const uint32_t *chains, double *vi_out, double *h_out);
+int bisbm_partition_contingency(bisbm_handle h, uint32_t c, uint32_t d, uint32_t *table_out);
+int bisbm_partition_modes(uint32_t m, const double *vi, double threshold, uint32_t *mode_out, uint32_t *medoid_out,
+                          uint32_t *n_modes_out);
+
 /* blockmodel_t::agg_merge(engine, diff_a, diff_b, nm) (blockmodel.hh, blockmodel.cc:109-206; call sites
  * mcmc_main.cc:385,429,434,446): merge diff_a type-a and diff_b type-b blocks in every chain -- nm proposals per
  * block (single_block_change :639-669), lowest merge dS first (compute_dS :335-372), blocks renumbered in the
