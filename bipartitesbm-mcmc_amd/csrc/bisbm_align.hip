@@ -257,77 +257,41 @@ hipError_t launch_marginals_aligned(const MarginalParams& p, const uint8_t* perm
 
 // ---- host side --------------------------------------------------------------------------------------------------------
 
-// the engines that run kernels under a handle (a plain handle; its groups; the device entries and their groups)
-template <class F>
-int each_leaf(bisbm_engine* h, F&& f) {
-    if (!h->devs.empty())
-        return on_devices(h, [&](bisbm_engine* d, size_t) { return each_leaf(d, f); });
-    if (!h->groups.empty()) return each_group(h, [&](bisbm_engine* g) { return f(g); });
-    return f(h);
-}
-
-bool any_wide(bisbm_engine* h) {
-    bool w = false;
-    for (bisbm_engine* d : h->devs) w = w || any_wide(d);
-    for (bisbm_engine* g : h->groups) w = w || g->wide;
-    return w || (h->devs.empty() && h->groups.empty() && h->wide);
-}
-
-// the block counts all chains of the handle share (BISBM_ERR_STATE when they differ)
-int shared_shape(bisbm_engine* h, uint32_t* ka, uint32_t* kb) {
-    if (!h->devs.empty()) return multi_common_shape(h, ka, kb);
-    if (!h->groups.empty() && !common_shape(h))
-        return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: no common marginal histogram");
-    *ka = h->ka, *kb = h->kb;
-    return BISBM_OK;
-}
-
-template <class T>
-int grow(bisbm_engine* h, T** p, size_t* cap, size_t count) {
-    if (*p && *cap >= count) return BISBM_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIPCHK(h, dalloc(p, count));
-    *cap = count;
-    return BISBM_OK;
-}
-
 // one aligned sample of the chains of a kernel-running engine e into counts; `top` holds the reference
 int align_leaf(bisbm_engine* e, const AlignState& top, uint32_t* counts) {
     AlignState& a = e->align;
     HIPCHK(e, hipSetDevice(e->device));
     const uint32_t ka = e->ka, kb = e->kb, K = ka + kb, C = e->n_chains;
     const size_t T = (size_t)ka * ka + (size_t)kb * kb;
-    if (!a.d_ref) HIPCHK(e, dalloc(&a.d_ref, e->label_stride));
+    RESERVE(e, a.d_ref, e->label_stride);
     if (a.uploaded != top.serial) {
         std::vector<uint8_t> ref(e->label_stride, 0);
         for (uint64_t v = 0; v < e->n; ++v) ref[v] = (uint8_t)top.ref[v];
-        HIPCHK(e, hipMemcpyAsync(a.d_ref, ref.data(), ref.size(), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(a.d_ref.get(), ref.data(), ref.size(), hipMemcpyHostToDevice, e->stream));
         HIPCHK(e, hipStreamSynchronize(e->stream));
         a.uploaded = top.serial;
     }
     a.have_perm = false;
-    if (int rc = grow(e, &a.d_tab, &a.tab_cap, C * T)) return rc;
-    if (int rc = grow(e, &a.d_perm, &a.perm_cap, (size_t)C * K)) return rc;
-    if (int rc = grow(e, &a.d_tot, &a.tot_cap, (size_t)C * 2)) return rc;
-    HIPCHK(e, hipMemsetAsync(a.d_tab, 0, sizeof(uint32_t) * C * T, e->stream));
+    RESERVE(e, a.d_tab, C * T);
+    RESERVE(e, a.d_perm, (size_t)C * K);
+    RESERVE(e, a.d_tot, (size_t)C * 2);
+    HIPCHK(e, hipMemsetAsync(a.d_tab.get(), 0, sizeof(uint32_t) * C * T, e->stream));
     OverlapParams op{};
     op.labels = e->d_labels;
     op.label_stride = e->label_stride;
-    op.ref = a.d_ref;
+    op.ref = a.d_ref.get();
     op.n = (uint32_t)e->n;
     op.na = (uint32_t)e->na;
     op.ka = ka;
     op.kb = kb;
-    op.tab = a.d_tab;
+    op.tab = a.d_tab.get();
     HIPCHK(e, launch_overlap(op, C, e->stream));
     AssignParams ap{};
-    ap.tab = a.d_tab;
+    ap.tab = a.d_tab.get();
     ap.ka = ka;
     ap.kb = kb;
-    ap.perm = a.d_perm;
-    ap.tot = a.d_tot;
+    ap.perm = a.d_perm.get();
+    ap.tot = a.d_tot.get();
     hipLaunchKernelGGL(align_assign_kernel, dim3(C, 2), dim3(64), 0, e->stream, ap);
     HIPCHK(e, hipGetLastError());
     MarginalParams mp{};
@@ -339,8 +303,8 @@ int align_leaf(bisbm_engine* e, const AlignState& top, uint32_t* counts) {
     mp.labels = e->d_labels;
     mp.label_stride = e->label_stride;
     mp.counts = counts;
-    mp.rung = e->temper.L ? e->temper.d_rung : nullptr;  // replica exchange: the cold chains only
-    HIPCHK(e, launch_marginals_aligned(mp, a.d_perm, K, e->stream));
+    mp.rung = e->temper.L ? e->temper.d_rung.get() : nullptr;  // replica exchange: the cold chains only
+    HIPCHK(e, launch_marginals_aligned(mp, a.d_perm.get(), K, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     a.have_perm = true, a.perm_ka = ka, a.perm_kb = kb;
     return BISBM_OK;
@@ -418,20 +382,6 @@ void solve_assignment(uint32_t K, const uint32_t* C, uint32_t* perm, uint64_t* t
 
 namespace bisbm {
 
-// the engine that runs chain `chain` of the handle, and the chain's index there
-bisbm_engine* leaf_of_chain(bisbm_engine* h, uint32_t chain, uint32_t* local) {
-    if (!h->devs.empty()) {
-        bisbm_engine* d = h->devs[dev_of_chain(h, chain, &chain)];
-        return leaf_of_chain(d, chain, local);
-    }
-    if (!h->groups.empty()) {
-        *local = h->where[chain].second;
-        return h->groups[h->where[chain].first];
-    }
-    *local = chain;
-    return h;
-}
-
 int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     if (!h->devs.empty() && device_counts)
         return fail(h, BISBM_ERR_UNSUPPORTED, "a handle over several devices accumulates into its own buffers (device_counts must be NULL); bisbm_marginals_map pools them");
@@ -442,9 +392,7 @@ int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     if (!device_counts) {
         // (as without the alignment: a histogram of other block counts is started afresh)
         bool stale = false;
-        if (h->devs.empty())
-            stale = !h->d_counts || h->counts_cols != std::max(ka, kb);
-        for (bisbm_engine* d : h->devs) stale = stale || !d->d_counts || d->counts_cols != std::max(ka, kb);
+        for (bisbm_engine* d : device_entries(h)) stale = stale || !d->d_counts || d->counts_cols != std::max(ka, kb);
         if (stale)
             if (int rc = bisbm_marginals_reset(h)) return rc;
     }
@@ -457,24 +405,8 @@ int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     }
     if (!a.has_ref)
         if (int rc = pick_reference(h, ka, kb)) return rc;
-    if (!h->devs.empty())
-        return on_devices(h, [&](bisbm_engine* d, size_t) {
-            return d->groups.empty() ? align_leaf(d, a, d->d_counts) : each_group(d, [&](bisbm_engine* g) { return align_leaf(g, a, d->d_counts); });
-        });
-    uint32_t* counts = device_counts ? device_counts : h->d_counts;
-    if (!h->groups.empty()) return each_group(h, [&](bisbm_engine* g) { return align_leaf(g, a, counts); });
-    return align_leaf(h, a, counts);
-}
-
-void align_free(bisbm_engine* h) {
-    AlignState& a = h->align;
-    void* ptrs[] = {a.d_ref, a.d_tab, a.d_perm, a.d_tot};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    a.d_ref = nullptr, a.d_tab = nullptr, a.d_perm = nullptr, a.d_tot = nullptr;
-    a.tab_cap = a.perm_cap = a.tot_cap = 0;
-    a.uploaded = 0;
-    a.have_perm = false;
+    // every leaf counts into the histogram of its device entry (a group's `root`), or into the caller's
+    return each_leaf(h, [&](bisbm_engine* e) { return align_leaf(e, a, device_counts ? device_counts : (e->root ? e->root : e)->d_counts); });
 }
 
 }  // namespace bisbm
@@ -532,8 +464,8 @@ int bisbm_marginals_get_alignment(bisbm_handle h, uint32_t chain, uint32_t* perm
     std::vector<uint8_t> perm(K);
     uint64_t tot[2];
     HIPCHK(h, hipSetDevice(e->device));
-    HIPCHK(h, hipMemcpy(perm.data(), a.d_perm + (size_t)local * K, K, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(tot, a.d_tot + (size_t)local * 2, sizeof(tot), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(perm.data(), a.d_perm.get() + (size_t)local * K, K, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(tot, a.d_tot.get() + (size_t)local * 2, sizeof(tot), hipMemcpyDeviceToHost));
     if (perm_out)
         for (uint32_t r = 0; r < K; ++r) perm_out[r] = perm[r];
     if (overlap_out) *overlap_out = tot[0] + tot[1];

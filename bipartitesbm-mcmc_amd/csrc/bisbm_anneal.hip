@@ -112,17 +112,12 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     p.T_base = 0;
     p.T_zero_after = 0;
     auto upload_table = [&](const std::vector<double>& T, uint64_t t0, int zero_after) -> int {
-        if (T.size() > h->d_T_cap) {
-            if (h->d_T) (void)hipFree(h->d_T);
-            h->d_T = nullptr;
-            h->d_T_cap = 0;
-            HIPCHK(h, dalloc(&h->d_T, T.size()));
-            h->d_T_cap = T.size();
+        if (!T.empty()) {
+            RESERVE(h, h->d_T, T.size());
+            HIPCHK(h, hipMemcpyAsync(h->d_T.get(), T.data(), sizeof(double) * T.size(), hipMemcpyHostToDevice, h->stream));
         }
-        if (!T.empty())
-            HIPCHK(h, hipMemcpyAsync(h->d_T, T.data(), sizeof(double) * T.size(), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        p.T_tab = h->d_T;
+        p.T_tab = h->d_T.get();
         p.T_len = T.size();
         p.T_base = t0;
         p.T_zero_after = zero_after;

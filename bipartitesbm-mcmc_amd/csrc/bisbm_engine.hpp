@@ -1,9 +1,10 @@
 // bisbm_engine.hpp -- what the translation units of the host side share (internal; the C ABI is include/bisbm.h): the handle,
-// the host-built tables, error / allocation helpers and the dispatch templates of container handles (chains of several shapes:
-// `groups`; several devices: `devs`).
+// the host-built tables, error / allocation helpers (DeviceBuf: the one owner of a device buffer that grows on demand) and the one
+// walk over container handles (chains of several shapes: `groups`; several devices: `devs`): leaves / each_leaf / device_entries /
+// any_grouped / any_wide / shared_shape / leaf_of_chain.
 //
 //   bisbm_tables.cpp     host-built numeric tables, temperature tables (no HIP)
-//   bisbm_handle.hip     create / destroy / labels in and out / init / shuffle / getters / entropy
+//   bisbm_handle.hip     create / destroy / labels in and out / init / shuffle / getters / entropy; the walk over a handle
 //   bisbm_anneal.hip     bisbm_anneal: LDS plan, launch slicing (table slices, pass depth), bookkeeping across launches
 //   bisbm_marginals.hip  per-node label histogram, MAP labels of one engine
 //   bisbm_multi.hip      several devices behind one handle: creation, dispatch, pooling (RCCL / peer copies)
@@ -60,6 +61,45 @@ double h_lbinom_fast(const HostTables& t, uint64_t N, uint64_t k);    // util.hh
 // metropolis_hasting.cc:10-13,20-23 with the host libm for steps t0 .. t0 + len - 1 of a call
 std::vector<double> schedule_table(int schedule, float kw0, float kw1, uint64_t t0, uint64_t len, int* zero_after);
 
+template <class T>
+hipError_t dalloc(T** p, size_t count) {
+    return hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1));
+}
+
+// A device buffer with one owner: freed when its owner goes, grown on demand.  It is allocated on whatever device is current
+// (as dalloc).  Growing does NOT keep the contents: no caller needs them kept.
+template <class T>
+class DeviceBuf {
+    T* p_ = nullptr;
+    size_t cap_ = 0;  // elements
+
+public:
+    DeviceBuf() = default;
+    DeviceBuf(DeviceBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
+    DeviceBuf& operator=(DeviceBuf&& o) noexcept {  // (what this one held goes with `o`)
+        std::swap(p_, o.p_), std::swap(cap_, o.cap_);
+        return *this;
+    }
+    ~DeviceBuf() { reset(); }
+    T* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    // room for `count` elements: an allocation that has it is kept, otherwise it is replaced; empty after a failure
+    hipError_t reserve(size_t count) {
+        if (p_ && cap_ >= count) return hipSuccess;
+        reset();
+        const hipError_t e = dalloc(&p_, count);
+        if (e == hipSuccess)
+            cap_ = count;
+        else
+            p_ = nullptr;
+        return e;
+    }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr, cap_ = 0;
+    }
+};
+
 // Label alignment of the marginal histogram (bisbm_align.hip).  The mode, the reference and `samples` belong to the handle
 // the caller holds; the buffers and the last permutations belong to the engines that run the kernels (a plain handle, a
 // group, a device entry).
@@ -73,11 +113,10 @@ struct AlignState {
     uint64_t serial = 0;          // bumped whenever the reference changes
     // kernel-running engine
     uint64_t uploaded = 0;        // serial of the reference in d_ref
-    uint8_t* d_ref = nullptr;     // label_stride bytes
-    uint32_t* d_tab = nullptr;    // [chain][ka*ka + kb*kb] overlap tables
-    uint8_t* d_perm = nullptr;    // [chain][ka + kb] permutation, global-label form
-    uint64_t* d_tot = nullptr;    // [chain][2] overlap totals per type
-    size_t tab_cap = 0, perm_cap = 0, tot_cap = 0;
+    DeviceBuf<uint8_t> d_ref;     // label_stride bytes
+    DeviceBuf<uint32_t> d_tab;    // [chain][ka*ka + kb*kb] overlap tables
+    DeviceBuf<uint8_t> d_perm;    // [chain][ka + kb] permutation, global-label form
+    DeviceBuf<uint64_t> d_tot;    // [chain][2] overlap totals per type
     bool have_perm = false;
     uint32_t perm_ka = 0, perm_kb = 0;
 };
@@ -89,12 +128,11 @@ struct TemperState {
     std::vector<float> ladder;    // L temperatures, non-decreasing
     uint64_t round = 0;           // exchange rounds since bisbm_tempering_set
     // kernel-running engine
-    float* d_T = nullptr;               // [chain] temperature of the chain's rung (SweepParams::T_chain)
-    uint32_t* d_rung = nullptr;         // [chain] rung of the chain (MarginalParams::rung)
-    uint32_t* d_at = nullptr;           // [ensemble][L] the chain (index in the engine) on every rung
-    float* d_ladder = nullptr;          // L temperatures
-    unsigned long long* d_stats = nullptr;  // [2][L - 1] attempted, accepted exchanges per rung pair
-    size_t cap_chains = 0, cap_L = 0;
+    DeviceBuf<float> d_T;                   // [chain] temperature of the chain's rung (SweepParams::T_chain)
+    DeviceBuf<uint32_t> d_rung;             // [chain] rung of the chain (MarginalParams::rung)
+    DeviceBuf<uint32_t> d_at;               // [ensemble][L] the chain (index in the engine) on every rung
+    DeviceBuf<float> d_ladder;              // L temperatures
+    DeviceBuf<unsigned long long> d_stats;  // [2][L - 1] attempted, accepted exchanges per rung pair
 };
 
 // Pair scores (bisbm_pair_scores.hip).  The buffers belong to the engine that owns the graph on a device (a plain handle, the
@@ -103,25 +141,23 @@ struct TemperState {
 struct PairScoreState {
     uint64_t n = 0;               // pairs set (0: none)
     uint64_t terms = 0;           // chain terms added to every sum since the last set / reset
-    uint32_t* d_u = nullptr;      // [n] type-a node of every pair, sorted order
-    uint32_t* d_v = nullptr;      // [n] type-b node
-    double* d_dd = nullptr;       // [n] (double)d(u) * (double)d(v)
-    double* d_sum = nullptr;      // [n] running sums, sorted order
-    double* d_part = nullptr;     // [slabs][n] partial sums of one sample
-    size_t part_cap = 0;          // doubles d_part is allocated for
+    DeviceBuf<uint32_t> d_u;      // [n] type-a node of every pair, sorted order
+    DeviceBuf<uint32_t> d_v;      // [n] type-b node
+    DeviceBuf<double> d_dd;       // [n] (double)d(u) * (double)d(v)
+    DeviceBuf<double> d_sum;      // [n] running sums, sorted order
+    DeviceBuf<double> d_part;     // [slabs][n] partial sums of one sample
     std::vector<uint32_t> order;  // sorted position -> index in the caller's arrays
 };
 
 // Partition distances (bisbm_partition.hip).  The scratch of the calls, on the engine whose device computes (a plain handle, the
 // container of shape groups, the first device entry); nothing of it outlives a call in meaning, it is only kept to be reused.
 struct PartitionState {
-    void* d_desc = nullptr;       // [selection] row pointer, ka, kb of every selected chain
-    void* d_tiles = nullptr;      // [tiles] (row tile, column tile)
-    double* d_A = nullptr;        // [selection] sum_r a_r ln a_r
-    double* d_snn = nullptr;      // [selection][selection] sum_rs n_rs ln n_rs of every pair i < j
-    uint32_t* d_tab = nullptr;    // few pairs: the integer tables of one launch
-    uint8_t* d_stage = nullptr;   // label rows of selected chains that live on another device
-    size_t desc_cap = 0, tiles_cap = 0, A_cap = 0, snn_cap = 0, tab_cap = 0, stage_cap = 0;  // bytes
+    DeviceBuf<uint8_t> d_desc;    // [selection] row pointer, ka, kb of every selected chain (the unit's ChainDesc, as bytes)
+    DeviceBuf<uint2> d_tiles;     // [tiles] (row tile, column tile)
+    DeviceBuf<double> d_A;        // [selection] sum_r a_r ln a_r
+    DeviceBuf<double> d_snn;      // [selection][selection] sum_rs n_rs ln n_rs of every pair i < j
+    DeviceBuf<uint32_t> d_tab;    // few pairs: the integer tables of one launch
+    DeviceBuf<uint8_t> d_stage;   // label rows of selected chains that live on another device
 };
 
 }  // namespace bisbm
@@ -162,8 +198,7 @@ struct bisbm_engine {
     double* d_lgamma = nullptr;
     double* d_logtab = nullptr;
     double* d_q = nullptr;
-    double* d_T = nullptr;
-    size_t d_T_cap = 0;
+    bisbm::DeviceBuf<double> d_T;  // temperature table of the pow / log schedules (bisbm_anneal)
     double* d_tmp_f64 = nullptr;  // n_chains doubles
     // block-state part of the description length of every chain as the last production launch without early-stop bookkeeping
     // left it (such launches do not keep the running sum of accepted dS: bisbm_anneal advances it by the change of this,
@@ -226,10 +261,15 @@ int fail(bisbm_engine* h, int code, const char* fmt, ...) __attribute__((format(
         if (e_ != hipSuccess) return fail((h), BISBM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-template <class T>
-hipError_t dalloc(T** p, size_t count) {
-    return hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1));
-}
+// room for `count` elements in a DeviceBuf, or the call fails with the function, the buffer and the size in the message
+#define RESERVE(h, buf, count)                                                                                                \
+    do {                                                                                                                      \
+        const size_t n_ = (count);                                                                                            \
+        hipError_t e_ = (buf).reserve(n_);                                                                                    \
+        if (e_ != hipSuccess)                                                                                                 \
+            return fail((h), BISBM_ERR_HIP, "%s: %zu bytes of device memory for " #buf " could not be allocated: %s", __func__, \
+                        n_ * sizeof(*(buf).get()), hipGetErrorString(e_));                                                    \
+    } while (0)
 
 void free_chain_arrays(bisbm_engine* h);
 void free_all(bisbm_engine* h);
@@ -251,8 +291,10 @@ int each_group(bisbm_engine* h, F f) {
     }
     return BISBM_OK;
 }
-// container handles: do all groups have one shape (again)?  If so the handle's own ka / kb / K follow it.
+// do all chains under the handle have one shape (again)?  If so the ka / kb / K of the containers on the way follow it.
 bool common_shape(bisbm_engine* h);
+// ... and the block counts they share, or BISBM_ERR_STATE with the one message of that refusal (the marginal calls, alignment)
+int shared_shape(bisbm_engine* h, uint32_t* ka, uint32_t* kb);
 // ... and gather one value per chain from the groups into the handle's chain order
 template <class T, class F>
 int gather_groups(bisbm_engine* h, T* out, F f) {
@@ -340,7 +382,33 @@ int on_devices(bisbm_engine* h, F&& fn) {
     return rc;
 }
 
-int multi_common_shape(bisbm_engine* h, uint32_t* ka, uint32_t* kb);
+// ---- one walk over a handle: a plain engine, a container of shape groups, a container of device entries (bisbm_handle.hip) ----
+// the device entries: the handle itself, or `devs`
+std::vector<bisbm_engine*> device_entries(bisbm_engine* h);
+// the engines that run kernels under the handle (a plain handle; its groups; the device entries and their groups), in device
+// order, then group order
+std::vector<bisbm_engine*> leaves(bisbm_engine* h);
+bool any_grouped(bisbm_engine* h);  // does the handle, or one of its device entries, keep its chains grouped by shape?
+bool any_wide(bisbm_engine* h);     // does some leaf hold two-byte labels?
+// the leaf that runs chain `chain` of the handle, and the chain's index there
+bisbm_engine* leaf_of_chain(bisbm_engine* h, uint32_t chain, uint32_t* local);
+// f(leaf, index there) for the leaf of one chain; the leaf's message becomes the handle's when it fails
+template <class F>
+int on_leaf_of_chain(bisbm_engine* h, uint32_t chain, F f) {
+    bisbm_engine* e = leaf_of_chain(h, chain, &chain);
+    const int rc = f(e, chain);
+    if (rc && e != h) h->err = e->err;
+    return rc;
+}
+// f(leaf) for every leaf: one host thread per device entry, the groups of an entry in order
+template <class F>
+int each_leaf(bisbm_engine* h, F&& f) {
+    if (!h->devs.empty())
+        return on_devices(h, [&](bisbm_engine* d, size_t) { return each_leaf(d, f); });
+    if (!h->groups.empty()) return each_group(h, [&](bisbm_engine* g) { return f(g); });
+    return f(h);
+}
+
 int multi_anneal(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t duration_steps, uint64_t steps_await, double* acc_rate_out);
 int multi_marginals_get(bisbm_engine* h, uint32_t* counts_out);
 int multi_marginals_map(bisbm_engine* h, uint32_t* labels_out);
@@ -352,19 +420,10 @@ void entropy_terms(const bisbm_engine* h, double t[8]);
 // bisbm_anneal on a kernel-running engine with a temperature per chain (T_chain: device pointer, NULL: none); bisbm_anneal.hip
 int anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t duration_steps, uint64_t steps_await,
                   double* acc_rate_out, const float* T_chain);
-// the buffers of replica exchange (bisbm_destroy); bisbm_tempering.hip
-void temper_free(bisbm_engine* h);
-// bisbm_marginals_accumulate with the alignment on; the buffers of alignment (bisbm_destroy); bisbm_align.hip
+// bisbm_marginals_accumulate with the alignment on; bisbm_align.hip
 int align_accumulate(bisbm_engine* h, uint32_t* device_counts);
-void align_free(bisbm_engine* h);
 // replica exchange is on and some engine under `h` keeps its chains grouped by shape: BISBM_ERR_STATE with the message of the
 // marginal histogram (a group engine knows no rungs), BISBM_OK otherwise; bisbm_marginals.hip
 int refuse_rungs_over_groups(bisbm_engine* h);
-// the buffers of the pair scores (bisbm_destroy); bisbm_pair_scores.hip
-void pair_scores_free(bisbm_engine* h);
-// the scratch of the partition distances (bisbm_destroy); bisbm_partition.hip
-void partition_free(bisbm_engine* h);
-// the engine that runs chain `chain` of the handle, and the chain's index there; bisbm_align.hip
-bisbm_engine* leaf_of_chain(bisbm_engine* h, uint32_t chain, uint32_t* local);
 
 }  // namespace bisbm

@@ -45,14 +45,13 @@ void free_all(bisbm_engine* h) {
     }
     h->groups.clear();
     free_chain_arrays(h);
-    align_free(h);
-    temper_free(h);
-    pair_scores_free(h);
-    partition_free(h);
+    // (the buffers of these go here, with the device current and before the stream and the events)
+    h->align = AlignState(), h->temper = TemperState(), h->pairs = PairScoreState(), h->partition = PartitionState();
+    h->d_T.reset();
     if (h->root) {  // a sub-engine: the graph and the tables belong to the handle it serves
         h->d_rowptr = nullptr, h->d_col = nullptr, h->d_lgamma = nullptr, h->d_logtab = nullptr, h->d_q = nullptr;
     }
-    void* ptrs[] = {h->d_rowptr, h->d_col, h->d_lgamma, h->d_logtab, h->d_q, h->d_T, h->d_stage_u32, h->d_simd_claims};
+    void* ptrs[] = {h->d_rowptr, h->d_col, h->d_lgamma, h->d_logtab, h->d_q, h->d_stage_u32, h->d_simd_claims};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -92,10 +91,56 @@ int rebuild_state(bisbm_engine* h) {
 }
 
 bool common_shape(bisbm_engine* h) {
-    for (bisbm_engine* g : h->groups)
-        if (g->ka != h->groups[0]->ka || g->kb != h->groups[0]->kb) return false;
-    h->ka = h->groups[0]->ka, h->kb = h->groups[0]->kb, h->K = h->ka + h->kb;
+    const std::vector<bisbm_engine*>& parts = h->devs.empty() ? h->groups : h->devs;
+    if (parts.empty()) return true;
+    for (bisbm_engine* e : parts)
+        if ((!h->devs.empty() && !common_shape(e)) || e->ka != parts[0]->ka || e->kb != parts[0]->kb) return false;
+    h->ka = parts[0]->ka, h->kb = parts[0]->kb, h->K = h->ka + h->kb;
     return true;
+}
+
+int shared_shape(bisbm_engine* h, uint32_t* ka, uint32_t* kb) {
+    if (!common_shape(h)) return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: no common marginal histogram");
+    if (ka) *ka = h->ka;
+    if (kb) *kb = h->kb;
+    return BISBM_OK;
+}
+
+std::vector<bisbm_engine*> device_entries(bisbm_engine* h) { return h->devs.empty() ? std::vector<bisbm_engine*>{h} : h->devs; }
+
+std::vector<bisbm_engine*> leaves(bisbm_engine* h) {
+    std::vector<bisbm_engine*> out;
+    for (bisbm_engine* d : device_entries(h))
+        if (d->groups.empty())
+            out.push_back(d);
+        else
+            out.insert(out.end(), d->groups.begin(), d->groups.end());
+    return out;
+}
+
+bool any_grouped(bisbm_engine* h) {
+    for (bisbm_engine* d : device_entries(h))
+        if (!d->groups.empty()) return true;
+    return false;
+}
+
+bool any_wide(bisbm_engine* h) {
+    for (bisbm_engine* e : leaves(h))
+        if (e->wide) return true;
+    return false;
+}
+
+bisbm_engine* leaf_of_chain(bisbm_engine* h, uint32_t chain, uint32_t* local) {
+    if (!h->devs.empty()) {
+        bisbm_engine* d = h->devs[dev_of_chain(h, chain, &chain)];
+        return leaf_of_chain(d, chain, local);
+    }
+    if (!h->groups.empty()) {
+        *local = h->where[chain].second;
+        return h->groups[h->where[chain].first];
+    }
+    *local = chain;
+    return h;
 }
 
 size_t generic_lds_base_bytes(uint32_t ka, uint32_t kb, bool wide, int rng_mode) {
@@ -352,20 +397,9 @@ int bisbm_set_memberships(bisbm_handle h, int64_t chain, const uint32_t* labels)
     if (!labels) return fail(h, BISBM_ERR_INVALID_ARG, "labels is NULL");
     if (chain != BISBM_ALL_CHAINS && (chain < 0 || chain >= (int64_t)h->n_chains))
         return fail(h, BISBM_ERR_INVALID_ARG, "chain %lld out of range", (long long)chain);
-    if (!h->devs.empty()) {
-        if (chain == BISBM_ALL_CHAINS) return on_devices(h, [&](bisbm_engine* d, size_t) { return bisbm_set_memberships(d, BISBM_ALL_CHAINS, labels); });
-        uint32_t local;
-        bisbm_engine* d = h->devs[dev_of_chain(h, (uint32_t)chain, &local)];
-        const int rc = bisbm_set_memberships(d, local, labels);
-        if (rc) h->err = d->err;
-        return rc;
-    }
-    if (!h->groups.empty()) {  // (the labels must name blocks of the chain's own shape)
-        if (chain == BISBM_ALL_CHAINS) return each_group(h, [&](bisbm_engine* g) { return bisbm_set_memberships(g, BISBM_ALL_CHAINS, labels); });
-        bisbm_engine* g = h->groups[h->where[chain].first];
-        const int rc = bisbm_set_memberships(g, h->where[chain].second, labels);
-        if (rc) h->err = g->err;
-        return rc;
+    if (!h->devs.empty() || !h->groups.empty()) {  // (the labels must name blocks of the chain's own shape)
+        if (chain == BISBM_ALL_CHAINS) return each_leaf(h, [&](bisbm_engine* e) { return bisbm_set_memberships(e, BISBM_ALL_CHAINS, labels); });
+        return on_leaf_of_chain(h, (uint32_t)chain, [&](bisbm_engine* e, uint32_t local) { return bisbm_set_memberships(e, local, labels); });
     }
     for (uint64_t v = 0; v < h->n; ++v) {
         const uint32_t b = labels[v];
@@ -382,18 +416,16 @@ int bisbm_set_memberships(bisbm_handle h, int64_t chain, const uint32_t* labels)
     return BISBM_OK;
 }
 
-int bisbm_init(bisbm_handle h) {
-    if (!h) return BISBM_ERR_INVALID_ARG;
-    if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_init(d); });
-    if (!h->groups.empty()) return each_group(h, [](bisbm_engine* g) { return bisbm_init(g); });
+}  // extern "C"
+
+namespace {
+
+int init_leaf(bisbm_engine* h) {
     HIPCHK(h, hipSetDevice(h->device));
     return rebuild_state(h);
 }
 
-int bisbm_shuffle(bisbm_handle h) {
-    if (!h) return BISBM_ERR_INVALID_ARG;
-    if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_shuffle(d); });
-    if (!h->groups.empty()) return each_group(h, [](bisbm_engine* g) { return bisbm_shuffle(g); });
+int shuffle_leaf(bisbm_engine* h) {
     HIPCHK(h, hipSetDevice(h->device));
     ShuffleParams sp{};
     sp.n = (uint32_t)h->n;
@@ -416,22 +448,19 @@ int bisbm_shuffle(bisbm_handle h) {
     return rebuild_state(h);
 }
 
+}  // namespace
+
+extern "C" {
+
+int bisbm_init(bisbm_handle h) { return h ? each_leaf(h, init_leaf) : BISBM_ERR_INVALID_ARG; }
+
+int bisbm_shuffle(bisbm_handle h) { return h ? each_leaf(h, shuffle_leaf) : BISBM_ERR_INVALID_ARG; }
+
 int bisbm_get_memberships(bisbm_handle h, uint32_t chain, uint32_t* labels_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (!labels_out || chain >= h->n_chains) return fail(h, BISBM_ERR_INVALID_ARG, "bad chain or NULL output");
-    if (!h->devs.empty()) {
-        uint32_t local;
-        bisbm_engine* d = h->devs[dev_of_chain(h, chain, &local)];
-        const int rc = bisbm_get_memberships(d, local, labels_out);
-        if (rc) h->err = d->err;
-        return rc;
-    }
-    if (!h->groups.empty()) {
-        bisbm_engine* g = h->groups[h->where[chain].first];
-        const int rc = bisbm_get_memberships(g, h->where[chain].second, labels_out);
-        if (rc) h->err = g->err;
-        return rc;
-    }
+    if (!h->devs.empty() || !h->groups.empty())
+        return on_leaf_of_chain(h, chain, [&](bisbm_engine* e, uint32_t local) { return bisbm_get_memberships(e, local, labels_out); });
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, launch_labels_widen(h->d_labels + (size_t)chain * h->label_stride * h->lbytes(), h->wide, h->d_stage_u32, (uint32_t)h->n, h->stream));
     HIPCHK(h, hipMemcpyAsync(labels_out, h->d_stage_u32, sizeof(uint32_t) * h->n, hipMemcpyDeviceToHost, h->stream));
@@ -442,19 +471,8 @@ int bisbm_get_memberships(bisbm_handle h, uint32_t chain, uint32_t* labels_out) 
 int bisbm_get_block_state(bisbm_handle h, uint32_t chain, int32_t* m, int32_t* m_r, int32_t* n_r, uint32_t* eta) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (chain >= h->n_chains) return fail(h, BISBM_ERR_INVALID_ARG, "chain out of range");
-    if (!h->devs.empty()) {
-        uint32_t local;
-        bisbm_engine* d = h->devs[dev_of_chain(h, chain, &local)];
-        const int rc = bisbm_get_block_state(d, local, m, m_r, n_r, eta);
-        if (rc) h->err = d->err;
-        return rc;
-    }
-    if (!h->groups.empty()) {  // (array sizes follow the chain's own shape: bisbm_get_ka_kb_chain)
-        bisbm_engine* g = h->groups[h->where[chain].first];
-        const int rc = bisbm_get_block_state(g, h->where[chain].second, m, m_r, n_r, eta);
-        if (rc) h->err = g->err;
-        return rc;
-    }
+    if (!h->devs.empty() || !h->groups.empty())  // (array sizes follow the chain's own shape: bisbm_get_ka_kb_chain)
+        return on_leaf_of_chain(h, chain, [&](bisbm_engine* e, uint32_t local) { return bisbm_get_block_state(e, local, m, m_r, n_r, eta); });
     if (!h->state_ready) return fail(h, BISBM_ERR_STATE, "block state not built yet");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -533,8 +551,7 @@ int bisbm_entropy(bisbm_handle h, double* out) {
 
 int bisbm_get_ka_kb(bisbm_handle h, uint32_t* ka, uint32_t* kb) {
     if (!h) return BISBM_ERR_INVALID_ARG;
-    if (!h->devs.empty()) return multi_common_shape(h, ka, kb);
-    if (!h->groups.empty() && !common_shape(h))
+    if (!common_shape(h))
         return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: ask per chain (bisbm_get_ka_kb_chain)");
     if (ka) *ka = h->ka;
     if (kb) *kb = h->kb;
@@ -573,20 +590,17 @@ int bisbm_debug_log_q(bisbm_handle h, const int32_t* n, const int32_t* k, size_t
     if (!n || !k || !out) return fail(h, BISBM_ERR_INVALID_ARG, "NULL argument");
     if (count == 0) return BISBM_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    int32_t *dn = nullptr, *dk = nullptr;
-    double* dout = nullptr;
-    HIPCHK(h, dalloc(&dn, count));
-    HIPCHK(h, dalloc(&dk, count));
-    HIPCHK(h, dalloc(&dout, count));
-    HIPCHK(h, hipMemcpy(dn, n, sizeof(int32_t) * count, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dk, k, sizeof(int32_t) * count, hipMemcpyHostToDevice));
+    DeviceBuf<int32_t> dn, dk;
+    DeviceBuf<double> dout;
+    RESERVE(h, dn, count);
+    RESERVE(h, dk, count);
+    RESERVE(h, dout, count);
+    HIPCHK(h, hipMemcpy(dn.get(), n, sizeof(int32_t) * count, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(dk.get(), k, sizeof(int32_t) * count, hipMemcpyHostToDevice));
     Tables tab{h->d_lgamma, h->tab->lg.size(), h->d_q, h->q_stride, h->d_logtab};
-    HIPCHK(h, launch_log_q_probe(tab, dn, dk, count, dout, fast, h->stream));
+    HIPCHK(h, launch_log_q_probe(tab, dn.get(), dk.get(), count, dout.get(), fast, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(out, dout, sizeof(double) * count, hipMemcpyDeviceToHost));
-    (void)hipFree(dn);
-    (void)hipFree(dk);
-    (void)hipFree(dout);
+    HIPCHK(h, hipMemcpy(out, dout.get(), sizeof(double) * count, hipMemcpyDeviceToHost));
     return BISBM_OK;
 }
 

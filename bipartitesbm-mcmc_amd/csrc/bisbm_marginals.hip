@@ -8,28 +8,22 @@ namespace bisbm {
 
 // MAP labels from the internal histogram of one engine (no pooling): argmax kernel + copy
 int single_marginals_map(bisbm_engine* h, uint32_t* labels_out) {
-    if (!h->groups.empty() && !common_shape(h))
-        return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: no common marginal histogram");
+    if (int rc = shared_shape(h, nullptr, nullptr)) return rc;
     if (!h->d_counts || h->counts_cols != std::max(h->ka, h->kb)) return fail(h, BISBM_ERR_STATE, "no marginal histogram of the present block counts yet");
     HIPCHK(h, hipSetDevice(h->device));
-    uint16_t* d_lab = nullptr;
-    HIPCHK(h, dalloc(&d_lab, (size_t)h->n));
+    DeviceBuf<uint16_t> d_lab;
+    RESERVE(h, d_lab, (size_t)h->n);
     std::vector<uint16_t> lab((size_t)h->n);
-    hipError_t e = launch_marginal_map(h->d_counts, (uint32_t)h->n, h->counts_cols, 0, (uint32_t)h->n, (uint32_t)h->na, h->ka, d_lab, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(lab.data(), d_lab, sizeof(uint16_t) * h->n, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_lab);
-    if (e != hipSuccess) return fail(h, BISBM_ERR_HIP, "marginal MAP labels: %s", hipGetErrorString(e));
+    HIPCHK(h, launch_marginal_map(h->d_counts, (uint32_t)h->n, h->counts_cols, 0, (uint32_t)h->n, (uint32_t)h->na, h->ka, d_lab.get(), h->stream));
+    HIPCHK(h, hipMemcpyAsync(lab.data(), d_lab.get(), sizeof(uint16_t) * h->n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     for (uint64_t v = 0; v < h->n; ++v) labels_out[v] = lab[v];
     return BISBM_OK;
 }
 
 int refuse_rungs_over_groups(bisbm_engine* h) {
-    if (!h->temper.L) return BISBM_OK;
     // (a group engine knows no rungs: refused wherever the chains are grouped, on any device entry, raw or aligned)
-    bool grouped = !h->groups.empty();
-    for (bisbm_engine* d : h->devs) grouped = grouped || !d->groups.empty();
-    if (grouped)
+    if (h->temper.L && any_grouped(h))
         return fail(h, BISBM_ERR_STATE, "replica exchange is on and the chains of this handle are grouped by shape (after bisbm_agg_merge_total): no cold-chain histogram");
     return BISBM_OK;
 }
@@ -43,8 +37,7 @@ int bisbm_marginals_reset(bisbm_handle h) {
     h->align.samples = false;
     if (h->align.has_ref && h->align.ref_chain >= 0) h->align.has_ref = false;  // (a caller's reference stays)
     if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_marginals_reset(d); });
-    if (!h->groups.empty() && !common_shape(h))
-        return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: no common marginal histogram");
+    if (int rc = shared_shape(h, nullptr, nullptr)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const uint32_t kmax = std::max(h->ka, h->kb);
     const size_t cnt = (size_t)std::max<uint64_t>(h->n, h->counts_rows) * kmax;  // (rows past n stay zero: see DevicePool)
@@ -67,13 +60,10 @@ int bisbm_marginals_reset(bisbm_handle h) {
 namespace {
 
 int accumulate_plain(bisbm_engine* h, uint32_t* device_counts) {
-    if (!h->devs.empty()) {
-        if (device_counts) return fail(h, BISBM_ERR_UNSUPPORTED, "a handle over several devices accumulates into its own buffers (device_counts must be NULL); bisbm_marginals_map pools them");
-        if (int rc = multi_common_shape(h, nullptr, nullptr)) return rc;
-        return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_marginals_accumulate(d, nullptr); });
-    }
-    if (!h->groups.empty() && !common_shape(h))
-        return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: no common marginal histogram");
+    if (!h->devs.empty() && device_counts)
+        return fail(h, BISBM_ERR_UNSUPPORTED, "a handle over several devices accumulates into its own buffers (device_counts must be NULL); bisbm_marginals_map pools them");
+    if (int rc = shared_shape(h, nullptr, nullptr)) return rc;
+    if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_marginals_accumulate(d, nullptr); });
     HIPCHK(h, hipSetDevice(h->device));
     if (!device_counts) {
         // (a histogram made before a merge / split changed max(KA, KB) has another row length: start afresh)
@@ -95,7 +85,7 @@ int accumulate_plain(bisbm_engine* h, uint32_t* device_counts) {
     mp.label_stride = h->label_stride;
     mp.wide = h->wide ? 1u : 0u;
     mp.counts = device_counts;
-    mp.rung = h->temper.L ? h->temper.d_rung : nullptr;  // replica exchange: the cold chains only
+    mp.rung = h->temper.L ? h->temper.d_rung.get() : nullptr;  // replica exchange: the cold chains only
     HIPCHK(h, launch_marginals(mp, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
@@ -117,8 +107,7 @@ int bisbm_marginals_get(bisbm_handle h, uint32_t* counts_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (!counts_out) return fail(h, BISBM_ERR_INVALID_ARG, "counts_out is NULL");
     if (!h->devs.empty()) return multi_marginals_get(h, counts_out);
-    if (!h->groups.empty() && !common_shape(h))
-        return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: no common marginal histogram");
+    if (int rc = shared_shape(h, nullptr, nullptr)) return rc;
     if (!h->d_counts) return fail(h, BISBM_ERR_STATE, "no internal marginal buffer yet");
     if (h->counts_cols != std::max(h->ka, h->kb))
         return fail(h, BISBM_ERR_STATE, "the block counts changed since the histogram was made (%u columns then, %u now)", h->counts_cols,

@@ -331,11 +331,9 @@ int run_split(bisbm_engine* h, int type, int nm) {
         h->wide = true;
     }
 
-    uint32_t *d_rank = nullptr, *d_bits = nullptr, *d_chosen = nullptr, *d_rank_base = nullptr, *d_block_off = nullptr;
-    int32_t *d_out_k = nullptr, *d_out_deg = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {(void*)d_rank, (void*)d_bits, (void*)d_chosen, (void*)d_out_k, (void*)d_out_deg, (void*)d_rank_base, (void*)d_block_off})
-            if (p) (void)hipFree(p);
+    DeviceBuf<uint32_t> d_rank, d_bits, d_chosen, d_rank_base, d_block_off;
+    DeviceBuf<int32_t> d_out_k, d_out_deg;
+    auto settle_labels = [&]() {  // on every way out once the labels may have been widened
         if (narrow_labels) {
             if (!applied) {  // the split did not happen: back to byte labels
                 (void)hipFree(h->d_labels);
@@ -353,12 +351,12 @@ int run_split(bisbm_engine* h, int type, int nm) {
     do {                                                                           \
         hipError_t e_ = (expr);                                                    \
         if (e_ != hipSuccess) {                                                    \
-            cleanup();                                                             \
+            settle_labels();                                                       \
             return fail(h, BISBM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
         }                                                                          \
     } while (0)
-    SCHK(dalloc(&d_rank, C * n_type));
-    SCHK(dalloc(&d_chosen, 2 * C));
+    SCHK(d_rank.reserve(C * n_type));
+    SCHK(d_chosen.reserve(2 * C));
 
     SplitParams sp{};
     sp.rowptr = h->d_rowptr;
@@ -377,12 +375,12 @@ int run_split(bisbm_engine* h, int type, int nm) {
     sp.label_stride = h->label_stride;
     sp.n_r = h->d_n_r;
     sp.scalars = h->d_scalars;
-    sp.rank = d_rank;
+    sp.rank = d_rank.get();
     sp.wide = h->wide ? 1u : 0u;
     if (h->wide) {
-        SCHK(dalloc(&d_rank_base, C * K));
-        SCHK(hipMemsetAsync(d_rank_base, 0, sizeof(uint32_t) * C * K, h->stream));
-        sp.rank_base = d_rank_base;
+        SCHK(d_rank_base.reserve(C * K));
+        SCHK(hipMemsetAsync(d_rank_base.get(), 0, sizeof(uint32_t) * C * K, h->stream));
+        sp.rank_base = d_rank_base.get();
         std::vector<uint32_t> off(C * k_type);  // (compat: where a block's bits start in a trial's cut)
         for (size_t c = 0; c < C; ++c) {
             uint32_t acc = 0;
@@ -391,9 +389,9 @@ int run_split(bisbm_engine* h, int type, int nm) {
                 acc += (uint32_t)n_r[c * K + b_lo + b];
             }
         }
-        SCHK(dalloc(&d_block_off, off.size()));
-        SCHK(hipMemcpy(d_block_off, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice));
-        sp.block_off = d_block_off;
+        SCHK(d_block_off.reserve(off.size()));
+        SCHK(hipMemcpy(d_block_off.get(), off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice));
+        sp.block_off = d_block_off.get();
     }
     SCHK(launch_split_rank(sp, h->stream));
 
@@ -402,7 +400,7 @@ int run_split(bisbm_engine* h, int type, int nm) {
     const size_t bit_words = (n_type + 31) / 32;
     if (compat) {
         if ((double)C * nm * bit_words * 4.0 > 2.0e9) {
-            cleanup();
+            settle_labels();
             return fail(h, BISBM_ERR_UNSUPPORTED, "mt19937-compat agg_split needs %.1f GB of cut bits; use fewer chains (compat is the parity path)",
                         (double)C * nm * bit_words * 4.0 / 1e9);
         }
@@ -438,24 +436,24 @@ int run_split(bisbm_engine* h, int type, int nm) {
             for (int i = 0; i < 624; ++i) ss >> mt_e[c * 624 + i];
             ss >> sc[c].engine_idx;
         }
-        SCHK(dalloc(&d_bits, bits.size()));
-        SCHK(hipMemcpy(d_bits, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
-        sp.bits = d_bits;
+        SCHK(d_bits.reserve(bits.size()));
+        SCHK(hipMemcpy(d_bits.get(), bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
+        sp.bits = d_bits.get();
         sp.bit_words = (uint32_t)bit_words;
     }
 
     // trials in batches of at most ~256 MB of counts
     const size_t per_trial = C * k_type * k_oth * sizeof(int32_t);
     if (per_trial > ((size_t)2 << 30)) {
-        cleanup();
+        settle_labels();
         return fail(h, BISBM_ERR_UNSUPPORTED, "agg_split: the edge counts of one trial take %.1f GB (%zu chains x %zu x %zu blocks); use fewer chains",
                     (double)per_trial / 1e9, C, k_type, k_oth);
     }
     const size_t batch = std::max<size_t>(1, std::min<size_t>((size_t)nm, ((size_t)256 << 20) / std::max<size_t>(per_trial, 1)));
-    SCHK(dalloc(&d_out_k, C * batch * k_type * k_oth));
-    SCHK(dalloc(&d_out_deg, C * batch * k_type));
-    sp.out_k = d_out_k;
-    sp.out_deg = d_out_deg;
+    SCHK(d_out_k.reserve(C * batch * k_type * k_oth));
+    SCHK(d_out_deg.reserve(C * batch * k_type));
+    sp.out_k = d_out_k.get();
+    sp.out_deg = d_out_deg.get();
     std::vector<int32_t> out_k(C * batch * k_type * k_oth), out_deg(C * batch * k_type);
     struct Best {
         double dS = std::numeric_limits<double>::infinity();
@@ -469,13 +467,13 @@ int run_split(bisbm_engine* h, int type, int nm) {
         sp.trial0 = (uint32_t)t0;
         sp.n_trials = (uint32_t)nt;
         if (h->wide) {  // (counted with global atomics)
-            SCHK(hipMemsetAsync(d_out_k, 0, sizeof(int32_t) * C * nt * k_type * k_oth, h->stream));
-            SCHK(hipMemsetAsync(d_out_deg, 0, sizeof(int32_t) * C * nt * k_type, h->stream));
+            SCHK(hipMemsetAsync(d_out_k.get(), 0, sizeof(int32_t) * C * nt * k_type * k_oth, h->stream));
+            SCHK(hipMemsetAsync(d_out_deg.get(), 0, sizeof(int32_t) * C * nt * k_type, h->stream));
         }
         SCHK(launch_split_eval(sp, h->stream));
         SCHK(hipStreamSynchronize(h->stream));
-        SCHK(hipMemcpy(out_k.data(), d_out_k, sizeof(int32_t) * C * nt * k_type * k_oth, hipMemcpyDeviceToHost));
-        SCHK(hipMemcpy(out_deg.data(), d_out_deg, sizeof(int32_t) * C * nt * k_type, hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(out_k.data(), d_out_k.get(), sizeof(int32_t) * C * nt * k_type * k_oth, hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(out_deg.data(), d_out_deg.get(), sizeof(int32_t) * C * nt * k_type, hipMemcpyDeviceToHost));
         auto eval_chain = [&](size_t c) {
             for (size_t b = 0; b < k_type; ++b) {
                 if (n_r[c * K + b_lo + b] <= 1) continue;
@@ -508,21 +506,21 @@ int run_split(bisbm_engine* h, int type, int nm) {
             }
         };
         if (!for_each_chain(C, eval_chain)) {  // chains are independent
-            cleanup();
+            settle_labels();
             return fail(h, BISBM_ERR_STATE, "agg_split: host-side evaluation failed (out of memory?)");
         }
     }
     std::vector<uint32_t> chosen(2 * C);
     for (size_t c = 0; c < C; ++c) {
         if (!best[c].found) {  // every dS was +inf or NaN: cannot happen with finite tables
-            cleanup();
+            settle_labels();
             return fail(h, BISBM_ERR_STATE, "chain %zu: no finite split dS", c);
         }
         chosen[2 * c] = best[c].block;
         chosen[2 * c + 1] = best[c].trial;
     }
-    SCHK(hipMemcpy(d_chosen, chosen.data(), sizeof(uint32_t) * chosen.size(), hipMemcpyHostToDevice));
-    sp.chosen = d_chosen;
+    SCHK(hipMemcpy(d_chosen.get(), chosen.data(), sizeof(uint32_t) * chosen.size(), hipMemcpyHostToDevice));
+    sp.chosen = d_chosen.get();
     SCHK(launch_split_apply(sp, h->stream));
     applied = true;
     SCHK(hipStreamSynchronize(h->stream));
@@ -530,7 +528,7 @@ int run_split(bisbm_engine* h, int type, int nm) {
     SCHK(hipMemcpy(h->d_scalars, sc.data(), sizeof(ChainScalars) * C, hipMemcpyHostToDevice));
     if (compat) SCHK(hipMemcpy(h->d_mt_engine, mt_e.data(), sizeof(uint32_t) * mt_e.size(), hipMemcpyHostToDevice));
 #undef SCHK
-    cleanup();
+    settle_labels();
 
     // one block more: the block-state arrays grow with K
     if (type)
@@ -581,10 +579,10 @@ int run_merges(bisbm_engine* h, int which, int diff_a, int diff_b, int nm, std::
     // first node of every label, all chains
     // (label maps hold one entry per block before the call, padded to a multiple of 256; bytes, or two bytes when wide)
     const size_t L = (K0 + 255) & ~(size_t)255, lb = h->lbytes();
-    uint8_t* d_map = nullptr;
-    uint32_t* d_first = nullptr;
-    HIPCHK(h, dalloc(&d_map, C * L * lb));
-    HIPCHK(h, dalloc(&d_first, C * L));
+    DeviceBuf<uint8_t> d_map;
+    DeviceBuf<uint32_t> d_first;
+    RESERVE(h, d_map, C * L * lb);
+    RESERVE(h, d_first, C * L);
     std::vector<uint8_t> ident(C * L * lb);
     for (size_t i = 0; i < C * L; ++i) {
         const uint16_t l = (uint16_t)(i % L);
@@ -593,36 +591,24 @@ int run_merges(bisbm_engine* h, int which, int diff_a, int diff_b, int nm, std::
         else
             ident[i] = (uint8_t)l;
     }
-    auto cleanup = [&]() {
-        (void)hipFree(d_map);
-        (void)hipFree(d_first);
-    };
-#define MCHK(expr)                                                                                     \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            cleanup();                                                                                 \
-            return fail(h, BISBM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                     \
-        }                                                                                              \
-    } while (0)
-    MCHK(hipMemcpy(d_map, ident.data(), ident.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_map.get(), ident.data(), ident.size(), hipMemcpyHostToDevice));
     // (on the handle's stream: it is a non-blocking stream, which a null-stream memset is not ordered with)
-    MCHK(hipMemsetAsync(d_first, 0xff, sizeof(uint32_t) * C * L, h->stream));
-    MCHK(launch_merge_first(h->d_labels, h->wide, h->label_stride, (uint32_t)h->n, h->n_chains, (uint32_t)L, d_map, d_first, h->stream));
-    MCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemsetAsync(d_first.get(), 0xff, sizeof(uint32_t) * C * L, h->stream));
+    HIPCHK(h, launch_merge_first(h->d_labels, h->wide, h->label_stride, (uint32_t)h->n, h->n_chains, (uint32_t)L, d_map.get(), d_first.get(), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<uint32_t> first(C * L);
-    MCHK(hipMemcpy(first.data(), d_first, sizeof(uint32_t) * first.size(), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(first.data(), d_first.get(), sizeof(uint32_t) * first.size(), hipMemcpyDeviceToHost));
     std::vector<int32_t> quad(C * ka0 * kb0);
-    MCHK(hipMemcpy(quad.data(), h->d_m, sizeof(int32_t) * quad.size(), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(quad.data(), h->d_m, sizeof(int32_t) * quad.size(), hipMemcpyDeviceToHost));
     std::vector<ChainScalars> sc(C);
-    MCHK(hipMemcpy(sc.data(), h->d_scalars, sizeof(ChainScalars) * C, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(sc.data(), h->d_scalars, sizeof(ChainScalars) * C, hipMemcpyDeviceToHost));
     std::vector<uint32_t> mt_e, mt_g;
     const bool compat = h->rng_mode == BISBM_RNG_MT19937_COMPAT;
     if (compat) {
         mt_e.resize(C * 624);
         mt_g.resize(C * 624);
-        MCHK(hipMemcpy(mt_e.data(), h->d_mt_engine, sizeof(uint32_t) * mt_e.size(), hipMemcpyDeviceToHost));
-        MCHK(hipMemcpy(mt_g.data(), h->d_mt_gen, sizeof(uint32_t) * mt_g.size(), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(mt_e.data(), h->d_mt_engine, sizeof(uint32_t) * mt_e.size(), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(mt_g.data(), h->d_mt_gen, sizeof(uint32_t) * mt_g.size(), hipMemcpyDeviceToHost));
     }
     auto load_mt = [](std::mt19937& g, const uint32_t* st, uint32_t pos) {  // libstdc++ textual state: 624 words, position
         std::stringstream ss;
@@ -678,45 +664,37 @@ int run_merges(bisbm_engine* h, int which, int diff_a, int diff_b, int nm, std::
             store_mt(mc.gen, &mt_g[c * 624], sc[c].gen_idx);
         }
     };
-    if (!for_each_chain(C, one_chain)) {
-        cleanup();
+    if (!for_each_chain(C, one_chain))
         return fail(h, BISBM_ERR_STATE, "agg_merge: host-side selection failed (out of memory? a chain's merge state is K x K integers)");
-    }
     for (size_t c = 0; c < C; ++c)
-        if (rcs[c] != 0) {
-            cleanup();
+        if (rcs[c] != 0)
             return fail(h, BISBM_ERR_STATE,
                         rcs[c] == -3 ? "chain %zu: agg_merge cannot reach the requested block counts (the reference would recurse without end)"
                                      : "chain %zu: block renumbering inconsistent (the reference's sanity check, blockmodel.cc:605-609)",
                         c);
-        }
     const size_t nka = ends[0].first, nkb = ends[0].second;
     bool diverged = false;
     for (size_t c = 1; c < C; ++c)
         if (ends[c] != ends[0]) {
-            if (!ends_out) {
-                cleanup();
+            if (!ends_out)
                 return fail(h, BISBM_ERR_STATE,
                             "chains ended with different block counts (chain 0: %zu+%zu, chain %zu: %zu+%zu); one (Ka,Kb) per handle",
                             nka, nkb, c, ends[c].first, ends[c].second);
-            }
             diverged = true;
         }
     if (h->wide) {
-        MCHK(hipMemcpy(d_map, fmap.data(), sizeof(uint16_t) * fmap.size(), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(d_map.get(), fmap.data(), sizeof(uint16_t) * fmap.size(), hipMemcpyHostToDevice));
     } else {
         std::vector<uint8_t> fmap8(fmap.begin(), fmap.end());
-        MCHK(hipMemcpy(d_map, fmap8.data(), fmap8.size(), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(d_map.get(), fmap8.data(), fmap8.size(), hipMemcpyHostToDevice));
     }
-    MCHK(launch_merge_relabel(h->d_labels, h->wide, h->label_stride, (uint32_t)h->n, h->n_chains, (uint32_t)L, d_map, h->stream));
-    MCHK(hipMemcpy(h->d_scalars, sc.data(), sizeof(ChainScalars) * C, hipMemcpyHostToDevice));
+    HIPCHK(h, launch_merge_relabel(h->d_labels, h->wide, h->label_stride, (uint32_t)h->n, h->n_chains, (uint32_t)L, d_map.get(), h->stream));
+    HIPCHK(h, hipMemcpy(h->d_scalars, sc.data(), sizeof(ChainScalars) * C, hipMemcpyHostToDevice));
     if (compat) {
-        MCHK(hipMemcpy(h->d_mt_engine, mt_e.data(), sizeof(uint32_t) * mt_e.size(), hipMemcpyHostToDevice));
-        MCHK(hipMemcpy(h->d_mt_gen, mt_g.data(), sizeof(uint32_t) * mt_g.size(), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->d_mt_engine, mt_e.data(), sizeof(uint32_t) * mt_e.size(), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->d_mt_gen, mt_g.data(), sizeof(uint32_t) * mt_g.size(), hipMemcpyHostToDevice));
     }
-    MCHK(hipStreamSynchronize(h->stream));
-#undef MCHK
-    cleanup();
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     if (diverged) {  // every chain's labels are in its own new numbering; the caller regroups the chains by shape
         *ends_out = ends;
         h->state_ready = false;
@@ -912,41 +890,28 @@ int merge_total_grouped(bisbm_engine* h, int diff, int nm) {
 
 int bisbm_agg_merge(bisbm_handle h, int diff_a, int diff_b, int nm) {
     if (!h) return BISBM_ERR_INVALID_ARG;
+    if (h->devs.empty() && h->groups.empty()) return run_merges(h, 0, diff_a, diff_b, nm);
+    // (all or nothing, as for a plain handle: a request a chain of some device or group cannot meet is refused before any changes)
+    for (bisbm_engine* g : leaves(h))
+        if (diff_a >= (int)g->ka || diff_b >= (int)g->kb)
+            return fail(h, BISBM_ERR_STATE, "agg_merge(%d, %d): a chain of this handle has %u + %u blocks", diff_a, diff_b, g->ka, g->kb);
     if (!h->devs.empty()) {
-        // (all or nothing, as for one device: a request a chain of some device cannot meet is refused before any device changes)
-        for (bisbm_engine* d : h->devs)
-            for (bisbm_engine* g : d->groups.empty() ? std::vector<bisbm_engine*>{d} : d->groups)
-                if (diff_a >= (int)g->ka || diff_b >= (int)g->kb)
-                    return fail(h, BISBM_ERR_STATE, "agg_merge(%d, %d): a chain of this handle has %u + %u blocks", diff_a, diff_b, g->ka, g->kb);
         const int rc = on_devices(h, [&](bisbm_engine* d, size_t) { return bisbm_agg_merge(d, diff_a, diff_b, nm); });
-        (void)multi_common_shape(h, nullptr, nullptr);
+        (void)common_shape(h);
         return rc;
     }
-    if (!h->groups.empty()) {  // the same change of counts in every group: each keeps one shape
-        for (bisbm_engine* g : h->groups)  // (all or nothing: a request no chain of some group can meet is refused before any group changes)
-            if (diff_a >= (int)g->ka || diff_b >= (int)g->kb)
-                return fail(h, BISBM_ERR_STATE, "agg_merge(%d, %d): a chain of this handle has %u + %u blocks", diff_a, diff_b, g->ka, g->kb);
-        for (bisbm_engine* g : h->groups) {
-            const int rc = run_merges(g, 0, diff_a, diff_b, nm);
-            if (rc) {
-                h->err = g->err;
-                return rc;
-            }
-        }
-        return BISBM_OK;
-    }
-    return run_merges(h, 0, diff_a, diff_b, nm);
+    // the same change of counts in every group: each keeps one shape
+    return each_group(h, [&](bisbm_engine* g) { return run_merges(g, 0, diff_a, diff_b, nm); });
 }
 
 int bisbm_agg_merge_total(bisbm_handle h, int diff, int nm) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (!h->devs.empty()) {
-        for (bisbm_engine* d : h->devs)
-            for (bisbm_engine* g : d->groups.empty() ? std::vector<bisbm_engine*>{d} : d->groups)
-                if (diff > (int)g->ka + (int)g->kb - 2)
-                    return fail(h, BISBM_ERR_STATE, "agg_merge(%d): a chain of this handle has %u + %u blocks", diff, g->ka, g->kb);
+        for (bisbm_engine* g : leaves(h))
+            if (diff > (int)g->ka + (int)g->kb - 2)
+                return fail(h, BISBM_ERR_STATE, "agg_merge(%d): a chain of this handle has %u + %u blocks", diff, g->ka, g->kb);
         const int rc = on_devices(h, [&](bisbm_engine* d, size_t) { return bisbm_agg_merge_total(d, diff, nm); });
-        (void)multi_common_shape(h, nullptr, nullptr);
+        (void)common_shape(h);
         return rc;
     }
     return merge_total_grouped(h, diff, nm);
@@ -955,12 +920,7 @@ int bisbm_agg_merge_total(bisbm_handle h, int diff, int nm) {
 int bisbm_get_ka_kb_chain(bisbm_handle h, uint32_t chain, uint32_t* ka, uint32_t* kb) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (chain >= h->n_chains) return fail(h, BISBM_ERR_INVALID_ARG, "chain out of range");
-    if (!h->devs.empty()) {
-        uint32_t local;
-        bisbm_engine* d = h->devs[dev_of_chain(h, chain, &local)];
-        return bisbm_get_ka_kb_chain(d, local, ka, kb);
-    }
-    const bisbm_engine* e = h->groups.empty() ? h : h->groups[h->where[chain].first];
+    const bisbm_engine* e = leaf_of_chain(h, chain, &chain);
     if (ka) *ka = e->ka;
     if (kb) *kb = e->kb;
     return BISBM_OK;

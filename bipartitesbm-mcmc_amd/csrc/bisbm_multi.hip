@@ -187,20 +187,6 @@ int pool_prepare(bisbm_engine* h, uint32_t kmax) {
 }  // namespace
 
 // ---- the calls of the C ABI on a container ------------------------------------------------------------------------------
-int multi_common_shape(bisbm_engine* h, uint32_t* ka, uint32_t* kb) {
-    uint32_t a0 = 0, b0 = 0;
-    for (size_t i = 0; i < h->devs.size(); ++i) {
-        uint32_t a, b;
-        if (bisbm_get_ka_kb(h->devs[i], &a, &b) != BISBM_OK || (i > 0 && (a != a0 || b != b0)))
-            return fail(h, BISBM_ERR_STATE, "the chains of this handle have different block counts: ask per chain (bisbm_get_ka_kb_chain)");
-        a0 = a, b0 = b;
-    }
-    h->ka = a0, h->kb = b0, h->K = a0 + b0;
-    if (ka) *ka = a0;
-    if (kb) *kb = b0;
-    return BISBM_OK;
-}
-
 int multi_anneal(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t duration_steps, uint64_t steps_await, double* acc_rate_out) {
     const int rc = on_devices(h, [&](bisbm_engine* d, size_t i) {
         return bisbm_anneal(d, schedule, kwargs, duration_steps, steps_await, acc_rate_out ? acc_rate_out + h->dev_first[i] : nullptr);
@@ -217,7 +203,7 @@ int multi_anneal(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t 
 
 int multi_marginals_get(bisbm_engine* h, uint32_t* counts_out) {
     uint32_t ka, kb;
-    if (int rc = multi_common_shape(h, &ka, &kb)) return rc;
+    if (int rc = shared_shape(h, &ka, &kb)) return rc;
     const size_t cnt = (size_t)h->n * std::max(ka, kb);
     std::memset(counts_out, 0, sizeof(uint32_t) * cnt);
     std::vector<uint32_t> part(cnt);
@@ -233,7 +219,7 @@ int multi_marginals_get(bisbm_engine* h, uint32_t* counts_out) {
 
 int multi_marginals_map(bisbm_engine* h, uint32_t* labels_out) {
     uint32_t ka, kb;
-    if (int rc = multi_common_shape(h, &ka, &kb)) return rc;
+    if (int rc = shared_shape(h, &ka, &kb)) return rc;
     const uint32_t kmax = std::max(ka, kb);
     const size_t nd = h->devs.size();
     for (bisbm_engine* d : h->devs)

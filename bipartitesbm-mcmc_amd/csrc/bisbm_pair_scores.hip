@@ -135,13 +135,6 @@ hipError_t launch_pair_scores_fold(double* sum, const double* part, uint32_t sla
     return hipGetLastError();
 }
 
-void pair_scores_free(bisbm_engine* h) {
-    PairScoreState& s = h->pairs;
-    for (void* p : {(void*)s.d_u, (void*)s.d_v, (void*)s.d_dd, (void*)s.d_sum, (void*)s.d_part})
-        if (p) (void)hipFree(p);
-    s = PairScoreState();
-}
-
 }  // namespace bisbm
 
 namespace {
@@ -151,12 +144,7 @@ int add_sample(bisbm_engine* h, bisbm_engine* e) {
     PairScoreState& s = h->pairs;
     if (!e->state_ready) return fail(h, BISBM_ERR_STATE, "call bisbm_init or bisbm_shuffle before bisbm_pair_scores_accumulate");
     const uint32_t slabs = pair_score_slabs(s.n, e->n_chains);
-    if (s.part_cap < (size_t)slabs * s.n) {
-        if (s.d_part) (void)hipFree(s.d_part);
-        s.d_part = nullptr, s.part_cap = 0;
-        HIPCHK(h, dalloc(&s.d_part, (size_t)slabs * s.n));
-        s.part_cap = (size_t)slabs * s.n;
-    }
+    RESERVE(h, s.d_part, (size_t)slabs * s.n);
     PairScoreParams p{};
     p.n_pairs = (uint32_t)s.n;
     p.na = (uint32_t)h->na;
@@ -164,18 +152,18 @@ int add_sample(bisbm_engine* h, bisbm_engine* e) {
     p.kb = e->kb;
     p.n_chains = e->n_chains;
     p.slabs = slabs;
-    p.u = s.d_u;
-    p.v = s.d_v;
-    p.dd = s.d_dd;
+    p.u = s.d_u.get();
+    p.v = s.d_v.get();
+    p.dd = s.d_dd.get();
     p.labels = e->d_labels;
     p.label_stride = e->label_stride;
     p.wide = e->wide ? 1u : 0u;
     p.m = e->d_m;
     p.m_r = e->d_m_r;
-    p.rung = e->temper.L ? e->temper.d_rung : nullptr;  // replica exchange: the cold chains only
-    p.part = s.d_part;
+    p.rung = e->temper.L ? e->temper.d_rung.get() : nullptr;  // replica exchange: the cold chains only
+    p.part = s.d_part.get();
     HIPCHK(h, launch_pair_scores(p, h->stream));
-    HIPCHK(h, launch_pair_scores_fold(s.d_sum, s.d_part, slabs, p.n_pairs, h->stream));
+    HIPCHK(h, launch_pair_scores_fold(s.d_sum.get(), s.d_part.get(), slabs, p.n_pairs, h->stream));
     s.terms += e->temper.L ? e->n_chains / e->temper.L : e->n_chains;  // (every ensemble has one chain on rung 0)
     return BISBM_OK;
 }
@@ -199,7 +187,7 @@ int bisbm_pair_scores_set(bisbm_handle h, uint64_t n_pairs, const uint32_t* u, c
     }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    pair_scores_free(h);
+    h->pairs = PairScoreState();  // (the old pairs, their sums and buffers go)
     if (n_pairs == 0) return BISBM_OK;
     PairScoreState& s = h->pairs;
     // sorted by (u, v), equal pairs in the caller's order
@@ -209,17 +197,17 @@ int bisbm_pair_scores_set(bisbm_handle h, uint64_t n_pairs, const uint32_t* u, c
     std::vector<uint32_t> su((size_t)n_pairs), sv((size_t)n_pairs);
     s.order.resize((size_t)n_pairs);
     for (size_t i = 0; i < keyed.size(); ++i) su[i] = (uint32_t)(keyed[i].first >> 32), sv[i] = (uint32_t)keyed[i].first, s.order[i] = keyed[i].second;
-    hipError_t e = dalloc(&s.d_u, (size_t)n_pairs);
-    if (e == hipSuccess) e = dalloc(&s.d_v, (size_t)n_pairs);
-    if (e == hipSuccess) e = dalloc(&s.d_dd, (size_t)n_pairs);
-    if (e == hipSuccess) e = dalloc(&s.d_sum, (size_t)n_pairs);
-    if (e == hipSuccess) e = hipMemcpyAsync(s.d_u, su.data(), sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s.d_v, sv.data(), sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s.d_sum, 0, sizeof(double) * n_pairs, h->stream);
-    if (e == hipSuccess) e = launch_pair_degrees(h->d_rowptr, s.d_u, s.d_v, (uint32_t)n_pairs, s.d_dd, h->stream);
+    hipError_t e = s.d_u.reserve((size_t)n_pairs);
+    if (e == hipSuccess) e = s.d_v.reserve((size_t)n_pairs);
+    if (e == hipSuccess) e = s.d_dd.reserve((size_t)n_pairs);
+    if (e == hipSuccess) e = s.d_sum.reserve((size_t)n_pairs);
+    if (e == hipSuccess) e = hipMemcpyAsync(s.d_u.get(), su.data(), sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s.d_v.get(), sv.data(), sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.d_sum.get(), 0, sizeof(double) * n_pairs, h->stream);
+    if (e == hipSuccess) e = launch_pair_degrees(h->d_rowptr, s.d_u.get(), s.d_v.get(), (uint32_t)n_pairs, s.d_dd.get(), h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
-        pair_scores_free(h);
+        h->pairs = PairScoreState();
         return fail(h, BISBM_ERR_HIP, "bisbm_pair_scores_set: %s", hipGetErrorString(e));
     }
     s.n = n_pairs;
@@ -232,12 +220,8 @@ int bisbm_pair_scores_accumulate(bisbm_handle h) {
     if (int rc = refuse_rungs_over_groups(h)) return rc;
     if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_pair_scores_accumulate(d); });
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->groups.empty()) {
-        if (int rc = add_sample(h, h)) return rc;
-    } else {  // chains grouped by shape: every group adds its chains, in group order
-        for (bisbm_engine* g : h->groups)
-            if (int rc = add_sample(h, g)) return rc;
-    }
+    for (bisbm_engine* e : leaves(h))  // (chains grouped by shape: every group adds its chains, in group order)
+        if (int rc = add_sample(h, e)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
 }
@@ -248,7 +232,7 @@ int bisbm_pair_scores_reset(bisbm_handle h) {
     h->pairs.terms = 0;
     if (!h->pairs.n) return BISBM_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemsetAsync(h->pairs.d_sum, 0, sizeof(double) * h->pairs.n, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->pairs.d_sum.get(), 0, sizeof(double) * h->pairs.n, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
 }
@@ -279,7 +263,7 @@ int bisbm_pair_scores_get(bisbm_handle h, double* sum_out, uint64_t* terms_out) 
     HIPCHK(h, hipSetDevice(h->device));
     std::vector<double> sorted(P);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(sorted.data(), h->pairs.d_sum, sizeof(double) * P, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(sorted.data(), h->pairs.d_sum.get(), sizeof(double) * P, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < P; ++i) sum_out[h->pairs.order[i]] = sorted[i];
     return BISBM_OK;
 }

@@ -209,45 +209,21 @@ hipError_t launch_count(uint32_t T, dim3 grid, uint32_t threads, size_t lds, hip
     }
 }
 
-int grow_bytes(bisbm_engine* h, void** p, size_t* cap, size_t bytes, const char* what) {
-    if (*p && *cap >= bytes) return BISBM_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr, *cap = 0;
-    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(h, BISBM_ERR_HIP, "partition distances: %zu bytes of device scratch for %s could not be allocated: %s", bytes, what, hipGetErrorString(e));
-    }
-    *cap = bytes;
-    return BISBM_OK;
-}
-
-void leaves_of(bisbm_engine* h, std::vector<bisbm_engine*>& out) {
-    if (!h->devs.empty()) {
-        for (bisbm_engine* d : h->devs) leaves_of(d, out);
-    } else if (!h->groups.empty()) {
-        for (bisbm_engine* g : h->groups) out.push_back(g);
-    } else {
-        out.push_back(h);
-    }
-}
-
 // the engine whose device computes and whose PartitionState holds the scratch
 bisbm_engine* computing_engine(bisbm_engine* h) { return h->devs.empty() ? h : h->devs[0]; }
 
 // checks the handle, waits for its chains' streams and describes the listed chains on the computing device (rows of chains
 // on another device are copied into the staging buffer: peer copy, through the host where that is refused)
 int describe(bisbm_engine* h, const char* call, const std::vector<uint32_t>& sel, std::vector<ChainDesc>& desc) {
-    std::vector<bisbm_engine*> leaves;
-    leaves_of(h, leaves);
-    for (bisbm_engine* e : leaves)
+    const std::vector<bisbm_engine*> all = leaves(h);
+    for (bisbm_engine* e : all)
         if (e->wide)
             return fail(h, BISBM_ERR_UNSUPPORTED, "partition distances serve byte labels only (at most 256 blocks; this handle has %u + %u)", e->ka, e->kb);
-    for (bisbm_engine* e : leaves)
+    for (bisbm_engine* e : all)
         if (!e->state_ready) return fail(h, BISBM_ERR_STATE, "call bisbm_init or bisbm_shuffle before %s", call);
     // (node indices are 32-bit in the kernels and run up to a workgroup's stride past n)
     if (h->n >= 0xFFFFFFFFull - 8192) return fail(h, BISBM_ERR_UNSUPPORTED, "more than 2^32 - 8193 nodes");
-    for (bisbm_engine* e : leaves) {
+    for (bisbm_engine* e : all) {
         HIPCHK(h, hipSetDevice(e->device));
         HIPCHK(h, hipStreamSynchronize(e->stream));
     }
@@ -273,10 +249,10 @@ int describe(bisbm_engine* h, const char* call, const std::vector<uint32_t>& sel
         }
     }
     if (staged) {
-        if (int rc = grow_bytes(h, (void**)&s.d_stage, &s.stage_cap, staged * srow, "the label rows of chains on other devices")) return rc;
+        RESERVE(h, s.d_stage, staged * srow);
         std::vector<uint8_t> bounce;
         for (size_t k = 0; k < away.size(); ++k) {
-            uint8_t* dst = s.d_stage + k * srow;
+            uint8_t* dst = s.d_stage.get() + k * srow;
             // (on the computing stream: the kernels that read the staging buffer are ordered behind the copy)
             if (hipMemcpyPeerAsync(dst, ce->device, away[k].second, away_dev[k], srow, ce->stream) != hipSuccess) {
                 bounce.resize(srow);
@@ -288,8 +264,8 @@ int describe(bisbm_engine* h, const char* call, const std::vector<uint32_t>& sel
             desc[away[k].first].row = dst;
         }
     }
-    if (int rc = grow_bytes(h, &s.d_desc, &s.desc_cap, sizeof(ChainDesc) * desc.size(), "the chain descriptors")) return rc;
-    HIPCHK(h, hipMemcpyAsync(s.d_desc, desc.data(), sizeof(ChainDesc) * desc.size(), hipMemcpyHostToDevice, ce->stream));
+    RESERVE(h, s.d_desc, sizeof(ChainDesc) * desc.size());
+    HIPCHK(h, hipMemcpyAsync(s.d_desc.get(), desc.data(), sizeof(ChainDesc) * desc.size(), hipMemcpyHostToDevice, ce->stream));
     return BISBM_OK;
 }
 
@@ -324,48 +300,48 @@ int run_pairs(bisbm_engine* h, const std::vector<ChainDesc>& desc, double* snn, 
     HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ce->device));
     // many pairs: a tile per workgroup fills the compute units; few pairs: the nodes are split as well
     const bool fused = !table_out && !direct && (regime == kFused || (regime == kAuto && tiles.size() >= (size_t)cus));
-    if (int rc = grow_bytes(h, &s.d_tiles, &s.tiles_cap, sizeof(uint2) * tiles.size(), "the tile list")) return rc;
-    if (int rc = grow_bytes(h, (void**)&s.d_snn, &s.snn_cap, sizeof(double) * (size_t)m * m, "the pair sums")) return rc;
-    HIPCHK(h, hipMemcpyAsync(s.d_tiles, tiles.data(), sizeof(uint2) * tiles.size(), hipMemcpyHostToDevice, ce->stream));
+    RESERVE(h, s.d_tiles, tiles.size());
+    RESERVE(h, s.d_snn, (size_t)m * m);
+    HIPCHK(h, hipMemcpyAsync(s.d_tiles.get(), tiles.data(), sizeof(uint2) * tiles.size(), hipMemcpyHostToDevice, ce->stream));
     CountParams p{};
-    p.chains = (const ChainDesc*)s.d_desc;
+    p.chains = (const ChainDesc*)s.d_desc.get();
     p.m = m;
     p.n = (uint32_t)h->n;
     p.na = (uint32_t)h->na;
     p.stride = stride;
     p.hbm_direct = direct ? 1u : 0u;
-    p.snn = s.d_snn;
+    p.snn = s.d_snn.get();
     const size_t lds = direct ? 0 : (size_t)T * T * pair_bytes;
     const uint32_t threads = lds > 40 * 1024 ? 1024u : 256u;
     if (fused) {
-        p.tiles = (const uint2*)s.d_tiles;
+        p.tiles = s.d_tiles.get();
         p.nodes_per_block = (p.n + 1023u) & ~1023u;
         HIPCHK(h, launch_count<true>(T, dim3((uint32_t)tiles.size(), 1), threads, lds, ce->stream, p));
     } else {
         const size_t tile_bytes = (size_t)T * T * pair_bytes;
         const size_t per = std::max<size_t>(1, std::min<size_t>(tiles.size(), kTabScratch / tile_bytes));
-        if (int rc = grow_bytes(h, (void**)&s.d_tab, &s.tab_cap, per * tile_bytes, "the contingency tables of one launch")) return rc;
-        p.tab = s.d_tab;
+        RESERVE(h, s.d_tab, per * tile_bytes / sizeof(uint32_t));
+        p.tab = s.d_tab.get();
         for (size_t t0 = 0; t0 < tiles.size(); t0 += per) {
             const uint32_t nb = (uint32_t)std::min(per, tiles.size() - t0);
-            p.tiles = (const uint2*)s.d_tiles + t0;
+            p.tiles = s.d_tiles.get() + t0;
             // about 8 workgroups per compute unit, at least 4096 nodes each (the LDS tables are zeroed and added to HBM once per
             // workgroup)
             const uint32_t max_chunks = (p.n + 4095u) / 4096u, want = 8u * (uint32_t)std::max(cus, 1);
             const uint32_t chunks = std::max(1u, std::min(max_chunks, (want + nb - 1) / nb));
             p.nodes_per_block = (((p.n + chunks - 1) / chunks) + 1023u) & ~1023u;
-            HIPCHK(h, hipMemsetAsync(s.d_tab, 0, (size_t)nb * tile_bytes, ce->stream));
+            HIPCHK(h, hipMemsetAsync(s.d_tab.get(), 0, (size_t)nb * tile_bytes, ce->stream));
             HIPCHK(h, launch_count<false>(T, dim3(nb, (p.n + p.nodes_per_block - 1) / p.nodes_per_block), threads, lds, ce->stream, p));
             if (table_out) {
                 table_out->resize(stride);
-                HIPCHK(h, hipMemcpyAsync(table_out->data(), s.d_tab, pair_bytes, hipMemcpyDeviceToHost, ce->stream));
+                HIPCHK(h, hipMemcpyAsync(table_out->data(), s.d_tab.get(), pair_bytes, hipMemcpyDeviceToHost, ce->stream));
             } else {
                 hipLaunchKernelGGL(partition_reduce_kernel, dim3(nb, T * T), dim3(64), 0, ce->stream, p, T);
                 HIPCHK(h, hipGetLastError());
             }
         }
     }
-    if (snn) HIPCHK(h, hipMemcpyAsync(snn, s.d_snn, sizeof(double) * (size_t)m * m, hipMemcpyDeviceToHost, ce->stream));
+    if (snn) HIPCHK(h, hipMemcpyAsync(snn, s.d_snn.get(), sizeof(double) * (size_t)m * m, hipMemcpyDeviceToHost, ce->stream));
     HIPCHK(h, hipStreamSynchronize(ce->stream));
     return BISBM_OK;
 }
@@ -373,26 +349,15 @@ int run_pairs(bisbm_engine* h, const std::vector<ChainDesc>& desc, double* snn, 
 int run_sizes(bisbm_engine* h, uint32_t m, double* A) {
     bisbm_engine* ce = computing_engine(h);
     PartitionState& s = ce->partition;
-    if (int rc = grow_bytes(h, (void**)&s.d_A, &s.A_cap, sizeof(double) * m, "the per-chain sums")) return rc;
-    hipLaunchKernelGGL(partition_sizes_kernel, dim3(m), dim3(1024), 0, ce->stream, (const ChainDesc*)s.d_desc, (uint32_t)h->n, s.d_A);
+    RESERVE(h, s.d_A, m);
+    hipLaunchKernelGGL(partition_sizes_kernel, dim3(m), dim3(1024), 0, ce->stream, (const ChainDesc*)s.d_desc.get(), (uint32_t)h->n, s.d_A.get());
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(A, s.d_A, sizeof(double) * m, hipMemcpyDeviceToHost, ce->stream));
+    HIPCHK(h, hipMemcpyAsync(A, s.d_A.get(), sizeof(double) * m, hipMemcpyDeviceToHost, ce->stream));
     HIPCHK(h, hipStreamSynchronize(ce->stream));
     return BISBM_OK;
 }
 
 }  // namespace
-
-namespace bisbm {
-
-void partition_free(bisbm_engine* h) {
-    PartitionState& s = h->partition;
-    for (void* p : {s.d_desc, s.d_tiles, (void*)s.d_A, (void*)s.d_snn, (void*)s.d_tab, (void*)s.d_stage})
-        if (p) (void)hipFree(p);
-    s = PartitionState();
-}
-
-}  // namespace bisbm
 
 extern "C" {
 

@@ -54,21 +54,9 @@ __global__ __launch_bounds__(256) void tempering_exchange_kernel(ExchangeParams 
 
 constexpr uint64_t kNoStop = 1ull << 60;  // steps_await of every segment: no early stop (as BlockModel.run_sweeps)
 
-// the engines that run kernels under a handle: a plain handle, or its device entries
-std::vector<bisbm_engine*> leaves(bisbm_engine* h) { return h->devs.empty() ? std::vector<bisbm_engine*>{h} : h->devs; }
-
 int mixed_shapes(bisbm_engine* h) {
-    for (bisbm_engine* e : leaves(h))
-        if (!e->groups.empty())
-            return fail(h, BISBM_ERR_STATE, "the chains of this handle are grouped by shape (a one-argument bisbm_agg_merge_total left different block counts): replica exchange needs one common shape");
-    return BISBM_OK;
-}
-
-template <class T>
-int grow(bisbm_engine* e, T** p, size_t count) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    HIPCHK(e, dalloc(p, count));
+    if (any_grouped(h))
+        return fail(h, BISBM_ERR_STATE, "the chains of this handle are grouped by shape (a one-argument bisbm_agg_merge_total left different block counts): replica exchange needs one common shape");
     return BISBM_OK;
 }
 
@@ -77,25 +65,19 @@ int setup_leaf(bisbm_engine* e, uint32_t L, const float* ladder) {
     TemperState& t = e->temper;
     HIPCHK(e, hipSetDevice(e->device));
     const uint32_t C = e->n_chains;
-    if (t.cap_chains < C || !t.d_T) {
-        if (int rc = grow(e, &t.d_T, C)) return rc;
-        if (int rc = grow(e, &t.d_rung, C)) return rc;
-        if (int rc = grow(e, &t.d_at, C)) return rc;
-        t.cap_chains = C;
-    }
-    if (t.cap_L < L || !t.d_ladder) {
-        if (int rc = grow(e, &t.d_ladder, L)) return rc;
-        if (int rc = grow(e, &t.d_stats, 2 * (size_t)L)) return rc;
-        t.cap_L = L;
-    }
+    RESERVE(e, t.d_T, C);
+    RESERVE(e, t.d_rung, C);
+    RESERVE(e, t.d_at, C);
+    RESERVE(e, t.d_ladder, L);
+    RESERVE(e, t.d_stats, 2 * (size_t)L);
     std::vector<float> T(C);
     std::vector<uint32_t> rung(C), at(C);
     for (uint32_t c = 0; c < C; ++c) T[c] = ladder[c % L], rung[c] = c % L, at[c] = c;
-    HIPCHK(e, hipMemcpyAsync(t.d_T, T.data(), sizeof(float) * C, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(t.d_rung, rung.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(t.d_at, at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(t.d_ladder, ladder, sizeof(float) * L, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemsetAsync(t.d_stats, 0, sizeof(unsigned long long) * 2 * L, e->stream));
+    HIPCHK(e, hipMemcpyAsync(t.d_T.get(), T.data(), sizeof(float) * C, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(t.d_rung.get(), rung.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(t.d_at.get(), at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(t.d_ladder.get(), ladder, sizeof(float) * L, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemsetAsync(t.d_stats.get(), 0, sizeof(unsigned long long) * 2 * L, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     t.L = L;
     t.ladder.assign(ladder, ladder + L);
@@ -122,11 +104,11 @@ int exchange_round(bisbm_engine* e) {
     p.first_gid = e->first_chain_id;
     p.seed = e->seed;
     p.round = t.round;
-    p.ladder = t.d_ladder;
-    p.T = t.d_T;
-    p.rung = t.d_rung;
-    p.at = t.d_at;
-    p.stats = t.d_stats;
+    p.ladder = t.d_ladder.get();
+    p.T = t.d_T.get();
+    p.rung = t.d_rung.get();
+    p.at = t.d_at.get();
+    p.stats = t.d_stats.get();
     const uint32_t lanes = p.n_ens * p.pairs;
     if (lanes) {
         hipLaunchKernelGGL(tempering_exchange_kernel, dim3((lanes + 255) / 256), dim3(256), 0, e->stream, p);
@@ -145,7 +127,7 @@ int run_leaf(bisbm_engine* e, uint64_t sweeps, uint32_t every, double* acc_rate_
     double ms = 0;
     uint64_t updates = 0;
     auto segment = [&](uint64_t k) -> int {
-        if (int rc = anneal_engine(e, BISBM_SCHED_CONSTANT, kw, k * e->n, kNoStop, rate.data(), t.d_T)) return rc;
+        if (int rc = anneal_engine(e, BISBM_SCHED_CONSTANT, kw, k * e->n, kNoStop, rate.data(), t.d_T.get())) return rc;
         for (uint32_t c = 0; c < e->n_chains; ++c) acc[c] += rate[c] * (double)k;  // (rate: accepted / steps of the segment)
         ms += e->last_kernel_ms;
         updates += e->last_updates;
@@ -166,20 +148,6 @@ int run_leaf(bisbm_engine* e, uint64_t sweeps, uint32_t every, double* acc_rate_
 }
 
 }  // namespace
-
-namespace bisbm {
-
-void temper_free(bisbm_engine* h) {
-    TemperState& t = h->temper;
-    void* ptrs[] = {t.d_T, t.d_rung, t.d_at, t.d_ladder, t.d_stats};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    t.d_T = nullptr, t.d_rung = nullptr, t.d_at = nullptr, t.d_ladder = nullptr, t.d_stats = nullptr;
-    t.cap_chains = t.cap_L = 0;
-    t.L = 0;
-}
-
-}  // namespace bisbm
 
 extern "C" {
 
@@ -207,12 +175,12 @@ int bisbm_tempering_set(bisbm_handle h, uint32_t L, const float* ladder) {
     if (h->first_chain_id % L)
         return fail(h, BISBM_ERR_INVALID_ARG, "the first global chain id %u is not a multiple of L = %u: ensembles are global ids [g L, (g + 1) L)",
                     h->first_chain_id, L);
-    for (bisbm_engine* e : leaves(h))
+    for (bisbm_engine* e : device_entries(h))
         if (e->n_chains % L)
             return fail(h, BISBM_ERR_INVALID_ARG, "%s holds %u chains, not a multiple of L = %u: an ensemble may not straddle device entries",
                         h->devs.empty() ? "the handle" : ("the entry of device " + std::to_string(e->device)).c_str(), e->n_chains, L);
     h->temper.L = 0;
-    for (bisbm_engine* e : leaves(h)) {
+    for (bisbm_engine* e : device_entries(h)) {
         if (int rc = setup_leaf(e, L, ladder)) {
             if (e != h) h->err = e->err;
             for (bisbm_engine* d : h->devs) d->temper.L = 0;
@@ -251,12 +219,12 @@ int bisbm_tempering_get(bisbm_handle h, uint32_t* rung_of_chain, float* T_of_cha
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (!h->temper.L) return fail(h, BISBM_ERR_STATE, "replica exchange is off");
     uint32_t first = 0;
-    for (bisbm_engine* e : leaves(h)) {
+    for (bisbm_engine* e : device_entries(h)) {
         HIPCHK(h, hipSetDevice(e->device));
         HIPCHK(h, hipStreamSynchronize(e->stream));
         if (rung_of_chain)
-            HIPCHK(h, hipMemcpy(rung_of_chain + first, e->temper.d_rung, sizeof(uint32_t) * e->n_chains, hipMemcpyDeviceToHost));
-        if (T_of_chain) HIPCHK(h, hipMemcpy(T_of_chain + first, e->temper.d_T, sizeof(float) * e->n_chains, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(rung_of_chain + first, e->temper.d_rung.get(), sizeof(uint32_t) * e->n_chains, hipMemcpyDeviceToHost));
+        if (T_of_chain) HIPCHK(h, hipMemcpy(T_of_chain + first, e->temper.d_T.get(), sizeof(float) * e->n_chains, hipMemcpyDeviceToHost));
         first += e->n_chains;
     }
     return BISBM_OK;
@@ -267,10 +235,10 @@ int bisbm_tempering_stats(bisbm_handle h, uint64_t* attempted, uint64_t* accepte
     if (!h->temper.L) return fail(h, BISBM_ERR_STATE, "replica exchange is off");
     const uint32_t P = h->temper.L - 1;
     std::vector<uint64_t> sum(2 * (size_t)P, 0), part(2 * (size_t)P);
-    for (bisbm_engine* e : leaves(h)) {
+    for (bisbm_engine* e : device_entries(h)) {
         HIPCHK(h, hipSetDevice(e->device));
         HIPCHK(h, hipStreamSynchronize(e->stream));
-        HIPCHK(h, hipMemcpy(part.data(), e->temper.d_stats, sizeof(uint64_t) * 2 * P, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(part.data(), e->temper.d_stats.get(), sizeof(uint64_t) * 2 * P, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < part.size(); ++i) sum[i] += part[i];
     }
     for (uint32_t i = 0; i < P; ++i) {

@@ -98,6 +98,11 @@ def test_devices_behind_one_handle_equal_one_device(graph, devices, mode):
             g.agg_merge(2, None, 10)
             mh.anneal(g, "abrupt_cool", [0.0], n, BIG)
         _same_state(one, many, chains)
+        # a per-chain write where the device entries keep their chains grouped by shape: it lands on the chain's group
+        for g in (one, many):
+            g.set_memberships(g.get_memberships(5).copy(), chain=5)
+            g.init_bisbm()
+        _same_state(one, many, chains)
         assert many.mixed_shapes == one.mixed_shapes
     one.close()
     many.close()
