@@ -34,6 +34,7 @@ BISBM_ERR_HIP = 5
 BISBM_ERR_STATE = 6
 ALIGN_NONE = 0
 ALIGN_REFERENCE = 1
+MODE_NONE = 0xFFFFFFFF  # BISBM_MODE_NONE: a chain that no mode counts
 RNG_PHILOX = 0
 RNG_MT19937_COMPAT = 1
 ALL_CHAINS = -1
@@ -75,6 +76,12 @@ ABI = {
     "bisbm_marginals_get_reference": (C.c_int, [C.c_void_p, _u32p, C.POINTER(C.c_int64)]),
     "bisbm_marginals_get_alignment": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u64p]),
     "bisbm_align_assignment": (C.c_int, [C.c_uint32, _u32p, _u32p, _u64p]),
+    "bisbm_marginals_set_modes": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
+    "bisbm_marginals_get_modes": (C.c_int, [C.c_void_p, _u32p, _u32p, C.POINTER(C.c_int64), _u64p]),
+    "bisbm_marginals_set_mode_reference": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
+    "bisbm_marginals_get_mode_reference": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.POINTER(C.c_int64)]),
+    "bisbm_marginals_get_mode": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
+    "bisbm_marginals_map_mode": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "bisbm_tempering_set": (C.c_int, [C.c_void_p, C.c_uint32, _f32p]),
     "bisbm_tempering_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, _f64p]),
     "bisbm_tempering_get": (C.c_int, [C.c_void_p, _u32p, _f32p]),
@@ -554,10 +561,40 @@ class BlockModel:
         device buffer of n * kmax uint32 / int32 at `device_ptr` (e.g. torch_tensor.data_ptr())."""
         self._check(self._L.bisbm_marginals_accumulate(self._h, C.c_void_p(device_ptr) if device_ptr else None))
 
-    def marginals_get(self):
+    def marginals_get(self, mode=None):
+        """The internal histogram [n, kmax]; with `mode` the histogram of that mode (marginals_set_modes)."""
         out = np.zeros((self.n, self.kmax), dtype=np.uint32)
-        self._check(self._L.bisbm_marginals_get(self._h, _p(out, _u32p)))
+        if mode is None:
+            self._check(self._L.bisbm_marginals_get(self._h, _p(out, _u32p)))
+        else:
+            self._check(self._L.bisbm_marginals_get_mode(self._h, int(mode), _p(out, _u32p)))
         return out
+
+    # -- mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals")
+    def marginals_set_modes(self, mode_of_chain=None, n_modes=None):
+        """One aligned histogram per posterior mode.  `mode_of_chain`: per chain its mode 0 .. M-1 or MODE_NONE (not counted);
+        or the dict partition_modes() returns (chains outside its selection become MODE_NONE); None turns the feature off.
+        `n_modes`: M (default: the highest mode + 1).  Refused while the histogram holds samples (marginals_reset first)."""
+        if mode_of_chain is None:
+            self._check(self._L.bisbm_marginals_set_modes(self._h, 0, None))
+            return
+        moc, n_modes = mode_assignment(mode_of_chain, self.n_chains, n_modes)
+        self._check(self._L.bisbm_marginals_set_modes(self._h, n_modes, _p(moc, _u32p)))
+
+    def marginals_modes(self):
+        """What marginals_set_modes set and what the samples made of it, as a dict: `n_modes`, `mode_of_chain` uint32
+        [n_chains], `ref_chain` int64 [M] (-1: the caller's reference, -2: none yet), `terms` uint64 [M] (chain samples in
+        every mode's histogram), `weights` [M] (each mode's share of the counted chains).  n_modes = 0: the feature is off."""
+        nm = C.c_uint32()
+        self._check(self._L.bisbm_marginals_get_modes(self._h, C.byref(nm), None, None, None))
+        M = nm.value
+        moc = np.full(self.n_chains, MODE_NONE, dtype=np.uint32)
+        ref = np.zeros(max(M, 1), dtype=np.int64)
+        terms = np.zeros(max(M, 1), dtype=np.uint64)
+        self._check(self._L.bisbm_marginals_get_modes(self._h, C.byref(nm), _p(moc, _u32p), _p(ref, C.POINTER(C.c_int64)), _p(terms, _u64p)))
+        size = np.bincount(moc[moc != MODE_NONE].astype(np.int64), minlength=M)[:M]
+        return {"n_modes": M, "mode_of_chain": moc, "ref_chain": ref[:M], "terms": terms[:M],
+                "weights": size / max(int(size.sum()), 1)}
 
     def marginals_set_alignment(self, mode):
         """ALIGN_REFERENCE (or True): every chain's labels are counted through its permutation onto the reference partition
@@ -566,22 +603,30 @@ class BlockModel:
         self._check(self._L.bisbm_marginals_set_alignment(self._h, int(mode)))
         self.alignment = int(mode)
 
-    def marginals_set_reference(self, labels=None):
+    def marginals_set_reference(self, labels=None, mode=None):
         """n labels of the present block counts as the reference of the alignment; None: the lowest-description-length chain,
-        taken at the next aligned sample."""
+        taken at the next aligned sample.  With `mode`: the reference of that mode (marginals_set_modes)."""
+        def call(ptr):
+            if mode is None:
+                return self._L.bisbm_marginals_set_reference(self._h, ptr)
+            return self._L.bisbm_marginals_set_mode_reference(self._h, int(mode), ptr)
         if labels is None:
-            self._check(self._L.bisbm_marginals_set_reference(self._h, None))
+            self._check(call(None))
             return
         lab = np.ascontiguousarray(labels, dtype=np.uint32)
         if len(lab) != self.n:
             raise ValueError("reference has %d labels, graph has %d nodes" % (len(lab), self.n))
-        self._check(self._L.bisbm_marginals_set_reference(self._h, _p(lab, _u32p)))
+        self._check(call(_p(lab, _u32p)))
 
-    def marginals_reference(self):
-        """(labels uint32 [n], chain): the reference of the alignment and the chain it came from (-1: set by the caller)."""
+    def marginals_reference(self, mode=None):
+        """(labels uint32 [n], chain): the reference of the alignment and the chain it came from (-1: set by the caller).  With
+        `mode`: the reference of that mode."""
         out = np.zeros(self.n, dtype=np.uint32)
         chain = C.c_int64()
-        self._check(self._L.bisbm_marginals_get_reference(self._h, _p(out, _u32p), C.byref(chain)))
+        if mode is None:
+            self._check(self._L.bisbm_marginals_get_reference(self._h, _p(out, _u32p), C.byref(chain)))
+        else:
+            self._check(self._L.bisbm_marginals_get_mode_reference(self._h, int(mode), _p(out, _u32p), C.byref(chain)))
         return out, chain.value
 
     def marginals_alignment(self, chain):
@@ -593,12 +638,20 @@ class BlockModel:
         self._check(self._L.bisbm_marginals_get_alignment(self._h, int(chain), _p(perm, _u32p), C.byref(tot)))
         return perm, tot.value
 
-    def marginals_map(self):
+    def marginals_map(self, mode=None, return_top=False):
         """MAP block of every node from the internal histogram (most frequent block, ties -> the lowest), pooled over the
-        handle's devices on the devices (``bisbm_marginals_map``: reduce-scatter -> argmax -> all-gather)."""
+        handle's devices on the devices (``bisbm_marginals_map``: reduce-scatter -> argmax -> all-gather).  With `mode`: the
+        MAP of that mode's histogram in the numbering of the mode's reference, and with `return_top` also every node's winning
+        count (labels, top): top / terms of the mode says how settled the node is within it."""
         out = np.zeros(self.n, dtype=np.uint32)
-        self._check(self._L.bisbm_marginals_map(self._h, _p(out, _u32p)))
-        return out
+        if mode is None:
+            if return_top:
+                raise ValueError("return_top needs a mode (marginals_set_modes)")
+            self._check(self._L.bisbm_marginals_map(self._h, _p(out, _u32p)))
+            return out
+        top = np.zeros(self.n, dtype=np.uint32)
+        self._check(self._L.bisbm_marginals_map_mode(self._h, int(mode), _p(out, _u32p), _p(top, _u32p)))
+        return (out, top) if return_top else out
 
     # -- pair scores (include/bisbm.h, "Posterior-predictive pair scores")
     def pair_scores_set(self, pairs):
@@ -706,6 +759,33 @@ def align_assignment(table):
     return perm, tot.value
 
 
+def mode_assignment(mode_of_chain, n_chains, n_modes=None):
+    """(mode_of_chain uint32 [n_chains], n_modes) from a per-chain array (MODE_NONE: not counted) or from the dict
+    BlockModel.partition_modes returns (chains outside its selection become MODE_NONE).  Needs no device."""
+    if isinstance(mode_of_chain, dict):
+        sel = np.asarray(mode_of_chain["chains"], dtype=np.int64).ravel()
+        mode = np.asarray(mode_of_chain["mode"], dtype=np.int64).ravel()
+        if len(sel) != len(mode) or (len(sel) and (sel.min() < 0 or sel.max() >= n_chains)):
+            raise ValueError("the grouping names chains outside the model's %d" % n_chains)
+        moc = np.full(n_chains, MODE_NONE, dtype=np.uint32)
+        moc[sel] = mode
+        if n_modes is None:
+            n_modes = len(mode_of_chain["medoids"])
+    else:
+        raw = np.asarray(mode_of_chain)
+        if raw.ndim != 1 or len(raw) != n_chains:
+            raise ValueError("mode_of_chain has %s entries, the model has %d chains" % (raw.shape, n_chains))
+        if not np.issubdtype(raw.dtype, np.integer) or (len(raw) and (raw.min() < 0 or raw.max() > MODE_NONE)):
+            raise ValueError("mode_of_chain must hold integers in [0, 2^32)")
+        moc = np.ascontiguousarray(raw, dtype=np.uint32)
+        if n_modes is None:
+            counted = moc[moc != MODE_NONE]
+            n_modes = int(counted.max()) + 1 if len(counted) else 0
+    if int(n_modes) < 1:
+        raise ValueError("no chain is given a mode")
+    return moc, int(n_modes)
+
+
 def partition_modes(vi, threshold):
     """Modes of a symmetric VI matrix [m, m] on the host (bisbm_partition_modes): single linkage over VI <= threshold ->
     (mode uint32 [m], numbered by lowest member; medoids uint32 [n_modes], indices into the matrix).  Needs no device."""
@@ -766,4 +846,4 @@ metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
 from .distributed import ChainShard, numpy_pair_scores, shard_chains  # noqa: E402,F401
-from .marginalize import marginalize  # noqa: E402,F401
+from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

@@ -209,9 +209,11 @@ __global__ __launch_bounds__(256) void marginals_aligned_kernel(MarginalParams p
     }
 }
 
+}  // namespace
+
 // Which overlap-table kernel serves a shape: the per-wave tables up to 64 KiB per workgroup (32 + 32 blocks: 32 KiB), one table
 // per workgroup up to 64 KiB, HBM above.  BISBM_ALIGN_TABLE=wave|block|hbm forces a mode where it fits (tools/align_bench.py).
-int overlap_mode(uint32_t T) {
+int bisbm::overlap_mode(uint32_t T) {
     const size_t limit = 64 * 1024;
     int mode = 4 * sizeof(uint32_t) * (size_t)T <= limit ? kTablePerWave : sizeof(uint32_t) * (size_t)T <= limit ? kTablePerBlock : kTableInHbm;
     if (const char* e = std::getenv("BISBM_ALIGN_TABLE")) {
@@ -220,6 +222,20 @@ int overlap_mode(uint32_t T) {
     }
     return mode;
 }
+
+// (shared with the mode-resolved marginals, bisbm_mode_marginals.hip, like overlap_mode)
+hipError_t bisbm::launch_align_assign(const uint32_t* tab, uint32_t ka, uint32_t kb, uint8_t* perm, uint64_t* tot, uint32_t n_tables, hipStream_t stream) {
+    AssignParams ap{};
+    ap.tab = tab;
+    ap.ka = ka;
+    ap.kb = kb;
+    ap.perm = perm;
+    ap.tot = tot;
+    hipLaunchKernelGGL(align_assign_kernel, dim3(n_tables, 2), dim3(64), 0, stream, ap);
+    return hipGetLastError();
+}
+
+namespace {
 
 hipError_t launch_overlap(const OverlapParams& p0, uint32_t n_chains, hipStream_t stream) {
     OverlapParams p = p0;
@@ -286,14 +302,7 @@ int align_leaf(bisbm_engine* e, const AlignState& top, uint32_t* counts) {
     op.kb = kb;
     op.tab = a.d_tab.get();
     HIPCHK(e, launch_overlap(op, C, e->stream));
-    AssignParams ap{};
-    ap.tab = a.d_tab.get();
-    ap.ka = ka;
-    ap.kb = kb;
-    ap.perm = a.d_perm.get();
-    ap.tot = a.d_tot.get();
-    hipLaunchKernelGGL(align_assign_kernel, dim3(C, 2), dim3(64), 0, e->stream, ap);
-    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, launch_align_assign(a.d_tab.get(), ka, kb, a.d_perm.get(), a.d_tot.get(), C, e->stream));
     MarginalParams mp{};
     mp.n = (uint32_t)e->n;
     mp.na = (uint32_t)e->na;
@@ -424,6 +433,7 @@ int bisbm_marginals_set_alignment(bisbm_handle h, int mode) {
 
 int bisbm_marginals_set_reference(bisbm_handle h, const uint32_t* labels) {
     if (!h) return BISBM_ERR_INVALID_ARG;
+    if (int rc = refuse_while_modes(h, "bisbm_marginals_set_reference", "bisbm_marginals_set_mode_reference")) return rc;
     AlignState& a = h->align;
     if (!labels) {
         a.has_ref = false;
@@ -445,6 +455,7 @@ int bisbm_marginals_set_reference(bisbm_handle h, const uint32_t* labels) {
 
 int bisbm_marginals_get_reference(bisbm_handle h, uint32_t* labels_out, int64_t* chain_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
+    if (int rc = refuse_while_modes(h, "bisbm_marginals_get_reference", "bisbm_marginals_get_mode_reference")) return rc;
     const AlignState& a = h->align;
     if (!a.has_ref) return fail(h, BISBM_ERR_STATE, "no reference partition (none set, and no aligned sample since the last reset)");
     if (labels_out) std::copy(a.ref.begin(), a.ref.end(), labels_out);
@@ -455,6 +466,7 @@ int bisbm_marginals_get_reference(bisbm_handle h, uint32_t* labels_out, int64_t*
 int bisbm_marginals_get_alignment(bisbm_handle h, uint32_t chain, uint32_t* perm_out, uint64_t* overlap_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (chain >= h->n_chains) return fail(h, BISBM_ERR_INVALID_ARG, "chain %u out of range", chain);
+    if (h->modes.n_modes) return mode_get_alignment(h, chain, perm_out, overlap_out);
     uint32_t local = 0;
     bisbm_engine* e = leaf_of_chain(h, chain, &local);
     const AlignState& a = e->align;

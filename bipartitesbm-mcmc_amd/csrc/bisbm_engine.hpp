@@ -13,6 +13,7 @@
 //   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
+//   bisbm_mode_marginals.hip  mode-resolved marginals: one aligned histogram per posterior mode, each with its own reference
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -160,6 +161,42 @@ struct PartitionState {
     DeviceBuf<uint8_t> d_stage;   // label rows of selected chains that live on another device
 };
 
+// Mode-resolved marginals (bisbm_mode_marginals.hip).  The assignment of chains to modes, the references and `terms` belong to
+// the handle the caller holds; the chain list, the buffers and the histogram slices belong to the engines that run the kernels
+// (a plain handle, a device entry: chains grouped by shape are refused).
+struct ModeRef {
+    bool has = false;
+    int64_t chain = -1;           // chain the reference came from; -1: set by the caller
+    uint32_t ka = 0, kb = 0;
+    std::vector<uint32_t> labels; // n labels
+};
+struct ModeState {
+    uint32_t n_modes = 0;            // 0: off
+    std::vector<uint32_t> of_chain;  // [n_chains] mode of every chain of the handle, BISBM_MODE_NONE: not counted
+    std::vector<ModeRef> refs;       // [n_modes]
+    std::vector<uint64_t> terms;     // [n_modes] chain samples in every mode's histogram
+    uint64_t list_serial = 0;        // bumped whenever the assignment changes
+    uint64_t ref_serial = 0;         // bumped whenever a reference changes
+    // kernel-running engine
+    uint64_t list_uploaded = 0, ref_uploaded = 0;
+    std::vector<uint32_t> list;      // counted chains of this engine (index in the engine), sorted by (mode, chain)
+    std::vector<uint32_t> pos;       // [n_chains of the engine] position in `list`, BISBM_MODE_NONE: not counted
+    DeviceBuf<uint32_t> d_list;      // [counted] `list`
+    DeviceBuf<uint32_t> d_mode;      // [counted] mode of every list position
+    DeviceBuf<uint32_t> d_range;     // [n_modes + 1] list positions of every mode
+    DeviceBuf<uint8_t> d_ref;        // [n_modes][label_stride] the references
+    DeviceBuf<uint32_t> d_tab;       // [counted][ka*ka + kb*kb] overlap tables
+    DeviceBuf<uint8_t> d_perm;       // [counted][ka + kb] permutations, global-label form
+    DeviceBuf<uint64_t> d_tot;       // [counted][2] overlap totals per type
+    bool have_perm = false;
+    uint32_t perm_ka = 0, perm_kb = 0;
+    DeviceBuf<uint32_t> d_counts;    // [slices][n][max(hist_ka, hist_kb)] one histogram per mode
+    uint32_t slices = 0, hist_ka = 0, hist_kb = 0;  // what d_counts holds (slices 0: nothing)
+    DeviceBuf<uint32_t> d_sum, d_stage;  // map_mode over several devices: the slices of a mode added on the first device
+    DeviceBuf<uint16_t> d_lab;       // map_mode: labels
+    DeviceBuf<uint32_t> d_top;       // map_mode: winning counts
+};
+
 }  // namespace bisbm
 
 // ------------------------------------------------------------------------------------------
@@ -247,6 +284,7 @@ struct bisbm_engine {
     bisbm::TemperState temper;
     bisbm::PairScoreState pairs;
     bisbm::PartitionState partition;
+    bisbm::ModeState modes;
 };
 
 namespace bisbm {
@@ -425,5 +463,15 @@ int align_accumulate(bisbm_engine* h, uint32_t* device_counts);
 // replica exchange is on and some engine under `h` keeps its chains grouped by shape: BISBM_ERR_STATE with the message of the
 // marginal histogram (a group engine knows no rungs), BISBM_OK otherwise; bisbm_marginals.hip
 int refuse_rungs_over_groups(bisbm_engine* h);
+// pieces of the alignment that the mode-resolved marginals run too; bisbm_align.hip
+int overlap_mode(uint32_t T);  // which overlap-table placement serves tables of T cells: 0 per wave in LDS, 1 per workgroup, 2 HBM
+// the assignment of `n_tables` overlap tables (tab[i][ka*ka + kb*kb]) into perm[i][ka + kb] and tot[i][2]
+hipError_t launch_align_assign(const uint32_t* tab, uint32_t ka, uint32_t kb, uint8_t* perm, uint64_t* tot, uint32_t n_tables, hipStream_t stream);
+// mode-resolved marginals (include/bisbm.h); bisbm_mode_marginals.hip
+int mode_accumulate(bisbm_engine* h, uint32_t* device_counts);  // bisbm_marginals_accumulate while modes are set
+int mode_reset(bisbm_engine* h);                                // ... bisbm_marginals_reset
+int mode_get_alignment(bisbm_engine* h, uint32_t chain, uint32_t* perm_out, uint64_t* overlap_out);  // ... bisbm_marginals_get_alignment
+// BISBM_ERR_STATE with a message that names the per-mode call while modes are set, BISBM_OK otherwise
+int refuse_while_modes(bisbm_engine* h, const char* call, const char* per_mode_call);
 
 }  // namespace bisbm

@@ -36,6 +36,7 @@ int bisbm_marginals_reset(bisbm_handle h) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     h->align.samples = false;
     if (h->align.has_ref && h->align.ref_chain >= 0) h->align.has_ref = false;  // (a caller's reference stays)
+    if (h->modes.n_modes) return mode_reset(h);  // (one histogram per mode instead of the pooled one)
     if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_marginals_reset(d); });
     if (int rc = shared_shape(h, nullptr, nullptr)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
@@ -98,7 +99,7 @@ extern "C" {
 int bisbm_marginals_accumulate(bisbm_handle h, uint32_t* device_counts) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (int rc = refuse_rungs_over_groups(h)) return rc;
-    const int rc = h->align.mode == BISBM_ALIGN_REFERENCE ? align_accumulate(h, device_counts) : accumulate_plain(h, device_counts);
+    const int rc = h->modes.n_modes ? mode_accumulate(h, device_counts) : h->align.mode == BISBM_ALIGN_REFERENCE ? align_accumulate(h, device_counts) : accumulate_plain(h, device_counts);
     if (rc == BISBM_OK && !device_counts) h->align.samples = true;
     return rc;
 }
@@ -106,6 +107,7 @@ int bisbm_marginals_accumulate(bisbm_handle h, uint32_t* device_counts) {
 int bisbm_marginals_get(bisbm_handle h, uint32_t* counts_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (!counts_out) return fail(h, BISBM_ERR_INVALID_ARG, "counts_out is NULL");
+    if (int rc = refuse_while_modes(h, "bisbm_marginals_get", "bisbm_marginals_get_mode")) return rc;
     if (!h->devs.empty()) return multi_marginals_get(h, counts_out);
     if (int rc = shared_shape(h, nullptr, nullptr)) return rc;
     if (!h->d_counts) return fail(h, BISBM_ERR_STATE, "no internal marginal buffer yet");
@@ -121,6 +123,7 @@ int bisbm_marginals_get(bisbm_handle h, uint32_t* counts_out) {
 int bisbm_marginals_map(bisbm_handle h, uint32_t* labels_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (!labels_out) return fail(h, BISBM_ERR_INVALID_ARG, "labels_out is NULL");
+    if (int rc = refuse_while_modes(h, "bisbm_marginals_map", "bisbm_marginals_map_mode")) return rc;
     return h->devs.empty() ? single_marginals_map(h, labels_out) : multi_marginals_map(h, labels_out);
 }
 

@@ -297,6 +297,39 @@ public:
             throw std::runtime_error(std::string("bisbm: ") + bisbm_last_error(nullptr));
         medoids.resize(n_modes);
     }
+    // mode-resolved marginals (include/bisbm.h): the chains' modes (BISBM_MODE_NONE: not counted; an empty vector turns the
+    // feature off), what the samples made of them, a caller's reference of a mode, a mode's histogram and its MAP labels with
+    // every node's winning count
+    void marginals_set_modes(uint32_t n_modes, const std::vector<uint32_t>& mode_of_chain) {
+        if (n_modes && mode_of_chain.size() != n_chains_) throw std::runtime_error("marginals_set_modes: one mode per chain");
+        check(bisbm_marginals_set_modes(h_, n_modes, n_modes ? mode_of_chain.data() : nullptr));
+    }
+    uint32_t marginals_modes(std::vector<uint32_t>& mode_of_chain, std::vector<int64_t>& ref_chain, std::vector<uint64_t>& terms) {
+        uint32_t n_modes = 0;
+        check(bisbm_marginals_get_modes(h_, &n_modes, nullptr, nullptr, nullptr));
+        mode_of_chain.assign(n_chains_, BISBM_MODE_NONE);
+        ref_chain.assign(n_modes, -2);
+        terms.assign(n_modes, 0);
+        check(bisbm_marginals_get_modes(h_, &n_modes, mode_of_chain.data(), ref_chain.data(), terms.data()));
+        return n_modes;
+    }
+    void marginals_set_mode_reference(uint32_t mode, const std::vector<uint32_t>* labels) {
+        if (labels && labels->size() != n_) throw std::runtime_error("marginals_set_mode_reference: one label per node");
+        check(bisbm_marginals_set_mode_reference(h_, mode, labels ? labels->data() : nullptr));
+    }
+    std::vector<uint32_t> marginals_get_mode(uint32_t mode) {
+        uint32_t ka = 0, kb = 0;
+        check(bisbm_get_ka_kb(h_, &ka, &kb));
+        std::vector<uint32_t> counts(n_ * std::max(ka, kb));
+        check(bisbm_marginals_get_mode(h_, mode, counts.data()));
+        return counts;
+    }
+    std::vector<uint32_t> marginals_map_mode(uint32_t mode, std::vector<uint32_t>* top = nullptr) {
+        std::vector<uint32_t> lab(n_);
+        if (top) top->assign(n_, 0);
+        check(bisbm_marginals_map_mode(h_, mode, lab.data(), top ? top->data() : nullptr));
+        return lab;
+    }
     // the marginal estimate of README.md:49-53: every node's most frequent block, pooled over the handle's devices on the
     // devices (bisbm_marginals_map)
     uint_vec_t marginal_map_labels(size_t /*NA*/) {

@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --score_pairs, --modes.
+// --tempering, --exchange_every, --score_pairs, --modes, --mode_marginals.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -49,7 +49,7 @@ const option_spec kOptions[] = {
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
     {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
-    {"modes", 0, 2},
+    {"modes", 0, 2},            {"mode_marginals", 0, 1},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -190,6 +190,12 @@ void print_help(const char* argv0) {
                  "                                        chains joined by a path of pairs with VI <= THRESHOLD share a mode.  OUT\n"
                  "                                        receives `chain mode VI-to-the-mode's-medoid` per sampled chain; the\n"
                  "                                        modes' sizes, shares and medoids are reported on stderr.\n"
+                 "  --mode_marginals PREFIX               With --marginalize --modes: the chains are grouped into modes after the\n"
+                 "                                        burn-in and every mode gets a histogram of its own, aligned to its own\n"
+                 "                                        lowest-description-length chain.  PREFIX.<g>.txt receives `label count`\n"
+                 "                                        per node for mode g (the node's most frequent block within the mode and\n"
+                 "                                        how many chain samples chose it); stdout gets the labels of the heaviest\n"
+                 "                                        mode.  Not with --tempering.\n"
                  "  --csr_cache                           Keep a binary CSR beside the edge list (<path>.bisbm_csr, checked\n"
                  "                                        against the file's size and mtime); the text file stays the input.\n";
 }
@@ -239,6 +245,14 @@ int main(int argc, char const* argv[]) {
             std::cerr << "Invalid --modes. The threshold must be a finite number >= 0 (nats), e.g. --modes modes.txt 0.05.\n";
             return 1;
         }
+    }
+    if (count("mode_marginals") && !var_map.count("modes")) {
+        std::cerr << "--mode_marginals counts one histogram per mode: it needs --modes (with --marginalize) for the grouping.\n";
+        return 1;
+    }
+    if (count("mode_marginals") && count("tempering")) {
+        std::cerr << "--mode_marginals gives every chain a mode of its own: it cannot be combined with --tempering, where chains trade temperatures.\n";
+        return 1;
     }
     // replica exchange: the ladder and the exchange period are checked before anything else runs
     std::vector<float> ladder;
@@ -765,6 +779,23 @@ int main(int argc, char const* argv[]) {
             if (burn_in >= N) advance(burn_in / N);
             blockmodel.marginals_reset();
             if (count("align")) blockmodel.marginals_set_alignment(true);
+            // the sampled chains grouped into modes at `modes_threshold` (--modes): sel = the chains, mode per selected chain,
+            // medoid per mode (positions in sel), vi = their distance matrix
+            std::vector<uint32_t> sel, mode, medoids;
+            std::vector<double> vi;
+            auto group_modes = [&] {
+                sel.clear();
+                const std::vector<uint32_t> rung = ladder.empty() ? std::vector<uint32_t>(opt.n_chains, 0) : blockmodel.tempering_rungs();
+                for (uint32_t c = 0; c < opt.n_chains; ++c)
+                    if (rung[c] == 0) sel.push_back(c);
+                vi = blockmodel.partition_distances(sel);
+                blockmodel_t::partition_modes(vi, sel.size(), modes_threshold, mode, medoids);
+            };
+            const bool per_mode = count("mode_marginals") > 0;
+            if (per_mode) {  // the grouping after the burn-in decides which histogram a chain is counted into
+                group_modes();
+                blockmodel.marginals_set_modes((uint32_t)medoids.size(), mode);
+            }
             if (count("score_pairs")) {  // (--reorder: the engine knows the nodes by their new ids)
                 std::vector<uint32_t> pu, pv;
                 for (auto const& pr : score_pairs) {
@@ -796,7 +827,7 @@ int main(int argc, char const* argv[]) {
                               << (att[i] ? (double)acc[i] / (double)att[i] : 0.) << ")";
                 std::clog << "\n";
             }
-            if (count("align"))
+            if (count("align") && !per_mode)
                 std::clog << "align: labels matched to chain " << blockmodel.marginals_reference_chain() << " (lowest description length)\n";
             if (count("score_pairs")) {
                 const std::string out_path = var_map["score_pairs"][1];
@@ -815,15 +846,43 @@ int main(int argc, char const* argv[]) {
                 }
                 std::clog << "score_pairs: " << score_pairs.size() << " pair(s), " << terms << " chain term(s) each -> " << out_path << "\n";
             }
+            uint_vec_t heaviest_labels;
+            if (per_mode) {
+                std::vector<uint32_t> of_chain;
+                std::vector<int64_t> ref_chain;
+                std::vector<uint64_t> terms;
+                const uint32_t M = blockmodel.marginals_modes(of_chain, ref_chain, terms);
+                std::vector<size_t> size(M, 0);
+                for (uint32_t c : of_chain)
+                    if (c != BISBM_MODE_NONE) size[c] += 1;
+                uint32_t heaviest = 0;
+                std::clog << "mode_marginals: " << M << " mode(s)\n";
+                for (uint32_t g = 0; g < M; ++g) {
+                    if (size[g] > size[heaviest]) heaviest = g;  // (ties -> the lowest mode)
+                    std::vector<uint32_t> top;
+                    const std::vector<uint32_t> lab = blockmodel.marginals_map_mode(g, &top);
+                    const std::string out_path = var_map["mode_marginals"][0] + "." + std::to_string(g) + ".txt";
+                    std::ofstream out(out_path);
+                    double settled = 0.;
+                    for (size_t v = 0; v < N; ++v) {  // (--reorder: the engine knows node v by new_id[v])
+                        const size_t e = new_id.empty() ? v : new_id[v];
+                        out << lab[e] << " " << top[e] << "\n";
+                        settled += (double)top[e] / (double)terms[g];
+                    }
+                    out.close();
+                    if (!out) {
+                        std::cerr << "[error] --mode_marginals: cannot write " << out_path << "\n";
+                        return 1;
+                    }
+                    std::clog << "mode " << g << ": share " << (double)size[g] / (double)sel.size() << ", reference chain "
+                              << opt.first_chain_id + (uint32_t)ref_chain[g] << ", " << terms[g] << " term(s), mean top/terms " << settled / (double)N
+                              << " -> " << out_path << "\n";
+                    if (g == heaviest) heaviest_labels = uint_vec_t(lab.begin(), lab.end());
+                }
+            }
             if (var_map.count("modes")) {  // (a partition's distance to another does not depend on the node numbering: --reorder is fine)
-                std::vector<uint32_t> sel;
-                const std::vector<uint32_t> rung = ladder.empty() ? std::vector<uint32_t>(opt.n_chains, 0) : blockmodel.tempering_rungs();
-                for (uint32_t c = 0; c < opt.n_chains; ++c)
-                    if (rung[c] == 0) sel.push_back(c);
+                group_modes();
                 const size_t m = sel.size();
-                const std::vector<double> vi = blockmodel.partition_distances(sel);
-                std::vector<uint32_t> mode, medoids;
-                blockmodel_t::partition_modes(vi, m, modes_threshold, mode, medoids);
                 const std::vector<double> dl = blockmodel.entropy_all();
                 const std::string out_path = var_map["modes"][0];
                 std::ofstream out(out_path);
@@ -849,7 +908,7 @@ int main(int argc, char const* argv[]) {
                               << opt.first_chain_id + sel[medoids[k]] << ", lowest description length chain " << opt.first_chain_id + sel[low] << "\n";
                 }
             }
-            emit_labels(blockmodel.marginal_map_labels(NA));
+            emit_labels(per_mode ? heaviest_labels : blockmodel.marginal_map_labels(NA));
         } catch (const std::exception& e) {
             std::cerr << e.what() << "\n";
             return 3;

@@ -111,6 +111,67 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     return labels, counts
 
 
+def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None):
+    """Mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): the chains are grouped into posterior modes and
+    every mode gets an aligned histogram and a MAP of its own, in the numbering of its own reference.
+    Exactly one of `threshold` and `mode_of_chain`: with `threshold` the grouping is model.partition_modes(threshold) taken
+    after the burn-in; `mode_of_chain` is a caller's grouping (per chain its mode, or MODE_NONE for a chain not to count).
+    The model's histogram is reset and its modes are set for the run (they stay set); every mode's reference is its member
+    chain of the lowest description length at the first sample.  Returns a dict (M modes):
+      modes      the grouping used: the dict of partition_modes, or the mode_of_chain array
+      labels     uint32 [M, n]        MAP block of every node within the mode
+      top        uint32 [M, n]        that block's count; top / terms[g] says how settled the node is within mode g
+      counts     int64  [M, n, kmax]  the histograms
+      terms      uint64 [M]           chain samples in every histogram
+      weights    [M]                  each mode's share of the counted chains
+      ref_chain  int64  [M]           the chain every mode's reference came from (-1: the caller's)
+      moved      the number of chains whose set of co-members under the same threshold differs after the last sample (0 with
+                 `mode_of_chain`): whether the chains stayed in their modes while they were sampled
+    Chains spread over ranks (`shard`, or model.shard, with world_size > 1) raise ValueError: pooling modes across ranks is
+    not done here."""
+    if (threshold is None) == (mode_of_chain is None):
+        raise ValueError("exactly one of threshold and mode_of_chain must be given")
+    shard = shard if shard is not None else getattr(model, "shard", None)
+    if shard is not None and getattr(shard, "world_size", 1) > 1:
+        raise ValueError("marginalize_modes serves the chains of one rank: pooling modes across ranks is not done here")
+    from . import mode_assignment
+    if mode_of_chain is not None:
+        moc, n_modes = mode_assignment(mode_of_chain, model.n_chains)
+    if burn_in_sweeps > 0:
+        model.run_sweeps(burn_in_sweeps)
+    if threshold is not None:
+        modes = model.partition_modes(threshold)
+        moc, n_modes = mode_assignment(modes, model.n_chains)
+    else:
+        modes = moc.copy()
+    model.marginals_reset()
+    model.marginals_set_modes(moc, n_modes)
+    for _ in range(int(n_samples)):
+        if sampling_frequency_sweeps > 0:
+            model.run_sweeps(sampling_frequency_sweeps)
+        model.marginals_accumulate(None)
+    state = model.marginals_modes()
+    labels = np.zeros((n_modes, model.n), dtype=np.uint32)
+    top = np.zeros((n_modes, model.n), dtype=np.uint32)
+    counts = np.zeros((n_modes, model.n, model.kmax), dtype=np.int64)
+    for g in range(n_modes):
+        counts[g] = model.marginals_get(mode=g)
+        if int(n_samples) > 0:
+            labels[g], top[g] = model.marginals_map(mode=g, return_top=True)
+    moved = 0
+    if threshold is not None:
+        after = model.partition_modes(threshold, chains=modes["chains"])
+        moved = int(sum(_co_members(modes, c) != _co_members(after, c) for c in range(len(modes["chains"]))))
+    return {"modes": modes, "labels": labels, "top": top, "counts": counts, "terms": state["terms"], "weights": state["weights"],
+            "ref_chain": state["ref_chain"], "moved": moved}
+
+
+def _co_members(grouping, i):
+    """The chains that share a mode with the i-th selected chain of a partition_modes dict."""
+    mode = np.asarray(grouping["mode"])
+    return frozenset(np.asarray(grouping["chains"])[mode == mode[i]].tolist())
+
+
 def _drop_library_reference(model):
     """A reference the library took at an earlier run (no reset since) is taken afresh; a caller's stays."""
     from . import BisbmError

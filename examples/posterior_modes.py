@@ -1,7 +1,8 @@
 """How many different answers did the chains find?  64 chains sample partitions of the shipped 1000-node data set from
 independent shuffles; their partitions are compared pair by pair on the device (variation of information, in nats: include/bisbm.h,
 "Partition distances and posterior modes") and grouped into modes: chains joined by a path of pairs with VI <= the threshold share
-a mode.  The threshold is the caller's resolution; here a tenth of the mean partition entropy."""
+a mode.  The threshold is the caller's resolution; here a tenth of the mean partition entropy.  Then every mode gets a marginal
+of its own (include/bisbm.h, "Mode-resolved marginals"): one histogram per mode, aligned to the mode's own reference."""
 import importlib
 import os
 import sys
@@ -34,3 +35,12 @@ print("chains %d and %d, VI %.3f, contingency table:" % (c, d, vi[c, d]))
 print(model.partition_contingency(c, d))
 assert (vi == vi.T).all() and (np.diag(vi) == 0).all() and abs(found["weights"].sum() - 1) < 1e-12
 assert model.partition_contingency(c, d).sum() == na + nb
+
+# each answer by itself: the chains are counted into the histogram of their mode, 10 samples a sweep apart
+out = bisbm.marginalize_modes(model, 0, 10, 1, mode_of_chain=found)
+for g, (weight, ref, terms) in enumerate(zip(out["weights"], out["ref_chain"], out["terms"])):
+    settled = out["top"][g] / terms
+    sizes = np.bincount(out["labels"][g], minlength=10)
+    print("mode %d: share %.3f, aligned to chain %d, %d chain samples, mean top/terms %.3f, %d nodes below 0.9, block sizes %s"
+          % (g, weight, ref, terms, settled.mean(), int((settled < 0.9).sum()), sizes.tolist()))
+assert (out["counts"].sum(axis=2) == out["terms"][:, None]).all() and out["terms"].sum() == 10 * 64

@@ -23,8 +23,9 @@ extern "C" {
 
 /* 2: bisbm_get_ka_kb_chain; KA + KB above 256 (wide mode); handles whose chains differ in shape.
  * 3: bisbm_check_shape; several devices behind one handle (bisbm_create_multi); bisbm_last_pass_steps; later additions: label
- *    alignment (bisbm_marginals_set_alignment ...), replica exchange (bisbm_tempering_*), pair scores (bisbm_pair_scores_*).
- *    Additions only. */
+ *    alignment (bisbm_marginals_set_alignment ...), replica exchange (bisbm_tempering_*), pair scores (bisbm_pair_scores_*),
+ *    partition distances and modes (bisbm_partition_*), mode-resolved marginals (bisbm_marginals_set_modes ...,
+ *    bisbm_marginals_get_mode, bisbm_marginals_map_mode).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -306,6 +307,55 @@ int bisbm_partition_distances(bisbm_handle h, uint32_t n_sel, const uint32_t *ch
 int bisbm_partition_contingency(bisbm_handle h, uint32_t c, uint32_t d, uint32_t *table_out);
 int bisbm_partition_modes(uint32_t m, const double *vi, double threshold, uint32_t *mode_out, uint32_t *medoid_out,
                           uint32_t *n_modes_out);
+
+/* Mode-resolved marginals (no reference counterpart).  Chains at T = 1 settle in different posterior modes
+ * (bisbm_partition_distances / bisbm_partition_modes tell which).  A chain of another mode has no good permutation onto one
+ * common reference, so the pooled aligned histogram smears it over the columns and its MAP describes no mode.  With modes set
+ * there is one histogram PER MODE, each mode aligned to a reference of its own: "the pool holds k answers; here is each one
+ * and how sure we are of every node in it".  Off (the default) nothing else in this file behaves differently.
+ *
+ * set_modes: chain c (index in the handle) is counted into mode mode_of_chain[c] in 0 .. n_modes-1; BISBM_MODE_NONE: the chain
+ *   is not counted.  n_modes = 0 turns the feature off (the pointer may be NULL) and frees the histograms.  Every call drops
+ *   all mode references, the caller's too.  BISBM_ERR_INVALID_ARG: a label >= n_modes that is not BISBM_MODE_NONE, a mode
+ *   without any chain (bisbm_last_error names the chain / the mode).  BISBM_ERR_STATE: the internal histogram, pooled or per
+ *   mode, holds samples (bisbm_marginals_reset first: the rule of bisbm_marginals_set_alignment); replica exchange is on
+ *   (chains trade temperatures, so a chain's membership means nothing across rungs; likewise bisbm_tempering_set with L > 0
+ *   is BISBM_ERR_STATE while modes are set); the chains are grouped by shape (after bisbm_agg_merge_total).
+ * A sample while modes are set is bisbm_marginals_accumulate(h, NULL): every counted chain is counted through its permutation
+ *   onto ITS MODE's reference -- exactly the procedure of "Label alignment before pooling": overlap table per type, the same
+ *   assignment solver, the same tie rule -- into histogram g = mode_of_chain[c], and terms[g] grows by the number of chains
+ *   counted into g.  bisbm_marginals_set_alignment is neither consulted nor changed.  A caller's device_counts is
+ *   BISBM_ERR_UNSUPPORTED; a wide handle is BISBM_ERR_UNSUPPORTED at the sample, chains grouped by shape BISBM_ERR_STATE.
+ * References: the caller's (set_mode_reference: n labels validated as bisbm_marginals_set_reference does; NULL clears), or
+ *   else -- taken at the first sample after a reset -- the labels of the mode's member chain of the lowest bisbm_entropy (ties
+ *   -> the lowest chain).  get_mode_reference: the labels and the chain they came from (-1: the caller's); BISBM_ERR_STATE
+ *   while the mode has none.  The references live with the handle: over several devices a mode may span devices and its
+ *   reference chain may live on another device than the one counting.
+ * get_modes: the assignment, per mode the reference chain (-1: set by the caller, -2: none yet) and terms; any pointer may be
+ *   NULL; *n_modes = 0 and nothing else written while the feature is off.
+ * While modes are set bisbm_marginals_get, bisbm_marginals_map, bisbm_marginals_set_reference and
+ *   bisbm_marginals_get_reference are BISBM_ERR_STATE with a message that names the per-mode call: a sum of histograms in
+ *   different numberings is not a marginal.  bisbm_marginals_get_alignment keeps working: the chain's permutation onto its
+ *   mode's reference at the last sample (an uncounted chain: BISBM_ERR_STATE).
+ * bisbm_marginals_reset zeroes every mode's histogram and terms and drops library-chosen references; the assignment and the
+ *   caller's references stay.  After a merge or split that changes the block counts the histograms start afresh at the next
+ *   sample and library-chosen references are taken afresh; a caller's stale reference is BISBM_ERR_STATE ("set it again").
+ * get_mode: the histogram of one mode, n * kmax counters laid out as bisbm_marginals_get's (several devices: the devices'
+ *   slices added on the host).
+ * map_mode: labels_out[v] = the most frequent block of v in the mode (ties -> the lowest block), in the numbering of the
+ *   mode's reference; top_out[v] (may be NULL) = that block's count, so top_out[v] / terms[mode] says how settled the node is
+ *   within the mode.  Several devices: the slices of the mode are added on the first device, bit for bit what one device with
+ *   all the chains gives.  BISBM_ERR_STATE before the mode's first sample.
+ * Memory: every device holds n_modes * n * kmax * 4 bytes (128 MB per mode at n = 1e6, kmax = 32); an allocation failure is
+ *   BISBM_ERR_HIP with the size in the message.  There is no hidden cap and nothing is subsampled. */
+#define BISBM_MODE_NONE 0xffffffffu
+int bisbm_marginals_set_modes(bisbm_handle h, uint32_t n_modes, const uint32_t *mode_of_chain /* n_chains */);
+int bisbm_marginals_get_modes(bisbm_handle h, uint32_t *n_modes, uint32_t *mode_of_chain /* n_chains */,
+                              int64_t *ref_chain /* n_modes */, uint64_t *terms /* n_modes */);
+int bisbm_marginals_set_mode_reference(bisbm_handle h, uint32_t mode, const uint32_t *labels /* n, NULL clears */);
+int bisbm_marginals_get_mode_reference(bisbm_handle h, uint32_t mode, uint32_t *labels_out, int64_t *chain_out);
+int bisbm_marginals_get_mode(bisbm_handle h, uint32_t mode, uint32_t *counts_out /* n*kmax, host */);
+int bisbm_marginals_map_mode(bisbm_handle h, uint32_t mode, uint32_t *labels_out /* n */, uint32_t *top_out /* n, may be NULL */);
 
 /* blockmodel_t::agg_merge(engine, diff_a, diff_b, nm) (blockmodel.hh, blockmodel.cc:109-206; call sites
  * mcmc_main.cc:385,429,434,446): merge diff_a type-a and diff_b type-b blocks in every chain -- nm proposals per
