@@ -1,12 +1,16 @@
-// bisbm_align.hip -- label alignment of the chains before their samples are pooled into the marginal histogram
-// (include/bisbm.h, "Label alignment before pooling").  A block label means something only inside one chain; per sample and
-// per chain and node type this unit
-//   1. counts the overlap table C[r][s] of the chain's labels with the reference partition (align_overlap_kernel),
+// bisbm_align.hip -- aligned marginal samples (include/bisbm.h, "Label alignment before pooling" and "Mode-resolved
+// marginals").  A block label means something only inside one chain, so before the chains' samples are pooled into a histogram
+// every chain is renumbered to the histogram's reference partition.  A mode-resolved sample keeps one histogram per mode, each
+// with its reference; the pooled aligned sample is the same thing with one mode that holds every chain.  One pipeline serves
+// both, indexed by the position y in the engine's list of counted chains (sorted by (mode, chain)); per sample it
+//   1. counts the overlap table C[r][s] of the labels of chain list[y] with the reference of its mode, per node type
+//      (align_overlap_kernel),
 //   2. finds the permutation of the chain's blocks that maximises the overlap, exactly (align_assign_kernel: one wavefront per
-//      chain and type runs the shortest-augmenting-path assignment of bisbm_align_assignment below),
-//   3. counts the chain's labels through that permutation (marginals_aligned_kernel: the marginals kernel of
-//      bisbm_kernels.hip with the permutation rows staged in LDS).
-// The chains' own state is only read.
+//      position and type runs the shortest-augmenting-path assignment of bisbm_align_assignment below),
+//   3. counts the chain's labels through that permutation into its mode's histogram (marginals_aligned_kernel: a mode's list
+//      positions are contiguous, so their permutation rows are staged in LDS in chunks).
+// Integer adds only: nothing depends on an order.  The chains' own state is only read.  This unit also holds the pooled
+// histogram's part of the C ABI; the per-mode calls are bisbm_mode_marginals.hip.
 #include "bisbm_engine.hpp"
 
 using namespace bisbm;
@@ -16,17 +20,9 @@ namespace {
 constexpr long long kInf = 0x3fffffffffffffffLL;
 
 // ------------------------------------------------------------------------------------------
-// 1. overlap tables: tab[c][ka*ka + kb*kb], type a at 0 (C[r][s] at r*ka + s), type b at ka*ka (r*kb + s), r = the chain's
+// 1. overlap tables: tab[y][ka*ka + kb*kb], type a at 0 (C[r][s] at r*ka + s), type b at ka*ka (r*kb + s), r = the chain's
 // label, s = the reference's, both within the type.  Integer atomics: the tables do not depend on the order of the adds.
 // ------------------------------------------------------------------------------------------
-struct OverlapParams {
-    const uint8_t* labels;  // [chain][label_stride]
-    size_t label_stride;
-    const uint8_t* ref;     // [label_stride] (n used)
-    uint32_t n, na, ka, kb, nodes_per_block;
-    uint32_t* tab;
-};
-
 enum TableMode { kTablePerWave = 0, kTablePerBlock = 1, kTableInHbm = 2 };
 
 // kTablePerWave: a table per wave in LDS (an aligned chain sends most nodes of a wave to the K diagonal cells: the four waves
@@ -35,22 +31,23 @@ enum TableMode { kTablePerWave = 0, kTablePerBlock = 1, kTableInHbm = 2 };
 template <int MODE>
 __global__ __launch_bounds__(256) void align_overlap_kernel(OverlapParams p) {
     extern __shared__ __align__(16) uint32_t lds_tab[];
-    const uint32_t c = blockIdx.y;
+    const uint32_t y = blockIdx.y;
     const uint32_t T = p.ka * p.ka + p.kb * p.kb;
-    uint32_t* out = p.tab + (size_t)c * T;
+    uint32_t* out = p.tab + (size_t)y * T;
     uint32_t* t = MODE == kTableInHbm ? out : lds_tab + (MODE == kTablePerWave ? (threadIdx.x / 64) * T : 0);
     if constexpr (MODE != kTableInHbm) {
         const uint32_t tot = MODE == kTablePerWave ? 4 * T : T;
         for (uint32_t i = threadIdx.x; i < tot; i += 256) lds_tab[i] = 0;
         __syncthreads();
     }
-    const uint8_t* lab = p.labels + (size_t)c * p.label_stride;
+    const uint8_t* lab = p.labels + (size_t)p.list[y] * p.label_stride;
+    const uint8_t* ref = p.ref + (size_t)p.ref_row[y] * p.label_stride;
     const uint32_t v0 = blockIdx.x * p.nodes_per_block;  // (a multiple of 1024: the word loads below are aligned)
     const uint32_t v1 = min(p.n, v0 + p.nodes_per_block);
     for (uint32_t w = v0 + 4 * threadIdx.x; w < v1; w += 4 * 256) {
-        // (w + 3 < label_stride: rows are padded to a multiple of 256 labels, the reference buffer is label_stride bytes)
+        // (w + 3 < label_stride: label rows and reference rows are padded to a multiple of 256 labels)
         const uint32_t L = *(const uint32_t*)(lab + w);
-        const uint32_t R = *(const uint32_t*)(p.ref + w);
+        const uint32_t R = *(const uint32_t*)(ref + w);
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
             const uint32_t v = w + j;
@@ -177,36 +174,55 @@ __global__ __launch_bounds__(64) void align_assign_kernel(AssignParams p) {
 }
 
 // ------------------------------------------------------------------------------------------
-// 3. the marginals kernel (bisbm_kernels.hip) counting perm[c][label] instead of label.  The permutation rows of kPermChunk
-// chains at a time are staged in LDS behind the per-thread counter rows.
+// 3. counting.  Grid (ceil(n / 256), n_modes); thread = node: workgroup (x, g) counts its 256 nodes over the chains of mode g,
+// list positions range[g] .. range[g + 1] - 1, through their permutations into slice g of the histogram.  IN_LDS: one row of
+// (kmax | 1) counters per thread (the odd stride puts the 64 rows of a wave on 64 different banks), then the permutation rows of
+// kPermChunk list positions; otherwise the thread owns row v of slice g and counts straight into it.  COLD_ONLY (replica exchange:
+// the pooled sample only, whose list is the identity): position y is chain y, counted while it is on rung 0.  The test is a
+// template flag because a branch in the loop over the chains keeps the compiler from batching the label loads of four chains,
+// which is worth a third of the kernel's time where nothing is filtered.
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t kPermChunk = 64;
 
-template <bool IN_LDS>
-__global__ __launch_bounds__(256) void marginals_aligned_kernel(MarginalParams p, const uint8_t* perm, uint32_t K) {
-    extern __shared__ __align__(16) uint32_t hist[];  // IN_LDS: one row of (kmax | 1) counters per thread; then the perm rows
+struct AlignedCountParams {
+    uint32_t n, na, ka, kmax, K;
+    const uint8_t* labels;
+    size_t label_stride;
+    const uint32_t* list;   // [position] chain
+    const uint32_t* range;  // [n_modes + 1] positions of every mode
+    const uint32_t* rung;   // [chain] COLD_ONLY: rung of every chain
+    const uint8_t* perm;    // [position][K]
+    uint32_t* counts;       // [n_modes][n][kmax]
+};
+
+template <bool IN_LDS, bool COLD_ONLY>
+__global__ __launch_bounds__(256) void marginals_aligned_kernel(AlignedCountParams p) {
+    extern __shared__ __align__(16) uint32_t hist[];
     const uint32_t stride = p.kmax | 1u;
     uint8_t* pm = (uint8_t*)(hist + (IN_LDS ? 256 * stride : 0u));
+    const uint32_t g = blockIdx.y;
+    const uint32_t y0 = p.range[g], y1 = p.range[g + 1];
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = v < p.n;
     const uint32_t base = v < p.na ? 0u : p.ka;
-    uint32_t* row = IN_LDS ? hist + threadIdx.x * stride : p.counts + (size_t)v * p.kmax;
+    uint32_t* out = p.counts + ((size_t)g * p.n + (live ? v : 0u)) * p.kmax;
+    uint32_t* row = IN_LDS ? hist + threadIdx.x * stride : out;
     if (IN_LDS)
         for (uint32_t j = 0; j < p.kmax; ++j) row[j] = 0;
-    for (uint32_t c0 = 0; c0 < p.n_chains; c0 += kPermChunk) {
-        const uint32_t nc = min(kPermChunk, p.n_chains - c0);
+    for (uint32_t c0 = y0; c0 < y1; c0 += kPermChunk) {
+        const uint32_t nc = min(kPermChunk, y1 - c0);
         __syncthreads();
-        for (uint32_t i = threadIdx.x; i < nc * K; i += 256) pm[i] = perm[(size_t)c0 * K + i];
+        for (uint32_t i = threadIdx.x; i < nc * p.K; i += 256) pm[i] = p.perm[(size_t)c0 * p.K + i];
         __syncthreads();
         if (live)
-            for (uint32_t c = 0; c < nc; ++c)
-                if (!p.rung || p.rung[c0 + c] == 0u) row[(uint32_t)pm[c * K + p.labels[(size_t)(c0 + c) * p.label_stride + v]] - base] += 1;
+            for (uint32_t c = 0; c < nc; ++c) {
+                const uint32_t chain = COLD_ONLY ? c0 + c : p.list[c0 + c];
+                if (!COLD_ONLY || p.rung[chain] == 0u) row[(uint32_t)pm[c * p.K + p.labels[(size_t)chain * p.label_stride + v]] - base] += 1;
+            }
     }
-    if (IN_LDS && live) {
-        uint32_t* out = p.counts + (size_t)v * p.kmax;
+    if (IN_LDS && live)
         for (uint32_t j = 0; j < p.kmax; ++j)
             if (row[j]) out[j] += row[j];
-    }
 }
 
 }  // namespace
@@ -223,7 +239,6 @@ int bisbm::overlap_mode(uint32_t T) {
     return mode;
 }
 
-// (shared with the mode-resolved marginals, bisbm_mode_marginals.hip, like overlap_mode)
 hipError_t bisbm::launch_align_assign(const uint32_t* tab, uint32_t ka, uint32_t kb, uint8_t* perm, uint64_t* tot, uint32_t n_tables, hipStream_t stream) {
     AssignParams ap{};
     ap.tab = tab;
@@ -235,16 +250,14 @@ hipError_t bisbm::launch_align_assign(const uint32_t* tab, uint32_t ka, uint32_t
     return hipGetLastError();
 }
 
-namespace {
-
-hipError_t launch_overlap(const OverlapParams& p0, uint32_t n_chains, hipStream_t stream) {
+hipError_t bisbm::launch_overlap(const OverlapParams& p0, uint32_t n_pos, hipStream_t stream) {
     OverlapParams p = p0;
     const uint32_t T = p.ka * p.ka + p.kb * p.kb;
-    // about 8192 workgroups over all chains, at least 4096 nodes each (the LDS tables are zeroed and summed once per workgroup)
+    // about 8192 workgroups over all tables, at least 4096 nodes each (the LDS tables are zeroed and summed once per workgroup)
     const uint32_t max_chunks = (p.n + 4095) / 4096;
-    const uint32_t chunks = std::max(1u, std::min(max_chunks, (8192 + n_chains - 1) / n_chains));
+    const uint32_t chunks = std::max(1u, std::min(max_chunks, (8192 + n_pos - 1) / n_pos));
     p.nodes_per_block = (((p.n + chunks - 1) / chunks) + 1023) & ~1023u;
-    const dim3 grid((p.n + p.nodes_per_block - 1) / p.nodes_per_block, n_chains), block(256);
+    const dim3 grid((p.n + p.nodes_per_block - 1) / p.nodes_per_block, n_pos), block(256);
     switch (overlap_mode(T)) {
         case kTablePerWave:
             hipLaunchKernelGGL(align_overlap_kernel<kTablePerWave>, grid, block, 4 * sizeof(uint32_t) * T, stream, p);
@@ -258,89 +271,23 @@ hipError_t launch_overlap(const OverlapParams& p0, uint32_t n_chains, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_marginals_aligned(const MarginalParams& p, const uint8_t* perm, uint32_t K, hipStream_t stream) {
-    const size_t pm = kPermChunk * K, hist = sizeof(uint32_t) * 256 * (p.kmax | 1u);
-    const dim3 grid((p.n + 255) / 256), block(256);
+namespace {
+
+template <bool COLD_ONLY>
+hipError_t launch_marginals_aligned(const AlignedCountParams& p, uint32_t n_modes, hipStream_t stream) {
+    const size_t pm = (size_t)kPermChunk * p.K, hist = sizeof(uint32_t) * 256 * (p.kmax | 1u);
+    const dim3 grid((p.n + 255) / 256, n_modes), block(256);
     if (hist + pm > kLdsPerCu) {
-        hipLaunchKernelGGL(marginals_aligned_kernel<false>, grid, block, pm, stream, p, perm, K);
+        hipLaunchKernelGGL((marginals_aligned_kernel<false, COLD_ONLY>), grid, block, pm, stream, p);
         return hipGetLastError();
     }
-    hipError_t e = hipFuncSetAttribute((const void*)marginals_aligned_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(hist + pm));
+    hipError_t e = hipFuncSetAttribute((const void*)marginals_aligned_kernel<true, COLD_ONLY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(hist + pm));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(marginals_aligned_kernel<true>, grid, block, hist + pm, stream, p, perm, K);
+    hipLaunchKernelGGL((marginals_aligned_kernel<true, COLD_ONLY>), grid, block, hist + pm, stream, p);
     return hipGetLastError();
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-
-// one aligned sample of the chains of a kernel-running engine e into counts; `top` holds the reference
-int align_leaf(bisbm_engine* e, const AlignState& top, uint32_t* counts) {
-    AlignState& a = e->align;
-    HIPCHK(e, hipSetDevice(e->device));
-    const uint32_t ka = e->ka, kb = e->kb, K = ka + kb, C = e->n_chains;
-    const size_t T = (size_t)ka * ka + (size_t)kb * kb;
-    RESERVE(e, a.d_ref, e->label_stride);
-    if (a.uploaded != top.serial) {
-        std::vector<uint8_t> ref(e->label_stride, 0);
-        for (uint64_t v = 0; v < e->n; ++v) ref[v] = (uint8_t)top.ref[v];
-        HIPCHK(e, hipMemcpyAsync(a.d_ref.get(), ref.data(), ref.size(), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        a.uploaded = top.serial;
-    }
-    a.have_perm = false;
-    RESERVE(e, a.d_tab, C * T);
-    RESERVE(e, a.d_perm, (size_t)C * K);
-    RESERVE(e, a.d_tot, (size_t)C * 2);
-    HIPCHK(e, hipMemsetAsync(a.d_tab.get(), 0, sizeof(uint32_t) * C * T, e->stream));
-    OverlapParams op{};
-    op.labels = e->d_labels;
-    op.label_stride = e->label_stride;
-    op.ref = a.d_ref.get();
-    op.n = (uint32_t)e->n;
-    op.na = (uint32_t)e->na;
-    op.ka = ka;
-    op.kb = kb;
-    op.tab = a.d_tab.get();
-    HIPCHK(e, launch_overlap(op, C, e->stream));
-    HIPCHK(e, launch_align_assign(a.d_tab.get(), ka, kb, a.d_perm.get(), a.d_tot.get(), C, e->stream));
-    MarginalParams mp{};
-    mp.n = (uint32_t)e->n;
-    mp.na = (uint32_t)e->na;
-    mp.ka = ka;
-    mp.kmax = std::max(ka, kb);
-    mp.n_chains = C;
-    mp.labels = e->d_labels;
-    mp.label_stride = e->label_stride;
-    mp.counts = counts;
-    mp.rung = e->temper.L ? e->temper.d_rung.get() : nullptr;  // replica exchange: the cold chains only
-    HIPCHK(e, launch_marginals_aligned(mp, a.d_perm.get(), K, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    a.have_perm = true, a.perm_ka = ka, a.perm_kb = kb;
-    return BISBM_OK;
-}
-
-// the library's reference: the labels of the lowest-description-length chain (ties -> the lowest global chain id, which is
-// the lowest chain index of the handle); with replica exchange on, among the chains on rung 0
-int pick_reference(bisbm_engine* h, uint32_t ka, uint32_t kb) {
-    uint32_t n_chains = 0;
-    if (int rc = bisbm_get_sizes(h, nullptr, nullptr, nullptr, &n_chains)) return rc;
-    std::vector<double> S(n_chains);
-    if (int rc = bisbm_entropy(h, S.data())) return rc;
-    std::vector<uint32_t> rung(n_chains, 0);
-    if (h->temper.L)
-        if (int rc = bisbm_tempering_get(h, rung.data(), nullptr)) return rc;
-    int64_t pick = -1;
-    for (uint32_t c = 0; c < n_chains; ++c)
-        if (rung[c] == 0u && (pick < 0 || S[c] < S[pick])) pick = c;
-    const uint32_t best = (uint32_t)pick;  // (rung 0 holds n_chains / L >= 1 chains)
-    std::vector<uint32_t> lab((size_t)h->n);
-    if (int rc = bisbm_get_memberships(h, best, lab.data())) return rc;
-    AlignState& a = h->align;
-    a.ref.swap(lab);
-    a.has_ref = true, a.ref_chain = best, a.ref_ka = ka, a.ref_kb = kb;
-    ++a.serial;
-    return BISBM_OK;
-}
 
 // the host solver (include/bisbm.h): the Jonker-Volgenant / Hungarian shortest-augmenting-path form, 1-based with column 0 as
 // the virtual start; the device kernel above runs the same steps
@@ -391,13 +338,123 @@ void solve_assignment(uint32_t K, const uint32_t* C, uint32_t* perm, uint64_t* t
 
 namespace bisbm {
 
+int aligned_sample(bisbm_engine* e, AlignScratch& s, const AlignPlan& plan, uint32_t first, uint32_t* counts) {
+    HIPCHK(e, hipSetDevice(e->device));
+    const uint32_t ka = e->ka, kb = e->kb, K = ka + kb, M = plan.n_modes;
+    const size_t T = (size_t)ka * ka + (size_t)kb * kb;
+    // (pos is empty before a leaf's first sample; the pooled plan's list never moves, and shape groups are leaves of different sizes)
+    if (s.list_uploaded != plan.list_serial || s.pos.size() != e->n_chains) {
+        // the counted chains of this engine sorted by (mode, chain), the positions of every mode
+        s.list.clear();
+        s.pos.assign(e->n_chains, BISBM_MODE_NONE);
+        std::vector<uint32_t> mode, range(M + 1, 0);
+        for (uint32_t g = 0; g < M; ++g) {
+            range[g] = (uint32_t)s.list.size();
+            for (uint32_t c = 0; c < e->n_chains; ++c)
+                if (plan.of_chain ? plan.of_chain[first + c] == g : g == 0) {
+                    s.pos[c] = (uint32_t)s.list.size();
+                    s.list.push_back(c);
+                    mode.push_back(g);
+                }
+        }
+        range[M] = (uint32_t)s.list.size();
+        RESERVE(e, s.d_list, s.list.size());
+        RESERVE(e, s.d_mode, s.list.size());
+        RESERVE(e, s.d_range, M + 1);
+        if (!s.list.empty()) {
+            HIPCHK(e, hipMemcpyAsync(s.d_list.get(), s.list.data(), sizeof(uint32_t) * s.list.size(), hipMemcpyHostToDevice, e->stream));
+            HIPCHK(e, hipMemcpyAsync(s.d_mode.get(), mode.data(), sizeof(uint32_t) * mode.size(), hipMemcpyHostToDevice, e->stream));
+        }
+        HIPCHK(e, hipMemcpyAsync(s.d_range.get(), range.data(), sizeof(uint32_t) * range.size(), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));  // (the host vectors go)
+        s.list_uploaded = plan.list_serial;
+    }
+    s.have_perm = false;
+    const uint32_t Y = (uint32_t)s.list.size();
+    if (!Y) return BISBM_OK;  // (no counted chain lives here: the histograms stay as they are)
+    if (s.ref_uploaded != plan.ref_serial) {
+        RESERVE(e, s.d_ref, (size_t)M * e->label_stride);
+        std::vector<uint8_t> ref((size_t)M * e->label_stride, 0);
+        for (uint32_t g = 0; g < M; ++g)
+            for (uint64_t v = 0; v < e->n; ++v) ref[(size_t)g * e->label_stride + v] = (uint8_t)plan.refs[g].labels[v];
+        HIPCHK(e, hipMemcpyAsync(s.d_ref.get(), ref.data(), ref.size(), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        s.ref_uploaded = plan.ref_serial;
+    }
+    RESERVE(e, s.d_tab, Y * T);
+    RESERVE(e, s.d_perm, (size_t)Y * K);
+    RESERVE(e, s.d_tot, (size_t)Y * 2);
+    HIPCHK(e, hipMemsetAsync(s.d_tab.get(), 0, sizeof(uint32_t) * Y * T, e->stream));
+    OverlapParams op{};
+    op.labels = e->d_labels;
+    op.label_stride = e->label_stride;
+    op.ref = s.d_ref.get();
+    op.list = s.d_list.get();
+    op.ref_row = s.d_mode.get();
+    op.n = (uint32_t)e->n;
+    op.na = (uint32_t)e->na;
+    op.ka = ka;
+    op.kb = kb;
+    op.tab = s.d_tab.get();
+    HIPCHK(e, launch_overlap(op, Y, e->stream));
+    HIPCHK(e, launch_align_assign(s.d_tab.get(), ka, kb, s.d_perm.get(), s.d_tot.get(), Y, e->stream));
+    AlignedCountParams cp{};
+    cp.n = (uint32_t)e->n;
+    cp.na = (uint32_t)e->na;
+    cp.ka = ka;
+    cp.kmax = std::max(ka, kb);
+    cp.K = K;
+    cp.labels = e->d_labels;
+    cp.label_stride = e->label_stride;
+    cp.list = s.d_list.get();
+    cp.range = s.d_range.get();
+    cp.perm = s.d_perm.get();
+    cp.counts = counts;
+    if (e->temper.L) {  // replica exchange: the cold chains only (modes are refused then: the list is the identity)
+        cp.rung = e->temper.d_rung.get();
+        HIPCHK(e, launch_marginals_aligned<true>(cp, M, e->stream));
+    } else {
+        HIPCHK(e, launch_marginals_aligned<false>(cp, M, e->stream));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    s.have_perm = true, s.perm_ka = ka, s.perm_kb = kb;
+    return BISBM_OK;
+}
+
+int refuse_wide_labels(bisbm_engine* h, uint32_t ka, uint32_t kb) {
+    if (!any_wide(h)) return BISBM_OK;
+    return fail(h, BISBM_ERR_UNSUPPORTED, "label alignment serves byte labels only (at most 256 blocks; this handle has %u + %u)", ka, kb);
+}
+
+int check_reference_labels(bisbm_engine* h, const uint32_t* labels, uint32_t ka, uint32_t kb) {
+    for (uint64_t v = 0; v < h->n; ++v) {
+        const bool tb = v >= h->na;
+        if (labels[v] < (tb ? ka : 0u) || labels[v] >= (tb ? ka + kb : ka))
+            return fail(h, BISBM_ERR_INVALID_ARG, "reference label %u of node %llu is outside its type's blocks [%u, %u)", labels[v],
+                        (unsigned long long)v, tb ? ka : 0u, tb ? ka + kb : ka);
+    }
+    return BISBM_OK;
+}
+
+int read_alignment(bisbm_engine* h, bisbm_engine* e, const AlignScratch& s, uint32_t y, uint32_t* perm_out, uint64_t* overlap_out) {
+    const uint32_t K = e->ka + e->kb;
+    std::vector<uint8_t> perm(K);
+    uint64_t tot[2];
+    HIPCHK(h, hipSetDevice(e->device));
+    HIPCHK(h, hipMemcpy(perm.data(), s.d_perm.get() + (size_t)y * K, K, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(tot, s.d_tot.get() + (size_t)y * 2, sizeof(tot), hipMemcpyDeviceToHost));
+    if (perm_out)
+        for (uint32_t r = 0; r < K; ++r) perm_out[r] = perm[r];
+    if (overlap_out) *overlap_out = tot[0] + tot[1];
+    return BISBM_OK;
+}
+
 int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     if (!h->devs.empty() && device_counts)
         return fail(h, BISBM_ERR_UNSUPPORTED, "a handle over several devices accumulates into its own buffers (device_counts must be NULL); bisbm_marginals_map pools them");
     uint32_t ka = 0, kb = 0;
     if (int rc = shared_shape(h, &ka, &kb)) return rc;
-    if (any_wide(h))
-        return fail(h, BISBM_ERR_UNSUPPORTED, "label alignment serves byte labels only (at most 256 blocks; this handle has %u + %u)", ka, kb);
+    if (int rc = refuse_wide_labels(h, ka, kb)) return rc;
     if (!device_counts) {
         // (as without the alignment: a histogram of other block counts is started afresh)
         bool stale = false;
@@ -406,16 +463,31 @@ int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
             if (int rc = bisbm_marginals_reset(h)) return rc;
     }
     AlignState& a = h->align;
-    if (a.has_ref && (a.ref_ka != ka || a.ref_kb != kb)) {
-        if (a.ref_chain < 0)
-            return fail(h, BISBM_ERR_STATE, "the reference partition was set for %u + %u blocks, the chains now have %u + %u: set it again", a.ref_ka,
-                        a.ref_kb, ka, kb);
-        a.has_ref = false;
+    if (a.ref.has && (a.ref.ka != ka || a.ref.kb != kb)) {
+        if (a.ref.chain < 0)
+            return fail(h, BISBM_ERR_STATE, "the reference partition was set for %u + %u blocks, the chains now have %u + %u: set it again", a.ref.ka,
+                        a.ref.kb, ka, kb);
+        a.ref.has = false;
     }
-    if (!a.has_ref)
-        if (int rc = pick_reference(h, ka, kb)) return rc;
-    // every leaf counts into the histogram of its device entry (a group's `root`), or into the caller's
-    return each_leaf(h, [&](bisbm_engine* e) { return align_leaf(e, a, device_counts ? device_counts : (e->root ? e->root : e)->d_counts); });
+    if (!a.ref.has) {
+        // the library's reference: the lowest description length (ties -> the lowest global chain id, which is the lowest chain
+        // index of the handle); with replica exchange on, among the chains on rung 0 (there are n_chains / L >= 1)
+        uint32_t n_chains = 0;
+        if (int rc = bisbm_get_sizes(h, nullptr, nullptr, nullptr, &n_chains)) return rc;
+        std::vector<double> S(n_chains);
+        if (int rc = bisbm_entropy(h, S.data())) return rc;
+        std::vector<uint32_t> rung(n_chains, 0);
+        if (h->temper.L)
+            if (int rc = bisbm_tempering_get(h, rung.data(), nullptr)) return rc;
+        if (int rc = pick_reference(h, S, [&](uint32_t c) { return rung[c] == 0u; }, ka, kb, a.ref)) return rc;
+        ++a.serial;
+    }
+    // one mode that holds every chain of the leaf; every leaf counts into the histogram of its device entry (a group's `root`),
+    // or into the caller's
+    AlignPlan plan;
+    plan.refs = &a.ref;
+    plan.ref_serial = a.serial;
+    return each_leaf(h, [&](bisbm_engine* e) { return aligned_sample(e, e->align.scratch, plan, 0, device_counts ? device_counts : (e->root ? e->root : e)->d_counts); });
 }
 
 }  // namespace bisbm
@@ -436,19 +508,14 @@ int bisbm_marginals_set_reference(bisbm_handle h, const uint32_t* labels) {
     if (int rc = refuse_while_modes(h, "bisbm_marginals_set_reference", "bisbm_marginals_set_mode_reference")) return rc;
     AlignState& a = h->align;
     if (!labels) {
-        a.has_ref = false;
+        a.ref.has = false;
         return BISBM_OK;
     }
     uint32_t ka = 0, kb = 0;
     if (int rc = shared_shape(h, &ka, &kb)) return rc;
-    for (uint64_t v = 0; v < h->n; ++v) {
-        const bool tb = v >= h->na;
-        if (labels[v] < (tb ? ka : 0u) || labels[v] >= (tb ? ka + kb : ka))
-            return fail(h, BISBM_ERR_INVALID_ARG, "reference label %u of node %llu is outside its type's blocks [%u, %u)", labels[v],
-                        (unsigned long long)v, tb ? ka : 0u, tb ? ka + kb : ka);
-    }
-    a.ref.assign(labels, labels + h->n);
-    a.has_ref = true, a.ref_chain = -1, a.ref_ka = ka, a.ref_kb = kb;
+    if (int rc = check_reference_labels(h, labels, ka, kb)) return rc;
+    a.ref.labels.assign(labels, labels + h->n);
+    a.ref.has = true, a.ref.chain = -1, a.ref.ka = ka, a.ref.kb = kb;
     ++a.serial;
     return BISBM_OK;
 }
@@ -456,10 +523,10 @@ int bisbm_marginals_set_reference(bisbm_handle h, const uint32_t* labels) {
 int bisbm_marginals_get_reference(bisbm_handle h, uint32_t* labels_out, int64_t* chain_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (int rc = refuse_while_modes(h, "bisbm_marginals_get_reference", "bisbm_marginals_get_mode_reference")) return rc;
-    const AlignState& a = h->align;
-    if (!a.has_ref) return fail(h, BISBM_ERR_STATE, "no reference partition (none set, and no aligned sample since the last reset)");
-    if (labels_out) std::copy(a.ref.begin(), a.ref.end(), labels_out);
-    if (chain_out) *chain_out = a.ref_chain;
+    const AlignRef& r = h->align.ref;
+    if (!r.has) return fail(h, BISBM_ERR_STATE, "no reference partition (none set, and no aligned sample since the last reset)");
+    if (labels_out) std::copy(r.labels.begin(), r.labels.end(), labels_out);
+    if (chain_out) *chain_out = r.chain;
     return BISBM_OK;
 }
 
@@ -469,19 +536,10 @@ int bisbm_marginals_get_alignment(bisbm_handle h, uint32_t chain, uint32_t* perm
     if (h->modes.n_modes) return mode_get_alignment(h, chain, perm_out, overlap_out);
     uint32_t local = 0;
     bisbm_engine* e = leaf_of_chain(h, chain, &local);
-    const AlignState& a = e->align;
-    if (!a.have_perm || a.perm_ka != e->ka || a.perm_kb != e->kb)
+    const AlignScratch& s = e->align.scratch;
+    if (!s.have_perm || s.perm_ka != e->ka || s.perm_kb != e->kb)
         return fail(h, BISBM_ERR_STATE, "chain %u has no aligned sample of its present block counts", chain);
-    const uint32_t K = e->ka + e->kb;
-    std::vector<uint8_t> perm(K);
-    uint64_t tot[2];
-    HIPCHK(h, hipSetDevice(e->device));
-    HIPCHK(h, hipMemcpy(perm.data(), a.d_perm.get() + (size_t)local * K, K, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(tot, a.d_tot.get() + (size_t)local * 2, sizeof(tot), hipMemcpyDeviceToHost));
-    if (perm_out)
-        for (uint32_t r = 0; r < K; ++r) perm_out[r] = perm[r];
-    if (overlap_out) *overlap_out = tot[0] + tot[1];
-    return BISBM_OK;
+    return read_alignment(h, e, s, s.pos[local], perm_out, overlap_out);
 }
 
 int bisbm_align_assignment(uint32_t k, const uint32_t* table, uint32_t* perm_out, uint64_t* total_out) {

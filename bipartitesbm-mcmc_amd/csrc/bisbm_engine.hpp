@@ -1,5 +1,6 @@
 // bisbm_engine.hpp -- what the translation units of the host side share (internal; the C ABI is include/bisbm.h): the handle,
-// the host-built tables, error / allocation helpers (DeviceBuf: the one owner of a device buffer that grows on demand) and the one
+// the host-built tables, error / allocation helpers (DeviceBuf: the one owner of a device buffer that grows on demand; DeviceGuard:
+// the caller's current device put back), the aligned-sample pipeline that the pooled and the mode-resolved marginals share and the one
 // walk over container handles (chains of several shapes: `groups`; several devices: `devs`): leaves / each_leaf / device_entries /
 // any_grouped / any_wide / shared_shape / leaf_of_chain.
 //
@@ -9,11 +10,12 @@
 //   bisbm_marginals.hip  per-node label histogram, MAP labels of one engine
 //   bisbm_multi.hip      several devices behind one handle: creation, dispatch, pooling (RCCL / peer copies)
 //   bisbm_merge.hip      agg_merge / agg_split between anneals, chains of one handle in different shapes
-//   bisbm_align.hip      label alignment of the chains to a reference partition before their samples are pooled
+//   bisbm_align.hip      aligned marginal samples: every counted chain renumbered to the reference of its mode, then counted (the
+//                        overlap, assignment and counting kernels; one mode of every chain: the pooled aligned histogram)
 //   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
-//   bisbm_mode_marginals.hip  mode-resolved marginals: one aligned histogram per posterior mode, each with its own reference
+//   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -101,25 +103,53 @@ public:
     }
 };
 
-// Label alignment of the marginal histogram (bisbm_align.hip).  The mode, the reference and `samples` belong to the handle
-// the caller holds; the buffers and the last permutations belong to the engines that run the kernels (a plain handle, a
-// group, a device entry).
+// The calling thread's current device, put back when the call returns: the calls that visit every device of a handle on the
+// caller's thread must not move a torch caller's later "current device" allocations with them.
+struct DeviceGuard {
+    int saved = -1;
+    DeviceGuard() {
+        if (hipGetDevice(&saved) != hipSuccess) saved = -1;
+    }
+    ~DeviceGuard() {
+        if (saved >= 0) (void)hipSetDevice(saved);
+    }
+};
+
+// Aligned marginal samples (bisbm_align.hip): the pooled histogram with the alignment on is the mode-resolved one with a single
+// mode that holds every chain, and both run through one pipeline.  The reference partition the chains of a histogram are
+// aligned to:
+struct AlignRef {
+    bool has = false;
+    int64_t chain = -1;           // chain the reference came from; -1: set by the caller
+    uint32_t ka = 0, kb = 0;
+    std::vector<uint32_t> labels; // n labels
+};
+// What an engine that runs the kernels (a plain handle, a group, a device entry) keeps of its aligned samples: the list of its
+// counted chains sorted by (mode, chain) -- everything on the device is indexed by the position in it --, the buffers and the
+// last permutations.
+struct AlignScratch {
+    uint64_t list_uploaded = 0, ref_uploaded = 0;  // serials of what d_list / d_mode / d_range and what d_ref hold
+    std::vector<uint32_t> list;   // counted chains of this engine (index in the engine), sorted by (mode, chain)
+    std::vector<uint32_t> pos;    // [n_chains of the engine] position in `list`, BISBM_MODE_NONE: not counted
+    DeviceBuf<uint32_t> d_list;   // [counted] `list`
+    DeviceBuf<uint32_t> d_mode;   // [counted] mode of every list position: its row of d_ref
+    DeviceBuf<uint32_t> d_range;  // [modes + 1] list positions of every mode
+    DeviceBuf<uint8_t> d_ref;     // [modes][label_stride] the references
+    DeviceBuf<uint32_t> d_tab;    // [counted][ka*ka + kb*kb] overlap tables
+    DeviceBuf<uint8_t> d_perm;    // [counted][ka + kb] permutations, global-label form
+    DeviceBuf<uint64_t> d_tot;    // [counted][2] overlap totals per type
+    bool have_perm = false;
+    uint32_t perm_ka = 0, perm_kb = 0;
+};
+
+// Label alignment of the pooled marginal histogram.  The mode, the reference and `samples` belong to the handle the caller
+// holds; `scratch` belongs to the engines that run the kernels.
 struct AlignState {
     int mode = 0;                 // BISBM_ALIGN_NONE / BISBM_ALIGN_REFERENCE
     bool samples = false;         // the internal histogram holds samples (a mode change is refused then)
-    bool has_ref = false;
-    int64_t ref_chain = -1;       // chain the reference came from; -1: set by the caller
-    uint32_t ref_ka = 0, ref_kb = 0;
-    std::vector<uint32_t> ref;    // n labels
+    AlignRef ref;
     uint64_t serial = 0;          // bumped whenever the reference changes
-    // kernel-running engine
-    uint64_t uploaded = 0;        // serial of the reference in d_ref
-    DeviceBuf<uint8_t> d_ref;     // label_stride bytes
-    DeviceBuf<uint32_t> d_tab;    // [chain][ka*ka + kb*kb] overlap tables
-    DeviceBuf<uint8_t> d_perm;    // [chain][ka + kb] permutation, global-label form
-    DeviceBuf<uint64_t> d_tot;    // [chain][2] overlap totals per type
-    bool have_perm = false;
-    uint32_t perm_ka = 0, perm_kb = 0;
+    AlignScratch scratch;         // kernel-running engine
 };
 
 // Replica exchange (bisbm_tempering.hip).  The ladder and the round counter belong to the handle the caller holds and are
@@ -162,34 +192,17 @@ struct PartitionState {
 };
 
 // Mode-resolved marginals (bisbm_mode_marginals.hip).  The assignment of chains to modes, the references and `terms` belong to
-// the handle the caller holds; the chain list, the buffers and the histogram slices belong to the engines that run the kernels
-// (a plain handle, a device entry: chains grouped by shape are refused).
-struct ModeRef {
-    bool has = false;
-    int64_t chain = -1;           // chain the reference came from; -1: set by the caller
-    uint32_t ka = 0, kb = 0;
-    std::vector<uint32_t> labels; // n labels
-};
+// the handle the caller holds; `scratch` and the histogram slices belong to the engines that run the kernels (a plain handle, a
+// device entry: chains grouped by shape are refused).
 struct ModeState {
     uint32_t n_modes = 0;            // 0: off
     std::vector<uint32_t> of_chain;  // [n_chains] mode of every chain of the handle, BISBM_MODE_NONE: not counted
-    std::vector<ModeRef> refs;       // [n_modes]
+    std::vector<AlignRef> refs;      // [n_modes]
     std::vector<uint64_t> terms;     // [n_modes] chain samples in every mode's histogram
     uint64_t list_serial = 0;        // bumped whenever the assignment changes
     uint64_t ref_serial = 0;         // bumped whenever a reference changes
     // kernel-running engine
-    uint64_t list_uploaded = 0, ref_uploaded = 0;
-    std::vector<uint32_t> list;      // counted chains of this engine (index in the engine), sorted by (mode, chain)
-    std::vector<uint32_t> pos;       // [n_chains of the engine] position in `list`, BISBM_MODE_NONE: not counted
-    DeviceBuf<uint32_t> d_list;      // [counted] `list`
-    DeviceBuf<uint32_t> d_mode;      // [counted] mode of every list position
-    DeviceBuf<uint32_t> d_range;     // [n_modes + 1] list positions of every mode
-    DeviceBuf<uint8_t> d_ref;        // [n_modes][label_stride] the references
-    DeviceBuf<uint32_t> d_tab;       // [counted][ka*ka + kb*kb] overlap tables
-    DeviceBuf<uint8_t> d_perm;       // [counted][ka + kb] permutations, global-label form
-    DeviceBuf<uint64_t> d_tot;       // [counted][2] overlap totals per type
-    bool have_perm = false;
-    uint32_t perm_ka = 0, perm_kb = 0;
+    AlignScratch scratch;            // (its own, not AlignState's: a pooled sample's permutations are not a mode's)
     DeviceBuf<uint32_t> d_counts;    // [slices][n][max(hist_ka, hist_kb)] one histogram per mode
     uint32_t slices = 0, hist_ka = 0, hist_kb = 0;  // what d_counts holds (slices 0: nothing)
     DeviceBuf<uint32_t> d_sum, d_stage;  // map_mode over several devices: the slices of a mode added on the first device
@@ -463,10 +476,51 @@ int align_accumulate(bisbm_engine* h, uint32_t* device_counts);
 // replica exchange is on and some engine under `h` keeps its chains grouped by shape: BISBM_ERR_STATE with the message of the
 // marginal histogram (a group engine knows no rungs), BISBM_OK otherwise; bisbm_marginals.hip
 int refuse_rungs_over_groups(bisbm_engine* h);
-// pieces of the alignment that the mode-resolved marginals run too; bisbm_align.hip
+// ---- the aligned-sample pipeline, for the pooled histogram and the mode-resolved ones alike; bisbm_align.hip ----
 int overlap_mode(uint32_t T);  // which overlap-table placement serves tables of T cells: 0 per wave in LDS, 1 per workgroup, 2 HBM
-// the assignment of `n_tables` overlap tables (tab[i][ka*ka + kb*kb]) into perm[i][ka + kb] and tot[i][2]
+// step 1: the overlap table tab[y] of every list position y < n_pos: the labels of chain list[y] with row ref_row[y] of `ref`
+struct OverlapParams {
+    const uint8_t* labels;     // [chain][label_stride]
+    size_t label_stride;
+    const uint8_t* ref;        // [rows][label_stride] (n used)
+    const uint32_t* list;      // [position] chain
+    const uint32_t* ref_row;   // [position] row of `ref`
+    uint32_t n, na, ka, kb, nodes_per_block;  // (nodes_per_block: the launcher's)
+    uint32_t* tab;             // [position][ka*ka + kb*kb], zeroed
+};
+hipError_t launch_overlap(const OverlapParams& p, uint32_t n_pos, hipStream_t stream);
+// step 2: the assignment of `n_tables` overlap tables (tab[i][ka*ka + kb*kb]) into perm[i][ka + kb] and tot[i][2]
 hipError_t launch_align_assign(const uint32_t* tab, uint32_t ka, uint32_t kb, uint8_t* perm, uint64_t* tot, uint32_t n_tables, hipStream_t stream);
+// What one aligned sample counts: the chains of the handle sorted into `n_modes` histograms, each with its reference.
+struct AlignPlan {
+    uint32_t n_modes = 1;
+    const uint32_t* of_chain = nullptr;  // [chains of the handle] mode of every chain, BISBM_MODE_NONE: not counted; NULL: all in mode 0
+    const AlignRef* refs = nullptr;      // [n_modes]
+    uint64_t list_serial = 0, ref_serial = 0;  // move with of_chain / with a reference
+};
+// One aligned sample of the chains of kernel-running engine e (chains first .. of the handle) into counts[mode][n][kmax]: the
+// three steps over e's list of counted chains.  With replica exchange on only the cold chains are counted; that goes with the
+// pooled plan alone (modes refuse replica exchange): the counting kernel then takes list position y for chain y.
+int aligned_sample(bisbm_engine* e, AlignScratch& s, const AlignPlan& plan, uint32_t first, uint32_t* counts);
+// BISBM_ERR_UNSUPPORTED while some leaf holds two-byte labels
+int refuse_wide_labels(bisbm_engine* h, uint32_t ka, uint32_t kb);
+// BISBM_ERR_INVALID_ARG unless every label of a caller's reference is a block of its node's type
+int check_reference_labels(bisbm_engine* h, const uint32_t* labels, uint32_t ka, uint32_t kb);
+// the library's reference: the labels of the chain of the lowest description length S[c] among those with counted(c) (ties ->
+// the lowest chain; there is one)
+template <class Pred>
+int pick_reference(bisbm_engine* h, const std::vector<double>& S, Pred counted, uint32_t ka, uint32_t kb, AlignRef& r) {
+    int64_t pick = -1;
+    for (uint32_t c = 0; c < S.size(); ++c)
+        if (counted(c) && (pick < 0 || S[c] < S[pick])) pick = c;
+    std::vector<uint32_t> lab((size_t)h->n);
+    if (int rc = bisbm_get_memberships(h, (uint32_t)pick, lab.data())) return rc;
+    r.labels.swap(lab);
+    r.has = true, r.chain = pick, r.ka = ka, r.kb = kb;
+    return BISBM_OK;
+}
+// the permutation and the overlap total of list position y of the last sample of e
+int read_alignment(bisbm_engine* h, bisbm_engine* e, const AlignScratch& s, uint32_t y, uint32_t* perm_out, uint64_t* overlap_out);
 // mode-resolved marginals (include/bisbm.h); bisbm_mode_marginals.hip
 int mode_accumulate(bisbm_engine* h, uint32_t* device_counts);  // bisbm_marginals_accumulate while modes are set
 int mode_reset(bisbm_engine* h);                                // ... bisbm_marginals_reset

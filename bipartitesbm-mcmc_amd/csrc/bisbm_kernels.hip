@@ -911,9 +911,9 @@ __global__ __launch_bounds__(256) void marginals_kernel(MarginalParams p) {
 
 // MAP block of the nodes first .. first + rows - 1 from (a slice of) the pooled histogram: the most frequent block of the
 // node's type, ties -> the lowest index (README.md:49-53: "the marginal estimate"), in the reference's numbering (type-b
-// blocks offset by ka).  Thread = node; `counts` points at the row of node `first`.
+// blocks offset by ka).  Thread = node; `counts` points at the row of node `first`.  top_out (may be NULL): the winning count.
 __global__ __launch_bounds__(256) void marginal_map_kernel(const uint32_t* counts, uint32_t rows, uint32_t kmax, uint32_t first,
-                                                           uint32_t n, uint32_t na, uint32_t ka, uint16_t* labels_out) {
+                                                           uint32_t n, uint32_t na, uint32_t ka, uint16_t* labels_out, uint32_t* top_out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows) return;
     const uint32_t v = first + i;
@@ -927,6 +927,7 @@ __global__ __launch_bounds__(256) void marginal_map_kernel(const uint32_t* count
         arg += v < na ? 0u : ka;
     }
     labels_out[i] = (uint16_t)arg;
+    if (top_out) top_out[i] = best;
 }
 
 // a[i] += b[i]: the owner of a node range adds another device's slice of the histogram (peer-copy pooling path)
@@ -1392,9 +1393,9 @@ hipError_t launch_log_q_probe(const Tables& tab, const int32_t* n, const int32_t
 }
 
 hipError_t launch_marginal_map(const uint32_t* counts, uint32_t rows, uint32_t kmax, uint32_t first, uint32_t n, uint32_t na,
-                               uint32_t ka, uint16_t* labels_out, hipStream_t stream) {
+                               uint32_t ka, uint16_t* labels_out, uint32_t* top_out, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(marginal_map_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, counts, rows, kmax, first, n, na, ka, labels_out);
+    hipLaunchKernelGGL(marginal_map_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, counts, rows, kmax, first, n, na, ka, labels_out, top_out);
     return hipGetLastError();
 }
 

@@ -283,9 +283,10 @@ hipError_t launch_merge_relabel(uint8_t* labels, bool wide, size_t label_stride,
 hipError_t launch_shuffle(const ShuffleParams& p, int rng_mode, hipStream_t stream);
 hipError_t launch_entropy(const EntropyParams& p, hipStream_t stream);
 hipError_t launch_marginals(const MarginalParams& p, hipStream_t stream);
-// MAP labels of `rows` nodes from the histogram rows at `counts` (node `first` on); a += b over `count` counters
+// MAP labels of `rows` nodes from the histogram rows at `counts` (node `first` on), with the winning counts where top_out is
+// not NULL; a += b over `count` counters
 hipError_t launch_marginal_map(const uint32_t* counts, uint32_t rows, uint32_t kmax, uint32_t first, uint32_t n, uint32_t na,
-                               uint32_t ka, uint16_t* labels_out, hipStream_t stream);
+                               uint32_t ka, uint16_t* labels_out, uint32_t* top_out, hipStream_t stream);
 hipError_t launch_counts_add(uint32_t* a, const uint32_t* b, size_t count, hipStream_t stream);
 // dd[i] = (double)d(u[i]) * (double)d(v[i]) from the CSR row lengths
 hipError_t launch_pair_degrees(const uint32_t* rowptr, const uint32_t* u, const uint32_t* v, uint32_t n_pairs, double* dd, hipStream_t stream);

@@ -14,7 +14,7 @@ int single_marginals_map(bisbm_engine* h, uint32_t* labels_out) {
     DeviceBuf<uint16_t> d_lab;
     RESERVE(h, d_lab, (size_t)h->n);
     std::vector<uint16_t> lab((size_t)h->n);
-    HIPCHK(h, launch_marginal_map(h->d_counts, (uint32_t)h->n, h->counts_cols, 0, (uint32_t)h->n, (uint32_t)h->na, h->ka, d_lab.get(), h->stream));
+    HIPCHK(h, launch_marginal_map(h->d_counts, (uint32_t)h->n, h->counts_cols, 0, (uint32_t)h->n, (uint32_t)h->na, h->ka, d_lab.get(), nullptr, h->stream));
     HIPCHK(h, hipMemcpyAsync(lab.data(), d_lab.get(), sizeof(uint16_t) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (uint64_t v = 0; v < h->n; ++v) labels_out[v] = lab[v];
@@ -35,7 +35,7 @@ extern "C" {
 int bisbm_marginals_reset(bisbm_handle h) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     h->align.samples = false;
-    if (h->align.has_ref && h->align.ref_chain >= 0) h->align.has_ref = false;  // (a caller's reference stays)
+    if (h->align.ref.has && h->align.ref.chain >= 0) h->align.ref.has = false;  // (a caller's reference stays)
     if (h->modes.n_modes) return mode_reset(h);  // (one histogram per mode instead of the pooled one)
     if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_marginals_reset(d); });
     if (int rc = shared_shape(h, nullptr, nullptr)) return rc;

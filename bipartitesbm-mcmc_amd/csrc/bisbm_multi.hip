@@ -73,18 +73,6 @@ namespace bisbm {
 
 namespace {
 
-// the calling thread's current device, put back when the call returns (the pooling calls visit every device of the handle on
-// the caller's thread; a torch caller's later "current device" allocations must not move with them)
-struct DeviceGuard {
-    int saved = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&saved) != hipSuccess) saved = -1;
-    }
-    ~DeviceGuard() {
-        if (saved >= 0) (void)hipSetDevice(saved);
-    }
-};
-
 void pool_free(bisbm_engine* h) {
     DevicePool* P = h->pool;
     if (!P) return;
@@ -246,7 +234,7 @@ int multi_marginals_map(bisbm_engine* h, uint32_t* labels_out) {
         if (r != ncclSuccess || re != ncclSuccess) return fail(h, BISBM_ERR_HIP, "ncclReduceScatter: %s", R.GetErrorString(r != ncclSuccess ? r : re));
         for (size_t i = 0; i < nd; ++i) {
             HIPCHK(h, hipSetDevice(h->devs[i]->device));
-            HIPCHK(h, launch_marginal_map(P->d_red[i], (uint32_t)per, kmax, (uint32_t)(i * per), (uint32_t)h->n, (uint32_t)h->na, ka, P->d_lab[i], h->devs[i]->stream));
+            HIPCHK(h, launch_marginal_map(P->d_red[i], (uint32_t)per, kmax, (uint32_t)(i * per), (uint32_t)h->n, (uint32_t)h->na, ka, P->d_lab[i], nullptr, h->devs[i]->stream));
         }
         r = R.GroupStart();
         if (r != ncclSuccess) return fail(h, BISBM_ERR_HIP, "ncclGroupStart: %s", R.GetErrorString(r));
@@ -278,7 +266,7 @@ int multi_marginals_map(bisbm_engine* h, uint32_t* labels_out) {
             HIPCHK(d, hipMemcpyPeerAsync(P->d_stage[i], d->device, h->devs[j]->d_counts + i * slice, h->devs[j]->device, sizeof(uint32_t) * slice, d->stream));
             HIPCHK(d, launch_counts_add(P->d_red[i], P->d_stage[i], slice, d->stream));
         }
-        HIPCHK(d, launch_marginal_map(P->d_red[i], (uint32_t)per, kmax, (uint32_t)(i * per), (uint32_t)h->n, (uint32_t)h->na, ka, P->d_lab[i], d->stream));
+        HIPCHK(d, launch_marginal_map(P->d_red[i], (uint32_t)per, kmax, (uint32_t)(i * per), (uint32_t)h->n, (uint32_t)h->na, ka, P->d_lab[i], nullptr, d->stream));
         HIPCHK(d, hipMemcpyAsync(lab.data() + i * per, P->d_lab[i], sizeof(uint16_t) * per, hipMemcpyDeviceToHost, d->stream));
         HIPCHK(d, hipStreamSynchronize(d->stream));
         return BISBM_OK;

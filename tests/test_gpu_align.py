@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import oracle_lib as O
 from test_align import PLANTED, agreement, aligned_sample, planted_graph, relabelled_planted_starts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,6 +110,66 @@ def test_aligned_sample_equals_the_model(shape):
     assert m.marginals_reference()[1] == -1
     perm, tot = m.marginals_alignment(chains - 1)
     assert (perm == np.arange(ka + kb)).all() and tot == na + nb
+
+
+def _pooled_sample_equals_the_model(m, na, ka, kb):
+    m.shuffle_bisbm()
+    m.run_sweeps(2)
+    m.marginals_reset()
+    m.marginals_set_alignment(True)
+    labs = _all_labels(m)
+    m.marginals_accumulate()
+    ref, chain = m.marginals_reference()
+    assert chain == int(np.argmin(m.entropy())) and (ref == labs[chain]).all()
+    counts, perms, totals = aligned_sample(labs, ref, na, ka, kb)
+    assert (m.marginals_get().astype(np.int64) == counts).all()
+    for c in range(m.n_chains):
+        perm, tot = m.marginals_alignment(c)
+        assert (perm == perms[c]).all() and tot == totals[c], c
+
+
+# The pooled sample is one mode that holds every chain: it runs the staging of a mode's permutation rows in chunks of 64 list
+# positions and the grid over 256-node workgroups at these edges.
+@pytest.mark.parametrize("shape", [
+    (300, 200, 4, 4, 3000, 130),   # three staging chunks, the last with 2 chains
+    (1025, 260, 5, 3, 6000, 6),    # the node count is no multiple of 256 or of 1024
+], ids=["130_chains", "1285_nodes"])
+def test_pooled_sample_at_the_chunk_and_workgroup_edges(shape):
+    na, nb, ka, kb, edges, chains = shape
+    m = _model(na, nb, ka, kb, edges, chains)
+    _pooled_sample_equals_the_model(m, na, ka, kb)
+    m.close()
+
+
+def test_pooled_sample_of_fewer_nodes_than_a_workgroup():
+    rowptr, col, na, nb = O.load_graph("southernWomen")
+    assert (na, nb) == (18, 14)
+    m = B.BlockModel(O.contiguous_labels(na, nb, 2, 2), syn.types_vector(na, nb), 4, 2, 2, 1.0, (rowptr, col), n_chains=6, seed=3)
+    _pooled_sample_equals_the_model(m, na, 2, 2)
+    m.close()
+
+
+def test_pooled_sample_equals_one_mode_of_every_chain():
+    chains = 12
+    m = _model(300, 200, 6, 5, 3000, chains)
+    m.shuffle_bisbm()
+    m.run_sweeps(2)
+    m.marginals_reset()
+    m.marginals_set_alignment(True)
+    m.marginals_accumulate()
+    ref, _ = m.marginals_reference()
+    pooled = m.marginals_get(), [m.marginals_alignment(c) for c in range(chains)], m.marginals_map()
+    assert pooled[0].sum() == chains * 500
+    m.marginals_reset()
+    m.marginals_set_modes(np.zeros(chains, dtype=np.uint32))
+    m.marginals_set_reference(ref, mode=0)
+    m.marginals_accumulate()
+    assert (m.marginals_get(mode=0) == pooled[0]).all()
+    for c in range(chains):
+        perm, tot = m.marginals_alignment(c)
+        assert (perm == pooled[1][c][0]).all() and tot == pooled[1][c][1], c
+    assert (m.marginals_map(mode=0) == pooled[2]).all()
+    m.close()
 
 
 def _state(m):

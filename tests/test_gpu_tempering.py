@@ -216,6 +216,33 @@ def test_marginals_count_the_cold_chains_only():
     m2.close()
 
 
+def test_aligned_marginals_count_the_cold_chains_across_staging_chunks():
+    # 136 chains: the permutation rows are staged 64 chains at a time, the 34 cold chains lie scattered over the three chunks
+    chains, L = 136, 4
+    na, nb, ka, kb = 300, 200, 4, 4
+    m = _planted(na, nb, 3000, ka, kb, chains)
+    m.shuffle_bisbm()
+    m.set_tempering([1.0] * L)
+    m.tempering_run(5, 1)
+    rung, _ = m.tempering_state()
+    cold = [c for c in range(chains) if rung[c] == 0]
+    assert len(cold) == chains // L and cold[0] < 64 and 64 <= cold[len(cold) // 2] < 128 and cold[-1] >= 128
+    lab = np.array([m.get_memberships(c) for c in range(chains)])
+    S = m.entropy()
+    m.marginals_reset()
+    m.marginals_set_alignment(True)
+    m.marginals_accumulate()
+    ref, ref_chain = m.marginals_reference()
+    assert ref_chain == cold[int(np.argmin(S[cold]))] and rung[ref_chain] == 0
+    want = np.zeros((na + nb, max(ka, kb)), dtype=np.int64)
+    base = np.where(np.arange(na + nb) >= na, ka, 0)
+    for c in cold:
+        perm, _ = m.marginals_alignment(c)
+        np.add.at(want, (np.arange(na + nb), perm[lab[c]].astype(np.int64) - base), 1)
+    assert (m.marginals_get() == want).all()
+    m.close()
+
+
 def test_several_entries_equal_one():
     chains = 16
     kw = dict(na=400, nb=300, edges=4000, ka=5, kb=5, chains=chains)
