@@ -157,6 +157,61 @@ constexpr uint32_t kRowCap = 255;     // longest row the feeder walks (a k_v cou
     double name = (value);     \
     __asm__ volatile("" : "+v"(name))
 
+// What a multi-step pass reads once a step's target s is known, per lane: the lane's entry of row s of m, eta and m_r / n_r of r
+// (even lanes) or s (odd lanes) folded into the arguments of the scalar terms, and the four table gathers behind them
+// (target_lds, target_gathers).  One opposite-type block (leaf) per lane ...
+struct TargetReads {
+    uint32_t s_loc, a_st, e_idx, tail_idx;
+    int32_t m_st_raw, m_st;
+    int ee, qn, qk;
+    double logn, tail_lg, L2, L4;
+};
+// ... and two (step_pair64, step_quad32)
+struct TargetReads2 {
+    uint32_t s_loc, a_st0, a_st1, e_idx, tail_idx;
+    int32_t m_st_raw0, m_st_raw1, m_st0, m_st1;
+    int ee, qn, qk;
+    double logn, tail_lg, L2_0, L2_1, L4_0, L4_1;
+};
+
+// The two steps of a two-steps pass (step_pair, step_pair64): step q (A) and step q + 1 (B) as wave-uniform words, and the
+// lane's own step (lower half: A, upper half: B)
+struct PairSteps {
+    uint32_t r_locA, r_locB, degA, degB, t_locB, s_prdA, s_prdB;  // own block, degree, pivot block, predicted target
+    uint32_t liveA, liveB;                                        // n_r != 1 (:467-471: a block is never emptied); B: and the step exists
+    uint32_t selfA, selfB, warmA, warmB;                          // r == s; T > 0 (pair_selfs)
+    uint32_t prop, pack_v, deg, r_loc, t_loc;                     // per lane
+    double u_acc;
+    // what the verdicts will be combined with, in one word (the scalar file is full): bit 0 step q can
+    // move, bit 1 step q is an accepted r == s, bits 2, 3 the same for step q + 1, bit 4 the clash
+    __device__ __forceinline__ uint32_t flags(uint32_t clash) const {
+        return (liveA & (selfA ^ 1u)) | ((liveA & selfA & warmA) << 1) | ((liveB & (selfB ^ 1u)) << 2) | ((liveB & selfB & warmB) << 3) |
+               (clash << 4);
+    }
+};
+
+// verdicts of a four-steps pass, in step order: bits 15 / 31 / 47 / 63 -> bits 0..3
+__device__ __forceinline__ uint32_t rows4(unsigned long long b) {
+    const unsigned long long x = b >> 15;
+    return (uint32_t)(x | (x >> 15) | (x >> 30) | (x >> 45)) & 0xfu;
+}
+// The commit chain of a four-steps pass (step_quad, step_quad32).  nst: steps that exist; clash_bits: bit 4 i + j, step i, if it
+// moves, touches what step j read; mv4: steps that would move.  commit: bit j, steps 0..j all stand; moved: the moved bits of
+// committed steps only.
+__device__ __forceinline__ void commit_four(uint32_t nst, uint32_t clash_bits, uint32_t mv4, uint32_t& moved, uint32_t& commit) {
+    const uint32_t c01 = (clash_bits >> 1) & 1u, c02 = (clash_bits >> 2) & 1u, c03 = (clash_bits >> 3) & 1u;
+    const uint32_t c12 = (clash_bits >> 6) & 1u, c13 = (clash_bits >> 7) & 1u, c23 = (clash_bits >> 11) & 1u;
+    const uint32_t m0 = mv4 & 1u;
+    const uint32_t k1 = sflag(nst - 1u) & ((m0 & c01) ^ 1u);  // (nst >= 2)
+    const uint32_t m1 = k1 & (mv4 >> 1) & 1u;
+    const uint32_t k2 = k1 & (nst > 2u ? 1u : 0u) & ((m0 & c02) ^ 1u) & ((m1 & c12) ^ 1u);
+    const uint32_t m2 = k2 & (mv4 >> 2) & 1u;
+    const uint32_t k3 = k2 & (nst > 3u ? 1u : 0u) & ((m0 & c03) ^ 1u) & ((m1 & c13) ^ 1u) & ((m2 & c23) ^ 1u);
+    const uint32_t m3 = k3 & (mv4 >> 3) & 1u;
+    commit = 1u | (k1 << 1) | (k2 << 2) | (k3 << 3);
+    moved = m0 | (m1 << 1) | (m2 << 2) | (m3 << 3);
+}
+
 // EL: all of eta in LDS; otherwise a WINDOW of it: the rows of the phase's own type, p.eta_w consecutive degrees from
 // p.eta_lo_a / p.eta_lo_b on (chosen by the host to hold most nodes), swapped at the phase change -- steps of nodes whose degree
 // lies outside take the general path, which reads and writes those entries in HBM.  CT: constant schedule.  K32: both block counts <= 32 (five-level scans and sums).  K16 (with K32): both
@@ -299,10 +354,10 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
     LogQConsts lqc = log_q_consts();  // log_q closed form
     if (!(Q32 && !EL))  // (held in vector registers for the whole kernel, except where registers are scarcest: built at the use there)
         __asm__ volatile("" : "+v"(lqc.nc0l2e), "+v"(lqc.c1c0), "+v"(lqc.c1), "+v"(lqc.c2c0), "+v"(lqc.lfc));
-    double c_576 = kDirectU2;                      // 18^2: tier test k^2 > 324 n (the name is of the round when it was 24^2)
-    if ((K32 && !Q32) || CT) __asm__ volatile("" : "+v"(c_576));  // (pinned like the others, except where registers are scarcest)
-    double c_169 = 169.0;                          // 13^2: tier test k^2 >= 169 n
-    if (K32 && !Q32) __asm__ volatile("" : "+v"(c_169));   // (pinned like the others, except in the two-blocks-per-lane variants: registers)
+    double c_direct_u2 = kDirectU2;                // 18^2: tier test k^2 > 324 n
+    if ((K32 && !Q32) || CT) __asm__ volatile("" : "+v"(c_direct_u2));  // (pinned like the others, except where registers are scarcest)
+    double c_closed2_u2 = 169.0;                   // 13^2: tier test k^2 >= 169 n
+    if (K32 && !Q32) __asm__ volatile("" : "+v"(c_closed2_u2));  // (pinned like the others, except in the two-blocks-per-lane variants: registers)
     uint64_t sweeps_done = 0;
     // Sum of accepted dS (blockmodel_t::entropy_) and accepted count: lane 0's copy is the value.  They are bumped
     // inside the lane-0 region of an accepted step (a vector add under the execution mask, no LDS round trip).
@@ -759,14 +814,14 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const double k2 = kd * kd;
                     // (the tier tests as lane masks, combined on the scalar side: every lane of the wave is active in a pass)
                     const unsigned long long m_big = __builtin_amdgcn_ballot_w64(qn > kQNmax);
-                    const unsigned long long m_direct = m_big & __builtin_amdgcn_ballot_w64(k2 > c_576 * nd);
+                    const unsigned long long m_direct = m_big & __builtin_amdgcn_ballot_w64(k2 > c_direct_u2 * nd);
                     if (__builtin_expect(m_direct == ~0ull, 1)) {
                         double sq, rr;
                         sqrt_rsqrt(nd, sq, rr);
                         return log_q_closed(kd, sq, rr, logn, lqc);
                     }
                     if (m_big == 0ull) return log_q_table(tab, qn, qk2);  // small graphs (int_part.hh:27-37)
-                    const unsigned long long m_ge13 = m_big & __builtin_amdgcn_ballot_w64(k2 >= c_169 * nd);
+                    const unsigned long long m_ge13 = m_big & __builtin_amdgcn_ballot_w64(k2 >= c_closed2_u2 * nd);
                     const unsigned long long m_ge8 = m_big & __builtin_amdgcn_ballot_w64(k2 >= ldexp(nd, 6));
                     if ((MID ? m_ge8 : m_ge13) != ~0ull) return log_q<true>(tab, qn, qk, logn);
                     double sq, rr;
@@ -839,7 +894,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             if (ok) new_minimum(q);
                         return;
                     }
-                    const uint32_t r = own_base + r_loc, s = own_base + s_loc;
+                    const uint32_t s = own_base + s_loc;
                     const int ideg = (int)deg;
                     const uint32_t a_st = mq_at(s_loc, lane);
                     const int32_t m_st_raw = mq[a_st];
@@ -920,6 +975,271 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     FSTAMP_STEP(8);
                     if constexpr (TM) new_minimum(q);
                 };
+                // ---- several steps per pass: the stages the passes share ----
+                // Lanes beyond the first 32 / 16 / 8 evaluate the steps after q in the same instructions, against the state BEFORE
+                // step q (step_pair below has the argument).  The passes differ in how many steps share the wave and how many
+                // blocks a lane holds; what follows is what they have in common, defined once.
+                int half_mask_l = lane >= 32u ? -1 : 0;  // (all ones in the upper half: a per-lane select of two scalar words as bit operations)
+                __asm__ volatile("" : "+v"(half_mask_l));
+                uint32_t acc_chunk = 0;  // accepted steps of the chunk's pair passes (a scalar word; added to acc_l0 per chunk)
+                // (cooling schedules: the temperature is the lane's own step's; steps at T = 0 are decided by the sign of dS)
+                const unsigned long long zeroT_mask = CT ? 0ull : __builtin_amdgcn_ballot_w64(T_l == 0.);
+
+                // Everything that depends on the target s of the lane's step, one leaf per lane (the lane's block: lb): row s of m,
+                // eta, m_r / n_r of r and s -- LDS and cross-lane reads ...
+                auto target_lds = [&](TargetReads& t, uint32_t s_loc, uint32_t r_loc, uint32_t deg, int32_t kmask) {
+                    t.s_loc = s_loc;
+                    const uint32_t idx_l = r_loc ^ ((r_loc ^ s_loc) & (uint32_t)odd_mask_l);  // odd lanes: s, even lanes: r
+                    t.a_st = mq_at(s_loc, lb);
+                    t.m_st_raw = mq[t.a_st];
+                    t.e_idx = eta_at(idx_l, deg);
+                    t.ee = (int)eta_l[t.e_idx];
+                    const int mm = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), mr_own);
+                    const int nn = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), nr_own);
+                    t.m_st = t.m_st_raw & kmask;
+                    t.qn = mm + __mul24((int)deg, dsgn_l);        // m0r, m0s, m0r - deg, m0s + deg
+                    t.tail_idx = (uint32_t)((t.qn ^ ((t.qn ^ t.ee) & eta_mask_l)) + toff_l);
+                    t.qk = nn + dq_l;
+                };
+                // ... and the four table gathers that depend on the target (logn_first: which of the first two goes out first is the
+                // pass's own, kept as each pass had it when it was tuned)
+                auto target_gathers = [&](TargetReads& t, uint32_t kk, auto logn_first) {
+                    if constexpr (decltype(logn_first)::value) t.logn = tab_at(tab.logtab, (uint32_t)t.qn);
+                    t.tail_lg = tab_at(tab.lg, t.tail_idx);
+                    if constexpr (!decltype(logn_first)::value) t.logn = tab_at(tab.logtab, (uint32_t)t.qn);
+                    t.L2 = tab_at(tab.lg, (uint32_t)(t.m_st + 1));
+                    t.L4 = tab_at(tab.lg, (uint32_t)(t.m_st + 1) + kk);
+                };
+                // The same with two leaves per lane: the opposite-type blocks l and l + stride (step_pair64: l = lh, stride 32;
+                // step_quad32: l = l16, stride 16)
+                auto target_lds2 = [&](TargetReads2& t, uint32_t s_loc, uint32_t r_loc, uint32_t deg, int32_t kmask0, int32_t kmask1, uint32_t l,
+                                       uint32_t stride) {
+                    t.s_loc = s_loc;
+                    const uint32_t idx_l = r_loc ^ ((r_loc ^ s_loc) & (uint32_t)odd_mask_l);  // odd lanes: s, even lanes: r
+                    t.a_st0 = mq_at(s_loc, l), t.a_st1 = mq_at(s_loc, l + stride);
+                    t.m_st_raw0 = mq[t.a_st0], t.m_st_raw1 = mq[t.a_st1];
+                    t.e_idx = eta_at(idx_l, deg);
+                    t.ee = (int)eta_l[t.e_idx];
+                    const int mm = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), mr_own);
+                    const int nn = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), nr_own);
+                    t.m_st0 = t.m_st_raw0 & kmask0, t.m_st1 = t.m_st_raw1 & kmask1;
+                    t.qn = mm + __mul24((int)deg, dsgn_l);        // m0r, m0s, m0r - deg, m0s + deg
+                    t.tail_idx = (uint32_t)((t.qn ^ ((t.qn ^ t.ee) & eta_mask_l)) + toff_l);
+                    t.qk = nn + dq_l;
+                };
+                auto target_gathers2 = [&](TargetReads2& t, uint32_t kk0, uint32_t kk1, auto logn_first) {
+                    if constexpr (decltype(logn_first)::value) t.logn = tab_at(tab.logtab, (uint32_t)t.qn);
+                    t.tail_lg = tab_at(tab.lg, t.tail_idx);
+                    if constexpr (!decltype(logn_first)::value) t.logn = tab_at(tab.logtab, (uint32_t)t.qn);
+                    t.L2_0 = tab_at(tab.lg, (uint32_t)(t.m_st0 + 1)), t.L4_0 = tab_at(tab.lg, (uint32_t)(t.m_st0 + 1) + kk0);
+                    t.L2_1 = tab_at(tab.lg, (uint32_t)(t.m_st1 + 1)), t.L4_1 = tab_at(tab.lg, (uint32_t)(t.m_st1 + 1) + kk1);
+                };
+
+                // accept (:47-61): u accu0 < accu1 exp(-dS/T), decided on a 1e-7-accurate exponential unless the two sides are within
+                // 1e-5 of each other (then the exact one decides); steps at T = 0: dS < 0 decides (:49-50), nothing to be close to.
+                // Two halves (step_pair, step_pair64), in the lanes that hold the sums: bit 31 is step q's verdict, bit 63 step q + 1's ...
+                auto accept_halves = [&](double dS, double accu0, double accu1, double u_acc, uint32_t qs, uint32_t warmA,
+                                         uint32_t warmB) -> unsigned long long {
+                    double invT = invT_const;
+                    if (!CT) invT = invT_of(qs);
+                    const double z = -dS * invT;
+                    const double est = accu1 * exp2_filter(z * c_l2e);
+                    const double lhs = u_acc * accu0;
+                    unsigned long long b_acc = __builtin_amdgcn_ballot_w64(lhs < est);
+                    unsigned long long b_far = __builtin_amdgcn_ballot_w64(fabs(lhs - est) > c_tol * est);
+                    if (!CT) {
+                        const unsigned long long cold = ((unsigned long long)(0u - (warmB ^ 1u)) << 32) | (0u - (warmA ^ 1u));
+                        const unsigned long long b_neg = __builtin_amdgcn_ballot_w64(dS < 0.);
+                        b_acc = (b_acc & ~cold) | (b_neg & cold);
+                        b_far |= cold;
+                    }
+                    if (__builtin_expect((((uint32_t)b_far & (uint32_t)(b_far >> 32)) >> 31) == 0u, 0)) {  // a verdict too close to call
+                        const unsigned long long exact = __builtin_amdgcn_ballot_w64(lhs < accu1 * exp(z));
+                        b_acc = (b_acc & b_far) | (exact & ~b_far);
+                    }
+                    return b_acc;
+                };
+                // ... and per row / group (step_quad, step_quad32, step_oct).  m_warm: lanes of the steps at T > 0; b_can: the lanes
+                // whose verdict counts
+                auto accept_rows = [&](double dS, double accu0, double accu1, double u_acc, uint32_t qs, unsigned long long m_warm,
+                                       unsigned long long b_can) -> unsigned long long {
+                    double invT = invT_const;
+                    if (!CT) invT = invT_of(qs);
+                    const double z = -dS * invT;
+                    const double est = accu1 * exp2_filter(z * c_l2e);
+                    const double lhs = u_acc * accu0;
+                    unsigned long long b_acc = __builtin_amdgcn_ballot_w64(lhs < est);
+                    unsigned long long b_far = __builtin_amdgcn_ballot_w64(fabs(lhs - est) > c_tol * est);
+                    if (!CT) {
+                        b_acc = (b_acc & m_warm) | (__builtin_amdgcn_ballot_w64(dS < 0.) & ~m_warm);
+                        b_far |= ~m_warm;
+                    }
+                    if (__builtin_expect((~b_far & b_can) != 0ull, 0)) {  // a verdict too close to call
+                        const unsigned long long exact = __builtin_amdgcn_ballot_w64(lhs < accu1 * exp(z));
+                        b_acc = (b_acc & b_far) | (exact & ~b_far);
+                    }
+                    return b_acc;
+                };
+
+                // ---- two-steps passes (step_pair, step_pair64): prologue, r == s exits, verdicts and writes ----
+                // q: first step of the pass; pairable: 1 = lanes 32..63 evaluate step q + 1, 0 = nothing to pair with
+                // (last step of the chunk, or a step that needs the general path next): both halves evaluate step q.
+                // qB = q + pairable; qs: the lane's own step.
+                auto pair_head = [&](uint32_t q, uint32_t qB, uint32_t qs, uint32_t pairable) -> PairSteps {
+                    PairSteps P;
+                    P.prop = prop_of(qs);
+                    P.u_acc = u_acc_of(qs);
+                    const uint32_t packA = readlane(pack_l, q), packB = readlane(pack_l, qB);
+                    P.r_locA = (packA >> 8) & 63u, P.r_locB = (packB >> 8) & 63u;
+                    P.degA = packA & 255u, P.degB = packB & 255u, P.t_locB = (packB >> 16) & 63u;
+                    P.s_prdA = packA >> 24, P.s_prdB = packB >> 24;
+                    // the lane's own step: lower half step q, upper half step qB (from the two scalars: no LDS round trip
+                    // in front of the first reads)
+                    // (one select of the whole packed word per lane, then the fields out of it: 6 instructions where four selects
+                    // of the scalar fields took 12)
+                    P.pack_v = packA ^ ((packA ^ packB) & (uint32_t)half_mask_l);
+                    P.deg = P.pack_v & 255u, P.r_loc = (P.pack_v >> 8) & 63u, P.t_loc = (P.pack_v >> 16) & 63u;
+                    P.liveA = sflag((uint32_t)readlane(nr_own, P.r_locA) ^ 1u);
+                    P.liveB = smin((uint32_t)readlane(nr_own, P.r_locB) ^ 1u, pairable);
+                    return P;
+                };
+                // the targets are known: which of the two steps is an r == s, and which runs at T > 0
+                auto pair_selfs = [&](PairSteps& P, uint32_t q, uint32_t qB, uint32_t s_locA, uint32_t s_locB) {
+                    P.selfA = 1u - sflag(s_locA ^ P.r_locA), P.selfB = 1u - sflag(s_locB ^ P.r_locB);
+                    // T = 0 (the greedy tail of a cooling schedule): r == s is not accepted (dS = 0 is not < 0, :49-50)
+                    P.warmA = CT ? 1u : ((uint32_t)(zeroT_mask >> q) & 1u) ^ 1u;
+                    P.warmB = CT ? 1u : ((uint32_t)(zeroT_mask >> qB) & 1u) ^ 1u;
+                };
+                // both r == s: nothing changes (:109-112); the steps the pass is done with
+                auto pair_both_self = [&](auto tm, const PairSteps& P, uint32_t q, uint32_t qB, uint32_t pairable) -> uint32_t {
+                    acc_chunk += (P.liveA & P.warmA) + (P.liveB & P.warmB);
+                    if constexpr (decltype(tm)::value) {
+                        if ((P.liveA & P.warmA) != 0u) new_minimum(q);
+                        if ((P.liveB & P.warmB) != 0u) new_minimum(qB);
+                    }
+                    PCOUNT(0, 1u);
+                    PCOUNT(1, 1u + pairable);
+                    return 1u + pairable;
+                };
+                // The verdicts (b_acc: bit 31 step q's, bit 63 step q + 1's) against the flags word, the stand rule, and
+                // apply_mcmc_moves for the step(s) that move.  paired: step q + 1 is there and has been evaluated on its own target;
+                // dl / dm: +-1 / +-degree on the lanes of s and r, per step; wr_eta: eta_r - 1, eta_s + 1 in lanes 4, 5;
+                // write_mq(movers): the pass's writes of rows r and s of m (one or two leaves per lane); pass_counts(chA, stands):
+                // the diagnostic counters.  Returns the steps the pass is done with.
+                auto pair_commit = [&](auto tm, uint32_t q, uint32_t qB, uint32_t qs, uint32_t paired, uint32_t flags, unsigned long long b_acc,
+                                       double dS, int dlA, int dlB, int dmA, int dmB, const uint32_t e_idx, int wr_eta, uint32_t s_loc,
+                                       auto&& write_mq, auto&& pass_counts) -> uint32_t {
+                    constexpr bool TM = decltype(tm)::value;
+                    const uint32_t yesA = (uint32_t)(b_acc >> 31) & 1u, yesB = (uint32_t)(b_acc >> 63) & 1u;
+                    const uint32_t chA = flags & yesA;                                  // step q moves its node
+                    const uint32_t okA = chA | ((flags >> 1) & 1u);                     // ... counts as accepted
+                    const uint32_t stands = paired & ((chA & (flags >> 4)) ^ 1u);       // step q + 1's evaluation stands
+                    pass_counts(chA, stands);
+                    const uint32_t chB = stands & (flags >> 2) & yesB;
+                    const uint32_t okB = chB | (stands & (flags >> 3) & 1u);
+                    acc_chunk += okA + okB;
+                    if ((TM ? (okA | okB) : (chA | chB)) != 0u) {  // (with the early-stop bookkeeping on: every accepted step is looked at)
+                        // ---- apply_mcmc_moves, blockmodel.cc:461-503, for the step(s) that move: their rows differ ----
+                        const uint32_t mA = 0u - chA, mB = 0u - chB;  // all ones / zero
+                        const unsigned long long movers = ((unsigned long long)mB << 32) | mA;
+                        wfence();
+                        write_mq(movers);  // k == 0: rewrites the same values
+                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0000003000000030ull))  // lanes 4, 5: eta_r - 1, eta_s + 1
+                            eta_l[e_idx] = (uint32_t)wr_eta;
+                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0000000100000001ull)) new_lab[qs] = (uint8_t)(own_base + s_loc);
+                        mr_own += (dmA & (int)mA) + (dmB & (int)mB);
+                        nr_own += (dlA & (int)mA) + (dlB & (int)mB);
+                        if constexpr (TM) {  // :500, in step order; without the early-stop bookkeeping nobody looks at the running sum
+                                             // during the launch: the host takes it from the description length (kSumFromEntropy)
+                            const int dS_A_lo = __builtin_amdgcn_readlane(__double2loint(dS), 31), dS_A_hi = __builtin_amdgcn_readlane(__double2hiint(dS), 31);
+                            const int dS_B_lo = __builtin_amdgcn_readlane(__double2loint(dS), 63), dS_B_hi = __builtin_amdgcn_readlane(__double2hiint(dS), 63);
+                            // (a step that does not move adds +0.0: x + 0.0 is x, the running sum is never -0.0)
+                            cum_l0 += __hiloint2double(dS_A_hi & (int)mA, dS_A_lo & (int)mA);
+                            if (okA) new_minimum(q);  // (:86-90, after step q's move and before step q + 1's)
+                            cum_l0 += __hiloint2double(dS_B_hi & (int)mB, dS_B_lo & (int)mB);
+                            if (okB) new_minimum(qB);
+                        }
+                        wfence();
+                    }
+                    return 1u + stands;
+                };
+
+                // ---- four- and eight-steps passes (step_quad, step_quad32, step_oct): clashes, writes, the pass loop ----
+                // pairwise: would step i, if it moves its node, touch what step j read?  One pair (i, j) per lane: li, lj are the
+                // bpermute addresses of the first lanes of steps i and j, k_of_i_at(li, t_j) fetches k of step i at block t_j.
+                // (worked out while the table gathers are in flight: after ALL of them have been issued -- the table tier of log_q is one more --, see step_pair)
+                auto clash_pairs = [&](uint32_t r_loc, uint32_t s_loc, uint32_t t_loc, int li, int lj, auto&& k_of_i_at) -> unsigned long long {
+                    uint32_t r_c = r_loc, s_c = s_loc, t_c = t_loc;
+                    __asm__ volatile("" : "+v"(r_c), "+v"(s_c), "+v"(t_c)::"memory");
+                    const uint32_t r_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)r_c);
+                    const uint32_t s_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)s_c);
+                    const uint32_t r_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)r_c);
+                    const uint32_t s_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)s_c);
+                    const uint32_t t_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)t_c);
+                    const uint32_t k_i_tj = k_of_i_at(li, t_j);
+                    const uint32_t set_i = (1u << r_i) | (1u << s_i), set_j = (1u << r_j) | (1u << s_j);
+                    const uint32_t lo = min(r_i, s_i), hi = max(r_i, s_i);
+                    const uint32_t between = ((1u << hi) - 1u) & ~((2u << lo) - 1u);  // blocks strictly between r_i and s_i
+                    // (bit arithmetic, no short-circuit: a lane-divergent `||` becomes a branch over the execution mask)
+                    const uint32_t in_between = (between >> s_j) & min(k_i_tj, 1u);
+                    return __builtin_amdgcn_ballot_w64(((set_i & set_j) | in_between) != 0u);
+                };
+                // apply_mcmc_moves, blockmodel.cc:461-503, for the steps of a pass of `width` steps that move (bits of `moved`; their
+                // rows of m differ); selfok: committed steps that are an accepted r == s.  The lane's step is qs, group grp_l of
+                // 64 / width lanes; ee: the lane's eta entry; write_mq(movers): the pass's writes of rows r and s of m (one or two leaves per lane).
+                auto apply_moves = [&](auto tm, auto width, uint32_t q, uint32_t qs, uint32_t grp_l, uint32_t moved, uint32_t selfok, uint32_t r_loc,
+                                       uint32_t s_loc, uint32_t deg, double dS, uint32_t e_idx, int ee, auto&& write_mq) {
+                    constexpr bool TM = decltype(tm)::value;
+                    constexpr uint32_t W = decltype(width)::value, L = 64u / W;  // lanes per step
+                    constexpr unsigned long long kFirst = W == 4u ? 0x0001000100010001ull : 0x0101010101010101ull;  // lane 0 of every group
+                    acc_chunk += (uint32_t)__builtin_popcount(moved | selfok);
+                    if ((TM ? (moved | selfok) : moved) != 0u) {
+                        const unsigned long long movers = __builtin_amdgcn_ballot_w64(((moved >> grp_l) & 1u) != 0u);  // all lanes of every mover's group
+                        wfence();
+                        write_mq(movers);  // k == 0: rewrites the same values
+                        if (__builtin_amdgcn_inverse_ballot_w64(movers & (kFirst * 0x30ull)))  // lanes 4, 5 of a group: eta_r - 1, eta_s + 1
+                            eta_l[e_idx] = (uint32_t)(ee + ((int)(lb & 1u) * 2 - 1));
+                        if (__builtin_amdgcn_inverse_ballot_w64(movers & kFirst)) new_lab[qs] = (uint8_t)(own_base + s_loc);
+                        // the register copies of m_r / n_r, sum dS (:500) and the early-stop bookkeeping, in step order
+#pragma unroll
+                        for (uint32_t g = 0; g < W; ++g) {
+                            if ((moved >> g) & 1u) {
+                                const uint32_t rg = readlane(r_loc, L * g), sg = readlane(s_loc, L * g), dg = readlane(deg, L * g);
+                                const int dl = (int)min(lb ^ rg, 1u) - (int)min(lb ^ sg, 1u);  // +1 on lane s, -1 on lane r
+                                mr_own += __mul24((int)dg, dl);
+                                nr_own += dl;
+                                if constexpr (TM) cum_l0 += readlane(dS, L * g + L - 1u);
+                                if constexpr (TM) new_minimum(q + g);
+                            } else if (TM && ((selfok >> g) & 1u)) {
+                                new_minimum(q + g);  // an accepted r == s step (see new_minimum)
+                            }
+                        }
+                        wfence();
+                    }
+                };
+                // the chunk's steps in passes of up to `width`: steps that need the general path (bit 31 of prop_l) go one at a time
+                auto multi_loop = [&](auto tm, auto width, auto&& pass) {
+                    constexpr uint32_t W = decltype(width)::value;
+                    uint32_t q = 0;
+                    acc_chunk = 0;
+                    while (q < cnt) {
+                        const uint32_t some = (uint32_t)(gen_mask >> q) & ((1u << W) - 1u);
+                        if (__builtin_expect((some & 1u) != 0u, 0)) {
+                            step_general(q, T_of_step(q));
+                            q += 1u;
+                        } else {  // the steps up to the next one that needs the general path, or to the end of the chunk
+                            const uint32_t nst = min(min((uint32_t)__builtin_ctz(some | (1u << W)), W), cnt - q);
+                            const uint32_t done = pass(tm, q, nst);
+                            PCOUNT(0, 1u);
+                            PCOUNT(1, done);
+                            q += done;
+                        }
+                    }
+                    acc_l0 += (unsigned long long)acc_chunk;
+                };
+                using Four = std::integral_constant<uint32_t, 4u>;
+                using Eight = std::integral_constant<uint32_t, 8u>;
+
                 // ---- two steps per pass (K <= 32, constant T > 0, no early-stop bookkeeping) ----
                 // The hot step uses lanes 0..31 (one lane per block).  Here lanes 32..63 evaluate step q + 1 in the same
                 // instructions, against the same state, i.e. the state BEFORE step q.  That is step q + 1's true outcome
@@ -934,81 +1254,35 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                 // steps are committed (their writes touch different rows).  The chain is the serial chain, bit for
                 // bit: the CPU checker steps one node at a time and the parity tests compare against it (measured on the
                 // bench workload: the second step stands in ~80 % of the passes, 1.8 steps per pass).
-                int half_mask_l = lane >= 32u ? -1 : 0;  // (all ones in the upper half: a per-lane select of two scalar words as bit operations)
-                __asm__ volatile("" : "+v"(half_mask_l));
-                uint32_t acc_chunk = 0;  // accepted steps of the chunk's pair passes (a scalar word; added to acc_l0 per chunk)
-                // q: first step of the pass; pairable: 1 = lanes 32..63 evaluate step q + 1, 0 = nothing to pair with
-                // (last step of the chunk, or a step that needs the general path next): both halves evaluate step q
-                // (cooling schedules: the temperature is the lane's own step's; steps at T = 0 are decided by the sign of dS)
-                const unsigned long long zeroT_mask = CT ? 0ull : __builtin_amdgcn_ballot_w64(T_l == 0.);
                 auto step_pair = [&](auto tm, uint32_t q, uint32_t pairable) -> uint32_t {
-                    constexpr bool TM = decltype(tm)::value;
                     const uint32_t qB = q + pairable;
                     const uint32_t qs = q + ((uint32_t)half_mask_l & pairable);  // (flags are 0 / 1 words and selections arithmetic: a bool
                                                                          // select of uniform values goes through the vector unit and back)
-                    const int sel = (int)(qs << 2);
                     FSTAMP_STEP(0);
-                    const uint32_t prop = prop_of(qs);
-                    const double u_acc = u_acc_of(qs);
-                    const uint32_t packA = readlane(pack_l, q), packB = readlane(pack_l, qB);
-                    const uint32_t r_locA = (packA >> 8) & 63u, r_locB = (packB >> 8) & 63u;
-                    const uint32_t degA = packA & 255u, degB = packB & 255u, t_locA = (packA >> 16) & 63u, t_locB = (packB >> 16) & 63u;
-                    // the lane's own step: lower half step q, upper half step qB (from the two scalars: no LDS round trip
-                    // in front of the first reads)
-                    // (one select of the whole packed word per lane, then the fields out of it: 6 instructions where four selects
-                    // of the scalar fields took 12)
-                    const uint32_t pack_v = packA ^ ((packA ^ packB) & (uint32_t)half_mask_l);
-                    const uint32_t deg = pack_v & 255u, r_loc = (pack_v >> 8) & 63u, t_loc = (pack_v >> 16) & 63u;
+                    PairSteps P = pair_head(q, qB, qs, pairable);
+                    const uint32_t r_locA = P.r_locA, s_prdA = P.s_prdA, r_locB = P.r_locB, s_prdB = P.s_prdB, t_locB = P.t_locB;
+                    const uint32_t prop = P.prop, deg = P.deg, r_loc = P.r_loc, t_loc = P.t_loc;
                     const int k = (int)hist8_cur[qs * kHistStride + lb];
                     const uint32_t a_rt = mq_at(r_loc, lb);
                     const int32_t m_rt_raw = mq[a_rt];
                     const int w_piv = mq[mq_at(lb, t_loc)];
-                    const uint32_t liveA = sflag((uint32_t)readlane(nr_own, r_locA) ^ 1u);  // n_r != 1 (:467-471: a block is never emptied)
-                    const uint32_t liveB = smin((uint32_t)readlane(nr_own, r_locB) ^ 1u, pairable);
                     const int32_t kmask = (0 - k) >> 31;
                     const int32_t m_rt = m_rt_raw & kmask;
                     const uint32_t kk = (uint32_t)k;
-                    const int ideg = (int)deg;
                     // Everything that depends on the target s, as a function of the target's block index per half.  kPredictTarget:
                     // evaluated on the feeder's PREDICTION (bits 24.. of the packed word), i.e. the reads of row s, eta and m_r / n_r
                     // go out with the first reads and all six table gathers right behind them, while the scan that finds the
                     // target on the state of this moment runs in their shadow; the pass goes ahead only where the two agree (below).
                     // Otherwise (and in every other kind of pass): evaluated on the scan's result, behind it.
-                    uint32_t s_loc, idx_l, a_st, e_idx, tail_idx;
-                    int32_t m_st_raw, m_st;
-                    int ee, qn, qk;
-                    double logn, tail_lg, L1, L2, L3, L4;
-                    auto target_lds = [&](uint32_t sA, uint32_t sB, bool predicted) {  // row s of m, eta, m_r / n_r of r and s: LDS and cross-lane reads
-                        if (predicted)
-                            s_loc = pack_v >> 24;
-                        else
-                            s_loc = sA + ((sB - sA) & (uint32_t)half_mask_l);
-                        idx_l = r_loc ^ ((r_loc ^ s_loc) & (uint32_t)odd_mask_l);  // odd lanes: s, even lanes: r
-                        a_st = mq_at(s_loc, lb);
-                        m_st_raw = mq[a_st];
-                        e_idx = eta_at(idx_l, deg);
-                        ee = (int)eta_l[e_idx];
-                        const int mm = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), mr_own);
-                        const int nn = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), nr_own);
-                        m_st = m_st_raw & kmask;
-                        qn = mm + __mul24(ideg, dsgn_l);        // m0r, m0s, m0r - deg, m0s + deg
-                        tail_idx = (uint32_t)((qn ^ ((qn ^ ee) & eta_mask_l)) + toff_l);
-                        qk = nn + dq_l;
-                    };
-                    auto target_gathers = [&]() {  // the four table gathers that depend on the target
-                        logn = tab_at(tab.logtab, (uint32_t)qn);
-                        tail_lg = tab_at(tab.lg, tail_idx);
-                        L2 = tab_at(tab.lg, (uint32_t)(m_st + 1));
-                        L4 = tab_at(tab.lg, (uint32_t)(m_st + 1) + kk);
-                    };
+                    TargetReads t;
+                    double L1, L3;
                     auto row_r_gathers = [&]() {  // the two that only need row r
                         L1 = tab_at(tab.lg, (uint32_t)(m_rt + 1));
                         L3 = tab_at(tab.lg, (uint32_t)(m_rt + 1) - kk);
                     };
-                    const uint32_t s_prdA = packA >> 24, s_prdB = packB >> 24;
                     if constexpr (kPredictTarget) {
-                        target_lds(s_prdA, s_prdB, true);
-                        target_gathers();
+                        target_lds(t, P.pack_v >> 24, r_loc, deg, kmask);
+                        target_gathers(t, kk, std::true_type{});
                         row_r_gathers();
                         __asm__ volatile("" ::: "memory");
                     }
@@ -1028,32 +1302,20 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     __asm__("s_ff1_i32_b32 %0, %1" : "=s"(fhA) : "s"((uint32_t)hit));
                     __asm__("s_ff1_i32_b32 %0, %1" : "=s"(fhB) : "s"((uint32_t)(hit >> 32)));
                     const uint32_t s_locA = min(fhA, last_own), s_locB = min(fhB, last_own);
-                    const uint32_t selfA = 1u - sflag(s_locA ^ r_locA), selfB = 1u - sflag(s_locB ^ r_locB);
-                    // T = 0 (the greedy tail of a cooling schedule): r == s is not accepted (dS = 0 is not < 0, :49-50)
-                    const uint32_t warmA = CT ? 1u : ((uint32_t)(zeroT_mask >> q) & 1u) ^ 1u;
-                    const uint32_t warmB = CT ? 1u : ((uint32_t)(zeroT_mask >> qB) & 1u) ^ 1u;
+                    pair_selfs(P, q, qB, s_locA, s_locB);
                     FSTAMP_STEP(2);
-                    if ((selfA & selfB) != 0u) {  // both r == s: nothing changes (:109-112)
-                        acc_chunk += (liveA & warmA) + (liveB & warmB);
-                        if constexpr (TM) {
-                            if ((liveA & warmA) != 0u) new_minimum(q);
-                            if ((liveB & warmB) != 0u) new_minimum(qB);
-                        }
-                        PCOUNT(0, 1u);
-                        PCOUNT(1, 1u + pairable);
-                        return 1u + pairable;
-                    }
+                    if ((P.selfA & P.selfB) != 0u) return pair_both_self(tm, P, q, qB, pairable);
                     if constexpr (kPredictTarget) {
                         // a target that is not the predicted one: the reads that depend on it, again (nothing has been written).  (The
                         // test on the scalar side as written: as a C expression of two inequalities it became two compares, two
                         // s_cselect_b64, two s_and_b64 and a branch on vcc -- 1 % of the pass)
                         if (__builtin_expect(sflag((s_locA ^ s_prdA) | (s_locB ^ s_prdB)) != 0u, 0)) {
-                            target_lds(s_locA, s_locB, false);
-                            target_gathers();
+                            target_lds(t, s_locA + ((s_locB - s_locA) & (uint32_t)half_mask_l), r_loc, deg, kmask);
+                            target_gathers(t, kk, std::true_type{});
                         }
                     } else {
-                        target_lds(s_locA, s_locB, false);
-                        target_gathers();
+                        target_lds(t, s_locA + ((s_locB - s_locA) & (uint32_t)half_mask_l), r_loc, deg, kmask);
+                        target_gathers(t, kk, std::true_type{});
                     }
                     FSTAMP_STEP(3);
                     // (the verdict logic's inputs are worked out here, while the table gathers are in flight -- after the gathers have
@@ -1070,10 +1332,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const uint32_t col = (between >> s_locB) & 1u;
                     const uint32_t set_clash = sflag(setA & setB);
                     const uint32_t clash = set_clash | (col & target_moves(margin, kAtB));
-                    // what the verdicts will be combined with, in one word (the scalar file is full): bit 0 step q can
-                    // move, bit 1 step q is an accepted r == s, bits 2, 3 the same for step q + 1, bit 4 the clash
-                    const uint32_t flags = (liveA & (selfA ^ 1u)) | ((liveA & selfA & warmA) << 1) | ((liveB & (selfB ^ 1u)) << 2) |
-                                           ((liveB & selfB & warmB) << 3) | (clash << 4);
+                    const uint32_t flags = P.flags(clash);
 
                     uint32_t flags_pin = flags;
                     __asm__ volatile("" : "+s"(flags_pin));
@@ -1083,12 +1342,12 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     // bench line, same box, tools/ab.sh)
                     int dlA = (int)__builtin_amdgcn_ubfe(1u << s_locA, lb, 1u) - (int)__builtin_amdgcn_ubfe(1u << r_locA, lb, 1u);
                     int dlB = (int)__builtin_amdgcn_ubfe(1u << s_locB, lb, 1u) - (int)__builtin_amdgcn_ubfe(1u << r_locB, lb, 1u);
-                    int dmA = __mul24((int)degA, dlA), dmB = __mul24((int)degB, dlB);
+                    int dmA = __mul24((int)P.degA, dlA), dmB = __mul24((int)P.degB, dlB);
                     __asm__ volatile("" : "+v"(dlA), "+v"(dlB), "+v"(dmA), "+v"(dmB));
                     // (what apply_mcmc_moves will write, worked out while the table gathers are in flight and pinned there)
-                    int wr_rt = m_rt_raw - k, wr_st = m_st_raw + k, wr_eta = ee + ((int)(lb & 1u) * 2 - 1);
+                    int wr_rt = m_rt_raw - k, wr_st = t.m_st_raw + k, wr_eta = t.ee + ((int)(lb & 1u) * 2 - 1);
                     __asm__ volatile("" : "+v"(wr_rt), "+v"(wr_st), "+v"(wr_eta));
-                    const double a0 = k * (m_st + eps) * inv_blk;
+                    const double a0 = k * (t.m_st + eps) * inv_blk;
                     const double a1 = k * (m_rt - k + eps) * inv_blk;
                     double accu0, accu1;  // lanes 16..31: step q, lanes 48..63: step q + 1
                     butterfly_accu_rows32(a0, a1, accu0, accu1);
@@ -1097,10 +1356,10 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
 #pragma unroll
                     for (int i_ = 0; i_ < BISBM_PROBE_NOPS; ++i_) __asm__ volatile("s_nop 0");
 #endif
-                    const double lq = hot_log_q(std::true_type{}, qn, qk, logn);
+                    const double lq = hot_log_q(std::true_type{}, t.qn, t.qk, t.logn);
                     FSTAMP_STEP(5);
-                    double d = (L1 + L2) - (L3 + L4);
-                    d = d + tail_lg * sign_tail;
+                    double d = (L1 + t.L2) - (L3 + t.L4);
+                    d = d + t.tail_lg * sign_tail;
                     d = d + lq * sign_q;
                     const double dS = butterfly_rows32(d);
 #ifdef BISBM_PROBE_NOPS_TAIL  // diagnostic: the same number of idle slots on the tail, where nothing is in flight
@@ -1108,61 +1367,19 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     for (int i_ = 0; i_ < BISBM_PROBE_NOPS_TAIL; ++i_) __asm__ volatile("s_nop 0");
 #endif
                     FSTAMP_STEP(6);
-                    // accept (:47-61) in the lanes that hold the sums; bit 31 is step q's verdict, bit 63 step q + 1's
-                    double invT = invT_const;
-                    if (!CT) invT = invT_of(qs);
-                    const double z = -dS * invT;
-                    const double est = accu1 * exp2_filter(z * c_l2e);
-                    const double lhs = u_acc * accu0;
-                    unsigned long long b_acc = __builtin_amdgcn_ballot_w64(lhs < est);
-                    unsigned long long b_far = __builtin_amdgcn_ballot_w64(fabs(lhs - est) > c_tol * est);
-                    if (!CT) {  // steps at T = 0: dS < 0 decides (:49-50); nothing to be close to
-                        const unsigned long long cold = ((unsigned long long)(0u - (warmB ^ 1u)) << 32) | (0u - (warmA ^ 1u));
-                        const unsigned long long b_neg = __builtin_amdgcn_ballot_w64(dS < 0.);
-                        b_acc = (b_acc & ~cold) | (b_neg & cold);
-                        b_far |= cold;
-                    }
-                    if (__builtin_expect((((uint32_t)b_far & (uint32_t)(b_far >> 32)) >> 31) == 0u, 0)) {  // a verdict too close to call
-                        const unsigned long long exact = __builtin_amdgcn_ballot_w64(lhs < accu1 * exp(z));
-                        b_acc = (b_acc & b_far) | (exact & ~b_far);
-                    }
+                    const unsigned long long b_acc = accept_halves(dS, accu0, accu1, P.u_acc, qs, P.warmA, P.warmB);
                     FSTAMP_STEP(7);
-                    const uint32_t yesA = (uint32_t)(b_acc >> 31) & 1u, yesB = (uint32_t)(b_acc >> 63) & 1u;
-                    const uint32_t chA = flags & yesA;                                  // step q moves its node
-                    const uint32_t okA = chA | ((flags >> 1) & 1u);                     // ... counts as accepted
-                    const uint32_t stands = pairable & ((chA & (flags >> 4)) ^ 1u);     // step q + 1's evaluation stands
-                    PASS_COUNTS_PAIR(pairable);
-                    const uint32_t chB = stands & (flags >> 2) & yesB;
-                    const uint32_t okB = chB | (stands & (flags >> 3) & 1u);
-                    acc_chunk += okA + okB;
-                    if ((TM ? (okA | okB) : (chA | chB)) != 0u) {  // (with the early-stop bookkeeping on: every accepted step is looked at)
-                        // ---- apply_mcmc_moves, blockmodel.cc:461-503, for the step(s) that move: their rows differ ----
-                        const uint32_t mA = 0u - chA, mB = 0u - chB;  // all ones / zero
-                        const unsigned long long movers = ((unsigned long long)mB << 32) | mA;
-                        wfence();
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {  // k == 0: rewrites the same values
-                            mq[a_rt] = wr_rt;
-                            mq[a_st] = wr_st;
-                        }
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0000003000000030ull))  // lanes 4, 5: eta_r - 1, eta_s + 1
-                            eta_l[e_idx] = (uint32_t)wr_eta;
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0000000100000001ull)) new_lab[qs] = (uint8_t)(own_base + s_loc);
-                        mr_own += (dmA & (int)mA) + (dmB & (int)mB);
-                        nr_own += (dlA & (int)mA) + (dlB & (int)mB);
-                        if constexpr (TM) {  // :500, in step order; without the early-stop bookkeeping nobody looks at the running sum
-                                             // during the launch: the host takes it from the description length (kSumFromEntropy)
-                            const int dS_A_lo = __builtin_amdgcn_readlane(__double2loint(dS), 31), dS_A_hi = __builtin_amdgcn_readlane(__double2hiint(dS), 31);
-                            const int dS_B_lo = __builtin_amdgcn_readlane(__double2loint(dS), 63), dS_B_hi = __builtin_amdgcn_readlane(__double2hiint(dS), 63);
-                            // (a step that does not move adds +0.0: x + 0.0 is x, the running sum is never -0.0)
-                            cum_l0 += __hiloint2double(dS_A_hi & (int)mA, dS_A_lo & (int)mA);
-                            if (okA) new_minimum(q);  // (:86-90, after step q's move and before step q + 1's)
-                            cum_l0 += __hiloint2double(dS_B_hi & (int)mB, dS_B_lo & (int)mB);
-                            if (okB) new_minimum(qB);
-                        }
-                        wfence();
-                    }
+                    const uint32_t done = pair_commit(
+                        tm, q, qB, qs, pairable, flags, b_acc, dS, dlA, dlB, dmA, dmB, t.e_idx, wr_eta, t.s_loc,
+                        [&](unsigned long long movers) {
+                            if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {
+                                mq[a_rt] = wr_rt;
+                                mq[t.a_st] = wr_st;
+                            }
+                        },
+                        [&](uint32_t chA, uint32_t stands) { PASS_COUNTS_PAIR(pairable); });
                     FSTAMP_STEP(8);
-                    return 1u + stands;
+                    return done;
                 };
 
                 // ---- two steps per pass with more than 32 blocks of a type (the K > 32 variant) ----
@@ -1170,66 +1387,31 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                 // opposite-type blocks l and l + 32 -- their k, their entries of rows r and s, their table gathers, their leaves of
                 // the three sums, added first (level 32 of the summation tree, bisbm_device.hpp) -- and, for the inverse CDF,
                 // entries l and l + 32 of column t.  m_r / n_r sit one block per lane across the whole wave and are read by lane
-                // index.  The stand rule, the verdict logic and the writes are step_pair's (block sets as 64-bit masks).
-                                auto step_pair64 = [&](auto tm, uint32_t q, uint32_t pairable) -> uint32_t {
-                    constexpr bool TM = decltype(tm)::value;
+                // index.  The stand rule is step_pair's on 64-bit block sets; verdicts and writes are the shared ones.
+                auto step_pair64 = [&](auto tm, uint32_t q, uint32_t pairable) -> uint32_t {
                     const uint32_t qB = q + pairable;
                     const uint32_t qs = q + ((uint32_t)half_mask_l & pairable);
-                    const int sel = (int)(qs << 2);
-                    const uint32_t prop = prop_of(qs);
-                    const double u_acc = u_acc_of(qs);
-                    const uint32_t packA = readlane(pack_l, q), packB = readlane(pack_l, qB);
-                    const uint32_t r_locA = (packA >> 8) & 63u, r_locB = (packB >> 8) & 63u;
-                    const uint32_t degA = packA & 255u, degB = packB & 255u, t_locA = (packA >> 16) & 63u, t_locB = (packB >> 16) & 63u;
-                    const uint32_t pack_v = packA ^ ((packA ^ packB) & (uint32_t)half_mask_l);  // (see step_pair)
-                    const uint32_t deg = pack_v & 255u, r_loc = (pack_v >> 8) & 63u, t_loc = (pack_v >> 16) & 63u;
+                    PairSteps P = pair_head(q, qB, qs, pairable);
+                    const uint32_t r_locA = P.r_locA, s_prdA = P.s_prdA, r_locB = P.r_locB, s_prdB = P.s_prdB, t_locB = P.t_locB;
+                    const uint32_t prop = P.prop, deg = P.deg, r_loc = P.r_loc, t_loc = P.t_loc;
                     const int k0 = (int)hist8_cur[qs * kHistStride + lh], k1 = (int)hist8_cur[qs * kHistStride + lh + 32u];
                     const uint32_t a_rt0 = mq_at(r_loc, lh), a_rt1 = mq_at(r_loc, lh + 32u);
                     const int32_t m_rt_raw0 = mq[a_rt0], m_rt_raw1 = mq[a_rt1];
                     const int w0 = mq[mq_at(lh, t_loc)], w1 = mq[mq_at(lh + 32u, t_loc)];
-                    const uint32_t liveA = sflag((uint32_t)readlane(nr_own, r_locA) ^ 1u);
-                    const uint32_t liveB = smin((uint32_t)readlane(nr_own, r_locB) ^ 1u, pairable);
                     const int32_t kmask0 = (0 - k0) >> 31, kmask1 = (0 - k1) >> 31;
                     const int32_t m_rt0 = m_rt_raw0 & kmask0, m_rt1 = m_rt_raw1 & kmask1;
                     const uint32_t kk0 = (uint32_t)k0, kk1 = (uint32_t)k1;
-                    const int ideg = (int)deg;
                     // what depends on the target s (see step_pair): on the feeder's prediction, in front of the scan (kPredictTarget), or on
                     // the scan's result, behind it
-                    uint32_t s_loc, idx_l, a_st0, a_st1, e_idx, tail_idx;
-                    int32_t m_st_raw0, m_st_raw1, m_st0, m_st1;
-                    int ee, qn, qk;
-                    double tail_lg, logn, L1_0, L1_1, L2_0, L2_1, L3_0, L3_1, L4_0, L4_1;
-                    auto target_lds = [&](uint32_t sA, uint32_t sB, bool predicted) {
-                        if (predicted)
-                            s_loc = pack_v >> 24;
-                        else
-                            s_loc = sA + ((sB - sA) & (uint32_t)half_mask_l);
-                        idx_l = r_loc ^ ((r_loc ^ s_loc) & (uint32_t)odd_mask_l);  // odd lanes: s, even lanes: r
-                        a_st0 = mq_at(s_loc, lh), a_st1 = mq_at(s_loc, lh + 32u);
-                        m_st_raw0 = mq[a_st0], m_st_raw1 = mq[a_st1];
-                        e_idx = eta_at(idx_l, deg);
-                        ee = (int)eta_l[e_idx];
-                        const int mm = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), mr_own);
-                        const int nn = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), nr_own);
-                        m_st0 = m_st_raw0 & kmask0, m_st1 = m_st_raw1 & kmask1;
-                        qn = mm + __mul24(ideg, dsgn_l);        // m0r, m0s, m0r - deg, m0s + deg
-                        tail_idx = (uint32_t)((qn ^ ((qn ^ ee) & eta_mask_l)) + toff_l);
-                        qk = nn + dq_l;
-                    };
-                    auto target_gathers = [&]() {
-                        tail_lg = tab_at(tab.lg, tail_idx);
-                        logn = tab_at(tab.logtab, (uint32_t)qn);
-                        L2_0 = tab_at(tab.lg, (uint32_t)(m_st0 + 1)), L4_0 = tab_at(tab.lg, (uint32_t)(m_st0 + 1) + kk0);
-                        L2_1 = tab_at(tab.lg, (uint32_t)(m_st1 + 1)), L4_1 = tab_at(tab.lg, (uint32_t)(m_st1 + 1) + kk1);
-                    };
+                    TargetReads2 t;
+                    double L1_0, L1_1, L3_0, L3_1;
                     auto row_r_gathers = [&]() {
                         L1_0 = tab_at(tab.lg, (uint32_t)(m_rt0 + 1)), L3_0 = tab_at(tab.lg, (uint32_t)(m_rt0 + 1) - kk0);
                         L1_1 = tab_at(tab.lg, (uint32_t)(m_rt1 + 1)), L3_1 = tab_at(tab.lg, (uint32_t)(m_rt1 + 1) - kk1);
                     };
-                    const uint32_t s_prdA = packA >> 24, s_prdB = packB >> 24;
                     if constexpr (kPredictTarget) {
-                        target_lds(s_prdA, s_prdB, true);
-                        target_gathers();
+                        target_lds2(t, P.pack_v >> 24, r_loc, deg, kmask0, kmask1, lh, 32u);
+                        target_gathers2(t, kk0, kk1, std::false_type{});
                         row_r_gathers();
                         __asm__ volatile("" ::: "memory");
                     }
@@ -1252,19 +1434,8 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     __asm__("s_ff1_i32_b64 %0, %1" : "=s"(fhA) : "s"(hitsA));
                     __asm__("s_ff1_i32_b64 %0, %1" : "=s"(fhB) : "s"(hitsB));
                     const uint32_t s_locA = min(fhA, last_own), s_locB = min(fhB, last_own);
-                    const uint32_t selfA = 1u - sflag(s_locA ^ r_locA), selfB = 1u - sflag(s_locB ^ r_locB);
-                    const uint32_t warmA = CT ? 1u : ((uint32_t)(zeroT_mask >> q) & 1u) ^ 1u;
-                    const uint32_t warmB = CT ? 1u : ((uint32_t)(zeroT_mask >> qB) & 1u) ^ 1u;
-                    if ((selfA & selfB) != 0u) {  // both r == s: nothing changes (:109-112)
-                        acc_chunk += (liveA & warmA) + (liveB & warmB);
-                        if constexpr (TM) {
-                            if ((liveA & warmA) != 0u) new_minimum(q);
-                            if ((liveB & warmB) != 0u) new_minimum(qB);
-                        }
-                        PCOUNT(0, 1u);
-                        PCOUNT(1, 1u + pairable);
-                        return 1u + pairable;
-                    }
+                    pair_selfs(P, q, qB, s_locA, s_locB);
+                    if ((P.selfA & P.selfB) != 0u) return pair_both_self(tm, P, q, qB, pairable);
                     uint32_t pair_ok = pairable;  // step q + 1 is there and has been evaluated on its own target
                     if constexpr (kPredictTarget) {
                         // step q's target is not the predicted one: nothing has been written -- the caller sends step q down the general
@@ -1274,8 +1445,8 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                         if (__builtin_expect(s_locA != s_prdA, 0)) return 0u;
                         pair_ok = pairable & (sflag(s_locB ^ s_prdB) ^ 1u);
                     } else {
-                        target_lds(s_locA, s_locB, false);
-                        target_gathers();
+                        target_lds2(t, s_locA + ((s_locB - s_locA) & (uint32_t)half_mask_l), r_loc, deg, kmask0, kmask1, lh, 32u);
+                        target_gathers2(t, kk0, kk1, std::false_type{});
                     }
                     // (worked out while the gathers are in flight and pinned there, see step_pair: the verdict logic's inputs ...)
                     // would step q, if it moves its node, touch what step q + 1 read?  (step_pair's rule on 64-bit block sets)
@@ -1295,80 +1466,40 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const uint32_t col = (uint32_t)(between >> s_locB) & 1u;
                     const uint32_t set_clash = sflag((uint32_t)common | (uint32_t)(common >> 32));
                     const uint32_t clash = set_clash | (col & target_moves(margin, kAtB));
-                    const uint32_t flags = (liveA & (selfA ^ 1u)) | ((liveA & selfA & warmA) << 1) | ((liveB & (selfB ^ 1u)) << 2) |
-                                           ((liveB & selfB & warmB) << 3) | (clash << 4);
+                    const uint32_t flags = P.flags(clash);
                     uint32_t flags_pin = flags;
                     __asm__ volatile("" : "+s"(flags_pin));
                     (void)flags_pin;
                     // (... and what apply_mcmc_moves will write, to be masked by the movers)
                     int dlA = (int)min(lane ^ r_locA, 1u) - (int)min(lane ^ s_locA, 1u);  // +1 on lane s, -1 on lane r (lane <-> block)
                     int dlB = (int)min(lane ^ r_locB, 1u) - (int)min(lane ^ s_locB, 1u);
-                    int dmA = __mul24((int)degA, dlA), dmB = __mul24((int)degB, dlB);
+                    int dmA = __mul24((int)P.degA, dlA), dmB = __mul24((int)P.degB, dlB);
                     __asm__ volatile("" : "+v"(dlA), "+v"(dlB), "+v"(dmA), "+v"(dmB));
                     // the lane's two leaves of each sum, added first (level 32)
-                    const double a0 = k0 * (m_st0 + eps) * inv_lo + k1 * (m_st1 + eps) * inv_hi;
+                    const double a0 = k0 * (t.m_st0 + eps) * inv_lo + k1 * (t.m_st1 + eps) * inv_hi;
                     const double a1 = k0 * (m_rt0 - k0 + eps) * inv_lo + k1 * (m_rt1 - k1 + eps) * inv_hi;
                     double accu0, accu1;  // lanes 16..31: step q, lanes 48..63: step q + 1
                     butterfly_accu_rows32(a0, a1, accu0, accu1);
-                    const double lq = hot_log_q(std::false_type{}, qn, qk, logn);
-                    double d = (L1_0 + L2_0) - (L3_0 + L4_0);
-                    d = d + tail_lg * sign_tail;  // the scalar terms sit in leaves 0..7 / 0..3: the lane's lower leaf
+                    const double lq = hot_log_q(std::false_type{}, t.qn, t.qk, t.logn);
+                    double d = (L1_0 + t.L2_0) - (L3_0 + t.L4_0);
+                    d = d + t.tail_lg * sign_tail;  // the scalar terms sit in leaves 0..7 / 0..3: the lane's lower leaf
                     d = d + lq * sign_q;
-                    d = d + ((L1_1 + L2_1) - (L3_1 + L4_1));
+                    d = d + ((L1_1 + t.L2_1) - (L3_1 + t.L4_1));
                     const double dS = butterfly_rows32(d);
-                    double invT = invT_const;
-                    if (!CT) invT = invT_of(qs);
-                    const double z = -dS * invT;
-                    const double est = accu1 * exp2_filter(z * c_l2e);
-                    const double lhs = u_acc * accu0;
-                    unsigned long long b_acc = __builtin_amdgcn_ballot_w64(lhs < est);
-                    unsigned long long b_far = __builtin_amdgcn_ballot_w64(fabs(lhs - est) > c_tol * est);
-                    if (!CT) {  // steps at T = 0: dS < 0 decides (:49-50)
-                        const unsigned long long cold = ((unsigned long long)(0u - (warmB ^ 1u)) << 32) | (0u - (warmA ^ 1u));
-                        const unsigned long long b_neg = __builtin_amdgcn_ballot_w64(dS < 0.);
-                        b_acc = (b_acc & ~cold) | (b_neg & cold);
-                        b_far |= cold;
-                    }
-                    if (__builtin_expect((((uint32_t)b_far & (uint32_t)(b_far >> 32)) >> 31) == 0u, 0)) {  // a verdict too close to call
-                        const unsigned long long exact = __builtin_amdgcn_ballot_w64(lhs < accu1 * exp(z));
-                        b_acc = (b_acc & b_far) | (exact & ~b_far);
-                    }
-                    const uint32_t yesA = (uint32_t)(b_acc >> 31) & 1u, yesB = (uint32_t)(b_acc >> 63) & 1u;
-                    const uint32_t chA = flags & yesA;
-                    const uint32_t okA = chA | ((flags >> 1) & 1u);
-                    const uint32_t stands = pair_ok & ((chA & (flags >> 4)) ^ 1u);
-                    PASS_COUNTS_PAIR(pair_ok);
-                    const uint32_t chB = stands & (flags >> 2) & yesB;
-                    const uint32_t okB = chB | (stands & (flags >> 3) & 1u);
-                    acc_chunk += okA + okB;
-                    if ((TM ? (okA | okB) : (chA | chB)) != 0u) {
-                        const uint32_t mA = 0u - chA, mB = 0u - chB;
-                        const unsigned long long movers = ((unsigned long long)mB << 32) | mA;
-                        wfence();
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth64_lo)) {  // k == 0: rewrites the same values
-                            mq[a_rt0] = m_rt_raw0 - k0;
-                            mq[a_st0] = m_st_raw0 + k0;
-                        }
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth64_hi)) {
-                            mq[a_rt1] = m_rt_raw1 - k1;
-                            mq[a_st1] = m_st_raw1 + k1;
-                        }
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0000003000000030ull))  // lanes 4, 5: eta_r - 1, eta_s + 1
-                            eta_l[e_idx] = (uint32_t)(ee + ((int)(lh & 1u) * 2 - 1));
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0000000100000001ull)) new_lab[qs] = (uint8_t)(own_base + s_loc);
-                        mr_own += (dmA & (int)mA) + (dmB & (int)mB);
-                        nr_own += (dlA & (int)mA) + (dlB & (int)mB);
-                        if constexpr (TM) {  // (see step_pair)
-                            const int dS_A_lo = __builtin_amdgcn_readlane(__double2loint(dS), 31), dS_A_hi = __builtin_amdgcn_readlane(__double2hiint(dS), 31);
-                            const int dS_B_lo = __builtin_amdgcn_readlane(__double2loint(dS), 63), dS_B_hi = __builtin_amdgcn_readlane(__double2hiint(dS), 63);
-                            cum_l0 += __hiloint2double(dS_A_hi & (int)mA, dS_A_lo & (int)mA);
-                            if (okA) new_minimum(q);
-                            cum_l0 += __hiloint2double(dS_B_hi & (int)mB, dS_B_lo & (int)mB);
-                            if (okB) new_minimum(qB);
-                        }
-                        wfence();
-                    }
-                    return 1u + stands;
+                    const unsigned long long b_acc = accept_halves(dS, accu0, accu1, P.u_acc, qs, P.warmA, P.warmB);
+                    return pair_commit(
+                        tm, q, qB, qs, pair_ok, flags, b_acc, dS, dlA, dlB, dmA, dmB, t.e_idx, t.ee + ((int)(lh & 1u) * 2 - 1), t.s_loc,
+                        [&](unsigned long long movers) {
+                            if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth64_lo)) {
+                                mq[a_rt0] = m_rt_raw0 - k0;
+                                mq[t.a_st0] = t.m_st_raw0 + k0;
+                            }
+                            if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth64_hi)) {
+                                mq[a_rt1] = m_rt_raw1 - k1;
+                                mq[t.a_st1] = t.m_st_raw1 + k1;
+                            }
+                        },
+                        [&](uint32_t chA, uint32_t stands) { PASS_COUNTS_PAIR(pair_ok); });
                 };
 
                 // ---- four steps per pass (both block counts <= 16) ----
@@ -1379,6 +1510,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                 // conditions compose); the first step that does not stand opens the next pass.  The six pairwise tests
                 // are evaluated lane-parallel (lane 4 i + j: steps i and j) and arrive as one 16-bit word.
                 const uint32_t row = lane >> 4;
+                constexpr unsigned long long kRowRep = 0x8000800080008000ull;  // one lane per row (its last)
                 auto step_quad = [&](auto tm, uint32_t q, uint32_t nst) -> uint32_t {  // nst: steps of this pass that exist (1..4)
                     constexpr bool TM = decltype(tm)::value;
                     const uint32_t qs = q + min(row, nst - 1u);  // (rows past nst repeat the last step; their results are ignored)
@@ -1409,7 +1541,6 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const unsigned long long m_self = __builtin_amdgcn_ballot_w64(s_loc == r_loc);
                     // T = 0: r == s is not accepted, and dS < 0 decides the others (:49-50)
                     const unsigned long long m_warm = CT ? ~0ull : ~__builtin_amdgcn_ballot_w64(((zeroT_mask >> qs) & 1ull) != 0ull);
-                    constexpr unsigned long long kRowRep = 0x8000800080008000ull;  // one lane per row (its last)
                     const unsigned long long b_can = m_valid & m_live & ~m_self & kRowRep;
                     const unsigned long long b_selfok = m_valid & m_live & m_self & m_warm & kRowRep;
                     if (b_can == 0ull) {  // every step of the pass is an r == s (or a vetoed one): nothing changes (:109-112)
@@ -1418,135 +1549,34 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             if (b_selfok != 0ull) new_minimum(q + ((uint32_t)__builtin_ctzll(b_selfok) >> 4));  // (the first accepted one; the sum does not change)
                         return nst;
                     }
-                    const uint32_t idx_l = r_loc ^ ((r_loc ^ s_loc) & (uint32_t)odd_mask_l);  // odd lanes: s, even lanes: r
-                    const uint32_t a_st = mq_at(s_loc, lb);
-                    const int32_t m_st_raw = mq[a_st];
-                    const uint32_t e_idx = eta_at(idx_l, deg);
-                    const int ee = (int)eta_l[e_idx];
-                    const int mm = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), mr_own);
-                    const int nn = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), nr_own);
-                    const int32_t m_st = m_st_raw & kmask;
-                    const int ideg = (int)deg;
-                    const int qn = mm + __mul24(ideg, dsgn_l);        // m0r, m0s, m0r - deg, m0s + deg
-                    const uint32_t tail_idx = (uint32_t)((qn ^ ((qn ^ ee) & eta_mask_l)) + toff_l);
-                    const int qk = nn + dq_l;
-                    const double tail_lg = tab_at(tab.lg, tail_idx);
-                    const double logn = tab_at(tab.logtab, (uint32_t)qn);
-                    const double L2 = tab_at(tab.lg, (uint32_t)(m_st + 1));
-                    const double L4 = tab_at(tab.lg, (uint32_t)(m_st + 1) + kk);
-                    const double a0 = k * (m_st + eps) * inv_blk;
+                    TargetReads t;
+                    target_lds(t, s_loc, r_loc, deg, kmask);
+                    target_gathers(t, kk, std::false_type{});
+                    const double a0 = k * (t.m_st + eps) * inv_blk;
                     const double a1 = k * (m_rt - k + eps) * inv_blk;
                     const double accu0 = butterfly_rows16(a0);  // every lane of a row: the row's sum
                     const double accu1 = butterfly_rows16(a1);
-                    const double lq = hot_log_q(std::true_type{}, qn, qk, logn);
-                    // pairwise: would step i, if it moves its node, touch what step j read?  (lane 4 i + j, any row)
-                    // (worked out while the table gathers are in flight: after ALL of them have been issued -- the table tier of log_q is one more --, see step_pair)
-                    uint32_t clash_bits;
-                    {
-                        uint32_t r_c = r_loc, s_c = s_loc, t_c = t_loc;
-                        __asm__ volatile("" : "+v"(r_c), "+v"(s_c), "+v"(t_c)::"memory");
-                        const int li = (int)(((lane >> 2) & 3u) << 6), lj = (int)((lane & 3u) << 6);  // lane 16 i, lane 16 j
-                        const uint32_t r_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)r_c);
-                        const uint32_t s_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)s_c);
-                        const uint32_t r_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)r_c);
-                        const uint32_t s_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)s_c);
-                        const uint32_t t_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)t_c);
-                        const uint32_t k_i_tj = (uint32_t)__builtin_amdgcn_ds_bpermute(li + (int)(t_j << 2), (int)kk);  // k of step i at block t_j
-                        const uint32_t set_i = (1u << r_i) | (1u << s_i), set_j = (1u << r_j) | (1u << s_j);
-                        const uint32_t lo = min(r_i, s_i), hi = max(r_i, s_i);
-                        const uint32_t between = ((1u << hi) - 1u) & ~((2u << lo) - 1u);  // blocks strictly between r_i and s_i
-                        // (bit arithmetic, no short-circuit: a lane-divergent `||` becomes a branch over the execution mask)
-                        const uint32_t in_between = (between >> s_j) & min(k_i_tj, 1u);
-                        clash_bits = (uint32_t)__builtin_amdgcn_ballot_w64(((set_i & set_j) | in_between) != 0u) & 0xffffu;  // bit 4 i + j
-                    }
-                    double d = (L1 + L2) - (L3 + L4);
-                    d = d + tail_lg * sign_tail;
+                    const double lq = hot_log_q(std::true_type{}, t.qn, t.qk, t.logn);
+                    // lane 4 i + j, any row: steps i and j (first lanes 16 i, 16 j); bit 4 i + j of the word
+                    const uint32_t clash_bits =
+                        (uint32_t)clash_pairs(r_loc, s_loc, t_loc, (int)(((lane >> 2) & 3u) << 6), (int)((lane & 3u) << 6), [&](int li, uint32_t t_j) {
+                            return (uint32_t)__builtin_amdgcn_ds_bpermute(li + (int)(t_j << 2), (int)kk);  // k of step i at block t_j
+                        }) & 0xffffu;
+                    double d = (L1 + t.L2) - (L3 + t.L4);
+                    d = d + t.tail_lg * sign_tail;
                     d = d + lq * sign_q;
                     const double dS = butterfly_rows16(d);
-                    // accept (:47-61), per row
-                    double invT = invT_const;
-                    if (!CT) invT = invT_of(qs);
-                    const double z = -dS * invT;
-                    const double est = accu1 * exp2_filter(z * c_l2e);
-                    const double lhs = u_acc * accu0;
-                    unsigned long long b_acc = __builtin_amdgcn_ballot_w64(lhs < est);
-                    unsigned long long b_far = __builtin_amdgcn_ballot_w64(fabs(lhs - est) > c_tol * est);
-                    if (!CT) {  // steps at T = 0: dS < 0 decides (:49-50); nothing to be close to
-                        b_acc = (b_acc & m_warm) | (__builtin_amdgcn_ballot_w64(dS < 0.) & ~m_warm);
-                        b_far |= ~m_warm;
-                    }
-                    if (__builtin_expect((~b_far & b_can) != 0ull, 0)) {  // a verdict too close to call
-                        const unsigned long long exact = __builtin_amdgcn_ballot_w64(lhs < accu1 * exp(z));
-                        b_acc = (b_acc & b_far) | (exact & ~b_far);
-                    }
-                    // verdicts, in step order: bits 15 / 31 / 47 / 63 -> bits 0..3
-                    auto rows4 = [](unsigned long long b) -> uint32_t {
-                        const unsigned long long x = b >> 15;
-                        return (uint32_t)(x | (x >> 15) | (x >> 30) | (x >> 45)) & 0xfu;
-                    };
+                    const unsigned long long b_acc = accept_rows(dS, accu0, accu1, u_acc, qs, m_warm, b_can);  // per row
                     const uint32_t mv4 = rows4(b_can & b_acc), selfok4 = rows4(b_selfok);
-                    // commit_j: steps 0..j all stand.  moved bits of committed steps only.
-                    uint32_t moved = mv4 & 1u, commit = 1u;
-                    {
-                        const uint32_t c01 = (clash_bits >> 1) & 1u, c02 = (clash_bits >> 2) & 1u, c03 = (clash_bits >> 3) & 1u;
-                        const uint32_t c12 = (clash_bits >> 6) & 1u, c13 = (clash_bits >> 7) & 1u, c23 = (clash_bits >> 11) & 1u;
-                        const uint32_t m0 = moved & 1u;
-                        const uint32_t k1 = sflag(nst - 1u) & ((m0 & c01) ^ 1u);  // (nst >= 2)
-                        const uint32_t m1 = k1 & (mv4 >> 1) & 1u;
-                        const uint32_t k2 = k1 & (nst > 2u ? 1u : 0u) & ((m0 & c02) ^ 1u) & ((m1 & c12) ^ 1u);
-                        const uint32_t m2 = k2 & (mv4 >> 2) & 1u;
-                        const uint32_t k3 = k2 & (nst > 3u ? 1u : 0u) & ((m0 & c03) ^ 1u) & ((m1 & c13) ^ 1u) & ((m2 & c23) ^ 1u);
-                        const uint32_t m3 = k3 & (mv4 >> 3) & 1u;
-                        commit = 1u | (k1 << 1) | (k2 << 2) | (k3 << 3);
-                        moved = m0 | (m1 << 1) | (m2 << 2) | (m3 << 3);
-                    }
-                    acc_chunk += (uint32_t)__builtin_popcount(moved | (commit & selfok4));
-                    if ((TM ? (moved | (commit & selfok4)) : moved) != 0u) {
-                        // ---- apply_mcmc_moves, blockmodel.cc:461-503, for the steps that move: their rows of m differ ----
-                        const unsigned long long movers = __builtin_amdgcn_ballot_w64(((moved >> row) & 1u) != 0u);  // all lanes of every mover's row
-                        wfence();
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {  // k == 0: rewrites the same values
+                    uint32_t moved, commit;
+                    commit_four(nst, clash_bits, mv4, moved, commit);
+                    apply_moves(tm, Four{}, q, qs, row, moved, commit & selfok4, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
+                        if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {
                             mq[a_rt] = m_rt_raw - k;
-                            mq[a_st] = m_st_raw + k;
+                            mq[t.a_st] = t.m_st_raw + k;
                         }
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0030003000300030ull))  // lanes 4, 5 of a row: eta_r - 1, eta_s + 1
-                            eta_l[e_idx] = (uint32_t)(ee + ((int)(lb & 1u) * 2 - 1));
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0001000100010001ull)) new_lab[qs] = (uint8_t)(own_base + s_loc);
-                        // the register copies of m_r / n_r, sum dS (:500) and the early-stop bookkeeping, in step order
-#pragma unroll
-                        for (uint32_t g = 0; g < 4u; ++g) {
-                            if ((moved >> g) & 1u) {
-                                const uint32_t rg = readlane(r_loc, 16u * g), sg = readlane(s_loc, 16u * g), dg = readlane(deg, 16u * g);
-                                const int dl = (int)min(lb ^ rg, 1u) - (int)min(lb ^ sg, 1u);  // +1 on lane s, -1 on lane r
-                                mr_own += __mul24((int)dg, dl);
-                                nr_own += dl;
-                                if constexpr (TM) cum_l0 += readlane(dS, 16u * g + 15u);
-                                if constexpr (TM) new_minimum(q + g);
-                            } else if (TM && (((commit & selfok4) >> g) & 1u)) {
-                                new_minimum(q + g);  // an accepted r == s step (see new_minimum)
-                            }
-                        }
-                        wfence();
-                    }
+                    });
                     return (uint32_t)__builtin_popcount(commit);
-                };
-                auto quad_loop = [&](auto tm) {
-                    uint32_t q = 0;
-                    acc_chunk = 0;
-                    while (q < cnt) {
-                        const uint32_t four = (uint32_t)(gen_mask >> q) & 0xfu;
-                        if (__builtin_expect((four & 1u) != 0u, 0)) {
-                            step_general(q, T_of_step(q));
-                            q += 1u;
-                        } else {  // the steps up to the next one that needs the general path, or to the end of the chunk
-                            const uint32_t nst = min(min((uint32_t)__builtin_ctz(four | 0x10u), 4u), cnt - q);
-                            const uint32_t done = step_quad(tm, q, nst);
-                            PCOUNT(0, 1u);
-                            PCOUNT(1, done);
-                            q += done;
-                        }
-                    }
-                    acc_l0 += (unsigned long long)acc_chunk;
                 };
                 // ---- four steps per pass with 17..32 blocks of a type (the Q32 variant) ----
                 // step_quad with TWO leaves per lane, the way step_pair64 extends step_pair: lane l of row g (step q + g) holds the
@@ -1554,7 +1584,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                 // three sums -- and, for the inverse CDF, entries l and l + 16 of column t.  The summation trees are the 64-leaf ones
                 // (bisbm_device.hpp): the Hastings sums have level 16 second, so the lane adds its two leaves first; dS has it last,
                 // so its two 16-leaf halves are summed separately and added at the end.  m_r / n_r sit one block per lane (two copies,
-                // lanes 0..31 and 32..63) and are read by lane index.  Stand rule, verdicts and writes are step_quad's.
+                // lanes 0..31 and 32..63) and are read by lane index.  Stand rule, verdicts and writes are the ones step_quad uses.
                 auto step_quad32 = [&](auto tm, uint32_t q, uint32_t nst) -> uint32_t {  // nst: steps of this pass that exist (1..4)
                     constexpr bool TM = decltype(tm)::value;
                     const uint32_t qs = q + min(row, nst - 1u);  // (rows past nst repeat the last step; their results are ignored)
@@ -1593,7 +1623,6 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const unsigned long long m_self = __builtin_amdgcn_ballot_w64(s_loc == r_loc);
                     // T = 0: r == s is not accepted, and dS < 0 decides the others (:49-50)
                     const unsigned long long m_warm = CT ? ~0ull : ~__builtin_amdgcn_ballot_w64(((zeroT_mask >> qs) & 1ull) != 0ull);
-                    constexpr unsigned long long kRowRep = 0x8000800080008000ull;  // one lane per row (its last)
                     const unsigned long long b_can = m_valid & m_live & ~m_self & kRowRep;
                     const unsigned long long b_selfok = m_valid & m_live & m_self & m_warm & kRowRep;
                     if (b_can == 0ull) {  // every step of the pass is an r == s (or a vetoed one): nothing changes (:109-112)
@@ -1602,143 +1631,43 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             if (b_selfok != 0ull) new_minimum(q + ((uint32_t)__builtin_ctzll(b_selfok) >> 4));
                         return nst;
                     }
-                    const uint32_t idx_l = r_loc ^ ((r_loc ^ s_loc) & (uint32_t)odd_mask_l);  // odd lanes: s, even lanes: r
-                    const uint32_t a_st0 = mq_at(s_loc, l16), a_st1 = mq_at(s_loc, l16 + 16u);
-                    const int32_t m_st_raw0 = mq[a_st0], m_st_raw1 = mq[a_st1];
-                    const uint32_t e_idx = eta_at(idx_l, deg);
-                    const int ee = (int)eta_l[e_idx];
-                    const int mm = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), mr_own);
-                    const int nn = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), nr_own);
-                    const int32_t m_st0 = m_st_raw0 & kmask0, m_st1 = m_st_raw1 & kmask1;
-                    const int ideg = (int)deg;
-                    const int qn = mm + __mul24(ideg, dsgn_l);        // m0r, m0s, m0r - deg, m0s + deg
-                    const uint32_t tail_idx = (uint32_t)((qn ^ ((qn ^ ee) & eta_mask_l)) + toff_l);
-                    const int qk = nn + dq_l;
-                    const double logn = tab_at(tab.logtab, (uint32_t)qn);
-                    const double tail_lg = tab_at(tab.lg, tail_idx);
-                    const double L2_0 = tab_at(tab.lg, (uint32_t)(m_st0 + 1)), L4_0 = tab_at(tab.lg, (uint32_t)(m_st0 + 1) + kk0);
-                    const double L2_1 = tab_at(tab.lg, (uint32_t)(m_st1 + 1)), L4_1 = tab_at(tab.lg, (uint32_t)(m_st1 + 1) + kk1);
+                    TargetReads2 t;
+                    target_lds2(t, s_loc, r_loc, deg, kmask0, kmask1, l16, 16u);
+                    target_gathers2(t, kk0, kk1, std::true_type{});
                     // the lane's two leaves of each Hastings sum, added first (level 16 of their tree)
-                    const double a0 = k0 * (m_st0 + eps) * invq_lo + k1 * (m_st1 + eps) * invq_hi;
+                    const double a0 = k0 * (t.m_st0 + eps) * invq_lo + k1 * (t.m_st1 + eps) * invq_hi;
                     const double a1 = k0 * (m_rt0 - k0 + eps) * invq_lo + k1 * (m_rt1 - k1 + eps) * invq_hi;
                     const double accu0 = butterfly_rows16(a0);  // every lane of a row: the row's sum
                     const double accu1 = butterfly_rows16(a1);
-                    const double lq = hot_log_q(std::false_type{}, qn, qk, logn);
-                    // pairwise: would step i, if it moves its node, touch what step j read?  (lane 4 i + j, any row)
-                    // (worked out while the table gathers are in flight: after ALL of them have been issued -- the table tier of log_q is one more --, see step_pair)
-                    uint32_t clash_bits;
-                    {
-                        uint32_t r_c = r_loc, s_c = s_loc, t_c = t_loc;
-                        __asm__ volatile("" : "+v"(r_c), "+v"(s_c), "+v"(t_c)::"memory");
-                        const int li = (int)(((lane >> 2) & 3u) << 6), lj = (int)((lane & 3u) << 6);  // lane 16 i, lane 16 j
-                        const uint32_t r_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)r_c);
-                        const uint32_t s_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)s_c);
-                        const uint32_t r_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)r_c);
-                        const uint32_t s_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)s_c);
-                        const uint32_t t_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)t_c);
-                        const int src = li + (int)((t_j & 15u) << 2);  // k of step i at block t_j: leaf t_j >> 4 of lane t_j & 15 of row i
-                        const uint32_t k_lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk0);
-                        const uint32_t k_hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk1);
-                        const uint32_t k_i_tj = k_lo ^ ((k_lo ^ k_hi) & (0u - (t_j >> 4)));
-                        const uint32_t set_i = (1u << r_i) | (1u << s_i), set_j = (1u << r_j) | (1u << s_j);
-                        const uint32_t lo = min(r_i, s_i), hi = max(r_i, s_i);
-                        const uint32_t between = ((1u << hi) - 1u) & ~((2u << lo) - 1u);  // blocks strictly between r_i and s_i
-                        // (bit arithmetic, no short-circuit: a lane-divergent `||` becomes a branch over the execution mask)
-                        const uint32_t in_between = (between >> s_j) & min(k_i_tj, 1u);
-                        clash_bits = (uint32_t)__builtin_amdgcn_ballot_w64(((set_i & set_j) | in_between) != 0u) & 0xffffu;  // bit 4 i + j
-                    }
-                    double d0 = (L1_0 + L2_0) - (L3_0 + L4_0);
-                    d0 = d0 + tail_lg * sign_tail;  // the scalar terms sit in leaves 0..7 / 0..3: the lane's lower leaf
+                    const double lq = hot_log_q(std::false_type{}, t.qn, t.qk, t.logn);
+                    // lane 4 i + j, any row: steps i and j, as in step_quad
+                    const uint32_t clash_bits =
+                        (uint32_t)clash_pairs(r_loc, s_loc, t_loc, (int)(((lane >> 2) & 3u) << 6), (int)((lane & 3u) << 6), [&](int li, uint32_t t_j) {
+                            const int src = li + (int)((t_j & 15u) << 2);  // k of step i at block t_j: leaf t_j >> 4 of lane t_j & 15 of row i
+                            const uint32_t k_lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk0);
+                            const uint32_t k_hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk1);
+                            return k_lo ^ ((k_lo ^ k_hi) & (0u - (t_j >> 4)));
+                        }) & 0xffffu;
+                    double d0 = (L1_0 + t.L2_0) - (L3_0 + t.L4_0);
+                    d0 = d0 + t.tail_lg * sign_tail;  // the scalar terms sit in leaves 0..7 / 0..3: the lane's lower leaf
                     d0 = d0 + lq * sign_q;
-                    const double d1 = (L1_1 + L2_1) - (L3_1 + L4_1);
+                    const double d1 = (L1_1 + t.L2_1) - (L3_1 + t.L4_1);
                     const double dS = butterfly_rows16(d1) + butterfly_rows16(d0);  // level 16 of the dS tree comes last
-                    // accept (:47-61), per row
-                    double invT = invT_const;
-                    if (!CT) invT = invT_of(qs);
-                    const double z = -dS * invT;
-                    const double est = accu1 * exp2_filter(z * c_l2e);
-                    const double lhs = u_acc * accu0;
-                    unsigned long long b_acc = __builtin_amdgcn_ballot_w64(lhs < est);
-                    unsigned long long b_far = __builtin_amdgcn_ballot_w64(fabs(lhs - est) > c_tol * est);
-                    if (!CT) {  // steps at T = 0: dS < 0 decides (:49-50); nothing to be close to
-                        b_acc = (b_acc & m_warm) | (__builtin_amdgcn_ballot_w64(dS < 0.) & ~m_warm);
-                        b_far |= ~m_warm;
-                    }
-                    if (__builtin_expect((~b_far & b_can) != 0ull, 0)) {  // a verdict too close to call
-                        const unsigned long long exact = __builtin_amdgcn_ballot_w64(lhs < accu1 * exp(z));
-                        b_acc = (b_acc & b_far) | (exact & ~b_far);
-                    }
-                    // verdicts, in step order: bits 15 / 31 / 47 / 63 -> bits 0..3
-                    auto rows4 = [](unsigned long long b) -> uint32_t {
-                        const unsigned long long x = b >> 15;
-                        return (uint32_t)(x | (x >> 15) | (x >> 30) | (x >> 45)) & 0xfu;
-                    };
+                    const unsigned long long b_acc = accept_rows(dS, accu0, accu1, u_acc, qs, m_warm, b_can);  // per row
                     const uint32_t mv4 = rows4(b_can & b_acc), selfok4 = rows4(b_selfok);
-                    uint32_t moved = mv4 & 1u, commit = 1u;
-                    {
-                        const uint32_t c01 = (clash_bits >> 1) & 1u, c02 = (clash_bits >> 2) & 1u, c03 = (clash_bits >> 3) & 1u;
-                        const uint32_t c12 = (clash_bits >> 6) & 1u, c13 = (clash_bits >> 7) & 1u, c23 = (clash_bits >> 11) & 1u;
-                        const uint32_t m0 = moved & 1u;
-                        const uint32_t k1c = sflag(nst - 1u) & ((m0 & c01) ^ 1u);  // (nst >= 2)
-                        const uint32_t m1 = k1c & (mv4 >> 1) & 1u;
-                        const uint32_t k2c = k1c & (nst > 2u ? 1u : 0u) & ((m0 & c02) ^ 1u) & ((m1 & c12) ^ 1u);
-                        const uint32_t m2 = k2c & (mv4 >> 2) & 1u;
-                        const uint32_t k3c = k2c & (nst > 3u ? 1u : 0u) & ((m0 & c03) ^ 1u) & ((m1 & c13) ^ 1u) & ((m2 & c23) ^ 1u);
-                        const uint32_t m3 = k3c & (mv4 >> 3) & 1u;
-                        commit = 1u | (k1c << 1) | (k2c << 2) | (k3c << 3);
-                        moved = m0 | (m1 << 1) | (m2 << 2) | (m3 << 3);
-                    }
-                    acc_chunk += (uint32_t)__builtin_popcount(moved | (commit & selfok4));
-                    if ((TM ? (moved | (commit & selfok4)) : moved) != 0u) {
-                        // ---- apply_mcmc_moves, blockmodel.cc:461-503, for the steps that move: their rows of m differ ----
-                        const unsigned long long movers = __builtin_amdgcn_ballot_w64(((moved >> row) & 1u) != 0u);  // all lanes of every mover's row
-                        wfence();
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth32_lo)) {  // k == 0: rewrites the same values
+                    uint32_t moved, commit;
+                    commit_four(nst, clash_bits, mv4, moved, commit);
+                    apply_moves(tm, Four{}, q, qs, row, moved, commit & selfok4, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
+                        if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth32_lo)) {
                             mq[a_rt0] = m_rt_raw0 - k0;
-                            mq[a_st0] = m_st_raw0 + k0;
+                            mq[t.a_st0] = t.m_st_raw0 + k0;
                         }
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth32_hi)) {
                             mq[a_rt1] = m_rt_raw1 - k1;
-                            mq[a_st1] = m_st_raw1 + k1;
+                            mq[t.a_st1] = t.m_st_raw1 + k1;
                         }
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0030003000300030ull))  // lanes 4, 5 of a row: eta_r - 1, eta_s + 1
-                            eta_l[e_idx] = (uint32_t)(ee + ((int)(lane & 1u) * 2 - 1));
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0001000100010001ull)) new_lab[qs] = (uint8_t)(own_base + s_loc);
-                        // the register copies of m_r / n_r, sum dS (:500) and the early-stop bookkeeping, in step order
-#pragma unroll
-                        for (uint32_t g = 0; g < 4u; ++g) {
-                            if ((moved >> g) & 1u) {
-                                const uint32_t rg = readlane(r_loc, 16u * g), sg = readlane(s_loc, 16u * g), dg = readlane(deg, 16u * g);
-                                const int dl = (int)min(lb ^ rg, 1u) - (int)min(lb ^ sg, 1u);  // +1 on lane s, -1 on lane r
-                                mr_own += __mul24((int)dg, dl);
-                                nr_own += dl;
-                                if constexpr (TM) cum_l0 += readlane(dS, 16u * g + 15u);
-                                if constexpr (TM) new_minimum(q + g);
-                            } else if (TM && (((commit & selfok4) >> g) & 1u)) {
-                                new_minimum(q + g);  // an accepted r == s step (see new_minimum)
-                            }
-                        }
-                        wfence();
-                    }
+                    });
                     return (uint32_t)__builtin_popcount(commit);
-                };
-                auto quad32_loop = [&](auto tm) {
-                    uint32_t q = 0;
-                    acc_chunk = 0;
-                    while (q < cnt) {
-                        const uint32_t four = (uint32_t)(gen_mask >> q) & 0xfu;
-                        if (__builtin_expect((four & 1u) != 0u, 0)) {
-                            step_general(q, T_of_step(q));
-                            q += 1u;
-                        } else {  // the steps up to the next one that needs the general path, or to the end of the chunk
-                            const uint32_t nst = min(min((uint32_t)__builtin_ctz(four | 0x10u), 4u), cnt - q);
-                            const uint32_t done = step_quad32(tm, q, nst);
-                            PCOUNT(0, 1u);
-                            PCOUNT(1, done);
-                            q += done;
-                        }
-                    }
-                    acc_l0 += (unsigned long long)acc_chunk;
                 };
                 // ---- eight steps per pass (both block counts <= 8) ----
                 // step_quad once more: group g of eight lanes evaluates step q + g.  The 28 pairwise tests fill the wave (lane
@@ -1783,63 +1712,24 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             if (b_selfok != 0ull) new_minimum(q + ((uint32_t)__builtin_ctzll(b_selfok) >> 3));
                         return nst;
                     }
-                    const uint32_t idx_l = r_loc ^ ((r_loc ^ s_loc) & (uint32_t)odd_mask_l);
-                    const uint32_t a_st = mq_at(s_loc, lb);
-                    const int32_t m_st_raw = mq[a_st];
-                    const uint32_t e_idx = eta_at(idx_l, deg);
-                    const int ee = (int)eta_l[e_idx];
-                    const int mm = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), mr_own);
-                    const int nn = __builtin_amdgcn_ds_bpermute((int)(idx_l << 2), nr_own);
-                    const int32_t m_st = m_st_raw & kmask;
-                    const int ideg = (int)deg;
-                    const int qn = mm + __mul24(ideg, dsgn_l);
-                    const uint32_t tail_idx = (uint32_t)((qn ^ ((qn ^ ee) & eta_mask_l)) + toff_l);
-                    const int qk = nn + dq_l;
-                    const double tail_lg = tab_at(tab.lg, tail_idx);
-                    const double logn = tab_at(tab.logtab, (uint32_t)qn);
-                    const double L2 = tab_at(tab.lg, (uint32_t)(m_st + 1));
-                    const double L4 = tab_at(tab.lg, (uint32_t)(m_st + 1) + kk);
-                    const double a0 = k * (m_st + eps) * inv_blk;
+                    TargetReads t;
+                    target_lds(t, s_loc, r_loc, deg, kmask);
+                    target_gathers(t, kk, std::false_type{});
+                    const double a0 = k * (t.m_st + eps) * inv_blk;
                     const double a1 = k * (m_rt - k + eps) * inv_blk;
                     const double accu0 = butterfly_groups8(a0);
                     const double accu1 = butterfly_groups8(a1);
-                    const double lq = hot_log_q(std::true_type{}, qn, qk, logn);
-                    unsigned long long clash_bits;  // byte j, bit i: step i (earlier), if it moves, touches what step j read
-                    {  // (worked out while the table gathers are in flight: after ALL of them have been issued -- the table tier of log_q is one more --, see step_pair)
-                        uint32_t r_c = r_loc, s_c = s_loc, t_c = t_loc;
-                        __asm__ volatile("" : "+v"(r_c), "+v"(s_c), "+v"(t_c)::"memory");
-                        const int li = (int)((lane & 7u) << 5), lj = (int)((lane >> 3) << 5);  // lane 8 i, lane 8 j
-                        const uint32_t r_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)r_c);
-                        const uint32_t s_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)s_c);
-                        const uint32_t r_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)r_c);
-                        const uint32_t s_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)s_c);
-                        const uint32_t t_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)t_c);
-                        const uint32_t k_i_tj = (uint32_t)__builtin_amdgcn_ds_bpermute(li + (int)(t_j << 2), (int)kk);
-                        const uint32_t set_i = (1u << r_i) | (1u << s_i), set_j = (1u << r_j) | (1u << s_j);
-                        const uint32_t lo = min(r_i, s_i), hi = max(r_i, s_i);
-                        const uint32_t between = ((1u << hi) - 1u) & ~((2u << lo) - 1u);
-                        const uint32_t in_between = (between >> s_j) & min(k_i_tj, 1u);  // (bit arithmetic: no lane-divergent branch)
-                        clash_bits = __builtin_amdgcn_ballot_w64(((set_i & set_j) | in_between) != 0u);
-                    }
-                    double d = (L1 + L2) - (L3 + L4);
-                    d = d + tail_lg * sign_tail;
+                    const double lq = hot_log_q(std::true_type{}, t.qn, t.qk, t.logn);
+                    // lane 8 j + i: steps i and j (first lanes 8 i, 8 j).  byte j, bit i: step i (earlier), if it moves, touches what step j read
+                    const unsigned long long clash_bits =
+                        clash_pairs(r_loc, s_loc, t_loc, (int)((lane & 7u) << 5), (int)((lane >> 3) << 5), [&](int li, uint32_t t_j) {
+                            return (uint32_t)__builtin_amdgcn_ds_bpermute(li + (int)(t_j << 2), (int)kk);
+                        });
+                    double d = (L1 + t.L2) - (L3 + t.L4);
+                    d = d + t.tail_lg * sign_tail;
                     d = d + lq * sign_q;
                     const double dS = butterfly_groups8(d);
-                    double invT = invT_const;
-                    if (!CT) invT = invT_of(qs);
-                    const double z = -dS * invT;
-                    const double est = accu1 * exp2_filter(z * c_l2e);
-                    const double lhs = u_acc * accu0;
-                    unsigned long long b_acc = __builtin_amdgcn_ballot_w64(lhs < est);
-                    unsigned long long b_far = __builtin_amdgcn_ballot_w64(fabs(lhs - est) > c_tol * est);
-                    if (!CT) {  // steps at T = 0: dS < 0 decides (:49-50); nothing to be close to
-                        b_acc = (b_acc & m_warm) | (__builtin_amdgcn_ballot_w64(dS < 0.) & ~m_warm);
-                        b_far |= ~m_warm;
-                    }
-                    if (__builtin_expect((~b_far & b_can) != 0ull, 0)) {
-                        const unsigned long long exact = __builtin_amdgcn_ballot_w64(lhs < accu1 * exp(z));
-                        b_acc = (b_acc & b_far) | (exact & ~b_far);
-                    }
+                    const unsigned long long b_acc = accept_rows(dS, accu0, accu1, u_acc, qs, m_warm, b_can);
                     // bits 7 / 15 / ... / 63 -> bits 0..7
                     auto groups8 = [](unsigned long long b) -> uint32_t { return (uint32_t)(((b >> 7) * 0x0102040810204080ull) >> 56) & 0xffu; };
                     const uint32_t mv8 = groups8(b_can & b_acc), selfok8 = groups8(b_selfok);
@@ -1851,51 +1741,13 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                         commit |= stands << j;
                         moved |= (stands & (mv8 >> j) & 1u) << j;
                     }
-                    acc_chunk += (uint32_t)__builtin_popcount(moved | (commit & selfok8));
-                    if ((TM ? (moved | (commit & selfok8)) : moved) != 0u) {
-                        const unsigned long long movers = __builtin_amdgcn_ballot_w64(((moved >> grp) & 1u) != 0u);  // all eight lanes of every mover's group
-                        wfence();
+                    apply_moves(tm, Eight{}, q, qs, grp, moved, commit & selfok8, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {
                             mq[a_rt] = m_rt_raw - k;
-                            mq[a_st] = m_st_raw + k;
+                            mq[t.a_st] = t.m_st_raw + k;
                         }
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x3030303030303030ull))  // lanes 4, 5 of a group: eta_r - 1, eta_s + 1
-                            eta_l[e_idx] = (uint32_t)(ee + ((int)(lb & 1u) * 2 - 1));
-                        if (__builtin_amdgcn_inverse_ballot_w64(movers & 0x0101010101010101ull)) new_lab[qs] = (uint8_t)(own_base + s_loc);
-#pragma unroll
-                        for (uint32_t g = 0; g < 8u; ++g) {
-                            if ((moved >> g) & 1u) {
-                                const uint32_t rg = readlane(r_loc, 8u * g), sg = readlane(s_loc, 8u * g), dg = readlane(deg, 8u * g);
-                                const int dl = (int)min(lb ^ rg, 1u) - (int)min(lb ^ sg, 1u);
-                                mr_own += __mul24((int)dg, dl);
-                                nr_own += dl;
-                                if constexpr (TM) cum_l0 += readlane(dS, 8u * g + 7u);
-                                if constexpr (TM) new_minimum(q + g);
-                            } else if (TM && (((commit & selfok8) >> g) & 1u)) {
-                                new_minimum(q + g);
-                            }
-                        }
-                        wfence();
-                    }
+                    });
                     return (uint32_t)__builtin_popcount(commit);
-                };
-                auto oct_loop = [&](auto tm) {
-                    uint32_t q = 0;
-                    acc_chunk = 0;
-                    while (q < cnt) {
-                        const uint32_t eight = (uint32_t)(gen_mask >> q) & 0xffu;
-                        if (__builtin_expect((eight & 1u) != 0u, 0)) {
-                            step_general(q, T_of_step(q));
-                            q += 1u;
-                        } else {
-                            const uint32_t nst = min(min((uint32_t)__builtin_ctz(eight | 0x100u), 8u), cnt - q);
-                            const uint32_t done = step_oct(tm, q, nst);
-                            PCOUNT(0, 1u);
-                            PCOUNT(1, done);
-                            q += done;
-                        }
-                    }
-                    acc_l0 += (unsigned long long)acc_chunk;
                 };
                 // steps that need the general path (bit 31 of prop_l) go one at a time
                 auto pair_loop = [&](auto tm) {
@@ -1925,19 +1777,19 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                         pair_loop(std::false_type{});
                 } else if (K8 && oct_mode) {
                     if (track_min != 0u)
-                        oct_loop(std::true_type{});
+                        multi_loop(std::true_type{}, Eight{}, step_oct);
                     else
-                        oct_loop(std::false_type{});
+                        multi_loop(std::false_type{}, Eight{}, step_oct);
                 } else if (K16 && quad_mode) {
                     if (track_min != 0u)
-                        quad_loop(std::true_type{});
+                        multi_loop(std::true_type{}, Four{}, step_quad);
                     else
-                        quad_loop(std::false_type{});
+                        multi_loop(std::false_type{}, Four{}, step_quad);
                 } else if (Q32 && quad32_mode) {
                     if (track_min != 0u)
-                        quad32_loop(std::true_type{});
+                        multi_loop(std::true_type{}, Four{}, step_quad32);
                     else
-                        quad32_loop(std::false_type{});
+                        multi_loop(std::false_type{}, Four{}, step_quad32);
                 } else if (K32 && !K16 && !Q32 && pair_mode) {  // (the K <= 16 / K <= 8 kernels hold their own kind of pass only: registers)
                     if (track_min != 0u)
                         pair_loop(std::true_type{});

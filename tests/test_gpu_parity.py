@@ -152,6 +152,28 @@ def test_eta_window_in_lds(name, window, monkeypatch):
     production kernel keeps a window of it there -- the rows of the phase's own type, a run of consecutive degrees placed where
     most nodes are -- and steps of nodes of other degrees take the general step with eta in HBM.  Whatever the window (the
     library's choice, or three degrees / one degree wide: most steps outside), the chains equal the oracle's."""
+    _eta_window_chains_equal_oracle(name, window, monkeypatch)
+
+
+# case, BISBM_PASS_DEPTH (None: the library's own choice, which this shape leaves no room for), steps per pass the launch reports
+ETA_WINDOW_PINNED = [("k32_eta_in_hbm", "2", 2), ("k32_eta_in_hbm", "4", 4), ("k16_eta_in_hbm", "4", 4),
+                     ("k8_eta_in_hbm", "8", 8), ("k64_eta_in_hbm", None, 2)]
+
+
+@pytest.mark.parametrize("name,depth,pass_steps", ETA_WINDOW_PINNED, ids=["%s-depth%s" % (c, d) for c, d, _ in ETA_WINDOW_PINNED])
+def test_eta_window_in_lds_at_pinned_depths(name, depth, pass_steps, monkeypatch):
+    """Every kind of pass of the windowed kernels (step_pair, step_quad32, step_quad, step_oct, step_pair64 with eta outside the
+    LDS) at a pinned depth, three degrees wide: most steps leave the window for the general step, the rest take the pass.  Under
+    the constant schedule, the cooling one with the early stop in reach and abrupt_cool every launch reports the pinned number of
+    steps per pass, and the chains equal the oracle's."""
+    if depth is None:
+        monkeypatch.delenv("BISBM_PASS_DEPTH", raising=False)
+    else:
+        monkeypatch.setenv("BISBM_PASS_DEPTH", depth)
+    _eta_window_chains_equal_oracle(name, "3", monkeypatch, pass_steps)
+
+
+def _eta_window_chains_equal_oracle(name, window, monkeypatch, pass_steps=None):
     if window is None:
         monkeypatch.delenv("BISBM_ETA_WINDOW", raising=False)
     else:
@@ -164,7 +186,11 @@ def test_eta_window_in_lds(name, window, monkeypatch):
     g.shuffle_bisbm()
     mh = B.MetropolisHasting()
     runs = [("constant", [1.0], 3 * n, BIG), ("exponential", [1.5, 0.9999], 6 * n, n), ("abrupt_cool", [1.5 * n], 3 * n, BIG)]
-    got = [mh.anneal(g, s_, kw, dur, aw).copy() for s_, kw, dur, aw in runs]
+    got = []
+    for s_, kw, dur, aw in runs:
+        got.append(mh.anneal(g, s_, kw, dur, aw).copy())
+        if pass_steps is not None:
+            assert g.last_pass_steps() == pass_steps, (name, s_, g.last_pass_steps())
     for c in range(chains):
         o = O.OracleModel(rowptr, col, na, nb, ka, kb, eps, labels)
         o.seed_philox(31, first + c)
