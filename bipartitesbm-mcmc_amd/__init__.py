@@ -79,6 +79,8 @@ ABI = {
     "bisbm_marginals_set_modes": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
     "bisbm_marginals_get_modes": (C.c_int, [C.c_void_p, _u32p, _u32p, C.POINTER(C.c_int64), _u64p]),
     "bisbm_marginals_set_mode_reference": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
+    "bisbm_marginals_set_mode_anchors": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_double]),
+    "bisbm_marginals_get_mode_assignment": (C.c_int, [C.c_void_p, _f64p, _u64p, _u64p, _u64p]),
     "bisbm_marginals_get_mode_reference": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.POINTER(C.c_int64)]),
     "bisbm_marginals_get_mode": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
     "bisbm_marginals_map_mode": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
@@ -91,6 +93,7 @@ ABI = {
     "bisbm_pair_scores_reset": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_get": (C.c_int, [C.c_void_p, _f64p, _u64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
+    "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
     "bisbm_partition_modes": (C.c_int, [C.c_uint32, _f64p, C.c_double, _u32p, _u32p, _u32p]),
     "bisbm_get_ka_kb": (C.c_int, [C.c_void_p, _u32p, _u32p]),
@@ -581,10 +584,44 @@ class BlockModel:
         moc, n_modes = mode_assignment(mode_of_chain, self.n_chains, n_modes)
         self._check(self._L.bisbm_marginals_set_modes(self._h, n_modes, _p(moc, _u32p)))
 
+    def marginals_set_mode_anchors(self, anchors, threshold):
+        """Anchored modes (include/bisbm.h, "Anchored modes"): one histogram per row of `anchors` [M, n]; at every sample each
+        counted chain goes into the mode of its nearest anchor (VI, ties -> the lowest mode) if that VI is <= `threshold`
+        (float('inf'): always).  Allowed with replica exchange on.  None or an empty array turns the feature off."""
+        if anchors is None or np.size(anchors) == 0:
+            self._check(self._L.bisbm_marginals_set_mode_anchors(self._h, 0, None, 0.0))
+            return
+        a = np.ascontiguousarray(np.atleast_2d(anchors), dtype=np.uint32)
+        if a.ndim != 2 or a.shape[1] != self.n:
+            raise ValueError("anchors must have shape (n_modes, %d), got %s" % (self.n, a.shape))
+        self._check(self._L.bisbm_marginals_set_mode_anchors(self._h, a.shape[0], _p(a, _u32p), float(threshold)))
+
+    def marginals_mode_assignment(self):
+        """Anchored modes, as a dict: `vi` float64 [n_chains, M] of the last sample (NaN rows: chains that were not counted),
+        `visits` uint64 [n_chains, M] (samples of chain c counted into mode g), `unassigned` (counted chains beyond the
+        threshold, over all samples), `samples`."""
+        nm = C.c_uint32()
+        self._check(self._L.bisbm_marginals_get_modes(self._h, C.byref(nm), None, None, None))
+        M = max(nm.value, 1)
+        vi = np.zeros((self.n_chains, M), dtype=np.float64)
+        visits = np.zeros((self.n_chains, M), dtype=np.uint64)
+        un, sm = C.c_uint64(), C.c_uint64()
+        self._check(self._L.bisbm_marginals_get_mode_assignment(self._h, _p(vi, _f64p), _p(visits, _u64p), C.byref(un), C.byref(sm)))
+        return {"vi": vi, "visits": visits, "unassigned": un.value, "samples": sm.value}
+
+    def _anchored_unassigned(self):
+        """`unassigned` while anchors are set, None otherwise."""
+        un = C.c_uint64()
+        if self._L.bisbm_marginals_get_mode_assignment(self._h, None, None, C.byref(un), None) != BISBM_OK:
+            return None
+        return un.value
+
     def marginals_modes(self):
         """What marginals_set_modes set and what the samples made of it, as a dict: `n_modes`, `mode_of_chain` uint32
         [n_chains], `ref_chain` int64 [M] (-1: the caller's reference, -2: none yet), `terms` uint64 [M] (chain samples in
-        every mode's histogram), `weights` [M] (each mode's share of the counted chains).  n_modes = 0: the feature is off."""
+        every mode's histogram), `weights` [M] (each mode's share of the counted chains).  n_modes = 0: the feature is off.
+        While anchors are set (marginals_set_mode_anchors): `mode_of_chain` is the last sample's assignment, there is
+        `unassigned` as well, and `weights` are the sample shares terms / (sum of terms + unassigned)."""
         nm = C.c_uint32()
         self._check(self._L.bisbm_marginals_get_modes(self._h, C.byref(nm), None, None, None))
         M = nm.value
@@ -592,6 +629,11 @@ class BlockModel:
         ref = np.zeros(max(M, 1), dtype=np.int64)
         terms = np.zeros(max(M, 1), dtype=np.uint64)
         self._check(self._L.bisbm_marginals_get_modes(self._h, C.byref(nm), _p(moc, _u32p), _p(ref, C.POINTER(C.c_int64)), _p(terms, _u64p)))
+        un = self._anchored_unassigned() if M else None
+        if un is not None:
+            t = terms[:M].astype(np.float64)
+            return {"n_modes": M, "mode_of_chain": moc, "ref_chain": ref[:M], "terms": terms[:M], "unassigned": un,
+                    "weights": t / max(float(t.sum()) + un, 1.0)}
         size = np.bincount(moc[moc != MODE_NONE].astype(np.int64), minlength=M)[:M]
         return {"n_modes": M, "mode_of_chain": moc, "ref_chain": ref[:M], "terms": terms[:M],
                 "weights": size / max(int(size.sum()), 1)}
@@ -697,6 +739,31 @@ class BlockModel:
         vi = np.zeros((m, m), dtype=np.float64)
         H = np.zeros(m, dtype=np.float64)
         self._check(self._L.bisbm_partition_distances(self._h, m, ptr, _p(vi, _f64p), _p(H, _f64p)))
+        return vi, H
+
+    def partition_distances_to(self, refs, chains=None, shapes=None):
+        """(vi float64 [m, R], H_ref float64 [R]): the variation of information (nats) between every selected chain's partition
+        (None: all chains) and every row of `refs` [R, n], partitions of the same nodes that need not be chains, and each
+        reference's partition entropy.  `shapes`: (ka, kb) for all references or one pair per reference; default: the model's
+        (KA, KB).  Reads labels only."""
+        r = np.ascontiguousarray(np.atleast_2d(refs), dtype=np.uint32)
+        if r.ndim != 2 or r.shape[1] != self.n:
+            raise ValueError("refs must have shape (n_refs, %d), got %s" % (self.n, r.shape))
+        R = r.shape[0]
+        sh = np.asarray((self.KA, self.KB) if shapes is None else shapes, dtype=np.int64)
+        sh = np.broadcast_to(sh, (R, 2)) if sh.ndim == 1 else sh
+        if sh.shape != (R, 2) or (R and (sh.min() < 0 or sh.max() > 0xFFFFFFFF)):
+            raise ValueError("shapes must be one (ka, kb) or one per reference")
+        rka = np.ascontiguousarray(sh[:, 0], dtype=np.uint32)
+        rkb = np.ascontiguousarray(sh[:, 1], dtype=np.uint32)
+        if chains is None:
+            sel, m, ptr = None, self.n_chains, None
+        else:
+            sel = np.ascontiguousarray(chains, dtype=np.uint32).ravel()
+            m, ptr = len(sel), _p(sel, _u32p)
+        vi = np.zeros((m, R), dtype=np.float64)
+        H = np.zeros(R, dtype=np.float64)
+        self._check(self._L.bisbm_partition_distances_to(self._h, m, ptr, R, _p(r, _u32p), _p(rka, _u32p), _p(rkb, _u32p), _p(vi, _f64p), _p(H, _f64p)))
         return vi, H
 
     def partition_contingency(self, c, d):

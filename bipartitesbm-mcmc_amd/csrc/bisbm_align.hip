@@ -178,7 +178,7 @@ __global__ __launch_bounds__(64) void align_assign_kernel(AssignParams p) {
 // list positions range[g] .. range[g + 1] - 1, through their permutations into slice g of the histogram.  IN_LDS: one row of
 // (kmax | 1) counters per thread (the odd stride puts the 64 rows of a wave on 64 different banks), then the permutation rows of
 // kPermChunk list positions; otherwise the thread owns row v of slice g and counts straight into it.  COLD_ONLY (replica exchange:
-// the pooled sample only, whose list is the identity): position y is chain y, counted while it is on rung 0.  The test is a
+// the pooled sample only, whose list is the identity; AlignPlan::cold_only): position y is chain y, counted while it is on rung 0.  The test is a
 // template flag because a branch in the loop over the chains keeps the compiler from batching the label loads of four chains,
 // which is worth a third of the kernel's time where nothing is filtered.
 // ------------------------------------------------------------------------------------------
@@ -410,7 +410,7 @@ int aligned_sample(bisbm_engine* e, AlignScratch& s, const AlignPlan& plan, uint
     cp.range = s.d_range.get();
     cp.perm = s.d_perm.get();
     cp.counts = counts;
-    if (e->temper.L) {  // replica exchange: the cold chains only (modes are refused then: the list is the identity)
+    if (plan.cold_only) {  // replica exchange, pooled: the list is the identity, the kernel counts the cold chains only
         cp.rung = e->temper.d_rung.get();
         HIPCHK(e, launch_marginals_aligned<true>(cp, M, e->stream));
     } else {
@@ -487,6 +487,7 @@ int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     AlignPlan plan;
     plan.refs = &a.ref;
     plan.ref_serial = a.serial;
+    plan.cold_only = h->temper.L != 0;
     return each_leaf(h, [&](bisbm_engine* e) { return aligned_sample(e, e->align.scratch, plan, 0, device_counts ? device_counts : (e->root ? e->root : e)->d_counts); });
 }
 

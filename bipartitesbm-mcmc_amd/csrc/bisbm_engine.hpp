@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <future>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -189,6 +190,7 @@ struct PartitionState {
     DeviceBuf<double> d_snn;      // [selection][selection] sum_rs n_rs ln n_rs of every pair i < j
     DeviceBuf<uint32_t> d_tab;    // few pairs: the integer tables of one launch
     DeviceBuf<uint8_t> d_stage;   // label rows of selected chains that live on another device
+    DeviceBuf<uint8_t> d_refs;    // distances_to: the caller's reference partitions as byte rows, padded like label rows
 };
 
 // Mode-resolved marginals (bisbm_mode_marginals.hip).  The assignment of chains to modes, the references and `terms` belong to
@@ -201,7 +203,15 @@ struct ModeState {
     std::vector<uint64_t> terms;     // [n_modes] chain samples in every mode's histogram
     uint64_t list_serial = 0;        // bumped whenever the assignment changes
     uint64_t ref_serial = 0;         // bumped whenever a reference changes
+    // anchored modes (bisbm_marginals_set_mode_anchors): refs are the anchors, of_chain is the last sample's assignment
+    bool anchored = false;
+    double threshold = 0;            // a chain farther than this from its nearest anchor is not counted
+    std::vector<double> vi_last;     // [n_chains][n_modes] VI of the last sample, NaN rows: chains that were not counted
+    std::vector<uint64_t> visits;    // [n_chains][n_modes] samples of chain c counted into mode g
+    uint64_t unassigned = 0, samples = 0;
+    uint64_t pending_unassigned = 0; // counted chains of the sample under way that are beyond the threshold
     // kernel-running engine
+    DeviceBuf<uint8_t> d_anchor;     // [n_modes][label_stride] the anchors as byte rows (anchored modes only)
     AlignScratch scratch;            // (its own, not AlignState's: a pooled sample's permutations are not a mode's)
     DeviceBuf<uint32_t> d_counts;    // [slices][n][max(hist_ka, hist_kb)] one histogram per mode
     uint32_t slices = 0, hist_ka = 0, hist_kb = 0;  // what d_counts holds (slices 0: nothing)
@@ -497,10 +507,12 @@ struct AlignPlan {
     const uint32_t* of_chain = nullptr;  // [chains of the handle] mode of every chain, BISBM_MODE_NONE: not counted; NULL: all in mode 0
     const AlignRef* refs = nullptr;      // [n_modes]
     uint64_t list_serial = 0, ref_serial = 0;  // move with of_chain / with a reference
+    bool cold_only = false;  // the list is the identity and the counting kernel skips the chains off rung 0 (pooled plan under
+                             // replica exchange; an anchored plan lists the cold chains itself)
 };
 // One aligned sample of the chains of kernel-running engine e (chains first .. of the handle) into counts[mode][n][kmax]: the
-// three steps over e's list of counted chains.  With replica exchange on only the cold chains are counted; that goes with the
-// pooled plan alone (modes refuse replica exchange): the counting kernel then takes list position y for chain y.
+// three steps over e's list of counted chains.  plan.cold_only: the counting kernel takes list position y for chain y and
+// counts it while it is on rung 0.
 int aligned_sample(bisbm_engine* e, AlignScratch& s, const AlignPlan& plan, uint32_t first, uint32_t* counts);
 // BISBM_ERR_UNSUPPORTED while some leaf holds two-byte labels
 int refuse_wide_labels(bisbm_engine* h, uint32_t ka, uint32_t kb);
@@ -525,6 +537,10 @@ int read_alignment(bisbm_engine* h, bisbm_engine* e, const AlignScratch& s, uint
 int mode_accumulate(bisbm_engine* h, uint32_t* device_counts);  // bisbm_marginals_accumulate while modes are set
 int mode_reset(bisbm_engine* h);                                // ... bisbm_marginals_reset
 int mode_get_alignment(bisbm_engine* h, uint32_t chain, uint32_t* perm_out, uint64_t* overlap_out);  // ... bisbm_marginals_get_alignment
+// VI[i][g] of chain chains[i] (index in kernel-running engine e) with row g of d_refs (n_refs byte rows of ref_stride bytes on
+// e's device, of e's shape) into vi[chains.size() * n_refs]: the kernels and the arithmetic of bisbm_partition_distances_to, on
+// e's stream with e's scratch; bisbm_partition.hip
+int partition_distances_rows(bisbm_engine* e, const std::vector<uint32_t>& chains, const uint8_t* d_refs, size_t ref_stride, uint32_t n_refs, double* vi);
 // BISBM_ERR_STATE with a message that names the per-mode call while modes are set, BISBM_OK otherwise
 int refuse_while_modes(bisbm_engine* h, const char* call, const char* per_mode_call);
 

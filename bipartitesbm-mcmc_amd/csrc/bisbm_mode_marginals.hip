@@ -1,8 +1,11 @@
 // bisbm_mode_marginals.hip -- mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): one aligned histogram per
 // posterior mode, each mode aligned to a reference of its own.  The caller assigns chains to modes (bisbm_marginals_set_modes,
 // e.g. from bisbm_partition_modes); a sample is one run of the aligned-sample pipeline of bisbm_align.hip over the counted
-// chains, with every mode's reference and into every mode's slice of the histogram.  This unit holds the host side only: the
-// assignment, the references, the slices and their part of the C ABI.
+// chains, with every mode's reference and into every mode's slice of the histogram.  Anchored modes
+// (bisbm_marginals_set_mode_anchors) take the assignment afresh at every sample: the counted chains' VI to one anchor partition
+// per mode (partition_distances_rows, the kernels of bisbm_partition.hip), the nearest anchor within the threshold on the host,
+// then the same pipeline with the anchors as references.  This unit holds the host side only: the assignment, the references,
+// the slices and their part of the C ABI.
 #include "bisbm_engine.hpp"
 
 using namespace bisbm;
@@ -22,6 +25,56 @@ bool histograms_fit(bisbm_engine* h, uint32_t ka, uint32_t kb) {
     for (bisbm_engine* d : device_entries(h))
         if (!d->modes.d_counts || d->modes.hist_ka != ka || d->modes.hist_kb != kb || d->modes.slices != h->modes.n_modes) return false;
     return true;
+}
+
+// Anchored modes, the assignment of one sample: the counted chains (all; under replica exchange those on rung 0 now) get the
+// mode of their nearest anchor (ties -> the lowest mode) if it is within the threshold.  Every device entry measures its own
+// chains against its copy of the anchors; the decision is taken here from the copied matrix.
+int assign_to_anchors(bisbm_engine* h) {
+    ModeState& m = h->modes;
+    const uint32_t M = m.n_modes, C = h->n_chains;
+    std::vector<uint32_t> rung(C, 0);
+    if (h->temper.L)
+        if (int rc = bisbm_tempering_get(h, rung.data(), nullptr)) return rc;
+    m.vi_last.assign((size_t)C * M, std::numeric_limits<double>::quiet_NaN());
+    auto measure = [&](bisbm_engine* d, size_t i) {
+        const uint32_t first = h->devs.empty() ? 0u : h->dev_first[i];
+        std::vector<uint32_t> cold;
+        for (uint32_t c = 0; c < d->n_chains; ++c)
+            if (rung[first + c] == 0u) cold.push_back(c);
+        std::vector<double> vi(cold.size() * M);
+        if (int rc = partition_distances_rows(d, cold, d->modes.d_anchor.get(), d->label_stride, M, vi.data())) return rc;
+        for (size_t y = 0; y < cold.size(); ++y) std::copy(vi.begin() + y * M, vi.begin() + (y + 1) * M, m.vi_last.begin() + (size_t)(first + cold[y]) * M);
+        return (int)BISBM_OK;
+    };
+    DeviceGuard keep;
+    if (int rc = h->devs.empty() ? measure(h, 0) : on_devices(h, measure)) return rc;
+    m.pending_unassigned = 0;
+    for (uint32_t c = 0; c < C; ++c) {
+        m.of_chain[c] = kNone;
+        if (rung[c] != 0u) continue;
+        const double* v = m.vi_last.data() + (size_t)c * M;
+        uint32_t best = 0;
+        for (uint32_t g = 1; g < M; ++g)
+            if (v[g] < v[best]) best = g;
+        if (v[best] <= m.threshold)
+            m.of_chain[c] = best;
+        else
+            m.pending_unassigned += 1;
+    }
+    ++m.list_serial;  // (the list of counted chains is this sample's)
+    return BISBM_OK;
+}
+
+// the modes are off again: the histograms, the anchors and the scratch go back
+void drop_mode_buffers(bisbm_engine* h, bool off) {
+    for (bisbm_engine* d : device_entries(h)) {
+        d->modes.slices = 0;
+        d->modes.scratch.have_perm = false;
+        d->modes.d_counts.reset();
+        d->modes.d_anchor.reset();
+        if (off) d->modes = ModeState();
+    }
 }
 
 }  // namespace
@@ -52,6 +105,8 @@ int mode_reset(bisbm_engine* h) {
         s.scratch.have_perm = false;
     }
     std::fill(m.terms.begin(), m.terms.end(), 0);
+    std::fill(m.visits.begin(), m.visits.end(), 0);
+    m.unassigned = m.samples = 0;
     for (AlignRef& r : m.refs)
         if (r.has && r.chain >= 0) r.has = false;  // (a caller's reference stays)
     return BISBM_OK;
@@ -73,6 +128,9 @@ int mode_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     for (uint32_t g = 0; g < m.n_modes; ++g) {
         AlignRef& r = m.refs[g];
         if (r.has && (r.ka != ka || r.kb != kb)) {
+            if (m.anchored)
+                return fail(h, BISBM_ERR_STATE, "the anchor of mode %u was set for %u + %u blocks, the chains now have %u + %u: set the anchors again", g, r.ka,
+                            r.kb, ka, kb);
             if (r.chain < 0)
                 return fail(h, BISBM_ERR_STATE, "the reference partition of mode %u was set for %u + %u blocks, the chains now have %u + %u: set it again", g,
                             r.ka, r.kb, ka, kb);
@@ -88,6 +146,8 @@ int mode_accumulate(bisbm_engine* h, uint32_t* device_counts) {
             ++m.ref_serial;
         }
     }
+    if (m.anchored)
+        if (int rc = assign_to_anchors(h)) return rc;
     AlignPlan plan;
     plan.n_modes = m.n_modes;
     plan.of_chain = m.of_chain.data();
@@ -98,7 +158,14 @@ int mode_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     const int rc = h->devs.empty() ? sample(h, 0) : on_devices(h, sample);
     if (rc) return rc;
     for (uint32_t c = 0; c < h->n_chains; ++c)
-        if (m.of_chain[c] != kNone) m.terms[m.of_chain[c]] += 1;
+        if (m.of_chain[c] != kNone) {
+            m.terms[m.of_chain[c]] += 1;
+            if (m.anchored) m.visits[(size_t)c * m.n_modes + m.of_chain[c]] += 1;
+        }
+    if (m.anchored) {
+        m.unassigned += m.pending_unassigned;
+        m.samples += 1;
+    }
     return BISBM_OK;
 }
 
@@ -143,14 +210,85 @@ int bisbm_marginals_set_modes(bisbm_handle h, uint32_t n_modes, const uint32_t* 
     m.of_chain.assign(mode_of_chain, mode_of_chain + (n_modes ? h->n_chains : 0));
     m.refs.assign(n_modes, AlignRef());
     m.terms.assign(n_modes, 0);
+    m.anchored = false, m.threshold = 0, m.unassigned = m.samples = 0;
+    m.vi_last.clear(), m.visits.clear();
     ++m.list_serial, ++m.ref_serial;
-    for (bisbm_engine* d : device_entries(h)) {  // (histograms of another assignment are gone; off: the memory goes back)
-        d->modes.slices = 0;
-        d->modes.scratch.have_perm = false;
-        d->modes.d_counts.reset();
-        if (!n_modes) d->modes = ModeState();
-    }
+    drop_mode_buffers(h, !n_modes);  // (histograms of another assignment are gone; off: the memory goes back)
     if (!n_modes) m = ModeState();
+    return BISBM_OK;
+}
+
+int bisbm_marginals_set_mode_anchors(bisbm_handle h, uint32_t n_modes, const uint32_t* anchor_labels, double threshold) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    ModeState& m = h->modes;
+    if (!n_modes) {
+        if (m.n_modes && h->align.samples)
+            return fail(h, BISBM_ERR_STATE, "the marginal histogram holds samples counted under the present assignment: bisbm_marginals_reset first");
+        if (m.n_modes) {
+            drop_mode_buffers(h, true);
+            m = ModeState();
+        }
+        return BISBM_OK;
+    }
+    if (!anchor_labels) return fail(h, BISBM_ERR_INVALID_ARG, "anchor_labels is NULL");
+    if (n_modes == BISBM_MODE_NONE) return fail(h, BISBM_ERR_INVALID_ARG, "n_modes = %u is the value of BISBM_MODE_NONE", n_modes);
+    if (!(threshold >= 0.)) return fail(h, BISBM_ERR_INVALID_ARG, "the threshold must be a number >= 0 (+inf: always the nearest anchor), got %g", threshold);
+    if (h->align.samples)
+        return fail(h, BISBM_ERR_STATE, "the marginal histogram holds samples counted under the present assignment: bisbm_marginals_reset first");
+    if (any_grouped(h))
+        return fail(h, BISBM_ERR_STATE, "the chains of this handle are grouped by shape (after bisbm_agg_merge_total): no mode-resolved marginals");
+    uint32_t ka = 0, kb = 0;
+    if (int rc = shared_shape(h, &ka, &kb)) return rc;
+    for (uint32_t g = 0; g < n_modes; ++g)
+        if (int rc = check_reference_labels(h, anchor_labels + (size_t)g * h->n, ka, kb)) {
+            h->err = "anchor " + std::to_string(g) + ": " + h->err;
+            return rc;
+        }
+    try {
+        // a wide handle's labels do not fit the byte rows: it keeps the anchors on the host and is refused at the sample
+        const bool bytes = !any_wide(h);
+        DeviceGuard keep;
+        for (bisbm_engine* d : device_entries(h)) {
+            d->modes.slices = 0;
+            d->modes.scratch.have_perm = false;
+            d->modes.d_counts.reset();
+            if (!bytes) continue;
+            // (rows padded with zeroes like label rows: the distance kernels load words past n)
+            std::vector<uint8_t> rows((size_t)n_modes * d->label_stride, 0);
+            for (uint32_t g = 0; g < n_modes; ++g)
+                for (uint64_t v = 0; v < h->n; ++v) rows[(size_t)g * d->label_stride + v] = (uint8_t)anchor_labels[(size_t)g * h->n + v];
+            HIPCHK(h, hipSetDevice(d->device));
+            RESERVE(h, d->modes.d_anchor, rows.size());
+            HIPCHK(h, hipMemcpy(d->modes.d_anchor.get(), rows.data(), rows.size(), hipMemcpyHostToDevice));
+        }
+        m.n_modes = n_modes;
+        m.of_chain.assign(h->n_chains, kNone);
+        m.refs.assign(n_modes, AlignRef());
+        for (uint32_t g = 0; g < n_modes; ++g) {
+            AlignRef& r = m.refs[g];
+            r.labels.assign(anchor_labels + (size_t)g * h->n, anchor_labels + (size_t)(g + 1) * h->n);
+            r.has = true, r.chain = -1, r.ka = ka, r.kb = kb;
+        }
+        m.terms.assign(n_modes, 0);
+        m.anchored = true, m.threshold = threshold;
+        m.vi_last.assign((size_t)h->n_chains * n_modes, std::numeric_limits<double>::quiet_NaN());
+        m.visits.assign((size_t)h->n_chains * n_modes, 0);
+        m.unassigned = m.samples = 0;
+        ++m.list_serial, ++m.ref_serial;
+    } catch (const std::bad_alloc&) {
+        return fail(h, BISBM_ERR_STATE, "out of host memory");
+    }
+    return BISBM_OK;
+}
+
+int bisbm_marginals_get_mode_assignment(bisbm_handle h, double* vi_out, uint64_t* visits_out, uint64_t* unassigned_out, uint64_t* samples_out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    const ModeState& m = h->modes;
+    if (!m.anchored) return fail(h, BISBM_ERR_STATE, "no mode anchors are set: bisbm_marginals_set_mode_anchors first");
+    if (vi_out) std::copy(m.vi_last.begin(), m.vi_last.end(), vi_out);
+    if (visits_out) std::copy(m.visits.begin(), m.visits.end(), visits_out);
+    if (unassigned_out) *unassigned_out = m.unassigned;
+    if (samples_out) *samples_out = m.samples;
     return BISBM_OK;
 }
 
@@ -170,6 +308,8 @@ int bisbm_marginals_get_modes(bisbm_handle h, uint32_t* n_modes, uint32_t* mode_
 int bisbm_marginals_set_mode_reference(bisbm_handle h, uint32_t mode, const uint32_t* labels) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (int rc = check_mode(h, mode)) return rc;
+    if (h->modes.anchored)
+        return fail(h, BISBM_ERR_STATE, "mode anchors are set: every mode is aligned to its anchor (bisbm_marginals_set_mode_anchors sets them)");
     AlignRef& r = h->modes.refs[mode];
     if (!labels) {
         r.has = false;

@@ -12,6 +12,11 @@
 //   few pairs: the nodes are split over workgroups, the tables are added into HBM and partition_reduce_kernel reduces them
 //     (bisbm_partition_contingency copies one such table out instead); a table too large for LDS is counted straight in HBM.
 // Both reduce with wave_xlnx: one wave per table, lane-strided, butterfly -- the same bits from the same integers.
+// Chains against reference partitions that are no chains (bisbm_partition_distances_to, and the anchored modes of
+// bisbm_mode_marginals.hip through partition_distances_rows) run the same kernels in their RECT form: the tile is T selected
+// chains (rows) x T references (columns, byte rows of their own shapes), every pair (row < m, column < mc) is live instead of
+// i < j, and a slot's `stride` is kaM_chain * kaM_ref + kbM_chain * kbM_ref, the largest shape of either side taken separately.
+// B_g = sum_s b_s ln b_s of a reference is partition_sizes_kernel over the reference rows.
 // The chains' state is only read.
 #include "bisbm_engine.hpp"
 
@@ -25,12 +30,19 @@ struct ChainDesc {
 };
 
 struct CountParams {
-    const ChainDesc* chains;  // [m]
-    const uint2* tiles;       // [tiles of the launch] (row tile, column tile), row <= column
-    uint32_t m, n, na, stride, nodes_per_block, hbm_direct;
+    const ChainDesc* chains;  // [m] the row partitions
+    const ChainDesc* cols;    // [mc] the column partitions: `chains` again, or (RECT) the references
+    const uint2* tiles;       // [tiles of the launch] (row tile, column tile); square: row <= column
+    uint32_t m, mc, n, na, stride, nodes_per_block, hbm_direct;
     uint32_t* tab;  // few pairs: [tile of the launch][T * T][stride]
-    double* snn;    // [m][m], entry (i, j) of every pair i < j
+    double* snn;    // [m][mc], entry (i, j) of every live pair
 };
+
+// is (row i, column j) a pair of the call?  Square: each unordered pair once; RECT: every chain with every reference
+template <bool RECT>
+__device__ __forceinline__ bool pair_live(const CountParams& p, uint32_t i, uint32_t j) {
+    return RECT ? i < p.m && j < p.mc : i < j && j < p.m;
+}
 
 constexpr uint32_t kNone = 0xffffffffu;
 
@@ -64,7 +76,7 @@ __device__ __forceinline__ void count_cell(uint32_t* t, uint32_t idx, uint32_t l
 
 // the node loop of partition_count_kernel: counts the nodes [v0, v1) of the tile's pairs into tabs (LDS, or HBM for tables too
 // large for it: a function, so that each call site keeps its pointer's address space and the LDS one gets LDS atomics)
-template <int T>
+template <int T, bool RECT>
 __device__ __forceinline__ void count_tile(uint32_t* tabs, const ChainDesc* ch, const CountParams& p, uint32_t i0, uint32_t j0) {
     const uint8_t *rowr[T], *rowc[T];
     uint32_t kar[T], kbr[T], kac[T], kbc[T];
@@ -97,7 +109,7 @@ __device__ __forceinline__ void count_tile(uint32_t* tabs, const ChainDesc* ch, 
             for (int a = 0; a < T; ++a) {
 #pragma unroll
                 for (int b = 0; b < T; ++b) {
-                    if (!(i0 + a < j0 + b && j0 + b < p.m)) continue;  // (the same for every lane)
+                    if (!pair_live<RECT>(p, i0 + a, j0 + b)) continue;  // (the same for every lane)
                     const uint32_t r = ((Lr[a] >> (8 * j)) & 0xffu) - (tb ? kar[a] : 0u), kr = tb ? kbr[a] : kar[a];
                     const uint32_t s = ((Lc[b] >> (8 * j)) & 0xffu) - (tb ? kac[b] : 0u), ks = tb ? kbc[b] : kac[b];
                     const uint32_t idx = live && r < kr && s < ks ? (uint32_t)(a * T + b) * p.stride + (tb ? kar[a] * kac[b] : 0u) + r * ks + s : kNone;
@@ -108,7 +120,7 @@ __device__ __forceinline__ void count_tile(uint32_t* tabs, const ChainDesc* ch, 
     }
 }
 
-template <int T, bool FUSED>
+template <int T, bool FUSED, bool RECT>
 __global__ __launch_bounds__(1024) void partition_count_kernel(CountParams p) {
     extern __shared__ __align__(16) uint32_t lds_tab[];  // [T * T][stride] unless hbm_direct
     __shared__ ChainDesc ch[2 * T];                      // the tile's row chains, then its column chains
@@ -116,30 +128,32 @@ __global__ __launch_bounds__(1024) void partition_count_kernel(CountParams p) {
     const uint32_t i0 = tile.x * T, j0 = tile.y * T;
     const bool direct = !FUSED && T == 1 && p.hbm_direct;
     if (threadIdx.x < 2 * T) {
-        const uint32_t idx = threadIdx.x < T ? i0 + threadIdx.x : j0 + threadIdx.x - T;
-        const bool have = idx < p.m;  // (past the selection: a chain without a row, in no pair)
-        ch[threadIdx.x].row = have ? p.chains[idx].row : nullptr;
-        ch[threadIdx.x].ka = have ? p.chains[idx].ka : 0u;
-        ch[threadIdx.x].kb = have ? p.chains[idx].kb : 0u;
+        const bool is_row = threadIdx.x < T;
+        const uint32_t idx = is_row ? i0 + threadIdx.x : j0 + threadIdx.x - T;
+        const ChainDesc* from = is_row ? p.chains : p.cols;
+        const bool have = idx < (is_row ? p.m : p.mc);  // (past the selection: a partition without a row, in no pair)
+        ch[threadIdx.x].row = have ? from[idx].row : nullptr;
+        ch[threadIdx.x].ka = have ? from[idx].ka : 0u;
+        ch[threadIdx.x].kb = have ? from[idx].kb : 0u;
     }
     uint32_t* const out = FUSED ? nullptr : p.tab + (size_t)blockIdx.x * (T * T) * p.stride;
     if (!direct)
         for (uint32_t i = threadIdx.x; i < T * T * p.stride; i += blockDim.x) lds_tab[i] = 0;
     __syncthreads();
     if (direct)
-        count_tile<T>(out, ch, p, i0, j0);
+        count_tile<T, RECT>(out, ch, p, i0, j0);
     else
-        count_tile<T>(lds_tab, ch, p, i0, j0);
+        count_tile<T, RECT>(lds_tab, ch, p, i0, j0);
     if (direct) return;
     __syncthreads();
     if constexpr (FUSED) {
         const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x / 64u, waves = blockDim.x / 64u;
         for (uint32_t q = wave; q < T * T; q += waves) {
             const uint32_t a = q / T, b = q % T, gi = i0 + a, gj = j0 + b;
-            if (!(gi < gj && gj < p.m)) continue;
+            if (!pair_live<RECT>(p, gi, gj)) continue;
             const uint32_t cells = ch[a].ka * ch[T + b].ka + ch[a].kb * ch[T + b].kb;
             const double s = wave_xlnx(lds_tab + q * p.stride, cells, lane);
-            if (lane == 0) p.snn[(size_t)gi * p.m + gj] = s;
+            if (lane == 0) p.snn[(size_t)gi * p.mc + gj] = s;
         }
     } else {
         for (uint32_t i = threadIdx.x; i < T * T * p.stride; i += blockDim.x) {
@@ -150,13 +164,14 @@ __global__ __launch_bounds__(1024) void partition_count_kernel(CountParams p) {
 }
 
 // few pairs: one wave per pair slot of the launch's tiles reduces its HBM table
+template <bool RECT>
 __global__ __launch_bounds__(64) void partition_reduce_kernel(CountParams p, uint32_t T) {
     const uint2 tile = p.tiles[blockIdx.x];
     const uint32_t q = blockIdx.y, gi = tile.x * T + q / T, gj = tile.y * T + q % T;
-    if (!(gi < gj && gj < p.m)) return;
-    const ChainDesc c = p.chains[gi], d = p.chains[gj];
+    if (!pair_live<RECT>(p, gi, gj)) return;
+    const ChainDesc c = p.chains[gi], d = p.cols[gj];
     const double s = wave_xlnx(p.tab + ((size_t)blockIdx.x * (T * T) + q) * p.stride, c.ka * d.ka + c.kb * d.kb, threadIdx.x);
-    if (threadIdx.x == 0) p.snn[(size_t)gi * p.m + gj] = s;
+    if (threadIdx.x == 0) p.snn[(size_t)gi * p.mc + gj] = s;
 }
 
 // A_c = sum_r a_r ln a_r of every selected chain: one workgroup per chain counts the label bytes into a table per wave (256
@@ -192,20 +207,20 @@ __global__ __launch_bounds__(1024) void partition_sizes_kernel(const ChainDesc* 
 constexpr size_t kLdsTables = kLdsPerCu - 1024;  // dynamic LDS a workgroup may take for its tables (ch[] is static)
 constexpr size_t kTabScratch = 256u << 20;       // few pairs: HBM tables of one launch (at least one tile's)
 
-template <int T, bool FUSED>
+template <int T, bool FUSED, bool RECT>
 hipError_t launch_count_t(dim3 grid, uint32_t threads, size_t lds, hipStream_t stream, const CountParams& p) {
-    hipError_t e = hipFuncSetAttribute((const void*)partition_count_kernel<T, FUSED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)partition_count_kernel<T, FUSED, RECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((partition_count_kernel<T, FUSED>), grid, dim3(threads), lds, stream, p);
+    hipLaunchKernelGGL((partition_count_kernel<T, FUSED, RECT>), grid, dim3(threads), lds, stream, p);
     return hipGetLastError();
 }
 
-template <bool FUSED>
+template <bool FUSED, bool RECT>
 hipError_t launch_count(uint32_t T, dim3 grid, uint32_t threads, size_t lds, hipStream_t stream, const CountParams& p) {
     switch (T) {
-        case 4: return launch_count_t<4, FUSED>(grid, threads, lds, stream, p);
-        case 2: return launch_count_t<2, FUSED>(grid, threads, lds, stream, p);
-        default: return launch_count_t<1, FUSED>(grid, threads, lds, stream, p);
+        case 4: return launch_count_t<4, FUSED, RECT>(grid, threads, lds, stream, p);
+        case 2: return launch_count_t<2, FUSED, RECT>(grid, threads, lds, stream, p);
+        default: return launch_count_t<1, FUSED, RECT>(grid, threads, lds, stream, p);
     }
 }
 
@@ -264,36 +279,57 @@ int describe(bisbm_engine* h, const char* call, const std::vector<uint32_t>& sel
             desc[away[k].first].row = dst;
         }
     }
-    RESERVE(h, s.d_desc, sizeof(ChainDesc) * desc.size());
-    HIPCHK(h, hipMemcpyAsync(s.d_desc.get(), desc.data(), sizeof(ChainDesc) * desc.size(), hipMemcpyHostToDevice, ce->stream));
     return BISBM_OK;
+}
+
+// the descriptors of a call onto the computing engine ce: the row partitions, then (distances_to) the references
+int upload_desc(bisbm_engine* h, bisbm_engine* ce, const std::vector<ChainDesc>& rows, const std::vector<ChainDesc>* refs) {
+    PartitionState& s = ce->partition;
+    const size_t m = rows.size(), r = refs ? refs->size() : 0;
+    RESERVE(h, s.d_desc, sizeof(ChainDesc) * (m + r));
+    HIPCHK(h, hipMemcpyAsync(s.d_desc.get(), rows.data(), sizeof(ChainDesc) * m, hipMemcpyHostToDevice, ce->stream));
+    if (r) HIPCHK(h, hipMemcpyAsync(s.d_desc.get() + sizeof(ChainDesc) * m, refs->data(), sizeof(ChainDesc) * r, hipMemcpyHostToDevice, ce->stream));
+    return BISBM_OK;
+}
+
+hipError_t launch_count_any(bool fused, bool rect, uint32_t T, dim3 grid, uint32_t threads, size_t lds, hipStream_t stream, const CountParams& p) {
+    if (fused) return rect ? launch_count<true, true>(T, grid, threads, lds, stream, p) : launch_count<true, false>(T, grid, threads, lds, stream, p);
+    return rect ? launch_count<false, true>(T, grid, threads, lds, stream, p) : launch_count<false, false>(T, grid, threads, lds, stream, p);
 }
 
 enum Regime { kAuto = 0, kFused = 1, kSplit = 2 };
 
 // S_cd of every pair i < j of the described chains into snn[m * m] (host), or -- table_out given, m = 2 -- the integer table
-// of the pair (0, 1) in the kernel's layout
-int run_pairs(bisbm_engine* h, const std::vector<ChainDesc>& desc, double* snn, std::vector<uint32_t>* table_out) {
-    bisbm_engine* ce = computing_engine(h);
+// of the pair (0, 1) in the kernel's layout; refs given (the descriptors behind the chains' on ce): S of every chain with every
+// reference into snn[m * refs]
+int run_pairs(bisbm_engine* h, bisbm_engine* ce, const std::vector<ChainDesc>& desc, const std::vector<ChainDesc>* refs, double* snn,
+              std::vector<uint32_t>* table_out) {
     PartitionState& s = ce->partition;
-    const uint32_t m = (uint32_t)desc.size();
-    uint32_t kaM = 0, kbM = 0;
+    const bool rect = refs != nullptr;
+    const uint32_t m = (uint32_t)desc.size(), mc = rect ? (uint32_t)refs->size() : m;
+    // (a slot holds the largest table of the call: the largest row shape with the largest column shape, each on its own)
+    uint32_t kaM = 0, kbM = 0, kaC = 0, kbC = 0;
     for (const ChainDesc& d : desc) kaM = std::max(kaM, d.ka), kbM = std::max(kbM, d.kb);
-    const uint32_t stride = kaM * kaM + kbM * kbM;
+    for (const ChainDesc& d : rect ? *refs : desc) kaC = std::max(kaC, d.ka), kbC = std::max(kbC, d.kb);
+    const uint32_t stride = kaM * kaC + kbM * kbC;
     const size_t pair_bytes = sizeof(uint32_t) * (size_t)stride;
     const bool direct = pair_bytes > kLdsTables;
     uint32_t T = 1;
     if (!table_out) {
         if (16 * pair_bytes <= kLdsTables) T = 4;
         else if (4 * pair_bytes <= kLdsTables) T = 2;
-        while (T > 1 && T >= m) T /= 2;
+        // (no tile wider than the call: square tiles pair i < j, so T < m; rectangular ones only need T / 2 < max(m, refs))
+        while (T > 1 && (rect ? T / 2 >= std::max(m, mc) : T >= m)) T /= 2;
     }
     std::vector<uint2> tiles;
-    const uint32_t nT = (m + T - 1) / T;
+    const uint32_t nT = (m + T - 1) / T, nTc = (mc + T - 1) / T;
     for (uint32_t ti = 0; ti < nT; ++ti)
-        for (uint32_t tj = ti; tj < nT; ++tj)
-            if (ti != tj || (T > 1 && m - ti * T >= 2)) tiles.push_back(make_uint2(ti, tj));
-    if (tiles.empty()) return BISBM_OK;
+        for (uint32_t tj = rect ? 0 : ti; tj < nTc; ++tj)
+            if (rect || ti != tj || (T > 1 && m - ti * T >= 2)) tiles.push_back(make_uint2(ti, tj));
+    if (tiles.empty() || !stride) {
+        if (snn) std::fill(snn, snn + (size_t)m * mc, 0.);
+        return BISBM_OK;
+    }
     int regime = kAuto;
     if (const char* e = std::getenv("BISBM_PARTITION_REGIME")) regime = !strcmp(e, "fused") ? kFused : !strcmp(e, "split") ? kSplit : kAuto;
     int cus = 0;
@@ -301,11 +337,13 @@ int run_pairs(bisbm_engine* h, const std::vector<ChainDesc>& desc, double* snn, 
     // many pairs: a tile per workgroup fills the compute units; few pairs: the nodes are split as well
     const bool fused = !table_out && !direct && (regime == kFused || (regime == kAuto && tiles.size() >= (size_t)cus));
     RESERVE(h, s.d_tiles, tiles.size());
-    RESERVE(h, s.d_snn, (size_t)m * m);
+    RESERVE(h, s.d_snn, (size_t)m * mc);
     HIPCHK(h, hipMemcpyAsync(s.d_tiles.get(), tiles.data(), sizeof(uint2) * tiles.size(), hipMemcpyHostToDevice, ce->stream));
     CountParams p{};
     p.chains = (const ChainDesc*)s.d_desc.get();
+    p.cols = rect ? p.chains + m : p.chains;
     p.m = m;
+    p.mc = mc;
     p.n = (uint32_t)h->n;
     p.na = (uint32_t)h->na;
     p.stride = stride;
@@ -316,7 +354,7 @@ int run_pairs(bisbm_engine* h, const std::vector<ChainDesc>& desc, double* snn, 
     if (fused) {
         p.tiles = s.d_tiles.get();
         p.nodes_per_block = (p.n + 1023u) & ~1023u;
-        HIPCHK(h, launch_count<true>(T, dim3((uint32_t)tiles.size(), 1), threads, lds, ce->stream, p));
+        HIPCHK(h, launch_count_any(true, rect, T, dim3((uint32_t)tiles.size(), 1), threads, lds, ce->stream, p));
     } else {
         const size_t tile_bytes = (size_t)T * T * pair_bytes;
         const size_t per = std::max<size_t>(1, std::min<size_t>(tiles.size(), kTabScratch / tile_bytes));
@@ -331,23 +369,26 @@ int run_pairs(bisbm_engine* h, const std::vector<ChainDesc>& desc, double* snn, 
             const uint32_t chunks = std::max(1u, std::min(max_chunks, (want + nb - 1) / nb));
             p.nodes_per_block = (((p.n + chunks - 1) / chunks) + 1023u) & ~1023u;
             HIPCHK(h, hipMemsetAsync(s.d_tab.get(), 0, (size_t)nb * tile_bytes, ce->stream));
-            HIPCHK(h, launch_count<false>(T, dim3(nb, (p.n + p.nodes_per_block - 1) / p.nodes_per_block), threads, lds, ce->stream, p));
+            HIPCHK(h, launch_count_any(false, rect, T, dim3(nb, (p.n + p.nodes_per_block - 1) / p.nodes_per_block), threads, lds, ce->stream, p));
             if (table_out) {
                 table_out->resize(stride);
                 HIPCHK(h, hipMemcpyAsync(table_out->data(), s.d_tab.get(), pair_bytes, hipMemcpyDeviceToHost, ce->stream));
             } else {
-                hipLaunchKernelGGL(partition_reduce_kernel, dim3(nb, T * T), dim3(64), 0, ce->stream, p, T);
+                if (rect)
+                    hipLaunchKernelGGL(partition_reduce_kernel<true>, dim3(nb, T * T), dim3(64), 0, ce->stream, p, T);
+                else
+                    hipLaunchKernelGGL(partition_reduce_kernel<false>, dim3(nb, T * T), dim3(64), 0, ce->stream, p, T);
                 HIPCHK(h, hipGetLastError());
             }
         }
     }
-    if (snn) HIPCHK(h, hipMemcpyAsync(snn, s.d_snn.get(), sizeof(double) * (size_t)m * m, hipMemcpyDeviceToHost, ce->stream));
+    if (snn) HIPCHK(h, hipMemcpyAsync(snn, s.d_snn.get(), sizeof(double) * (size_t)m * mc, hipMemcpyDeviceToHost, ce->stream));
     HIPCHK(h, hipStreamSynchronize(ce->stream));
     return BISBM_OK;
 }
 
-int run_sizes(bisbm_engine* h, uint32_t m, double* A) {
-    bisbm_engine* ce = computing_engine(h);
+// sum_r a_r ln a_r of the first m described partitions on ce (chains, then references)
+int run_sizes(bisbm_engine* h, bisbm_engine* ce, uint32_t m, double* A) {
     PartitionState& s = ce->partition;
     RESERVE(h, s.d_A, m);
     hipLaunchKernelGGL(partition_sizes_kernel, dim3(m), dim3(1024), 0, ce->stream, (const ChainDesc*)s.d_desc.get(), (uint32_t)h->n, s.d_A.get());
@@ -357,32 +398,74 @@ int run_sizes(bisbm_engine* h, uint32_t m, double* A) {
     return BISBM_OK;
 }
 
+// the selection of a distances call: chains = NULL is every chain; no chain out of range or twice
+int select_chains(bisbm_engine* h, uint32_t n_sel, const uint32_t* chains, std::vector<uint32_t>& sel) {
+    if (!chains && n_sel != h->n_chains)
+        return fail(h, BISBM_ERR_INVALID_ARG, "chains = NULL selects all %u chains of the handle, n_sel is %u", h->n_chains, n_sel);
+    if (n_sel == 0) return fail(h, BISBM_ERR_INVALID_ARG, "no chain selected");
+    sel.resize(n_sel);
+    std::vector<int64_t> seen(h->n_chains, -1);
+    for (uint32_t i = 0; i < n_sel; ++i) {
+        const uint32_t c = chains ? chains[i] : i;
+        if (c >= h->n_chains)
+            return fail(h, BISBM_ERR_INVALID_ARG, "chain %u (position %u of the selection) is out of range: the handle has %u chains", c, i, h->n_chains);
+        if (seen[c] >= 0)
+            return fail(h, BISBM_ERR_INVALID_ARG, "chain %u is listed twice (positions %lld and %u of the selection)", c, (long long)seen[c], i);
+        seen[c] = i, sel[i] = c;
+    }
+    return BISBM_OK;
+}
+
+// VI of every described chain with every described reference (rows on ce's device) into vi[m * refs], H of the references
+int run_rect(bisbm_engine* h, bisbm_engine* ce, const std::vector<ChainDesc>& desc, const std::vector<ChainDesc>& refs, double* vi, double* h_ref) {
+    const uint32_t m = (uint32_t)desc.size(), r = (uint32_t)refs.size();
+    if (int rc = upload_desc(h, ce, desc, &refs)) return rc;
+    std::vector<double> A(m + r), snn((size_t)m * r, 0.);
+    if (int rc = run_sizes(h, ce, m + r, A.data())) return rc;
+    if (int rc = run_pairs(h, ce, desc, &refs, snn.data(), nullptr)) return rc;
+    const double n = (double)h->n;
+    if (h_ref)
+        for (uint32_t j = 0; j < r; ++j) h_ref[j] = std::log(n) - A[m + j] / n;
+    if (vi)
+        for (uint32_t i = 0; i < m; ++i)
+            for (uint32_t j = 0; j < r; ++j) {
+                const double v = ((A[i] + A[m + j]) - 2. * snn[(size_t)i * r + j]) / n;
+                vi[(size_t)i * r + j] = v > 0. ? v : 0.;
+            }
+    return BISBM_OK;
+}
+
 }  // namespace
+
+int bisbm::partition_distances_rows(bisbm_engine* e, const std::vector<uint32_t>& chains, const uint8_t* d_refs, size_t ref_stride, uint32_t n_refs, double* vi) {
+    if (chains.empty() || !n_refs) return BISBM_OK;
+    if (e->n >= 0xFFFFFFFFull - 8192) return fail(e, BISBM_ERR_UNSUPPORTED, "more than 2^32 - 8193 nodes");
+    HIPCHK(e, hipSetDevice(e->device));
+    try {
+        std::vector<ChainDesc> desc(chains.size()), refs(n_refs);
+        for (size_t i = 0; i < chains.size(); ++i) desc[i] = ChainDesc{e->d_labels + (size_t)chains[i] * e->label_stride, e->ka, e->kb};
+        for (uint32_t g = 0; g < n_refs; ++g) refs[g] = ChainDesc{d_refs + (size_t)g * ref_stride, e->ka, e->kb};
+        return run_rect(e, e, desc, refs, vi, nullptr);
+    } catch (const std::bad_alloc&) {
+        return fail(e, BISBM_ERR_STATE, "out of host memory");
+    }
+}
 
 extern "C" {
 
 int bisbm_partition_distances(bisbm_handle h, uint32_t n_sel, const uint32_t* chains, double* vi_out, double* h_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
-    if (!chains && n_sel != h->n_chains)
-        return fail(h, BISBM_ERR_INVALID_ARG, "chains = NULL selects all %u chains of the handle, n_sel is %u", h->n_chains, n_sel);
-    if (n_sel == 0) return fail(h, BISBM_ERR_INVALID_ARG, "no chain selected");
     try {
-        std::vector<uint32_t> sel(n_sel);
-        std::vector<int64_t> seen(h->n_chains, -1);
-        for (uint32_t i = 0; i < n_sel; ++i) {
-            const uint32_t c = chains ? chains[i] : i;
-            if (c >= h->n_chains)
-                return fail(h, BISBM_ERR_INVALID_ARG, "chain %u (position %u of the selection) is out of range: the handle has %u chains", c, i, h->n_chains);
-            if (seen[c] >= 0)
-                return fail(h, BISBM_ERR_INVALID_ARG, "chain %u is listed twice (positions %lld and %u of the selection)", c, (long long)seen[c], i);
-            seen[c] = i, sel[i] = c;
-        }
+        std::vector<uint32_t> sel;
+        if (int rc = select_chains(h, n_sel, chains, sel)) return rc;
         std::vector<ChainDesc> desc;
         if (int rc = describe(h, "bisbm_partition_distances", sel, desc)) return rc;
+        bisbm_engine* ce = computing_engine(h);
+        if (int rc = upload_desc(h, ce, desc, nullptr)) return rc;
         std::vector<double> A(n_sel), snn(vi_out ? (size_t)n_sel * n_sel : 0, 0.);
-        if (int rc = run_sizes(h, n_sel, A.data())) return rc;
+        if (int rc = run_sizes(h, ce, n_sel, A.data())) return rc;
         if (vi_out)
-            if (int rc = run_pairs(h, desc, snn.data(), nullptr)) return rc;
+            if (int rc = run_pairs(h, ce, desc, nullptr, snn.data(), nullptr)) return rc;
         const double n = (double)h->n;
         if (h_out)
             for (uint32_t i = 0; i < n_sel; ++i) h_out[i] = std::log(n) - A[i] / n;
@@ -400,6 +483,45 @@ int bisbm_partition_distances(bisbm_handle h, uint32_t n_sel, const uint32_t* ch
     return BISBM_OK;
 }
 
+int bisbm_partition_distances_to(bisbm_handle h, uint32_t n_sel, const uint32_t* chains, uint32_t n_refs, const uint32_t* ref_labels, const uint32_t* ref_ka,
+                                 const uint32_t* ref_kb, double* vi_out, double* h_ref_out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (n_refs == 0) return fail(h, BISBM_ERR_INVALID_ARG, "no reference partition (n_refs = 0)");
+    if (!ref_labels || !ref_ka || !ref_kb || !vi_out) return fail(h, BISBM_ERR_INVALID_ARG, "ref_labels, ref_ka, ref_kb and vi_out must be non-NULL");
+    try {
+        std::vector<uint32_t> sel;
+        if (int rc = select_chains(h, n_sel, chains, sel)) return rc;
+        std::vector<ChainDesc> desc;
+        if (int rc = describe(h, "bisbm_partition_distances_to", sel, desc)) return rc;
+        bisbm_engine* ce = computing_engine(h);
+        // the references as byte rows, padded with zeroes like a chain's label row (the kernels load words past n)
+        const size_t srow = ((size_t)h->n + 255) & ~(size_t)255;
+        std::vector<uint8_t> rows((size_t)n_refs * srow, 0);
+        for (uint32_t g = 0; g < n_refs; ++g) {
+            const uint32_t ka = ref_ka[g], kb = ref_kb[g];
+            if ((uint64_t)ka + kb > 256)
+                return fail(h, BISBM_ERR_INVALID_ARG, "reference %u has %u + %u blocks: partition distances serve at most 256", g, ka, kb);
+            const uint32_t* lab = ref_labels + (size_t)g * h->n;
+            for (uint64_t v = 0; v < h->n; ++v) {
+                const bool tb = v >= h->na;
+                if (lab[v] < (tb ? ka : 0u) || lab[v] >= (tb ? ka + kb : ka))
+                    return fail(h, BISBM_ERR_INVALID_ARG, "reference %u: label %u of node %llu is outside its type's blocks [%u, %u)", g, lab[v],
+                                (unsigned long long)v, tb ? ka : 0u, tb ? ka + kb : ka);
+                rows[(size_t)g * srow + v] = (uint8_t)lab[v];
+            }
+        }
+        PartitionState& s = ce->partition;
+        RESERVE(h, s.d_refs, rows.size());
+        HIPCHK(h, hipMemcpyAsync(s.d_refs.get(), rows.data(), rows.size(), hipMemcpyHostToDevice, ce->stream));
+        HIPCHK(h, hipStreamSynchronize(ce->stream));
+        std::vector<ChainDesc> refs(n_refs);
+        for (uint32_t g = 0; g < n_refs; ++g) refs[g] = ChainDesc{s.d_refs.get() + (size_t)g * srow, ref_ka[g], ref_kb[g]};
+        return run_rect(h, ce, desc, refs, vi_out, h_ref_out);
+    } catch (const std::bad_alloc&) {
+        return fail(h, BISBM_ERR_STATE, "out of host memory");
+    }
+}
+
 int bisbm_partition_contingency(bisbm_handle h, uint32_t c, uint32_t d, uint32_t* table_out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (!table_out) return fail(h, BISBM_ERR_INVALID_ARG, "table_out is NULL");
@@ -408,8 +530,10 @@ int bisbm_partition_contingency(bisbm_handle h, uint32_t c, uint32_t d, uint32_t
     try {
         std::vector<ChainDesc> desc;
         if (int rc = describe(h, "bisbm_partition_contingency", {c, d}, desc)) return rc;
+        bisbm_engine* ce = computing_engine(h);
+        if (int rc = upload_desc(h, ce, desc, nullptr)) return rc;
         std::vector<uint32_t> tab;
-        if (int rc = run_pairs(h, desc, nullptr, &tab)) return rc;
+        if (int rc = run_pairs(h, ce, desc, nullptr, nullptr, &tab)) return rc;
         const uint32_t kac = desc[0].ka, kbc = desc[0].kb, kad = desc[1].ka, kbd = desc[1].kb, Kd = kad + kbd;
         std::fill(table_out, table_out + (size_t)(kac + kbc) * Kd, 0u);
         for (uint32_t r = 0; r < kac; ++r)

@@ -172,7 +172,7 @@ int bisbm_tempering_set(bisbm_handle h, uint32_t L, const float* ladder) {
     if (h->rng_mode == BISBM_RNG_MT19937_COMPAT)
         return fail(h, BISBM_ERR_UNSUPPORTED, "replica exchange runs in Philox mode only (mt19937-compat mode is the reference's verification path)");
     if (int rc = mixed_shapes(h)) return rc;
-    if (h->modes.n_modes)
+    if (h->modes.n_modes && !h->modes.anchored)  // (anchored modes assign the cold chains afresh at every sample)
         return fail(h, BISBM_ERR_STATE, "mode-resolved marginals are set (bisbm_marginals_set_modes): chains that trade temperatures have no mode of their own; turn the modes off first");
     if (h->first_chain_id % L)
         return fail(h, BISBM_ERR_INVALID_ARG, "the first global chain id %u is not a multiple of L = %u: ensembles are global ids [g L, (g + 1) L)",

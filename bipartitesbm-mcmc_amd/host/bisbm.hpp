@@ -288,6 +288,19 @@ public:
         check(bisbm_partition_distances(h_, (uint32_t)chains.size(), chains.data(), vi.data(), nullptr));
         return vi;
     }
+    // chains against reference partitions that are no chains (bisbm_partition_distances_to): refs holds n labels per reference,
+    // shapes (ka, kb) per reference; returns vi[chains][references], H of the references into h_ref when given
+    std::vector<double> partition_distances_to(const std::vector<uint32_t>& chains, const std::vector<uint32_t>& refs,
+                                               const std::vector<uint32_t>& ref_ka, const std::vector<uint32_t>& ref_kb,
+                                               std::vector<double>* h_ref = nullptr) {
+        if (ref_ka.size() != ref_kb.size() || refs.size() != ref_ka.size() * n_)
+            throw std::runtime_error("partition_distances_to: n labels and one (ka, kb) per reference");
+        std::vector<double> vi(chains.size() * ref_ka.size());
+        if (h_ref) h_ref->assign(ref_ka.size(), 0.);
+        check(bisbm_partition_distances_to(h_, (uint32_t)chains.size(), chains.data(), (uint32_t)ref_ka.size(), refs.data(), ref_ka.data(),
+                                           ref_kb.data(), vi.data(), h_ref ? h_ref->data() : nullptr));
+        return vi;
+    }
     static void partition_modes(const std::vector<double>& vi, size_t m, double threshold, std::vector<uint32_t>& mode,
                                 std::vector<uint32_t>& medoids) {
         mode.assign(m, 0);
@@ -312,6 +325,18 @@ public:
         terms.assign(n_modes, 0);
         check(bisbm_marginals_get_modes(h_, &n_modes, mode_of_chain.data(), ref_chain.data(), terms.data()));
         return n_modes;
+    }
+    // anchored modes (include/bisbm.h): n labels per anchor, n_modes anchors; every sample counts each chain into the mode of
+    // its nearest anchor within the threshold.  marginals_mode_assignment: visits[chain][mode], unassigned, samples
+    void marginals_set_mode_anchors(uint32_t n_modes, const std::vector<uint32_t>& anchors, double threshold) {
+        if (anchors.size() != (size_t)n_modes * n_) throw std::runtime_error("marginals_set_mode_anchors: n labels per anchor");
+        check(bisbm_marginals_set_mode_anchors(h_, n_modes, n_modes ? anchors.data() : nullptr, threshold));
+    }
+    void marginals_mode_assignment(uint32_t n_modes, std::vector<uint64_t>& visits, uint64_t& unassigned, uint64_t& samples,
+                                   std::vector<double>* vi = nullptr) {
+        visits.assign((size_t)n_chains_ * n_modes, 0);
+        if (vi) vi->assign((size_t)n_chains_ * n_modes, 0.);
+        check(bisbm_marginals_get_mode_assignment(h_, vi ? vi->data() : nullptr, visits.data(), &unassigned, &samples));
     }
     void marginals_set_mode_reference(uint32_t mode, const std::vector<uint32_t>* labels) {
         if (labels && labels->size() != n_) throw std::runtime_error("marginals_set_mode_reference: one label per node");

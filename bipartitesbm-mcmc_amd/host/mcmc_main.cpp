@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --score_pairs, --modes, --mode_marginals.
+// --tempering, --exchange_every, --score_pairs, --modes, --mode_marginals, --reassign.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -49,7 +49,7 @@ const option_spec kOptions[] = {
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
     {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
-    {"modes", 0, 2},            {"mode_marginals", 0, 1},
+    {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -195,7 +195,13 @@ void print_help(const char* argv0) {
                  "                                        lowest-description-length chain.  PREFIX.<g>.txt receives `label count`\n"
                  "                                        per node for mode g (the node's most frequent block within the mode and\n"
                  "                                        how many chain samples chose it); stdout gets the labels of the heaviest\n"
-                 "                                        mode.  Not with --tempering.\n"
+                 "                                        mode.  Not with --tempering (unless --reassign).\n"
+                 "  --reassign                            With --mode_marginals: the grouping only picks one anchor per mode (its\n"
+                 "                                        lowest-description-length chain); every sample counts each chain into the\n"
+                 "                                        mode of its nearest anchor if its VI to it is <= THRESHOLD.  Allowed with\n"
+                 "                                        --tempering (the chains at T0 are counted).  PREFIX.assignment.txt\n"
+                 "                                        receives `chain visits-per-mode` per chain and a last line `unassigned N`;\n"
+                 "                                        a mode's reported share is its share of the samples.\n"
                  "  --csr_cache                           Keep a binary CSR beside the edge list (<path>.bisbm_csr, checked\n"
                  "                                        against the file's size and mtime); the text file stays the input.\n";
 }
@@ -250,7 +256,11 @@ int main(int argc, char const* argv[]) {
         std::cerr << "--mode_marginals counts one histogram per mode: it needs --modes (with --marginalize) for the grouping.\n";
         return 1;
     }
-    if (count("mode_marginals") && count("tempering")) {
+    if (count("reassign") && !count("mode_marginals")) {
+        std::cerr << "--reassign counts every sample into the mode of its nearest anchor: it needs --mode_marginals (with --marginalize --modes).\n";
+        return 1;
+    }
+    if (count("mode_marginals") && count("tempering") && !count("reassign")) {
         std::cerr << "--mode_marginals gives every chain a mode of its own: it cannot be combined with --tempering, where chains trade temperatures.\n";
         return 1;
     }
@@ -791,10 +801,25 @@ int main(int argc, char const* argv[]) {
                 vi = blockmodel.partition_distances(sel);
                 blockmodel_t::partition_modes(vi, sel.size(), modes_threshold, mode, medoids);
             };
-            const bool per_mode = count("mode_marginals") > 0;
+            const bool per_mode = count("mode_marginals") > 0, reassign = count("reassign") > 0;
             if (per_mode) {  // the grouping after the burn-in decides which histogram a chain is counted into
                 group_modes();
-                blockmodel.marginals_set_modes((uint32_t)medoids.size(), mode);
+                if (reassign) {
+                    // ... or only the anchors: every mode's member of the lowest description length; every sample then counts
+                    // each (cold) chain into the mode of its nearest anchor within the threshold
+                    const std::vector<double> dl = blockmodel.entropy_all();
+                    std::vector<uint32_t> anchors;
+                    for (size_t k = 0; k < medoids.size(); ++k) {
+                        size_t low = sel.size();
+                        for (size_t i = 0; i < sel.size(); ++i)
+                            if (mode[i] == k && (low == sel.size() || dl[sel[i]] < dl[sel[low]])) low = i;
+                        const uint_vec_t* lab = blockmodel.get_memberships(sel[low]);
+                        anchors.insert(anchors.end(), lab->begin(), lab->end());
+                    }
+                    blockmodel.marginals_set_mode_anchors((uint32_t)medoids.size(), anchors, modes_threshold);
+                } else {
+                    blockmodel.marginals_set_modes((uint32_t)medoids.size(), mode);
+                }
             }
             if (count("score_pairs")) {  // (--reorder: the engine knows the nodes by their new ids)
                 std::vector<uint32_t> pu, pv;
@@ -852,32 +877,62 @@ int main(int argc, char const* argv[]) {
                 std::vector<int64_t> ref_chain;
                 std::vector<uint64_t> terms;
                 const uint32_t M = blockmodel.marginals_modes(of_chain, ref_chain, terms);
-                std::vector<size_t> size(M, 0);
-                for (uint32_t c : of_chain)
-                    if (c != BISBM_MODE_NONE) size[c] += 1;
+                // a mode's share: of the counted chains (a fixed assignment), of the samples (--reassign)
+                std::vector<double> size(M, 0.);
+                double all = (double)sel.size();
+                std::vector<uint64_t> visits;
+                uint64_t unassigned = 0, n_counted = 0;
+                if (reassign) {
+                    blockmodel.marginals_mode_assignment(M, visits, unassigned, n_counted);
+                    all = (double)unassigned;
+                    for (uint32_t g = 0; g < M; ++g) size[g] = (double)terms[g], all += (double)terms[g];
+                } else {
+                    for (uint32_t c : of_chain)
+                        if (c != BISBM_MODE_NONE) size[c] += 1.;
+                }
                 uint32_t heaviest = 0;
                 std::clog << "mode_marginals: " << M << " mode(s)\n";
                 for (uint32_t g = 0; g < M; ++g) {
                     if (size[g] > size[heaviest]) heaviest = g;  // (ties -> the lowest mode)
-                    std::vector<uint32_t> top;
-                    const std::vector<uint32_t> lab = blockmodel.marginals_map_mode(g, &top);
+                    std::vector<uint32_t> top(N, 0);
+                    // (--reassign: a mode that no sample fell into has no MAP; its file holds zeroes)
+                    const std::vector<uint32_t> lab = terms[g] ? blockmodel.marginals_map_mode(g, &top) : std::vector<uint32_t>(N, 0);
                     const std::string out_path = var_map["mode_marginals"][0] + "." + std::to_string(g) + ".txt";
                     std::ofstream out(out_path);
                     double settled = 0.;
                     for (size_t v = 0; v < N; ++v) {  // (--reorder: the engine knows node v by new_id[v])
                         const size_t e = new_id.empty() ? v : new_id[v];
                         out << lab[e] << " " << top[e] << "\n";
-                        settled += (double)top[e] / (double)terms[g];
+                        if (terms[g]) settled += (double)top[e] / (double)terms[g];
                     }
                     out.close();
                     if (!out) {
                         std::cerr << "[error] --mode_marginals: cannot write " << out_path << "\n";
                         return 1;
                     }
-                    std::clog << "mode " << g << ": share " << (double)size[g] / (double)sel.size() << ", reference chain "
-                              << opt.first_chain_id + (uint32_t)ref_chain[g] << ", " << terms[g] << " term(s), mean top/terms " << settled / (double)N
-                              << " -> " << out_path << "\n";
+                    std::clog << "mode " << g << ": share " << size[g] / all << ", reference ";
+                    if (reassign)
+                        std::clog << "its anchor";
+                    else
+                        std::clog << "chain " << opt.first_chain_id + (uint32_t)ref_chain[g];
+                    std::clog << ", " << terms[g] << " term(s), mean top/terms " << settled / (double)N << " -> " << out_path << "\n";
                     if (g == heaviest) heaviest_labels = uint_vec_t(lab.begin(), lab.end());
+                }
+                if (reassign) {  // one line per chain: its visits per mode; a last line: the samples beyond the threshold
+                    const std::string out_path = var_map["mode_marginals"][0] + ".assignment.txt";
+                    std::ofstream out(out_path);
+                    for (uint32_t c = 0; c < opt.n_chains; ++c) {
+                        out << opt.first_chain_id + c;
+                        for (uint32_t g = 0; g < M; ++g) out << " " << visits[(size_t)c * M + g];
+                        out << "\n";
+                    }
+                    out << "unassigned " << unassigned << "\n";
+                    out.close();
+                    if (!out) {
+                        std::cerr << "[error] --mode_marginals: cannot write " << out_path << "\n";
+                        return 1;
+                    }
+                    std::clog << "reassign: " << n_counted << " sample(s), " << unassigned << " chain sample(s) beyond the threshold -> " << out_path << "\n";
                 }
             }
             if (var_map.count("modes")) {  // (a partition's distance to another does not depend on the node numbering: --reorder is fine)

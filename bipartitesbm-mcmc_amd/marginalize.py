@@ -111,7 +111,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     return labels, counts
 
 
-def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None):
+def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,
+                      reassign=False, tempering=None, exchange_every=1):
     """Mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): the chains are grouped into posterior modes and
     every mode gets an aligned histogram and a MAP of its own, in the numbering of its own reference.
     Exactly one of `threshold` and `mode_of_chain`: with `threshold` the grouping is model.partition_modes(threshold) taken
@@ -127,28 +128,51 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
       ref_chain  int64  [M]           the chain every mode's reference came from (-1: the caller's)
       moved      the number of chains whose set of co-members under the same threshold differs after the last sample (0 with
                  `mode_of_chain`): whether the chains stayed in their modes while they were sampled
+    `reassign`: anchored modes (include/bisbm.h, "Anchored modes").  The grouping (with `threshold`, after the burn-in) only
+    chooses the anchors -- the labels of every mode's `lowest_entropy` chain -- and every sample counts each chain into the mode
+    of its nearest anchor if its VI to it is <= threshold.  The dict then also has `unassigned` (counted chains beyond the
+    threshold, over all samples) and `visits` uint64 [n_chains, M]; `weights` are the sample shares
+    terms / (sum of terms + unassigned), `moved` is the number of chains counted into more than one mode, and `ref_chain` is -1
+    throughout.  `tempering` (with `reassign` only; ValueError otherwise): a temperature ladder as in marginalize(); burn-in
+    and the gaps between samples run through model.tempering_run(sweeps, exchange_every), the grouping and every sample take
+    the chains on rung 0.  `mode_of_chain` with `reassign` is a ValueError: the anchors come from a grouping.
     Chains spread over ranks (`shard`, or model.shard, with world_size > 1) raise ValueError: pooling modes across ranks is
     not done here."""
     if (threshold is None) == (mode_of_chain is None):
         raise ValueError("exactly one of threshold and mode_of_chain must be given")
+    if tempering is not None and not reassign:
+        raise ValueError("tempering needs reassign=True: chains that trade temperatures have no fixed mode")
+    if reassign and mode_of_chain is not None:
+        raise ValueError("reassign takes its anchors from a grouping: give threshold, not mode_of_chain")
     shard = shard if shard is not None else getattr(model, "shard", None)
     if shard is not None and getattr(shard, "world_size", 1) > 1:
         raise ValueError("marginalize_modes serves the chains of one rank: pooling modes across ranks is not done here")
     from . import mode_assignment
     if mode_of_chain is not None:
         moc, n_modes = mode_assignment(mode_of_chain, model.n_chains)
+    if tempering is not None:
+        model.set_tempering(tempering)
+
+        def advance(sweeps):
+            model.tempering_run(sweeps, exchange_every)
+    else:
+        advance = model.run_sweeps
     if burn_in_sweeps > 0:
-        model.run_sweeps(burn_in_sweeps)
+        advance(burn_in_sweeps)
     if threshold is not None:
         modes = model.partition_modes(threshold)
         moc, n_modes = mode_assignment(modes, model.n_chains)
     else:
         modes = moc.copy()
     model.marginals_reset()
-    model.marginals_set_modes(moc, n_modes)
+    if reassign:
+        anchors = np.array([model.get_memberships(int(c)) for c in modes["lowest_entropy"]], dtype=np.uint32)
+        model.marginals_set_mode_anchors(anchors, threshold)
+    else:
+        model.marginals_set_modes(moc, n_modes)
     for _ in range(int(n_samples)):
         if sampling_frequency_sweeps > 0:
-            model.run_sweeps(sampling_frequency_sweeps)
+            advance(sampling_frequency_sweeps)
         model.marginals_accumulate(None)
     state = model.marginals_modes()
     labels = np.zeros((n_modes, model.n), dtype=np.uint32)
@@ -156,8 +180,13 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     counts = np.zeros((n_modes, model.n, model.kmax), dtype=np.int64)
     for g in range(n_modes):
         counts[g] = model.marginals_get(mode=g)
-        if int(n_samples) > 0:
+        if int(state["terms"][g]) > 0:
             labels[g], top[g] = model.marginals_map(mode=g, return_top=True)
+    if reassign:
+        visits = model.marginals_mode_assignment()["visits"]
+        return {"modes": modes, "labels": labels, "top": top, "counts": counts, "terms": state["terms"], "weights": state["weights"],
+                "ref_chain": state["ref_chain"], "moved": int(((visits > 0).sum(axis=1) > 1).sum()), "unassigned": state["unassigned"],
+                "visits": visits}
     moved = 0
     if threshold is not None:
         after = model.partition_modes(threshold, chains=modes["chains"])

@@ -2,7 +2,8 @@
 independent shuffles; their partitions are compared pair by pair on the device (variation of information, in nats: include/bisbm.h,
 "Partition distances and posterior modes") and grouped into modes: chains joined by a path of pairs with VI <= the threshold share
 a mode.  The threshold is the caller's resolution; here a tenth of the mean partition entropy.  Then every mode gets a marginal
-of its own (include/bisbm.h, "Mode-resolved marginals"): one histogram per mode, aligned to the mode's own reference."""
+of its own (include/bisbm.h, "Mode-resolved marginals"): one histogram per mode, aligned to the mode's own reference -- first with
+the chains' modes fixed by the grouping, then anchored: every sample goes to the mode of its nearest anchor partition."""
 import importlib
 import os
 import sys
@@ -44,3 +45,14 @@ for g, (weight, ref, terms) in enumerate(zip(out["weights"], out["ref_chain"], o
     print("mode %d: share %.3f, aligned to chain %d, %d chain samples, mean top/terms %.3f, %d nodes below 0.9, block sizes %s"
           % (g, weight, ref, terms, settled.mean(), int((settled < 0.9).sum()), sizes.tolist()))
 assert (out["counts"].sum(axis=2) == out["terms"][:, None]).all() and out["terms"].sum() == 10 * 64
+
+# the same with anchored modes (include/bisbm.h, "Anchored modes"): the grouping only picks one anchor partition per mode, and every
+# sample counts each chain into the mode of its nearest anchor within the threshold, so a chain that hops is counted where it
+# is and a mode's weight is its share of the samples
+out = bisbm.marginalize_modes(model, 0, 10, 1, threshold=threshold, reassign=True)
+print("anchored: %d mode(s), sample shares %s, %d chain sample(s) beyond the threshold, %d chain(s) counted into more than one mode"
+      % (len(out["terms"]), np.round(out["weights"], 3).tolist(), out["unassigned"], out["moved"]))
+assert out["terms"].sum() + out["unassigned"] == 10 * 64 and (out["visits"].sum(axis=0) == out["terms"]).all()
+# how far is every chain from a partition that is no chain: here the contiguous start
+to_start, H_start = model.partition_distances_to(start)
+print("VI to the contiguous start partition (entropy %.3f): %.3f .. %.3f" % (H_start[0], to_start.min(), to_start.max()))

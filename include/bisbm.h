@@ -25,7 +25,8 @@ extern "C" {
  * 3: bisbm_check_shape; several devices behind one handle (bisbm_create_multi); bisbm_last_pass_steps; later additions: label
  *    alignment (bisbm_marginals_set_alignment ...), replica exchange (bisbm_tempering_*), pair scores (bisbm_pair_scores_*),
  *    partition distances and modes (bisbm_partition_*), mode-resolved marginals (bisbm_marginals_set_modes ...,
- *    bisbm_marginals_get_mode, bisbm_marginals_map_mode).  Additions only. */
+ *    bisbm_marginals_get_mode, bisbm_marginals_map_mode), distances to reference partitions (bisbm_partition_distances_to),
+ *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -308,6 +309,31 @@ int bisbm_partition_contingency(bisbm_handle h, uint32_t c, uint32_t d, uint32_t
 int bisbm_partition_modes(uint32_t m, const double *vi, double threshold, uint32_t *mode_out, uint32_t *medoid_out,
                           uint32_t *n_modes_out);
 
+/* Distances to reference partitions: the selected chains against n_refs partitions of the same n nodes that are not chains -- a
+ * planted or ground-truth partition, the result of an earlier run, a medoid saved to disk.  The definitions are those above
+ * with the chain as the row partition and the reference as the column partition: vi_out[i * n_refs + g] = VI(chain i of the
+ * selection, reference g), h_ref_out[g] = H(reference g) (may be NULL).  Reference g has a shape of its own: its type-a labels
+ * lie in [0, ref_ka[g]), its type-b labels in [ref_ka[g], ref_ka[g] + ref_kb[g]), ref_ka[g] + ref_kb[g] <= 256;
+ * ref_labels[g * n + v] on the host.
+ * The three sums of a VI are each added by one wavefront in the fixed order described above, so the same handle and the same
+ * call give the same bits; they are added in different orders, though, so a reference that equals a chain's labels gives a VI
+ * of rounding size (below 1e-10 for n < 1e5) and not necessarily exactly 0.0, and VI(c, labels of d) agrees with
+ * bisbm_partition_distances' VI(c, d) to that size, not to the bit.  A negative rounding result is returned as 0.0.
+ * Served and refused as bisbm_partition_distances is (labels are only read; both RNG modes, chains grouped by shape, several
+ * devices with the first one computing, replica exchange on; wide handles BISBM_ERR_UNSUPPORTED, BISBM_ERR_STATE before
+ * bisbm_init / bisbm_shuffle, a chain out of range or listed twice BISBM_ERR_INVALID_ARG); also BISBM_ERR_INVALID_ARG:
+ * n_refs = 0, a NULL pointer other than chains and h_ref_out, a reference of more than 256 blocks, a reference label outside
+ * its type's range (bisbm_last_error names the reference and the node).
+ * A workgroup counts a tile of up to 4 chains x 4 references.  Device scratch of a call with m chains, r references, largest
+ * shapes kaM + kbM (chains) and kaR + kbR (references): 16 (m + r) bytes of descriptors, 8 m r + 8 (m + r) bytes of sums, 8
+ * bytes per tile, r rows of n rounded up to 256 bytes, staged rows of chains on other devices as above, and -- only when the
+ * tiles are too few to fill the device or a table does not fit the LDS -- integer tables of 4 (kaM kaR + kbM kbR) bytes per
+ * (chain, reference) for as many tiles as fit 256 MiB (at least one). */
+int bisbm_partition_distances_to(bisbm_handle h, uint32_t n_sel, const uint32_t *chains /* NULL: all */, uint32_t n_refs,
+                                 const uint32_t *ref_labels /* n_refs * n, host */, const uint32_t *ref_ka,
+                                 const uint32_t *ref_kb /* n_refs each */, double *vi_out /* n_sel * n_refs, row = chain */,
+                                 double *h_ref_out /* n_refs, may be NULL */);
+
 /* Mode-resolved marginals (no reference counterpart).  Chains at T = 1 settle in different posterior modes
  * (bisbm_partition_distances / bisbm_partition_modes tell which).  A chain of another mode has no good permutation onto one
  * common reference, so the pooled aligned histogram smears it over the columns and its MAP describes no mode.  With modes set
@@ -356,6 +382,40 @@ int bisbm_marginals_set_mode_reference(bisbm_handle h, uint32_t mode, const uint
 int bisbm_marginals_get_mode_reference(bisbm_handle h, uint32_t mode, uint32_t *labels_out, int64_t *chain_out);
 int bisbm_marginals_get_mode(bisbm_handle h, uint32_t mode, uint32_t *counts_out /* n*kmax, host */);
 int bisbm_marginals_map_mode(bisbm_handle h, uint32_t mode, uint32_t *labels_out /* n */, uint32_t *top_out /* n, may be NULL */);
+
+/* Anchored modes (no reference counterpart): mode-resolved marginals whose assignment is taken afresh at every sample, by
+ * distance to one anchor partition per mode.  A chain that hops to another mode is counted there from then on, replica
+ * exchange is served, and a mode's weight is the share of samples that fall into it.
+ * set_mode_anchors: n_modes histograms and no fixed assignment; anchor g (anchor_labels[g * n + v], validated as
+ *   bisbm_marginals_set_reference validates, against the handle's common shape) is also mode g's alignment reference, as a
+ *   caller's reference (ref_chain = -1).  threshold >= 0, +inf allowed ("always the nearest"); NaN or negative:
+ *   BISBM_ERR_INVALID_ARG.  n_modes = 0 turns the feature off as set_modes(0) does.  BISBM_ERR_STATE as for set_modes (the
+ *   histogram holds samples; chains grouped by shape) except that replica exchange may be on, and bisbm_tempering_set with
+ *   L > 0 is allowed while anchors are set.  bisbm_marginals_set_mode_reference is BISBM_ERR_STATE while anchors are set (the
+ *   anchors are the references).  set_modes replaces anchors; set_mode_anchors replaces a static assignment.
+ * A sample is bisbm_marginals_accumulate(h, NULL).  The counted chains are every chain, or, with replica exchange on, the
+ *   chains on rung 0 at that moment.  For every counted chain c and anchor g, VI(c, g) is computed as
+ *   bisbm_partition_distances_to computes it; g* is the anchor of least VI (ties -> the lowest g).  If VI(c, g*) <= threshold
+ *   the chain is counted into histogram g* through its permutation onto anchor g* (the pipeline of static modes), terms[g*]
+ *   and visits[c][g*] grow by one; otherwise it is not counted and `unassigned` grows by one.  `samples` grows by one per call.
+ *   A wide handle and a caller's device_counts are BISBM_ERR_UNSUPPORTED.  After a merge or split that changes the block
+ *   counts the next sample is BISBM_ERR_STATE ("set the anchors again").
+ * bisbm_marginals_get_modes returns the last sample's assignment (BISBM_MODE_NONE: not counted or unassigned; all of them
+ *   before the first sample) and terms.  get_mode_assignment: vi_out[n_chains * n_modes] of the last sample (NaN rows: chains
+ *   that were not counted, every row before the first sample), the running visits_out[n_chains * n_modes], unassigned and
+ *   samples; any pointer may be NULL; BISBM_ERR_STATE while no anchors are set.  get_mode, map_mode, get_mode_reference and
+ *   bisbm_marginals_get_alignment work as with static modes (map_mode of a mode with terms = 0: BISBM_ERR_STATE).
+ * bisbm_marginals_reset zeroes the histograms, terms, visits, unassigned and samples; anchors and threshold stay.
+ * Several devices: the anchors are replicated, every device assigns and counts its own chains, terms / visits / unassigned live
+ *   with the handle; the results equal those of one device with all the chains bit for bit.
+ * Memory: as for static modes, plus per device n_modes anchor rows of the label stride (n rounded up to 256 bytes) and the
+ *   scratch of bisbm_partition_distances_to for the device's counted chains x n_modes (no reference rows of its own); on the
+ *   host 16 n_chains n_modes bytes of VI and visits and 4 n n_modes bytes of anchors. */
+int bisbm_marginals_set_mode_anchors(bisbm_handle h, uint32_t n_modes, const uint32_t *anchor_labels /* n_modes * n */,
+                                     double threshold);
+int bisbm_marginals_get_mode_assignment(bisbm_handle h, double *vi_out /* n_chains * n_modes */,
+                                        uint64_t *visits_out /* n_chains * n_modes */, uint64_t *unassigned_out,
+                                        uint64_t *samples_out);
 
 /* blockmodel_t::agg_merge(engine, diff_a, diff_b, nm) (blockmodel.hh, blockmodel.cc:109-206; call sites
  * mcmc_main.cc:385,429,434,446): merge diff_a type-a and diff_b type-b blocks in every chain -- nm proposals per
