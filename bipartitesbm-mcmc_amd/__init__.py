@@ -38,6 +38,10 @@ MODE_NONE = 0xFFFFFFFF  # BISBM_MODE_NONE: a chain that no mode counts
 RNG_PHILOX = 0
 RNG_MT19937_COMPAT = 1
 ALL_CHAINS = -1
+# bisbm_query_scores_*: candidates x queries of one workgroup of the accumulate kernel and the largest k of the top-k selection
+# (csrc/bisbm_kernels.hpp: kQueryCandTile, kQueryTile, kQueryMaxK), and the entry past a query's eligible candidates
+QUERY_CAND_TILE, QUERY_TILE, QUERY_MAX_K = 1024, 8, 1024
+QUERY_NONE = 0xFFFFFFFF
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
 _u64p = C.POINTER(C.c_uint64)
@@ -92,6 +96,11 @@ ABI = {
     "bisbm_pair_scores_accumulate": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_reset": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_get": (C.c_int, [C.c_void_p, _f64p, _u64p]),
+    "bisbm_query_scores_set": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
+    "bisbm_query_scores_accumulate": (C.c_int, [C.c_void_p]),
+    "bisbm_query_scores_reset": (C.c_int, [C.c_void_p]),
+    "bisbm_query_scores_get_row": (C.c_int, [C.c_void_p, C.c_uint32, _f64p, _u64p]),
+    "bisbm_query_scores_topk": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, _u32p, _f64p, _u64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
@@ -727,6 +736,59 @@ class BlockModel:
         self._check(self._L.bisbm_pair_scores_get(self._h, _p(out, _f64p), C.byref(terms)))
         return out, terms.value
 
+    # -- query scores (include/bisbm.h, "Query scores")
+    def query_scores_set(self, queries):
+        """The nodes to rank candidates for: an integer array [Q] of node ids of either type (they may repeat); replaces earlier
+        queries and zeroes the sums.  Every query gets a row of one f64 per node of the other type on the device.  An empty
+        array frees everything."""
+        q = np.asarray(queries)
+        if q.size == 0:
+            q = np.zeros(0, dtype=np.uint32)
+        if q.ndim != 1 or not np.issubdtype(q.dtype, np.integer):
+            raise ValueError("queries must be a one-dimensional integer array")
+        if len(q) and (q.min() < 0 or q.max() > 0xFFFFFFFF):
+            raise ValueError("a query is outside [0, 2^32)")
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        self._check(self._L.bisbm_query_scores_set(self._h, len(q), _p(q, _u32p)))
+        self.queries = q.copy()
+
+    def query_scores_accumulate(self):
+        """One sample: every counted chain's term is added to the sum of every (query, candidate), chain by chain in ascending
+        order (with replica exchange on, the chains on rung 0 only)."""
+        self._check(self._L.bisbm_query_scores_accumulate(self._h))
+
+    def query_scores_reset(self):
+        self._check(self._L.bisbm_query_scores_reset(self._h))
+
+    def query_scores(self, i):
+        """(row float64 [n_other], terms) of the i-th query: the sums of its candidates in id order (candidate j of a type-a
+        query is node na + j, of a type-b query node j)."""
+        queries = getattr(self, "queries", np.zeros(0, dtype=np.uint32))
+        i = int(i)
+        if not 0 <= i < len(queries):
+            raise IndexError("query index %d: %d queries are set" % (i, len(queries)))
+        out = np.zeros(self.n - self.na if queries[i] < self.na else self.na, dtype=np.float64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_query_scores_get_row(self._h, i, _p(out, _f64p), C.byref(terms)))
+        return out, terms.value
+
+    def query_topk(self, k, exclude_edges=True):
+        """(nodes uint32 [Q, k], sums float64 [Q, k], terms): every query's k best candidates by pooled sum, descending, ties to
+        the lowest node id, selected on the device.  exclude_edges: the query's neighbours are not eligible.  Entries past the
+        eligible candidates are 0xffffffff / 0.0."""
+        Q = len(getattr(self, "queries", ()))
+        nodes = np.zeros((Q, int(k)), dtype=np.uint32)
+        sums = np.zeros((Q, int(k)), dtype=np.float64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_query_scores_topk(self._h, int(k), 1 if exclude_edges else 0, _p(nodes, _u32p), _p(sums, _f64p), C.byref(terms)))
+        return nodes, sums, terms.value
+
+    def recommend(self, k, exclude_edges=True):
+        """(nodes uint32 [Q, k], scores float64 [Q, k], terms): query_topk with scores = sum / terms, the estimate of the expected
+        number of edges between the query and the node."""
+        nodes, sums, terms = self.query_topk(k, exclude_edges)
+        return nodes, sums / terms, terms
+
     # -- partition distances and posterior modes (include/bisbm.h, "Partition distances and posterior modes")
     def partition_distances(self, chains=None):
         """(vi float64 [m, m], H float64 [m]): the variation of information (nats) between every two of the selected chains'
@@ -912,5 +974,5 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import ChainShard, numpy_pair_scores, shard_chains  # noqa: E402,F401
+from .distributed import ChainShard, numpy_pair_scores, numpy_query_topk, shard_chains  # noqa: E402,F401
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

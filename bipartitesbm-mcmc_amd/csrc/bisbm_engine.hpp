@@ -14,6 +14,7 @@
 //                        overlap, assignment and counting kernels; one mode of every chain: the pooled aligned histogram)
 //   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
+//   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains, top-k on the device; kernels and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
 //
@@ -181,6 +182,25 @@ struct PairScoreState {
     std::vector<uint32_t> order;  // sorted position -> index in the caller's arrays
 };
 
+// Query scores (bisbm_query_scores.hip).  The sums belong to the engine that owns the graph on a device (a plain handle, the
+// container of shape groups, a device entry); the container of device entries keeps the host side (n, q, off) only.  The scratch
+// of bisbm_query_scores_topk is on the engine whose device selects (a plain handle, the first device entry).
+struct QueryScoreState {
+    uint32_t n = 0;               // queries set (0: none)
+    uint32_t n_a = 0;             // ... of type a
+    uint64_t terms = 0;           // chain terms added to every sum since the last set / reset
+    std::vector<uint32_t> q;      // [n] node of every query, caller's order
+    std::vector<uint64_t> off;    // [n + 1] first cell of every query's row; off[n]: cells in all
+    DeviceBuf<uint32_t> d_q;      // [n] `q`
+    DeviceBuf<uint64_t> d_off;    // [n + 1] `off`
+    DeviceBuf<uint32_t> d_list;   // [n] indices of the type-a queries, then of the type-b queries, each ascending
+    DeviceBuf<double> d_sum;      // [off[n]] running sums, query by query, candidates in id order
+    DeviceBuf<uint8_t> d_mask;    // topk: neighbour mask of one chunk of queries
+    DeviceBuf<double> d_rows, d_stage;  // topk over several devices: the chunk's rows added in device order, one device's part
+    DeviceBuf<uint32_t> d_node;   // topk: [chunk][k] selected nodes
+    DeviceBuf<double> d_val;      // topk: [chunk][k] their sums
+};
+
 // Partition distances (bisbm_partition.hip).  The scratch of the calls, on the engine whose device computes (a plain handle, the
 // container of shape groups, the first device entry); nothing of it outlives a call in meaning, it is only kept to be reused.
 struct PartitionState {
@@ -306,6 +326,7 @@ struct bisbm_engine {
     bisbm::AlignState align;
     bisbm::TemperState temper;
     bisbm::PairScoreState pairs;
+    bisbm::QueryScoreState queries;
     bisbm::PartitionState partition;
     bisbm::ModeState modes;
 };

@@ -168,6 +168,39 @@ struct PairScoreParams {
 };
 constexpr uint32_t kPairTile = 2048;  // pairs per workgroup: 256 lanes, 8 pairs each
 
+// Query scores (bisbm_query_scores.hip): one sample of the chains of one engine into the rows of the queries of one type.  A
+// workgroup owns kQueryCandTile candidates x kQueryTile queries of the list and adds the counted chains onto its cells of `sum`
+// one at a time, in ascending chain order.
+struct QueryScoreParams {
+    uint32_t n, na, ka, kb, n_chains;
+    uint32_t type;            // 0: type-a queries (candidates na .. n-1), 1: type-b queries (candidates 0 .. na-1)
+    uint32_t n_list;          // queries of this type
+    uint32_t cand_tiles, q_tile0;  // the launcher's: candidate tiles of the type, first query tile of the launch
+    const uint32_t* list;     // [n_list] their indices in the caller's order
+    const uint32_t* queries;  // [n_queries] node of every query
+    const uint64_t* off;      // [n_queries + 1] first cell of every query's row in `sum`
+    const uint32_t* rowptr;
+    const uint8_t* labels;    // byte labels
+    size_t label_stride;      // (a multiple of 4: a lane reads four candidates' labels as one word)
+    const int32_t* m;         // [chain][ka*kb]
+    const int32_t* m_r;       // [chain][K]
+    const uint32_t* rung;     // replica exchange: only chains with rung[c] == 0 are counted; NULL: every chain
+    double* sum;
+};
+constexpr uint32_t kQueryCandTile = 1024;  // candidates per workgroup: 256 lanes, one word of 4 labels each
+constexpr uint32_t kQueryTile = 8;         // queries per workgroup
+constexpr uint32_t kQueryMaxK = 1024;      // bisbm_query_scores_topk: the largest k (the selection is kept in LDS)
+// Selection of one chunk of queries (q0 .. q0 + n_q - 1): rows / mask hold the chunk's cells from cell off[q0] on.
+struct QuerySelectParams {
+    uint32_t n, na, q0, n_q, k;
+    const uint32_t* queries;
+    const uint64_t* off;
+    const double* rows;
+    const uint8_t* mask;  // 1: not eligible; NULL: every candidate is
+    uint32_t* node_out;   // [n_q][k] global node ids in rank order, 0xffffffff past the eligible ones
+    double* sum_out;      // [n_q][k]
+};
+
 // agg_split (blockmodel.cc:505-565): evaluation of `n_trials` random half-cuts of every block of one type, all chains
 struct SplitParams {
     const uint32_t* rowptr;
@@ -294,6 +327,11 @@ hipError_t launch_pair_scores(const PairScoreParams& p, hipStream_t stream);
 // sum[i] += part[0][i] + ... + part[slabs - 1][i], added in slab order
 hipError_t launch_pair_scores_fold(double* sum, const double* part, uint32_t slabs, uint32_t n_pairs, hipStream_t stream);
 uint32_t pair_score_slabs(uint64_t n_pairs, uint32_t n_chains);
+hipError_t launch_query_scores(const QueryScoreParams& p, hipStream_t stream);
+// mask[cell of (query, neighbour)] = 1 for every entry of the CSR rows of queries q0 .. q0 + n_q - 1 (mask: the chunk's, zeroed)
+hipError_t launch_query_mask(const uint32_t* rowptr, const uint32_t* col, const QuerySelectParams& p, uint8_t* mask, hipStream_t stream);
+hipError_t launch_query_select(const QuerySelectParams& p, hipStream_t stream);
+hipError_t launch_query_rows_add(double* a, const double* b, uint64_t count, hipStream_t stream);  // a += b
 hipError_t launch_log_q_probe(const Tables& tab, const int32_t* n, const int32_t* k, size_t count, double* out,
                               int fast, hipStream_t stream);
 

@@ -207,3 +207,24 @@ def numpy_pair_scores(labels_by_chain, m_by_chain, m_r_by_chain, deg, pairs):
         term[live] = (dd[live] * m[bu, bv].astype(np.float64)) / (m_r[bu].astype(np.float64) * m_r[bv].astype(np.float64))
         total += term
     return total
+
+
+QUERY_NONE = 0xFFFFFFFF  # bisbm_query_scores_topk: an entry past the eligible candidates
+
+
+def numpy_query_topk(row, k, excluded=()):
+    """Host statement of the ranking of bisbm_query_scores_topk for one query: `row` holds the sums of its candidates in id
+    order, `excluded` the candidate indices that are not eligible (any order, repeats allowed).  Returns (index uint32 [k], sum
+    float64 [k]): the eligible candidates by sum descending, ties to the lowest index; entries past the eligible ones are
+    QUERY_NONE / 0.0.  The indices count within the row: add the first candidate's node id for global ids."""
+    row = np.asarray(row, dtype=np.float64)
+    ids = np.arange(len(row))
+    keep = np.ones(len(row), dtype=bool)
+    keep[np.asarray(excluded, dtype=np.int64)] = False
+    ids = ids[keep]
+    order = ids[np.lexsort((ids, -row[ids]))][:int(k)]
+    idx = np.full(int(k), QUERY_NONE, dtype=np.uint32)
+    val = np.zeros(int(k), dtype=np.float64)
+    idx[:len(order)] = order
+    val[:len(order)] = row[order]
+    return idx, val

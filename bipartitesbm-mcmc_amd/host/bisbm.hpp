@@ -174,7 +174,7 @@ public:
         : KA_(KA), KB_(KB), n_chains_(opt.n_chains) {
         size_t na = 0, nb = 0;
         for (auto t : types) (t == 0 ? na : nb) += 1;
-        n_ = na + nb;
+        n_ = na + nb, na_ = na;
         const int rc = opt.devices.size() > 1
                            ? bisbm_create_multi(&h_, n_, na, nb, adj_list_ptr->rowptr.data(), adj_list_ptr->col.data(), (uint32_t)KA,
                                                 (uint32_t)KB, epsilon, opt.n_chains, opt.first_chain_id, opt.devices.data(),
@@ -274,6 +274,26 @@ public:
         std::vector<double> sum(n_pairs_);
         check(bisbm_pair_scores_get(h_, sum.data(), &terms));
         return sum;
+    }
+    // query scores (include/bisbm.h): the query nodes (either type), a sample of every counted chain, one query's row over its
+    // candidates (all nodes of the other type, in id order), and every query's k best candidates selected on the device
+    // (nodes / sums [queries * k], 0xffffffff / 0.0 past the eligible ones; the estimate of an entry is sum / terms)
+    void query_scores_set(const std::vector<uint32_t>& queries) {
+        check(bisbm_query_scores_set(h_, (uint32_t)queries.size(), queries.data()));
+        queries_ = queries;
+    }
+    void query_scores_accumulate() { check(bisbm_query_scores_accumulate(h_)); }
+    void query_scores_reset() { check(bisbm_query_scores_reset(h_)); }
+    std::vector<double> query_scores_row(uint32_t query_index, uint64_t& terms) {
+        if (query_index >= queries_.size()) throw std::runtime_error("query_scores_row: no such query");
+        std::vector<double> sum(queries_[query_index] < na_ ? n_ - na_ : na_);
+        check(bisbm_query_scores_get_row(h_, query_index, sum.data(), &terms));
+        return sum;
+    }
+    void query_scores_topk(uint32_t k, bool exclude_neighbours, std::vector<uint32_t>& nodes, std::vector<double>& sums, uint64_t& terms) {
+        nodes.assign(queries_.size() * (size_t)k, 0);
+        sums.assign(queries_.size() * (size_t)k, 0.);
+        check(bisbm_query_scores_topk(h_, k, exclude_neighbours ? 1 : 0, nodes.data(), sums.data(), &terms));
     }
     // rung of every chain under replica exchange (bisbm_tempering_get)
     std::vector<uint32_t> tempering_rungs() {
@@ -376,7 +396,8 @@ private:
         KB_ = kb;
     }
     bisbm_handle h_ = nullptr;
-    size_t KA_, KB_, n_ = 0, n_pairs_ = 0;
+    size_t KA_, KB_, n_ = 0, na_ = 0, n_pairs_ = 0;
+    std::vector<uint32_t> queries_;
     uint32_t n_chains_;
     uint_vec_t memberships_;
 };

@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --score_pairs, --modes, --mode_marginals, --reassign.
+// --tempering, --exchange_every, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -49,6 +49,7 @@ const option_spec kOptions[] = {
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
     {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
+    {"recommend", 0, 2},        {"include_edges", 0, 0},
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
 };
 
@@ -185,6 +186,13 @@ void print_help(const char* argv0) {
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
                  "                                        (score = the mean over samples and chains, printed with %.17g).\n"
+                 "  --recommend QUERIES OUT K             With --marginalize: QUERIES holds one node id per line (either type);\n"
+                 "                                        every sample adds every sampled chain's expected edge count between the\n"
+                 "                                        node and EVERY node of the other type, and OUT receives the K best\n"
+                 "                                        candidates of every query that are not its neighbours already, as\n"
+                 "                                        `query candidate score` lines in rank order (score descending, ties to\n"
+                 "                                        the lowest id; score = the mean over samples and chains, %.17g).\n"
+                 "  --include_edges                       With --recommend: the query's neighbours are ranked as well.\n"
                  "  --modes OUT THRESHOLD                 With --marginalize: after the last sample the sampled chains' partitions\n"
                  "                                        are compared (variation of information, nats) and grouped into modes:\n"
                  "                                        chains joined by a path of pairs with VI <= THRESHOLD share a mode.  OUT\n"
@@ -233,6 +241,29 @@ int main(int argc, char const* argv[]) {
     if (count("score_pairs") && var_map["score_pairs"].size() != 2) {
         std::cerr << "Invalid --score_pairs. Two paths: the file of pairs to read and the file of scores to write.\n";
         return 1;
+    }
+    if ((count("recommend") || count("include_edges")) && !count("marginalize")) {
+        std::cerr << "--recommend ranks the candidates of nodes over the samples of the chains: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("include_edges") && !count("recommend")) {
+        std::cerr << "--include_edges keeps a query's neighbours among its candidates: it needs --recommend.\n";
+        return 1;
+    }
+    uint32_t recommend_k = 0;
+    if (var_map.count("recommend")) {
+        if (var_map["recommend"].size() != 3) {
+            std::cerr << "Invalid --recommend. Three arguments: the file of query nodes to read, the file to write and K.\n";
+            return 1;
+        }
+        const std::string tok = var_map["recommend"][2];
+        char* end = nullptr;
+        const unsigned long k = std::strtoul(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0' || tok[0] == '-' || tok[0] == '+' || k == 0 || k > 0xffffffffUL) {
+            std::cerr << "Invalid --recommend. K must be a positive integer, e.g. --recommend queries.txt out.txt 10.\n";
+            return 1;
+        }
+        recommend_k = (uint32_t)k;
     }
     double modes_threshold = 0.;
     if (var_map.count("modes") && !count("marginalize")) {
@@ -333,6 +364,30 @@ int main(int argc, char const* argv[]) {
                           << ") must name a type-a node [0, " << NA << ") and a type-b node [" << NA << ", " << NA + NB << ")\n";
                 return 1;
             }
+    }
+    // --recommend: the queries are read and checked before any device is touched (ids as in the edge list file)
+    std::vector<uint32_t> recommend_queries;
+    if (var_map.count("recommend")) {
+        const std::string in = var_map["recommend"][0];
+        std::ifstream file(in);
+        if (!file) {
+            std::cerr << "[error] --recommend: cannot read " << in << "\n";
+            return 1;
+        }
+        std::string text;
+        for (size_t line_no = 1; std::getline(file, text); ++line_no) {
+            const size_t b = text.find_first_not_of(" \t\r");
+            if (b == std::string::npos) continue;  // (an empty line)
+            const size_t e = text.find_last_not_of(" \t\r");
+            const std::string tok = text.substr(b, e - b + 1);
+            char* end = nullptr;
+            const unsigned long long id = std::strtoull(tok.c_str(), &end, 10);
+            if (*end != '\0' || tok[0] == '-' || tok[0] == '+' || id >= NA + NB) {
+                std::cerr << "[error] --recommend: line " << line_no << " of " << in << " (" << tok << ") must name a node [0, " << NA + NB << ")\n";
+                return 1;
+            }
+            recommend_queries.push_back((uint32_t)id);
+        }
     }
     const std::string cooling_schedule = single("cooling_schedule", "abrupt_cool");
     const size_t sampling_steps = std::strtoull(single("sampling_steps", "1000").c_str(), nullptr, 10);
@@ -829,10 +884,16 @@ int main(int argc, char const* argv[]) {
                 }
                 blockmodel.pair_scores_set(pu, pv);
             }
+            if (!recommend_queries.empty()) {  // (--reorder: the engine knows the nodes by their new ids)
+                std::vector<uint32_t> q;
+                for (uint32_t v : recommend_queries) q.push_back(new_id.empty() ? v : new_id[v]);
+                blockmodel.query_scores_set(q);
+            }
             for (size_t sample = 0; sample < n_samples; ++sample) {
                 advance(sweeps_between);
                 blockmodel.marginals_accumulate();
                 if (!score_pairs.empty()) blockmodel.pair_scores_accumulate();
+                if (!recommend_queries.empty()) blockmodel.query_scores_accumulate();
             }
             std::clog << "marginalize: burn-in " << burn_in / N << " sweeps, " << n_samples << " samples " << sweeps_between
                       << " sweep(s) apart, " << opt.n_chains << " chain(s) pooled\n";
@@ -870,6 +931,32 @@ int main(int argc, char const* argv[]) {
                     return 1;
                 }
                 std::clog << "score_pairs: " << score_pairs.size() << " pair(s), " << terms << " chain term(s) each -> " << out_path << "\n";
+            }
+            if (var_map.count("recommend")) {
+                const std::string out_path = var_map["recommend"][1];
+                std::ofstream out(out_path);
+                uint64_t terms = 0;
+                std::vector<uint32_t> nodes;
+                std::vector<double> sums;
+                if (!recommend_queries.empty()) blockmodel.query_scores_topk(recommend_k, !count("include_edges"), nodes, sums, terms);
+                std::vector<uint32_t> old_id(new_id.size());
+                for (size_t v = 0; v < new_id.size(); ++v) old_id[new_id[v]] = (uint32_t)v;
+                char line[128];
+                for (size_t i = 0; i < recommend_queries.size(); ++i)
+                    for (size_t r = 0; r < recommend_k; ++r) {
+                        const uint32_t node = nodes[i * recommend_k + r];
+                        if (node == 0xffffffffu) continue;  // (fewer than K candidates are eligible)
+                        std::snprintf(line, sizeof(line), "%u %u %.17g\n", recommend_queries[i], new_id.empty() ? node : old_id[node],
+                                      sums[i * recommend_k + r] / (double)terms);
+                        out << line;
+                    }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --recommend: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "recommend: " << recommend_queries.size() << " query node(s), " << recommend_k << " candidate(s) each, " << terms
+                          << " chain term(s) per score -> " << out_path << "\n";
             }
             uint_vec_t heaviest_labels;
             if (per_mode) {

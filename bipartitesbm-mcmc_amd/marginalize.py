@@ -17,7 +17,7 @@ import numpy as np
 
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
-                return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None):
+                return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -44,7 +44,10 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     `score_pairs`: an integer array [P, 2] of (type-a node, type-b node) pairs (include/bisbm.h, "Posterior-predictive pair
     scores"): set, with zeroed sums, before the first sample, and every sample also adds every counted chain's term to every
     pair's sum (with `tempering` the chains on rung 0 only).  The return value does not change: model.pair_scores() gives
-    (sum, terms) afterwards, shard.pooled_pair_scores(model) the same over ranks."""
+    (sum, terms) afterwards, shard.pooled_pair_scores(model) the same over ranks.
+    `recommend`: (queries, k) or (queries, k, exclude_edges) (include/bisbm.h, "Query scores"): the queries are set, with zeroed
+    sums, before the first sample, every sample also adds every counted chain's term to every (query, candidate) sum, and the
+    return value becomes (labels, counts, model.recommend(k, exclude_edges)) -- the chains of this rank only."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
@@ -61,6 +64,14 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     if score_pairs is not None:
         model.pair_scores_set(score_pairs)
         model.pair_scores_reset()
+    if recommend is not None:
+        model.query_scores_set(recommend[0])
+        model.query_scores_reset()
+
+    def result(labels, counts):
+        if recommend is None:
+            return labels, counts
+        return labels, counts, model.recommend(int(recommend[1]), bool(recommend[2]) if len(recommend) > 2 else True)
     if device_counts is None and not multi:
         # one rank, no caller buffer: the library's own histogram
         model.marginals_reset()
@@ -72,9 +83,11 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             model.marginals_accumulate(None)
             if score_pairs is not None:
                 model.pair_scores_accumulate()
+            if recommend is not None:
+                model.query_scores_accumulate()
         counts = model.marginals_get().astype(np.int64)
         base = np.where(np.arange(n) >= model.na, model.KA, 0)
-        return (counts.argmax(axis=1) + base).astype(np.uint32), (counts if return_counts else None)
+        return result((counts.argmax(axis=1) + base).astype(np.uint32), (counts if return_counts else None))
 
     import torch
     if device_counts is None:
@@ -99,16 +112,18 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         model.marginals_accumulate(device_counts.data_ptr())  # adds into the tensor, on the device
         if score_pairs is not None:
             model.pair_scores_accumulate()
+        if recommend is not None:
+            model.query_scores_accumulate()
     if not multi:
         from .distributed import _argmax_first
         arg = _argmax_first(device_counts)
         node = torch.arange(n, device=device_counts.device)
         labels = (arg + torch.where(node >= model.na, model.KA, 0)).cpu().numpy().astype(np.uint32)
-        return labels, (device_counts.cpu().numpy().astype(np.int64) if return_counts else None)
+        return result(labels, (device_counts.cpu().numpy().astype(np.int64) if return_counts else None))
     send = device_counts if _uses_cuda_backend(shard) else device_counts.cpu()
     labels = shard.map_labels(send, model.na, model.KA).cpu().numpy().astype(np.uint32)
     counts = shard.pooled_marginals(send).cpu().numpy().astype(np.int64) if return_counts else None
-    return labels, counts
+    return result(labels, counts)
 
 
 def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,

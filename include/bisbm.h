@@ -26,7 +26,8 @@ extern "C" {
  *    alignment (bisbm_marginals_set_alignment ...), replica exchange (bisbm_tempering_*), pair scores (bisbm_pair_scores_*),
  *    partition distances and modes (bisbm_partition_*), mode-resolved marginals (bisbm_marginals_set_modes ...,
  *    bisbm_marginals_get_mode, bisbm_marginals_map_mode), distances to reference partitions (bisbm_partition_distances_to),
- *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment).  Additions only. */
+ *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
+ *    (bisbm_query_scores_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -266,6 +267,45 @@ int bisbm_pair_scores_set(bisbm_handle h, uint64_t n_pairs, const uint32_t *u, c
 int bisbm_pair_scores_accumulate(bisbm_handle h);
 int bisbm_pair_scores_reset(bisbm_handle h);
 int bisbm_pair_scores_get(bisbm_handle h, double *sum_out /* n_pairs, host */, uint64_t *terms_out);
+
+/* Query scores: for one node, every node of the other type scored and ranked (no reference counterpart).  A QUERY is a node q of
+ * either type; its CANDIDATES are all nodes of the other type in id order: na .. n-1 for q < na, 0 .. na-1 for q >= na
+ * (n_other of them).  One chain's term for (query, candidate) is exactly the pair-score term above of the pair (type-a node u,
+ * type-b node v) the two form,
+ *     ((double)d(u) * (double)d(v)) * (double)m[b_u][b_v] / ((double)m_r[b_u] * (double)m_r[b_v]),
+ * the same f64 operations in the same order without a fused multiply-add, 0.0 where a degree is 0: bit-equal to what
+ * bisbm_pair_scores_* gives one chain for that pair.  Over all candidates one chain's terms add up to d(q).  A SAMPLE
+ * (bisbm_query_scores_accumulate) adds the term of every counted chain to sum[query][candidate] and the number of counted chains
+ * to `terms`; counted = every chain, or with replica exchange on only the chains on rung 0.  The ORDER OF THE ADDITIONS is part
+ * of the definition: per device the counted chains are added one at a time in ascending chain index (chains grouped by shape:
+ * group by group in group order, ascending within a group), each with one f64 add onto the running sum -- the result does not
+ * depend on tile sizes or launch geometry and a sequential loop on the host reproduces it bit for bit.  Several devices: each
+ * keeps the sums of its own chains, and they are added in device order when they are read.  Nothing is aligned (the term does
+ * not depend on how a chain numbers its blocks); both RNG modes, chains of different shapes and several devices are served;
+ * replica exchange over chains grouped by shape is BISBM_ERR_STATE, as for the pair scores.  A handle with two-byte labels
+ * (KA + KB > 256) is refused by accumulate with BISBM_ERR_UNSUPPORTED: bisbm_pair_scores_* serves it, list the pairs there.
+ * Sums and terms survive merges, splits and regrouping by shape.  Memory: 8 bytes per (query, candidate) per device.
+ * set: uploads n_queries nodes (they may repeat, both types may be mixed), replacing earlier ones, and allocates and zeroes
+ *   sum over the queries of n_other doubles per device (64-bit cell indices; nothing is capped or subsampled: an allocation that
+ *   fails is BISBM_ERR_HIP with the size in the message).  A query >= n is BISBM_ERR_INVALID_ARG, bisbm_last_error names the
+ *   first offending index, and the earlier queries stay in place.  n_queries = 0 frees everything.
+ * accumulate: one sample; BISBM_ERR_STATE before bisbm_init / bisbm_shuffle or without queries.
+ * reset: zeroes sums and terms, keeps the queries.
+ * get_row: the row of query `query_index` (its position in the array given to set) in candidate-id order; sum_out or terms_out
+ *   may be NULL.
+ * topk: for every query its k best candidates by pooled sum, descending, ties to the lowest node id, selected on the device:
+ *   node_out[query][rank] holds global node ids, sum_out (may be NULL) their sums, bit-equal to get_row's.  With
+ *   exclude_neighbours != 0 every node in the query's CSR row is not eligible (a neighbour by several edges is simply not
+ *   there).  Candidates of sum 0.0 are eligible and rank last, by id.  Where fewer than k candidates are eligible the remaining
+ *   entries are 0xffffffff and 0.0.  k = 0 is BISBM_ERR_INVALID_ARG; every k <= 1024 is served, a larger k is
+ *   BISBM_ERR_UNSUPPORTED; BISBM_ERR_STATE while terms == 0.  Several devices: the rows are added on the first device in device
+ *   order, a bounded chunk of queries at a time, and selected there. */
+int bisbm_query_scores_set(bisbm_handle h, uint32_t n_queries, const uint32_t *queries);
+int bisbm_query_scores_accumulate(bisbm_handle h);
+int bisbm_query_scores_reset(bisbm_handle h);
+int bisbm_query_scores_get_row(bisbm_handle h, uint32_t query_index, double *sum_out /* n_other, host */, uint64_t *terms_out);
+int bisbm_query_scores_topk(bisbm_handle h, uint32_t k, int exclude_neighbours, uint32_t *node_out /* n_queries * k, host */,
+                            double *sum_out /* n_queries * k, host, may be NULL */, uint64_t *terms_out);
 
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
