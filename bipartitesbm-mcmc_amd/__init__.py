@@ -42,6 +42,9 @@ ALL_CHAINS = -1
 # (csrc/bisbm_kernels.hpp: kQueryCandTile, kQueryTile, kQueryMaxK), and the entry past a query's eligible candidates
 QUERY_CAND_TILE, QUERY_TILE, QUERY_MAX_K = 1024, 8, 1024
 QUERY_NONE = 0xFFFFFFFF
+# bisbm_coassign_*: candidates x queries of one workgroup of the counting kernel (csrc/bisbm_kernels.hpp: kCoassignCandTile,
+# kCoassignTile); the largest k of bisbm_coassign_topk is QUERY_MAX_K, an entry past the eligible nodes QUERY_NONE
+COASSIGN_CAND_TILE, COASSIGN_TILE = 1024, 16
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
 _u64p = C.POINTER(C.c_uint64)
@@ -101,6 +104,11 @@ ABI = {
     "bisbm_query_scores_reset": (C.c_int, [C.c_void_p]),
     "bisbm_query_scores_get_row": (C.c_int, [C.c_void_p, C.c_uint32, _f64p, _u64p]),
     "bisbm_query_scores_topk": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, _u32p, _f64p, _u64p]),
+    "bisbm_coassign_set": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
+    "bisbm_coassign_accumulate": (C.c_int, [C.c_void_p]),
+    "bisbm_coassign_reset": (C.c_int, [C.c_void_p]),
+    "bisbm_coassign_get_row": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u64p]),
+    "bisbm_coassign_topk": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p, _u64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
@@ -789,6 +797,59 @@ class BlockModel:
         nodes, sums, terms = self.query_topk(k, exclude_edges)
         return nodes, sums / terms, terms
 
+    # -- co-assignment (include/bisbm.h, "Co-assignment")
+    def coassign_set(self, queries):
+        """The nodes to find similar nodes for: an integer array [Q] of node ids of either type (they may repeat); replaces
+        earlier queries and zeroes the counts.  Every query gets a row of one uint32 per node of its own type on the device.
+        An empty array frees everything."""
+        q = np.asarray(queries)
+        if q.size == 0:
+            q = np.zeros(0, dtype=np.uint32)
+        if q.ndim != 1 or not np.issubdtype(q.dtype, np.integer):
+            raise ValueError("queries must be a one-dimensional integer array")
+        if len(q) and (q.min() < 0 or q.max() > 0xFFFFFFFF):
+            raise ValueError("a query is outside [0, 2^32)")
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        self._check(self._L.bisbm_coassign_set(self._h, len(q), _p(q, _u32p)))
+        self.coassign_queries = q.copy()
+
+    def coassign_accumulate(self):
+        """One sample: every counted chain adds 1 to every (query, node of its type) whose labels agree in that chain (with
+        replica exchange on, the chains on rung 0 only)."""
+        self._check(self._L.bisbm_coassign_accumulate(self._h))
+
+    def coassign_reset(self):
+        self._check(self._L.bisbm_coassign_reset(self._h))
+
+    def coassignment(self, i):
+        """(row uint32 [n_own], terms) of the i-th query: in how many of the `terms` counted (sample, chain) pairs every node
+        of its type shared its block, in id order (candidate j of a type-a query is node j, of a type-b query node na + j)."""
+        queries = getattr(self, "coassign_queries", np.zeros(0, dtype=np.uint32))
+        i = int(i)
+        if not 0 <= i < len(queries):
+            raise IndexError("query index %d: %d queries are set" % (i, len(queries)))
+        out = np.zeros(self.na if queries[i] < self.na else self.n - self.na, dtype=np.uint32)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_coassign_get_row(self._h, i, _p(out, _u32p), C.byref(terms)))
+        return out, terms.value
+
+    def coassign_topk(self, k):
+        """(nodes uint32 [Q, k], counts uint32 [Q, k], terms): every query's k nodes of its own type with the largest counts,
+        descending, ties to the lowest node id, selected on the device; the query node itself is never among them.  Entries
+        past the eligible nodes are 0xffffffff / 0."""
+        Q = len(getattr(self, "coassign_queries", ()))
+        nodes = np.zeros((Q, int(k)), dtype=np.uint32)
+        counts = np.zeros((Q, int(k)), dtype=np.uint32)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_coassign_topk(self._h, int(k), _p(nodes, _u32p), _p(counts, _u32p), C.byref(terms)))
+        return nodes, counts, terms.value
+
+    def similar(self, k):
+        """(nodes uint32 [Q, k], probability float64 [Q, k], terms): coassign_topk with count / terms, the estimate of the
+        posterior probability that the node shares the query's block."""
+        nodes, counts, terms = self.coassign_topk(k)
+        return nodes, counts / terms, terms
+
     # -- partition distances and posterior modes (include/bisbm.h, "Partition distances and posterior modes")
     def partition_distances(self, chains=None):
         """(vi float64 [m, m], H float64 [m]): the variation of information (nats) between every two of the selected chains'
@@ -974,5 +1035,5 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import ChainShard, numpy_pair_scores, numpy_query_topk, shard_chains  # noqa: E402,F401
+from .distributed import ChainShard, numpy_coassign, numpy_pair_scores, numpy_query_topk, shard_chains  # noqa: E402,F401
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

@@ -15,6 +15,7 @@
 //   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
 //   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains, top-k on the device; kernels and C ABI
+//   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block, top-k; kernels and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
 //
@@ -201,6 +202,27 @@ struct QueryScoreState {
     DeviceBuf<double> d_val;      // topk: [chunk][k] their sums
 };
 
+// Co-assignment (bisbm_coassign.hip).  As QueryScoreState: the counts belong to the engine that owns the graph on a device, the
+// container of device entries keeps the host side (n, q, off) only, the scratch of bisbm_coassign_topk is on the engine whose
+// device selects.
+struct CoassignState {
+    uint32_t n = 0;               // queries set (0: none)
+    uint32_t n_a = 0;             // ... of type a
+    uint32_t q_slots = 0;         // slots per chain in d_qlab: both types padded to whole query tiles
+    uint64_t terms = 0;           // counted (sample, chain) pairs since the last set / reset
+    std::vector<uint32_t> q;      // [n] node of every query, caller's order
+    std::vector<uint64_t> off;    // [n + 1] first cell of every query's row; off[n]: cells in all
+    DeviceBuf<uint32_t> d_q;      // [n] `q`
+    DeviceBuf<uint64_t> d_off;    // [n + 1] `off`
+    DeviceBuf<uint32_t> d_list;   // [n] indices of the type-a queries, then of the type-b queries, each ascending
+    DeviceBuf<uint32_t> d_slot;   // [q_slots] query index of every slot of d_qlab, 0xffffffff: padding
+    DeviceBuf<uint32_t> d_qlab;   // [chains of the engine sampled][q_slots] the queries' labels of one sample
+    DeviceBuf<uint32_t> d_count;  // [off[n]] counts, query by query, candidates in id order
+    DeviceBuf<uint32_t> d_rows, d_stage;  // topk over several devices: the chunk's rows added up, one device's part
+    DeviceBuf<uint32_t> d_node;   // topk: [chunk][k] selected nodes
+    DeviceBuf<uint32_t> d_val;    // topk: [chunk][k] their counts
+};
+
 // Partition distances (bisbm_partition.hip).  The scratch of the calls, on the engine whose device computes (a plain handle, the
 // container of shape groups, the first device entry); nothing of it outlives a call in meaning, it is only kept to be reused.
 struct PartitionState {
@@ -327,6 +349,7 @@ struct bisbm_engine {
     bisbm::TemperState temper;
     bisbm::PairScoreState pairs;
     bisbm::QueryScoreState queries;
+    bisbm::CoassignState coassign;
     bisbm::PartitionState partition;
     bisbm::ModeState modes;
 };

@@ -201,6 +201,48 @@ struct QuerySelectParams {
     double* sum_out;      // [n_q][k]
 };
 
+// Co-assignment (bisbm_coassign.hip): one sample of the chains of one engine into the rows of the queries of one type.  A
+// workgroup owns kCoassignCandTile candidates (nodes of the queries' own type) x kCoassignTile queries and adds 1 to a cell for
+// every counted chain in which candidate and query carry the same label.  The queries' labels come from `qlab`, which the
+// gather kernel fills once per sample: slot s of chain c holds the label of the query in slot s (type-a queries first, each
+// type padded to whole query tiles), with byte labels replicated into all four bytes of the word.
+struct CoassignParams {
+    uint32_t n, na, n_chains;
+    uint32_t type;            // 0: type-a queries (candidates 0 .. na-1), 1: type-b queries (candidates na .. n-1)
+    uint32_t n_list;          // queries of this type
+    uint32_t slot0, q_slots;  // first slot of this type and slots per chain in `qlab`
+    uint32_t cand_tiles, q_tile0;  // the launcher's: candidate tiles of the type, first query tile of the launch
+    int plain;                // byte labels: the extract-compare-add form instead of the packed one (the bench tool's A/B)
+    const uint32_t* list;     // [n_list] their indices in the caller's order
+    const uint64_t* off;      // [n_queries + 1] first cell of every query's row in `count`
+    const uint8_t* labels;    // [chain][label_stride] labels, one or two bytes each
+    size_t label_stride;      // in labels (a multiple of 4: a lane reads four candidates' labels as one or two words)
+    const uint32_t* rung;     // replica exchange: only chains with rung[c] == 0 are counted; NULL: every chain
+    const uint32_t* qlab;     // [chain][q_slots]
+    uint32_t* count;
+};
+constexpr uint32_t kCoassignCandTile = 1024;  // candidates per workgroup: 256 lanes, four labels each
+constexpr uint32_t kCoassignTile = 16;        // queries per workgroup
+// qlab[c][s] = label of node queries[slot[s]] in chain c (slot[s] = 0xffffffff: a padding slot, set to 0)
+struct CoassignGatherParams {
+    uint32_t n_chains, q_slots;
+    const uint32_t* slot;     // [q_slots] query index of every slot
+    const uint32_t* queries;  // [n_queries] node of every query
+    const uint8_t* labels;
+    size_t label_stride;
+    uint32_t* qlab;
+};
+// Selection of one chunk of queries (q0 .. q0 + n_q - 1): rows holds the chunk's cells from cell off[q0] on.  The query's own
+// node is the one candidate that is not eligible.
+struct CoassignSelectParams {
+    uint32_t n, na, q0, n_q, k;
+    const uint32_t* queries;
+    const uint64_t* off;
+    const uint32_t* rows;
+    uint32_t* node_out;   // [n_q][k] global node ids in rank order, 0xffffffff past the eligible ones
+    uint32_t* count_out;  // [n_q][k]
+};
+
 // agg_split (blockmodel.cc:505-565): evaluation of `n_trials` random half-cuts of every block of one type, all chains
 struct SplitParams {
     const uint32_t* rowptr;
@@ -332,6 +374,10 @@ hipError_t launch_query_scores(const QueryScoreParams& p, hipStream_t stream);
 hipError_t launch_query_mask(const uint32_t* rowptr, const uint32_t* col, const QuerySelectParams& p, uint8_t* mask, hipStream_t stream);
 hipError_t launch_query_select(const QuerySelectParams& p, hipStream_t stream);
 hipError_t launch_query_rows_add(double* a, const double* b, uint64_t count, hipStream_t stream);  // a += b
+hipError_t launch_coassign_gather(const CoassignGatherParams& p, bool wide, hipStream_t stream);
+hipError_t launch_coassign_count(const CoassignParams& p, bool wide, hipStream_t stream);
+hipError_t launch_coassign_select(const CoassignSelectParams& p, hipStream_t stream);
+hipError_t launch_coassign_rows_add(uint32_t* a, const uint32_t* b, uint64_t count, hipStream_t stream);  // a += b
 hipError_t launch_log_q_probe(const Tables& tab, const int32_t* n, const int32_t* k, size_t count, double* out,
                               int fast, hipStream_t stream);
 

@@ -228,3 +228,21 @@ def numpy_query_topk(row, k, excluded=()):
     idx[:len(order)] = order
     val[:len(order)] = row[order]
     return idx, val
+
+
+def numpy_coassign(labels_by_chain, queries, na):
+    """Host statement of one or more samples of bisbm_coassign_accumulate: `labels_by_chain` holds the n labels of every counted
+    (sample, chain) pair, in any order (the counts are integers).  Returns one uint32 row per query, in the queries' order (they
+    may repeat): over the nodes of the query's own type in id order (0 .. na-1 for q < na, na .. n-1 otherwise), in how many of
+    the given label vectors the node carries the query's label.  The query's own cell is the number of vectors."""
+    rows = []
+    for q in np.asarray(queries, dtype=np.int64):
+        q = int(q)
+        row = None
+        for lab in labels_by_chain:
+            lab = np.asarray(lab)
+            own = lab[:na] if q < na else lab[na:]
+            row = np.zeros(len(own), dtype=np.uint32) if row is None else row
+            row += (own == lab[q]).astype(np.uint32)
+        rows.append(row)
+    return rows

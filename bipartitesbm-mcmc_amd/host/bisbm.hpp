@@ -295,6 +295,26 @@ public:
         sums.assign(queries_.size() * (size_t)k, 0.);
         check(bisbm_query_scores_topk(h_, k, exclude_neighbours ? 1 : 0, nodes.data(), sums.data(), &terms));
     }
+    // co-assignment (include/bisbm.h): the query nodes (either type), a sample of every counted chain, one query's row over the
+    // nodes of its own type in id order, and every query's k most often co-assigned nodes selected on the device (nodes / counts
+    // [queries * k], 0xffffffff / 0 past the eligible ones; the estimate of an entry is count / terms)
+    void coassign_set(const std::vector<uint32_t>& queries) {
+        check(bisbm_coassign_set(h_, (uint32_t)queries.size(), queries.data()));
+        coassign_queries_ = queries;
+    }
+    void coassign_accumulate() { check(bisbm_coassign_accumulate(h_)); }
+    void coassign_reset() { check(bisbm_coassign_reset(h_)); }
+    std::vector<uint32_t> coassign_row(uint32_t query_index, uint64_t& terms) {
+        if (query_index >= coassign_queries_.size()) throw std::runtime_error("coassign_row: no such query");
+        std::vector<uint32_t> count(coassign_queries_[query_index] < na_ ? na_ : n_ - na_);
+        check(bisbm_coassign_get_row(h_, query_index, count.data(), &terms));
+        return count;
+    }
+    void coassign_topk(uint32_t k, std::vector<uint32_t>& nodes, std::vector<uint32_t>& counts, uint64_t& terms) {
+        nodes.assign(coassign_queries_.size() * (size_t)k, 0);
+        counts.assign(coassign_queries_.size() * (size_t)k, 0);
+        check(bisbm_coassign_topk(h_, k, nodes.data(), counts.data(), &terms));
+    }
     // rung of every chain under replica exchange (bisbm_tempering_get)
     std::vector<uint32_t> tempering_rungs() {
         std::vector<uint32_t> rung(n_chains_);
@@ -397,7 +417,7 @@ private:
     }
     bisbm_handle h_ = nullptr;
     size_t KA_, KB_, n_ = 0, na_ = 0, n_pairs_ = 0;
-    std::vector<uint32_t> queries_;
+    std::vector<uint32_t> queries_, coassign_queries_;
     uint32_t n_chains_;
     uint_vec_t memberships_;
 };

@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign.
+// --tempering, --exchange_every, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -50,6 +50,7 @@ const option_spec kOptions[] = {
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
     {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
     {"recommend", 0, 2},        {"include_edges", 0, 0},
+    {"similar", 0, 2},
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
 };
 
@@ -193,6 +194,12 @@ void print_help(const char* argv0) {
                  "                                        `query candidate score` lines in rank order (score descending, ties to\n"
                  "                                        the lowest id; score = the mean over samples and chains, %.17g).\n"
                  "  --include_edges                       With --recommend: the query's neighbours are ranked as well.\n"
+                 "  --similar QUERIES OUT K               With --marginalize: QUERIES holds one node id per line (either type);\n"
+                 "                                        every sample counts, for EVERY node of the query's own type, the\n"
+                 "                                        sampled chains in which it shares the query's block, and OUT receives\n"
+                 "                                        the K nodes that do so most often (the query itself left out) as\n"
+                 "                                        `query node probability` lines in rank order (count descending, ties\n"
+                 "                                        to the lowest id; probability = count / (samples x chains), %.17g).\n"
                  "  --modes OUT THRESHOLD                 With --marginalize: after the last sample the sampled chains' partitions\n"
                  "                                        are compared (variation of information, nats) and grouped into modes:\n"
                  "                                        chains joined by a path of pairs with VI <= THRESHOLD share a mode.  OUT\n"
@@ -264,6 +271,29 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
         recommend_k = (uint32_t)k;
+    }
+    if (count("similar") && !count("marginalize")) {
+        std::cerr << "--similar counts the chains in which nodes share a block over the samples of the chains: it needs --marginalize.\n";
+        return 1;
+    }
+    uint32_t similar_k = 0;
+    if (var_map.count("similar")) {
+        if (var_map["similar"].size() != 3) {
+            std::cerr << "Invalid --similar. Three arguments: the file of query nodes to read, the file to write and K.\n";
+            return 1;
+        }
+        const std::string tok = var_map["similar"][2];
+        char* end = nullptr;
+        const unsigned long k = std::strtoul(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0' || tok[0] == '-' || tok[0] == '+' || k == 0 || k > 0xffffffffUL) {
+            std::cerr << "Invalid --similar. K must be a positive integer, e.g. --similar queries.txt out.txt 10.\n";
+            return 1;
+        }
+        if (k > 1024) {  // (bisbm_coassign_topk's limit, known before a device is touched)
+            std::cerr << "Invalid --similar. K is at most 1024, the most nodes the selection on the device returns per query.\n";
+            return 1;
+        }
+        similar_k = (uint32_t)k;
     }
     double modes_threshold = 0.;
     if (var_map.count("modes") && !count("marginalize")) {
@@ -387,6 +417,30 @@ int main(int argc, char const* argv[]) {
                 return 1;
             }
             recommend_queries.push_back((uint32_t)id);
+        }
+    }
+    // --similar: likewise
+    std::vector<uint32_t> similar_queries;
+    if (var_map.count("similar")) {
+        const std::string in = var_map["similar"][0];
+        std::ifstream file(in);
+        if (!file) {
+            std::cerr << "[error] --similar: cannot read " << in << "\n";
+            return 1;
+        }
+        std::string text;
+        for (size_t line_no = 1; std::getline(file, text); ++line_no) {
+            const size_t b = text.find_first_not_of(" \t\r");
+            if (b == std::string::npos) continue;  // (an empty line)
+            const size_t e = text.find_last_not_of(" \t\r");
+            const std::string tok = text.substr(b, e - b + 1);
+            char* end = nullptr;
+            const unsigned long long id = std::strtoull(tok.c_str(), &end, 10);
+            if (*end != '\0' || tok[0] == '-' || tok[0] == '+' || id >= NA + NB) {
+                std::cerr << "[error] --similar: line " << line_no << " of " << in << " (" << tok << ") must name a node [0, " << NA + NB << ")\n";
+                return 1;
+            }
+            similar_queries.push_back((uint32_t)id);
         }
     }
     const std::string cooling_schedule = single("cooling_schedule", "abrupt_cool");
@@ -889,11 +943,17 @@ int main(int argc, char const* argv[]) {
                 for (uint32_t v : recommend_queries) q.push_back(new_id.empty() ? v : new_id[v]);
                 blockmodel.query_scores_set(q);
             }
+            if (!similar_queries.empty()) {
+                std::vector<uint32_t> q;
+                for (uint32_t v : similar_queries) q.push_back(new_id.empty() ? v : new_id[v]);
+                blockmodel.coassign_set(q);
+            }
             for (size_t sample = 0; sample < n_samples; ++sample) {
                 advance(sweeps_between);
                 blockmodel.marginals_accumulate();
                 if (!score_pairs.empty()) blockmodel.pair_scores_accumulate();
                 if (!recommend_queries.empty()) blockmodel.query_scores_accumulate();
+                if (!similar_queries.empty()) blockmodel.coassign_accumulate();
             }
             std::clog << "marginalize: burn-in " << burn_in / N << " sweeps, " << n_samples << " samples " << sweeps_between
                       << " sweep(s) apart, " << opt.n_chains << " chain(s) pooled\n";
@@ -957,6 +1017,31 @@ int main(int argc, char const* argv[]) {
                 }
                 std::clog << "recommend: " << recommend_queries.size() << " query node(s), " << recommend_k << " candidate(s) each, " << terms
                           << " chain term(s) per score -> " << out_path << "\n";
+            }
+            if (var_map.count("similar")) {
+                const std::string out_path = var_map["similar"][1];
+                std::ofstream out(out_path);
+                uint64_t terms = 0;
+                std::vector<uint32_t> nodes, counts;
+                if (!similar_queries.empty()) blockmodel.coassign_topk(similar_k, nodes, counts, terms);
+                std::vector<uint32_t> old_id(new_id.size());
+                for (size_t v = 0; v < new_id.size(); ++v) old_id[new_id[v]] = (uint32_t)v;
+                char line[128];
+                for (size_t i = 0; i < similar_queries.size(); ++i)
+                    for (size_t r = 0; r < similar_k; ++r) {
+                        const uint32_t node = nodes[i * similar_k + r];
+                        if (node == 0xffffffffu) continue;  // (fewer than K nodes are eligible)
+                        std::snprintf(line, sizeof(line), "%u %u %.17g\n", similar_queries[i], new_id.empty() ? node : old_id[node],
+                                      (double)counts[i * similar_k + r] / (double)terms);
+                        out << line;
+                    }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --similar: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "similar: " << similar_queries.size() << " query node(s), " << similar_k << " node(s) each, " << terms
+                          << " chain term(s) per count -> " << out_path << "\n";
             }
             uint_vec_t heaviest_labels;
             if (per_mode) {

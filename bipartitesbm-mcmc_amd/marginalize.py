@@ -17,7 +17,8 @@ import numpy as np
 
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
-                return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None):
+                return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
+                similar=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -47,7 +48,11 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     (sum, terms) afterwards, shard.pooled_pair_scores(model) the same over ranks.
     `recommend`: (queries, k) or (queries, k, exclude_edges) (include/bisbm.h, "Query scores"): the queries are set, with zeroed
     sums, before the first sample, every sample also adds every counted chain's term to every (query, candidate) sum, and the
-    return value becomes (labels, counts, model.recommend(k, exclude_edges)) -- the chains of this rank only."""
+    return value becomes (labels, counts, model.recommend(k, exclude_edges)) -- the chains of this rank only.
+    `similar`: (queries, k) (include/bisbm.h, "Co-assignment"): the queries are set, with zeroed counts, before the first sample,
+    every sample also counts in which chains every node of a query's own type shares its block, and model.similar(k) -- (nodes,
+    count / terms, terms) -- is appended as the last element of the return value.  The chains of this rank only: pooling over
+    ranks is out of scope."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
@@ -67,11 +72,17 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     if recommend is not None:
         model.query_scores_set(recommend[0])
         model.query_scores_reset()
+    if similar is not None:
+        model.coassign_set(similar[0])
+        model.coassign_reset()
 
     def result(labels, counts):
-        if recommend is None:
-            return labels, counts
-        return labels, counts, model.recommend(int(recommend[1]), bool(recommend[2]) if len(recommend) > 2 else True)
+        out = (labels, counts)
+        if recommend is not None:
+            out += (model.recommend(int(recommend[1]), bool(recommend[2]) if len(recommend) > 2 else True),)
+        if similar is not None:
+            out += (model.similar(int(similar[1])),)
+        return out
     if device_counts is None and not multi:
         # one rank, no caller buffer: the library's own histogram
         model.marginals_reset()
@@ -85,6 +96,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
                 model.pair_scores_accumulate()
             if recommend is not None:
                 model.query_scores_accumulate()
+            if similar is not None:
+                model.coassign_accumulate()
         counts = model.marginals_get().astype(np.int64)
         base = np.where(np.arange(n) >= model.na, model.KA, 0)
         return result((counts.argmax(axis=1) + base).astype(np.uint32), (counts if return_counts else None))
@@ -114,6 +127,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             model.pair_scores_accumulate()
         if recommend is not None:
             model.query_scores_accumulate()
+        if similar is not None:
+            model.coassign_accumulate()
     if not multi:
         from .distributed import _argmax_first
         arg = _argmax_first(device_counts)

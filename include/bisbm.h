@@ -27,7 +27,7 @@ extern "C" {
  *    partition distances and modes (bisbm_partition_*), mode-resolved marginals (bisbm_marginals_set_modes ...,
  *    bisbm_marginals_get_mode, bisbm_marginals_map_mode), distances to reference partitions (bisbm_partition_distances_to),
  *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
- *    (bisbm_query_scores_*).  Additions only. */
+ *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -306,6 +306,48 @@ int bisbm_query_scores_reset(bisbm_handle h);
 int bisbm_query_scores_get_row(bisbm_handle h, uint32_t query_index, double *sum_out /* n_other, host */, uint64_t *terms_out);
 int bisbm_query_scores_topk(bisbm_handle h, uint32_t k, int exclude_neighbours, uint32_t *node_out /* n_queries * k, host */,
                             double *sum_out /* n_queries * k, host, may be NULL */, uint64_t *terms_out);
+
+/* Co-assignment: for one node, how often every node of its OWN type shares its block (no reference counterpart).  The posterior
+ * co-assignment probability P(b_v = b_q | graph) is one row of the consensus (co-classification) matrix; the full n x n matrix
+ * is never formed.  A QUERY is a node q of either type; its CANDIDATES are all nodes of its own type in id order, q included:
+ * candidate j of a type-a query is node j (na of them), of a type-b query node na + j (nb of them).  A SAMPLE
+ * (bisbm_coassign_accumulate) adds, for every counted chain c and every candidate v, 1 to count[query][v] iff
+ * label_c(v) == label_c(q), and the number of counted chains to `terms`; counted = every chain, or with replica exchange on
+ * only the chains on rung 0 (the rule of bisbm_query_scores_accumulate; replica exchange over chains grouped by shape is
+ * BISBM_ERR_STATE).  The estimate of a cell is count / terms.  Label equality does not depend on how a chain numbers its
+ * blocks and needs no block tables: nothing is aligned, chains grouped by shape all count, both RNG modes, several devices and
+ * handles with two-byte labels (KA + KB > 256) are served, and counts survive merges, splits, regrouping by shape and the
+ * change from two-byte to byte labels.  Every result is an integer: count[q][q] == terms, count[q][v] == count[v][q] when both
+ * are queries, and a row adds up to the sum over the counted (sample, chain) pairs of n_r[label_c(q)].  Cells are uint32:
+ * accumulate refuses with BISBM_ERR_STATE and a message when terms plus the chains about to be counted would pass 2^32 - 1
+ * (over all devices together).  Several devices: each keeps the counts of its own chains, and they are added when they are
+ * read; integer adds are order-free, so several device entries give the bits of one handle.  Memory: 4 bytes per (query,
+ * candidate) per device, plus 4 bytes per (chain of the device, query) for the queries' labels of one sample.
+ * set: uploads n_queries nodes (they may repeat -- a repeated query has a row of its own -- and both types may be mixed),
+ *   replacing earlier ones, and allocates and zeroes the counts (an allocation that fails is BISBM_ERR_HIP with the size in the
+ *   message).  A query >= n is BISBM_ERR_INVALID_ARG, bisbm_last_error names the first offending index, and the earlier
+ *   queries stay in place.  n_queries = 0 frees everything.
+ * accumulate: one sample; BISBM_ERR_STATE before bisbm_init / bisbm_shuffle or without queries.
+ * reset: zeroes counts and terms, keeps the queries.
+ * get_row: the row of query `query_index` (its position in the array given to set) in candidate-id order; count_out or
+ *   terms_out may be NULL.
+ * topk: for every query the k nodes of its own type with the largest counts, THE QUERY NODE ITSELF NEVER ELIGIBLE (another
+ *   query row of the same node is a different row, but its node id is the same and is left out too), descending by count, ties
+ *   to the lowest node id, selected on the device: node_out[query][rank] holds global node ids, count_out (may be NULL) their
+ *   counts.  Nodes of count 0 are eligible and rank last, by id.  Where fewer than k nodes are eligible the remaining entries
+ *   are 0xffffffff and 0.  k = 0 is BISBM_ERR_INVALID_ARG; every k <= 1024 is served, a larger k is BISBM_ERR_UNSUPPORTED;
+ *   BISBM_ERR_STATE while terms == 0.  Several devices: the rows are added on the first device, a bounded chunk of queries at
+ *   a time, and selected there.
+ * Diagnostic switch: with byte labels the counting kernel compares four labels as one word and keeps byte-wide partial counts;
+ * the environment variable BISBM_COASSIGN_FORM=plain, read at every accumulate, selects the form that extracts, compares and
+ * adds every cell on its own instead (the A/B of tools/coassign_bench.py).  The counts are the same in both forms.
+ * Out of scope: pooling over processes (one process per GPU), the full n x n matrix, a consensus partition from the rows. */
+int bisbm_coassign_set(bisbm_handle h, uint32_t n_queries, const uint32_t *queries);
+int bisbm_coassign_accumulate(bisbm_handle h);
+int bisbm_coassign_reset(bisbm_handle h);
+int bisbm_coassign_get_row(bisbm_handle h, uint32_t query_index, uint32_t *count_out /* n_own, host */, uint64_t *terms_out);
+int bisbm_coassign_topk(bisbm_handle h, uint32_t k, uint32_t *node_out /* n_queries * k, host */,
+                        uint32_t *count_out /* n_queries * k, host, may be NULL */, uint64_t *terms_out);
 
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
