@@ -45,8 +45,13 @@ QUERY_NONE = 0xFFFFFFFF
 # bisbm_coassign_*: candidates x queries of one workgroup of the counting kernel (csrc/bisbm_kernels.hpp: kCoassignCandTile,
 # kCoassignTile); the largest k of bisbm_coassign_topk is QUERY_MAX_K, an entry past the eligible nodes QUERY_NONE
 COASSIGN_CAND_TILE, COASSIGN_TILE = 1024, 16
+# bisbm_foldin_*: the row kinds (BISBM_FOLDIN_RECOMMEND, BISBM_FOLDIN_SIMILAR) and candidates x virtual nodes of one workgroup of
+# the rows kernel (csrc/bisbm_kernels.hpp: kFoldinCandTile, kFoldinTile); the largest k of bisbm_foldin_topk is QUERY_MAX_K
+FOLDIN_RECOMMEND, FOLDIN_SIMILAR = 1, 2
+FOLDIN_CAND_TILE, FOLDIN_TILE = 1024, 8
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
+_u8p = C.POINTER(C.c_uint8)
 _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
@@ -109,6 +114,12 @@ ABI = {
     "bisbm_coassign_reset": (C.c_int, [C.c_void_p]),
     "bisbm_coassign_get_row": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u64p]),
     "bisbm_coassign_topk": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p, _u64p]),
+    "bisbm_foldin_set": (C.c_int, [C.c_void_p, C.c_uint32, _u8p, _u64p, _u32p, C.c_double, C.c_uint32]),
+    "bisbm_foldin_accumulate": (C.c_int, [C.c_void_p]),
+    "bisbm_foldin_reset": (C.c_int, [C.c_void_p]),
+    "bisbm_foldin_get_posteriors": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p]),
+    "bisbm_foldin_get_row": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p, _u64p]),
+    "bisbm_foldin_topk": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, _u32p, _f64p, _u64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
@@ -850,6 +861,90 @@ class BlockModel:
         nodes, counts, terms = self.coassign_topk(k)
         return nodes, counts / terms, terms
 
+    # -- fold-in queries (include/bisbm.h, "Fold-in queries")
+    def foldin_set(self, nodes, alpha=None, what=FOLDIN_RECOMMEND | FOLDIN_SIMILAR):
+        """The virtual nodes to fold in: a sequence of (type, neighbours) with type "a" / "b" (or 0 / 1) and neighbours a
+        non-empty sequence of ids of existing nodes of the OTHER type (they may repeat; the order is kept).  alpha: the
+        smoothing constant, by default the model's epsilon.  what: the row kinds to keep.  Replaces earlier virtual nodes and
+        zeroes the sums; an empty sequence frees everything."""
+        types, lists = [], []
+        for node in nodes:
+            t, ids = node
+            t = {"a": 0, "b": 1}.get(t, t)
+            if isinstance(t, str) or int(t) != t or not 0 <= int(t) <= 255:
+                raise ValueError("a virtual node's type must be 'a', 'b', 0 or 1")
+            ids = np.asarray(ids)
+            if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+                raise ValueError("a virtual node's neighbours must be a one-dimensional integer array")
+            if ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF):
+                raise ValueError("a neighbour is outside [0, 2^32)")
+            types.append(int(t))
+            lists.append(ids.astype(np.uint32))
+        t = np.ascontiguousarray(types, dtype=np.uint8)
+        ptr = np.zeros(len(lists) + 1, dtype=np.uint64)
+        ptr[1:] = np.cumsum([len(x) for x in lists])
+        flat = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), dtype=np.uint32)
+        alpha = self.epsilon if alpha is None else float(alpha)
+        self._check(self._L.bisbm_foldin_set(self._h, len(t), _p(t, _u8p), _p(ptr, _u64p), _p(flat, _u32p), alpha, int(what)))
+        self.foldin_types, self.foldin_lists = t.copy(), lists
+
+    def foldin_accumulate(self):
+        """One sample: every counted chain's block posterior of every virtual node, and its terms added to the kept rows chain by
+        chain in ascending order (with replica exchange on, the chains on rung 0 only)."""
+        self._check(self._L.bisbm_foldin_accumulate(self._h))
+
+    def foldin_reset(self):
+        self._check(self._L.bisbm_foldin_reset(self._h))
+
+    def _foldin_index(self, i):
+        types = getattr(self, "foldin_types", np.zeros(0, dtype=np.uint8))
+        i = int(i)
+        if not 0 <= i < len(types):
+            raise IndexError("virtual node %d: %d are set" % (i, len(types)))
+        return i, int(types[i])
+
+    def foldin_posteriors(self, i):
+        """float64 [n_chains, K_own]: the i-th virtual node's block posterior in every chain at the last sample (row c, column =
+        block within the node's type; K_own: the largest block count of that type among the chains, 0.0 past a chain's own;
+        NaN rows: chains that were not counted)."""
+        i, t = self._foldin_index(i)
+        stride = max(self.ka_kb(c)[t] for c in range(self.n_chains)) if self.mixed_shapes else (self.KB if t else self.KA)
+        out = np.zeros((self.n_chains, stride), dtype=np.float64)
+        self._check(self._L.bisbm_foldin_get_posteriors(self._h, i, stride, _p(out, _f64p)))
+        return out
+
+    def foldin_scores(self, i, what):
+        """(row float64, terms) of the i-th virtual node: what = FOLDIN_RECOMMEND: the sums over the nodes of the other type in id
+        order; FOLDIN_SIMILAR: over the nodes of its own type (candidate j of type a is node j, of type b node na + j)."""
+        i, t = self._foldin_index(i)
+        cand_b = (t == 0) if what == FOLDIN_RECOMMEND else (t == 1)
+        out = np.zeros(self.n - self.na if cand_b else self.na, dtype=np.float64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_foldin_get_row(self._h, int(what), i, _p(out, _f64p), C.byref(terms)))
+        return out, terms.value
+
+    def foldin_topk(self, what, k, exclude_listed=False):
+        """(nodes uint32 [Q, k], sums float64 [Q, k], terms): every virtual node's k best candidates of the rows of kind `what`,
+        descending, ties to the lowest node id, selected on the device; 0xffffffff / 0.0 past the eligible candidates."""
+        Q = len(getattr(self, "foldin_types", ()))
+        nodes = np.zeros((Q, int(k)), dtype=np.uint32)
+        sums = np.zeros((Q, int(k)), dtype=np.float64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_foldin_topk(self._h, int(what), int(k), 1 if exclude_listed else 0, _p(nodes, _u32p), _p(sums, _f64p), C.byref(terms)))
+        return nodes, sums, terms.value
+
+    def foldin_recommend(self, k, exclude_listed=True):
+        """(nodes, scores, terms): foldin_topk of the recommend rows with scores = sum / terms, the estimate of the expected number
+        of edges between the virtual node and the node; exclude_listed: the nodes of its list are not eligible."""
+        nodes, sums, terms = self.foldin_topk(FOLDIN_RECOMMEND, k, exclude_listed)
+        return nodes, sums / terms, terms
+
+    def foldin_similar(self, k):
+        """(nodes, probability, terms): foldin_topk of the similar rows with sum / terms, the estimate of the posterior
+        probability that the node shares the virtual node's block."""
+        nodes, sums, terms = self.foldin_topk(FOLDIN_SIMILAR, k, False)
+        return nodes, sums / terms, terms
+
     # -- partition distances and posterior modes (include/bisbm.h, "Partition distances and posterior modes")
     def partition_distances(self, chains=None):
         """(vi float64 [m, m], H float64 [m]): the variation of information (nats) between every two of the selected chains'
@@ -1035,5 +1130,6 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import ChainShard, numpy_coassign, numpy_pair_scores, numpy_query_topk, shard_chains  # noqa: E402,F401
+from .distributed import (ChainShard, numpy_coassign, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables,  # noqa: E402,F401
+                          numpy_pair_scores, numpy_query_topk, shard_chains)
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

@@ -16,6 +16,7 @@
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
 //   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains, top-k on the device; kernels and C ABI
 //   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block, top-k; kernels and C ABI
+//   bisbm_foldin.hip     fold-in queries: block posterior, recommendations and peers of a node that is not in the graph; kernels and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
 //
@@ -223,6 +224,41 @@ struct CoassignState {
     DeviceBuf<uint32_t> d_val;    // topk: [chunk][k] their counts
 };
 
+// Fold-in queries (bisbm_foldin.hip).  As QueryScoreState: the sums, the tables and the posteriors of the last sample belong to
+// the engine that owns the graph on a device, the container of device entries keeps the host side only, the scratch of
+// bisbm_foldin_topk is on the engine whose device selects.  A row kind that is not kept has no cells (its `off` is all 0).
+struct FoldinState {
+    uint32_t n = 0;               // virtual nodes set (0: none)
+    uint32_t n_a = 0;             // ... of type a
+    uint32_t what = 0;            // BISBM_FOLDIN_RECOMMEND | BISBM_FOLDIN_SIMILAR: the row kinds kept
+    double alpha = 0;
+    uint64_t terms = 0;           // chain terms added to every sum since the last set / reset
+    std::vector<uint8_t> type;    // [n] 0: a, 1: b, caller's order
+    std::vector<uint64_t> ptr;    // [n + 1] first list entry of every virtual node, caller's order
+    std::vector<uint32_t> list;   // the lists
+    std::vector<uint32_t> slot;   // [n] slot of every virtual node: the type-a ones in order, then the type-b ones
+    std::vector<uint64_t> off[2]; // [n + 1] first cell of every node's recommend / similar row
+    DeviceBuf<uint8_t> d_type;    // [n] `type`
+    DeviceBuf<uint64_t> d_ptr;    // [n + 1] `ptr`
+    DeviceBuf<uint32_t> d_nbr;    // `list`
+    DeviceBuf<uint32_t> d_order;  // [n] caller's index of every slot
+    DeviceBuf<uint64_t> d_off[2]; // `off`
+    DeviceBuf<double> d_sum[2];   // running sums of the recommend / similar rows
+    DeviceBuf<double> d_P;        // posteriors of the last sample: the segments below back to back
+    DeviceBuf<double> d_g;        // recommend tables of one chunk of chains
+    // the last sample's posteriors, one segment per leaf: chains ridx[..] of this engine, shape (ka, kb), from d_P[base] on
+    struct Segment {
+        uint32_t ka = 0, kb = 0;
+        size_t base = 0;
+        std::vector<uint32_t> chain;
+    };
+    std::vector<Segment> segments;
+    DeviceBuf<uint8_t> d_mask;    // topk: mask of the listed nodes of one chunk
+    DeviceBuf<double> d_rows, d_stage;  // topk over several devices: the chunk's rows added in device order, one device's part
+    DeviceBuf<uint32_t> d_node;   // topk: [chunk][k] selected nodes
+    DeviceBuf<double> d_val;      // topk: [chunk][k] their sums
+};
+
 // Partition distances (bisbm_partition.hip).  The scratch of the calls, on the engine whose device computes (a plain handle, the
 // container of shape groups, the first device entry); nothing of it outlives a call in meaning, it is only kept to be reused.
 struct PartitionState {
@@ -350,6 +386,7 @@ struct bisbm_engine {
     bisbm::PairScoreState pairs;
     bisbm::QueryScoreState queries;
     bisbm::CoassignState coassign;
+    bisbm::FoldinState foldin;
     bisbm::PartitionState partition;
     bisbm::ModeState modes;
 };

@@ -243,6 +243,63 @@ struct CoassignSelectParams {
     uint32_t* count_out;  // [n_q][k]
 };
 
+// Fold-in queries (bisbm_foldin.hip): virtual nodes given by a type and a list of neighbours of the other type.  The table kernel
+// turns every (counted chain, virtual node) into the node's block posterior P[k_own] and its recommend table g[k_oth]; the rows
+// kernel adds one table lookup per (virtual node, candidate) and chain onto the running sums, chain by chain in ascending order.
+// Slots: the type-a virtual nodes in the caller's order, then the type-b ones.  One chain's tables: the slots' rows back to back,
+// n_a * ka + n_b * kb doubles of P, n_a * kb + n_b * ka doubles of g.
+struct FoldinTableParams {
+    uint32_t na, ka, kb;
+    uint32_t chain0, n_chains;  // the chains of the launch: chain0 .. chain0 + n_chains - 1 of the engine
+    uint32_t n_q, n_a;          // slots, of which type a
+    uint32_t recommend;         // 0: only P is wanted
+    double alpha;
+    const uint32_t* order;      // [n_q] index of every slot's virtual node in the caller's order
+    const uint64_t* ptr;        // [n_q + 1] by caller's index: first list entry of every virtual node
+    const uint32_t* nbr;        // the lists, in the caller's order
+    const uint8_t* labels;      // byte labels
+    size_t label_stride;
+    const int32_t* m;           // [chain][ka*kb]
+    const int32_t* m_r;         // [chain][K]
+    const int32_t* n_r;         // [chain][K]
+    const uint32_t* rung;       // replica exchange: only chains with rung[c] == 0 are counted (the others: NaN rows of P); NULL: all
+    double* P;                  // [chain of the engine][n_a * ka + n_b * kb]
+    double* g;                  // [chain - chain0][n_a * kb + n_b * ka]
+};
+struct FoldinRowsParams {
+    uint32_t chain0, n_chains;  // as above
+    uint32_t first, n_cand;     // the candidates: nodes first .. first + n_cand - 1
+    uint32_t lab0, k_tab;       // first label and block count of the candidates' type: a table row has k_tab entries
+    uint32_t slot0, n_list;     // the slots of the virtual nodes' type
+    uint32_t cand_tiles, q_tile0;  // the launcher's: candidate tiles, first tile of virtual nodes of the launch
+    const uint32_t* order;      // [n_q] index of every slot's virtual node in the caller's order
+    const uint64_t* ptr;        // [n_q + 1] by caller's index: the list length is the virtual node's degree
+    const uint64_t* off;        // [n_queries + 1] by caller's index: first cell of the node's row in `sum`
+    const uint32_t* rowptr;
+    const uint8_t* labels;
+    size_t label_stride;        // (a multiple of 4: a lane reads four candidates' labels as one word)
+    const uint32_t* rung;
+    const double* tab;          // tables of chain chain0 on: tab[c * chain_stride + type_base + (slot - slot0) * k_tab + block]
+    size_t chain_stride, type_base;
+    double* sum;
+};
+constexpr uint32_t kFoldinCandTile = 1024;  // candidates per workgroup: 256 lanes, one word of 4 labels each
+constexpr uint32_t kFoldinTile = 8;         // virtual nodes per workgroup
+// Selection of one chunk of virtual nodes (q0 .. q0 + n_q - 1, caller's order) of one row kind: rows / mask hold the chunk's
+// cells from cell off[q0] on.
+struct FoldinSelectParams {
+    uint32_t n, na, q0, n_q, k;
+    uint32_t similar;         // the candidates are the nodes of the virtual node's own type (else: of the other type)
+    const uint8_t* type;      // [n_queries] 0: a, 1: b
+    const uint64_t* off;
+    const uint64_t* ptr;      // [n_queries + 1] by caller's index (the mask kernel's)
+    const uint32_t* nbr;
+    const double* rows;
+    const uint8_t* mask;      // 1: not eligible; NULL: every candidate is
+    uint32_t* node_out;       // [n_q][k] global node ids in rank order, 0xffffffff past the eligible ones
+    double* sum_out;          // [n_q][k]
+};
+
 // agg_split (blockmodel.cc:505-565): evaluation of `n_trials` random half-cuts of every block of one type, all chains
 struct SplitParams {
     const uint32_t* rowptr;
@@ -378,6 +435,10 @@ hipError_t launch_coassign_gather(const CoassignGatherParams& p, bool wide, hipS
 hipError_t launch_coassign_count(const CoassignParams& p, bool wide, hipStream_t stream);
 hipError_t launch_coassign_select(const CoassignSelectParams& p, hipStream_t stream);
 hipError_t launch_coassign_rows_add(uint32_t* a, const uint32_t* b, uint64_t count, hipStream_t stream);  // a += b
+hipError_t launch_foldin_tables(const FoldinTableParams& p, hipStream_t stream);
+hipError_t launch_foldin_rows(const FoldinRowsParams& p, bool recommend, hipStream_t stream);
+hipError_t launch_foldin_mask(const FoldinSelectParams& p, uint8_t* mask, hipStream_t stream);  // the listed nodes of a chunk (mask: zeroed)
+hipError_t launch_foldin_select(const FoldinSelectParams& p, hipStream_t stream);
 hipError_t launch_log_q_probe(const Tables& tab, const int32_t* n, const int32_t* k, size_t count, double* out,
                               int fast, hipStream_t stream);
 

@@ -246,3 +246,67 @@ def numpy_coassign(labels_by_chain, queries, na):
             row += (own == lab[q]).astype(np.uint32)
         rows.append(row)
     return rows
+
+
+def _foldin_blocks(m, m_r, n_r, ka, qtype):
+    """the block state as the virtual node's type sees it: (m [K_own, K_oth], m_r and n_r of its own blocks, m_r of the other type's)"""
+    m, m_r, n_r = np.asarray(m), np.asarray(m_r), np.asarray(n_r)
+    K, ka = len(m_r), int(ka)
+    a, b = np.arange(ka), np.arange(ka, K)
+    quad = m[np.ix_(a, b)]  # (the type-a row, type-b column quadrant the engine keeps)
+    if qtype:
+        return quad.T, m_r[b], n_r[b], m_r[a]
+    return quad, m_r[a], n_r[a], m_r[b]
+
+
+def numpy_foldin_posterior(labels, m, m_r, n_r, ka, qtype, neighbours, alpha):
+    """Host statement of steps 1 and 2 of the fold-in queries (include/bisbm.h, "Fold-in queries") for one chain and one virtual
+    node: the posterior P[K_own] over the blocks of its type, bit for bit what the device computes.  `labels`, `m`, `m_r`, `n_r`:
+    what get_memberships / get_m / get_m_r / get_n_r return for the chain (global labels, the full K x K matrix); `ka`: the
+    chain's type-a block count; `qtype`: 0 (a) or 1 (b); `neighbours`: the list, in order.  The blocks are taken side by side,
+    the list one entry after the other, which is the order of operations of every single block."""
+    labels = np.asarray(labels).astype(np.int64)
+    quad, mr, nr, mr_oth = _foldin_blocks(m, m_r, n_r, ka, qtype)
+    oth0 = 0 if qtype else int(ka)
+    alpha = float(alpha)
+    live = nr > 0
+    mant, ex = np.frexp(np.where(live, nr, 0).astype(np.float64))
+    ex = ex.astype(np.int64)
+    den = mr.astype(np.float64) + alpha * float(len(mr_oth))
+    for w in np.asarray(neighbours, dtype=np.int64):
+        x = (quad[:, labels[w] - oth0].astype(np.float64) + alpha) / den
+        mant = mant * x
+        mant, e2 = np.frexp(mant)
+        ex = ex + e2
+    rel = np.where(live, ex - ex[live].max(), 0)
+    wgt = np.where(live & (rel >= -1000), np.ldexp(mant, np.maximum(rel, -1000).astype(np.int32)), 0.0)
+    Z = float(wgt[0])
+    for x in wgt[1:]:
+        Z = Z + float(x)
+    return wgt / Z
+
+
+def numpy_foldin_tables(labels, m, m_r, n_r, ka, qtype, neighbours, alpha):
+    """(P [K_own], g [K_oth]): the posterior of numpy_foldin_posterior and the recommend table of step 3, the sum over the
+    virtual node's blocks taken in ascending order for all blocks of the other type side by side."""
+    P = numpy_foldin_posterior(labels, m, m_r, n_r, ka, qtype, neighbours, alpha)
+    quad, mr, nr, mr_oth = _foldin_blocks(m, m_r, n_r, ka, qtype)
+    acc = np.zeros(len(mr_oth), dtype=np.float64)
+    for r in range(len(mr)):
+        if mr[r] == 0 or P[r] == 0.0:
+            continue
+        acc = acc + (P[r] * quad[r].astype(np.float64)) / float(mr[r])
+    g = np.zeros(len(mr_oth), dtype=np.float64)
+    has = mr_oth != 0
+    g[has] = acc[has] / mr_oth[has].astype(np.float64)
+    return P, g
+
+
+def numpy_foldin_rows(labels, deg, na, ka, qtype, d_q, P, g):
+    """(recommend row, similar row) of one chain (step 4): the terms of all nodes of the other type and of the virtual node's own
+    type, each in id order.  `deg`: the degree of every node; `d_q`: the length of the virtual node's list."""
+    labels, deg = np.asarray(labels).astype(np.int64), np.asarray(deg)
+    a, b = slice(0, na), slice(na, len(labels))
+    own, oth, own0, oth0 = (b, a, int(ka), 0) if qtype else (a, b, 0, int(ka))
+    rec = (float(d_q) * deg[oth].astype(np.float64)) * np.asarray(g)[labels[oth] - oth0]
+    return rec, np.asarray(P)[labels[own] - own0].astype(np.float64)

@@ -315,6 +315,41 @@ public:
         counts.assign(coassign_queries_.size() * (size_t)k, 0);
         check(bisbm_coassign_topk(h_, k, nodes.data(), counts.data(), &terms));
     }
+    // fold-in queries (include/bisbm.h): virtual nodes given by a type (0: a, 1: b) and a list of neighbours of the other type; a
+    // sample of every counted chain; one node's block posterior per chain at the last sample ([n_chains * stride]); one node's
+    // row of kind `what` (BISBM_FOLDIN_RECOMMEND: over the other type's nodes, BISBM_FOLDIN_SIMILAR: over its own type's); every
+    // node's k best candidates of one kind selected on the device (the estimate of an entry is sum / terms)
+    void foldin_set(const std::vector<uint8_t>& types, const std::vector<std::vector<uint32_t>>& lists, double alpha,
+                    uint32_t what = BISBM_FOLDIN_RECOMMEND | BISBM_FOLDIN_SIMILAR) {
+        if (types.size() != lists.size()) throw std::runtime_error("foldin_set: one list per virtual node");
+        std::vector<uint64_t> ptr(1, 0);
+        std::vector<uint32_t> flat;
+        for (auto const& l : lists) {
+            flat.insert(flat.end(), l.begin(), l.end());
+            ptr.push_back(flat.size());
+        }
+        check(bisbm_foldin_set(h_, (uint32_t)types.size(), types.data(), ptr.data(), flat.data(), alpha, what));
+        foldin_types_ = types;
+    }
+    void foldin_accumulate() { check(bisbm_foldin_accumulate(h_)); }
+    void foldin_reset() { check(bisbm_foldin_reset(h_)); }
+    std::vector<double> foldin_posteriors(uint32_t query_index, uint32_t stride) {
+        std::vector<double> p((size_t)n_chains_ * stride);
+        check(bisbm_foldin_get_posteriors(h_, query_index, stride, p.data()));
+        return p;
+    }
+    std::vector<double> foldin_row(uint32_t what, uint32_t query_index, uint64_t& terms) {
+        if (query_index >= foldin_types_.size()) throw std::runtime_error("foldin_row: no such virtual node");
+        const bool cand_b = what == BISBM_FOLDIN_RECOMMEND ? foldin_types_[query_index] == 0 : foldin_types_[query_index] != 0;
+        std::vector<double> sum(cand_b ? n_ - na_ : na_);
+        check(bisbm_foldin_get_row(h_, what, query_index, sum.data(), &terms));
+        return sum;
+    }
+    void foldin_topk(uint32_t what, uint32_t k, bool exclude_listed, std::vector<uint32_t>& nodes, std::vector<double>& sums, uint64_t& terms) {
+        nodes.assign(foldin_types_.size() * (size_t)k, 0);
+        sums.assign(foldin_types_.size() * (size_t)k, 0.);
+        check(bisbm_foldin_topk(h_, what, k, exclude_listed ? 1 : 0, nodes.data(), sums.data(), &terms));
+    }
     // rung of every chain under replica exchange (bisbm_tempering_get)
     std::vector<uint32_t> tempering_rungs() {
         std::vector<uint32_t> rung(n_chains_);
@@ -418,6 +453,7 @@ private:
     bisbm_handle h_ = nullptr;
     size_t KA_, KB_, n_ = 0, na_ = 0, n_pairs_ = 0;
     std::vector<uint32_t> queries_, coassign_queries_;
+    std::vector<uint8_t> foldin_types_;
     uint32_t n_chains_;
     uint_vec_t memberships_;
 };

@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar.
+// --tempering, --exchange_every, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -21,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <set>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <atomic>
@@ -51,6 +52,7 @@ const option_spec kOptions[] = {
     {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
     {"recommend", 0, 2},        {"include_edges", 0, 0},
     {"similar", 0, 2},
+    {"foldin", 0, 2},           {"foldin_alpha", 0, 1},
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
 };
 
@@ -200,6 +202,16 @@ void print_help(const char* argv0) {
                  "                                        the K nodes that do so most often (the query itself left out) as\n"
                  "                                        `query node probability` lines in rank order (count descending, ties\n"
                  "                                        to the lowest id; probability = count / (samples x chains), %.17g).\n"
+                 "  --foldin QUERIES OUT K                With --marginalize and --foldin_alpha: QUERIES holds one node that is NOT\n"
+                 "                                        in the graph per line, `a|b id id id ...`: its type and its neighbours,\n"
+                 "                                        nodes of the other type (ids as in the edge list file; they may repeat).\n"
+                 "                                        Every sample gives it a block posterior in every sampled chain; OUT\n"
+                 "                                        receives, per line of QUERIES, `line recommend node score` for the K\n"
+                 "                                        nodes of the other type with the largest expected edge count (the listed\n"
+                 "                                        ones left out), then `line similar node probability` for the K nodes of\n"
+                 "                                        its own type most likely to share its block (means over samples and\n"
+                 "                                        chains, %.17g; lines count from 0, empty lines not counted).\n"
+                 "  --foldin_alpha A                      With --foldin: the smoothing constant of the block posterior, A > 0.\n"
                  "  --modes OUT THRESHOLD                 With --marginalize: after the last sample the sampled chains' partitions\n"
                  "                                        are compared (variation of information, nats) and grouped into modes:\n"
                  "                                        chains joined by a path of pairs with VI <= THRESHOLD share a mode.  OUT\n"
@@ -294,6 +306,44 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
         similar_k = (uint32_t)k;
+    }
+    if ((count("foldin") || count("foldin_alpha")) && !count("marginalize")) {
+        std::cerr << "--foldin folds nodes that are not in the graph into the samples of the chains: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("foldin_alpha") && !count("foldin")) {
+        std::cerr << "--foldin_alpha sets the smoothing constant of the fold-in queries: it needs --foldin.\n";
+        return 1;
+    }
+    uint32_t foldin_k = 0;
+    double foldin_alpha = 0.;
+    if (var_map.count("foldin")) {
+        if (var_map["foldin"].size() != 3) {
+            std::cerr << "Invalid --foldin. Three arguments: the file of virtual nodes to read, the file to write and K.\n";
+            return 1;
+        }
+        const std::string tok = var_map["foldin"][2];
+        char* end = nullptr;
+        const unsigned long k = std::strtoul(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0' || tok[0] == '-' || tok[0] == '+' || k == 0 || k > 0xffffffffUL) {
+            std::cerr << "Invalid --foldin. K must be a positive integer, e.g. --foldin new_nodes.txt out.txt 10.\n";
+            return 1;
+        }
+        if (k > 1024) {  // (bisbm_foldin_topk's limit, known before a device is touched)
+            std::cerr << "Invalid --foldin. K is at most 1024, the most nodes the selection on the device returns per row.\n";
+            return 1;
+        }
+        foldin_k = (uint32_t)k;
+        if (!count("foldin_alpha")) {
+            std::cerr << "--foldin needs --foldin_alpha A, the smoothing constant of the block posterior (A > 0; the model's -E epsilon is a usual choice).\n";
+            return 1;
+        }
+        const std::string a = single("foldin_alpha", "");
+        foldin_alpha = std::strtod(a.c_str(), &end);
+        if (a.empty() || *end != '\0' || !std::isfinite(foldin_alpha) || !(foldin_alpha > 0.)) {
+            std::cerr << "Invalid --foldin_alpha. A finite number > 0, e.g. --foldin_alpha 0.1.\n";
+            return 1;
+        }
     }
     double modes_threshold = 0.;
     if (var_map.count("modes") && !count("marginalize")) {
@@ -441,6 +491,50 @@ int main(int argc, char const* argv[]) {
                 return 1;
             }
             similar_queries.push_back((uint32_t)id);
+        }
+    }
+    // --foldin: the virtual nodes are read and checked before any device is touched (ids as in the edge list file)
+    std::vector<uint8_t> foldin_types;
+    std::vector<std::vector<uint32_t>> foldin_lists;
+    if (var_map.count("foldin")) {
+        const std::string in = var_map["foldin"][0];
+        std::ifstream file(in);
+        if (!file) {
+            std::cerr << "[error] --foldin: cannot read " << in << "\n";
+            return 1;
+        }
+        std::string text;
+        for (size_t line_no = 1; std::getline(file, text); ++line_no) {
+            std::istringstream words(text);
+            std::string tok;
+            if (!(words >> tok)) continue;  // (an empty line)
+            if (tok != "a" && tok != "b") {
+                std::cerr << "[error] --foldin: line " << line_no << " of " << in << " must begin with the node's type, a or b (found " << tok << ")\n";
+                return 1;
+            }
+            const bool type_b = tok == "b";
+            std::vector<uint32_t> ids;
+            while (words >> tok) {
+                char* end = nullptr;
+                const unsigned long long id = std::strtoull(tok.c_str(), &end, 10);
+                if (*end != '\0' || tok[0] == '-' || tok[0] == '+') {
+                    std::cerr << "[error] --foldin: line " << line_no << " of " << in << ": " << tok << " is not a node id\n";
+                    return 1;
+                }
+                if (type_b ? id >= NA : (id < NA || id >= NA + NB)) {
+                    std::cerr << "[error] --foldin: line " << line_no << " of " << in << ": the neighbours of a type-" << (type_b ? "b" : "a")
+                              << " node are type-" << (type_b ? "a" : "b") << " nodes [" << (type_b ? 0 : NA) << ", " << (type_b ? NA : NA + NB)
+                              << "), " << tok << " is not\n";
+                    return 1;
+                }
+                ids.push_back((uint32_t)id);
+            }
+            if (ids.empty()) {
+                std::cerr << "[error] --foldin: line " << line_no << " of " << in << " names no neighbour\n";
+                return 1;
+            }
+            foldin_types.push_back(type_b ? 1 : 0);
+            foldin_lists.push_back(ids);
         }
     }
     const std::string cooling_schedule = single("cooling_schedule", "abrupt_cool");
@@ -948,9 +1042,17 @@ int main(int argc, char const* argv[]) {
                 for (uint32_t v : similar_queries) q.push_back(new_id.empty() ? v : new_id[v]);
                 blockmodel.coassign_set(q);
             }
+            if (!foldin_types.empty()) {  // (--reorder: the engine knows the nodes by their new ids)
+                std::vector<std::vector<uint32_t>> lists = foldin_lists;
+                if (!new_id.empty())
+                    for (auto& l : lists)
+                        for (uint32_t& v : l) v = new_id[v];
+                blockmodel.foldin_set(foldin_types, lists, foldin_alpha);
+            }
             for (size_t sample = 0; sample < n_samples; ++sample) {
                 advance(sweeps_between);
                 blockmodel.marginals_accumulate();
+                if (!foldin_types.empty()) blockmodel.foldin_accumulate();
                 if (!score_pairs.empty()) blockmodel.pair_scores_accumulate();
                 if (!recommend_queries.empty()) blockmodel.query_scores_accumulate();
                 if (!similar_queries.empty()) blockmodel.coassign_accumulate();
@@ -1042,6 +1144,36 @@ int main(int argc, char const* argv[]) {
                 }
                 std::clog << "similar: " << similar_queries.size() << " query node(s), " << similar_k << " node(s) each, " << terms
                           << " chain term(s) per count -> " << out_path << "\n";
+            }
+            if (var_map.count("foldin")) {
+                const std::string out_path = var_map["foldin"][1];
+                std::ofstream out(out_path);
+                uint64_t terms = 0;
+                std::vector<uint32_t> old_id(new_id.size());
+                for (size_t v = 0; v < new_id.size(); ++v) old_id[new_id[v]] = (uint32_t)v;
+                std::vector<uint32_t> nodes[2];
+                std::vector<double> sums[2];
+                if (!foldin_types.empty()) {
+                    blockmodel.foldin_topk(BISBM_FOLDIN_RECOMMEND, foldin_k, true, nodes[0], sums[0], terms);
+                    blockmodel.foldin_topk(BISBM_FOLDIN_SIMILAR, foldin_k, false, nodes[1], sums[1], terms);
+                }
+                char line[128];
+                for (size_t i = 0; i < foldin_types.size(); ++i)
+                    for (int kind = 0; kind < 2; ++kind)
+                        for (size_t r = 0; r < foldin_k; ++r) {
+                            const uint32_t node = nodes[kind][i * foldin_k + r];
+                            if (node == 0xffffffffu) continue;  // (fewer than K nodes are eligible)
+                            std::snprintf(line, sizeof(line), "%zu %s %u %.17g\n", i, kind ? "similar" : "recommend", new_id.empty() ? node : old_id[node],
+                                          sums[kind][i * foldin_k + r] / (double)terms);
+                            out << line;
+                        }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --foldin: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "foldin: " << foldin_types.size() << " virtual node(s), " << foldin_k << " node(s) per row, alpha " << foldin_alpha << ", "
+                          << terms << " chain term(s) per sum -> " << out_path << "\n";
             }
             uint_vec_t heaviest_labels;
             if (per_mode) {

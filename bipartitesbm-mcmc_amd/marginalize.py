@@ -18,7 +18,7 @@ import numpy as np
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
-                similar=None):
+                similar=None, foldin=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -52,7 +52,11 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     `similar`: (queries, k) (include/bisbm.h, "Co-assignment"): the queries are set, with zeroed counts, before the first sample,
     every sample also counts in which chains every node of a query's own type shares its block, and model.similar(k) -- (nodes,
     count / terms, terms) -- is appended as the last element of the return value.  The chains of this rank only: pooling over
-    ranks is out of scope."""
+    ranks is out of scope.
+    `foldin`: (nodes, k) or (nodes, k, alpha) (include/bisbm.h, "Fold-in queries"; nodes as model.foldin_set takes them): the
+    virtual nodes are set, with zeroed sums, before the first sample, every sample also adds every counted chain's terms to their
+    rows, and (model.foldin_recommend(k), model.foldin_similar(k)) is appended as the last element of the return value.  The
+    chains of this rank only."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
@@ -75,6 +79,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     if similar is not None:
         model.coassign_set(similar[0])
         model.coassign_reset()
+    if foldin is not None:
+        model.foldin_set(foldin[0], foldin[2] if len(foldin) > 2 else None)
 
     def result(labels, counts):
         out = (labels, counts)
@@ -82,6 +88,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             out += (model.recommend(int(recommend[1]), bool(recommend[2]) if len(recommend) > 2 else True),)
         if similar is not None:
             out += (model.similar(int(similar[1])),)
+        if foldin is not None:
+            out += ((model.foldin_recommend(int(foldin[1])), model.foldin_similar(int(foldin[1]))),)
         return out
     if device_counts is None and not multi:
         # one rank, no caller buffer: the library's own histogram
@@ -98,6 +106,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
                 model.query_scores_accumulate()
             if similar is not None:
                 model.coassign_accumulate()
+            if foldin is not None:
+                model.foldin_accumulate()
         counts = model.marginals_get().astype(np.int64)
         base = np.where(np.arange(n) >= model.na, model.KA, 0)
         return result((counts.argmax(axis=1) + base).astype(np.uint32), (counts if return_counts else None))
@@ -129,6 +139,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             model.query_scores_accumulate()
         if similar is not None:
             model.coassign_accumulate()
+        if foldin is not None:
+            model.foldin_accumulate()
     if not multi:
         from .distributed import _argmax_first
         arg = _argmax_first(device_counts)

@@ -27,7 +27,7 @@ extern "C" {
  *    partition distances and modes (bisbm_partition_*), mode-resolved marginals (bisbm_marginals_set_modes ...,
  *    bisbm_marginals_get_mode, bisbm_marginals_map_mode), distances to reference partitions (bisbm_partition_distances_to),
  *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
- *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*).  Additions only. */
+ *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -348,6 +348,68 @@ int bisbm_coassign_reset(bisbm_handle h);
 int bisbm_coassign_get_row(bisbm_handle h, uint32_t query_index, uint32_t *count_out /* n_own, host */, uint64_t *terms_out);
 int bisbm_coassign_topk(bisbm_handle h, uint32_t k, uint32_t *node_out /* n_queries * k, host */,
                         uint32_t *count_out /* n_queries * k, host, may be NULL */, uint64_t *terms_out);
+
+/* Fold-in queries: block posterior, recommendations and peers of a node that is NOT in the graph (no reference counterpart).
+ * A VIRTUAL NODE q has a type (a or b) and a neighbour list w_0 .. w_{d-1}, d >= 1: ids of existing nodes of the OTHER type, which
+ * may repeat and whose order is kept; d_q = d.  alpha > 0 is the caller's smoothing constant (the engine's proposals use the
+ * model's epsilon in the same place).  For one counted chain c with labels b, quadrant m, block sums m_r and n_r, K_own blocks of
+ * the virtual node's type and K_oth of the other (r, s: block indices within their types), everything in f64 with the
+ * operations and in the order written here, without a fused multiply-add; there is no log or exp, only multiplies, one divide
+ * per factor, frexp and ldexp, so a sequential host loop reproduces every number bit for bit:
+ *   1. block weights, for every r with n_r[r] > 0: (mant, ex) = frexp((double)n_r[r]); for j = 0 .. d-1 in list order, with
+ *      s = b[w_j]: x = ((double)m[r][s] + alpha) / ((double)m_r[r] + alpha * (double)K_oth); mant = mant * x;
+ *      (mant, e2) = frexp(mant); ex += e2.  Blocks with n_r[r] == 0 have weight 0.
+ *   2. posterior: E = max ex_r over the blocks of step 1; w_r = (ex_r - E < -1000) ? 0.0 : ldexp(mant_r, ex_r - E);
+ *      Z = w_0 + w_1 + ... added in ascending r, one add at a time; P_c(r) = w_r / Z.
+ *   3. recommend table, per block s of the other type: acc = the sum over ascending r of (P_c(r) * (double)m[r][s]) /
+ *      (double)m_r[r], the blocks with m_r[r] == 0 or P_c(r) == 0.0 skipped; g_c[s] = acc / (double)m_r[s], 0.0 when m_r[s] == 0.
+ *   4. cells.  RECOMMEND row: the candidates are all nodes v of the other type in id order, the term is
+ *      ((double)d_q * (double)d(v)) * g_c[b_v], 0.0 when d(v) == 0 -- the term of bisbm_query_scores_* averaged over the block
+ *      posterior.  SIMILAR row: the candidates are all nodes v of the virtual node's own type in id order, the term is P_c(b_v)
+ *      -- the count of bisbm_coassign_* as a probability.
+ *   5. a SAMPLE (bisbm_foldin_accumulate) adds the term of every counted chain onto sum[q][v], one chain at a time in ascending
+ *      chain index with one f64 add each (chains grouped by shape: group by group in group order), and the number of counted
+ *      chains to `terms`; counted = every chain, or with replica exchange on only the chains on rung 0.  Several devices: each
+ *      keeps the sums of its own chains, and they are added in device order when they are read.
+ * One chain's terms of a recommend row add up to d_q times the sum of P_c(r) over the blocks with m_r[r] > 0, of a similar row
+ * to the sum of P_c(r) n_r[r], up to rounding.  Neither depends on how a chain numbers its blocks: nothing is aligned, both
+ * RNG modes, chains grouped by shape, several devices and replica exchange are served; replica exchange over chains grouped by
+ * shape is BISBM_ERR_STATE and a handle with two-byte labels BISBM_ERR_UNSUPPORTED at accumulate.  Sums and terms survive
+ * merges, splits and regrouping.
+ * set: replaces earlier virtual nodes and zeroes sums and terms; n_queries = 0 frees everything (the other arguments are not
+ *   looked at).  list_ptr[0] = 0, list_ptr[i + 1] - list_ptr[i] = the length of node i's list.  `what`: the row kinds to keep.
+ *   BISBM_ERR_INVALID_ARG, bisbm_last_error naming the first offending query and position, the earlier virtual nodes staying
+ *   in place: an empty list, a list entry that is not a node of the other type, alpha not finite or <= 0, what == 0 or with
+ *   an unknown bit, a type above 1.  Memory: 8 bytes per (virtual node, candidate) per kept row kind per device; nothing is
+ *   capped or subsampled; an allocation that fails is BISBM_ERR_HIP with the size in the message.
+ * accumulate: one sample; BISBM_ERR_STATE before bisbm_init / bisbm_shuffle or without virtual nodes.  Scratch per device: the
+ *   posteriors of the sample, 8 bytes per (chain, virtual node, block of its type), kept for get_posteriors; the recommend tables,
+ *   8 bytes per (chain, virtual node, block of the other type), for as many chains at a time as fit 256 MiB (at least one).
+ * reset: zeroes sums and terms and forgets the last sample's posteriors; keeps the virtual nodes.
+ * get_posteriors: P_c(.) of the LAST sample for every chain of the handle in handle chain order, p_out[c * stride + r], padded
+ *   with 0.0 up to stride; a chain that was not counted has a row of NaN (the convention of
+ *   bisbm_marginals_get_mode_assignment).  A stride below some chain's K_own is BISBM_ERR_INVALID_ARG; BISBM_ERR_STATE before
+ *   the first sample.
+ * get_row: the row of kind `what` (exactly one kept kind, else BISBM_ERR_INVALID_ARG) of virtual node `query_index` in
+ *   candidate-id order; sum_out or terms_out may be NULL.
+ * topk: for every virtual node the k best candidates of the rows of kind `what`, descending by sum, ties to the lowest node
+ *   id, selected exactly on the device, with the semantics of bisbm_query_scores_topk (k = 0 BISBM_ERR_INVALID_ARG, k <= 1024
+ *   else BISBM_ERR_UNSUPPORTED, 0xffffffff / 0.0 past the eligible candidates, BISBM_ERR_STATE while terms == 0).  With
+ *   exclude_listed != 0 and what == RECOMMEND the nodes of the virtual node's list are not eligible; for SIMILAR exclude_listed
+ *   must be 0 (a virtual node has no id of its own to leave out).
+ * Out of scope: a block posterior pooled over chains (it needs alignment), neighbours of the virtual node's own type, pooling
+ * over processes, two-byte labels. */
+#define BISBM_FOLDIN_RECOMMEND 1u
+#define BISBM_FOLDIN_SIMILAR 2u
+int bisbm_foldin_set(bisbm_handle h, uint32_t n_queries, const uint8_t *type /* 0 = a, 1 = b */,
+                     const uint64_t *list_ptr /* n_queries + 1 */, const uint32_t *list /* node ids */, double alpha,
+                     uint32_t what /* bit mask of the rows to keep */);
+int bisbm_foldin_accumulate(bisbm_handle h);
+int bisbm_foldin_reset(bisbm_handle h);
+int bisbm_foldin_get_posteriors(bisbm_handle h, uint32_t query_index, uint32_t stride, double *p_out /* n_chains * stride */);
+int bisbm_foldin_get_row(bisbm_handle h, uint32_t what, uint32_t query_index, double *sum_out, uint64_t *terms_out);
+int bisbm_foldin_topk(bisbm_handle h, uint32_t what, uint32_t k, int exclude_listed, uint32_t *node_out /* n_queries * k */,
+                      double *sum_out /* n_queries * k, may be NULL */, uint64_t *terms_out);
 
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
