@@ -100,6 +100,11 @@ ABI = {
     "bisbm_tempering_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, _f64p]),
     "bisbm_tempering_get": (C.c_int, [C.c_void_p, _u32p, _f32p]),
     "bisbm_tempering_stats": (C.c_int, [C.c_void_p, _u64p, _u64p, _u64p]),
+    "bisbm_population_offspring": (C.c_int, [C.c_uint32, _f64p, C.c_double, C.c_double, _u32p, _u32p, _f64p]),
+    "bisbm_population_resample": (C.c_int, [C.c_void_p, C.c_double, C.c_double, _u32p, _f64p]),
+    "bisbm_population_run": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, C.c_uint64, _f64p, _u32p, _f64p]),
+    "bisbm_population_get": (C.c_int, [C.c_void_p, _u32p, _u64p, _f64p]),
+    "bisbm_population_reset": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_set": (C.c_int, [C.c_void_p, C.c_uint64, _u32p, _u32p]),
     "bisbm_pair_scores_accumulate": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_reset": (C.c_int, [C.c_void_p]),
@@ -578,6 +583,37 @@ class BlockModel:
         rounds = C.c_uint64()
         self._check(self._L.bisbm_tempering_stats(self._h, _p(att, _u64p), _p(acc, _u64p), C.byref(rounds)))
         return att, acc, rounds.value
+
+    # -- population annealing (include/bisbm.h, "Population annealing")
+    def population_resample(self, beta_from, beta_to):
+        """One resampling step of all chains from inverse temperature beta_from to beta_to >= beta_from: every dead slot takes
+        its parent's state.  Returns (parent uint32 [n_chains], the step's estimate of ln Z(beta_to) / Z(beta_from))."""
+        parent = np.zeros(self.n_chains, dtype=np.uint32)
+        lr = C.c_double()
+        self._check(self._L.bisbm_population_resample(self._h, float(beta_from), float(beta_to), _p(parent, _u32p), C.byref(lr)))
+        return parent, lr.value
+
+    def population_run(self, temps, sweeps_per_step):
+        """For every temperature after the first: a resampling step from the one before, then `sweeps_per_step` sweeps of every
+        chain at it.  The caller has equilibrated the chains at temps[0].  Returns {"log_ratio" f64 [steps], "distinct" uint32
+        [steps] (distinct ancestors after every step), "rates" f64 [n_chains]}."""
+        T = validate_population_temps(temps)
+        lr = np.zeros(len(T) - 1, dtype=np.float64)
+        distinct = np.zeros(len(T) - 1, dtype=np.uint32)
+        rates = np.zeros(self.n_chains, dtype=np.float64)
+        self._check(self._L.bisbm_population_run(self._h, len(T), _p(T, _f32p), int(sweeps_per_step), _p(lr, _f64p),
+                                                 _p(distinct, _u32p), _p(rates, _f64p)))
+        return {"log_ratio": lr, "distinct": distinct, "rates": rates}
+
+    def population_state(self):
+        """{"ancestor" uint32 [n_chains], "rounds", "log_ratio_total"} since the last population_reset."""
+        anc = np.zeros(self.n_chains, dtype=np.uint32)
+        rounds, tot = C.c_uint64(), C.c_double()
+        self._check(self._L.bisbm_population_get(self._h, _p(anc, _u32p), C.byref(rounds), C.byref(tot)))
+        return {"ancestor": anc, "rounds": rounds.value, "log_ratio_total": tot.value}
+
+    def population_reset(self):
+        self._check(self._L.bisbm_population_reset(self._h))
 
     def counts_device(self):
         """torch device a caller-owned marginal histogram must live on."""
@@ -1104,6 +1140,52 @@ def validate_ladder(ladder):
         if i and t < lad[i - 1]:
             raise ValueError("ladder[%d] = %s < ladder[%d] = %s: the ladder must be non-decreasing" % (i, vals[i], i - 1, vals[i - 1]))
     return lad
+
+
+def validate_population_temps(temps):
+    """The temperatures of a population run as float32 (what the library runs), or ValueError: at least 2, each finite and > 0
+    as a float32, non-increasing."""
+    try:
+        vals = [float(x) for x in temps]
+    except (TypeError, ValueError):
+        raise ValueError("the temperatures must be a sequence of numbers")
+    if len(vals) < 2:
+        raise ValueError("a population run needs at least 2 temperatures, got %d" % len(vals))
+    with np.errstate(over="ignore"):
+        T = np.asarray(vals, dtype=np.float32)
+    for i, t in enumerate(T):
+        if not (np.isfinite(t) and t > 0):
+            raise ValueError("temps[%d] = %s: every temperature must be finite and > 0" % (i, vals[i]))
+        if i and t > T[i - 1]:
+            raise ValueError("temps[%d] = %s > temps[%d] = %s: the temperatures must be non-increasing" % (i, vals[i], i - 1, vals[i - 1]))
+    return T
+
+
+def population_offspring(S, delta_beta, u):
+    """Offspring counts, parent map and log ratio of one resampling step on the host (bisbm_population_offspring): description
+    lengths S [C], delta_beta >= 0, one uniform u in [0, 1) -> (offspring uint32 [C], parent uint32 [C], log_ratio).  Needs no
+    device."""
+    s = np.ascontiguousarray(S, dtype=np.float64).ravel()
+    off = np.zeros(max(len(s), 1), dtype=np.uint32)
+    parent = np.zeros(max(len(s), 1), dtype=np.uint32)
+    lr = C.c_double()
+    rc = lib().bisbm_population_offspring(len(s), _p(s, _f64p), float(delta_beta), float(u), _p(off, _u32p), _p(parent, _u32p), C.byref(lr))
+    if rc != BISBM_OK:
+        raise BisbmError(rc, (lib().bisbm_last_error(None) or b"").decode())
+    return off[: len(s)], parent[: len(s)], lr.value
+
+
+def population_anneal(model, temps, sweeps_per_step, burn_in_sweeps=0):
+    """Population annealing of all chains of `model`: `burn_in_sweeps` sweeps at temps[0], then BlockModel.population_run.
+    Returns its dict plus "entropy" (the description length of every chain at the end) and "best_chain" (its argmin, ties ->
+    the lowest chain)."""
+    T = validate_population_temps(temps)
+    if int(burn_in_sweeps) > 0:
+        model.run_sweeps(int(burn_in_sweeps), float(T[0]))
+    out = model.population_run(T, sweeps_per_step)
+    out["entropy"] = model.entropy()
+    out["best_chain"] = int(np.argmin(out["entropy"]))
+    return out
 
 
 def _fmt_g6(x):

@@ -13,6 +13,7 @@
 //   bisbm_align.hip      aligned marginal samples: every counted chain renumbered to the reference of its mode, then counted (the
 //                        overlap, assignment and counting kernels; one mode of every chain: the pooled aligned histogram)
 //   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
+//   bisbm_population.hip  population annealing: offspring counts on the host, the kernel that copies chain states between slots
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
 //   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains, top-k on the device; kernels and C ABI
 //   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block, top-k; kernels and C ABI
@@ -168,6 +169,16 @@ struct TemperState {
     DeviceBuf<uint32_t> d_at;               // [ensemble][L] the chain (index in the engine) on every rung
     DeviceBuf<float> d_ladder;              // L temperatures
     DeviceBuf<unsigned long long> d_stats;  // [2][L - 1] attempted, accepted exchanges per rung pair
+};
+
+// Population annealing (bisbm_population.hip).  The genealogy and the running totals belong to the handle the caller holds; the
+// job list belongs to the engines that run the copy kernel (a plain handle, a device entry).
+struct PopulationState {
+    std::vector<uint32_t> ancestor;  // [n_chains] chain of the last reset every slot's state descends from; empty: the identity
+    uint64_t rounds = 0;             // resampling steps since the last reset: the index of the next step's Philox draw
+    double log_ratio_total = 0;      // running sum of the steps' log ratios
+    // kernel-running engine
+    DeviceBuf<uint2> d_jobs;         // [dead slots of the engine] (dead slot, parent), indices in the engines of the launch
 };
 
 // Pair scores (bisbm_pair_scores.hip).  The buffers belong to the engine that owns the graph on a device (a plain handle, the
@@ -383,6 +394,7 @@ struct bisbm_engine {
     uint64_t counts_rows = 0;  // rows of the internal marginal buffer (n, or n rounded up to a multiple of the device count)
     bisbm::AlignState align;
     bisbm::TemperState temper;
+    bisbm::PopulationState population;
     bisbm::PairScoreState pairs;
     bisbm::QueryScoreState queries;
     bisbm::CoassignState coassign;
@@ -416,6 +428,23 @@ int fail(bisbm_engine* h, int code, const char* fmt, ...) __attribute__((format(
 void free_chain_arrays(bisbm_engine* h);
 void free_all(bisbm_engine* h);
 void mt_seed_host(uint32_t* mt, uint64_t seed);  // std::mt19937(seed): seed mod 2^32
+// phx_draw and u53 of bisbm_device.hpp on the host: the same integers
+inline void philox_host(uint64_t seed, uint32_t chain, uint32_t purpose, uint64_t idx, uint32_t out[4]) {
+    uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32), c2 = chain, c3 = purpose;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+inline double u53_host(uint32_t hi, uint32_t lo) { return (double)((((uint64_t)hi << 32) | lo) >> 11) * 0x1.0p-53; }
 inline void forget_pass_speeds(bisbm_engine* h) { h->passes.reset(); }
 int rebuild_state(bisbm_engine* h);
 // block-state part of entropy() of every chain into d_out (n_chains doubles on the device), on the handle's stream, no sync

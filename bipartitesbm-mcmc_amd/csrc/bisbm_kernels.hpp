@@ -328,6 +328,7 @@ struct SplitParams {
 };
 constexpr uint32_t PHX_SPLIT = 6;
 constexpr uint32_t PHX_EXCHANGE = 7;  // replica exchange: idx = round * L + lower rung, chain = the ensemble's first global id
+constexpr uint32_t PHX_RESAMPLE = 8;  // population annealing: idx = resampling step, chain = the handle's first global id
 
 hipError_t launch_split_rank(const SplitParams& p, hipStream_t stream);
 hipError_t launch_split_eval(const SplitParams& p, hipStream_t stream);

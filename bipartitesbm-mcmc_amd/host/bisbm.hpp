@@ -261,6 +261,27 @@ public:
         accepted.assign(L - 1, 0);
         check(bisbm_tempering_stats(h_, attempted.data(), accepted.data(), &rounds));
     }
+    // population annealing (include/bisbm.h): one resampling step (the parent of every slot, the step's log ratio); a run over
+    // non-increasing temperatures (log ratio and distinct ancestors per step, acceptance rate per chain); the genealogy
+    std::vector<uint32_t> population_resample(double beta_from, double beta_to, double& log_ratio) {
+        std::vector<uint32_t> parent(n_chains_);
+        check(bisbm_population_resample(h_, beta_from, beta_to, parent.data(), &log_ratio));
+        return parent;
+    }
+    void population_run(const std::vector<float>& temps, uint64_t sweeps_per_step, std::vector<double>& log_ratio,
+                        std::vector<uint32_t>& distinct, std::vector<double>& rates) {
+        const size_t steps = temps.empty() ? 0 : temps.size() - 1;
+        log_ratio.assign(steps, 0.);
+        distinct.assign(steps, 0);
+        rates.assign(n_chains_, 0.);
+        check(bisbm_population_run(h_, (uint32_t)temps.size(), temps.data(), sweeps_per_step, log_ratio.data(), distinct.data(), rates.data()));
+    }
+    std::vector<uint32_t> population_state(uint64_t& rounds, double& log_ratio_total) {
+        std::vector<uint32_t> ancestor(n_chains_);
+        check(bisbm_population_get(h_, ancestor.data(), &rounds, &log_ratio_total));
+        return ancestor;
+    }
+    void population_reset() { check(bisbm_population_reset(h_)); }
     // pair scores (include/bisbm.h): the pairs (u of type a, v of type b), a sample of every counted chain, the sums and the
     // number of chain terms in them (the estimate of a pair is sum / terms)
     void pair_scores_set(const std::vector<uint32_t>& u, const std::vector<uint32_t>& v) {

@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha.
+// --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -50,6 +50,7 @@ const option_spec kOptions[] = {
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
     {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
+    {"population", 0, 2},       {"population_sweeps", 0, 1},
     {"recommend", 0, 2},        {"include_edges", 0, 0},
     {"similar", 0, 2},
     {"foldin", 0, 2},           {"foldin_alpha", 0, 1},
@@ -185,6 +186,15 @@ void print_help(const char* argv0) {
                  "                                        temperatures, and only the chains at T0 are sampled.  The swap\n"
                  "                                        acceptance of every rung pair is reported on stderr.\n"
                  "  --exchange_every arg (=1)             With --tempering: sweeps between exchange rounds.\n"
+                 "  --population arg                      Population annealing over temperatures T0 >= ... >= TL (at least 2, each\n"
+                 "                                        > 0; Philox mode) in place of the -c / -a schedule: every chain runs\n"
+                 "                                        --population_sweeps sweeps at T0; then, for every further temperature,\n"
+                 "                                        the --chains are resampled by description length (chains with a high\n"
+                 "                                        one are replaced by copies of chains with a low one) and run that many\n"
+                 "                                        sweeps at it.  Prints the chain of the lowest description length; the\n"
+                 "                                        log ratio ln Z(1/T_k) / Z(1/T_{k-1}) and the distinct ancestors of every\n"
+                 "                                        step, and the total, are reported on stderr.\n"
+                 "  --population_sweeps arg (=1)          With --population: sweeps per temperature.\n"
                  "  --score_pairs IN OUT                  With --marginalize: IN holds one pair `u v` per line (u of type a, v of\n"
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
@@ -409,6 +419,53 @@ int main(int argc, char const* argv[]) {
                 return 1;
             }
             exchange_every = (uint32_t)k;
+        }
+    }
+    // population annealing: the temperatures and the sweeps per temperature are checked before anything else runs (one more
+    // refusal, an initial partition without the -z block counts, waits below until the partition has been read: before the
+    // ka != KA branch, which would merge down to -z instead of running the population)
+    std::vector<float> population;
+    uint64_t population_sweeps = 1;
+    if (count("population_sweeps") && !count("population")) {
+        std::cerr << "--population_sweeps sets the sweeps per temperature of a population run: it needs --population.\n";
+        return 1;
+    }
+    if (count("population")) {
+        if (count("marginalize")) {
+            std::cerr << "--population anneals the chains and prints the best one: it cannot be combined with --marginalize. For marginals of an annealed "
+                         "population use the Python interface: population_anneal, then marginalize with no burn-in.\n";
+            return 1;
+        }
+        for (const std::string& tok : var_map["population"]) {
+            char* end = nullptr;
+            const float T = std::strtof(tok.c_str(), &end);
+            if (tok.empty() || *end != '\0' || !std::isfinite(T) || !(T > 0.f) || (!population.empty() && T > population.back())) {
+                population.clear();
+                break;
+            }
+            population.push_back(T);
+        }
+        if (population.size() < 2) {
+            std::cerr << "Invalid --population. At least 2 finite temperatures > 0 that do not rise, e.g. --population 4 2.5 1.5 1.\n";
+            return 1;
+        }
+        if (count("population_sweeps")) {
+            const std::string v = single("population_sweeps", "1");
+            char* end = nullptr;
+            const unsigned long long k = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || v[0] == '-' || v[0] == '+') {
+                std::cerr << "Invalid --population_sweeps. Sweeps per temperature: an integer >= 0.\n";
+                return 1;
+            }
+            population_sweeps = k;
+        }
+        if (count("merge")) {
+            std::cerr << "--population replaces the cooling schedule of the annealing run: it cannot be combined with --merge.\n";
+            return 1;
+        }
+        if (single("rng", count("seed") ? "mt19937-compat" : "philox") != "philox") {  // (-d alone selects mt19937-compat)
+            std::cerr << "--population runs in Philox mode only (mt19937-compat is the reference's verification path): add --rng philox.\n";
+            return 1;
         }
     }
     if (count("edge_list_path") == 0) {
@@ -940,6 +997,10 @@ int main(int argc, char const* argv[]) {
         return 0;
     }
     if (ka != KA || kb != KB) {  // the initial partition has other block counts than asked for (:419-450)
+        if (!population.empty()) {
+            std::cerr << "--population replaces the cooling schedule of the annealing run: the initial partition must have the -z block counts.\n";
+            return 1;
+        }
         try {
             int diff_a = (int)ka - (int)KA, diff_b = (int)kb - (int)KB;
             blockmodel_t blockmodel(memberships_init, types_init, ka + kb, ka, kb, epsilon, &adj_list, opt);
@@ -1282,6 +1343,35 @@ int main(int argc, char const* argv[]) {
         else
             blockmodel.init_bisbm();
         metropolis_hasting algorithm;
+        if (!population.empty()) {
+            // population annealing in place of the cooling schedule: the sweeps at T0, then a resampling step and the sweeps per
+            // further temperature
+            const float_vec_t t0{population[0], 0.f};
+            if (population_sweeps) algorithm.anneal(blockmodel, &constant_schedule, t0, population_sweeps * (NA + NB), (size_t)1 << 60);
+            std::vector<double> log_ratio, rates;
+            std::vector<uint32_t> distinct;
+            blockmodel.population_run(population, population_sweeps, log_ratio, distinct, rates);
+            char line[160];
+            for (size_t k = 0; k < log_ratio.size(); ++k) {
+                std::snprintf(line, sizeof(line), "population step %zu: T %g -> %g, log ratio %.17g, distinct ancestors %u\n", k + 1,
+                              (double)population[k], (double)population[k + 1], log_ratio[k], distinct[k]);
+                std::clog << line;
+            }
+            uint64_t rounds = 0;
+            double total = 0.;
+            blockmodel.population_state(rounds, total);
+            std::snprintf(line, sizeof(line), "population: %llu steps, log ratio total %.17g\n", (unsigned long long)rounds, total);
+            std::clog << line;
+            uint32_t best = 0;
+            const std::vector<double> dl = blockmodel.entropy_all();
+            for (uint32_t c = 1; c < opt.n_chains; ++c)
+                if (dl[c] < dl[best]) best = c;
+            std::clog << "chains " << opt.n_chains << ", printing chain " << best << "\n";
+            std::clog << "acceptance ratio " << rates[best] << "\n";
+            blockmodel.summary(best);
+            emit_labels(*blockmodel.get_memberships(best));
+            return 0;
+        }
         schedule_fn fn = cooling_schedule == "exponential"   ? &exponential_schedule
                          : cooling_schedule == "linear"      ? &linear_schedule
                          : cooling_schedule == "logarithmic" ? &logarithmic_schedule

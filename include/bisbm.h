@@ -27,7 +27,8 @@ extern "C" {
  *    partition distances and modes (bisbm_partition_*), mode-resolved marginals (bisbm_marginals_set_modes ...,
  *    bisbm_marginals_get_mode, bisbm_marginals_map_mode), distances to reference partitions (bisbm_partition_distances_to),
  *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
- *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*).  Additions only. */
+ *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*), population annealing
+ *    (bisbm_population_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -235,6 +236,59 @@ int bisbm_tempering_get(bisbm_handle h, uint32_t *rung_of_chain, float *T_of_cha
 /* attempted[L - 1] / accepted[L - 1] exchanges of rung pair (i, i + 1) and the rounds run since bisbm_tempering_set; any pointer
  * may be NULL. */
 int bisbm_tempering_stats(bisbm_handle h, uint64_t *attempted, uint64_t *accepted, uint64_t *rounds);
+
+/* Population annealing (Hukushima & Iba 2003, Machta 2010; no reference counterpart: the reference runs one chain).  The
+ * population is all C chains of the handle, over every device of it, all at one temperature; between temperature steps it is
+ * resampled by description length, and sweeps at the new temperature then decorrelate the copies.  One resampling step from
+ * beta_from to beta_to, D = beta_to - beta_from >= 0 (all f64, in exactly this order of operations):
+ *  1. S_c = the description length of chain c: the double bisbm_entropy returns.
+ *  2. S_min = min_c S_c; w_c = exp(-D * (S_c - S_min)) with the host's exp; c_k = w_0 + ... + w_k added in ascending c;
+ *     W = c_{C-1}.
+ *  3. log_ratio = -D * S_min + log(W / C): the step's estimate of ln Z(beta_to) / Z(beta_from).
+ *  4. Offspring counts by systematic resampling with ONE uniform u in [0, 1): a_k = min(C, (C * c_k) / W) for k < C - 1,
+ *     a_{C-1} = C exactly, a_{-1} = 0; n_k = ceil(a_k - u) - ceil(a_{k-1} - u), where ceil(a - u) is taken exactly as
+ *     floor(a) + [a - floor(a) > u] (the f64 subtraction a - u itself would round: 513 - (1 - 2^-53) is 512).  The min is
+ *     needed: where the trailing weights vanish beside W (a large D), c_k == W before the last slot and the rounded
+ *     (C * W) / W can be C + 1 ulp, which u = 0 would round up to C + 1.  a_k does not fall with k and stays in [0, C], so
+ *     every n_k >= 0 and sum n_k = C for every u in [0, 1); D = 0 gives n_k = 1 for every k.
+ *  5. The parent map, in place: a survivor (n_k >= 1) keeps its slot, parent[k] = k; the dead slots (n_k = 0) in ascending
+ *     order take the surplus copies, dealt out survivor by survivor in ascending k, n_k - 1 each (numpy: parent[dead] =
+ *     repeat(arange(C), maximum(n - 1, 0))).  A source is never overwritten, so nothing is staged.
+ *  6. Every dead slot d takes the state of chain parent[d]: the label row, m, m_r, n_r, eta and the running sum of dS
+ *     (bisbm_get_cum_dS), bit for bit.  Slot d keeps what keys and counts ITS random streams and its acceptance bookkeeping
+ *     (the sweep, shuffle, merge and split counters, accu_r, the last_* and stop_* values): the copies of one parent diverge
+ *     at the next sweep, and no stream is ever replayed.
+ *  7. u = the 53-bit uniform of the first two words of Philox(seed, counter (round, the handle's first global chain id, purpose
+ *     8 = resample)); round = the resampling steps of this handle since the last bisbm_population_reset.
+ *  8. ancestor[c] (c at the last reset) becomes ancestor[parent[c]]; log_ratio_total adds up the steps' log_ratio; rounds
+ *     counts the steps.
+ * Started from a population equilibrated at beta_0, log_ratio_total estimates ln Z(beta_L) - ln Z(beta_0), Z(beta) = sum over
+ * partitions of exp(-beta S), and the share of the final population in a mode estimates that mode's posterior mass.
+ * Refused, with a message and nothing changed: mt19937-compat mode and two-byte labels (a wide handle) BISBM_ERR_UNSUPPORTED;
+ * chains grouped by shape, replica exchange on, static modes set (bisbm_marginals_set_modes; anchored modes are served)
+ * BISBM_ERR_STATE; D < 0 or not finite, temperatures that rise BISBM_ERR_INVALID_ARG.  Not served: populations over several
+ * processes, adaptive temperature steps, other resampling schemes, weighted (non-resampled) estimators. */
+
+/* Steps 2-5 on the host, without a device: S[n] -> offspring_out[n], parent_out[n], *log_ratio_out (any of them may be NULL).
+ * BISBM_ERR_INVALID_ARG (text: bisbm_last_error(NULL)): n = 0, S that is not finite, delta_beta < 0 or not finite, u outside
+ * [0, 1). */
+int bisbm_population_offspring(uint32_t n, const double *S, double delta_beta, double u,
+                               uint32_t *offspring_out, uint32_t *parent_out, double *log_ratio_out);
+/* One resampling step of the handle's chains (steps 1-8). */
+int bisbm_population_resample(bisbm_handle h, double beta_from, double beta_to,
+                              uint32_t *parent_out /* n_chains, may be NULL */, double *log_ratio_out);
+/* temps: n_temps >= 2 float temperatures, finite, > 0, non-increasing; the caller has equilibrated the population at temps[0].
+ * For k = 1 .. n_temps - 1: a resampling step from 1 / (double)temps[k - 1] to 1 / (double)temps[k], then sweeps_per_step
+ * sweeps of every chain at temps[k] (bisbm_anneal with BISBM_SCHED_CONSTANT and no early stop; 0: none).  log_ratio_out[k - 1]:
+ * the step's log_ratio; distinct_out[k - 1]: distinct values in `ancestor` after the step (C minus it: the family collapse);
+ * acc_rate_out[c]: accepted steps / steps of the run's sweeps.  Any output may be NULL. */
+int bisbm_population_run(bisbm_handle h, uint32_t n_temps, const float *temps, uint64_t sweeps_per_step,
+                         double *log_ratio_out /* n_temps-1 */, uint32_t *distinct_out /* n_temps-1 */,
+                         double *acc_rate_out /* n_chains, may be NULL */);
+/* The genealogy and the totals since the last reset (ancestor_out: n_chains entries; any pointer may be NULL). */
+int bisbm_population_get(bisbm_handle h, uint32_t *ancestor_out, uint64_t *rounds_out, double *log_ratio_total_out);
+/* ancestor = the identity, rounds = 0, log_ratio_total = 0.  The chains are not touched. */
+int bisbm_population_reset(bisbm_handle h);
 
 /* The marginal estimate README.md:49-53 asks for: the most frequent block of every node over all samples of all chains (ties ->
  * the lowest block), n labels in the reference's numbering, from the internal histogram.  Over several devices this is the
