@@ -49,6 +49,8 @@ COASSIGN_CAND_TILE, COASSIGN_TILE = 1024, 16
 # the rows kernel (csrc/bisbm_kernels.hpp: kFoldinCandTile, kFoldinTile); the largest k of bisbm_foldin_topk is QUERY_MAX_K
 FOLDIN_RECOMMEND, FOLDIN_SIMILAR = 1, 2
 FOLDIN_CAND_TILE, FOLDIN_TILE = 1024, 8
+# bisbm_conditionals_*: the bit of `what` that keeps the last sample's rows
+COND_KEEP_LAST = 1
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -125,6 +127,13 @@ ABI = {
     "bisbm_foldin_get_posteriors": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p]),
     "bisbm_foldin_get_row": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p, _u64p]),
     "bisbm_foldin_topk": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, _u32p, _f64p, _u64p]),
+    "bisbm_conditionals_set": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_double, C.c_uint32]),
+    "bisbm_conditionals_set_reference": (C.c_int, [C.c_void_p, _u32p]),
+    "bisbm_conditionals_accumulate": (C.c_int, [C.c_void_p]),
+    "bisbm_conditionals_reset": (C.c_int, [C.c_void_p]),
+    "bisbm_conditionals_get_stats": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p, _u64p, _u64p]),
+    "bisbm_conditionals_get_marginals": (C.c_int, [C.c_void_p, _f64p, _u32p, _u64p]),
+    "bisbm_conditionals_get_last": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p, _f64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
@@ -981,6 +990,79 @@ class BlockModel:
         nodes, sums, terms = self.foldin_topk(FOLDIN_SIMILAR, k, False)
         return nodes, sums / terms, terms
 
+    # -- node conditionals (include/bisbm.h, "Node conditionals")
+    def conditionals_set(self, nodes=None, beta=1.0, keep_last=False):
+        """The nodes whose full conditional P(b_v = s | all other labels) ~ exp(-beta dS(v -> s)) is evaluated: a sequence of
+        node ids of either type (they may repeat), None: every node in id order.  keep_last: keep the dS and P rows of the last
+        sample per chain (conditionals_last).  Replaces earlier queries, zeroes the sums and forgets the reference; an empty
+        sequence frees everything."""
+        if nodes is None:
+            q, nq, ptr = np.arange(self.n, dtype=np.uint32), self.n, None
+        else:
+            q = np.asarray(nodes)
+            if q.ndim != 1 or (q.size and not np.issubdtype(q.dtype, np.integer)):
+                raise ValueError("the queries must be a one-dimensional integer array")
+            if q.size and (q.min() < 0 or q.max() > 0xFFFFFFFF):
+                raise ValueError("a query is outside [0, 2^32)")
+            q = np.ascontiguousarray(q, dtype=np.uint32)
+            nq, ptr = len(q), _p(q, _u32p)
+        self._check(self._L.bisbm_conditionals_set(self._h, nq, ptr, float(beta), COND_KEEP_LAST if keep_last else 0))
+        self.conditional_queries = q.copy()
+
+    def conditionals_set_reference(self, labels):
+        """The reference partition (n labels) every chain is aligned to before its conditional rows go into the soft marginals;
+        None clears it.  Either way the soft marginals start afresh."""
+        if labels is None:
+            self._check(self._L.bisbm_conditionals_set_reference(self._h, None))
+            return
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        if lab.shape != (self.n,):
+            raise ValueError("the reference must hold n labels")
+        self._check(self._L.bisbm_conditionals_set_reference(self._h, _p(lab, _u32p)))
+
+    def conditionals_accumulate(self):
+        """One sample: every counted chain's conditional of every query, its terms added to the kept sums chain by chain in
+        ascending order (with replica exchange on, the chains on rung 0 only).  Chain state is only read."""
+        self._check(self._L.bisbm_conditionals_accumulate(self._h))
+
+    def conditionals_reset(self):
+        self._check(self._L.bisbm_conditionals_reset(self._h))
+
+    def conditionals_stats(self):
+        """{"stay", "entropy", "margin": float64 [Q] sums over the counted chains, "free": uint64 [Q], "terms": int}: divide stay
+        and entropy by terms, margin by free (the chains in which the node was not alone in its block)."""
+        Q = len(getattr(self, "conditional_queries", ()))
+        stay, ent, mar = (np.zeros(Q, dtype=np.float64) for _ in range(3))
+        free = np.zeros(Q, dtype=np.uint64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_conditionals_get_stats(self._h, _p(stay, _f64p), _p(ent, _f64p), _p(mar, _f64p), _p(free, _u64p), C.byref(terms)))
+        return {"stay": stay, "entropy": ent, "margin": mar, "free": free, "terms": terms.value}
+
+    def conditionals_marginals(self):
+        """(prob float64 [Q, kmax], terms): the soft marginals -- every counted chain's conditional row added through its
+        alignment to the reference; column = block within the query's type.  Needs conditionals_set_reference."""
+        Q = len(getattr(self, "conditional_queries", ()))
+        kmax, terms = C.c_uint32(), C.c_uint64()
+        self._check(self._L.bisbm_conditionals_get_marginals(self._h, None, C.byref(kmax), C.byref(terms)))
+        out = np.zeros((Q, kmax.value), dtype=np.float64)
+        self._check(self._L.bisbm_conditionals_get_marginals(self._h, _p(out, _f64p), C.byref(kmax), C.byref(terms)))
+        return out, terms.value
+
+    def conditionals_last(self, i):
+        """(dS, P) float64 [n_chains, K_own] of the i-th query at the last sample (row c, column = block within the node's type;
+        K_own: the largest block count of that type among the chains, 0.0 past a chain's own; NaN rows: chains that were not
+        counted).  Needs keep_last."""
+        q = getattr(self, "conditional_queries", np.zeros(0, dtype=np.uint32))
+        i = int(i)
+        if not 0 <= i < len(q):
+            raise IndexError("query %d: %d are set" % (i, len(q)))
+        t = 1 if q[i] >= self.na else 0
+        stride = max(self.ka_kb(c)[t] for c in range(self.n_chains)) if self.mixed_shapes else (self.KB if t else self.KA)
+        dS = np.zeros((self.n_chains, stride), dtype=np.float64)
+        P = np.zeros((self.n_chains, stride), dtype=np.float64)
+        self._check(self._L.bisbm_conditionals_get_last(self._h, i, stride, _p(dS, _f64p), _p(P, _f64p)))
+        return dS, P
+
     # -- partition distances and posterior modes (include/bisbm.h, "Partition distances and posterior modes")
     def partition_distances(self, chains=None):
         """(vi float64 [m, m], H float64 [m]): the variation of information (nats) between every two of the selected chains'
@@ -1212,6 +1294,6 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import (ChainShard, numpy_coassign, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables,  # noqa: E402,F401
+from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables,  # noqa: E402,F401
                           numpy_pair_scores, numpy_query_topk, shard_chains)
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

@@ -18,6 +18,7 @@
 //   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains, top-k on the device; kernels and C ABI
 //   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block, top-k; kernels and C ABI
 //   bisbm_foldin.hip     fold-in queries: block posterior, recommendations and peers of a node that is not in the graph; kernels and C ABI
+//   bisbm_conditionals.hip  node conditionals: dS of every target block of a node, the conditional and its pooled terms, soft marginals; kernels and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
 //
@@ -270,6 +271,39 @@ struct FoldinState {
     DeviceBuf<double> d_val;      // topk: [chunk][k] their sums
 };
 
+// Node conditionals (bisbm_conditionals.hip).  As FoldinState: the sums, the soft marginals and the rows of the last sample belong
+// to the engine that owns the graph on a device, the container of device entries keeps the host side (n, q, nbb, ref) only.  A
+// chain's rows: the queries' rows back to back in the caller's order, K_own doubles each -- query i starts at
+// (i - nbb[i]) * ka + nbb[i] * kb.
+struct ConditionalState {
+    uint32_t n = 0;               // queries set (0: none)
+    uint32_t n_b = 0;             // ... of type b
+    uint32_t what = 0;            // BISBM_COND_KEEP_LAST
+    double beta = 0;
+    uint64_t terms = 0;           // chain terms added to the label-free sums since the last set / reset
+    uint64_t prob_terms = 0;      // ... to the soft marginals (they start afresh whenever the reference is set)
+    std::vector<uint32_t> q;      // [n] node of every query, caller's order
+    std::vector<uint32_t> nbb;    // [n + 1] type-b queries before every query
+    AlignRef ref;                 // the caller's reference partition of the soft marginals (has: they are kept)
+    uint64_t ref_serial = 0;      // bumped whenever the reference changes
+    DeviceBuf<uint32_t> d_q;      // [n] `q`
+    DeviceBuf<uint32_t> d_nbb;    // [n + 1] `nbb`
+    DeviceBuf<double> d_stat;     // [3][n] stay_sum, entropy_sum, margin_sum
+    DeviceBuf<unsigned long long> d_free;  // [n] counted chains in which the query's node was free
+    DeviceBuf<double> d_prob;     // [n][max(ref.ka, ref.kb)] soft marginals
+    size_t prob_cells = 0;
+    DeviceBuf<double> d_dS, d_P;  // rows: of the last sample, the segments below back to back (KEEP_LAST), else of one chunk of chains
+    DeviceBuf<double> d_terms;    // [chunk][n][4] stay, entropy, margin, free of one chunk of chains
+    // the last sample's rows, one segment per leaf: chains ridx[..] of this engine, shape (ka, kb), from d_dS[base] / d_P[base] on
+    struct Segment {
+        uint32_t ka = 0, kb = 0;
+        size_t base = 0;
+        std::vector<uint32_t> chain;
+    };
+    std::vector<Segment> segments;
+    AlignScratch scratch;         // (its own: the permutations of a conditional sample are not the marginal histogram's)
+};
+
 // Partition distances (bisbm_partition.hip).  The scratch of the calls, on the engine whose device computes (a plain handle, the
 // container of shape groups, the first device entry); nothing of it outlives a call in meaning, it is only kept to be reused.
 struct PartitionState {
@@ -399,6 +433,7 @@ struct bisbm_engine {
     bisbm::QueryScoreState queries;
     bisbm::CoassignState coassign;
     bisbm::FoldinState foldin;
+    bisbm::ConditionalState cond;
     bisbm::PartitionState partition;
     bisbm::ModeState modes;
 };

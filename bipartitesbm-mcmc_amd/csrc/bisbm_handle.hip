@@ -47,7 +47,7 @@ void free_all(bisbm_engine* h) {
     free_chain_arrays(h);
     // (the buffers of these go here, with the device current and before the stream and the events)
     h->align = AlignState(), h->temper = TemperState(), h->population = PopulationState(), h->pairs = PairScoreState(), h->partition = PartitionState();
-    h->queries = QueryScoreState(), h->coassign = CoassignState(), h->foldin = FoldinState();
+    h->queries = QueryScoreState(), h->coassign = CoassignState(), h->foldin = FoldinState(), h->cond = ConditionalState();
     h->d_T.reset();
     if (h->root) {  // a sub-engine: the graph and the tables belong to the handle it serves
         h->d_rowptr = nullptr, h->d_col = nullptr, h->d_lgamma = nullptr, h->d_logtab = nullptr, h->d_q = nullptr;

@@ -300,6 +300,48 @@ struct FoldinSelectParams {
     double* sum_out;          // [n_q][k]
 };
 
+// Node conditionals (bisbm_conditionals.hip).  The rows kernel turns every (chain of the launch, query) into the node's rows dS[k_own]
+// and P[k_own] and the chain's four terms (stay, entropy, margin, free as 0.0 / 1.0); a chain that is not counted gets NaN.  One
+// chain's rows: the queries' rows back to back in the caller's order; nbb[i] = the type-b queries before query i.
+struct CondRowsParams {
+    uint32_t na, ka, kb, maxdeg;
+    uint32_t chain0, n_chains;  // the chains of the launch: chain0 .. chain0 + n_chains - 1 of the engine
+    uint32_t buf_chain0;        // the row and term buffers hold the chains from this one on
+    uint32_t n_q;
+    double beta;
+    size_t row_total;           // doubles of one chain's rows
+    const uint32_t* q;          // [n_q] node of every query
+    const uint32_t* nbb;        // [n_q + 1]
+    const uint32_t* rowptr;
+    const uint32_t* col;
+    const uint8_t* labels;      // byte labels
+    size_t label_stride;
+    const int32_t* m;           // [chain][ka*kb]
+    const int32_t* m_r;         // [chain][K]
+    const int32_t* n_r;         // [chain][K]
+    const uint32_t* eta;        // [chain][K*(maxdeg+1)]
+    const uint32_t* rung;       // replica exchange: only chains with rung[c] == 0 are counted; NULL: every chain
+    const double* lgamma_tab;
+    uint64_t lgamma_size;
+    const double* q_tab;
+    uint32_t q_stride;
+    const double* log_tab;
+    double* dS;                 // [chain - buf_chain0][row_total]
+    double* P;
+    double* terms;              // [chain - chain0][n_q][4]
+};
+// prob[query][perm[chain][block] - type base] += P[chain][query][block], chains in ascending order
+struct CondSoftParams {
+    uint32_t na, ka, kb, kmax, n_q;
+    uint32_t chain0, n_chains, buf_chain0;
+    size_t row_total;
+    const uint32_t* q;
+    const uint32_t* nbb;
+    const double* P;
+    const uint8_t* perm;        // [chain of the engine][ka + kb], global-label form
+    double* prob;               // [n_q][kmax]
+};
+
 // agg_split (blockmodel.cc:505-565): evaluation of `n_trials` random half-cuts of every block of one type, all chains
 struct SplitParams {
     const uint32_t* rowptr;
@@ -440,6 +482,10 @@ hipError_t launch_foldin_tables(const FoldinTableParams& p, hipStream_t stream);
 hipError_t launch_foldin_rows(const FoldinRowsParams& p, bool recommend, hipStream_t stream);
 hipError_t launch_foldin_mask(const FoldinSelectParams& p, uint8_t* mask, hipStream_t stream);  // the listed nodes of a chunk (mask: zeroed)
 hipError_t launch_foldin_select(const FoldinSelectParams& p, hipStream_t stream);
+hipError_t launch_cond_rows(const CondRowsParams& p, hipStream_t stream);
+// the terms of n_chains chains ([chain][n_q][4]) onto stat[3][n_q] and free_cnt[n_q], chain by chain in ascending order
+hipError_t launch_cond_pool(const double* terms, uint32_t n_q, uint32_t n_chains, double* stat, unsigned long long* free_cnt, hipStream_t stream);
+hipError_t launch_cond_soft(const CondSoftParams& p, hipStream_t stream);
 hipError_t launch_log_q_probe(const Tables& tab, const int32_t* n, const int32_t* k, size_t count, double* out,
                               int fast, hipStream_t stream);
 

@@ -259,6 +259,33 @@ def _foldin_blocks(m, m_r, n_r, ka, qtype):
     return quad, m_r[a], n_r[a], m_r[b]
 
 
+def numpy_conditional_row(dS_row, r_local, free, beta):
+    """Host statement of steps 3 and 4 of the node conditionals (include/bisbm.h, "Node conditionals") for one chain and one
+    query: (P [K_own], stay, entropy, margin) from the row dS_s over the blocks of the node's type, the node's block within its
+    type, whether the node is free (K_own > 1 and it is not alone in its block) and beta, with the operations in the order the
+    header states.  margin is None for a node that is not free.  The exponential and the logarithm are numpy's: the device's may
+    differ from them in the last bits, everything else is bit for bit."""
+    dS = np.asarray(dS_row, dtype=np.float64)
+    K, r, beta = len(dS), int(r_local), float(beta)
+    if not free:
+        P = np.zeros(K, dtype=np.float64)
+        P[r] = 1.0
+        margin = None
+    else:
+        x = beta * (dS - dS.min())
+        w = np.where(x > 700.0, 0.0, np.exp(-np.minimum(x, 700.0)))
+        Z = float(w[0])
+        for y in w[1:]:
+            Z = Z + float(y)
+        P = w / Z
+        margin = float(np.delete(dS, r).min())
+    acc = 0.0
+    for y in P:
+        if y != 0.0:
+            acc = acc + float(y) * float(np.log(y))
+    return P, float(P[r]), 0.0 - acc, margin
+
+
 def numpy_foldin_posterior(labels, m, m_r, n_r, ka, qtype, neighbours, alpha):
     """Host statement of steps 1 and 2 of the fold-in queries (include/bisbm.h, "Fold-in queries") for one chain and one virtual
     node: the posterior P[K_own] over the blocks of its type, bit for bit what the device computes.  `labels`, `m`, `m_r`, `n_r`:

@@ -248,6 +248,11 @@ public:
     void marginals_accumulate() { check(bisbm_marginals_accumulate(h_, nullptr)); }
     // label alignment before pooling (include/bisbm.h): on / off, and the chain the reference was taken from (-1: the caller's)
     void marginals_set_alignment(bool on) { check(bisbm_marginals_set_alignment(h_, on ? BISBM_ALIGN_REFERENCE : BISBM_ALIGN_NONE)); }
+    std::vector<uint32_t> marginals_reference_labels() {
+        std::vector<uint32_t> labels(n_);
+        check(bisbm_marginals_get_reference(h_, labels.data(), nullptr));
+        return labels;
+    }
     int64_t marginals_reference_chain() {
         int64_t chain = -1;
         check(bisbm_marginals_get_reference(h_, nullptr, &chain));
@@ -371,6 +376,43 @@ public:
         sums.assign(foldin_types_.size() * (size_t)k, 0.);
         check(bisbm_foldin_topk(h_, what, k, exclude_listed ? 1 : 0, nodes.data(), sums.data(), &terms));
     }
+    // node conditionals (include/bisbm.h, "Node conditionals"): the queries (existing nodes of either type; empty + all = true:
+    // every node), beta and whether the last sample's rows are kept; the caller's reference of the soft marginals (empty:
+    // cleared); one sample of every counted chain; the pooled label-free sums; the soft marginals ([n_queries * kmax]); one
+    // query's dS and P rows per chain at the last sample ([n_chains * stride] each)
+    void conditionals_set(const std::vector<uint32_t>& nodes, double beta = 1.0, bool keep_last = false, bool all = false) {
+        const uint32_t nq = all ? (uint32_t)n_ : (uint32_t)nodes.size();
+        check(bisbm_conditionals_set(h_, nq, all ? nullptr : nodes.data(), beta, keep_last ? BISBM_COND_KEEP_LAST : 0u));
+        n_conditionals_ = nq;
+    }
+    void conditionals_set_reference(const std::vector<uint32_t>& labels) {
+        if (!labels.empty() && labels.size() != n_) throw std::runtime_error("conditionals_set_reference: n labels");
+        check(bisbm_conditionals_set_reference(h_, labels.empty() ? nullptr : labels.data()));
+    }
+    void conditionals_accumulate() { check(bisbm_conditionals_accumulate(h_)); }
+    void conditionals_reset() { check(bisbm_conditionals_reset(h_)); }
+    struct conditional_stats_t {
+        std::vector<double> stay, entropy, margin;
+        std::vector<uint64_t> free;
+        uint64_t terms = 0;
+    };
+    conditional_stats_t conditionals_stats() {
+        conditional_stats_t s;
+        s.stay.assign(n_conditionals_, 0.), s.entropy.assign(n_conditionals_, 0.), s.margin.assign(n_conditionals_, 0.);
+        s.free.assign(n_conditionals_, 0);
+        check(bisbm_conditionals_get_stats(h_, s.stay.data(), s.entropy.data(), s.margin.data(), s.free.data(), &s.terms));
+        return s;
+    }
+    std::vector<double> conditionals_marginals(uint32_t& kmax, uint64_t& terms) {
+        check(bisbm_conditionals_get_marginals(h_, nullptr, &kmax, &terms));
+        std::vector<double> prob((size_t)n_conditionals_ * kmax);
+        check(bisbm_conditionals_get_marginals(h_, prob.data(), &kmax, &terms));
+        return prob;
+    }
+    void conditionals_last(uint32_t query_index, uint32_t stride, std::vector<double>& dS, std::vector<double>& p) {
+        dS.assign((size_t)n_chains_ * stride, 0.), p.assign((size_t)n_chains_ * stride, 0.);
+        check(bisbm_conditionals_get_last(h_, query_index, stride, dS.data(), p.data()));
+    }
     // rung of every chain under replica exchange (bisbm_tempering_get)
     std::vector<uint32_t> tempering_rungs() {
         std::vector<uint32_t> rung(n_chains_);
@@ -475,6 +517,7 @@ private:
     size_t KA_, KB_, n_ = 0, na_ = 0, n_pairs_ = 0;
     std::vector<uint32_t> queries_, coassign_queries_;
     std::vector<uint8_t> foldin_types_;
+    uint32_t n_conditionals_ = 0;
     uint32_t n_chains_;
     uint_vec_t memberships_;
 };

@@ -5,7 +5,8 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha.
+// --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
+// --conditionals, --conditionals_beta.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -54,6 +55,7 @@ const option_spec kOptions[] = {
     {"recommend", 0, 2},        {"include_edges", 0, 0},
     {"similar", 0, 2},
     {"foldin", 0, 2},           {"foldin_alpha", 0, 1},
+    {"conditionals", 0, 2},     {"conditionals_beta", 0, 1},
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
 };
 
@@ -222,6 +224,17 @@ void print_help(const char* argv0) {
                  "                                        its own type most likely to share its block (means over samples and\n"
                  "                                        chains, %.17g; lines count from 0, empty lines not counted).\n"
                  "  --foldin_alpha A                      With --foldin: the smoothing constant of the block posterior, A > 0.\n"
+                 "  --conditionals QUERIES OUT            With --marginalize: QUERIES holds one node id per line (either type);\n"
+                 "                                        every sample evaluates, in every sampled chain, the node's full\n"
+                 "                                        conditional over the blocks of its type given all other labels, and OUT\n"
+                 "                                        receives `node stay entropy margin` per line of QUERIES: the mean\n"
+                 "                                        probability of its current block, the mean entropy of the conditional\n"
+                 "                                        (nats) and the mean cost of the cheapest other block (nats; over the\n"
+                 "                                        chains where the node is not alone in its block, nan if there is none),\n"
+                 "                                        %.17g.  With --align the line goes on with the node's soft marginal over\n"
+                 "                                        the blocks of its type (the conditionals averaged through the alignment).\n"
+                 "  --conditionals_beta B                 With --conditionals: the inverse temperature of the conditional, B > 0\n"
+                 "                                        (default 1).\n"
                  "  --modes OUT THRESHOLD                 With --marginalize: after the last sample the sampled chains' partitions\n"
                  "                                        are compared (variation of information, nats) and grouped into modes:\n"
                  "                                        chains joined by a path of pairs with VI <= THRESHOLD share a mode.  OUT\n"
@@ -324,6 +337,30 @@ int main(int argc, char const* argv[]) {
     if (count("foldin_alpha") && !count("foldin")) {
         std::cerr << "--foldin_alpha sets the smoothing constant of the fold-in queries: it needs --foldin.\n";
         return 1;
+    }
+    if ((count("conditionals") || count("conditionals_beta")) && !count("marginalize")) {
+        std::cerr << "--conditionals evaluates the nodes' full conditionals at the samples of the chains: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("conditionals_beta") && !count("conditionals")) {
+        std::cerr << "--conditionals_beta sets the inverse temperature of the node conditionals: it needs --conditionals.\n";
+        return 1;
+    }
+    double conditionals_beta = 1.;
+    if (var_map.count("conditionals")) {
+        if (var_map["conditionals"].size() != 2) {
+            std::cerr << "Invalid --conditionals. Two arguments: the file of query nodes to read and the file to write.\n";
+            return 1;
+        }
+        if (count("conditionals_beta")) {
+            const std::string b = single("conditionals_beta", "");
+            char* end = nullptr;
+            conditionals_beta = std::strtod(b.c_str(), &end);
+            if (b.empty() || *end != '\0' || !std::isfinite(conditionals_beta) || !(conditionals_beta > 0.)) {
+                std::cerr << "Invalid --conditionals_beta. A finite number > 0, e.g. --conditionals_beta 1.\n";
+                return 1;
+            }
+        }
     }
     uint32_t foldin_k = 0;
     double foldin_alpha = 0.;
@@ -548,6 +585,30 @@ int main(int argc, char const* argv[]) {
                 return 1;
             }
             similar_queries.push_back((uint32_t)id);
+        }
+    }
+    // --conditionals: likewise
+    std::vector<uint32_t> conditional_queries;
+    if (var_map.count("conditionals")) {
+        const std::string in = var_map["conditionals"][0];
+        std::ifstream file(in);
+        if (!file) {
+            std::cerr << "[error] --conditionals: cannot read " << in << "\n";
+            return 1;
+        }
+        std::string text;
+        for (size_t line_no = 1; std::getline(file, text); ++line_no) {
+            const size_t b = text.find_first_not_of(" \t\r");
+            if (b == std::string::npos) continue;  // (an empty line)
+            const size_t e = text.find_last_not_of(" \t\r");
+            const std::string tok = text.substr(b, e - b + 1);
+            char* end = nullptr;
+            const unsigned long long id = std::strtoull(tok.c_str(), &end, 10);
+            if (*end != '\0' || tok[0] == '-' || tok[0] == '+' || id >= NA + NB) {
+                std::cerr << "[error] --conditionals: line " << line_no << " of " << in << " (" << tok << ") must name a node [0, " << NA + NB << ")\n";
+                return 1;
+            }
+            conditional_queries.push_back((uint32_t)id);
         }
     }
     // --foldin: the virtual nodes are read and checked before any device is touched (ids as in the edge list file)
@@ -1110,9 +1171,19 @@ int main(int argc, char const* argv[]) {
                         for (uint32_t& v : l) v = new_id[v];
                 blockmodel.foldin_set(foldin_types, lists, foldin_alpha);
             }
+            const bool soft = count("align") && !per_mode;  // the soft marginals take the aligned histogram's reference
+            if (!conditional_queries.empty()) {
+                std::vector<uint32_t> q;
+                for (uint32_t v : conditional_queries) q.push_back(new_id.empty() ? v : new_id[v]);
+                blockmodel.conditionals_set(q, conditionals_beta);
+            }
             for (size_t sample = 0; sample < n_samples; ++sample) {
                 advance(sweeps_between);
                 blockmodel.marginals_accumulate();
+                if (!conditional_queries.empty()) {
+                    if (soft && sample == 0) blockmodel.conditionals_set_reference(blockmodel.marginals_reference_labels());
+                    blockmodel.conditionals_accumulate();
+                }
                 if (!foldin_types.empty()) blockmodel.foldin_accumulate();
                 if (!score_pairs.empty()) blockmodel.pair_scores_accumulate();
                 if (!recommend_queries.empty()) blockmodel.query_scores_accumulate();
@@ -1235,6 +1306,43 @@ int main(int argc, char const* argv[]) {
                 }
                 std::clog << "foldin: " << foldin_types.size() << " virtual node(s), " << foldin_k << " node(s) per row, alpha " << foldin_alpha << ", "
                           << terms << " chain term(s) per sum -> " << out_path << "\n";
+            }
+            if (var_map.count("conditionals")) {
+                const std::string out_path = var_map["conditionals"][1];
+                std::ofstream out(out_path);
+                blockmodel_t::conditional_stats_t st;
+                std::vector<double> prob;
+                uint32_t kmax = 0;
+                uint64_t prob_terms = 0;
+                if (!conditional_queries.empty()) {
+                    st = blockmodel.conditionals_stats();
+                    if (soft) prob = blockmodel.conditionals_marginals(kmax, prob_terms);
+                }
+                char num[64];
+                for (size_t i = 0; i < conditional_queries.size(); ++i) {
+                    const double vals[3] = {st.stay[i] / (double)st.terms, st.entropy[i] / (double)st.terms,
+                                            st.free[i] ? st.margin[i] / (double)st.free[i] : std::numeric_limits<double>::quiet_NaN()};
+                    out << conditional_queries[i];
+                    for (double x : vals) {
+                        std::snprintf(num, sizeof(num), " %.17g", x);
+                        out << num;
+                    }
+                    if (soft) {
+                        const size_t k_own = conditional_queries[i] < NA ? KA : KB;
+                        for (size_t s = 0; s < k_own; ++s) {
+                            std::snprintf(num, sizeof(num), " %.17g", prob[i * kmax + s] / (double)prob_terms);
+                            out << num;
+                        }
+                    }
+                    out << "\n";
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --conditionals: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "conditionals: " << conditional_queries.size() << " query node(s), beta " << conditionals_beta << ", " << st.terms
+                          << " chain term(s) per sum" << (soft ? ", soft marginals" : "") << " -> " << out_path << "\n";
             }
             uint_vec_t heaviest_labels;
             if (per_mode) {

@@ -18,7 +18,7 @@ import numpy as np
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
-                similar=None, foldin=None):
+                similar=None, foldin=None, conditionals=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -56,7 +56,12 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     `foldin`: (nodes, k) or (nodes, k, alpha) (include/bisbm.h, "Fold-in queries"; nodes as model.foldin_set takes them): the
     virtual nodes are set, with zeroed sums, before the first sample, every sample also adds every counted chain's terms to their
     rows, and (model.foldin_recommend(k), model.foldin_similar(k)) is appended as the last element of the return value.  The
-    chains of this rank only."""
+    chains of this rank only.
+    `conditionals`: (nodes, beta) or (nodes,) (include/bisbm.h, "Node conditionals"; nodes as model.conditionals_set takes them,
+    None: every node): the queries are set, with zeroed sums, before the first sample, every marginal sample also takes one
+    conditional sample, and model.conditionals_stats() is appended to the return value; with `align` the soft marginals use the
+    reference the aligned histogram uses (taken over after the first marginal sample) and model.conditionals_marginals() --
+    (prob, terms) -- is appended after the stats.  The chains of this rank only."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
@@ -81,6 +86,17 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         model.coassign_reset()
     if foldin is not None:
         model.foldin_set(foldin[0], foldin[2] if len(foldin) > 2 else None)
+    if conditionals is not None:
+        model.conditionals_set(conditionals[0], conditionals[1] if len(conditionals) > 1 else 1.0)
+    taken = [0]
+
+    def conditional_sample():
+        if conditionals is None:
+            return
+        if align and taken[0] == 0:  # (the aligned histogram has its reference from its first sample on)
+            model.conditionals_set_reference(model.marginals_reference()[0])
+        model.conditionals_accumulate()
+        taken[0] += 1
 
     def result(labels, counts):
         out = (labels, counts)
@@ -90,6 +106,10 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             out += (model.similar(int(similar[1])),)
         if foldin is not None:
             out += ((model.foldin_recommend(int(foldin[1])), model.foldin_similar(int(foldin[1]))),)
+        if conditionals is not None:
+            out += (model.conditionals_stats(),)
+            if align:
+                out += (model.conditionals_marginals(),)
         return out
     if device_counts is None and not multi:
         # one rank, no caller buffer: the library's own histogram
@@ -108,6 +128,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
                 model.coassign_accumulate()
             if foldin is not None:
                 model.foldin_accumulate()
+            conditional_sample()
         counts = model.marginals_get().astype(np.int64)
         base = np.where(np.arange(n) >= model.na, model.KA, 0)
         return result((counts.argmax(axis=1) + base).astype(np.uint32), (counts if return_counts else None))
@@ -141,6 +162,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             model.coassign_accumulate()
         if foldin is not None:
             model.foldin_accumulate()
+        conditional_sample()
     if not multi:
         from .distributed import _argmax_first
         arg = _argmax_first(device_counts)

@@ -28,7 +28,7 @@ extern "C" {
  *    bisbm_marginals_get_mode, bisbm_marginals_map_mode), distances to reference partitions (bisbm_partition_distances_to),
  *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
  *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*), population annealing
- *    (bisbm_population_*).  Additions only. */
+ *    (bisbm_population_*), node conditionals (bisbm_conditionals_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -464,6 +464,79 @@ int bisbm_foldin_get_posteriors(bisbm_handle h, uint32_t query_index, uint32_t s
 int bisbm_foldin_get_row(bisbm_handle h, uint32_t what, uint32_t query_index, double *sum_out, uint64_t *terms_out);
 int bisbm_foldin_topk(bisbm_handle h, uint32_t what, uint32_t k, int exclude_listed, uint32_t *node_out /* n_queries * k */,
                       double *sum_out /* n_queries * k, may be NULL */, uint64_t *terms_out);
+
+/* Node conditionals: each node's full block posterior given the rest (no reference counterpart).  The step's dS(v: r -> s) is
+ * the change of the full description length, so P(b_v = s | all other labels, graph) ~ exp(-dS(v -> s)) is the node's exact
+ * full conditional in a chain.  A QUERY is an existing node v of either type; queries may repeat and may mix types;
+ * queries = NULL with n_queries = n means every node in id order.
+ * For one counted chain c with labels b, r = b_v, d = d(v), K_own blocks of v's type and K_oth of the other, s any block of v's
+ * type, k_t the number of v's CSR entries whose label is t (multi-edges count), eta_x = eta[x][d], lg the engine's lgamma_fast
+ * table, logq the Philox-mode log_q, everything in f64 without a fused multiply-add:
+ *   1. dS_r = 0.0 exactly; for s != r
+ *        acc   = 0.0; for t = 0 .. K_oth-1 in ascending order, the t with k_t == 0 skipped:
+ *                acc = acc + ((lg(m_rt+1) + lg(m_st+1)) - (lg(m_rt-k_t+1) + lg(m_st+k_t+1)))
+ *        tail1 = (lg(m_r[r]-d+1) - lg(m_r[r]+1)) + (lg(m_r[s]+d+1) - lg(m_r[s]+1))
+ *        tail2 = (lg(eta_r+1) - lg(eta_r)) + (lg(eta_s+1) - lg(eta_s+2))
+ *        tail3 = (logq(m_r[r]-d, n_r[r]-1) - logq(m_r[r], n_r[r])) + (logq(m_r[s]+d, n_r[s]+1) - logq(m_r[s], n_r[s]))
+ *        dS_s  = ((acc + tail1) + tail2) + tail3
+ *      -- the quantities of metropolis_hasting.cc:150-183.  The order of the additions is fixed by (K_own, K_oth) alone (a
+ *      skipped t would add +0.0) and no floating-point atomic is used: the same handle and calls give the same bits.  It is NOT
+ *      the sweep's 64-leaf butterfly: the two agree to rounding.
+ *   2. FREE: the node is free in chain c iff K_own > 1 and n_r[r] > 1 (the sampler vetoes a move that empties a block, so a
+ *      node alone in its block has the point mass on r as its conditional).
+ *   3. weights, with the caller's finite beta > 0.  Not free: P_c(r) = 1.0, all others 0.0.  Free: dS_min = min_s dS_s
+ *      (including the 0 at r); x_s = beta * (dS_s - dS_min); w_s = (x_s > 700.0) ? 0.0 : exp(-x_s); Z = w_0 + w_1 + ... in
+ *      ascending s, one add at a time; P_c(s) = w_s / Z.
+ *   4. label-free terms of the chain: stay = P_c(r); entropy = 0.0 - (the sum over ascending s of P_c(s) * ln P_c(s), the terms
+ *      with P_c(s) == 0.0 skipped); margin = min over s != r of dS_s, taken only when the node is free.
+ *   5. a SAMPLE (bisbm_conditionals_accumulate) adds every counted chain's stay and entropy to stay_sum[q] and entropy_sum[q]
+ *      and, where the node is free, margin to margin_sum[q] and 1 to free[q], one chain at a time in ascending chain index
+ *      with one f64 add each (chains grouped by shape: group by group in group order), and the number of counted chains to
+ *      `terms`; counted = every chain, or with replica exchange on only the chains on rung 0 (the rule of
+ *      bisbm_query_scores_accumulate; replica exchange over chains grouped by shape is BISBM_ERR_STATE).  Several devices: each
+ *      keeps the sums of its own chains, and they are added in device order when they are read.
+ *   6. SOFT MARGINALS, kept only while a reference partition is set (bisbm_conditionals_set_reference: n labels, checked as
+ *      the reference of bisbm_marginals_set_reference against the handle's common shape; NULL clears it; either zeroes prob and
+ *      its terms).  Every chain gets the permutation pi_c of "Label alignment before pooling" to the reference, computed afresh
+ *      at this sample with the same overlap table, solver and tie rule, and prob[q][pi_c(s) - type base] += P_c(s) for every
+ *      counted chain in ascending order, one f64 add each; prob has kmax = max(ka, kb) columns per query.  Refused like the
+ *      aligned histogram: a wide handle BISBM_ERR_UNSUPPORTED; chains grouped by shape, or a reference made for other block
+ *      counts (after a merge or split: "set it again"), BISBM_ERR_STATE.  There is no library-chosen reference: pass
+ *      bisbm_get_memberships of the chain you want.
+ *   7. LAST ROWS, kept only with BISBM_COND_KEEP_LAST in `what`: dS_s and P_c(s) of the last sample for every (chain of the
+ *      handle, query); chains that were not counted hold NaN.  16 * n_chains * (sum over the queries of K_own) bytes.
+ * Served: byte labels, chains grouped by shape (label-free sums and last rows), several devices, replica exchange (rung 0),
+ * anchored or static modes being set (nothing of theirs is touched).  Chain state, random streams and running sums are only
+ * read; the sums survive merges and splits.
+ * set: replaces earlier queries, zeroes everything and forgets the reference; n_queries = 0 frees everything.
+ *   BISBM_RNG_MT19937_COMPAT is BISBM_ERR_UNSUPPORTED (the definition is the Philox-mode arithmetic).  BISBM_ERR_INVALID_ARG,
+ *   bisbm_last_error naming the first offending index and the earlier queries staying in place: a query >= n, beta not finite
+ *   or <= 0, an unknown bit of `what`.  Memory per device: 40 bytes per query, 8 * kmax per query with a reference.
+ * accumulate: one sample; BISBM_ERR_STATE before bisbm_init / bisbm_shuffle or without queries, BISBM_ERR_UNSUPPORTED with
+ *   two-byte labels.  Scratch per device: 32 bytes per (chain, query) and, without KEEP_LAST, the rows, for as many chains at a
+ *   time as fit 256 MiB (at least one); with a reference the overlap tables of the aligned histogram for every chain.
+ * reset: zeroes sums, prob and terms and forgets the last rows; keeps queries, beta and the reference.
+ * get_stats: n_queries entries each, any pointer may be NULL.
+ * get_marginals: prob_out[n_queries * kmax] with the terms added to it since the reference was set (or the last reset);
+ *   BISBM_ERR_STATE without a reference.
+ * get_last: the conventions of bisbm_foldin_get_posteriors (handle chain order, row c at c * stride, padded with 0.0, a NaN
+ *   row for a chain that was not counted, a stride below some chain's K_own BISBM_ERR_INVALID_ARG); BISBM_ERR_STATE without
+ *   KEEP_LAST or before the first sample; dS_out or p_out may be NULL.
+ * Out of scope: conditionals in mt19937-compat arithmetic, two-byte labels, pooling over processes, a library-chosen
+ * reference, per-mode soft histograms, moving nodes (greedy polishing, Gibbs sweeps), top-k of the least settled nodes on the
+ * device (with n doubles per statistic the host sorts them). */
+#define BISBM_COND_KEEP_LAST 1u
+int bisbm_conditionals_set(bisbm_handle h, uint32_t n_queries, const uint32_t *queries /* NULL: all n nodes */, double beta,
+                           uint32_t what);
+int bisbm_conditionals_set_reference(bisbm_handle h, const uint32_t *labels /* n, NULL clears; zeroes prob */);
+int bisbm_conditionals_accumulate(bisbm_handle h);
+int bisbm_conditionals_reset(bisbm_handle h);
+int bisbm_conditionals_get_stats(bisbm_handle h, double *stay_sum, double *entropy_sum, double *margin_sum,
+                                 uint64_t *free_out /* n_queries each, any may be NULL */, uint64_t *terms_out);
+int bisbm_conditionals_get_marginals(bisbm_handle h, double *prob_out /* n_queries * kmax */, uint32_t *kmax_out,
+                                     uint64_t *terms_out);
+int bisbm_conditionals_get_last(bisbm_handle h, uint32_t query_index, uint32_t stride, double *dS_out,
+                                double *p_out /* n_chains * stride each, either may be NULL */);
 
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
