@@ -51,6 +51,8 @@ FOLDIN_RECOMMEND, FOLDIN_SIMILAR = 1, 2
 FOLDIN_CAND_TILE, FOLDIN_TILE = 1024, 8
 # bisbm_conditionals_*: the bit of `what` that keeps the last sample's rows
 COND_KEEP_LAST = 1
+# the Philox purpose of the heat-bath draw (csrc/bisbm_kernels.hpp: PHX_HEATBATH; DESIGN.md section 4 lists them all)
+PHILOX_PURPOSE_HEATBATH = 9
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -134,6 +136,7 @@ ABI = {
     "bisbm_conditionals_get_stats": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p, _u64p, _u64p]),
     "bisbm_conditionals_get_marginals": (C.c_int, [C.c_void_p, _f64p, _u32p, _u64p]),
     "bisbm_conditionals_get_last": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p, _f64p]),
+    "bisbm_heatbath_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_int, _u64p, _u64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
@@ -555,6 +558,25 @@ class BlockModel:
     def run_sweeps(self, sweeps, temperature=1.0):
         """`sweeps` sweeps at constant temperature (the "marginalize" regime: -c constant -a 1)."""
         return MetropolisHasting().anneal(self, constant_schedule, [temperature], int(sweeps) * self.n, 1 << 60)
+
+    # -- heat-bath sweeps and greedy polishing (include/bisbm.h, "Heat-bath sweeps and greedy polishing")
+    def _heatbath(self, sweeps, beta, stop_when_settled):
+        moved = np.zeros(self.n_chains, dtype=np.uint64)
+        sw = np.zeros(self.n_chains, dtype=np.uint64)
+        self._check(self._L.bisbm_heatbath_run(self._h, int(sweeps), float(beta), int(stop_when_settled), _p(moved, _u64p), _p(sw, _u64p)))
+        return moved, sw
+
+    def heatbath_sweeps(self, sweeps, beta=1.0):
+        """`sweeps` heat-bath (Gibbs) sweeps: every node in the MH sweep's visit order draws its block from its exact
+        conditional ~ exp(-beta dS).  Returns the moves per chain (uint64 [n_chains])."""
+        return self._heatbath(sweeps, beta, False)[0]
+
+    def polish(self, max_sweeps=100):
+        """Greedy sweeps (beta = +inf: every free node to the lowest block of least dS, only strictly downhill) until a whole
+        sweep moves nothing, at most `max_sweeps`.  Returns (moved, sweeps) per chain; a chain has settled -- it is a local
+        minimum of the description length under single-node moves -- when its last sweep moved nothing, which
+        sweeps < max_sweeps implies."""
+        return self._heatbath(max_sweeps, float("inf"), True)
 
     # -- replica exchange (include/bisbm.h, "Replica exchange")
     def set_tempering(self, ladder):
@@ -1294,6 +1316,6 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables,  # noqa: E402,F401
+from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice,  # noqa: E402,F401
                           numpy_pair_scores, numpy_query_topk, shard_chains)
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

@@ -19,6 +19,7 @@
 //   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block, top-k; kernels and C ABI
 //   bisbm_foldin.hip     fold-in queries: block posterior, recommendations and peers of a node that is not in the graph; kernels and C ABI
 //   bisbm_conditionals.hip  node conditionals: dS of every target block of a node, the conditional and its pooled terms, soft marginals; kernels and C ABI
+//   bisbm_heatbath.hip   heat-bath sweeps and greedy polishing: nodes moved by their conditionals; kernel and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
 //

@@ -1,0 +1,418 @@
+// bisbm_heatbath.hip -- moving nodes by their conditionals: heat-bath (Gibbs) sweeps at a finite beta and greedy polishing at
+// beta = +inf (no reference counterpart; include/bisbm.h, "Heat-bath sweeps and greedy polishing", states the visit order, the
+// choice and what a move updates).  The row of the visited node -- dS_s and P(s) over all blocks s of its type -- is the row of
+// "Node conditionals": the same f64 operations in the same order as cond_rows_kernel of bisbm_conditionals.hip, restated here
+// because this kernel reads the block state from LDS and keeps the list and the row in LDS arrays of its own.
+//
+// Kernel: one wave per chain, persistent over all sweeps of the call, like the generic sweep_kernel.  The chain's quadrant of m
+// (odd row stride), m_r, n_r, the k_v histogram and eta (when it fits, template parameter EL) live in LDS, loaded at the start
+// and stored at the end; labels stay in HBM.  A sweep is two phases, type a then type b, each walked through TiledOrder in
+// chunks of 64 positions that never straddle the two.  The visited class is an independent set: no step of a phase changes a
+// label that another step of the phase reads, so a chunk's header fetches everything the chunk needs from HBM at once -- lane q
+// the node, row extent and own label of position q, then the first 64 neighbour labels of all 64 rows, eight rows' id loads
+// and eight rows' label gathers in flight together -- and parks the labels in LDS as bytes.  Nothing of it is ever invalidated.
+// A step then touches HBM only for rows longer than 64, the lgamma / log_q tables and the label it writes.
+//
+// Step: the k_v histogram (integer LDS atomics), the non-zero (t, k_t) compacted in ascending t by ballots with the r side's two
+// table values, then lane <-> target block s (a type with more than 64 blocks is walked in chunks of 64 lanes): per list entry
+// two table gathers and one f64 add in list order, eight entries in flight together, then the three tails, whose gathers are
+// issued before the list is walked.  min, Z and the running sum C_s are sequential in ascending s over k_own terms: the lane of
+// block s holds its value and every lane adds them one v_readlane at a time.  A node that is not free (a one-
+// block type, or alone in its block) is skipped before any of this: its conditional is the point mass on r.
+#include "bisbm_engine.hpp"
+
+using namespace bisbm;
+
+namespace bisbm {
+
+namespace {
+
+__device__ __forceinline__ void hb_fence() {  // (one wave: LDS operations execute in issue order; this only stops code motion)
+    __builtin_amdgcn_wave_barrier();
+    __asm__ volatile("" ::: "memory");
+}
+
+// log n from the host table, as the caller of log_q<true> hands it over (bisbm_conditionals.hip: logq_of)
+__device__ __forceinline__ double hb_logn(const Tables& tab, int n) { return (n > 0 && (uint64_t)n < tab.lg_size) ? tab.logtab[n] : 0.; }
+
+template <bool EL>
+__global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const uint32_t chain = blockIdx.x;
+    if (chain >= p.n_chains) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t K = p.ka + p.kb, D = p.maxdeg + 1, S = p.kb | 1u;
+    const uint32_t kmax = p.ka > p.kb ? p.ka : p.kb;
+
+    // carve LDS (heatbath_lds_bytes restates the sizes)
+    unsigned char* cur = lds_raw;
+    double* s_L1 = (double*)cur;  // lg(m_rt + 1) per list entry
+    cur += sizeof(double) * kmax;
+    double* s_L3 = (double*)cur;  // lg(m_rt - k_t + 1)
+    cur += sizeof(double) * kmax;
+    double* s_dS = (double*)cur;  // dS per target
+    cur += sizeof(double) * kmax;
+    double* s_x = (double*)cur;   // w, then P per target
+    cur += sizeof(double) * kmax;
+    int32_t* mq = (int32_t*)cur;  // ka * S
+    cur += sizeof(int32_t) * p.ka * S;
+    int32_t* mr = (int32_t*)cur;
+    cur += sizeof(int32_t) * K;
+    int32_t* nr = (int32_t*)cur;
+    cur += sizeof(int32_t) * K;
+    int32_t* hist = (int32_t*)cur;
+    cur += sizeof(int32_t) * kmax;
+    uint32_t* s_t = (uint32_t*)cur;  // the non-zero t, ascending
+    cur += sizeof(uint32_t) * kmax;
+    int32_t* s_kt = (int32_t*)cur;   // their k_t
+    cur += sizeof(int32_t) * kmax;
+    uint8_t* lab_lds = (uint8_t*)cur;  // 64 rows x the labels of their first 64 neighbours
+    cur += kWave * kWave;
+    uint32_t* eta_l = (uint32_t*)cur;  // K * D when EL
+    uint32_t* eta_g = p.eta + (size_t)chain * K * D;
+    auto eta_at = [&](uint32_t idx) -> uint32_t* {
+        if constexpr (EL)
+            return eta_l + idx;
+        else
+            return eta_g + idx;
+    };
+
+    uint8_t* labels = p.labels + (size_t)chain * p.label_stride;
+    int32_t* m_g = p.m + (size_t)chain * p.ka * p.kb;
+    int32_t* mr_g = p.m_r + (size_t)chain * K;
+    int32_t* nr_g = p.n_r + (size_t)chain * K;
+    for (uint32_t i = lane; i < p.ka * p.kb; i += kWave) mq[(i / p.kb) * S + (i % p.kb)] = m_g[i];
+    for (uint32_t i = lane; i < K; i += kWave) {
+        mr[i] = mr_g[i];
+        nr[i] = nr_g[i];
+    }
+    if (EL)
+        for (uint32_t i = lane; i < K * D; i += kWave) eta_l[i] = eta_g[i];
+    ChainScalars* sc = p.scalars + chain;
+    double cum_dS = sc->cum_dS;
+    uint64_t sweeps_total = sc->sweeps_total;
+    __syncthreads();
+
+    const Tables tab{p.lgamma_tab, p.lgamma_size, p.q_tab, p.q_stride, p.log_tab};
+    const uint32_t chain_gid = chain_gid_of(p, chain);
+    uint64_t moved = 0, sweeps_run = 0;
+    for (uint64_t sweep = 0; sweep < p.sweeps; ++sweep) {
+        uint64_t moved_sweep = 0;
+        for (uint32_t phase = 0; phase < 2; ++phase) {
+            const bool tb = phase != 0;
+            const uint32_t n_cls = tb ? p.nb : p.na, v0 = tb ? p.na : 0u;
+            const uint32_t k_own = tb ? p.kb : p.ka, k_oth = tb ? p.ka : p.kb, own0 = tb ? p.ka : 0u, oth0 = tb ? 0u : p.ka;
+            if (k_own <= 1u) continue;  // (nobody of a one-block type is free)
+            TiledOrder order;
+            order.init(phx_draw(p.seed, chain_gid, PHX_SWEEP_KEY, 2 * sweeps_total + phase), n_cls);
+            auto Mq = [&](uint32_t i_own, uint32_t j_oth) -> int32_t& { return tb ? mq[j_oth * S + i_own] : mq[i_own * S + j_oth]; };
+            for (uint32_t vi0 = 0; vi0 < n_cls; vi0 += kWave) {
+                // ---- chunk header: lane q holds the node, row extent and own label of position vi0 + q ----
+                const uint32_t cnt = n_cls - vi0 < (uint32_t)kWave ? n_cls - vi0 : (uint32_t)kWave;
+                uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0;
+                if (lane < cnt) {
+                    v_l = v0 + order(vi0 + lane);
+                    beg_l = p.rowptr[v_l];
+                    deg_l = p.rowptr[v_l + 1] - beg_l;
+                    r_l = labels[v_l];
+                }
+                // the first 64 neighbour labels of the chunk's rows, eight rows at a time (idle lanes read node 0)
+                hb_fence();
+                for (uint32_t q0 = 0; q0 < cnt; q0 += 8) {
+                    uint32_t id[8], lb[8];
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) {
+                        const uint32_t b0 = readlane(beg_l, q0 + j), d0 = readlane(deg_l, q0 + j);  // (rows past cnt: deg 0)
+                        id[j] = lane < d0 ? p.col[b0 + lane] : 0u;
+                    }
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) lb[j] = labels[id[j]];
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) lab_lds[(q0 + j) * kWave + lane] = (uint8_t)lb[j];
+                }
+                hb_fence();
+
+                for (uint32_t q = 0; q < cnt; ++q) {
+                    const uint32_t v = readlane(v_l, q), beg = readlane(beg_l, q), deg = readlane(deg_l, q);
+                    const uint32_t r = readlane(r_l, q), r_loc = r - own0;
+                    if (r_loc >= k_own) continue;  // (a valid label: never)
+                    const int n0r = nr[r];
+                    if (n0r <= 1) continue;  // not free: the node stays, and no draw is used
+                    // 1. k_v: the histogram of the neighbours' labels
+                    for (uint32_t t = lane; t < k_oth; t += kWave) hist[t] = 0;
+                    hb_fence();
+                    if (lane < deg) {
+                        const uint32_t t = (uint32_t)lab_lds[q * kWave + lane] - oth0;
+                        if (t < k_oth) atomicAdd(&hist[t], 1);
+                    }
+                    for (uint32_t j = kWave + lane; j < deg; j += kWave) {  // rows longer than one wave
+                        const uint32_t t = (uint32_t)labels[p.col[beg + j]] - oth0;
+                        if (t < k_oth) atomicAdd(&hist[t], 1);
+                    }
+                    hb_fence();
+                    // 2. the non-zero (t, k_t) in ascending t, with the r side's two table values
+                    uint32_t nnz = 0;
+                    for (uint32_t c0 = 0; c0 < k_oth; c0 += kWave) {
+                        const uint32_t t = c0 + lane;
+                        const int kt = t < k_oth ? hist[t] : 0;
+                        const unsigned long long bal = __ballot(kt != 0);
+                        if (kt != 0) {
+                            const uint32_t pos = nnz + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                            const int32_t m_rt = Mq(r_loc, t);
+                            s_t[pos] = t, s_kt[pos] = kt;
+                            s_L1[pos] = lgamma_fast(tab, (long long)m_rt + 1);
+                            s_L3[pos] = lgamma_fast(tab, (long long)m_rt - kt + 1);
+                        }
+                        nnz += (uint32_t)__popcll(bal);
+                    }
+                    hb_fence();
+                    // 3. dS of target s = tid (steps 1 of "Node conditionals")
+                    const int ideg = (int)deg;
+                    const int m0r = mr[r];
+                    const long long eta_r = *eta_at(r * D + deg);
+                    // the r side of the tails is the same for every target
+                    const double tail1_r = lgamma_fast(tab, (long long)m0r - ideg + 1) - lgamma_fast(tab, (long long)m0r + 1);
+                    const double tail2_r = lgamma_fast(tab, eta_r + 1) - lgamma_fast(tab, eta_r);
+                    for (uint32_t c0 = 0; c0 < k_own; c0 += kWave) {
+                        const uint32_t tid = c0 + lane;
+                        const uint32_t s = tid < k_own ? own0 + tid : r;  // (idle lanes evaluate r's own values)
+                        const int m0s = mr[s], n0s = nr[s];
+                        // every table gather of the tails is issued before the list is walked: the s side's four lgamma values
+                        // and the log n of the three log_q evaluations below
+                        const long long eta_s = *eta_at(s * D + deg);
+                        const double lg_s1 = lgamma_fast(tab, (long long)m0s + ideg + 1), lg_s0 = lgamma_fast(tab, (long long)m0s + 1);
+                        const double lg_e1 = lgamma_fast(tab, eta_s + 1), lg_e2 = lgamma_fast(tab, eta_s + 2);
+                        const int qn_r = (lane & 1u) ? m0r : m0r - ideg, qk_r = (lane & 1u) ? n0r : n0r - 1;
+                        const double ln_s1 = hb_logn(tab, m0s + ideg), ln_s0 = hb_logn(tab, m0s), ln_r = hb_logn(tab, qn_r);
+                        double acc = 0.;
+                        // eight list entries at a time: their reads of m and the sixteen table gathers are in flight together;
+                        // the adds keep the list order (past the end of the list the last entry is read again and not added)
+                        for (uint32_t i = 0; i < nnz; i += 8) {
+                            int32_t m_st[8];
+                            double a[8], b[8];
+#pragma unroll
+                            for (uint32_t j = 0; j < 8; ++j) m_st[j] = Mq(tid < k_own ? tid : r_loc, s_t[i + j < nnz ? i + j : nnz - 1u]);
+#pragma unroll
+                            for (uint32_t j = 0; j < 8; ++j) {
+                                a[j] = lgamma_fast(tab, (long long)m_st[j] + 1);
+                                b[j] = lgamma_fast(tab, (long long)m_st[j] + s_kt[i + j < nnz ? i + j : nnz - 1u] + 1);
+                            }
+#pragma unroll
+                            for (uint32_t j = 0; j < 8; ++j)
+                                if (i + j < nnz) acc = acc + ((s_L1[i + j] + a[j]) - (s_L3[i + j] + b[j]));
+                        }
+                        // the four log_q values through one copy of its code: the target's two, then the r side's two in
+                        // lanes 0 and 1
+                        double lq_s1 = 0., lq_s0 = 0., lq_r = 0.;
+#pragma nounroll
+                        for (uint32_t it = 0; it < 3; ++it) {
+                            const int qn = it == 0 ? m0s + ideg : it == 1 ? m0s : qn_r;
+                            const int qk = it == 0 ? n0s + 1 : it == 1 ? n0s : qk_r;
+                            const double val = log_q<true>(tab, qn, qk, it == 0 ? ln_s1 : it == 1 ? ln_s0 : ln_r);
+                            if (it == 0)
+                                lq_s1 = val;
+                            else if (it == 1)
+                                lq_s0 = val;
+                            else
+                                lq_r = val;
+                        }
+                        const double tail1 = tail1_r + (lg_s1 - lg_s0);
+                        const double tail2 = tail2_r + (lg_e1 - lg_e2);
+                        const double tail3 = (readlane(lq_r, 0u) - readlane(lq_r, 1u)) + (lq_s1 - lq_s0);
+                        if (tid < k_own) s_dS[tid] = tid == r_loc ? 0. : ((acc + tail1) + tail2) + tail3;
+                    }
+                    hb_fence();
+                    // The passes that are sequential in ascending s by definition -- dS_min, Z, C_s -- run on registers: the lane of
+                    // block s holds its value, and every lane adds the values one v_readlane at a time (64 blocks per trip).
+                    // dS_min (the 0 at r included)
+                    double mn = 0.;
+                    for (uint32_t c0 = 0; c0 < k_own; c0 += kWave) {
+                        const uint32_t tid = c0 + lane, cn = k_own - c0 < (uint32_t)kWave ? k_own - c0 : (uint32_t)kWave;
+                        const double x = tid < k_own ? s_dS[tid] : 0.;
+                        for (uint32_t s = 0; s < cn; ++s) {
+                            const double y = readlane(x, s);
+                            mn = y < mn ? y : mn;
+                        }
+                    }
+                    uint32_t s_new = r_loc;
+                    if (p.greedy) {
+                        // 4. the lowest s that attains the minimum; a move only strictly downhill
+                        if (!(mn < 0.)) continue;
+                        for (uint32_t c0 = 0; c0 < k_own; c0 += kWave) {
+                            const uint32_t tid = c0 + lane;
+                            const unsigned long long hit = __ballot(tid < k_own && tid != r_loc && s_dS[tid] == mn);
+                            if (hit) {
+                                s_new = c0 + (uint32_t)__ffsll((long long)hit) - 1u;
+                                break;
+                            }
+                        }
+                    } else {
+                        // 3. weights and Z = w_0 + w_1 + ... (0.0 + w_0 is w_0) ...
+                        double Z = 0.;
+                        for (uint32_t c0 = 0; c0 < k_own; c0 += kWave) {
+                            const uint32_t tid = c0 + lane, cn = k_own - c0 < (uint32_t)kWave ? k_own - c0 : (uint32_t)kWave;
+                            double w = 0.;
+                            if (tid < k_own) {
+                                const double x = p.beta * (s_dS[tid] - mn);
+                                w = x > 700. ? 0. : exp(-x);
+                                s_x[tid] = w;
+                            }
+                            for (uint32_t s = 0; s < cn; ++s) Z = Z + readlane(w, s);
+                        }
+                        hb_fence();
+                        // ... then P = w / Z and C_s = P_0 + ... + P_s: the first s with u < C_s, else the largest s with P_s > 0
+                        const uint64_t pos = (uint64_t)v0 + vi0 + q;  // position in the sweep
+                        const U4 A = phx_draw(p.seed, chain_gid, PHX_HEATBATH, sweeps_total * (uint64_t)p.n + pos);
+                        const double u = u53(A.x, A.y);
+                        double C = 0.;
+                        for (uint32_t c0 = 0; c0 < k_own; c0 += kWave) {
+                            const uint32_t tid = c0 + lane, cn = k_own - c0 < (uint32_t)kWave ? k_own - c0 : (uint32_t)kWave;
+                            const double P = tid < k_own ? s_x[tid] / Z : 0.;
+                            double C_mine = 0.;
+                            for (uint32_t s = 0; s < cn; ++s) {
+                                C = C + readlane(P, s);
+                                if (lane == s) C_mine = C;
+                            }
+                            const unsigned long long hit = __ballot(tid < k_own && u < C_mine);
+                            if (hit) {
+                                s_new = c0 + (uint32_t)__ffsll((long long)hit) - 1u;
+                                break;
+                            }
+                            const unsigned long long some = __ballot(P > 0.);
+                            if (some) s_new = c0 + 63u - (uint32_t)__clzll((long long)some);  // (P_r > 0: there is one)
+                        }
+                    }
+                    s_new = readlane(s_new, 0u);  // (the same in every lane; this tells the compiler)
+                    if (s_new == r_loc || s_new >= k_own) continue;
+                    // 5. apply_mcmc_moves, as mh_step does
+                    const double dS_new = s_dS[s_new];
+                    const uint32_t s_glob = own0 + s_new;
+                    hb_fence();  // all lanes have read nr / mr / eta before lane 0 rewrites them
+                    // eta in HBM (EL = false) and the label are written by lane 0 with a vector store and atomics that return
+                    // nothing, and read by all lanes of later steps with plain loads; hb_fence only stops code motion.  This
+                    // rests on a property of the hardware: the vector memory operations of ONE wave go through one L1 and
+                    // reach the L2 in issue order, so a load issued after a store or atomic of the same wave to the same
+                    // address sees it (the generic sweep_kernel relies on the same for its labels and its eta in HBM).  No other
+                    // wave reads or writes a chain's arrays during the call.
+                    if (lane == 0) {
+                        atomicSub(&nr[r], 1);
+                        atomicAdd(&nr[s_glob], 1);
+                        atomicSub(eta_at(r * D + deg), 1u);
+                        atomicAdd(eta_at(s_glob * D + deg), 1u);
+                        atomicSub(&mr[r], (int)deg);
+                        atomicAdd(&mr[s_glob], (int)deg);
+                        labels[v] = (uint8_t)s_glob;
+                    }
+                    for (uint32_t i = lane; i < nnz; i += kWave) {
+                        const uint32_t t = s_t[i];
+                        const int k = s_kt[i];
+                        atomicSub(&Mq(r_loc, t), k);
+                        atomicAdd(&Mq(s_new, t), k);
+                    }
+                    cum_dS = cum_dS + dS_new;
+                    ++moved_sweep;
+                    hb_fence();
+                }
+            }
+            __threadfence_block();  // the labels this phase wrote are read by the next phase's headers
+        }
+        ++sweeps_total;
+        ++sweeps_run;
+        moved += moved_sweep;
+        if (p.stop_when_settled && moved_sweep == 0) break;
+    }
+
+    // store the chain back
+    __syncthreads();
+    for (uint32_t i = lane; i < p.ka * p.kb; i += kWave) m_g[i] = mq[(i / p.kb) * S + (i % p.kb)];
+    for (uint32_t i = lane; i < K; i += kWave) {
+        mr_g[i] = mr[i];
+        nr_g[i] = nr[i];
+    }
+    if (EL)
+        for (uint32_t i = lane; i < K * D; i += kWave) eta_g[i] = eta_l[i];
+    if (lane == 0) {
+        sc->cum_dS = cum_dS;
+        sc->sweeps_total = sweeps_total;
+        sc->last_accepted = moved;
+        sc->last_sweeps = sweeps_run;
+    }
+}
+
+}  // namespace
+
+size_t heatbath_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds) {
+    const size_t K = (size_t)ka + kb, S = kb | 1u, kmax = std::max(ka, kb);
+    size_t lds = sizeof(double) * 4 * kmax + sizeof(int32_t) * ((size_t)ka * S + 2 * K + 3 * kmax) + (size_t)kWave * kWave;
+    if (eta_in_lds) lds += sizeof(uint32_t) * K * ((size_t)maxdeg + 1);
+    return (lds + 15) & ~(size_t)15;
+}
+
+hipError_t launch_heatbath(const HeatbathParams& p, size_t lds_bytes, hipStream_t stream) {
+    if (p.n_chains == 0 || p.sweeps == 0) return hipSuccess;
+    auto kern = p.eta_in_lds ? heatbath_kernel<true> : heatbath_kernel<false>;
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(p.n_chains), dim3(kWave), lds_bytes, stream, p);
+    return hipGetLastError();
+}
+
+}  // namespace bisbm
+
+namespace {
+
+int heatbath_leaf(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_settled) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HeatbathParams p{};
+    p.rowptr = h->d_rowptr, p.col = h->d_col;
+    p.n = (uint32_t)h->n, p.na = (uint32_t)h->na, p.nb = (uint32_t)h->nb;
+    p.ka = h->ka, p.kb = h->kb, p.maxdeg = h->maxdeg;
+    p.n_chains = h->n_chains, p.first_chain_id = h->first_chain_id, p.chain_gids = h->d_gids;
+    p.labels = h->d_labels, p.label_stride = h->label_stride;
+    p.m = h->d_m, p.m_r = h->d_m_r, p.n_r = h->d_n_r, p.eta = h->d_eta;
+    p.scalars = h->d_scalars;
+    p.lgamma_tab = h->d_lgamma, p.lgamma_size = h->tab->lg.size(), p.q_tab = h->d_q, p.q_stride = h->q_stride, p.log_tab = h->d_logtab;
+    p.seed = h->seed;
+    p.sweeps = sweeps;
+    p.greedy = std::isinf(beta) ? 1u : 0u;
+    p.beta = p.greedy ? 0. : beta;
+    p.stop_when_settled = stop_when_settled ? 1u : 0u;
+    // eta goes to LDS when that still leaves room for four chains per CU, as in the generic sweep kernel's plan
+    p.eta_in_lds = heatbath_lds_bytes(h->ka, h->kb, h->maxdeg, true) <= 40 * 1024 ? 1 : 0;
+    const size_t lds = heatbath_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0);
+    if (lds > kLdsPerCu) return fail(h, BISBM_ERR_UNSUPPORTED, "chain state needs %zu B of LDS (> 160 KiB)", lds);
+    h->ent_prev_valid = false;  // (the block state moves)
+    HIPCHK(h, launch_heatbath(p, lds, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BISBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bisbm_heatbath_run(bisbm_handle h, uint64_t sweeps, double beta, int stop_when_settled, uint64_t* moved_out, uint64_t* sweeps_out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (h->rng_mode == BISBM_RNG_MT19937_COMPAT)
+        return fail(h, BISBM_ERR_UNSUPPORTED, "heat-bath sweeps are defined in the Philox-mode arithmetic: this handle runs BISBM_RNG_MT19937_COMPAT");
+    if (!(beta > 0.)) return fail(h, BISBM_ERR_INVALID_ARG, "beta = %g: a value above 0 is needed (+inf: greedy)", beta);
+    if (h->temper.L)
+        return fail(h, BISBM_ERR_STATE, "replica exchange is on: sweeps run through bisbm_tempering_run (bisbm_tempering_set(h, 0, NULL) turns it off)");
+    if (any_wide(h))
+        return fail(h, BISBM_ERR_UNSUPPORTED, "heat-bath sweeps serve byte labels only (at most 256 blocks): merge the blocks down first");
+    for (bisbm_engine* e : leaves(h))
+        if (!e->state_ready) return fail(h, BISBM_ERR_STATE, "call bisbm_init or bisbm_shuffle before bisbm_heatbath_run");
+    if (sweeps == 0) {
+        for (uint32_t c = 0; c < h->n_chains; ++c) {
+            if (moved_out) moved_out[c] = 0;
+            if (sweeps_out) sweeps_out[c] = 0;
+        }
+        return BISBM_OK;
+    }
+    DeviceGuard keep;
+    if (int rc = each_leaf(h, [&](bisbm_engine* e) { return heatbath_leaf(e, sweeps, beta, stop_when_settled); })) return rc;
+    if (!moved_out && !sweeps_out) return BISBM_OK;
+    return bisbm_get_last_counts(h, moved_out, sweeps_out);
+}
+
+}  // extern "C"

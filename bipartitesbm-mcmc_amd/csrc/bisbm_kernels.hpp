@@ -371,6 +371,36 @@ struct SplitParams {
 constexpr uint32_t PHX_SPLIT = 6;
 constexpr uint32_t PHX_EXCHANGE = 7;  // replica exchange: idx = round * L + lower rung, chain = the ensemble's first global id
 constexpr uint32_t PHX_RESAMPLE = 8;  // population annealing: idx = resampling step, chain = the handle's first global id
+constexpr uint32_t PHX_HEATBATH = 9;  // heat-bath sweeps: idx = sweeps_total * n + position in the sweep, chain = the chain's global id
+
+// Heat-bath sweeps and greedy polishing (bisbm_heatbath.hip): `sweeps` sweeps of every chain of one engine, one wave per chain.
+struct HeatbathParams {
+    const uint32_t* rowptr;
+    const uint32_t* col;
+    uint32_t n, na, nb, ka, kb, maxdeg;
+    uint32_t n_chains, first_chain_id;
+    const uint32_t* chain_gids;  // see SweepParams
+    uint8_t* labels;             // byte labels
+    size_t label_stride;
+    int32_t* m;                  // [chain][ka*kb]
+    int32_t* m_r;                // [chain][K]
+    int32_t* n_r;                // [chain][K]
+    uint32_t* eta;               // [chain][K*(maxdeg+1)]
+    ChainScalars* scalars;       // cum_dS, sweeps_total advance; last_accepted = moves, last_sweeps = sweeps run
+    const double* lgamma_tab;
+    uint64_t lgamma_size;
+    const double* q_tab;
+    uint32_t q_stride;
+    const double* log_tab;
+    uint64_t seed;
+    uint64_t sweeps;
+    double beta;                 // finite, > 0 (unused when greedy)
+    uint32_t greedy;             // beta = +inf: the lowest argmin of dS, only strictly downhill, no draw
+    uint32_t stop_when_settled;  // a chain stops after the first sweep that moved nothing
+    int eta_in_lds;
+};
+size_t heatbath_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds);
+hipError_t launch_heatbath(const HeatbathParams& p, size_t lds_bytes, hipStream_t stream);
 
 hipError_t launch_split_rank(const SplitParams& p, hipStream_t stream);
 hipError_t launch_split_eval(const SplitParams& p, hipStream_t stream);

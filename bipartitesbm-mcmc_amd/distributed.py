@@ -286,6 +286,33 @@ def numpy_conditional_row(dS_row, r_local, free, beta):
     return P, float(P[r]), 0.0 - acc, margin
 
 
+def numpy_heatbath_choice(dS_row, P_row, r, free, u, greedy):
+    """Host statement of steps 3 and 4 of the heat-bath sweeps (include/bisbm.h, "Heat-bath sweeps and greedy polishing") for one
+    visited node: the node's new block within its type from its rows dS_s and P(s), its current block r within its type, whether
+    it is free, the uniform u of the step and whether the call is greedy (beta = +inf; u and P_row are not looked at then).  A
+    node that is not free stays.  Bit for bit the device's choice when the rows are the device's."""
+    r = int(r)
+    if not free:
+        return r
+    if greedy:
+        dS = [float(x) for x in dS_row]
+        best = 0
+        for s in range(1, len(dS)):
+            if dS[s] < dS[best]:
+                best = s
+        return best if dS[best] < 0.0 else r
+    u = float(u)
+    C, last = 0.0, r
+    for s, y in enumerate(P_row):
+        y = float(y)
+        C = y if s == 0 else C + y
+        if y > 0.0:
+            last = s
+        if u < C:
+            return s
+    return last
+
+
 def numpy_foldin_posterior(labels, m, m_r, n_r, ka, qtype, neighbours, alpha):
     """Host statement of steps 1 and 2 of the fold-in queries (include/bisbm.h, "Fold-in queries") for one chain and one virtual
     node: the posterior P[K_own] over the blocks of its type, bit for bit what the device computes.  `labels`, `m`, `m_r`, `n_r`:

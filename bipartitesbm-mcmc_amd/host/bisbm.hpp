@@ -287,6 +287,19 @@ public:
         return ancestor;
     }
     void population_reset() { check(bisbm_population_reset(h_)); }
+    // heat-bath sweeps and greedy polishing (include/bisbm.h): `sweeps` sweeps in which every node draws its block from its
+    // conditional ~ exp(-beta dS) (the moves per chain); greedy sweeps until a whole sweep moves nothing, at most max_sweeps
+    // (moves and sweeps per chain)
+    std::vector<uint64_t> heatbath_sweeps(uint64_t sweeps, double beta = 1.0) {
+        std::vector<uint64_t> moved(n_chains_);
+        check(bisbm_heatbath_run(h_, sweeps, beta, 0, moved.data(), nullptr));
+        return moved;
+    }
+    void polish(uint64_t max_sweeps, std::vector<uint64_t>& moved, std::vector<uint64_t>& sweeps) {
+        moved.assign(n_chains_, 0);
+        sweeps.assign(n_chains_, 0);
+        check(bisbm_heatbath_run(h_, max_sweeps, std::numeric_limits<double>::infinity(), 1, moved.data(), sweeps.data()));
+    }
     // pair scores (include/bisbm.h): the pairs (u of type a, v of type b), a sample of every counted chain, the sums and the
     // number of chain terms in them (the estimate of a pair is sum / terms)
     void pair_scores_set(const std::vector<uint32_t>& u, const std::vector<uint32_t>& v) {

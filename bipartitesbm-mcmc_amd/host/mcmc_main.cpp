@@ -6,7 +6,7 @@
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
 // --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
-// --conditionals, --conditionals_beta.
+// --conditionals, --conditionals_beta, --polish, --heatbath.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -57,6 +57,7 @@ const option_spec kOptions[] = {
     {"foldin", 0, 2},           {"foldin_alpha", 0, 1},
     {"conditionals", 0, 2},     {"conditionals_beta", 0, 1},
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
+    {"polish", 0, 1},           {"heatbath", 0, 0},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -197,6 +198,13 @@ void print_help(const char* argv0) {
                  "                                        log ratio ln Z(1/T_k) / Z(1/T_{k-1}) and the distinct ancestors of every\n"
                  "                                        step, and the total, are reported on stderr.\n"
                  "  --population_sweeps arg (=1)          With --population: sweeps per temperature.\n"
+                 "  --polish N                            After the annealing run or the merges and before the labels are printed:\n"
+                 "                                        up to N greedy sweeps (every node to its block of least description\n"
+                 "                                        length, only strictly downhill; Philox mode) until a whole sweep moves\n"
+                 "                                        nothing.  Moves and sweeps of every chain are reported on stderr.\n"
+                 "  --heatbath                            With --marginalize: burn-in and the sweeps between samples are heat-bath\n"
+                 "                                        sweeps (every node draws its block from its exact conditional; Philox\n"
+                 "                                        mode, not with --tempering) instead of Metropolis-Hastings sweeps.\n"
                  "  --score_pairs IN OUT                  With --marginalize: IN holds one pair `u v` per line (u of type a, v of\n"
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
@@ -457,6 +465,30 @@ int main(int argc, char const* argv[]) {
             }
             exchange_every = (uint32_t)k;
         }
+    }
+    // greedy polishing and heat-bath sampling: checked before anything else runs (the RNG mode below, once it is known)
+    uint64_t polish_sweeps = 0;
+    if (count("polish")) {
+        if (count("marginalize")) {
+            std::cerr << "--polish moves the annealed chains to a local minimum before they are printed: it cannot be combined with --marginalize.\n";
+            return 1;
+        }
+        const std::string v = single("polish", "");
+        char* end = nullptr;
+        const unsigned long long k = std::strtoull(v.c_str(), &end, 10);
+        if (v.empty() || *end != '\0' || v[0] == '-' || k == 0) {
+            std::cerr << "Invalid --polish. The largest number of greedy sweeps: an integer >= 1, e.g. --polish 100.\n";
+            return 1;
+        }
+        polish_sweeps = k;
+    }
+    if (count("heatbath") && !count("marginalize")) {
+        std::cerr << "--heatbath runs the sweeps of the marginalization mode as heat-bath sweeps: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("heatbath") && count("tempering")) {
+        std::cerr << "--heatbath cannot be combined with --tempering: replica exchange runs Metropolis-Hastings sweeps.\n";
+        return 1;
     }
     // population annealing: the temperatures and the sweeps per temperature are checked before anything else runs (one more
     // refusal, an initial partition without the -z block counts, waits below until the partition has been read: before the
@@ -886,6 +918,11 @@ int main(int argc, char const* argv[]) {
         return 1;
     }
     opt.rng_mode = rng == "philox" ? BISBM_RNG_PHILOX : BISBM_RNG_MT19937_COMPAT;
+    if ((polish_sweeps || count("heatbath")) && opt.rng_mode != BISBM_RNG_PHILOX) {
+        std::cerr << (polish_sweeps ? "--polish" : "--heatbath")
+                  << " runs in Philox mode only (mt19937-compat is the reference's verification path): add --rng philox.\n";
+        return 1;
+    }
     if (!ladder.empty()) {
         if (opt.n_chains % ladder.size()) {
             std::cerr << "--tempering with " << ladder.size() << " temperatures needs --chains a multiple of " << ladder.size() << " (got " << opt.n_chains
@@ -911,7 +948,18 @@ int main(int argc, char const* argv[]) {
     // ---- agglomerative drivers, mcmc_main.cc:349-451 ----
     const double sigma = 1.01;  // :349
     const float_vec_t agg_merge_kwargs(1, 0.f);
+    // --polish: greedy sweeps of every chain until a whole sweep moves nothing, before the best chain is picked
+    auto polish_chains = [&](blockmodel_t& blockmodel, uint32_t first_chain) {
+        if (!polish_sweeps) return;
+        std::vector<uint64_t> moved, sweeps;
+        blockmodel.polish(polish_sweeps, moved, sweeps);
+        std::ostringstream lines;  // (one write: the runs of --merge --nature --chains report from threads of their own)
+        for (size_t c = 0; c < moved.size(); ++c)
+            lines << "polish: chain " << first_chain + c << " moved " << moved[c] << " node(s) in " << sweeps[c] << " sweep(s)\n";
+        std::clog << lines.str();
+    };
     auto print_best = [&](blockmodel_t& blockmodel, bool with_k) {
+        polish_chains(blockmodel, 0);
         uint32_t best = 0;
         if (opt.n_chains > 1) {
             const std::vector<double> dl = blockmodel.entropy_all();
@@ -990,6 +1038,7 @@ int main(int argc, char const* argv[]) {
                             algorithm.anneal(blockmodel, &abrupt_cool_schedule, agg_merge_kwargs, (NA + NB) * 1, steps_await);
                         }
                         algorithm.anneal(blockmodel, &abrupt_cool_schedule, kwargs, sampling_steps, steps_await);  // :398
+                        polish_chains(blockmodel, c);
                         runs[c].dl = blockmodel.entropy_all()[0];
                         runs[c].labels = *blockmodel.get_memberships(0);
                         runs[c].ka = blockmodel.get_KA();
@@ -1108,6 +1157,8 @@ int main(int argc, char const* argv[]) {
             auto advance = [&](size_t sweeps) {
                 if (!ladder.empty())
                     blockmodel.tempering_run(sweeps, exchange_every);
+                else if (count("heatbath"))
+                    blockmodel.heatbath_sweeps(sweeps, 1.0);
                 else
                     algorithm.anneal(blockmodel, &constant_schedule, t1, sweeps * N, never);
             };
@@ -1470,6 +1521,7 @@ int main(int argc, char const* argv[]) {
             blockmodel.population_state(rounds, total);
             std::snprintf(line, sizeof(line), "population: %llu steps, log ratio total %.17g\n", (unsigned long long)rounds, total);
             std::clog << line;
+            polish_chains(blockmodel, 0);
             uint32_t best = 0;
             const std::vector<double> dl = blockmodel.entropy_all();
             for (uint32_t c = 1; c < opt.n_chains; ++c)
@@ -1486,6 +1538,7 @@ int main(int argc, char const* argv[]) {
                          : cooling_schedule == "constant"    ? &constant_schedule
                                                              : &abrupt_cool_schedule;
         algorithm.anneal(blockmodel, fn, kwargs, sampling_steps, steps_await);  // :462-482
+        polish_chains(blockmodel, 0);
         uint32_t best = 0;
         if (opt.n_chains > 1) {
             const std::vector<double> dl = blockmodel.entropy_all();

@@ -18,7 +18,7 @@ import numpy as np
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
-                similar=None, foldin=None, conditionals=None):
+                similar=None, foldin=None, conditionals=None, sampler="mh"):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -61,18 +61,15 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     None: every node): the queries are set, with zeroed sums, before the first sample, every marginal sample also takes one
     conditional sample, and model.conditionals_stats() is appended to the return value; with `align` the soft marginals use the
     reference the aligned histogram uses (taken over after the first marginal sample) and model.conditionals_marginals() --
-    (prob, terms) -- is appended after the stats.  The chains of this rank only."""
+    (prob, terms) -- is appended after the stats.  The chains of this rank only.
+    `sampler`: "mh" (the default: model.run_sweeps) or "heatbath" -- burn-in and the gaps between samples run through
+    model.heatbath_sweeps(sweeps, 1.0) (include/bisbm.h, "Heat-bath sweeps and greedy polishing"); with `tempering` a ValueError
+    (the library refuses heat-bath sweeps while replica exchange is on)."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
         return_counts = not multi
-    if tempering is not None:
-        model.set_tempering(tempering)
-
-        def advance(sweeps):
-            model.tempering_run(sweeps, exchange_every)
-    else:
-        advance = model.run_sweeps
+    advance = _advance(model, tempering, exchange_every, sampler)
     if burn_in_sweeps > 0:
         advance(burn_in_sweeps)
     if score_pairs is not None:
@@ -176,7 +173,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
 
 
 def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,
-                      reassign=False, tempering=None, exchange_every=1):
+                      reassign=False, tempering=None, exchange_every=1, sampler="mh"):
     """Mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): the chains are grouped into posterior modes and
     every mode gets an aligned histogram and a MAP of its own, in the numbering of its own reference.
     Exactly one of `threshold` and `mode_of_chain`: with `threshold` the grouping is model.partition_modes(threshold) taken
@@ -200,6 +197,7 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     throughout.  `tempering` (with `reassign` only; ValueError otherwise): a temperature ladder as in marginalize(); burn-in
     and the gaps between samples run through model.tempering_run(sweeps, exchange_every), the grouping and every sample take
     the chains on rung 0.  `mode_of_chain` with `reassign` is a ValueError: the anchors come from a grouping.
+    `sampler`: "mh" or "heatbath", as in marginalize().
     Chains spread over ranks (`shard`, or model.shard, with world_size > 1) raise ValueError: pooling modes across ranks is
     not done here."""
     if (threshold is None) == (mode_of_chain is None):
@@ -214,13 +212,7 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     from . import mode_assignment
     if mode_of_chain is not None:
         moc, n_modes = mode_assignment(mode_of_chain, model.n_chains)
-    if tempering is not None:
-        model.set_tempering(tempering)
-
-        def advance(sweeps):
-            model.tempering_run(sweeps, exchange_every)
-    else:
-        advance = model.run_sweeps
+    advance = _advance(model, tempering, exchange_every, sampler)
     if burn_in_sweeps > 0:
         advance(burn_in_sweeps)
     if threshold is not None:
@@ -257,6 +249,21 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         moved = int(sum(_co_members(modes, c) != _co_members(after, c) for c in range(len(modes["chains"]))))
     return {"modes": modes, "labels": labels, "top": top, "counts": counts, "terms": state["terms"], "weights": state["weights"],
             "ref_chain": state["ref_chain"], "moved": moved}
+
+
+def _advance(model, tempering, exchange_every, sampler):
+    """The call that runs the sweeps of the burn-in and between samples: MH at T = 1, heat-bath sweeps at beta = 1, or -- with
+    a ladder, which is set here -- replica exchange."""
+    if sampler not in ("mh", "heatbath"):
+        raise ValueError("sampler must be \"mh\" or \"heatbath\", not %r" % (sampler,))
+    if tempering is not None:
+        if sampler == "heatbath":
+            raise ValueError("sampler=\"heatbath\" cannot be combined with tempering: replica exchange runs MH sweeps")
+        model.set_tempering(tempering)
+        return lambda sweeps: model.tempering_run(sweeps, exchange_every)
+    if sampler == "heatbath":
+        return lambda sweeps: model.heatbath_sweeps(sweeps, 1.0)
+    return model.run_sweeps
 
 
 def _co_members(grouping, i):

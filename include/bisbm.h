@@ -28,7 +28,8 @@ extern "C" {
  *    bisbm_marginals_get_mode, bisbm_marginals_map_mode), distances to reference partitions (bisbm_partition_distances_to),
  *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
  *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*), population annealing
- *    (bisbm_population_*), node conditionals (bisbm_conditionals_*).  Additions only. */
+ *    (bisbm_population_*), node conditionals (bisbm_conditionals_*), heat-bath sweeps and greedy polishing
+ *    (bisbm_heatbath_run).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -523,8 +524,8 @@ int bisbm_foldin_topk(bisbm_handle h, uint32_t what, uint32_t k, int exclude_lis
  *   row for a chain that was not counted, a stride below some chain's K_own BISBM_ERR_INVALID_ARG); BISBM_ERR_STATE without
  *   KEEP_LAST or before the first sample; dS_out or p_out may be NULL.
  * Out of scope: conditionals in mt19937-compat arithmetic, two-byte labels, pooling over processes, a library-chosen
- * reference, per-mode soft histograms, moving nodes (greedy polishing, Gibbs sweeps), top-k of the least settled nodes on the
- * device (with n doubles per statistic the host sorts them). */
+ * reference, per-mode soft histograms, top-k of the least settled nodes on the device (with n doubles per statistic the host
+ * sorts them).  Moving nodes by these rows is bisbm_heatbath_run below. */
 #define BISBM_COND_KEEP_LAST 1u
 int bisbm_conditionals_set(bisbm_handle h, uint32_t n_queries, const uint32_t *queries /* NULL: all n nodes */, double beta,
                            uint32_t what);
@@ -537,6 +538,41 @@ int bisbm_conditionals_get_marginals(bisbm_handle h, double *prob_out /* n_queri
                                      uint64_t *terms_out);
 int bisbm_conditionals_get_last(bisbm_handle h, uint32_t query_index, uint32_t stride, double *dS_out,
                                 double *p_out /* n_chains * stride each, either may be NULL */);
+
+/* Heat-bath sweeps and greedy polishing: nodes moved by their conditionals (no reference counterpart).  Where the MH step draws
+ * one target block and accepts or rejects it, a heat-bath (Gibbs) update draws the node's new block from its exact conditional
+ * P(b_v = s | rest) ~ exp(-beta dS_s), and the greedy update (beta = +inf) takes the block of the lowest dS.  For every chain,
+ * `sweeps` sweeps of n node updates; Philox mode and byte labels only.
+ *   1. VISIT ORDER: exactly the MH sweep's.  Sweep index = the chain's sweeps_total; the type-a class first, then type b, each
+ *      through the tiled keyed order of DESIGN.md section 4 with the keys Philox(seed; idx = 2 * sweeps_total (+ 1 for type b),
+ *      chain = global chain id, purpose 2).  sweeps_total advances by one per sweep run, so no later call of any kind replays
+ *      a visit order.
+ *   2. ROW: for the visited node v with current block r, dS_s and P(s) over all blocks s of v's type as steps 1-3 of "Node
+ *      conditionals" with this call's beta, the same f64 operations in the same order: bit-equal to what
+ *      bisbm_conditionals_accumulate (KEEP_LAST) returns for that node on the same state.
+ *   3. CHOICE, finite beta > 0: a node that is not free stays.  For a free node u = the 53-bit uniform
+ *      ((x << 32 | y) >> 11) * 2^-53 of the first two words x, y of Philox(seed; idx = sweeps_total * n + position in the sweep,
+ *      chain = global chain id, purpose 9); C_s = P_0 + ... + P_s, added one at a time in ascending s; the new block is the
+ *      first s with u < C_s, and if there is none (C of the last block rounded below 1) the largest s with P_s > 0.
+ *   4. CHOICE, beta = +inf (greedy): a node that is not free stays.  For a free node s* = the lowest s that attains min_s dS_s
+ *      over all s including r; the node moves iff dS_{s*} < 0 strictly.  No random draw is used.
+ *   5. APPLY: a move with s != r updates the label, m, m_r, n_r and eta as an accepted MH step does and adds dS_s onto the
+ *      chain's running sum (bisbm_get_cum_dS) with one f64 add.  A node never leaves a block it is alone in (the FREE rule).
+ *   6. stop_when_settled != 0: a chain stops after the first sweep in which it moved nothing; that sweep counts in sweeps_out,
+ *      and sweeps_total advances only by the sweeps actually run.  Meaningful with beta = +inf (the partition is then a local
+ *      minimum of the description length under single-node moves), allowed with any beta.
+ *   7. moved_out[c] = moves with s != r, sweeps_out[c] = sweeps run; bisbm_get_last_counts reports the same two numbers.  The
+ *      MH object's accu_r, anneal()'s early-stop bookkeeping, the population genealogy and every sum of the analysis calls
+ *      (marginals, pair scores, conditionals, ...) are untouched.
+ * Served: chains grouped by shape (group by group), several devices behind one handle (everything is keyed by the global chain
+ * id: the result equals one device with all the chains), static or anchored modes being set.
+ * Refused, with a message and nothing changed: BISBM_RNG_MT19937_COMPAT and two-byte labels BISBM_ERR_UNSUPPORTED; replica
+ * exchange on BISBM_ERR_STATE (as bisbm_anneal); before bisbm_init / bisbm_shuffle BISBM_ERR_STATE; beta NaN, <= 0 or -inf
+ * BISBM_ERR_INVALID_ARG.  sweeps = 0 is a no-op that returns BISBM_OK (the outputs are zeroed).
+ * Out of scope: a temperature per chain or per rung, heat-bath sweeps inside bisbm_tempering_run / bisbm_population_run,
+ * mt19937-compat arithmetic, wide handles, blocked or multi-node moves. */
+int bisbm_heatbath_run(bisbm_handle h, uint64_t sweeps, double beta, int stop_when_settled,
+                       uint64_t *moved_out /* n_chains, may be NULL */, uint64_t *sweeps_out /* n_chains, may be NULL */);
 
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
