@@ -21,6 +21,22 @@ def random_graph(seed, na, nb, ne, ka, kb, hubs=0, isolated=0):
     return rowptr, col
 
 
+def unequal_groups_graph(seed, sizes_a, sizes_b, mean_degree):
+    """Planted groups of unequal sizes (block i of type a goes with block i of type b; both lists have the same length): per
+    edge, a is uniform over the type-a nodes, the block of b is a's with probability 0.8 and otherwise uniform over the blocks,
+    and b is uniform inside its block.  (na + nb) * mean_degree / 2 edges, multi-edges kept.  Returns (rowptr, col), na, nb."""
+    sizes_a, sizes_b = np.asarray(sizes_a, dtype=np.int64), np.asarray(sizes_b, dtype=np.int64)
+    na, nb, k = int(sizes_a.sum()), int(sizes_b.sum()), len(sizes_a)
+    ne = (na + nb) * mean_degree // 2
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, na, ne)
+    block_a = np.searchsorted(np.cumsum(sizes_a), a, side="right")
+    block_b = np.where(rng.random(ne) < 0.8, block_a, rng.integers(0, k, ne))
+    first_b = np.concatenate([[0], np.cumsum(sizes_b)[:-1]])
+    b = na + first_b[block_b] + (rng.random(ne) * sizes_b[block_b]).astype(np.int64)
+    return O.edge_to_csr(a.astype(np.uint64), b.astype(np.uint64), na + nb), na, nb
+
+
 CASES = [
     # name, na, nb, edges, ka, kb, eps, hubs, isolated
     ("tiny", 12, 9, 40, 3, 2, 0.5, 0, 0),
@@ -41,6 +57,8 @@ CASES = [
     ("mid_tier", 5300, 5300, 26500, 2, 2, 1.0, 0, 0),
     # ... k / sqrt(n) around 10 (blocks of ~1200 nodes): the converged log_q tier in the hot step
     ("mid_tier_low", 2400, 2400, 28800, 2, 2, 1.0, 0, 0),
+    # ... k / sqrt(n) around 15.5 (blocks of 1900 nodes, m_r ~ 15000): log_q_closed2 in every block, 13 <= u <= 18
+    ("closed2_tier", 3800, 3800, 30000, 2, 2, 1.0, 0, 0),
     # ... and a dense graph (mean degree 40, blocks of 1000 nodes): k / sqrt(n) around 5, the low converged tier
     ("dense_low_tier", 2000, 2000, 80000, 2, 2, 1.0, 0, 0),
     # K = 32 + 32 with a hub of degree 600: eta (64 x 601 words) does not fit the LDS budget and stays in HBM while the
@@ -62,7 +80,20 @@ CASE = {c[0]: c for c in CASES}
 # The log_q tier every block of a case reaches after shuffle_bisbm, for the cases whose name or comment claims one
 # (tests/test_oracle.py guards this, so that a case drifting into another tier fails instead of passing vacuously).
 CASE_TIERS = {"big_m_r": "literal", "direct_tier": "closed", "direct_tier_wide": "table", "direct_tier_k40": "closed",
-              "mid_tier": "closed", "mid_tier_low": "mid", "dense_low_tier": "low", "eps0_direct": "closed"}
+              "mid_tier": "closed", "mid_tier_low": "mid", "dense_low_tier": "low", "eps0_direct": "closed", "closed2_tier": "closed2"}
+
+# Shapes of the heat-bath replays alone (tests/test_gpu_heatbath.py; the layout of CASES, graphs from random_graph(11, ...)): the
+# lane-chunk edges of heatbath_kernel.  They stay out of CASES, so the GPU-vs-oracle matrix does not grow by them.
+HEATBATH_CASES = {c[0]: c for c in [
+    # 64 targets in phase a (one full chunk of lanes), 65 in phase b (a second chunk of one lane); eta in LDS
+    ("hb_k64_k65", 400, 400, 4000, 64, 65, 1.0, 0, 0),
+    # 130 targets in phase a: three chunks of lanes
+    ("hb_k130", 400, 400, 4000, 130, 3, 1.0, 0, 0),
+    # 100 type-b blocks and a type-a hub of degree ~610: a non-zero list longer than one wave; eta in HBM
+    ("hb_long_list", 300, 200, 3000, 3, 100, 1.0, 1, 0),
+    # 10 + 10 blocks and the hub: eta in HBM with few rows, so the entries of r and s are rewritten and re-read often
+    ("hb_eta_in_hbm", 300, 200, 3000, 10, 10, 1.0, 1, 0),
+]}
 
 LOG_Q_TIERS = ("table", "closed", "closed2", "mid", "low", "literal")
 

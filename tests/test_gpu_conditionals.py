@@ -37,7 +37,7 @@ EPS = 2.0 ** -52
 NA, NB = 903, 701
 SEED = 9
 SHAPES = [(4, 4), (6, 5), (32, 32), (64, 64), (200, 56), (1, 255)]
-TIER_CASES = ["dense_low_tier", "mid_tier_low", "mid_tier", "direct_tier", "big_m_r"]
+TIER_CASES = ["dense_low_tier", "mid_tier_low", "closed2_tier", "mid_tier", "direct_tier", "big_m_r"]
 
 
 def _bits(x):

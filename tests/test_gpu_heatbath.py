@@ -46,7 +46,7 @@ _GRAPHS = {}
 
 def _case(name):
     if name not in _GRAPHS:
-        _, na, nb, ne, ka, kb, eps, hubs, iso = cases.CASE[name]
+        _, na, nb, ne, ka, kb, eps, hubs, iso = cases.HEATBATH_CASES[name] if name in cases.HEATBATH_CASES else cases.CASE[name]
         _GRAPHS[name] = (cases.random_graph(11, na, nb, ne, ka, kb, hubs, iso), na, nb, ka, kb, eps)
     return _GRAPHS[name]
 
@@ -93,20 +93,32 @@ def _assert_state_is_a_rebuild(m, rowptr, col, c):
 
 
 # ------------------------------------------------------------------------------------------------------- 1. exact replay
-def _replay(name, sweeps, beta, after_polish=False):
+def _replay(name, sweeps, beta, after_polish=False, alone=True, labels=None):
+    """alone: a node of each type is made the only one of its block first (on a graph of 2 + 2 blocks that would turn the sizes
+    into (1, n - 1) and take the blocks out of their log_q tier); labels: every chain starts from these through init_bisbm, with
+    no sweep run before.  Returns what the callers assert their edge on: per free step (v, deg, the number of distinct blocks
+    among the neighbours, k_own, r, s, whether the device's P row holds an exact 0), r and s within the type, and the replayed
+    chain's (m_r, n_r) before and after the device call."""
     (rowptr, col), na, nb, ka, kb, eps = _case(name)
     n, chains, greedy = na + nb, 3, beta == INF
-    m = _model(name, chains, first_chain_id=FIRST_ID)
-    m.shuffle_bisbm()
-    m.run_sweeps(3)
-    _make_alone(m, na, ka, kb, range(chains))
-    c, gid, sweep0 = chains - 1, FIRST_ID + chains - 1, 3  # (three MH sweeps so far: the chain's sweep index)
+    m = _model(name, chains, first_chain_id=FIRST_ID, labels=labels)
+    if labels is None:
+        m.shuffle_bisbm()
+        m.run_sweeps(3)
+    else:
+        m.init_bisbm()
+    if alone:
+        _make_alone(m, na, ka, kb, range(chains))
+    # (three MH sweeps so far, or none: the chain's sweep index)
+    c, gid, sweep0 = chains - 1, FIRST_ID + chains - 1, 3 if labels is None else 0
     if after_polish:  # a polish that stops early first: the counter has advanced by the sweeps it ran, and by no more
         ran_before = m.polish(100)[1]
         assert (ran_before < 100).all() and len(set(ran_before.tolist())) > 1  # (the chains' counters now differ)
         sweep0 += int(ran_before[c])
     lab = m.get_memberships(c).astype(np.int64)
     cum, S0 = m.get_entropy()[c], m.entropy()[c]
+    before = m.get_m_r(c).copy(), m.get_n_r(c).copy()
+    rp, steps = rowptr.astype(np.int64), []
     helper = _model(name, 1, labels=lab.astype(np.uint32))
     helper.conditionals_set(None, 1.0 if greedy else beta, keep_last=True)
 
@@ -121,7 +133,7 @@ def _replay(name, sweeps, beta, after_polish=False):
         moved_gpu, sweeps_gpu = m.heatbath_sweeps(sweeps, beta), None
     L = O.lib()
     for v, k in ((1, ka), (na + 1, kb)):  # (the set-up: a node alone in its block in every type that has two blocks)
-        assert k < 2 or after_polish or int((lab == lab[v]).sum()) == 1
+        assert k < 2 or after_polish or not alone or int((lab == lab[v]).sum()) == 1
     moved, total, free_seen, ran = 0, 0.0, 0, 0
     for sw in range(sweeps):
         order = [int(L.orc_philox_visit(SEED, gid, sweep0 + sw, na, nb, i)) for i in range(n)]
@@ -135,6 +147,9 @@ def _replay(name, sweeps, beta, after_polish=False):
             dS, P = (x[0] for x in helper.conditionals_last(v))
             o = philox(SEED, gid, B.PHILOX_PURPOSE_HEATBATH, (sweep0 + sw) * n + pos)
             s = D.numpy_heatbath_choice(dS, P, r, free, u53(o[0], o[1]), greedy)
+            if free:
+                steps.append((v, int(rp[v + 1] - rp[v]), len(set(lab[col[rp[v]:rp[v + 1]]].tolist())), k_own, r, s,
+                              bool((P[:k_own] == 0.0).any())))
             if s != r:
                 lab[v] = lo + s
                 cum = cum + dS[s]
@@ -161,8 +176,10 @@ def _replay(name, sweeps, beta, after_polish=False):
     assert abs((S1 - S0) - total) <= 1e-9 * abs(S0)
     for other in range(chains - 1):  # (the other chains ran too, and are consistent)
         _assert_state_is_a_rebuild(m, rowptr, col, other)
+    after = m.get_m_r(c).copy(), m.get_n_r(c).copy()
     m.close()
     helper.close()
+    return {"steps": steps, "before": before, "after": after}
 
 
 @pytest.mark.parametrize("name,sweeps", [("tiny", 2), ("ka1", 2), ("hubs_isolated", 2), ("huge_hub", 1), ("wideK", 1)])
@@ -176,6 +193,156 @@ def test_greedy_sweeps_are_the_host_replay():
 
 def test_heat_bath_sweeps_after_a_polish_that_stopped_early_are_the_host_replay():
     _replay("hubs_isolated", 1, 1.0, after_polish=True)
+
+
+# ------------------------------------------------------------------------------- 1a. the replay through the log_q tiers
+# log_q<true> looks at the log n it is handed only past the q table (n > 10^4); the kernel hands it over per evaluation -- the
+# target after and before the move, then the r side by lane parity -- so only blocks outside the table tell a mixed-up triple.
+def _assert_every_block_in_its_tier(rec, name):
+    for when in ("before", "after"):
+        got = cases.log_q_tiers(*rec[when])
+        assert (got == cases.CASE_TIERS[name]).all(), (name, when, cases.tier_counts(*rec[when]))
+
+
+def _reassign_every_fifth(lab, na, ka, kb):
+    """about 20 % of the nodes get a label drawn uniformly within their type (seeded)"""
+    lab = np.asarray(lab).astype(np.int64)
+    rng = np.random.default_rng(12)
+    again = np.flatnonzero(rng.random(len(lab)) < 0.2)
+    lab[again] = np.where(again < na, rng.integers(0, ka, len(again)), ka + rng.integers(0, kb, len(again)))
+    return lab.astype(np.uint32)
+
+
+@pytest.mark.parametrize("name", ["dense_low_tier", "mid_tier_low", "closed2_tier", "mid_tier"])
+def test_heat_bath_sweep_through_a_log_q_tier_is_the_host_replay(name):
+    _assert_every_block_in_its_tier(_replay(name, 1, 1.0, alone=False), name)
+
+
+def test_heat_bath_sweep_through_the_literal_log_q_tier_is_the_host_replay():
+    """big_m_r plants 2 + 3 groups: group i of type a goes with group i of type b, so the third group of type b receives the
+    uniform fifth of the edges only, some 4000 ends, and any labelling near the planted one has a block on the q table -- which
+    is where the three MH sweeps of the usual start take the chain.  The start here keeps all five blocks past the table for
+    the one sweep: the first group of type b split evenly over the first and the third block (about 14 000 ends each), the
+    other two groups together in the second."""
+    name = "big_m_r"
+    (rowptr, col), na, nb, ka, kb, eps = _case(name)
+    b = np.arange(nb)
+    lab = O.contiguous_labels(na, nb, ka, kb)
+    lab[na:] = ka + np.where(b < nb // 3, 2 * (b % 2), 1)
+    rec = _replay(name, 1, 1.0, alone=False, labels=lab)
+    _assert_every_block_in_its_tier(rec, name)
+    assert np.median([deg for _, deg, *_ in rec["steps"]]) > 256  # (rows of about 400 neighbours: the tail loop past the LDS labels)
+
+
+def test_greedy_sweep_through_a_log_q_tier_is_the_host_replay():
+    """(from the planted labels with every fifth node reassigned: a greedy sweep from the shuffled start empties two of the
+    four blocks far enough to leave the tier)"""
+    name = "mid_tier_low"
+    (rowptr, col), na, nb, ka, kb, eps = _case(name)
+    lab = _reassign_every_fifth(O.contiguous_labels(na, nb, ka, kb), na, ka, kb)
+    _assert_every_block_in_its_tier(_replay(name, 1, INF, alone=False, labels=lab), name)
+
+
+MIXED_SIZES = (700, 1900, 3500)
+
+
+def test_heat_bath_sweep_with_three_tiers_in_one_evaluation_is_the_host_replay():
+    """blocks of 700, 1900 and 3500 nodes per type at mean degree 8: m_r about 8000 / 15000 / 26000, the q table, log_q_closed2
+    and log_q_closed side by side in the lanes of one evaluation.  From the planted labels with every fifth node reassigned
+    uniformly within its type (the planted labelling itself would leave a sweep at beta = 1 next to nothing to move)."""
+    name, k = "mixed_tiers", len(MIXED_SIZES)
+    if name not in _GRAPHS:
+        graph, na, nb = cases.unequal_groups_graph(11, MIXED_SIZES, MIXED_SIZES, 8)
+        _GRAPHS[name] = (graph, na, nb, k, k, 1.0)
+    _, na, nb, ka, kb, _ = _GRAPHS[name]
+    lab = _reassign_every_fifth(O.labels_from_sizes(MIXED_SIZES + MIXED_SIZES), na, ka, kb)
+    rec = _replay(name, 1, 1.0, alone=False, labels=lab)
+    for when in ("before", "after"):
+        counts = cases.tier_counts(*rec[when])
+        assert min(counts["table"], counts["closed2"], counts["closed"]) >= 1, (when, counts, rec[when])
+
+
+# ------------------------------------------------------------------- 1b. lane chunks, list lengths, row lengths, eta in HBM
+def _moves(rec, type_b, na):
+    return [(r, s) for v, _, _, _, r, s, _ in rec["steps"] if (v >= na) == type_b and s != r]
+
+
+@pytest.mark.parametrize("beta,sweeps", [(1.0, 1), (INF, 1)])
+def test_64_and_65_targets_are_the_host_replay(beta, sweeps):
+    """64 blocks of type a: exactly one full chunk of target lanes; 65 of type b: a second chunk that holds one target"""
+    name = "hb_k64_k65"
+    na = _case(name)[1]
+    rec = _replay(name, sweeps, beta)
+    assert any(63 in rs for rs in _moves(rec, False, na)), "no move into or out of the last block of type a"
+    assert any(64 in rs for rs in _moves(rec, True, na)), "no move into or out of the last block of type b"
+
+
+@pytest.mark.parametrize("beta", [1.0, INF])
+def test_130_targets_are_the_host_replay(beta):
+    """three chunks of target lanes, the last one two wide"""
+    name = "hb_k130"
+    na = _case(name)[1]
+    rec = _replay(name, 1, beta)
+    assert any(s >= 128 for r, s in _moves(rec, False, na)), "no move into the third chunk"
+
+
+def _eta_is_outside_the_lds(name):
+    (rowptr, col), na, nb, ka, kb, eps = _case(name)
+    return 4 * (ka + kb) * (int(np.diff(rowptr.astype(np.int64)).max()) + 1) > 40 * 1024
+
+
+def test_a_list_longer_than_one_wave_is_the_host_replay():
+    """100 blocks of type b and a type-a hub with some 610 neighbours: its list of non-zero (t, k_t) runs into a second chunk of
+    64 lanes; six type-b rows of about 400 neighbours; eta in HBM"""
+    name = "hb_long_list"
+    assert _eta_is_outside_the_lds(name)
+    rec = _replay(name, 1, 1.0, alone=False)
+    assert max(blocks for _, _, blocks, *_ in rec["steps"]) > 64
+    hub = [(deg, blocks) for v, deg, blocks, *_ in rec["steps"] if v == 0]  # (a step is recorded only when the node is free)
+    assert len(hub) == 1 and hub[0][0] > 600 and hub[0][1] > 64, hub
+
+
+@pytest.mark.parametrize("beta,sweeps", [(1.0, 2), (INF, 1)])
+def test_eta_in_hbm_is_the_host_replay(beta, sweeps):
+    """10 + 10 blocks and a hub of degree 600: eta stays in HBM, where lane 0 rewrites the entries of r and s with atomics and
+    every lane reads them back with plain loads in later steps -- with so few rows, soon after"""
+    name = "hb_eta_in_hbm"
+    assert _eta_is_outside_the_lds(name)
+    _replay(name, sweeps, beta)
+
+
+DEGREES = (1, 63, 64, 65, 127, 128, 129, 255, 256, 257)
+
+
+def test_rows_of_64_and_65_neighbours_and_a_class_of_64_and_65_nodes_are_the_host_replay():
+    """rows that end at, one past and far past the 64 labels the chunk header parks in LDS (and at 128 and 256, the trip counts
+    of the tail loop); 64 nodes of type a: one chunk of exactly 64 positions; 65 of type b: a chunk of 64 and a chunk of one"""
+    name, na, nb, ka, kb = "hb_degrees", 64, 65, 3, 4
+    if name not in _GRAPHS:
+        a, b = [], []
+        for i in range(na):
+            for j in range(DEGREES[i] if i < len(DEGREES) else 3):
+                a.append(i)
+                b.append(na + ((11 * i + j) if i < len(DEGREES) else (7 * i + 5 * j)) % nb)
+        _GRAPHS[name] = (O.edge_to_csr(np.array(a, dtype=np.uint64), np.array(b, dtype=np.uint64), na + nb), na, nb, ka, kb, 1.0)
+    deg = np.diff(_GRAPHS[name][0][0].astype(np.int64))
+    assert tuple(deg[:len(DEGREES)]) == DEGREES and (deg[len(DEGREES):na] == 3).all()
+    assert deg[na:].min() == 21 and deg[na:].max() == 24  # (multi-edges are kept)
+    rec = _replay(name, 2, 1.0, alone=False)
+    seen = {d for v, d, *_ in rec["steps"] if v < na}
+    assert set(DEGREES) <= seen, sorted(set(DEGREES) - seen)
+
+
+# ------------------------------------------------------------------------------------------ 1c. the choice at extreme beta
+def test_exact_zeros_in_P_at_a_large_beta_are_the_host_replay():
+    """beta (dS - dS_min) > 700 makes w an exact 0: the first s with u < C_s, else the largest s with P_s > 0"""
+    rec = _replay("hubs_isolated", 1, 200.0)
+    assert any(zero for *_, zero in rec["steps"])
+
+
+def test_a_nearly_flat_P_at_a_small_beta_is_the_host_replay():
+    rec = _replay("hubs_isolated", 1, 1e-3)
+    assert 2 * sum(s != r for _, _, _, _, r, s, _ in rec["steps"]) >= len(rec["steps"])
 
 
 # ------------------------------------------------------------------------------------------- 2. stationary distribution
