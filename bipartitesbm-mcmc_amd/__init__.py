@@ -53,6 +53,9 @@ FOLDIN_CAND_TILE, FOLDIN_TILE = 1024, 8
 COND_KEEP_LAST = 1
 # the Philox purpose of the heat-bath draw (csrc/bisbm_kernels.hpp: PHX_HEATBATH; DESIGN.md section 4 lists them all)
 PHILOX_PURPOSE_HEATBATH = 9
+# ... and of the pair reshuffles (PHX_RESHUFFLE), and the record type of a move without a pair (BISBM_RESHUFFLE_NONE)
+PHILOX_PURPOSE_RESHUFFLE = 10
+RESHUFFLE_NONE = 0xFFFFFFFF
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -61,6 +64,15 @@ _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
 _f64p = C.POINTER(C.c_double)
 _f32p = C.POINTER(C.c_float)
+
+
+class ReshuffleRecord(C.Structure):
+    """bisbm_reshuffle_record (include/bisbm.h, "Pair reshuffles")"""
+    _fields_ = [("type", C.c_uint32), ("r", C.c_uint32), ("s", C.c_uint32), ("M", C.c_uint32),
+                ("dS_fwd", C.c_double), ("dS_rev", C.c_double), ("q_fwd_mant", C.c_double), ("q_rev_mant", C.c_double),
+                ("q_fwd_exp", C.c_int32), ("q_rev_exp", C.c_int32), ("u_acc", C.c_double), ("A", C.c_double),
+                ("accepted", C.c_uint32), ("reserved", C.c_uint32)]
+
 
 # every symbol include/bisbm.h and include/bisbm_io.h declare: (restype, argtypes)
 ABI = {
@@ -137,6 +149,10 @@ ABI = {
     "bisbm_conditionals_get_marginals": (C.c_int, [C.c_void_p, _f64p, _u32p, _u64p]),
     "bisbm_conditionals_get_last": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p, _f64p]),
     "bisbm_heatbath_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_int, _u64p, _u64p]),
+    "bisbm_reshuffle_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, _u64p]),
+    "bisbm_reshuffle_get_last": (C.c_int, [C.c_void_p, C.POINTER(ReshuffleRecord)]),
+    "bisbm_reshuffle_get_total": (C.c_int, [C.c_void_p, _u64p]),
+    "bisbm_debug_exp": (C.c_int, [C.c_void_p, _f64p, C.c_size_t, _f64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
@@ -577,6 +593,38 @@ class BlockModel:
         minimum of the description length under single-node moves -- when its last sweep moved nothing, which
         sweeps < max_sweeps implies."""
         return self._heatbath(max_sweeps, float("inf"), True)
+
+    # -- pair reshuffles (include/bisbm.h, "Pair reshuffles")
+    def reshuffle(self, moves, scans=3, beta=1.0):
+        """`moves` pair reshuffles per chain: the nodes of two blocks of one type are divided afresh between the two by
+        `scans` restricted Gibbs scans from a random launch state and one more that is the proposal, accepted or rejected as a
+        whole, so exp(-beta S) stays exactly invariant.  The default of 3 scans is a convention from the literature (Jain and
+        Neal's split-merge), not a measurement.  Returns the accepted moves per chain (uint64 [n_chains])."""
+        acc = np.zeros(self.n_chains, dtype=np.uint64)
+        self._check(self._L.bisbm_reshuffle_run(self._h, int(moves), int(scans), float(beta), _p(acc, _u64p)))
+        return acc
+
+    def reshuffle_last(self):
+        """The last move of the last reshuffle() of every chain: a list of dicts with type (0: a, 1: b, RESHUFFLE_NONE: the
+        shape has no pair), r, s (global labels), M, dS_fwd, dS_rev, q_fwd and q_rev as (mantissa, exponent), u_acc, A, accepted."""
+        rec = (ReshuffleRecord * self.n_chains)()
+        self._check(self._L.bisbm_reshuffle_get_last(self._h, rec))
+        return [{"type": x.type, "r": x.r, "s": x.s, "M": x.M, "dS_fwd": x.dS_fwd, "dS_rev": x.dS_rev,
+                 "q_fwd": (x.q_fwd_mant, x.q_fwd_exp), "q_rev": (x.q_rev_mant, x.q_rev_exp), "u_acc": x.u_acc, "A": x.A,
+                 "accepted": bool(x.accepted)} for x in rec]
+
+    def reshuffles_total(self):
+        """Pair reshuffles proposed over every chain's lifetime (the index of the next move's Philox draws)."""
+        out = np.zeros(self.n_chains, dtype=np.uint64)
+        self._check(self._L.bisbm_reshuffle_get_total(self._h, _p(out, _u64p)))
+        return out
+
+    def debug_exp(self, x):
+        """exp(x) as the device evaluates it (the host replays of the pair reshuffles take their exponentials from here)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.zeros(len(x), dtype=np.float64)
+        self._check(self._L.bisbm_debug_exp(self._h, _p(x, _f64p), len(x), _p(out, _f64p)))
+        return out
 
     # -- replica exchange (include/bisbm.h, "Replica exchange")
     def set_tempering(self, ladder):
@@ -1316,6 +1364,6 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice,  # noqa: E402,F401
+from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice, numpy_reshuffle_accept, numpy_reshuffle_launch, numpy_reshuffle_pair, numpy_reshuffle_q, numpy_reshuffle_step,  # noqa: E402,F401
                           numpy_pair_scores, numpy_query_topk, shard_chains)
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

@@ -20,6 +20,7 @@
 //   bisbm_foldin.hip     fold-in queries: block posterior, recommendations and peers of a node that is not in the graph; kernels and C ABI
 //   bisbm_conditionals.hip  node conditionals: dS of every target block of a node, the conditional and its pooled terms, soft marginals; kernels and C ABI
 //   bisbm_heatbath.hip   heat-bath sweeps and greedy polishing: nodes moved by their conditionals; kernel and C ABI
+//   bisbm_reshuffle.hip  pair reshuffles: two blocks' nodes divided afresh in one accepted or rejected move; kernel and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
 //
@@ -305,6 +306,16 @@ struct ConditionalState {
     AlignScratch scratch;         // (its own: the permutations of a conditional sample are not the marginal histogram's)
 };
 
+// Pair reshuffles (bisbm_reshuffle.hip).  Everything belongs to the engine that runs the kernel (a plain handle, a group, a
+// device entry): the scratch of the moves, and the records and accepted counts of the last call as the host read them back.
+struct ReshuffleState {
+    DeviceBuf<uint8_t> d_scratch;  // [chains][max(na, nb)] member ids (4 bytes), then original labels, then launch labels (1 each)
+    DeviceBuf<bisbm_reshuffle_record> d_record;    // [chains] the last move of the last call
+    DeviceBuf<unsigned long long> d_accepted;      // [chains] accepted moves of the last call
+    std::vector<bisbm_reshuffle_record> last;      // (empty: no call yet)
+    std::vector<unsigned long long> accepted;
+};
+
 // Partition distances (bisbm_partition.hip).  The scratch of the calls, on the engine whose device computes (a plain handle, the
 // container of shape groups, the first device entry); nothing of it outlives a call in meaning, it is only kept to be reused.
 struct PartitionState {
@@ -435,6 +446,7 @@ struct bisbm_engine {
     bisbm::CoassignState coassign;
     bisbm::FoldinState foldin;
     bisbm::ConditionalState cond;
+    bisbm::ReshuffleState reshuffle;
     bisbm::PartitionState partition;
     bisbm::ModeState modes;
 };

@@ -7,6 +7,8 @@
 
 #include "bisbm_device.hpp"
 
+struct bisbm_reshuffle_record;  // include/bisbm.h
+
 namespace bisbm {
 
 // Per-chain scalar state kept in HBM between kernels.
@@ -33,7 +35,7 @@ struct ChainScalars {
     uint64_t stop_mark;
     uint64_t stop_below1;
     uint32_t stopped;
-    uint32_t pad_;
+    uint32_t reshuffles_total;  // Philox counter: pair reshuffles proposed over the chain's lifetime (bisbm_reshuffle_run)
 };
 
 struct SweepParams {
@@ -401,6 +403,43 @@ struct HeatbathParams {
 };
 size_t heatbath_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds);
 hipError_t launch_heatbath(const HeatbathParams& p, size_t lds_bytes, hipStream_t stream);
+
+constexpr uint32_t PHX_RESHUFFLE = 10;  // pair reshuffles: idx = (reshuffles_total << 32) | k, chain = the chain's global id
+
+// Pair reshuffles (bisbm_reshuffle.hip): `moves` moves of every chain of one engine, one wave per chain.
+struct ReshuffleParams {
+    const uint32_t* rowptr;
+    const uint32_t* col;
+    uint32_t n, na, nb, ka, kb, maxdeg;
+    uint32_t n_chains, first_chain_id;
+    const uint32_t* chain_gids;  // see SweepParams
+    uint8_t* labels;             // byte labels
+    size_t label_stride;
+    int32_t* m;                  // [chain][ka*kb]
+    int32_t* m_r;                // [chain][K]
+    int32_t* n_r;                // [chain][K]
+    uint32_t* eta;               // [chain][K*(maxdeg+1)]
+    ChainScalars* scalars;       // cum_dS and reshuffles_total advance; nothing else is written
+    const double* lgamma_tab;
+    uint64_t lgamma_size;
+    const double* q_tab;
+    uint32_t q_stride;
+    const double* log_tab;
+    uint64_t seed;
+    uint64_t moves;
+    uint32_t scans;
+    double beta;                 // finite, > 0
+    int eta_in_lds;
+    // per-chain scratch, nmax = max(na, nb) entries each: the member ids, their original labels, their launch labels
+    uint32_t* member;            // [chain][nmax]
+    uint8_t* orig;               // [chain][nmax]
+    uint8_t* launch;             // [chain][nmax]
+    bisbm_reshuffle_record* record;  // [chain] the last move of the call
+    unsigned long long* accepted;    // [chain] accepted moves of the call
+};
+size_t reshuffle_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds);
+hipError_t launch_reshuffle(const ReshuffleParams& p, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_exp_probe(const double* x, size_t count, double* out, hipStream_t stream);
 
 hipError_t launch_split_rank(const SplitParams& p, hipStream_t stream);
 hipError_t launch_split_eval(const SplitParams& p, hipStream_t stream);

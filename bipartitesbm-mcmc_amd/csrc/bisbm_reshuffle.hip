@@ -1,0 +1,532 @@
+// bisbm_reshuffle.hip -- pair reshuffles: the nodes of two blocks of one type divided afresh between the two in one accepted or
+// rejected move (no reference counterpart; include/bisbm.h, "Pair reshuffles", states every draw, every order of operations and
+// what a move updates).  The dS of a member's one other block is entry o of the row of "Node conditionals": the same f64
+// operations in the same order as cond_rows_kernel of bisbm_conditionals.hip and heatbath_kernel of bisbm_heatbath.hip, restated
+// here because this kernel evaluates ONE target per step.
+//
+// Kernel: one wave per chain, persistent over all moves of the call.  The block state sits in LDS, laid out as
+// heatbath_kernel's (the quadrant of m with an odd row stride, m_r, n_r, the k_v histogram, eta when it fits: template
+// parameter EL); labels stay in HBM.  A move collects its members from the type's label row by ballot compaction into the
+// chain's scratch (member id, original label, launch label), then runs its passes -- transit to the launch labels, the launch
+// scans, the reverse pass, transit to L, the forward pass, transit back after a rejection -- through ONE copy of the pass loop,
+// told apart by `kind`.  The members are one type, hence an independent set and their neighbours' labels never change during a
+// move: heat-bath's chunk header applies unchanged (lane q takes the node, row extent and label of member q, the first 64
+// neighbour labels of 64 rows are parked in LDS with nothing ever invalidated).
+//
+// Step: a step has one non-trivial target, so the lanes are mapped to the non-zero (t, k_t) of the list instead of to targets:
+// lane i reads m_ct and m_ot and issues its four table gathers, 64 list entries in flight together, then the terms are added
+// in ascending t one v_readlane at a time, as the definition demands.  The four log_q evaluations of tail3 run side by side in
+// lanes 0 .. 3 through one copy of log_q's code; the eight lgamma values of tail1 and tail2 are issued before the list is
+// walked.  A transit step builds the list and applies the move, and reads no table.
+#include "bisbm_engine.hpp"
+
+using namespace bisbm;
+
+namespace bisbm {
+
+namespace {
+
+__device__ __forceinline__ void rs_fence() {  // (one wave: LDS operations execute in issue order; this only stops code motion)
+    __builtin_amdgcn_wave_barrier();
+    __asm__ volatile("" ::: "memory");
+}
+
+// log n from the host table, as the caller of log_q<true> hands it over (bisbm_conditionals.hip: logq_of)
+__device__ __forceinline__ double rs_logn(const Tables& tab, int n) { return (n > 0 && (uint64_t)n < tab.lg_size) ? tab.logtab[n] : 0.; }
+
+enum : uint32_t { RS_TRANSIT = 0, RS_FREE = 1, RS_FORCED = 2 };
+
+template <bool EL>
+__global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const uint32_t chain = blockIdx.x;
+    if (chain >= p.n_chains) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t K = p.ka + p.kb, D = p.maxdeg + 1, S = p.kb | 1u;
+    const uint32_t kmax = p.ka > p.kb ? p.ka : p.kb, nmax = p.na > p.nb ? p.na : p.nb;
+
+    // carve LDS (reshuffle_lds_bytes restates the sizes)
+    unsigned char* cur = lds_raw;
+    int32_t* mq = (int32_t*)cur;  // ka * S
+    cur += sizeof(int32_t) * p.ka * S;
+    int32_t* mr = (int32_t*)cur;
+    cur += sizeof(int32_t) * K;
+    int32_t* nr = (int32_t*)cur;
+    cur += sizeof(int32_t) * K;
+    int32_t* hist = (int32_t*)cur;
+    cur += sizeof(int32_t) * kmax;
+    uint32_t* s_t = (uint32_t*)cur;  // the non-zero t, ascending
+    cur += sizeof(uint32_t) * kmax;
+    int32_t* s_kt = (int32_t*)cur;   // their k_t
+    cur += sizeof(int32_t) * kmax;
+    uint8_t* lab_lds = (uint8_t*)cur;  // 64 rows x the labels of their first 64 neighbours
+    cur += kWave * kWave;
+    uint32_t* eta_l = (uint32_t*)cur;  // K * D when EL
+    uint32_t* eta_g = p.eta + (size_t)chain * K * D;
+    auto eta_at = [&](uint32_t idx) -> uint32_t* {
+        if constexpr (EL)
+            return eta_l + idx;
+        else
+            return eta_g + idx;
+    };
+
+    uint8_t* labels = p.labels + (size_t)chain * p.label_stride;
+    int32_t* m_g = p.m + (size_t)chain * p.ka * p.kb;
+    int32_t* mr_g = p.m_r + (size_t)chain * K;
+    int32_t* nr_g = p.n_r + (size_t)chain * K;
+    uint32_t* member = p.member + (size_t)chain * nmax;
+    uint8_t* orig = p.orig + (size_t)chain * nmax;
+    uint8_t* launch = p.launch + (size_t)chain * nmax;
+    for (uint32_t i = lane; i < p.ka * p.kb; i += kWave) mq[(i / p.kb) * S + (i % p.kb)] = m_g[i];
+    for (uint32_t i = lane; i < K; i += kWave) {
+        mr[i] = mr_g[i];
+        nr[i] = nr_g[i];
+    }
+    if (EL)
+        for (uint32_t i = lane; i < K * D; i += kWave) eta_l[i] = eta_g[i];
+    ChainScalars* sc = p.scalars + chain;
+    double cum_dS = sc->cum_dS;
+    uint32_t total = sc->reshuffles_total;
+    __syncthreads();
+
+    const Tables tab{p.lgamma_tab, p.lgamma_size, p.q_tab, p.q_stride, p.log_tab};
+    const uint32_t chain_gid = chain_gid_of(p, chain);
+    const uint32_t pairs_a = p.ka * (p.ka - 1u) / 2u, n_pairs = pairs_a + p.kb * (p.kb - 1u) / 2u;
+    unsigned long long n_accepted = 0;
+    bisbm_reshuffle_record rec{};
+    rec.type = BISBM_RESHUFFLE_NONE;
+
+    for (uint64_t move = 0; move < p.moves; ++move, ++total) {
+        const uint64_t idx0 = (uint64_t)total << 32;
+        rec = bisbm_reshuffle_record{};
+        rec.type = BISBM_RESHUFFLE_NONE;
+        if (n_pairs == 0) continue;  // (a counted no-op)
+        // 2. the pair
+        uint32_t pi = readlane((uint32_t)(((uint64_t)phx_draw(p.seed, chain_gid, PHX_RESHUFFLE, idx0).x * n_pairs) >> 32), 0u);
+        const bool tb = pi >= pairs_a;
+        if (tb) pi -= pairs_a;
+        const uint32_t n_cls = tb ? p.nb : p.na, v0 = tb ? p.na : 0u;
+        const uint32_t k_own = tb ? p.kb : p.ka, k_oth = tb ? p.ka : p.kb, own0 = tb ? p.ka : 0u, oth0 = tb ? 0u : p.ka;
+        uint32_t r_loc = 0;
+        while (pi >= k_own - 1u - r_loc) {
+            pi -= k_own - 1u - r_loc;
+            ++r_loc;
+        }
+        const uint32_t s_loc = r_loc + 1u + pi;
+        const uint32_t rg = own0 + r_loc, sg = own0 + s_loc;  // global labels
+        auto Mq = [&](uint32_t i_own, uint32_t j_oth) -> int32_t& { return tb ? mq[j_oth * S + i_own] : mq[i_own * S + j_oth]; };
+        const U4 acc_draw = phx_draw(p.seed, chain_gid, PHX_RESHUFFLE, idx0 | 1u);
+        const double u_acc = u53(acc_draw.x, acc_draw.y);
+
+        // 3. the members, ascending id, by ballot compaction
+        uint32_t M = 0;
+        for (uint32_t i0 = 0; i0 < n_cls; i0 += kWave) {
+            const uint32_t i = i0 + lane;
+            const uint32_t lab = i < n_cls ? (uint32_t)labels[v0 + i] : 0xffffffffu;
+            const bool is = lab == rg || lab == sg;
+            const unsigned long long bal = __ballot(is);
+            if (is) {
+                const uint32_t pos = M + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                member[pos] = v0 + i;
+                orig[pos] = (uint8_t)lab;
+            }
+            M += (uint32_t)__popcll(bal);
+        }
+        if (M < 2u) continue;  // (no block is ever empty: never)
+        // 4. the launch labels
+        const uint32_t W = (M + 127u) >> 7;
+        bool got_r = false, got_s = false;
+        for (uint32_t i0 = 0; i0 < M; i0 += kWave) {
+            const uint32_t i = i0 + lane;
+            uint32_t bit = 0;
+            if (i < M) {
+                const U4 x = phx_draw(p.seed, chain_gid, PHX_RESHUFFLE, idx0 | (uint64_t)(2u + (i >> 7)));
+                const uint32_t sel = (i >> 5) & 3u;
+                const uint32_t word = sel == 0 ? x.x : sel == 1 ? x.y : sel == 2 ? x.z : x.w;
+                bit = (word >> (i & 31u)) & 1u;
+                launch[i] = (uint8_t)(bit ? sg : rg);
+            }
+            got_s = got_s || __ballot(i < M && bit != 0) != 0;
+            got_r = got_r || __ballot(i < M && bit == 0) != 0;
+        }
+        __threadfence_block();
+        rs_fence();
+        if (lane == 0) {
+            if (!got_r) launch[0] = (uint8_t)rg;
+            if (!got_s) launch[M - 1u] = (uint8_t)sg;
+        }
+        __threadfence_block();  // the scratch this wave wrote is read by other lanes of it in the headers below
+        rs_fence();
+
+        // the passes: stage 0 transit to the launch labels; 1 .. scans the launch scans; scans + 1 the reverse pass; scans + 2
+        // transit to L; scans + 3 the forward pass; scans + 4 transit back to the original labels after a rejection
+        double q_m = 0.5, dsum = 0.;  // the running Q (mantissa, exponent) and sum of dS of the pass under way
+        int q_e = 1;
+        bool dead = false, accepted = false;
+        const uint64_t n_stages = (uint64_t)p.scans + 5u;
+        for (uint64_t stage = 0; stage < n_stages; ++stage) {
+            uint32_t kind = RS_TRANSIT;
+            const uint8_t* tgt = launch;
+            uint64_t draw0 = 0;  // k of member 0's uniform in a free scan
+            if (stage >= 1 && stage <= p.scans) {
+                kind = RS_FREE;
+                draw0 = 2u + (uint64_t)W + (stage - 1u) * (uint64_t)M;
+            } else if (stage == (uint64_t)p.scans + 1u) {
+                // L = the labels the launch scans ended at
+                for (uint32_t i = lane; i < M; i += kWave) launch[i] = labels[member[i]];
+                __threadfence_block();
+                rs_fence();
+                kind = RS_FORCED, tgt = orig;
+                q_m = 0.5, q_e = 1, dsum = 0.;
+            } else if (stage == (uint64_t)p.scans + 2u) {
+                rec.q_rev_mant = q_m, rec.q_rev_exp = q_e, rec.dS_rev = dsum;
+                if (dead) break;  // (the reverse pass has ended at the original state: a certain rejection)
+            } else if (stage == (uint64_t)p.scans + 3u) {
+                kind = RS_FREE;
+                draw0 = 2u + (uint64_t)W + (uint64_t)p.scans * (uint64_t)M;
+                q_m = 0.5, q_e = 1, dsum = 0.;
+            } else if (stage == (uint64_t)p.scans + 4u) {
+                // 8. accept
+                rec.q_fwd_mant = q_m, rec.q_fwd_exp = q_e, rec.dS_fwd = dsum;
+                const double dS = rec.dS_fwd - rec.dS_rev;
+                const double lnA = (0. - p.beta * dS) + (log(rec.q_rev_mant / rec.q_fwd_mant) + (double)(rec.q_rev_exp - rec.q_fwd_exp) * 0.6931471805599453);
+                rec.A = exp(lnA);
+                accepted = u_acc < rec.A;
+                if (accepted) {
+                    cum_dS = cum_dS + dS;
+                    break;
+                }
+                tgt = orig;
+            }
+
+            for (uint32_t i0 = 0; i0 < M; i0 += kWave) {
+                // ---- chunk header: lane q holds the node, row extent, current label and target of member i0 + q ----
+                const uint32_t cnt = M - i0 < (uint32_t)kWave ? M - i0 : (uint32_t)kWave;
+                uint32_t v_l = 0, beg_l = 0, deg_l = 0, c_l = 0, want_l = 0;
+                if (lane < cnt) {
+                    v_l = member[i0 + lane];
+                    beg_l = p.rowptr[v_l];
+                    deg_l = p.rowptr[v_l + 1] - beg_l;
+                    c_l = labels[v_l];
+                    want_l = tgt[i0 + lane];
+                }
+                // the first 64 neighbour labels of the chunk's rows, eight rows at a time (idle lanes read node 0)
+                rs_fence();
+                for (uint32_t q0 = 0; q0 < cnt; q0 += 8) {
+                    uint32_t id[8], lb[8];
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) {
+                        const uint32_t b0 = readlane(beg_l, q0 + j), d0 = readlane(deg_l, q0 + j);  // (rows past cnt: deg 0)
+                        id[j] = lane < d0 ? p.col[b0 + lane] : 0u;
+                    }
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) lb[j] = labels[id[j]];
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) lab_lds[(q0 + j) * kWave + lane] = (uint8_t)lb[j];
+                }
+                rs_fence();
+
+                for (uint32_t q = 0; q < cnt; ++q) {
+                    const uint32_t v = readlane(v_l, q), beg = readlane(beg_l, q), deg = readlane(deg_l, q);
+                    const uint32_t c = readlane(c_l, q), want = readlane(want_l, q);
+                    if (c != rg && c != sg) continue;  // (a member's label: never)
+                    const uint32_t o = c == rg ? sg : rg, c_loc = c - own0, o_loc = o - own0;
+                    const bool evaluate = kind != RS_TRANSIT && !dead;
+                    const int n0c = readlane(nr[c], 0u);
+                    uint32_t to = c;       // where the member goes
+                    bool tables = false;   // whether dS_o is evaluated
+                    if (!evaluate) {
+                        to = want;
+                    } else if (n0c <= 1) {  // not free: the member stays with the factor 1.0, or a forced move kills the pass
+                        if (kind == RS_FORCED && want != c) {
+                            dead = true, q_m = 0., q_e = 0;
+                            to = want;
+                        }
+                    } else {
+                        tables = true;
+                    }
+                    if (!tables && to == c) continue;
+                    // k_v: the histogram of the neighbours' labels
+                    for (uint32_t t = lane; t < k_oth; t += kWave) hist[t] = 0;
+                    rs_fence();
+                    if (lane < deg) {
+                        const uint32_t t = (uint32_t)lab_lds[q * kWave + lane] - oth0;
+                        if (t < k_oth) atomicAdd(&hist[t], 1);
+                    }
+                    for (uint32_t j = kWave + lane; j < deg; j += kWave) {  // rows longer than one wave
+                        const uint32_t t = (uint32_t)labels[p.col[beg + j]] - oth0;
+                        if (t < k_oth) atomicAdd(&hist[t], 1);
+                    }
+                    rs_fence();
+                    // the non-zero (t, k_t) in ascending t
+                    uint32_t nnz = 0;
+                    for (uint32_t c0 = 0; c0 < k_oth; c0 += kWave) {
+                        const uint32_t t = c0 + lane;
+                        const int kt = t < k_oth ? hist[t] : 0;
+                        const unsigned long long bal = __ballot(kt != 0);
+                        if (kt != 0) {
+                            const uint32_t pos = nnz + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                            s_t[pos] = t, s_kt[pos] = kt;
+                        }
+                        nnz += (uint32_t)__popcll(bal);
+                    }
+                    rs_fence();
+                    double dS_o = 0.;
+                    if (tables) {
+                        // dS_o (step 1 of "Node conditionals" with r = c, s = o)
+                        const int ideg = (int)deg;
+                        const int m0c = mr[c], m0o = mr[o], n0o = nr[o];
+                        const long long eta_c = *eta_at(c * D + deg), eta_o = *eta_at(o * D + deg);
+                        // every table gather of the tails is issued before the list is walked
+                        const double lg_c1 = lgamma_fast(tab, (long long)m0c - ideg + 1), lg_c0 = lgamma_fast(tab, (long long)m0c + 1);
+                        const double lg_o1 = lgamma_fast(tab, (long long)m0o + ideg + 1), lg_o0 = lgamma_fast(tab, (long long)m0o + 1);
+                        const double lg_ec1 = lgamma_fast(tab, eta_c + 1), lg_ec0 = lgamma_fast(tab, eta_c);
+                        const double lg_eo1 = lgamma_fast(tab, eta_o + 1), lg_eo2 = lgamma_fast(tab, eta_o + 2);
+                        // lanes 0 .. 3: the four log_q of tail3 in the order they are subtracted
+                        const uint32_t sel = lane & 3u;
+                        const int qn = sel == 0 ? m0c - ideg : sel == 1 ? m0c : sel == 2 ? m0o + ideg : m0o;
+                        const int qk = sel == 0 ? n0c - 1 : sel == 1 ? n0c : sel == 2 ? n0o + 1 : n0o;
+                        const double ln_q = rs_logn(tab, qn);
+                        double acc = 0.;
+                        for (uint32_t l0 = 0; l0 < nnz; l0 += kWave) {
+                            const uint32_t cn = nnz - l0 < (uint32_t)kWave ? nnz - l0 : (uint32_t)kWave;
+                            const uint32_t li = l0 + (lane < cn ? lane : cn - 1u);  // (idle lanes read the last entry again)
+                            const uint32_t t = s_t[li];
+                            const int kt = s_kt[li];
+                            const int32_t m_ct = Mq(c_loc, t), m_ot = Mq(o_loc, t);
+                            const double a1 = lgamma_fast(tab, (long long)m_ct + 1), a2 = lgamma_fast(tab, (long long)m_ot + 1);
+                            const double a3 = lgamma_fast(tab, (long long)m_ct - kt + 1), a4 = lgamma_fast(tab, (long long)m_ot + kt + 1);
+                            const double term = (a1 + a2) - (a3 + a4);
+                            for (uint32_t j = 0; j < cn; ++j) acc = acc + readlane(term, j);
+                        }
+                        const double lq = log_q<true>(tab, qn, qk, ln_q);
+                        const double tail1 = (lg_c1 - lg_c0) + (lg_o1 - lg_o0);
+                        const double tail2 = (lg_ec1 - lg_ec0) + (lg_eo1 - lg_eo2);
+                        const double tail3 = (readlane(lq, 0u) - readlane(lq, 1u)) + (readlane(lq, 2u) - readlane(lq, 3u));
+                        dS_o = ((acc + tail1) + tail2) + tail3;
+                        // the two weights, Z = w_r + w_s, the choice and its factor
+                        const double mn = dS_o < 0. ? dS_o : 0.;
+                        const double x_c = p.beta * (0. - mn), x_o = p.beta * (dS_o - mn);
+                        const double w_c = x_c > 700. ? 0. : exp(-x_c), w_o = x_o > 700. ? 0. : exp(-x_o);
+                        const double w_r = c == rg ? w_c : w_o, w_s = c == rg ? w_o : w_c;
+                        const double Z = w_r + w_s;
+                        const double P_r = w_r / Z, P_s = w_s / Z;
+                        if (kind == RS_FREE) {
+                            const U4 x = phx_draw(p.seed, chain_gid, PHX_RESHUFFLE, idx0 | (draw0 + i0 + q));
+                            to = u53(x.x, x.y) < P_r ? rg : sg;
+                        } else {
+                            to = want;
+                        }
+                        const double f = to == rg ? P_r : P_s;
+                        int e2;
+                        q_m = frexp(q_m * f, &e2);
+                        q_e += e2;
+                        if (readlane((uint32_t)(f == 0.), 0u) != 0u) {  // (a forced pass only) a certain rejection: nothing more is evaluated or added
+                            dead = true, q_m = 0., q_e = 0;
+                        } else if (to != c) {
+                            dsum = dsum + dS_o;
+                        }
+                        to = readlane(to, 0u);  // (the same in every lane; this tells the compiler)
+                        if (to == c) continue;
+                    }
+                    // apply the move c -> o, as a heat-bath move (lane 0 writes eta in HBM and the label; see heatbath_kernel on
+                    // why later loads of this wave see them)
+                    rs_fence();  // all lanes have read nr / mr / eta before lane 0 rewrites them
+                    if (lane == 0) {
+                        atomicSub(&nr[c], 1);
+                        atomicAdd(&nr[o], 1);
+                        atomicSub(eta_at(c * D + deg), 1u);
+                        atomicAdd(eta_at(o * D + deg), 1u);
+                        atomicSub(&mr[c], (int)deg);
+                        atomicAdd(&mr[o], (int)deg);
+                        labels[v] = (uint8_t)o;
+                    }
+                    for (uint32_t i = lane; i < nnz; i += kWave) {
+                        const uint32_t t = s_t[i];
+                        const int k = s_kt[i];
+                        atomicSub(&Mq(c_loc, t), k);
+                        atomicAdd(&Mq(o_loc, t), k);
+                    }
+                    rs_fence();
+                }
+            }
+            __threadfence_block();  // the labels this pass wrote are read by the next pass's headers
+        }
+        rec.type = tb ? 1u : 0u, rec.r = rg, rec.s = sg, rec.M = M;
+        rec.u_acc = u_acc;
+        rec.accepted = accepted ? 1u : 0u;
+        if (dead) rec.dS_fwd = 0., rec.q_fwd_mant = 0., rec.q_fwd_exp = 0, rec.A = 0.;
+        n_accepted += accepted ? 1u : 0u;
+    }
+
+    // store the chain back
+    __syncthreads();
+    for (uint32_t i = lane; i < p.ka * p.kb; i += kWave) m_g[i] = mq[(i / p.kb) * S + (i % p.kb)];
+    for (uint32_t i = lane; i < K; i += kWave) {
+        mr_g[i] = mr[i];
+        nr_g[i] = nr[i];
+    }
+    if (EL)
+        for (uint32_t i = lane; i < K * D; i += kWave) eta_g[i] = eta_l[i];
+    if (lane == 0) {
+        sc->cum_dS = cum_dS;
+        sc->reshuffles_total = total;
+        p.record[chain] = rec;
+        p.accepted[chain] = n_accepted;
+    }
+}
+
+__global__ void exp_probe_kernel(const double* x, size_t count, double* out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = exp(x[i]);
+}
+
+}  // namespace
+
+size_t reshuffle_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds) {
+    const size_t K = (size_t)ka + kb, S = kb | 1u, kmax = std::max(ka, kb);
+    size_t lds = sizeof(int32_t) * ((size_t)ka * S + 2 * K + 3 * kmax) + (size_t)kWave * kWave;
+    if (eta_in_lds) lds += sizeof(uint32_t) * K * ((size_t)maxdeg + 1);
+    return (lds + 15) & ~(size_t)15;
+}
+
+hipError_t launch_reshuffle(const ReshuffleParams& p, size_t lds_bytes, hipStream_t stream) {
+    if (p.n_chains == 0 || p.moves == 0) return hipSuccess;
+    auto kern = p.eta_in_lds ? reshuffle_kernel<true> : reshuffle_kernel<false>;
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(p.n_chains), dim3(kWave), lds_bytes, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_exp_probe(const double* x, size_t count, double* out, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(exp_probe_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, x, count, out);
+    return hipGetLastError();
+}
+
+}  // namespace bisbm
+
+namespace {
+
+int reshuffle_leaf(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta) {
+    HIPCHK(h, hipSetDevice(h->device));
+    ReshuffleState& st = h->reshuffle;
+    const size_t nmax = (size_t)std::max(h->na, h->nb), C = h->n_chains;
+    RESERVE(h, st.d_scratch, 6 * nmax * C);
+    RESERVE(h, st.d_record, C);
+    RESERVE(h, st.d_accepted, C);
+    ReshuffleParams p{};
+    p.rowptr = h->d_rowptr, p.col = h->d_col;
+    p.n = (uint32_t)h->n, p.na = (uint32_t)h->na, p.nb = (uint32_t)h->nb;
+    p.ka = h->ka, p.kb = h->kb, p.maxdeg = h->maxdeg;
+    p.n_chains = h->n_chains, p.first_chain_id = h->first_chain_id, p.chain_gids = h->d_gids;
+    p.labels = h->d_labels, p.label_stride = h->label_stride;
+    p.m = h->d_m, p.m_r = h->d_m_r, p.n_r = h->d_n_r, p.eta = h->d_eta;
+    p.scalars = h->d_scalars;
+    p.lgamma_tab = h->d_lgamma, p.lgamma_size = h->tab->lg.size(), p.q_tab = h->d_q, p.q_stride = h->q_stride, p.log_tab = h->d_logtab;
+    p.seed = h->seed;
+    p.moves = moves, p.scans = scans, p.beta = beta;
+    p.member = (uint32_t*)st.d_scratch.get();
+    p.orig = st.d_scratch.get() + 4 * nmax * C;
+    p.launch = st.d_scratch.get() + 5 * nmax * C;
+    p.record = st.d_record.get(), p.accepted = st.d_accepted.get();
+    // eta goes to LDS when that still leaves room for four chains per CU, as in the heat-bath kernel's plan
+    p.eta_in_lds = reshuffle_lds_bytes(h->ka, h->kb, h->maxdeg, true) <= 40 * 1024 ? 1 : 0;
+    const size_t lds = reshuffle_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0);
+    if (lds > kLdsPerCu) return fail(h, BISBM_ERR_UNSUPPORTED, "chain state needs %zu B of LDS (> 160 KiB)", lds);
+    h->ent_prev_valid = false;  // (the block state moves)
+    st.last.clear();
+    HIPCHK(h, launch_reshuffle(p, lds, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    st.last.resize(C);
+    st.accepted.resize(C);
+    HIPCHK(h, hipMemcpy(st.last.data(), st.d_record.get(), sizeof(bisbm_reshuffle_record) * C, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(st.accepted.data(), st.d_accepted.get(), sizeof(unsigned long long) * C, hipMemcpyDeviceToHost));
+    return BISBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bisbm_reshuffle_run(bisbm_handle h, uint64_t moves, uint32_t scans, double beta, uint64_t* accepted_out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (h->rng_mode == BISBM_RNG_MT19937_COMPAT)
+        return fail(h, BISBM_ERR_UNSUPPORTED, "pair reshuffles are defined in the Philox-mode arithmetic: this handle runs BISBM_RNG_MT19937_COMPAT");
+    if (!(beta > 0.) || std::isinf(beta)) return fail(h, BISBM_ERR_INVALID_ARG, "beta = %g: a finite value above 0 is needed", beta);
+    if (h->temper.L)
+        return fail(h, BISBM_ERR_STATE, "replica exchange is on: sweeps run through bisbm_tempering_run (bisbm_tempering_set(h, 0, NULL) turns it off)");
+    if (any_wide(h))
+        return fail(h, BISBM_ERR_UNSUPPORTED, "pair reshuffles serve byte labels only (at most 256 blocks): merge the blocks down first");
+    for (bisbm_engine* e : leaves(h))
+        if (!e->state_ready) return fail(h, BISBM_ERR_STATE, "call bisbm_init or bisbm_shuffle before bisbm_reshuffle_run");
+    const uint64_t nmax = std::max(h->na, h->nb);
+    if (nmax >= (1ull << 32) || 2 + (nmax + 127) / 128 + ((uint64_t)scans + 1) * nmax >= (1ull << 32))
+        return fail(h, BISBM_ERR_INVALID_ARG, "scans = %u: a move of up to %llu members could use 2^32 draws or more", scans, (unsigned long long)nmax);
+    if (moves == 0) {
+        for (uint32_t c = 0; accepted_out && c < h->n_chains; ++c) accepted_out[c] = 0;
+        return BISBM_OK;
+    }
+    DeviceGuard keep;
+    if (int rc = each_leaf(h, [&](bisbm_engine* e) { return reshuffle_leaf(e, moves, scans, beta); })) return rc;
+    for (uint32_t c = 0; accepted_out && c < h->n_chains; ++c) {
+        uint32_t local;
+        bisbm_engine* e = leaf_of_chain(h, c, &local);
+        accepted_out[c] = e->reshuffle.accepted[local];
+    }
+    return BISBM_OK;
+}
+
+int bisbm_reshuffle_get_last(bisbm_handle h, bisbm_reshuffle_record* out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!out) return fail(h, BISBM_ERR_INVALID_ARG, "out is NULL");
+    for (uint32_t c = 0; c < h->n_chains; ++c) {
+        uint32_t local;
+        bisbm_engine* e = leaf_of_chain(h, c, &local);
+        if (local >= e->reshuffle.last.size())
+            return fail(h, BISBM_ERR_STATE, "chain %u has no pair reshuffle on record: call bisbm_reshuffle_run first", c);
+    }
+    for (uint32_t c = 0; c < h->n_chains; ++c) {
+        uint32_t local;
+        bisbm_engine* e = leaf_of_chain(h, c, &local);
+        out[c] = e->reshuffle.last[local];
+    }
+    return BISBM_OK;
+}
+
+int bisbm_reshuffle_get_total(bisbm_handle h, uint64_t* out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->devs.empty() && out) return on_devices(h, [&](bisbm_engine* d, size_t i) { return bisbm_reshuffle_get_total(d, out + h->dev_first[i]); });
+    if (!out) return fail(h, BISBM_ERR_INVALID_ARG, "out is NULL");
+    if (!h->groups.empty()) return gather_groups<uint64_t>(h, out, [](bisbm_engine* g, uint64_t* o) { return bisbm_reshuffle_get_total(g, o); });
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<ChainScalars> sc(h->n_chains);
+    HIPCHK(h, hipMemcpy(sc.data(), h->d_scalars, sizeof(ChainScalars) * h->n_chains, hipMemcpyDeviceToHost));
+    for (uint32_t c = 0; c < h->n_chains; ++c) out[c] = sc[c].reshuffles_total;
+    return BISBM_OK;
+}
+
+int bisbm_debug_exp(bisbm_handle h, const double* x, size_t count, double* out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->devs.empty()) {
+        const int rc = bisbm_debug_exp(h->devs[0], x, count, out);
+        if (rc) h->err = h->devs[0]->err;
+        return rc;
+    }
+    if (!x || !out) return fail(h, BISBM_ERR_INVALID_ARG, "NULL argument");
+    if (count == 0) return BISBM_OK;
+    DeviceGuard keep;
+    HIPCHK(h, hipSetDevice(h->device));
+    DeviceBuf<double> dx, dout;
+    RESERVE(h, dx, count);
+    RESERVE(h, dout, count);
+    HIPCHK(h, hipMemcpy(dx.get(), x, sizeof(double) * count, hipMemcpyHostToDevice));
+    HIPCHK(h, launch_exp_probe(dx.get(), count, dout.get(), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(out, dout.get(), sizeof(double) * count, hipMemcpyDeviceToHost));
+    return BISBM_OK;
+}
+
+}  // extern "C"

@@ -313,6 +313,85 @@ def numpy_heatbath_choice(dS_row, P_row, r, free, u, greedy):
     return last
 
 
+def numpy_reshuffle_pair(x, ka, kb):
+    """Host statement of step 2 of the pair reshuffles (include/bisbm.h, "Pair reshuffles"): (type, r, s) -- r < s within the
+    type -- of the pair that the first word x of the move's draw 0 selects among the C(ka, 2) + C(kb, 2) pairs, type a first,
+    each type lexicographically; None when the shape has no pair."""
+    ka, kb = int(ka), int(kb)
+    pa = ka * (ka - 1) // 2
+    N = pa + kb * (kb - 1) // 2
+    if N == 0:
+        return None
+    pi = (int(x) * N) >> 32
+    t, k = (0, ka) if pi < pa else (1, kb)
+    pi -= pa * t
+    r = 0
+    while pi >= k - 1 - r:
+        pi -= k - 1 - r
+        r += 1
+    return t, r, r + 1 + pi
+
+
+def numpy_reshuffle_launch(bits, r, s):
+    """Host statement of the first half of step 4: the launch labels of the M members from their launch bits -- s where the bit
+    is set, else r; if no member got r, member 0 gets r; if none got s, the last member gets s."""
+    lab = [int(s) if b else int(r) for b in bits]
+    if int(r) not in lab:
+        lab[0] = int(r)
+    if int(s) not in lab:
+        lab[-1] = int(s)
+    return lab
+
+
+def numpy_reshuffle_step(dS_o, c_is_r, free, beta, u=None, forced_to_r=None, exp=np.exp):
+    """Host statement of step 5 (and of one member of steps 6 and 7) for a member in block c of {r, s}: (goes to r?, factor, dead).
+    dS_o: the dS of its other block (ignored when it is not free); c_is_r: whether c is r; free: n_r[c] > 1.  A free scan passes
+    the uniform `u`; a forced pass passes `forced_to_r`, whether the member's original label is r.  dead: the forced move of a
+    member that is not free, or a factor of exactly 0.0 -- Q becomes (0.0, 0) and nothing more is evaluated.  `exp`: the
+    exponential -- the device's (BlockModel.debug_exp) reproduces the device bit for bit, numpy's to the last bits."""
+    c_is_r = bool(c_is_r)
+    if not free:
+        if forced_to_r is not None and bool(forced_to_r) != c_is_r:
+            return bool(forced_to_r), 0.0, True
+        return c_is_r, 1.0, False
+    dS_o, beta = float(dS_o), float(beta)
+    mn = dS_o if dS_o < 0.0 else 0.0
+    x_c, x_o = beta * (0.0 - mn), beta * (dS_o - mn)
+    w_c = 0.0 if x_c > 700.0 else float(exp(np.float64(-x_c)))
+    w_o = 0.0 if x_o > 700.0 else float(exp(np.float64(-x_o)))
+    w_r, w_s = (w_c, w_o) if c_is_r else (w_o, w_c)
+    Z = w_r + w_s
+    P_r, P_s = w_r / Z, w_s / Z
+    to_r = (float(u) < P_r) if forced_to_r is None else bool(forced_to_r)
+    f = P_r if to_r else P_s
+    return to_r, f, f == 0.0
+
+
+def numpy_reshuffle_q(factors):
+    """Q of a pass as (mantissa, exponent): frexp(1.0) multiplied by one factor at a time with a frexp after every multiply; a
+    factor of 0.0 ends the pass at (0.0, 0)"""
+    import math
+    m, e = 0.5, 1
+    for f in factors:
+        if float(f) == 0.0:
+            return 0.0, 0
+        m, e2 = math.frexp(m * float(f))
+        e += e2
+    return m, e
+
+
+def numpy_reshuffle_accept(dS_fwd, dS_rev, q_fwd, q_rev, beta, u_acc):
+    """Host statement of step 8: (A, accepted) from the two sums of dS, the two Q as (mantissa, exponent), beta and u_acc.  A
+    dead reverse pass (q_rev mantissa 0.0) is A = 0.0 and a rejection."""
+    if float(q_rev[0]) == 0.0:
+        return 0.0, False
+    dS = float(dS_fwd) - float(dS_rev)
+    with np.errstate(over="ignore"):
+        lnA = (0.0 - float(beta) * dS) + (float(np.log(np.float64(q_rev[0]) / np.float64(q_fwd[0]))) + float(int(q_rev[1]) - int(q_fwd[1])) * 0.6931471805599453)
+        A = float(np.exp(np.float64(lnA)))
+    return A, float(u_acc) < A
+
+
 def numpy_foldin_posterior(labels, m, m_r, n_r, ka, qtype, neighbours, alpha):
     """Host statement of steps 1 and 2 of the fold-in queries (include/bisbm.h, "Fold-in queries") for one chain and one virtual
     node: the posterior P[K_own] over the blocks of its type, bit for bit what the device computes.  `labels`, `m`, `m_r`, `n_r`:

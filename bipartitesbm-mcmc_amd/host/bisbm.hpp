@@ -300,6 +300,19 @@ public:
         sweeps.assign(n_chains_, 0);
         check(bisbm_heatbath_run(h_, max_sweeps, std::numeric_limits<double>::infinity(), 1, moved.data(), sweeps.data()));
     }
+    // pair reshuffles (include/bisbm.h): `moves` moves per chain in which the nodes of two blocks of one type are divided afresh
+    // and accepted or rejected as a whole (the accepted moves per chain); the record of every chain's last move.  The default
+    // of 3 scans is a convention from the literature, not a measurement.
+    std::vector<uint64_t> reshuffle(uint64_t moves, uint32_t scans = 3, double beta = 1.0) {
+        std::vector<uint64_t> accepted(n_chains_);
+        check(bisbm_reshuffle_run(h_, moves, scans, beta, accepted.data()));
+        return accepted;
+    }
+    std::vector<bisbm_reshuffle_record> reshuffle_last() {
+        std::vector<bisbm_reshuffle_record> rec(n_chains_);
+        check(bisbm_reshuffle_get_last(h_, rec.data()));
+        return rec;
+    }
     // pair scores (include/bisbm.h): the pairs (u of type a, v of type b), a sample of every counted chain, the sums and the
     // number of chain terms in them (the estimate of a pair is sum / terms)
     void pair_scores_set(const std::vector<uint32_t>& u, const std::vector<uint32_t>& v) {

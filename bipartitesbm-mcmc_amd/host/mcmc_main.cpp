@@ -6,7 +6,7 @@
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
 // --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
-// --conditionals, --conditionals_beta, --polish, --heatbath.
+// --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -58,6 +58,7 @@ const option_spec kOptions[] = {
     {"conditionals", 0, 2},     {"conditionals_beta", 0, 1},
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
     {"polish", 0, 1},           {"heatbath", 0, 0},
+    {"reshuffle", 0, 1},        {"reshuffle_scans", 0, 1},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -205,6 +206,12 @@ void print_help(const char* argv0) {
                  "  --heatbath                            With --marginalize: burn-in and the sweeps between samples are heat-bath\n"
                  "                                        sweeps (every node draws its block from its exact conditional; Philox\n"
                  "                                        mode, not with --tempering) instead of Metropolis-Hastings sweeps.\n"
+                 "  --reshuffle M                         With --marginalize: M pair reshuffles per chain after the burn-in and after\n"
+                 "                                        every block of sweeps between samples (the nodes of two blocks of one type\n"
+                 "                                        divided afresh and accepted or rejected as a whole; Philox mode, not with\n"
+                 "                                        --tempering).  The acceptance is reported on stderr.\n"
+                 "  --reshuffle_scans arg (=3)            With --reshuffle: restricted Gibbs scans before the proposal (3 is the\n"
+                 "                                        convention of the literature, not a measurement).\n"
                  "  --score_pairs IN OUT                  With --marginalize: IN holds one pair `u v` per line (u of type a, v of\n"
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
@@ -489,6 +496,34 @@ int main(int argc, char const* argv[]) {
     if (count("heatbath") && count("tempering")) {
         std::cerr << "--heatbath cannot be combined with --tempering: replica exchange runs Metropolis-Hastings sweeps.\n";
         return 1;
+    }
+    uint64_t reshuffle_moves = 0;
+    uint32_t reshuffle_scans = 3;
+    if (count("reshuffle_scans") && !count("reshuffle")) {
+        std::cerr << "--reshuffle_scans sets the scans of the pair reshuffles: it needs --reshuffle.\n";
+        return 1;
+    }
+    if (count("reshuffle")) {
+        if (!count("marginalize")) {
+            std::cerr << "--reshuffle runs pair reshuffles between the sweeps of the marginalization mode: it needs --marginalize.\n";
+            return 1;
+        }
+        if (count("tempering")) {
+            std::cerr << "--reshuffle cannot be combined with --tempering: the library refuses pair reshuffles while replica exchange is on.\n";
+            return 1;
+        }
+        const std::string v = single("reshuffle", ""), t = single("reshuffle_scans", "3");
+        char *end = nullptr, *end2 = nullptr;
+        const unsigned long long k = std::strtoull(v.c_str(), &end, 10), sc = std::strtoull(t.c_str(), &end2, 10);
+        if (v.empty() || *end != '\0' || v[0] == '-' || k == 0) {
+            std::cerr << "Invalid --reshuffle. The moves per chain after every block of sweeps: an integer >= 1, e.g. --reshuffle 10.\n";
+            return 1;
+        }
+        if (t.empty() || *end2 != '\0' || t[0] == '-' || sc > 0xffffffffull) {
+            std::cerr << "Invalid --reshuffle_scans. An integer >= 0, e.g. --reshuffle_scans 3.\n";
+            return 1;
+        }
+        reshuffle_moves = k, reshuffle_scans = (uint32_t)sc;
     }
     // population annealing: the temperatures and the sweeps per temperature are checked before anything else runs (one more
     // refusal, an initial partition without the -z block counts, waits below until the partition has been read: before the
@@ -918,8 +953,8 @@ int main(int argc, char const* argv[]) {
         return 1;
     }
     opt.rng_mode = rng == "philox" ? BISBM_RNG_PHILOX : BISBM_RNG_MT19937_COMPAT;
-    if ((polish_sweeps || count("heatbath")) && opt.rng_mode != BISBM_RNG_PHILOX) {
-        std::cerr << (polish_sweeps ? "--polish" : "--heatbath")
+    if ((polish_sweeps || count("heatbath") || reshuffle_moves) && opt.rng_mode != BISBM_RNG_PHILOX) {
+        std::cerr << (polish_sweeps ? "--polish" : count("heatbath") ? "--heatbath" : "--reshuffle")
                   << " runs in Philox mode only (mt19937-compat is the reference's verification path): add --rng philox.\n";
         return 1;
     }
@@ -1154,6 +1189,7 @@ int main(int argc, char const* argv[]) {
             const size_t never = std::numeric_limits<size_t>::max();
             // with --tempering every chain runs at its rung's temperature and the exchange rounds run between the sweeps
             if (!ladder.empty()) blockmodel.tempering_set(ladder);
+            uint64_t reshuffles_proposed = 0, reshuffles_accepted = 0;
             auto advance = [&](size_t sweeps) {
                 if (!ladder.empty())
                     blockmodel.tempering_run(sweeps, exchange_every);
@@ -1161,6 +1197,10 @@ int main(int argc, char const* argv[]) {
                     blockmodel.heatbath_sweeps(sweeps, 1.0);
                 else
                     algorithm.anneal(blockmodel, &constant_schedule, t1, sweeps * N, never);
+                if (reshuffle_moves) {  // after every block of sweeps
+                    for (uint64_t a : blockmodel.reshuffle(reshuffle_moves, reshuffle_scans, 1.0)) reshuffles_accepted += a;
+                    reshuffles_proposed += reshuffle_moves * opt.n_chains;
+                }
             };
             if (burn_in >= N) advance(burn_in / N);
             blockmodel.marginals_reset();
@@ -1242,6 +1282,9 @@ int main(int argc, char const* argv[]) {
             }
             std::clog << "marginalize: burn-in " << burn_in / N << " sweeps, " << n_samples << " samples " << sweeps_between
                       << " sweep(s) apart, " << opt.n_chains << " chain(s) pooled\n";
+            if (reshuffle_moves)
+                std::clog << "reshuffle: " << reshuffles_accepted << " of " << reshuffles_proposed << " pair reshuffle(s) accepted (" << reshuffle_scans
+                          << " scan(s))\n";
             if (n_samples == 0) {
                 std::cerr << "[error] --marginalize: -t " << sampling_steps << " steps hold no sample (" << sweeps_between * N
                           << " steps per sample)\n";

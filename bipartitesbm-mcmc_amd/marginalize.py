@@ -18,7 +18,7 @@ import numpy as np
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
-                similar=None, foldin=None, conditionals=None, sampler="mh"):
+                similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -64,12 +64,16 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     (prob, terms) -- is appended after the stats.  The chains of this rank only.
     `sampler`: "mh" (the default: model.run_sweeps) or "heatbath" -- burn-in and the gaps between samples run through
     model.heatbath_sweeps(sweeps, 1.0) (include/bisbm.h, "Heat-bath sweeps and greedy polishing"); with `tempering` a ValueError
-    (the library refuses heat-bath sweeps while replica exchange is on)."""
+    (the library refuses heat-bath sweeps while replica exchange is on).
+    `reshuffles`: m > 0 runs model.reshuffle(m, reshuffle_scans, 1.0) after every block of sweeps -- the burn-in and every gap
+    between samples (include/bisbm.h, "Pair reshuffles"; 3 scans are the convention of the literature, not a measurement); with
+    `tempering` a ValueError.  model.reshuffle_stats = {"proposed", "accepted"} (totals over the chains of this rank) reports
+    the acceptance afterwards."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
         return_counts = not multi
-    advance = _advance(model, tempering, exchange_every, sampler)
+    advance = _advance(model, tempering, exchange_every, sampler, reshuffles, reshuffle_scans)
     if burn_in_sweeps > 0:
         advance(burn_in_sweeps)
     if score_pairs is not None:
@@ -251,11 +255,26 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
             "ref_chain": state["ref_chain"], "moved": moved}
 
 
-def _advance(model, tempering, exchange_every, sampler):
+def _advance(model, tempering, exchange_every, sampler, reshuffles=0, reshuffle_scans=3):
     """The call that runs the sweeps of the burn-in and between samples: MH at T = 1, heat-bath sweeps at beta = 1, or -- with
-    a ladder, which is set here -- replica exchange."""
+    a ladder, which is set here -- replica exchange.  reshuffles > 0: every such block of sweeps is followed by that many pair
+    reshuffles at beta = 1."""
     if sampler not in ("mh", "heatbath"):
         raise ValueError("sampler must be \"mh\" or \"heatbath\", not %r" % (sampler,))
+    if int(reshuffles) < 0 or int(reshuffle_scans) < 0:
+        raise ValueError("reshuffles and reshuffle_scans must not be negative")
+    if int(reshuffles) > 0:
+        if tempering is not None:
+            raise ValueError("reshuffles cannot be combined with tempering: the library refuses them while replica exchange is on")
+        sweeps_only = _advance(model, None, exchange_every, sampler)
+        model.reshuffle_stats = {"proposed": 0, "accepted": 0}
+
+        def block(sweeps):
+            sweeps_only(sweeps)
+            acc = model.reshuffle(int(reshuffles), int(reshuffle_scans), 1.0)
+            model.reshuffle_stats["proposed"] += int(reshuffles) * model.n_chains
+            model.reshuffle_stats["accepted"] += int(acc.sum())
+        return block
     if tempering is not None:
         if sampler == "heatbath":
             raise ValueError("sampler=\"heatbath\" cannot be combined with tempering: replica exchange runs MH sweeps")

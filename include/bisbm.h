@@ -29,7 +29,7 @@ extern "C" {
  *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
  *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*), population annealing
  *    (bisbm_population_*), node conditionals (bisbm_conditionals_*), heat-bath sweeps and greedy polishing
- *    (bisbm_heatbath_run).  Additions only. */
+ *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -570,9 +570,82 @@ int bisbm_conditionals_get_last(bisbm_handle h, uint32_t query_index, uint32_t s
  * exchange on BISBM_ERR_STATE (as bisbm_anneal); before bisbm_init / bisbm_shuffle BISBM_ERR_STATE; beta NaN, <= 0 or -inf
  * BISBM_ERR_INVALID_ARG.  sweeps = 0 is a no-op that returns BISBM_OK (the outputs are zeroed).
  * Out of scope: a temperature per chain or per rung, heat-bath sweeps inside bisbm_tempering_run / bisbm_population_run,
- * mt19937-compat arithmetic, wide handles, blocked or multi-node moves. */
+ * mt19937-compat arithmetic, wide handles.  A move of many nodes at once is bisbm_reshuffle_run below. */
 int bisbm_heatbath_run(bisbm_handle h, uint64_t sweeps, double beta, int stop_when_settled,
                        uint64_t *moved_out /* n_chains, may be NULL */, uint64_t *sweeps_out /* n_chains, may be NULL */);
+
+/* Pair reshuffles (no reference counterpart): the nodes of two blocks of one type are divided afresh between the two in ONE
+ * accepted or rejected move -- the split-merge move of Jain and Neal at a fixed block count, the "merge-split" of Peixoto
+ * 2020 -- where every other sampler of the engine moves one node at a time.  Philox mode and byte labels only; f64 without a
+ * fused multiply-add; exp and log are the device's (bisbm_debug_exp returns the device's exp to a host that replays a move).
+ * The move is defined per chain; j = the chain's reshuffles_total, a 32-bit counter beside sweeps_total that advances by one
+ * per proposed move, accepted or not, so no later call replays a draw (it wraps after 2^32 moves of one chain).
+ *   1. RANDOMNESS: X(k) = the four words of Philox(seed; idx = (j << 32) | k, chain = global chain id, purpose 10); U(k) = the
+ *      53-bit uniform of heat-bath step 3 from the first two words of X(k).  k = 0: the pair; k = 1: u_acc; with M members and
+ *      W = ceil(M / 128), k = 2 + (i >> 7) for i < M: the launch bit of member i is bit (i & 31) of word ((i >> 5) & 3) of X(k);
+ *      k = 2 + W + t * M + i: the uniform of member i in scan t (t = 0 .. scans-1: the launch scans; t = scans: the forward
+ *      pass).  A slot whose member is not free is never drawn.  A call with 2 + ceil(nmax / 128) + (scans + 1) * nmax >= 2^32,
+ *      nmax = max(na, nb), is BISBM_ERR_INVALID_ARG.
+ *   2. PAIR: N = C(ka, 2) + C(kb, 2) unordered pairs {r < s} of blocks of one type, enumerated type a first, each type
+ *      lexicographically ((0,1), (0,2), ..., (0,k-1), (1,2), ...); the pair is number (x * N) >> 32 with x the first word of
+ *      X(0), in 64-bit integers.  N = 0 (ka <= 1 and kb <= 1): the move is a counted no-op (record type BISBM_RESHUFFLE_NONE).
+ *      The choice never looks at the state.
+ *   3. MEMBERS: the nodes of that type whose label is r or s, in ascending id; M of them (M >= 2: no block is ever empty).
+ *   4. LAUNCH: member i gets s if its launch bit is set, else r; if no member got r, member 0 gets r; if none got s, member
+ *      M - 1 gets s; then `scans` >= 0 restricted scans (step 5).  The result L depends on the member set, the random stream
+ *      and the labels outside the set, never on how the members were divided.
+ *   5. RESTRICTED SCAN STEP: the members in ascending id.  Member v is in block c of {r, s}, o is the other one.  Not free
+ *      (n_r[c] == 1): v stays, the factor is 1.0, no uniform is drawn.  Free: dS_o = the entry of o of step 1 of "Node
+ *      conditionals" on the current state, bit for bit (the node's current block c in the place of r there), dS_c = 0.0;
+ *      dS_min = dS_o < 0.0 ? dS_o : 0.0; x = beta * (dS - dS_min); w = x > 700.0 ? 0.0 : exp(-x) for each of the two;
+ *      Z = w_r + w_s in that order; P_r = w_r / Z, P_s = w_s / Z; v goes to r iff u < P_r, else to s; the factor is the P of
+ *      the block it went to.  A move updates the label, m, m_r, n_r and eta as a heat-bath move does.
+ *   6. REVERSE PASS: from L, the members in the same order, each FORCED to its original label.  Q_rev starts as frexp(1.0) =
+ *      (0.5, 1) and is multiplied by one factor P(original label) at a time (1.0 for a member that is not free and stays):
+ *      mantissa = frexp(mantissa * factor, &e), exponent += e, so thousands of members do not underflow.  dS_rev starts at
+ *      0.0 and gets the dS_o of every forced move added, one at a time.  A forced move of a member that is not free, or a
+ *      factor of exactly 0.0, makes Q_rev = (0.0, 0) and the move a certain rejection: from that member on nothing is
+ *      evaluated or added (its own dS_o is not added either), the remaining members go to their original labels in transit
+ *      (step 9), the forward pass is not run, and the record holds dS_fwd = 0.0, Q_fwd = (0.0, 0), A = 0.0.  Either way the
+ *      pass ends exactly at the original state.
+ *   7. FORWARD PASS: L is set again (transit), then one free scan (t = scans) yields Q_fwd and dS_fwd as above; Q_fwd > 0
+ *      by construction.  The end state is the proposal.
+ *   8. ACCEPT: dS = dS_fwd - dS_rev; ln A = (0.0 - beta * dS) + (log(mant_rev / mant_fwd) + (double)(exp_rev - exp_fwd) *
+ *      0.6931471805599453); A = exp(ln A); accepted iff u_acc < A.  Accepted: the proposal stays and dS goes onto
+ *      bisbm_get_cum_dS with one add.  Rejected: labels, m, m_r, n_r and eta return to their values before the move, integer
+ *      for integer (transit), and the running sum is untouched.
+ *   9. TRANSIT (original -> launch labels, original -> L, proposal or a dead reverse pass -> original): moves are applied
+ *      without evaluating anything; a block may be empty on the way, and no table is read at such a state.
+ * Why exp(-beta S) stays invariant: the pair and L are drawn independently of how the members are divided, so x -> y and
+ * y -> x share every (pair, L); each contributes p(L) min(pi(x) q(y | L), pi(y) q(x | L)) to both directions (detailed balance).
+ * A move touches about 2 n / K nodes (scans + 2) times with an evaluation and up to three times in transit.
+ * Served and refused exactly as bisbm_heatbath_run: chains grouped by shape, several devices (everything is keyed by the global
+ * chain id), static or anchored modes being set are served; BISBM_RNG_MT19937_COMPAT and two-byte labels
+ * BISBM_ERR_UNSUPPORTED; replica exchange on BISBM_ERR_STATE; before bisbm_init / bisbm_shuffle BISBM_ERR_STATE; beta not
+ * finite or <= 0 BISBM_ERR_INVALID_ARG; each with a message and nothing changed.  moves = 0 is a no-op that zeroes
+ * accepted_out.  sweeps_total, accu_r, bisbm_get_last_counts, the early-stop bookkeeping, the genealogy and every analysis sum
+ * are untouched.  Scratch: 6 bytes per (chain, node of the larger type) -- member id, original label, launch label --
+ * allocated at the first call and freed with the handle; an allocation failure is BISBM_ERR_HIP with the size in the message.
+ * get_last: the last move of the last call of every chain (r, s: global labels); BISBM_ERR_STATE while a chain has none (no
+ * call yet, or its group was formed by a merge since).
+ * Out of scope: moves that change Ka or Kb, reshuffles inside bisbm_tempering_run / bisbm_population_run, a temperature per
+ * chain, mt19937-compat arithmetic, wide handles, choosing the pair by the state. */
+#define BISBM_RESHUFFLE_NONE 0xffffffffu
+typedef struct bisbm_reshuffle_record {
+    uint32_t type;     /* 0: a, 1: b, BISBM_RESHUFFLE_NONE: no pair (everything else 0) */
+    uint32_t r, s, M;
+    double dS_fwd, dS_rev;
+    double q_fwd_mant, q_rev_mant;
+    int32_t q_fwd_exp, q_rev_exp;
+    double u_acc, A;
+    uint32_t accepted;
+    uint32_t reserved;
+} bisbm_reshuffle_record;
+int bisbm_reshuffle_run(bisbm_handle h, uint64_t moves, uint32_t scans, double beta,
+                        uint64_t *accepted_out /* n_chains, may be NULL */);
+int bisbm_reshuffle_get_last(bisbm_handle h, bisbm_reshuffle_record *out /* n_chains */);
+/* The chains' reshuffles_total. */
+int bisbm_reshuffle_get_total(bisbm_handle h, uint64_t *out /* n_chains */);
 
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
@@ -779,6 +852,9 @@ int bisbm_last_pass_steps(bisbm_handle h, uint32_t *steps_per_pass);
  * evaluation, which uses a closed form of get_v/spence for k/sqrt(n) > 21. */
 int bisbm_debug_log_q(bisbm_handle h, const int32_t *n, const int32_t *k, size_t count, int fast,
                       double *out);
+
+/* Device numerics probe (tests, host replays of "Pair reshuffles"): out[i] = exp(x[i]) as the device evaluates it. */
+int bisbm_debug_exp(bisbm_handle h, const double *x, size_t count, double *out);
 
 const char *bisbm_last_error(bisbm_handle h); /* h may be NULL: error of the last failed create */
 int bisbm_abi_version(void);
