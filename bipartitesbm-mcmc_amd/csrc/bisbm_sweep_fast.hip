@@ -41,6 +41,7 @@
 // No generic pointers (flat loads wait on vmcnt AND lgkmcnt), no workgroup barriers on the step path.
 // Diagnostic hooks (BISBM_STAMPS, BISBM_ABLATE) are compiled out of the product build.
 #include "bisbm_kernels.hpp"
+#include "bisbm_stand_rule.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -105,21 +106,21 @@ __device__ __forceinline__ uint32_t smin(uint32_t x, uint32_t y) {
     return r;
 }
 
-// A later step's inverse-CDF target s' (the first block whose running sum S exceeds its draw x) lies strictly between the
-// blocks r and s of an earlier step that moves k of the column's edges from row r to row s.  Both S_{s'-1} and S_{s'} then move
-// by k: down when r < s (down = 1, edge = S_{s'}), up when r > s (down = 0, edge = S_{s'-1}).  The margin is how far they may
-// move with s' still the target: S_{s'} - 1 - x = ~(x - S_{s'}), or x - S_{s'-1}; both >= 0, and the target holds iff k <= margin.
-__device__ __forceinline__ uint32_t target_margin(uint32_t down, uint32_t edge, uint32_t x) { return (x - edge) ^ (0u - down); }
-// k > margin as a 0 / 1 word (both < 2^31: column sums are edge counts)
-__device__ __forceinline__ uint32_t target_moves(uint32_t margin, uint32_t k) { return (margin - k) >> 31; }
+// The stand rule's column test -- target_margin / target_moves of the two-steps passes, margin_up / margin_down /
+// column_clash of the deeper ones -- is bisbm_stand_rule.hpp: the text a CPU program checks is the text the kernel runs.
 
 // Diagnostic: committed steps per pass, and what the stand rule did with the passes in which the first step moved
 // (BISBM_PASS_COUNTS, compiled out of the product build; one line on stderr per launch)
 //   0 passes, 1 steps they committed, 2 two-steps passes whose first step moves with a second step to stand or fall, of those:
 //   3 a shared block, 4 / 5 a target strictly between r and s (k > 0, no shared block) that holds / moves, 6 / 7 the same at the
 //   boundary (k == margin / k == margin + 1)
+// Four- and eight-steps passes, over the pairs (i, j) whose earlier step i is committed and moves and whose later step j was still
+// in line to be committed (every step before it stands):
+//   8 a shared block, 9 / 10 a column candidate (target strictly between r_i and s_i, k > 0, no shared block) kept / refused,
+//   11 / 12 the same at the boundary ((D - 1) k == margin / (D - 1) k == margin + 1)
 #ifdef BISBM_PASS_COUNTS
-__device__ unsigned long long g_pass_counts[8];
+constexpr int kPassCounts = 13;
+__device__ unsigned long long g_pass_counts[kPassCounts];
 #define PCOUNT(i, v) (pc_acc[i] += (v))
 #define PASS_COUNTS_PAIR(paired)                                                          \
     do {                                                                                  \
@@ -376,7 +377,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
     __asm__ volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
 #endif
 #ifdef BISBM_PASS_COUNTS
-    unsigned long long pc_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long pc_acc[kPassCounts] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
 
     for (uint64_t sweep = 0; sweep < all_sweeps; ++sweep) {
@@ -1165,25 +1166,58 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                 };
 
                 // ---- four- and eight-steps passes (step_quad, step_quad32, step_oct): clashes, writes, the pass loop ----
+                using Four = std::integral_constant<uint32_t, 4u>;
+                using Eight = std::integral_constant<uint32_t, 8u>;
+#ifdef BISBM_PASS_COUNTS
+                uint32_t pc_pair_code = 0u;
+#endif
                 // pairwise: would step i, if it moves its node, touch what step j read?  One pair (i, j) per lane: li, lj are the
                 // bpermute addresses of the first lanes of steps i and j, k_of_i_at(li, t_j) fetches k of step i at block t_j.
                 // (worked out while the table gathers are in flight: after ALL of them have been issued -- the table tier of log_q is one more --, see step_pair)
-                auto clash_pairs = [&](uint32_t r_loc, uint32_t s_loc, uint32_t t_loc, int li, int lj, auto&& k_of_i_at) -> unsigned long long {
-                    uint32_t r_c = r_loc, s_c = s_loc, t_c = t_loc;
-                    __asm__ volatile("" : "+v"(r_c), "+v"(s_c), "+v"(t_c)::"memory");
+                // A target of step j strictly between r_i and s_i falls only if step i's move of column t_j can move it, with up to
+                // depth - 1 movers ahead of step j (column_clash, bisbm_stand_rule.hpp).  margins: the two margins of the lane's own step
+                // as the lane of block b sees them (pack_margins of margin_up / margin_down on its S_b and w_b; step_quad32: on the
+                // leaf that holds the step's target); the pair lane reads those of the lane that holds s_j.
+                auto clash_pairs = [&](auto depth, uint32_t r_loc, uint32_t s_loc, uint32_t t_loc, uint32_t margins, int li, int lj,
+                                       auto&& k_of_i_at) -> unsigned long long {
+                    constexpr uint32_t DEPTH = decltype(depth)::value;
+                    uint32_t r_c = r_loc, s_c = s_loc, t_c = t_loc, m_c = margins;
+                    __asm__ volatile("" : "+v"(r_c), "+v"(s_c), "+v"(t_c), "+v"(m_c)::"memory");
                     const uint32_t r_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)r_c);
                     const uint32_t s_i = (uint32_t)__builtin_amdgcn_ds_bpermute(li, (int)s_c);
                     const uint32_t r_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)r_c);
                     const uint32_t s_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)s_c);
                     const uint32_t t_j = (uint32_t)__builtin_amdgcn_ds_bpermute(lj, (int)t_c);
+                    const int at_sj = lj + (int)((s_j & 15u) << 2);  // the lane of step j that holds block s_j (either leaf)
+                    const uint32_t margins_j = (uint32_t)__builtin_amdgcn_ds_bpermute(at_sj, (int)m_c);
                     const uint32_t k_i_tj = k_of_i_at(li, t_j);
                     const uint32_t set_i = (1u << r_i) | (1u << s_i), set_j = (1u << r_j) | (1u << s_j);
-                    const uint32_t lo = min(r_i, s_i), hi = max(r_i, s_i);
-                    const uint32_t between = ((1u << hi) - 1u) & ~((2u << lo) - 1u);  // blocks strictly between r_i and s_i
                     // (bit arithmetic, no short-circuit: a lane-divergent `||` becomes a branch over the execution mask)
-                    const uint32_t in_between = (between >> s_j) & min(k_i_tj, 1u);
+                    const uint32_t in_between = column_clash<DEPTH>(r_i, s_i, s_j, k_i_tj, margins_j);
+#ifdef BISBM_PASS_COUNTS
+                    {  // what the pair would be counted as, should step i move: bit 0 shared block, 1 column candidate, 2 refused, 3 / 4 boundary
+                        const uint32_t shared = (set_i & set_j) != 0u ? 1u : 0u;
+                        const uint32_t cand = column_clash_any(r_i, s_i, s_j, k_i_tj) & (shared ^ 1u);
+                        const uint32_t margin = packed_margin(margins_j, r_i < s_i ? 1u : 0u), need = (DEPTH - 1u) * k_i_tj;
+                        pc_pair_code = shared | (cand << 1) | ((cand & in_between) << 2) | ((cand & (need == margin ? 1u : 0u)) << 3) |
+                                       ((cand & (need == margin + 1u ? 1u : 0u)) << 4);
+                    }
+#endif
                     return __builtin_amdgcn_ballot_w64(((set_i & set_j) | in_between) != 0u);
                 };
+#ifdef BISBM_PASS_COUNTS
+                // the diagnostic counters 8..12 of a deep pass: the lane's pair (i, j), counted if step i is a committed mover and
+                // every step before j stands
+                auto count_pairs = [&](uint32_t i, uint32_t j, bool pair_lane, uint32_t moved, uint32_t commit, uint32_t nst) {
+                    const bool on = pair_lane && i < j && j < nst && ((moved >> i) & 1u) != 0u && ((commit >> ((j - 1u) & 7u)) & 1u) != 0u;
+                    const uint32_t c = on ? pc_pair_code : 0u;
+                    pc_acc[8] += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64((c & 1u) != 0u));
+                    pc_acc[9] += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64((c & 6u) == 2u));
+                    pc_acc[10] += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64((c & 6u) == 6u));
+                    pc_acc[11] += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64((c & 8u) != 0u));
+                    pc_acc[12] += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64((c & 16u) != 0u));
+                };
+#endif
                 // apply_mcmc_moves, blockmodel.cc:461-503, for the steps of a pass of `width` steps that move (bits of `moved`; their
                 // rows of m differ); selfok: committed steps that are an accepted r == s.  The lane's step is qs, group grp_l of
                 // 64 / width lanes; ee: the lane's eta entry; write_mq(movers): the pass's writes of rows r and s of m (one or two leaves per lane).
@@ -1237,8 +1271,6 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     }
                     acc_l0 += (unsigned long long)acc_chunk;
                 };
-                using Four = std::integral_constant<uint32_t, 4u>;
-                using Eight = std::integral_constant<uint32_t, 8u>;
 
                 // ---- two steps per pass (K <= 32, constant T > 0, no early-stop bookkeeping) ----
                 // The hot step uses lanes 0..31 (one lane per block).  Here lanes 32..63 evaluate step q + 1 in the same
@@ -1559,7 +1591,8 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const double lq = hot_log_q(std::true_type{}, t.qn, t.qk, t.logn);
                     // lane 4 i + j, any row: steps i and j (first lanes 16 i, 16 j); bit 4 i + j of the word
                     const uint32_t clash_bits =
-                        (uint32_t)clash_pairs(r_loc, s_loc, t_loc, (int)(((lane >> 2) & 3u) << 6), (int)((lane & 3u) << 6), [&](int li, uint32_t t_j) {
+                        (uint32_t)clash_pairs(Four{}, r_loc, s_loc, t_loc, pack_margins(margin_up((uint32_t)scan, (uint32_t)w_piv, prop), margin_down((uint32_t)scan, prop)),
+                                              (int)(((lane >> 2) & 3u) << 6), (int)((lane & 3u) << 6), [&](int li, uint32_t t_j) {
                             return (uint32_t)__builtin_amdgcn_ds_bpermute(li + (int)(t_j << 2), (int)kk);  // k of step i at block t_j
                         }) & 0xffffu;
                     double d = (L1 + t.L2) - (L3 + t.L4);
@@ -1570,6 +1603,9 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const uint32_t mv4 = rows4(b_can & b_acc), selfok4 = rows4(b_selfok);
                     uint32_t moved, commit;
                     commit_four(nst, clash_bits, mv4, moved, commit);
+#ifdef BISBM_PASS_COUNTS
+                    count_pairs((lane >> 2) & 3u, lane & 3u, lane < 16u, moved, commit, nst);
+#endif
                     apply_moves(tm, Four{}, q, qs, row, moved, commit & selfok4, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {
                             mq[a_rt] = m_rt_raw - k;
@@ -1634,6 +1670,13 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     TargetReads2 t;
                     target_lds2(t, s_loc, r_loc, deg, kmask0, kmask1, l16, 16u);
                     target_gathers2(t, kk0, kk1, std::true_type{});
+                    // the step's margins on the leaf that holds the row's target (blocks 16.. are the upper leaf), in one register from
+                    // here on: the two scans, the two column entries and the draw end here (the variant has no register to spare)
+                    const uint32_t leaf_m = 0u - (s_loc >> 4);
+                    const uint32_t S_own = (uint32_t)scan0 ^ (((uint32_t)scan0 ^ (uint32_t)scan1) & leaf_m);
+                    const uint32_t w_own = (uint32_t)w0 ^ (((uint32_t)w0 ^ (uint32_t)w1) & leaf_m);
+                    uint32_t margins = pack_margins(margin_up(S_own, w_own, prop), margin_down(S_own, prop));
+                    __asm__ volatile("" : "+v"(margins));
                     // the lane's two leaves of each Hastings sum, added first (level 16 of their tree)
                     const double a0 = k0 * (t.m_st0 + eps) * invq_lo + k1 * (t.m_st1 + eps) * invq_hi;
                     const double a1 = k0 * (m_rt0 - k0 + eps) * invq_lo + k1 * (m_rt1 - k1 + eps) * invq_hi;
@@ -1642,7 +1685,8 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const double lq = hot_log_q(std::false_type{}, t.qn, t.qk, t.logn);
                     // lane 4 i + j, any row: steps i and j, as in step_quad
                     const uint32_t clash_bits =
-                        (uint32_t)clash_pairs(r_loc, s_loc, t_loc, (int)(((lane >> 2) & 3u) << 6), (int)((lane & 3u) << 6), [&](int li, uint32_t t_j) {
+                        (uint32_t)clash_pairs(Four{}, r_loc, s_loc, t_loc, margins,
+                                              (int)(((lane >> 2) & 3u) << 6), (int)((lane & 3u) << 6), [&](int li, uint32_t t_j) {
                             const int src = li + (int)((t_j & 15u) << 2);  // k of step i at block t_j: leaf t_j >> 4 of lane t_j & 15 of row i
                             const uint32_t k_lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk0);
                             const uint32_t k_hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk1);
@@ -1657,6 +1701,9 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const uint32_t mv4 = rows4(b_can & b_acc), selfok4 = rows4(b_selfok);
                     uint32_t moved, commit;
                     commit_four(nst, clash_bits, mv4, moved, commit);
+#ifdef BISBM_PASS_COUNTS
+                    count_pairs((lane >> 2) & 3u, lane & 3u, lane < 16u, moved, commit, nst);
+#endif
                     apply_moves(tm, Four{}, q, qs, row, moved, commit & selfok4, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth32_lo)) {
                             mq[a_rt0] = m_rt_raw0 - k0;
@@ -1722,7 +1769,8 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                     const double lq = hot_log_q(std::true_type{}, t.qn, t.qk, t.logn);
                     // lane 8 j + i: steps i and j (first lanes 8 i, 8 j).  byte j, bit i: step i (earlier), if it moves, touches what step j read
                     const unsigned long long clash_bits =
-                        clash_pairs(r_loc, s_loc, t_loc, (int)((lane & 7u) << 5), (int)((lane >> 3) << 5), [&](int li, uint32_t t_j) {
+                        clash_pairs(Eight{}, r_loc, s_loc, t_loc, pack_margins(margin_up((uint32_t)scan, (uint32_t)w_piv, prop), margin_down((uint32_t)scan, prop)),
+                                    (int)((lane & 7u) << 5), (int)((lane >> 3) << 5), [&](int li, uint32_t t_j) {
                             return (uint32_t)__builtin_amdgcn_ds_bpermute(li + (int)(t_j << 2), (int)kk);
                         });
                     double d = (L1 + t.L2) - (L3 + t.L4);
@@ -1741,6 +1789,9 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                         commit |= stands << j;
                         moved |= (stands & (mv8 >> j) & 1u) << j;
                     }
+#ifdef BISBM_PASS_COUNTS
+                    count_pairs(lane & 7u, lane >> 3, true, moved, commit, nst);
+#endif
                     apply_moves(tm, Eight{}, q, qs, grp, moved, commit & selfok8, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {
                             mq[a_rt] = m_rt_raw - k;
@@ -1875,7 +1926,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
 #endif
 #ifdef BISBM_PASS_COUNTS
     if (lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(&g_pass_counts[i], pc_acc[i]);
+        for (int i = 0; i < kPassCounts; ++i) atomicAdd(&g_pass_counts[i], pc_acc[i]);
 #endif
     if (lane == 0) {
         // (a launch without the early-stop bookkeeping has not kept the running sum: bisbm_anneal sets it from the change of the
@@ -1980,13 +2031,14 @@ hipError_t launch_sweep_fast(const SweepParams& p, size_t /*generic_lds_bytes*/,
 #ifdef BISBM_PASS_COUNTS
     if (e == hipSuccess) {
         (void)hipStreamSynchronize(stream);
-        unsigned long long h[8] = {0};
+        unsigned long long h[kPassCounts] = {0};
         (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pass_counts), sizeof(h));
         fprintf(stderr,
                 "[pass_counts] passes %llu steps %llu first_moves %llu shared_block %llu target_holds %llu target_moves %llu "
-                "holds_at_boundary %llu moves_at_boundary %llu\n",
-                h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-        const unsigned long long z[8] = {0};
+                "holds_at_boundary %llu moves_at_boundary %llu deep_shared_block %llu deep_kept %llu deep_refused %llu "
+                "deep_kept_at_boundary %llu deep_refused_at_boundary %llu\n",
+                h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12]);
+        const unsigned long long z[kPassCounts] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pass_counts), z, sizeof(z));
     }
 #endif
