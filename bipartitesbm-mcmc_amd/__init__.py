@@ -56,6 +56,8 @@ PHILOX_PURPOSE_HEATBATH = 9
 # ... and of the pair reshuffles (PHX_RESHUFFLE), and the record type of a move without a pair (BISBM_RESHUFFLE_NONE)
 PHILOX_PURPOSE_RESHUFFLE = 10
 RESHUFFLE_NONE = 0xFFFFFFFF
+# bisbm_trace_get_series: which series (BISBM_TRACE_S, BISBM_TRACE_H)
+TRACE_S, TRACE_H = 0, 1
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -157,6 +159,12 @@ ABI = {
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
     "bisbm_partition_modes": (C.c_int, [C.c_uint32, _f64p, C.c_double, _u32p, _u32p, _u32p]),
+    "bisbm_trace_set": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "bisbm_trace_record": (C.c_int, [C.c_void_p]),
+    "bisbm_trace_reset": (C.c_int, [C.c_void_p]),
+    "bisbm_trace_get_lags": (C.c_int, [C.c_void_p, _f64p, _u64p, _f64p, _u64p, _u64p]),
+    "bisbm_trace_get_series": (C.c_int, [C.c_void_p, C.c_int, _f64p]),
+    "bisbm_trace_summary": (C.c_int, [C.c_uint64, C.c_uint32, _f64p, C.c_double, _f64p, _u32p, _f64p]),
     "bisbm_get_ka_kb": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bisbm_get_ka_kb_chain": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "bisbm_agg_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -1201,6 +1209,52 @@ class BlockModel:
         return {"chains": sel, "mode": mode, "medoids": sel[med], "weights": np.bincount(mode, minlength=len(med)) / len(sel),
                 "lowest_entropy": low, "vi": vi}
 
+    # -- chain traces (include/bisbm.h, "Chain traces")
+    def trace_set(self, depth):
+        """A ring of `depth` snapshots of every chain's partition on the device (0 frees it); forgets every earlier record."""
+        self._check(self._L.bisbm_trace_set(self._h, int(depth)))
+        self.trace_depth = int(depth)
+
+    def trace_record(self):
+        """One record: every chain's VI and unchanged-node count against each of its held snapshots, its description length and
+        partition entropy appended to the series, then the current partitions pushed into the ring.  Reads state only."""
+        self._check(self._L.bisbm_trace_record(self._h))
+
+    def trace_reset(self):
+        """Forgets snapshots, sums and series; the depth stays."""
+        self._check(self._L.bisbm_trace_reset(self._h))
+
+    def _trace_raw(self):
+        D = int(getattr(self, "trace_depth", 0))
+        vi_sum = np.zeros((self.n_chains, D), dtype=np.float64)
+        agree = np.zeros((self.n_chains, D), dtype=np.uint64)
+        vi_last = np.zeros((self.n_chains, D), dtype=np.float64)
+        pairs = np.zeros(D, dtype=np.uint64)
+        rec = C.c_uint64()
+        self._check(self._L.bisbm_trace_get_lags(self._h, _p(vi_sum, _f64p), _p(agree, _u64p), _p(vi_last, _f64p), _p(pairs, _u64p), C.byref(rec)))
+        return vi_sum, agree, vi_last, pairs, int(rec.value)
+
+    def trace_lags(self):
+        """The lag curves since the last set / reset, a dict of arrays [n_chains, depth] (column a - 1: age a, in records):
+        `vi_mean` = vi_sum / pairs, `changed` = 1 - agree_sum / (pairs n), the share of nodes whose label differs, `vi_last` (the
+        last record's VI, NaN for ages not yet held); and `vi_sum`, `agree_sum` as the library keeps them, `pairs` uint64 [depth],
+        `records`.  Lags with pairs == 0 are NaN in vi_mean and changed."""
+        vi_sum, agree, vi_last, pairs, rec = self._trace_raw()
+        den = np.where(pairs > 0, pairs.astype(np.float64), np.nan)
+        return {"vi_mean": vi_sum / den, "changed": 1.0 - agree.astype(np.float64) / (den * float(self.n)), "vi_last": vi_last,
+                "vi_sum": vi_sum, "agree_sum": agree, "pairs": pairs, "records": rec}
+
+    def trace_series(self, what="S"):
+        """float64 [records, n_chains]: the description length ("S", what entropy() returned at every record) or the partition
+        entropy ("H") of every chain at every record."""
+        if what not in ("S", "H"):
+            raise ValueError("what must be \"S\" or \"H\", not %r" % (what,))
+        rec = C.c_uint64()
+        self._check(self._L.bisbm_trace_get_lags(self._h, None, None, None, None, C.byref(rec)))
+        out = np.zeros((int(rec.value), self.n_chains), dtype=np.float64)
+        self._check(self._L.bisbm_trace_get_series(self._h, TRACE_S if what == "S" else TRACE_H, _p(out, _f64p)))
+        return out
+
     def device_layout(self):
         """(device ordinals, first chain of each device) behind this handle."""
         nd = C.c_int()
@@ -1273,6 +1327,27 @@ def partition_modes(vi, threshold):
     if rc != BISBM_OK:
         raise BisbmError(rc, (lib().bisbm_last_error(None) or b"").decode())
     return mode[:m], med[: n_modes.value]
+
+
+def trace_summary(x, window=5.0):
+    """(tau float64 [C], window uint32 [C], rhat) of a series x [T, C] (one column per chain; a 1-d series is one chain) on the
+    host (bisbm_trace_summary): each chain's integrated autocorrelation time with Sokal's automatic window (stop at the first
+    lag M >= window * tau; window[c] == T // 2 says the series was too short, a chain that never moved has tau = inf and window
+    0), and the split R-hat over the chains.  5.0 is Sokal's convention, not a measurement.  Needs no device."""
+    v = np.asarray(x, dtype=np.float64)
+    if v.ndim == 1:
+        v = v[:, None]
+    if v.ndim != 2:
+        raise ValueError("x must be a series [T] or [T, C]")
+    v = np.ascontiguousarray(v)
+    T, Cn = v.shape
+    tau = np.zeros(max(Cn, 1), dtype=np.float64)
+    win = np.zeros(max(Cn, 1), dtype=np.uint32)
+    rhat = C.c_double()
+    rc = lib().bisbm_trace_summary(T, Cn, _p(v, _f64p), float(window), _p(tau, _f64p), _p(win, _u32p), C.byref(rhat))
+    if rc != BISBM_OK:
+        raise BisbmError(rc, (lib().bisbm_last_error(None) or b"").decode())
+    return tau[:Cn], win[:Cn], rhat.value
 
 
 def validate_ladder(ladder):

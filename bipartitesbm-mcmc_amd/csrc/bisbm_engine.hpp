@@ -23,6 +23,7 @@
 //   bisbm_reshuffle.hip  pair reshuffles: two blocks' nodes divided afresh in one accepted or rejected move; kernel and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
+//   bisbm_trace.hip      chain traces: a ring of each chain's own snapshots, lagged distances to them, the S / H series, tau and R-hat
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -328,6 +329,27 @@ struct PartitionState {
     DeviceBuf<uint8_t> d_refs;    // distances_to: the caller's reference partitions as byte rows, padded like label rows
 };
 
+// Chain traces (bisbm_trace.hip).  The depth, the sums and the series belong to the handle the caller holds, in its chain order;
+// the ring and the scratch belong to every device entry (a plain handle, an entry of `devs`) for its own chains, whatever their
+// grouping by shape.
+struct TraceState {
+    uint32_t depth = 0;              // snapshots held per chain; 0: off
+    uint64_t records = 0;            // records since the last set / reset; the next one goes to slot records % depth
+    std::vector<double> A_ring;      // [depth][n_chains] sum_r a_r ln a_r of every held snapshot
+    std::vector<uint32_t> snap_ka, snap_kb;  // [n_chains] the shape the held snapshots were taken with
+    std::vector<double> vi_sum, vi_last;     // [n_chains][depth]
+    std::vector<uint64_t> agree_sum;         // [n_chains][depth]
+    std::vector<uint64_t> pairs;             // [depth]
+    std::vector<double> S, H;        // [records][n_chains]
+    // device entry
+    DeviceBuf<uint8_t> d_ring;       // [depth][chains of the entry][label_stride] label rows
+    DeviceBuf<uint8_t> d_desc;       // [chains] row pointer, ka, kb of the current partitions (ChainDesc, as bytes)
+    DeviceBuf<double> d_A;           // [chains] sum_r a_r ln a_r now
+    DeviceBuf<double> d_snn;         // [chains][ages] sum_rs n_rs ln n_rs
+    DeviceBuf<unsigned long long> d_agree;   // [chains][ages] sum_r n_rr
+    DeviceBuf<uint32_t> d_tab;       // few workgroups or a table beyond the LDS: the integer tables of one launch
+};
+
 // Mode-resolved marginals (bisbm_mode_marginals.hip).  The assignment of chains to modes, the references and `terms` belong to
 // the handle the caller holds; `scratch` and the histogram slices belong to the engines that run the kernels (a plain handle, a
 // device entry: chains grouped by shape are refused).
@@ -449,6 +471,7 @@ struct bisbm_engine {
     bisbm::ReshuffleState reshuffle;
     bisbm::PartitionState partition;
     bisbm::ModeState modes;
+    bisbm::TraceState trace;
 };
 
 namespace bisbm {

@@ -12,6 +12,7 @@
 //   few pairs: the nodes are split over workgroups, the tables are added into HBM and partition_reduce_kernel reduces them
 //     (bisbm_partition_contingency copies one such table out instead); a table too large for LDS is counted straight in HBM.
 // Both reduce with wave_xlnx: one wave per table, lane-strided, butterfly -- the same bits from the same integers.
+// (ChainDesc, count_cell, wave_xlnx and partition_sizes_kernel: bisbm_partition_device.hpp, shared with bisbm_trace.hip.)
 // Chains against reference partitions that are no chains (bisbm_partition_distances_to, and the anchored modes of
 // bisbm_mode_marginals.hip through partition_distances_rows) run the same kernels in their RECT form: the tile is T selected
 // chains (rows) x T references (columns, byte rows of their own shapes), every pair (row < m, column < mc) is live instead of
@@ -19,15 +20,11 @@
 // B_g = sum_s b_s ln b_s of a reference is partition_sizes_kernel over the reference rows.
 // The chains' state is only read.
 #include "bisbm_engine.hpp"
+#include "bisbm_partition_device.hpp"
 
 using namespace bisbm;
 
 namespace {
-
-struct ChainDesc {
-    const uint8_t* row;  // n labels (readable up to the next multiple of 4)
-    uint32_t ka, kb;
-};
 
 struct CountParams {
     const ChainDesc* chains;  // [m] the row partitions
@@ -42,36 +39,6 @@ struct CountParams {
 template <bool RECT>
 __device__ __forceinline__ bool pair_live(const CountParams& p, uint32_t i, uint32_t j) {
     return RECT ? i < p.m && j < p.mc : i < j && j < p.m;
-}
-
-constexpr uint32_t kNone = 0xffffffffu;
-
-// sum of x ln x over a table by one wave, in an order fixed by `cells`: lane l adds cells l, l + 64, ... in turn, then a
-// butterfly over the lanes (every lane ends with the same bits)
-__device__ double wave_xlnx(const uint32_t* t, uint32_t cells, uint32_t lane) {
-    double s = 0.;
-    for (uint32_t i = lane; i < cells; i += 64) {
-        const uint32_t x = t[i];
-        if (x > 1u) {
-            const double d = (double)x;
-            s += d * log(d);
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
-}
-
-// one count into cell idx (kNone: nothing) by every lane of a converged wave: the lanes that share the first lane's cell add
-// once, together
-__device__ __forceinline__ void count_cell(uint32_t* t, uint32_t idx, uint32_t lane) {
-    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)idx);
-    const bool same = idx == first;
-    const unsigned long long mask = __ballot(same);
-    if (same) {
-        if (first != kNone && lane == (uint32_t)__ffsll(mask) - 1u) atomicAdd(t + idx, (uint32_t)__popcll(mask));
-    } else if (idx != kNone) {
-        atomicAdd(t + idx, 1u);
-    }
 }
 
 // the node loop of partition_count_kernel: counts the nodes [v0, v1) of the tile's pairs into tabs (LDS, or HBM for tables too
@@ -172,34 +139,6 @@ __global__ __launch_bounds__(64) void partition_reduce_kernel(CountParams p, uin
     const ChainDesc c = p.chains[gi], d = p.cols[gj];
     const double s = wave_xlnx(p.tab + ((size_t)blockIdx.x * (T * T) + q) * p.stride, c.ka * d.ka + c.kb * d.kb, threadIdx.x);
     if (threadIdx.x == 0) p.snn[(size_t)gi * p.mc + gj] = s;
-}
-
-// A_c = sum_r a_r ln a_r of every selected chain: one workgroup per chain counts the label bytes into a table per wave (256
-// cells, the global label is the index), adds the tables and reduces with wave_xlnx
-__global__ __launch_bounds__(1024) void partition_sizes_kernel(const ChainDesc* chains, uint32_t n, double* A) {
-    __shared__ uint32_t cnt[16 * 256];
-    const ChainDesc c = chains[blockIdx.x];
-    for (uint32_t i = threadIdx.x; i < 16 * 256; i += 1024) cnt[i] = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t* mine = cnt + (threadIdx.x / 64u) * 256u;
-    for (uint32_t w0 = 0; w0 < n; w0 += 4 * 1024) {
-        const uint32_t w = w0 + 4 * threadIdx.x;
-        const uint32_t L = w < n ? *(const uint32_t*)(c.row + w) : 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) count_cell(mine, w + j < n ? (L >> (8 * j)) & 0xffu : kNone, lane);
-    }
-    __syncthreads();
-    uint32_t x = 0;
-    if (threadIdx.x < 256)
-        for (uint32_t k = 0; k < 16; ++k) x += cnt[k * 256 + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x < 256) cnt[threadIdx.x] = x;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const double s = wave_xlnx(cnt, 256, lane);
-        if (lane == 0) A[blockIdx.x] = s;
-    }
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------

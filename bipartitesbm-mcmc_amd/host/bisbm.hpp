@@ -465,6 +465,27 @@ public:
                                            ref_kb.data(), vi.data(), h_ref ? h_ref->data() : nullptr));
         return vi;
     }
+    // chain traces (include/bisbm.h): the ring, one record, the lag sums and a series ([records][chains]); summary on the host
+    void trace_set(uint32_t depth) { check(bisbm_trace_set(h_, depth)); }
+    void trace_reset() { check(bisbm_trace_reset(h_)); }
+    void trace_record() { check(bisbm_trace_record(h_)); }
+    uint64_t trace_lags(uint32_t depth, std::vector<double>& vi_sum, std::vector<uint64_t>& agree_sum, std::vector<uint64_t>& pairs) {
+        vi_sum.assign((size_t)n_chains_ * depth, 0.), agree_sum.assign((size_t)n_chains_ * depth, 0), pairs.assign(depth, 0);
+        uint64_t records = 0;
+        check(bisbm_trace_get_lags(h_, vi_sum.data(), agree_sum.data(), nullptr, pairs.data(), &records));
+        return records;
+    }
+    std::vector<double> trace_series(int what, uint64_t records) {
+        std::vector<double> x((size_t)records * n_chains_);
+        check(bisbm_trace_get_series(h_, what, x.data()));
+        return x;
+    }
+    static void trace_summary(const std::vector<double>& x, uint64_t T, uint32_t C, double window, std::vector<double>& tau,
+                              std::vector<uint32_t>& win, double& rhat) {
+        tau.assign(C, 0.), win.assign(C, 0);
+        if (bisbm_trace_summary(T, C, x.data(), window, tau.data(), win.data(), &rhat) != BISBM_OK)
+            throw std::runtime_error(std::string("bisbm: ") + bisbm_last_error(nullptr));
+    }
     static void partition_modes(const std::vector<double>& vi, size_t m, double threshold, std::vector<uint32_t>& mode,
                                 std::vector<uint32_t>& medoids) {
         mode.assign(m, 0);

@@ -6,7 +6,7 @@
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
 // --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
-// --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans.
+// --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -59,6 +59,7 @@ const option_spec kOptions[] = {
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
     {"polish", 0, 1},           {"heatbath", 0, 0},
     {"reshuffle", 0, 1},        {"reshuffle_scans", 0, 1},
+    {"trace", 0, 2},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -267,6 +268,14 @@ void print_help(const char* argv0) {
                  "                                        --tempering (the chains at T0 are counted).  PREFIX.assignment.txt\n"
                  "                                        receives `chain visits-per-mode` per chain and a last line `unassigned N`;\n"
                  "                                        a mode's reported share is its share of the samples.\n"
+                 "  --trace OUT DEPTH                     With --marginalize: every chain keeps its last DEPTH sampled partitions\n"
+                 "                                        (1 <= DEPTH <= 1024) and every sample is compared with them.  OUT receives\n"
+                 "                                        `lag pairs mean_VI mean_changed` per lag (in samples; means over the\n"
+                 "                                        chains: VI in nats, the share of nodes whose label differs), then\n"
+                 "                                        `tau_S window` per chain, in chain order (the integrated autocorrelation\n"
+                 "                                        time of the description length, in samples, Sokal's window with c = 5;\n"
+                 "                                        window = samples / 2 means the run was too short), then one line with\n"
+                 "                                        rhat_S, the split R-hat of the description length over the chains.\n"
                  "  --csr_cache                           Keep a binary CSR beside the edge list (<path>.bisbm_csr, checked\n"
                  "                                        against the file's size and mtime); the text file stays the input.\n";
 }
@@ -424,6 +433,25 @@ int main(int argc, char const* argv[]) {
             std::cerr << "Invalid --modes. The threshold must be a finite number >= 0 (nats), e.g. --modes modes.txt 0.05.\n";
             return 1;
         }
+    }
+    uint32_t trace_depth = 0;
+    if (var_map.count("trace") && !count("marginalize")) {
+        std::cerr << "--trace compares every sample of a chain with its earlier samples: it needs --marginalize.\n";
+        return 1;
+    }
+    if (var_map.count("trace")) {
+        if (var_map["trace"].size() != 2) {
+            std::cerr << "Invalid --trace. Two arguments: the file to write and the number of earlier samples every chain keeps.\n";
+            return 1;
+        }
+        const std::string tok = var_map["trace"][1];
+        char* end = nullptr;
+        const unsigned long long d = std::strtoull(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0' || tok[0] == '-' || d < 1 || d > 1024) {
+            std::cerr << "Invalid --trace. The depth must be an integer in 1 .. 1024, e.g. --trace trace.txt 16.\n";
+            return 1;
+        }
+        trace_depth = (uint32_t)d;
     }
     if (count("mode_marginals") && !var_map.count("modes")) {
         std::cerr << "--mode_marginals counts one histogram per mode: it needs --modes (with --marginalize) for the grouping.\n";
@@ -1268,9 +1296,14 @@ int main(int argc, char const* argv[]) {
                 for (uint32_t v : conditional_queries) q.push_back(new_id.empty() ? v : new_id[v]);
                 blockmodel.conditionals_set(q, conditionals_beta);
             }
+            if (trace_depth) {
+                blockmodel.trace_set(trace_depth);
+                blockmodel.trace_reset();
+            }
             for (size_t sample = 0; sample < n_samples; ++sample) {
                 advance(sweeps_between);
                 blockmodel.marginals_accumulate();
+                if (trace_depth) blockmodel.trace_record();
                 if (!conditional_queries.empty()) {
                     if (soft && sample == 0) blockmodel.conditionals_set_reference(blockmodel.marginals_reference_labels());
                     blockmodel.conditionals_accumulate();
@@ -1303,6 +1336,40 @@ int main(int argc, char const* argv[]) {
             }
             if (count("align") && !per_mode)
                 std::clog << "align: labels matched to chain " << blockmodel.marginals_reference_chain() << " (lowest description length)\n";
+            if (trace_depth) {
+                const std::string out_path = var_map["trace"][0];
+                std::ofstream out(out_path);
+                std::vector<double> vi_sum, tau;
+                std::vector<uint64_t> agree_sum, pairs;
+                std::vector<uint32_t> win;
+                const uint64_t records = blockmodel.trace_lags(trace_depth, vi_sum, agree_sum, pairs);
+                char line[160];
+                for (uint32_t a = 0; a < trace_depth; ++a) {  // means over the chains; a lag that was never held: nan
+                    double vi = 0., agree = 0.;
+                    for (uint32_t c = 0; c < opt.n_chains; ++c) vi += vi_sum[(size_t)c * trace_depth + a], agree += (double)agree_sum[(size_t)c * trace_depth + a];
+                    const double den = pairs[a] ? (double)pairs[a] * (double)opt.n_chains : std::nan("");
+                    std::snprintf(line, sizeof(line), "%u %llu %.17g %.17g\n", a + 1, (unsigned long long)pairs[a], vi / den, 1. - agree / (den * (double)N));
+                    out << line;
+                }
+                double rhat = std::nan("");
+                if (records >= 4) {
+                    blockmodel_t::trace_summary(blockmodel.trace_series(BISBM_TRACE_S, records), records, opt.n_chains, 5.0, tau, win, rhat);
+                } else {  // (too few samples for a summary)
+                    tau.assign(opt.n_chains, std::nan("")), win.assign(opt.n_chains, 0);
+                }
+                for (uint32_t c = 0; c < opt.n_chains; ++c) {
+                    std::snprintf(line, sizeof(line), "%.17g %u\n", tau[c], win[c]);
+                    out << line;
+                }
+                std::snprintf(line, sizeof(line), "%.17g\n", rhat);
+                out << line;
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --trace: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "trace: " << records << " record(s) of " << opt.n_chains << " chain(s), " << trace_depth << " lag(s) -> " << out_path << "\n";
+            }
             if (count("score_pairs")) {
                 const std::string out_path = var_map["score_pairs"][1];
                 std::ofstream out(out_path);

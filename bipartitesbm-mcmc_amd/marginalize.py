@@ -18,7 +18,7 @@ import numpy as np
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
-                similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3):
+                similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -68,7 +68,11 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     `reshuffles`: m > 0 runs model.reshuffle(m, reshuffle_scans, 1.0) after every block of sweeps -- the burn-in and every gap
     between samples (include/bisbm.h, "Pair reshuffles"; 3 scans are the convention of the literature, not a measurement); with
     `tempering` a ValueError.  model.reshuffle_stats = {"proposed", "accepted"} (totals over the chains of this rank) reports
-    the acceptance afterwards."""
+    the acceptance afterwards.
+    `trace`: depth > 0 (include/bisbm.h, "Chain traces"): a ring of that many snapshots per chain is set, with everything
+    forgotten, before the first sample, and every sample is followed by one model.trace_record().  The return value does not
+    change: model.trace_lags() / model.trace_series() give the lag curves and the series afterwards (lags in units of
+    sampling_frequency_sweeps), trace_summary() tau and R-hat.  The chains of this rank only."""
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
@@ -89,9 +93,12 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         model.foldin_set(foldin[0], foldin[2] if len(foldin) > 2 else None)
     if conditionals is not None:
         model.conditionals_set(conditionals[0], conditionals[1] if len(conditionals) > 1 else 1.0)
+    _trace_start(model, trace)
     taken = [0]
 
     def conditional_sample():
+        if trace:
+            model.trace_record()
         if conditionals is None:
             return
         if align and taken[0] == 0:  # (the aligned histogram has its reference from its first sample on)
@@ -177,7 +184,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
 
 
 def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,
-                      reassign=False, tempering=None, exchange_every=1, sampler="mh"):
+                      reassign=False, tempering=None, exchange_every=1, sampler="mh", trace=None):
     """Mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): the chains are grouped into posterior modes and
     every mode gets an aligned histogram and a MAP of its own, in the numbering of its own reference.
     Exactly one of `threshold` and `mode_of_chain`: with `threshold` the grouping is model.partition_modes(threshold) taken
@@ -201,7 +208,8 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     throughout.  `tempering` (with `reassign` only; ValueError otherwise): a temperature ladder as in marginalize(); burn-in
     and the gaps between samples run through model.tempering_run(sweeps, exchange_every), the grouping and every sample take
     the chains on rung 0.  `mode_of_chain` with `reassign` is a ValueError: the anchors come from a grouping.
-    `sampler`: "mh" or "heatbath", as in marginalize().
+    `sampler`: "mh" or "heatbath", as in marginalize().  `trace`: a depth, as in marginalize() -- one model.trace_record() after
+    every sample; the dict does not change.
     Chains spread over ranks (`shard`, or model.shard, with world_size > 1) raise ValueError: pooling modes across ranks is
     not done here."""
     if (threshold is None) == (mode_of_chain is None):
@@ -230,10 +238,13 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         model.marginals_set_mode_anchors(anchors, threshold)
     else:
         model.marginals_set_modes(moc, n_modes)
+    _trace_start(model, trace)
     for _ in range(int(n_samples)):
         if sampling_frequency_sweeps > 0:
             advance(sampling_frequency_sweeps)
         model.marginals_accumulate(None)
+        if trace:
+            model.trace_record()
     state = model.marginals_modes()
     labels = np.zeros((n_modes, model.n), dtype=np.uint32)
     top = np.zeros((n_modes, model.n), dtype=np.uint32)
@@ -253,6 +264,16 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         moved = int(sum(_co_members(modes, c) != _co_members(after, c) for c in range(len(modes["chains"]))))
     return {"modes": modes, "labels": labels, "top": top, "counts": counts, "terms": state["terms"], "weights": state["weights"],
             "ref_chain": state["ref_chain"], "moved": moved}
+
+
+def _trace_start(model, trace):
+    """trace=depth of marginalize() / marginalize_modes(): the ring set and everything forgotten before the first sample."""
+    if trace is None or int(trace) == 0:
+        return
+    if int(trace) < 0:
+        raise ValueError("trace must be a depth >= 0")
+    model.trace_set(int(trace))
+    model.trace_reset()
 
 
 def _advance(model, tempering, exchange_every, sampler, reshuffles=0, reshuffle_scans=3):

@@ -29,7 +29,7 @@ extern "C" {
  *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
  *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*), population annealing
  *    (bisbm_population_*), node conditionals (bisbm_conditionals_*), heat-bath sweeps and greedy polishing
- *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp).  Additions only. */
+ *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp), chain traces (bisbm_trace_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -796,6 +796,69 @@ int bisbm_marginals_set_mode_anchors(bisbm_handle h, uint32_t n_modes, const uin
 int bisbm_marginals_get_mode_assignment(bisbm_handle h, double *vi_out /* n_chains * n_modes */,
                                         uint64_t *visits_out /* n_chains * n_modes */, uint64_t *unassigned_out,
                                         uint64_t *samples_out);
+
+/* Chain traces (no reference counterpart: the reference keeps no history).  Every other analysis here compares chains with each
+ * other or with a reference; this one compares a chain with its own past.  How many sweeps until the partition has forgotten
+ * where it was, how many independent samples did a run give, do the chains agree on the description length: every chain keeps a
+ * ring of snapshots of its own partition on the device, a record computes the label-invariant distance between now and every
+ * held lag and appends to the description-length series, and a small host routine gives integrated autocorrelation times and
+ * split-R-hat.
+ *
+ * set: every device of the handle allocates a ring of `depth` snapshots of its own chains' label rows: depth x chains of the
+ *   device x label stride (n rounded up to 256) bytes on the device, and 8 bytes per (slot, chain) on the host for the cached
+ *   size sum.  depth = 0 frees everything.  depth > 1024: BISBM_ERR_INVALID_ARG.  A failed allocation is BISBM_ERR_HIP with the
+ *   size in the message; nothing is capped or subsampled.  Calling it again replaces the ring and forgets everything.
+ *   BISBM_ERR_UNSUPPORTED while the handle holds two-byte labels.
+ * record: one record for every chain c of the handle (with replica exchange on, every chain whatever its rung):
+ *   1. S_c is the double bisbm_entropy returns; H_c = ln n - A_c / n with A_c = sum_r a_r ln a_r exactly as
+ *      bisbm_partition_distances' h_out computes it (the same kernel: H is bit-equal to that h_out).  Both are appended to
+ *      host-side series, 16 bytes per (record, chain).
+ *   2. For every held age a = 1 ... min(depth, records so far) there is a snapshot b' of chain c taken a records ago.  The
+ *      contingency table of (labels now, b') is counted in the layout of the partition distances (type a at r * ka + s, type b
+ *      at ka * ka + r * kb + s), S_nn = sum n_rs ln n_rs is added by one wavefront in the order described there, and
+ *        VI_c(a) = ((A_now + A_then) - 2 S_nn) / n   (a negative rounding result is returned as 0.0),
+ *      with A_then the value cached when the snapshot was "now"; agree_c(a) = sum_r n_rr, an integer, is the number of nodes
+ *      whose label is unchanged.  VI_c(a) is bit-equal to what bisbm_partition_distances_to returns for chain c against that
+ *      snapshot passed as a reference of the chain's own shape.
+ *   3. vi_sum[c][a-1] += VI_c(a) (one f64 add per record), agree_sum[c][a-1] += agree_c(a) (uint64), vi_last[c][a-1] = VI_c(a)
+ *      (NaN for ages not yet held), pairs[a-1] += 1.
+ *   4. The current rows and A_now overwrite the oldest slot (a device-to-device copy on the device's stream); records += 1.
+ *   Chain state, random streams, running sums and every other analysis sum are only read.  Several devices: each device records
+ *   its own chains, the results are laid out in handle chain order and equal one device with all the chains bit for bit.
+ *   Served: both RNG modes (labels and bisbm_entropy only), chains grouped by shape.  BISBM_ERR_UNSUPPORTED: two-byte labels.
+ *   BISBM_ERR_STATE: before bisbm_init / bisbm_shuffle, without a ring, and ("bisbm_trace_reset first") when a chain's (ka, kb)
+ *   differs from what its held snapshots were taken with, as after a merge or split.  A slot overwritten by
+ *   bisbm_population_resample is simply compared with the previous occupant's snapshots: callers reset after a resampling step
+ *   (the genealogy is not followed).  Lags are contiguous: the caller spaces records by calling every k sweeps.
+ *   A workgroup counts one chain against a tile of up to 4 ages, one table per age in LDS.  Device scratch of a record with C
+ *   chains on the device, the largest shape kaM + kbM: 16 C bytes of descriptors, 8 C + 16 C ages bytes of sums, and -- only
+ *   when the (chain, age tile) workgroups are too few to fill the device, or a table does not fit the LDS -- integer tables of
+ *   4 (kaM^2 + kbM^2) bytes per (chain, age) for as many as fit 256 MiB (at least one tile), run in as many launches as that
+ *   takes.  BISBM_PARTITION_REGIME=fused|split forces either form as for the partition distances; both give the same bits.
+ * reset: forgets snapshots, sums and series, keeps depth.
+ * get_lags: vi_sum, agree_sum, vi_last [n_chains * depth] (row = chain), pairs [depth], records (a scalar); any pointer may be
+ *   NULL.  get_series: what = BISBM_TRACE_S or BISBM_TRACE_H, out [records * n_chains], record-major.  Both BISBM_ERR_STATE
+ *   without a ring.
+ * summary: a pure host function, needs no device.  x[t * C + c], T >= 4 records of C >= 1 chains, a finite window > 0 (callers
+ *   pass 5.0: Sokal's convention, not a measurement).  Everything in f64, sums added one term at a time in ascending index, no
+ *   fused multiply-add.  Per chain: mu = (sum_t x_t) / T; d_t = x_t - mu; gamma(k) = (sum_{t=0}^{T-1-k} d_t d_{t+k}) / T.  If
+ *   gamma(0) == 0.0 the chain never moved: tau = +inf, window_out = 0.  Otherwise acc = 1.0 and for k = 1 ... floor(T/2):
+ *   acc = acc + 2.0 (gamma(k) / gamma(0)), M = k, stop at the first k with (double)k >= window * acc; tau = acc, window_out = M
+ *   (M == floor(T/2): the series was too short).  Split-R-hat with h = floor(T/2): the 2C sequences x[0:h, c] for c ascending,
+ *   then x[T-h:T, c]; each has its mean m_j and its variance v_j (denominator h - 1); W = (sum v_j) / (2C),
+ *   mbar = (sum m_j) / (2C), Bn = (sum (m_j - mbar)^2) / (2C - 1); rhat = sqrt((((double)(h-1) / (double)h) W + Bn) / W), NaN when
+ *   W == 0.  tau_out [C], window_out [C], rhat_out (a scalar); each may be NULL.  BISBM_ERR_INVALID_ARG: T < 4, C = 0, a
+ *   non-finite x, a window that is not finite and > 0. */
+#define BISBM_TRACE_S 0 /* the description length (bisbm_entropy) */
+#define BISBM_TRACE_H 1 /* the partition entropy */
+int bisbm_trace_set(bisbm_handle h, uint32_t depth);
+int bisbm_trace_record(bisbm_handle h);
+int bisbm_trace_reset(bisbm_handle h);
+int bisbm_trace_get_lags(bisbm_handle h, double *vi_sum, uint64_t *agree_sum, double *vi_last /* n_chains * depth each */,
+                         uint64_t *pairs /* depth */, uint64_t *records);
+int bisbm_trace_get_series(bisbm_handle h, int what, double *out /* records * n_chains */);
+int bisbm_trace_summary(uint64_t T, uint32_t C, const double *x /* T * C */, double window, double *tau_out /* C */,
+                        uint32_t *window_out /* C */, double *rhat_out);
 
 /* blockmodel_t::agg_merge(engine, diff_a, diff_b, nm) (blockmodel.hh, blockmodel.cc:109-206; call sites
  * mcmc_main.cc:385,429,434,446): merge diff_a type-a and diff_b type-b blocks in every chain -- nm proposals per
