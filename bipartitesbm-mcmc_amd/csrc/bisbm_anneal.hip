@@ -281,6 +281,11 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
                 depth = pd[0] == '2' ? 1u : pd[0] == '4' ? std::min(2u, max_depth) : pd[0] == '8' ? max_depth : depth;
         }
         p.pass_depth = depth;
+        // The four-steps pass of 17..32 blocks exists twice (SweepParams::one_stage).  Which one pays depends on how many steps of
+        // a pass move; the accepted fraction of the launch before stands for it (kOneStageAccepted; no launch yet: the per-mover
+        // loop).  BISBM_ONE_STAGE=0 / 1 pins it (A/B runs, tests).
+        p.one_stage = h->last_acc_frac >= kOneStageAccepted ? 1u : 0u;
+        if (const char* os = getenv("BISBM_ONE_STAGE")) p.one_stage = os[0] == '1' ? 1u : 0u;
         {  // (what launch_sweep_fast picks from these numbers)
             const uint32_t d = std::min(p.pair_steps, p.pass_depth);
             const bool cold = schedule == SCHED_CONSTANT && kwargs[0] == 0.f;  // T = 0 throughout: general steps only
@@ -315,6 +320,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
             uint64_t acc_now = 0;
             for (uint32_t c = 0; c < h->n_chains; ++c) acc_now += sc[c].last_accepted;
             const double acc_frac = (double)acc_now / (double)upd;
+            h->last_acc_frac = acc_frac;
             const double before[3] = {h->passes.figure(1), h->passes.figure(2), h->passes.figure(3)};
             const uint32_t incumbent = h->passes.current();
             h->passes.record(depth, speed, acc_frac);

@@ -441,6 +441,7 @@ struct bisbm_engine {
     // which depth of pass (two / four / eight steps) the next production launch runs: chosen from the timed launches so far
     // (bisbm_pass_policy.hpp); belongs to a partition: init / shuffle / merges / splits reset it
     bisbm::PassDepthPolicy passes;
+    double last_acc_frac = -1.;  // accepted fraction of the last timed sweep launch (-1: none yet): picks SweepParams::one_stage
     // Chains with different block counts (after a one-argument agg_merge, blockmodel.cc:208-271: every run ends where it
     // ends).  Kernels are launched for one (KA, KB), so the handle then becomes a CONTAINER: its chains live in
     // sub-engines, one per distinct shape (`groups`), which borrow the graph and the tables from it (`root`); chain c of
@@ -516,7 +517,10 @@ inline void philox_host(uint64_t seed, uint32_t chain, uint32_t purpose, uint64_
     out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
 }
 inline double u53_host(uint32_t hi, uint32_t lo) { return (double)((((uint64_t)hi << 32) | lo) >> 11) * 0x1.0p-53; }
-inline void forget_pass_speeds(bisbm_engine* h) { h->passes.reset(); }
+inline void forget_pass_speeds(bisbm_engine* h) {
+    h->passes.reset();
+    h->last_acc_frac = -1.;
+}
 int rebuild_state(bisbm_engine* h);
 // block-state part of entropy() of every chain into d_out (n_chains doubles on the device), on the handle's stream, no sync
 int launch_block_entropy(bisbm_engine* h, double* d_out);

@@ -92,6 +92,11 @@ struct SweepParams {
     // depth of this launch's passes where the block counts allow a choice (1 / 2 / 3 = two / four / eight steps per pass): the
     // host sets it from the measured speed of the launches before (bisbm_anneal)
     uint32_t pass_depth;
+    // production kernel, four steps per pass with 17..32 blocks of a type: 1 = the launch updates its register copies of m_r / n_r
+    // in one stage per pass (words prepared ahead of the verdicts: faster where two or more steps of a pass move), 0 = one mover
+    // at a time (faster where a pass has one mover or none).  The host sets it from the accepted fraction of the launch before
+    // (bisbm_anneal); the chain is the same chain either way.
+    uint32_t one_stage;
     // wide mode (KA + KB > 256; generic kernel only): `labels` holds two-byte labels (label_stride counts labels, not
     // bytes), and the a x b quadrant of m is read and updated in HBM
     uint32_t wide;
@@ -103,6 +108,11 @@ struct SweepParams {
     // float, like kw0: a chain at T runs exactly as a constant-schedule launch at kwargs {T, .}); NULL otherwise
     const float* T_chain;
 };
+// Accepted fraction of the launch before from which a four-steps launch of 17..32 blocks takes the one-stage kernel
+// (SweepParams::one_stage).  Measured at 32 + 32 blocks (profiles/EXPERIMENTS.md, round 7): the one stage wins by 3.9 % where 0.72
+// to 0.82 of the steps are accepted (randomised start: two to three movers per pass) and loses 1.6 % at 0.65 (chains on the planted
+// partition: most accepted steps are r == s, a pass has one mover or none).  Between the two nothing is measured: the per-mover loop runs.
+constexpr double kOneStageAccepted = 0.7;
 constexpr uint32_t kSimdClaims = 1u << 14;  // index: XCC_ID[3:0] | HW_ID se, sh, cu [15:8] | simd [5:4]
 
 struct BuildParams {

@@ -41,6 +41,7 @@
 // No generic pointers (flat loads wait on vmcnt AND lgkmcnt), no workgroup barriers on the step path.
 // Diagnostic hooks (BISBM_STAMPS, BISBM_ABLATE) are compiled out of the product build.
 #include "bisbm_kernels.hpp"
+#include "bisbm_move_word.hpp"
 #include "bisbm_stand_rule.hpp"
 
 #include <algorithm>
@@ -105,6 +106,18 @@ __device__ __forceinline__ uint32_t smin(uint32_t x, uint32_t y) {
     __asm__("s_min_u32 %0, %1, %2" : "=s"(r) : "s"(x), "s"(y) : "scc");
     return r;
 }
+
+// the cross-lane moves of combine_move_words (bisbm_move_word.hpp) as the instructions themselves
+struct LaneSwaps {
+    __device__ __forceinline__ void swap16(int a, int b, int& x, int& y) const {
+        const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+        x = (int)r[0], y = (int)r[1];
+    }
+    __device__ __forceinline__ void swap32(int a, int b, int& x, int& y) const {
+        const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+        x = (int)r[0], y = (int)r[1];
+    }
+};
 
 // The stand rule's column test -- target_margin / target_moves of the two-steps passes, margin_up / margin_down /
 // column_clash of the deeper ones -- is bisbm_stand_rule.hpp: the text a CPU program checks is the text the kernel runs.
@@ -218,9 +231,10 @@ __device__ __forceinline__ void commit_four(uint32_t nst, uint32_t clash_bits, u
 // lies outside take the general path, which reads and writes those entries in HBM.  CT: constant schedule.  K32: both block counts <= 32 (five-level scans and sums).  K16 (with K32): both
 // block counts <= 16: four steps per pass in the four 16-lane rows of the wave (step_quad).  K8 (with K16): both <= 8: eight
 // steps per pass in groups of eight lanes (step_oct).  Q32 (with K32, without K16): four steps per pass with up to 32 blocks
-// of a type, two blocks per lane (step_quad32) -- the kernel of a launch whose pass depth the host set to four.
-template <bool EL, bool CT, bool K32, bool K16, bool K8, bool Q32>
-__global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p) {
+// of a type, two blocks per lane (step_quad32) -- the kernel of a launch whose pass depth the host set to four.  OS (with Q32):
+// step_quad32 updates the register copies of m_r / n_r in one stage per pass, not one mover at a time (sweep_quad32_one_stage_kernel).
+template <bool EL, bool CT, bool K32, bool K16, bool K8, bool Q32, bool OS>
+__device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
     extern __shared__ __align__(16) uint32_t lds32[];
     const uint32_t chain = blockIdx.x;
     if (chain >= p.n_chains) return;
@@ -1221,8 +1235,17 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                 // apply_mcmc_moves, blockmodel.cc:461-503, for the steps of a pass of `width` steps that move (bits of `moved`; their
                 // rows of m differ); selfok: committed steps that are an accepted r == s.  The lane's step is qs, group grp_l of
                 // 64 / width lanes; ee: the lane's eta entry; write_mq(movers): the pass's writes of rows r and s of m (one or two leaves per lane).
+                // The register copies of m_r / n_r: one mover at a time (a scalar branch, three v_readlane and ~10 vector instructions per
+                // mover, all behind the verdicts), or -- `combined`, step_quad32 of the one-stage kernels -- in one stage: zw_lo, zw_hi are what the lane's step
+                // would add to m_r / n_r (move_word, bisbm_move_word.hpp) of the blocks that rows 0 / 2 and rows 1 / 3 of the wave hold
+                // in this lane's column (l16 and l16 + 16), formed in the shadow of the table gathers; the movers' words are combined
+                // across the rows by two swaps (the movers' block sets are disjoint: at most one word per block is non-zero).  From a
+                // randomised start, where two or three steps of a pass move, the one stage is the faster; where passes have one mover
+                // or none (near the mode; the workloads on which step_quad and step_oct are chosen) the loop is, so the host picks the kernel
+                // launch by launch (SweepParams::one_stage; profiles/EXPERIMENTS.md, round 7).
                 auto apply_moves = [&](auto tm, auto width, uint32_t q, uint32_t qs, uint32_t grp_l, uint32_t moved, uint32_t selfok, uint32_t r_loc,
-                                       uint32_t s_loc, uint32_t deg, double dS, uint32_t e_idx, int ee, auto&& write_mq) {
+                                       uint32_t s_loc, uint32_t deg, auto combined, int zw_lo, int zw_hi, double dS, uint32_t e_idx, int ee,
+                                       auto&& write_mq) {
                     constexpr bool TM = decltype(tm)::value;
                     constexpr uint32_t W = decltype(width)::value, L = 64u / W;  // lanes per step
                     constexpr unsigned long long kFirst = W == 4u ? 0x0001000100010001ull : 0x0101010101010101ull;  // lane 0 of every group
@@ -1234,18 +1257,29 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & (kFirst * 0x30ull)))  // lanes 4, 5 of a group: eta_r - 1, eta_s + 1
                             eta_l[e_idx] = (uint32_t)(ee + ((int)(lb & 1u) * 2 - 1));
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & kFirst)) new_lab[qs] = (uint8_t)(own_base + s_loc);
-                        // the register copies of m_r / n_r, sum dS (:500) and the early-stop bookkeeping, in step order
+                        if constexpr (decltype(combined)::value) {
+                            static_assert(W == 4u, "rows of 16 lanes");
+                            const bool mover_lane = __builtin_amdgcn_inverse_ballot_w64(movers);
+                            const int z = combine_move_words(mover_lane ? zw_lo : 0, mover_lane ? zw_hi : 0, LaneSwaps{});
+                            mr_own += move_word_dm(z);
+                            nr_own += move_word_dn(z);
+                        }
+                        // (one mover at a time;) sum dS (:500) and the early-stop bookkeeping, in step order
+                        if constexpr (TM || !decltype(combined)::value) {
 #pragma unroll
-                        for (uint32_t g = 0; g < W; ++g) {
-                            if ((moved >> g) & 1u) {
-                                const uint32_t rg = readlane(r_loc, L * g), sg = readlane(s_loc, L * g), dg = readlane(deg, L * g);
-                                const int dl = (int)min(lb ^ rg, 1u) - (int)min(lb ^ sg, 1u);  // +1 on lane s, -1 on lane r
-                                mr_own += __mul24((int)dg, dl);
-                                nr_own += dl;
-                                if constexpr (TM) cum_l0 += readlane(dS, L * g + L - 1u);
-                                if constexpr (TM) new_minimum(q + g);
-                            } else if (TM && ((selfok >> g) & 1u)) {
-                                new_minimum(q + g);  // an accepted r == s step (see new_minimum)
+                            for (uint32_t g = 0; g < W; ++g) {
+                                if ((moved >> g) & 1u) {
+                                    if constexpr (!decltype(combined)::value) {
+                                        const uint32_t rg = readlane(r_loc, L * g), sg = readlane(s_loc, L * g), dg = readlane(deg, L * g);
+                                        const int dl = (int)min(lb ^ rg, 1u) - (int)min(lb ^ sg, 1u);  // +1 on lane s, -1 on lane r
+                                        mr_own += __mul24((int)dg, dl);
+                                        nr_own += dl;
+                                    }
+                                    if constexpr (TM) cum_l0 += readlane(dS, L * g + L - 1u);
+                                    if constexpr (TM) new_minimum(q + g);
+                                } else if (TM && ((selfok >> g) & 1u)) {
+                                    new_minimum(q + g);  // an accepted r == s step (see new_minimum)
+                                }
                             }
                         }
                         wfence();
@@ -1606,7 +1640,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
 #ifdef BISBM_PASS_COUNTS
                     count_pairs((lane >> 2) & 3u, lane & 3u, lane < 16u, moved, commit, nst);
 #endif
-                    apply_moves(tm, Four{}, q, qs, row, moved, commit & selfok4, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
+                    apply_moves(tm, Four{}, q, qs, row, moved, commit & selfok4, r_loc, s_loc, deg, std::false_type{}, 0, 0, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {
                             mq[a_rt] = m_rt_raw - k;
                             mq[t.a_st] = t.m_st_raw + k;
@@ -1692,6 +1726,13 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
                             const uint32_t k_hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk1);
                             return k_lo ^ ((k_lo ^ k_hi) & (0u - (t_j >> 4)));
                         }) & 0xffffu;
+                    // (what the row's step adds to m_r / n_r of the two blocks of the lane's column if it moves: rows 0 / 2 hold block
+                    // l16 of the register copies, rows 1 / 3 block l16 + 16 -- worked out in the gathers' shadow and pinned there)
+                    int zw_lo = 0, zw_hi = 0;
+                    if constexpr (OS) {
+                        zw_lo = move_word(r_loc, s_loc, deg, l16), zw_hi = move_word(r_loc, s_loc, deg, l16 + 16u);
+                        __asm__ volatile("" : "+v"(zw_lo), "+v"(zw_hi));
+                    }
                     double d0 = (L1_0 + t.L2_0) - (L3_0 + t.L4_0);
                     d0 = d0 + t.tail_lg * sign_tail;  // the scalar terms sit in leaves 0..7 / 0..3: the lane's lower leaf
                     d0 = d0 + lq * sign_q;
@@ -1704,7 +1745,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
 #ifdef BISBM_PASS_COUNTS
                     count_pairs((lane >> 2) & 3u, lane & 3u, lane < 16u, moved, commit, nst);
 #endif
-                    apply_moves(tm, Four{}, q, qs, row, moved, commit & selfok4, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
+                    apply_moves(tm, Four{}, q, qs, row, moved, commit & selfok4, r_loc, s_loc, deg, std::bool_constant<OS>{}, zw_lo, zw_hi, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth32_lo)) {
                             mq[a_rt0] = m_rt_raw0 - k0;
                             mq[t.a_st0] = t.m_st_raw0 + k0;
@@ -1792,7 +1833,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
 #ifdef BISBM_PASS_COUNTS
                     count_pairs(lane & 7u, lane >> 3, true, moved, commit, nst);
 #endif
-                    apply_moves(tm, Eight{}, q, qs, grp, moved, commit & selfok8, r_loc, s_loc, deg, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
+                    apply_moves(tm, Eight{}, q, qs, grp, moved, commit & selfok8, r_loc, s_loc, deg, std::false_type{}, 0, 0, dS, t.e_idx, t.ee, [&](unsigned long long movers) {
                         if (__builtin_amdgcn_inverse_ballot_w64(movers & lanes_koth)) {
                             mq[a_rt] = m_rt_raw - k;
                             mq[t.a_st] = t.m_st_raw + k;
@@ -1945,13 +1986,27 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p)
     }
 }
 
+// The kernels: one per kind of pass, and the four-steps pass of 17..32 blocks a second time with the one-stage update of m_r / n_r
+// (OS; a kernel of its own name, chosen per launch by SweepParams::one_stage).
+template <bool EL, bool CT, bool K32, bool K16, bool K8, bool Q32>
+__global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_kernel(SweepParams p) {
+    sweep_fast_body<EL, CT, K32, K16, K8, Q32, false>(p);
+}
+template <bool EL, bool CT>
+__global__ __launch_bounds__(2 * kWave, 2) void sweep_quad32_one_stage_kernel(SweepParams p) {
+    sweep_fast_body<EL, CT, true, false, false, true, true>(p);
+}
+
+template <class Kernel>
+static hipError_t launch_fast_kernel(Kernel kernel, const SweepParams& p, size_t lds_bytes, hipStream_t stream) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(p.n_chains), dim3(2 * kWave), lds_bytes, stream, p);
+    return hipGetLastError();
+}
 template <bool EL, bool CT, bool K32, bool K16, bool K8, bool Q32 = false>
 static hipError_t launch_fast_variant3(const SweepParams& p, size_t lds_bytes, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)sweep_fast_kernel<EL, CT, K32, K16, K8, Q32>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((sweep_fast_kernel<EL, CT, K32, K16, K8, Q32>), dim3(p.n_chains), dim3(2 * kWave), lds_bytes, stream, p);
-    return hipGetLastError();
+    return launch_fast_kernel(sweep_fast_kernel<EL, CT, K32, K16, K8, Q32>, p, lds_bytes, stream);
 }
 
 // One kernel per kind of pass (a kernel that held all of them ran out of registers): p.pass_depth, set by the host, says
@@ -1961,12 +2016,14 @@ hipError_t launch_fast_variant(const SweepParams& p, size_t lds_bytes, hipStream
     const uint32_t depth = p.pair_steps < p.pass_depth ? p.pair_steps : p.pass_depth;  // 0 / 1 / 2 / 3: one, two, four, eight steps per pass
     if (p.ka <= 8u && p.kb <= 8u && depth >= 3u) return launch_fast_variant3<EL, CT, true, true, true>(p, lds_bytes, stream);
     if (p.ka <= 16u && p.kb <= 16u && depth >= 2u) return launch_fast_variant3<EL, CT, true, true, false>(p, lds_bytes, stream);
-    if (p.ka <= 32u && p.kb <= 32u && depth >= 2u) return launch_fast_variant3<EL, CT, true, false, false, true>(p, lds_bytes, stream);
+    if (p.ka <= 32u && p.kb <= 32u && depth >= 2u)
+        return p.one_stage != 0u ? launch_fast_kernel(sweep_quad32_one_stage_kernel<EL, CT>, p, lds_bytes, stream)
+                                 : launch_fast_variant3<EL, CT, true, false, false, true>(p, lds_bytes, stream);
     return (p.ka <= 32u && p.kb <= 32u) ? launch_fast_variant3<EL, CT, true, false, false>(p, lds_bytes, stream)
                                         : launch_fast_variant3<EL, CT, false, false, false>(p, lds_bytes, stream);
 }
 
-// The 20 variants compile side by side: the build (build.py) compiles this file once per BISBM_FAST_PART = 0 .. 3 -- the five
+// The 20 + 4 kernels compile side by side: the build (build.py) compiles this file once per BISBM_FAST_PART = 0 .. 3 -- the six
 // kernels of one (EL, CT) each -- and once with BISBM_FAST_PART = 4 for the dispatch below; undefined: everything in one unit
 // (diagnostic builds with in-kernel stamps, whose counters are one device symbol).
 #ifndef BISBM_FAST_PART
