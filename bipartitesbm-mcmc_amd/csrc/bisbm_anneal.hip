@@ -186,6 +186,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
         const char* single = getenv("BISBM_SINGLE_STEPS");  // =1: one step per pass in every variant (A/B checks, tests)
         p.pair_steps = !single ? 3u : single[0] == '1' ? 0u : single[0] == '2' ? 1u : single[0] == '4' ? 2u : 3u;  // =2 / =4: at most two / four per pass
     }
+    p.predict_skew = predict_skew_from_env(getenv("BISBM_PREDICT_SKEW"));  // =n: every n-th step of a chunk gets a wrong predicted target (tests)
     if (fast) {
         const char* fixed = getenv("BISBM_FIXED_ROLES");  // =1: wave 0 always steps, =2: wave 1 (A/B checks, tests)
         if (fixed && fixed[0] == '2') p.fixed_stepping_wave = 1;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bisbm_device.hpp"
+#include "bisbm_predict_skew.hpp"
 
 struct bisbm_reshuffle_record;  // include/bisbm.h
 
@@ -107,6 +108,10 @@ struct SweepParams {
     // replica exchange (bisbm_tempering.hip), schedule SCHED_PER_CHAIN: the constant temperature of every chain of the launch (a
     // float, like kw0: a chain at T runs exactly as a constant-schedule launch at kwargs {T, .}); NULL otherwise
     const float* T_chain;
+    // production kernel, tests only (BISBM_PREDICT_SKEW = n; 0: off): the feeder hands every n-th step of a chunk -- index n - 1
+    // modulo n -- a WRONG predicted target, (prediction + 1) mod k_own, so that the passes that start from a predicted target
+    // take their miss paths at a known rate (bisbm_predict_skew.hpp).  The chain is the same chain whatever the prediction says.
+    uint32_t predict_skew;
 };
 // Accepted fraction of the launch before from which a four-steps launch of 17..32 blocks takes the one-stage kernel
 // (SweepParams::one_stage).  Measured at 32 + 32 blocks (profiles/EXPERIMENTS.md, round 7): the one stage wins by 3.9 % where 0.72

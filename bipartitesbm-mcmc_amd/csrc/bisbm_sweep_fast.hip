@@ -23,8 +23,9 @@
 // a chunk's preparation (several dependent HBM round trips) is thereby off the step path entirely.  Which wave
 // steps is settled at kernel start so that no SIMD of the chip hosts the stepping waves of two chains.
 // The feeder also PREDICTS each step's inverse-CDF target from the block matrix as it stands a chunk ahead (round 4):
-// the two-steps passes issue everything that depends on the target with their first reads and check the prediction
-// against their own scan before anything is written (prepare, step_pair, step_pair64).
+// the two-steps passes and the four-steps pass of the one-stage kernels issue everything that depends on the target with
+// their first reads and check the prediction against their own scan before anything is written (prepare, step_pair,
+// step_pair64, step_quad32); a test can bend the prediction (BISBM_PREDICT_SKEW) and must see the same chain.
 // State on chip: the a x b quadrant of m (odd row stride: rows and columns conflict-free) and eta in
 // LDS; m_r / n_r in registers (lane i <-> block i of each type).  dS and the Hastings sums are DPP
 // butterflies; the four log_q values are one SIMT evaluation; the four uniforms of a step come from one
@@ -131,8 +132,11 @@ struct LaneSwaps {
 // in line to be committed (every step before it stands):
 //   8 a shared block, 9 / 10 a column candidate (target strictly between r_i and s_i, k > 0, no shared block) kept / refused,
 //   11 / 12 the same at the boundary ((D - 1) k == margin / (D - 1) k == margin + 1)
+// The four-steps pass that reads on predicted targets (step_quad32 of the one-stage kernels):
+//   13 passes whose first step's target was not the predicted one (the general step takes it; such a pass counts under 0 with no
+//   step under 1), 14 passes cut short by a later step's
 #ifdef BISBM_PASS_COUNTS
-constexpr int kPassCounts = 13;
+constexpr int kPassCounts = 15;
 __device__ unsigned long long g_pass_counts[kPassCounts];
 #define PCOUNT(i, v) (pc_acc[i] += (v))
 #define PASS_COUNTS_PAIR(paired)                                                          \
@@ -248,8 +252,9 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
     }
     const uint32_t ka = p.ka, kb = p.kb, K = ka + kb, na = p.na, nb = p.nb;
     const uint32_t D = p.maxdeg + 1, S = kb | 1u;
-    // the two-steps passes (step_pair, step_pair64) start from a predicted inverse-CDF target (see prepare and step_pair)
-    constexpr bool kPredictTarget = !K16 && !Q32 && (BISBM_PREDICT_TARGET != 0);
+    // the two-steps passes (step_pair, step_pair64) and the four-steps pass of the one-stage kernels (step_quad32 with OS) start
+    // from a predicted inverse-CDF target (see prepare, step_pair and step_quad32)
+    constexpr bool kPredictTarget = !K16 && (!Q32 || OS) && (BISBM_PREDICT_TARGET != 0);
     const uint32_t row_cap = p.maxdeg < kRowCap ? p.maxdeg : kRowCap;  // neighbours walked per row by the feeder
     // LDS layout, dword offsets
     const uint32_t o_mq = 0, o_eta = ka * S;
@@ -391,7 +396,7 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
     __asm__ volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
 #endif
 #ifdef BISBM_PASS_COUNTS
-    unsigned long long pc_acc[kPassCounts] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long pc_acc[kPassCounts] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
 
     for (uint64_t sweep = 0; sweep < all_sweeps; ++sweep) {
@@ -606,6 +611,9 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                         spred_l += cum <= x ? 1u : 0u;
                     }
                     spred_l = spred_l < k_own ? spred_l : k_own - 1u;
+                    // (tests: every p.predict_skew-th step of the chunk is handed the next block instead, bisbm_predict_skew.hpp)
+                    const uint32_t skew = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.predict_skew);
+                    if (__builtin_expect(skew != 0u, 0)) spred_l = skewed_prediction(spred_l, lane, skew, k_own);
                 }
                 // degree (<= 255 in the hot step), own block, pivot block and predicted target in one word (one cross-lane move per pass)
                 hand[6 * kWave + lane] = (deg_l & 255u) | ((rloc_l & 63u) << 8) | (tloc_l << 16) | (spred_l << 24);
@@ -1300,6 +1308,9 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                             const uint32_t done = pass(tm, q, nst);
                             PCOUNT(0, 1u);
                             PCOUNT(1, done);
+                            if constexpr (Q32 && OS && kPredictTarget) {  // (0: the predicted target of step q was not its target -- the general path takes it, see step_quad32)
+                                if (__builtin_expect(done == 0u, 0)) gen_mask |= 1ull << q;
+                            }
                             q += done;
                         }
                     }
@@ -1673,6 +1684,16 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     const uint32_t kk0 = (uint32_t)k0, kk1 = (uint32_t)k1;
                     const double L1_0 = tab_at(tab.lg, (uint32_t)(m_rt0 + 1)), L3_0 = tab_at(tab.lg, (uint32_t)(m_rt0 + 1) - kk0);
                     const double L1_1 = tab_at(tab.lg, (uint32_t)(m_rt1 + 1)), L3_1 = tab_at(tab.lg, (uint32_t)(m_rt1 + 1) - kk1);
+                    // The one-stage kernels (kPredictTarget): what depends on the row's target s is read on the feeder's PREDICTION
+                    // (bits 24.. of the packed word, see step_pair) -- row s of m, eta, m_r / n_r and the ten table gathers behind them
+                    // go out here, with the row-r gathers, and the scans, the votes and the exit test below run in their shadow.
+                    // The prediction decides only WHEN these reads are issued: the state is the one the pass starts from either
+                    // way (nothing is written before apply_moves), and a row whose scan finds another target is not committed.
+                    TargetReads2 t;
+                    if constexpr (OS && kPredictTarget) {
+                        target_lds2(t, pack >> 24, r_loc, deg, kmask0, kmask1, l16, 16u);
+                        target_gathers2(t, kk0, kk1, std::true_type{});
+                    }
                     __asm__ volatile("" ::: "memory");
                     // inverse CDF per row over 32 own blocks (:627-628): the scan of blocks 0..15, its total, the scan of blocks
                     // 16..31 on top (garbage past k_own, see step_pair64)
@@ -1687,6 +1708,22 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     const unsigned long long hit1 = __builtin_amdgcn_ballot_w64((uint32_t)scan1 > prop);
                     const uint32_t field = ((uint32_t)(hit0 >> (row << 4)) & 0xffffu) | ((uint32_t)(hit1 >> (row << 4)) << 16);
                     const uint32_t s_loc = min((uint32_t)__builtin_ctz(field | 0x80000000u), last_own);
+                    if constexpr (OS && kPredictTarget) {
+                        // The first row whose target is not the predicted one, among the steps that exist: it has read a wrong
+                        // (in-range) block, so it and the rows behind it are ignored from here on -- the pass goes on with the steps
+                        // in front of it, and that step opens the next pass.  The first row itself: nothing has been written, the
+                        // caller sends step q down the general path (as step_pair64 does; a second copy of the reads costs
+                        // registers this variant does not have).  (s_ff1 of no bit is -1: the minimum leaves nst alone)
+                        const unsigned long long wrong =
+                            __builtin_amdgcn_ballot_w64(s_loc != (pack >> 24)) & kRowRep & (nst >= 4u ? ~0ull : ((1ull << (16u * nst)) - 1ull));
+                        uint32_t first_wrong;
+                        __asm__("s_ff1_i32_b64 %0, %1" : "=s"(first_wrong) : "s"(wrong));
+                        const uint32_t nst_ok = smin(nst, first_wrong >> 4);
+                        PCOUNT(13, nst_ok == 0u ? 1u : 0u);
+                        PCOUNT(14, (nst_ok != 0u && nst_ok < nst) ? 1u : 0u);
+                        if (__builtin_expect(nst_ok == 0u, 0)) return 0u;
+                        nst = nst_ok;
+                    }
                     // (masks combined on the scalar side: one compare per ballot, no boolean round trips through the vector unit)
                     const unsigned long long m_valid = nst >= 4u ? ~0ull : ((1ull << (16u * nst)) - 1ull);  // lanes of the steps that exist
                     const unsigned long long m_live = __builtin_amdgcn_ballot_w64(nn_r != 1);  // (:467-471: a block is never emptied)
@@ -1695,15 +1732,18 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     const unsigned long long m_warm = CT ? ~0ull : ~__builtin_amdgcn_ballot_w64(((zeroT_mask >> qs) & 1ull) != 0ull);
                     const unsigned long long b_can = m_valid & m_live & ~m_self & kRowRep;
                     const unsigned long long b_selfok = m_valid & m_live & m_self & m_warm & kRowRep;
+                    // (the one-stage kernels without this exit -- its crossing and branch stand in front of nothing there, and at >= 0.7
+                    // accepted it is hardly ever taken: -0.44 % time, inside three times the spread, not kept; profiles/EXPERIMENTS.md, round 8)
                     if (b_can == 0ull) {  // every step of the pass is an r == s (or a vetoed one): nothing changes (:109-112)
                         acc_chunk += (uint32_t)__builtin_popcountll(b_selfok);
                         if constexpr (TM)
                             if (b_selfok != 0ull) new_minimum(q + ((uint32_t)__builtin_ctzll(b_selfok) >> 4));
                         return nst;
                     }
-                    TargetReads2 t;
-                    target_lds2(t, s_loc, r_loc, deg, kmask0, kmask1, l16, 16u);
-                    target_gathers2(t, kk0, kk1, std::true_type{});
+                    if constexpr (!(OS && kPredictTarget)) {
+                        target_lds2(t, s_loc, r_loc, deg, kmask0, kmask1, l16, 16u);
+                        target_gathers2(t, kk0, kk1, std::true_type{});
+                    }
                     // the step's margins on the leaf that holds the row's target (blocks 16.. are the upper leaf), in one register from
                     // here on: the two scans, the two column entries and the draw end here (the variant has no register to spare)
                     const uint32_t leaf_m = 0u - (s_loc >> 4);
@@ -2093,8 +2133,8 @@ hipError_t launch_sweep_fast(const SweepParams& p, size_t /*generic_lds_bytes*/,
         fprintf(stderr,
                 "[pass_counts] passes %llu steps %llu first_moves %llu shared_block %llu target_holds %llu target_moves %llu "
                 "holds_at_boundary %llu moves_at_boundary %llu deep_shared_block %llu deep_kept %llu deep_refused %llu "
-                "deep_kept_at_boundary %llu deep_refused_at_boundary %llu\n",
-                h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12]);
+                "deep_kept_at_boundary %llu deep_refused_at_boundary %llu first_step_mispredicted %llu cut_by_misprediction %llu\n",
+                h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11], h[12], h[13], h[14]);
         const unsigned long long z[kPassCounts] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pass_counts), z, sizeof(z));
     }
