@@ -68,6 +68,11 @@ _f64p = C.POINTER(C.c_double)
 _f32p = C.POINTER(C.c_float)
 
 
+class RoundRecipe(C.Structure):
+    """bisbm_round_recipe (include/bisbm.h, "Heat-bath sweeps and pair reshuffles inside replica exchange")"""
+    _fields_ = [("mh_sweeps", C.c_uint32), ("heatbath_sweeps", C.c_uint32), ("reshuffles", C.c_uint32), ("reshuffle_scans", C.c_uint32)]
+
+
 class ReshuffleRecord(C.Structure):
     """bisbm_reshuffle_record (include/bisbm.h, "Pair reshuffles")"""
     _fields_ = [("type", C.c_uint32), ("r", C.c_uint32), ("s", C.c_uint32), ("M", C.c_uint32),
@@ -118,6 +123,9 @@ ABI = {
     "bisbm_tempering_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, _f64p]),
     "bisbm_tempering_get": (C.c_int, [C.c_void_p, _u32p, _f32p]),
     "bisbm_tempering_stats": (C.c_int, [C.c_void_p, _u64p, _u64p, _u64p]),
+    "bisbm_tempering_run_rounds": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(RoundRecipe), C.c_int]),
+    "bisbm_tempering_rung_stats": (C.c_int, [C.c_void_p, _u64p]),
+    "bisbm_rounds_population_run": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, C.c_uint64, C.POINTER(RoundRecipe), _f64p, _u32p, _f64p]),
     "bisbm_population_offspring": (C.c_int, [C.c_uint32, _f64p, C.c_double, C.c_double, _u32p, _u32p, _f64p]),
     "bisbm_population_resample": (C.c_int, [C.c_void_p, C.c_double, C.c_double, _u32p, _f64p]),
     "bisbm_population_run": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, C.c_uint64, _f64p, _u32p, _f64p]),
@@ -671,6 +679,24 @@ class BlockModel:
         self._check(self._L.bisbm_tempering_stats(self._h, _p(att, _u64p), _p(acc, _u64p), C.byref(rounds)))
         return att, acc, rounds.value
 
+    def tempering_rounds(self, rounds, mh=1, heatbath=0, reshuffles=0, scans=3, exchange=True):
+        """`rounds` rounds of replica exchange with mixed moves: per round `mh` MH sweeps of every chain at its rung's
+        temperature T_c, then `heatbath` heat-bath sweeps and `reshuffles` pair reshuffles (`scans` launch scans each) at
+        beta_c = 1 / T_c, then one exchange round (exchange=False: none).  tempering_rung_stats() reports what each move did
+        on every rung."""
+        rec = round_recipe(mh, heatbath, reshuffles, scans)
+        if int(rounds) < 0:
+            raise ValueError("rounds must not be negative")
+        self._check(self._L.bisbm_tempering_run_rounds(self._h, int(rounds), C.byref(rec), 1 if exchange else 0))
+
+    def tempering_rung_stats(self):
+        """Per rung since set_tempering, uint64 [L] each: {"mh_steps", "mh_accepted", "heatbath_steps", "heatbath_moves",
+        "reshuffles", "reshuffles_accepted"} -- what the chains did while they held the rung."""
+        out = np.zeros(6 * max(self.tempering_L, 1), dtype=np.uint64)
+        self._check(self._L.bisbm_tempering_rung_stats(self._h, _p(out, _u64p)))
+        out = out.reshape(-1, 6)
+        return {name: out[:, i].copy() for i, name in enumerate(RUNG_STAT_COLUMNS)}
+
     # -- population annealing (include/bisbm.h, "Population annealing")
     def population_resample(self, beta_from, beta_to):
         """One resampling step of all chains from inverse temperature beta_from to beta_to >= beta_from: every dead slot takes
@@ -690,6 +716,21 @@ class BlockModel:
         rates = np.zeros(self.n_chains, dtype=np.float64)
         self._check(self._L.bisbm_population_run(self._h, len(T), _p(T, _f32p), int(sweeps_per_step), _p(lr, _f64p),
                                                  _p(distinct, _u32p), _p(rates, _f64p)))
+        return {"log_ratio": lr, "distinct": distinct, "rates": rates}
+
+    def population_rounds(self, temps, rounds_per_step, mh=1, heatbath=0, reshuffles=0, scans=3):
+        """population_run with, after every resampling step, `rounds_per_step` rounds of `mh` MH sweeps, `heatbath` heat-bath
+        sweeps and `reshuffles` pair reshuffles at the step's temperature.  Returns the dict of population_run (rates: of the
+        MH steps)."""
+        T = validate_population_temps(temps)
+        rec = round_recipe(mh, heatbath, reshuffles, scans)
+        if int(rounds_per_step) < 0:
+            raise ValueError("rounds_per_step must not be negative")
+        lr = np.zeros(len(T) - 1, dtype=np.float64)
+        distinct = np.zeros(len(T) - 1, dtype=np.uint32)
+        rates = np.zeros(self.n_chains, dtype=np.float64)
+        self._check(self._L.bisbm_rounds_population_run(self._h, len(T), _p(T, _f32p), int(rounds_per_step), C.byref(rec), _p(lr, _f64p),
+                                                        _p(distinct, _u32p), _p(rates, _f64p)))
         return {"log_ratio": lr, "distinct": distinct, "rates": rates}
 
     def population_state(self):
@@ -1369,6 +1410,48 @@ def validate_ladder(ladder):
     return lad
 
 
+RUNG_STAT_COLUMNS = ("mh_steps", "mh_accepted", "heatbath_steps", "heatbath_moves", "reshuffles", "reshuffles_accepted")
+
+
+def round_recipe(mh=1, heatbath=0, reshuffles=0, scans=3):
+    """The bisbm_round_recipe of a round of `mh` MH sweeps, `heatbath` heat-bath sweeps and `reshuffles` pair reshuffles of
+    `scans` launch scans, or ValueError: every count an integer in [0, 2^32), not all three moves 0."""
+    vals = []
+    for name, v in (("mh", mh), ("heatbath", heatbath), ("reshuffles", reshuffles), ("scans", scans)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s = %r is not an integer" % (name, v))
+        if not 0 <= int(v) < 1 << 32:
+            raise ValueError("%s = %r is outside [0, 2^32)" % (name, v))
+        vals.append(int(v))
+    if vals[0] == 0 and vals[1] == 0 and vals[2] == 0:
+        raise ValueError("a round of mh = 0, heatbath = 0 and reshuffles = 0 runs nothing")
+    return RoundRecipe(*vals)
+
+
+def rung_moves_recipe(rung_moves):
+    """The keyword `rung_moves` of marginalize() and friends -- a dict with some of the keys mh (default 1), heatbath (0),
+    reshuffles (0), scans (3) -- as keyword arguments of BlockModel.tempering_rounds, or ValueError."""
+    if not isinstance(rung_moves, dict):
+        raise ValueError("rung_moves must be a dict with the keys mh, heatbath, reshuffles, scans, not %r" % (rung_moves,))
+    unknown = sorted(set(rung_moves) - {"mh", "heatbath", "reshuffles", "scans"})
+    if unknown:
+        raise ValueError("rung_moves has unknown keys %s (known: mh, heatbath, reshuffles, scans)" % unknown)
+    kw = {"mh": 1, "heatbath": 0, "reshuffles": 0, "scans": 3}
+    kw.update(rung_moves)
+    round_recipe(**kw)
+    return {k: int(v) for k, v in kw.items()}
+
+
+def numpy_rung_tally(stats, rung, mh_steps=0, mh_accepted=0, heatbath_steps=0, heatbath_moves=0, reshuffles=0, reshuffles_accepted=0):
+    """The per-rung tally of one round on the host (bisbm_tempering_rung_stats): every chain's six deltas (scalars or arrays
+    [n_chains]) added to row rung[c] of `stats` (uint64 [L, 6], changed in place and returned) -- the rungs the chains held
+    during the round, before its exchange."""
+    rung = np.asarray(rung, dtype=np.int64)
+    for col, d in enumerate((mh_steps, mh_accepted, heatbath_steps, heatbath_moves, reshuffles, reshuffles_accepted)):
+        np.add.at(stats[:, col], rung, np.broadcast_to(np.asarray(d, dtype=np.uint64), rung.shape))
+    return stats
+
+
 def validate_population_temps(temps):
     """The temperatures of a population run as float32 (what the library runs), or ValueError: at least 2, each finite and > 0
     as a float32, non-increasing."""
@@ -1402,14 +1485,16 @@ def population_offspring(S, delta_beta, u):
     return off[: len(s)], parent[: len(s)], lr.value
 
 
-def population_anneal(model, temps, sweeps_per_step, burn_in_sweeps=0):
+def population_anneal(model, temps, sweeps_per_step, burn_in_sweeps=0, rung_moves=None):
     """Population annealing of all chains of `model`: `burn_in_sweeps` sweeps at temps[0], then BlockModel.population_run.
     Returns its dict plus "entropy" (the description length of every chain at the end) and "best_chain" (its argmin, ties ->
-    the lowest chain)."""
+    the lowest chain).  `rung_moves`: a dict {"mh", "heatbath", "reshuffles", "scans"} as in marginalize() -- every step then
+    runs `sweeps_per_step` ROUNDS of those moves at the step's temperature (BlockModel.population_rounds)."""
     T = validate_population_temps(temps)
+    recipe = rung_moves_recipe(rung_moves) if rung_moves is not None else None
     if int(burn_in_sweeps) > 0:
         model.run_sweeps(int(burn_in_sweeps), float(T[0]))
-    out = model.population_run(T, sweeps_per_step)
+    out = model.population_run(T, sweeps_per_step) if recipe is None else model.population_rounds(T, sweeps_per_step, **recipe)
     out["entropy"] = model.entropy()
     out["best_chain"] = int(np.argmin(out["entropy"]))
     return out

@@ -12,7 +12,8 @@
 //   bisbm_merge.hip      agg_merge / agg_split between anneals, chains of one handle in different shapes
 //   bisbm_align.hip      aligned marginal samples: every counted chain renumbered to the reference of its mode, then counted (the
 //                        overlap, assignment and counting kernels; one mode of every chain: the pooled aligned histogram)
-//   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel
+//   bisbm_tempering.hip  replica exchange: temperature ladders over ensembles of chains, the exchange kernel; rounds of MH sweeps,
+//                        heat-bath sweeps and pair reshuffles at a beta per chain, the per-rung tally
 //   bisbm_population.hip  population annealing: offspring counts on the host, the kernel that copies chain states between slots
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
 //   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains, top-k on the device; kernels and C ABI
@@ -173,6 +174,8 @@ struct TemperState {
     DeviceBuf<uint32_t> d_at;               // [ensemble][L] the chain (index in the engine) on every rung
     DeviceBuf<float> d_ladder;              // L temperatures
     DeviceBuf<unsigned long long> d_stats;  // [2][L - 1] attempted, accepted exchanges per rung pair
+    DeviceBuf<double> d_beta;               // [L] 1.0 / (double)ladder[i], the host's quotient (HeatbathParams / ReshuffleParams::beta_rung)
+    DeviceBuf<unsigned long long> d_rung_stats;  // [L][6] per rung: MH steps, accepted, heat-bath steps, moves, reshuffles proposed, accepted
 };
 
 // Population annealing (bisbm_population.hip).  The genealogy and the running totals belong to the handle the caller holds; the
@@ -666,6 +669,16 @@ void entropy_terms(const bisbm_engine* h, double t[8]);
 // bisbm_anneal on a kernel-running engine with a temperature per chain (T_chain: device pointer, NULL: none); bisbm_anneal.hip
 int anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t duration_steps, uint64_t steps_await,
                   double* acc_rate_out, const float* T_chain);
+// `sweeps` heat-bath sweeps of a kernel-running engine on its stream; per_rung: every chain at the beta of its rung
+// (TemperState::d_beta, d_rung) instead of `beta`; sync: wait for the stream before returning; bisbm_heatbath.hip
+int heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_settled, bool per_rung, bool sync);
+// `moves` pair reshuffles of a kernel-running engine on its stream, per_rung as above; read_back: wait for the stream and copy the
+// records and accepted counts of the call to the host (ReshuffleState::last / accepted), otherwise they stay on the device and
+// `last` is emptied; bisbm_reshuffle.hip
+int reshuffle_engine(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta, bool per_rung, bool read_back);
+int reshuffle_read_back(bisbm_engine* h);  // ... the copy alone, after a wait for the stream
+// BISBM_ERR_INVALID_ARG when a move of up to max(na, nb) members with `scans` launch scans could use 2^32 draws or more
+int reshuffle_check_scans(bisbm_engine* h, uint32_t scans);
 // bisbm_marginals_accumulate with the alignment on; bisbm_align.hip
 int align_accumulate(bisbm_engine* h, uint32_t* device_counts);
 // replica exchange is on and some engine under `h` keeps its chains grouped by shape: BISBM_ERR_STATE with the message of the

@@ -95,6 +95,7 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
 
     const Tables tab{p.lgamma_tab, p.lgamma_size, p.q_tab, p.q_stride, p.log_tab};
     const uint32_t chain_gid = chain_gid_of(p, chain);
+    const double beta = chain_beta_of(p, chain);  // (the launch's, or under replica exchange the chain's own)
     uint64_t moved = 0, sweeps_run = 0;
     for (uint64_t sweep = 0; sweep < p.sweeps; ++sweep) {
         uint64_t moved_sweep = 0;
@@ -253,7 +254,7 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                             const uint32_t tid = c0 + lane, cn = k_own - c0 < (uint32_t)kWave ? k_own - c0 : (uint32_t)kWave;
                             double w = 0.;
                             if (tid < k_own) {
-                                const double x = p.beta * (s_dS[tid] - mn);
+                                const double x = beta * (s_dS[tid] - mn);
                                 w = x > 700. ? 0. : exp(-x);
                                 s_x[tid] = w;
                             }
@@ -359,9 +360,7 @@ hipError_t launch_heatbath(const HeatbathParams& p, size_t lds_bytes, hipStream_
 
 }  // namespace bisbm
 
-namespace {
-
-int heatbath_leaf(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_settled) {
+int bisbm::heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_settled, bool per_rung, bool sync) {
     HIPCHK(h, hipSetDevice(h->device));
     HeatbathParams p{};
     p.rowptr = h->d_rowptr, p.col = h->d_col;
@@ -374,8 +373,9 @@ int heatbath_leaf(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_s
     p.lgamma_tab = h->d_lgamma, p.lgamma_size = h->tab->lg.size(), p.q_tab = h->d_q, p.q_stride = h->q_stride, p.log_tab = h->d_logtab;
     p.seed = h->seed;
     p.sweeps = sweeps;
-    p.greedy = std::isinf(beta) ? 1u : 0u;
+    p.greedy = !per_rung && std::isinf(beta) ? 1u : 0u;
     p.beta = p.greedy ? 0. : beta;
+    if (per_rung) p.beta_rung = h->temper.d_beta.get(), p.rung = h->temper.d_rung.get();
     p.stop_when_settled = stop_when_settled ? 1u : 0u;
     // eta goes to LDS when that still leaves room for four chains per CU, as in the generic sweep kernel's plan
     p.eta_in_lds = heatbath_lds_bytes(h->ka, h->kb, h->maxdeg, true) <= 40 * 1024 ? 1 : 0;
@@ -383,11 +383,9 @@ int heatbath_leaf(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_s
     if (lds > kLdsPerCu) return fail(h, BISBM_ERR_UNSUPPORTED, "chain state needs %zu B of LDS (> 160 KiB)", lds);
     h->ent_prev_valid = false;  // (the block state moves)
     HIPCHK(h, launch_heatbath(p, lds, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -410,7 +408,7 @@ int bisbm_heatbath_run(bisbm_handle h, uint64_t sweeps, double beta, int stop_wh
         return BISBM_OK;
     }
     DeviceGuard keep;
-    if (int rc = each_leaf(h, [&](bisbm_engine* e) { return heatbath_leaf(e, sweeps, beta, stop_when_settled); })) return rc;
+    if (int rc = each_leaf(h, [&](bisbm_engine* e) { return heatbath_engine(e, sweeps, beta, stop_when_settled, false, true); })) return rc;
     if (!moved_out && !sweeps_out) return BISBM_OK;
     return bisbm_get_last_counts(h, moved_out, sweeps_out);
 }

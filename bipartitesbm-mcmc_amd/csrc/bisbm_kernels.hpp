@@ -412,6 +412,10 @@ struct HeatbathParams {
     uint64_t seed;
     uint64_t sweeps;
     double beta;                 // finite, > 0 (unused when greedy)
+    // replica exchange (bisbm_tempering_run_rounds): a beta per chain of the launch (never greedy) -- chain c runs at beta_rung[rung[c]], the
+    // host's quotient 1.0 / (double)T of its rung's temperature (TemperState::d_beta, d_rung); NULL: `beta` for every chain
+    const double* beta_rung;
+    const uint32_t* rung;
     uint32_t greedy;             // beta = +inf: the lowest argmin of dS, only strictly downhill, no draw
     uint32_t stop_when_settled;  // a chain stops after the first sweep that moved nothing
     int eta_in_lds;
@@ -444,6 +448,10 @@ struct ReshuffleParams {
     uint64_t moves;
     uint32_t scans;
     double beta;                 // finite, > 0
+    // replica exchange (bisbm_tempering_run_rounds): a beta per chain of the launch -- chain c runs at beta_rung[rung[c]], the
+    // host's quotient 1.0 / (double)T of its rung's temperature (TemperState::d_beta, d_rung); NULL: `beta` for every chain
+    const double* beta_rung;
+    const uint32_t* rung;
     int eta_in_lds;
     // per-chain scratch, nmax = max(na, nb) entries each: the member ids, their original labels, their launch labels
     uint32_t* member;            // [chain][nmax]
@@ -461,6 +469,12 @@ hipError_t launch_split_eval(const SplitParams& p, hipStream_t stream);
 hipError_t launch_split_apply(const SplitParams& p, hipStream_t stream);
 hipError_t launch_labels_to_wide(const uint8_t* labels, uint8_t* wide_labels, size_t label_stride, uint32_t n, uint32_t n_chains,
                                  hipStream_t stream);
+
+// beta of chain `chain` of a heat-bath or reshuffle launch: read once at the head of the kernel, the same in every lane
+template <class P>
+__device__ __forceinline__ double chain_beta_of(const P& p, uint32_t chain) {
+    return p.beta_rung ? p.beta_rung[p.rung[chain]] : p.beta;
+}
 
 // global id of chain `chain` of a launch
 template <class P>

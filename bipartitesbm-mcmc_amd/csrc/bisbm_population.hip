@@ -323,4 +323,52 @@ int bisbm_population_run(bisbm_handle h, uint32_t n_temps, const float* temps, u
     return BISBM_OK;
 }
 
+int bisbm_rounds_population_run(bisbm_handle h, uint32_t n_temps, const float* temps, uint64_t rounds_per_step, const bisbm_round_recipe* recipe,
+                                double* log_ratio_out, uint32_t* distinct_out, double* acc_rate_out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (int rc = refuse(h)) return rc;
+    if (int rc = check_temps(h, n_temps, temps)) return rc;
+    if (rounds_per_step) {
+        if (!recipe) return fail(h, BISBM_ERR_INVALID_ARG, "recipe is NULL");
+        if (!recipe->mh_sweeps && !recipe->heatbath_sweeps && !recipe->reshuffles)
+            return fail(h, BISBM_ERR_INVALID_ARG, "the recipe runs nothing: mh_sweeps, heatbath_sweeps and reshuffles are all 0");
+    }
+    const bisbm_round_recipe r = rounds_per_step ? *recipe : bisbm_round_recipe{};
+    const uint32_t C = h->n_chains;
+    std::vector<double> rate(C), acc(C, 0.);
+    std::vector<uint8_t> seen(C);
+    double ms = 0;
+    uint64_t updates = 0;
+    for (uint32_t k = 1; k < n_temps; ++k) {
+        double log_ratio = 0.;
+        if (int rc = bisbm_population_resample(h, 1. / (double)temps[k - 1], 1. / (double)temps[k], nullptr, &log_ratio)) return rc;
+        if (log_ratio_out) log_ratio_out[k - 1] = log_ratio;
+        if (distinct_out) {
+            std::fill(seen.begin(), seen.end(), 0);
+            uint32_t distinct = 0;
+            for (uint32_t a : h->population.ancestor) distinct += !seen[a], seen[a] = 1;
+            distinct_out[k - 1] = distinct;
+        }
+        const float kw[2] = {temps[k], 0.f};
+        const double beta = 1. / (double)temps[k];
+        for (uint64_t round = 0; round < rounds_per_step; ++round) {
+            if (r.mh_sweeps) {
+                if (int rc = bisbm_anneal(h, BISBM_SCHED_CONSTANT, kw, (uint64_t)r.mh_sweeps * h->n, kNoStop, rate.data())) return rc;
+                for (uint32_t c = 0; c < C; ++c) acc[c] += rate[c];
+                ms += h->last_kernel_ms;
+                updates += h->last_updates;
+            }
+            if (r.heatbath_sweeps)
+                if (int rc = bisbm_heatbath_run(h, r.heatbath_sweeps, beta, 0, nullptr, nullptr)) return rc;
+            if (r.reshuffles)
+                if (int rc = bisbm_reshuffle_run(h, r.reshuffles, r.reshuffle_scans, beta, nullptr)) return rc;
+        }
+    }
+    if (rounds_per_step && r.mh_sweeps) h->last_kernel_ms = ms, h->last_updates = updates;  // (the run's MH sweeps as one call)
+    if (acc_rate_out)  // accepted MH steps / MH steps of the run: every round runs the same number of sweeps
+        for (uint32_t c = 0; c < C; ++c)
+            acc_rate_out[c] = rounds_per_step && r.mh_sweeps ? acc[c] / ((double)(n_temps - 1) * (double)rounds_per_step) : 0.;
+    return BISBM_OK;
+}
+
 }  // extern "C"

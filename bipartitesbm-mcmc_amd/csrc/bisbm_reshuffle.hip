@@ -91,6 +91,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
 
     const Tables tab{p.lgamma_tab, p.lgamma_size, p.q_tab, p.q_stride, p.log_tab};
     const uint32_t chain_gid = chain_gid_of(p, chain);
+    const double beta = chain_beta_of(p, chain);  // (the launch's, or under replica exchange the chain's own)
     const uint32_t pairs_a = p.ka * (p.ka - 1u) / 2u, n_pairs = pairs_a + p.kb * (p.kb - 1u) / 2u;
     unsigned long long n_accepted = 0;
     bisbm_reshuffle_record rec{};
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
                 // 8. accept
                 rec.q_fwd_mant = q_m, rec.q_fwd_exp = q_e, rec.dS_fwd = dsum;
                 const double dS = rec.dS_fwd - rec.dS_rev;
-                const double lnA = (0. - p.beta * dS) + (log(rec.q_rev_mant / rec.q_fwd_mant) + (double)(rec.q_rev_exp - rec.q_fwd_exp) * 0.6931471805599453);
+                const double lnA = (0. - beta * dS) + (log(rec.q_rev_mant / rec.q_fwd_mant) + (double)(rec.q_rev_exp - rec.q_fwd_exp) * 0.6931471805599453);
                 rec.A = exp(lnA);
                 accepted = u_acc < rec.A;
                 if (accepted) {
@@ -306,7 +307,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
                         dS_o = ((acc + tail1) + tail2) + tail3;
                         // the two weights, Z = w_r + w_s, the choice and its factor
                         const double mn = dS_o < 0. ? dS_o : 0.;
-                        const double x_c = p.beta * (0. - mn), x_o = p.beta * (dS_o - mn);
+                        const double x_c = beta * (0. - mn), x_o = beta * (dS_o - mn);
                         const double w_c = x_c > 700. ? 0. : exp(-x_c), w_o = x_o > 700. ? 0. : exp(-x_o);
                         const double w_r = c == rg ? w_c : w_o, w_s = c == rg ? w_o : w_c;
                         const double Z = w_r + w_s;
@@ -407,9 +408,7 @@ hipError_t launch_exp_probe(const double* x, size_t count, double* out, hipStrea
 
 }  // namespace bisbm
 
-namespace {
-
-int reshuffle_leaf(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta) {
+int bisbm::reshuffle_engine(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta, bool per_rung, bool read_back) {
     HIPCHK(h, hipSetDevice(h->device));
     ReshuffleState& st = h->reshuffle;
     const size_t nmax = (size_t)std::max(h->na, h->nb), C = h->n_chains;
@@ -427,6 +426,7 @@ int reshuffle_leaf(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta)
     p.lgamma_tab = h->d_lgamma, p.lgamma_size = h->tab->lg.size(), p.q_tab = h->d_q, p.q_stride = h->q_stride, p.log_tab = h->d_logtab;
     p.seed = h->seed;
     p.moves = moves, p.scans = scans, p.beta = beta;
+    if (per_rung) p.beta_rung = h->temper.d_beta.get(), p.rung = h->temper.d_rung.get();
     p.member = (uint32_t*)st.d_scratch.get();
     p.orig = st.d_scratch.get() + 4 * nmax * C;
     p.launch = st.d_scratch.get() + 5 * nmax * C;
@@ -438,6 +438,13 @@ int reshuffle_leaf(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta)
     h->ent_prev_valid = false;  // (the block state moves)
     st.last.clear();
     HIPCHK(h, launch_reshuffle(p, lds, h->stream));
+    return read_back ? reshuffle_read_back(h) : BISBM_OK;
+}
+
+int bisbm::reshuffle_read_back(bisbm_engine* h) {
+    ReshuffleState& st = h->reshuffle;
+    const size_t C = h->n_chains;
+    HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     st.last.resize(C);
     st.accepted.resize(C);
@@ -446,7 +453,12 @@ int reshuffle_leaf(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta)
     return BISBM_OK;
 }
 
-}  // namespace
+int bisbm::reshuffle_check_scans(bisbm_engine* h, uint32_t scans) {
+    const uint64_t nmax = std::max(h->na, h->nb);
+    if (nmax >= (1ull << 32) || 2 + (nmax + 127) / 128 + ((uint64_t)scans + 1) * nmax >= (1ull << 32))
+        return fail(h, BISBM_ERR_INVALID_ARG, "scans = %u: a move of up to %llu members could use 2^32 draws or more", scans, (unsigned long long)nmax);
+    return BISBM_OK;
+}
 
 extern "C" {
 
@@ -461,15 +473,13 @@ int bisbm_reshuffle_run(bisbm_handle h, uint64_t moves, uint32_t scans, double b
         return fail(h, BISBM_ERR_UNSUPPORTED, "pair reshuffles serve byte labels only (at most 256 blocks): merge the blocks down first");
     for (bisbm_engine* e : leaves(h))
         if (!e->state_ready) return fail(h, BISBM_ERR_STATE, "call bisbm_init or bisbm_shuffle before bisbm_reshuffle_run");
-    const uint64_t nmax = std::max(h->na, h->nb);
-    if (nmax >= (1ull << 32) || 2 + (nmax + 127) / 128 + ((uint64_t)scans + 1) * nmax >= (1ull << 32))
-        return fail(h, BISBM_ERR_INVALID_ARG, "scans = %u: a move of up to %llu members could use 2^32 draws or more", scans, (unsigned long long)nmax);
+    if (int rc = reshuffle_check_scans(h, scans)) return rc;
     if (moves == 0) {
         for (uint32_t c = 0; accepted_out && c < h->n_chains; ++c) accepted_out[c] = 0;
         return BISBM_OK;
     }
     DeviceGuard keep;
-    if (int rc = each_leaf(h, [&](bisbm_engine* e) { return reshuffle_leaf(e, moves, scans, beta); })) return rc;
+    if (int rc = each_leaf(h, [&](bisbm_engine* e) { return reshuffle_engine(e, moves, scans, beta, false, true); })) return rc;
     for (uint32_t c = 0; accepted_out && c < h->n_chains; ++c) {
         uint32_t local;
         bisbm_engine* e = leaf_of_chain(h, c, &local);

@@ -52,6 +52,32 @@ __global__ __launch_bounds__(256) void tempering_exchange_kernel(ExchangeParams 
     }
 }
 
+// The per-rung tally of a round (bisbm_tempering_rung_stats): what the kernel that has just run left per chain is added to the
+// row of the rung the chain holds -- before the round's exchange moves it.  which = 0: the MH segment (ChainScalars::last_sweeps
+// * n steps, last_accepted), 1: heat-bath sweeps (the same two scalars: visits, moves), 2: pair reshuffles (`moves` proposed,
+// accepted[c]).  One lane per chain, integer atomics that return nothing.
+__global__ __launch_bounds__(256) void tempering_tally_kernel(const ChainScalars* scalars, const unsigned long long* accepted, const uint32_t* rung,
+                                                              uint32_t n_chains, uint32_t which, unsigned long long n, unsigned long long moves,
+                                                              unsigned long long* stats) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_chains) return;
+    unsigned long long* row = stats + (size_t)rung[c] * 6u + 2u * which;
+    if (which < 2u) {
+        atomicAdd(&row[0], (unsigned long long)scalars[c].last_sweeps * n);
+        atomicAdd(&row[1], (unsigned long long)scalars[c].last_accepted);
+    } else {
+        atomicAdd(&row[0], moves);
+        atomicAdd(&row[1], accepted[c]);
+    }
+}
+
+int tally(bisbm_engine* e, uint32_t which, uint64_t moves) {
+    hipLaunchKernelGGL(tempering_tally_kernel, dim3((e->n_chains + 255) / 256), dim3(256), 0, e->stream, e->d_scalars, e->reshuffle.d_accepted.get(),
+                       e->temper.d_rung.get(), e->n_chains, which, (unsigned long long)e->n, (unsigned long long)moves, e->temper.d_rung_stats.get());
+    HIPCHK(e, hipGetLastError());
+    return BISBM_OK;
+}
+
 constexpr uint64_t kNoStop = 1ull << 60;  // steps_await of every segment: no early stop (as BlockModel.run_sweeps)
 
 int mixed_shapes(bisbm_engine* h) {
@@ -70,6 +96,10 @@ int setup_leaf(bisbm_engine* e, uint32_t L, const float* ladder) {
     RESERVE(e, t.d_at, C);
     RESERVE(e, t.d_ladder, L);
     RESERVE(e, t.d_stats, 2 * (size_t)L);
+    RESERVE(e, t.d_beta, L);
+    RESERVE(e, t.d_rung_stats, 6 * (size_t)L);
+    std::vector<double> beta(L);
+    for (uint32_t i = 0; i < L; ++i) beta[i] = 1.0 / (double)ladder[i];  // (the definition of a rung's beta: this host quotient)
     std::vector<float> T(C);
     std::vector<uint32_t> rung(C), at(C);
     for (uint32_t c = 0; c < C; ++c) T[c] = ladder[c % L], rung[c] = c % L, at[c] = c;
@@ -78,6 +108,8 @@ int setup_leaf(bisbm_engine* e, uint32_t L, const float* ladder) {
     HIPCHK(e, hipMemcpyAsync(t.d_at.get(), at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipMemcpyAsync(t.d_ladder.get(), ladder, sizeof(float) * L, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipMemsetAsync(t.d_stats.get(), 0, sizeof(unsigned long long) * 2 * L, e->stream));
+    HIPCHK(e, hipMemcpyAsync(t.d_beta.get(), beta.data(), sizeof(double) * L, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemsetAsync(t.d_rung_stats.get(), 0, sizeof(unsigned long long) * 6 * L, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     t.L = L;
     t.ladder.assign(ladder, ladder + L);
@@ -131,7 +163,7 @@ int run_leaf(bisbm_engine* e, uint64_t sweeps, uint32_t every, double* acc_rate_
         for (uint32_t c = 0; c < e->n_chains; ++c) acc[c] += rate[c] * (double)k;  // (rate: accepted / steps of the segment)
         ms += e->last_kernel_ms;
         updates += e->last_updates;
-        return BISBM_OK;
+        return tally(e, 0, 0);
     };
     for (uint64_t b = 0; b < blocks; ++b) {
         if (int rc = segment(every)) return rc;
@@ -144,6 +176,43 @@ int run_leaf(bisbm_engine* e, uint64_t sweeps, uint32_t every, double* acc_rate_
     e->last_updates = updates;
     if (acc_rate_out)
         for (uint32_t c = 0; c < e->n_chains; ++c) acc_rate_out[c] = sweeps ? acc[c] / (double)sweeps : 0.;
+    return BISBM_OK;
+}
+
+// `rounds` rounds of the recipe on a kernel-running engine: the MH segment of run_leaf, heat-bath sweeps and pair reshuffles at
+// every chain's own beta, the tally, the exchange.  Nothing per chain travels to the host between the rounds beyond what the MH
+// segment itself reads (bisbm_anneal's scalars); the reshuffle records of the last round are read back once, at the end.
+int rounds_leaf(bisbm_engine* e, uint64_t rounds, const bisbm_round_recipe& r, bool exchange) {
+    TemperState& t = e->temper;
+    HIPCHK(e, hipSetDevice(e->device));
+    const float kw[2] = {t.ladder[0], 0.f};
+    double ms = 0;
+    uint64_t updates = 0;
+    for (uint64_t k = 0; k < rounds; ++k) {
+        if (r.mh_sweeps) {
+            if (int rc = anneal_engine(e, BISBM_SCHED_CONSTANT, kw, (uint64_t)r.mh_sweeps * e->n, kNoStop, nullptr, t.d_T.get())) return rc;
+            ms += e->last_kernel_ms;
+            updates += e->last_updates;
+            if (int rc = tally(e, 0, 0)) return rc;
+        }
+        if (r.heatbath_sweeps) {
+            if (int rc = heatbath_engine(e, r.heatbath_sweeps, 0., 0, true, false)) return rc;
+            if (int rc = tally(e, 1, 0)) return rc;
+        }
+        if (r.reshuffles) {
+            if (int rc = reshuffle_engine(e, r.reshuffles, r.reshuffle_scans, 0., true, false)) return rc;
+            if (int rc = tally(e, 2, r.reshuffles)) return rc;
+        }
+        if (exchange)
+            if (int rc = exchange_round(e)) return rc;
+    }
+    if (r.reshuffles && rounds) {
+        if (int rc = reshuffle_read_back(e)) return rc;
+    } else {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+    }
+    e->last_kernel_ms = ms;
+    e->last_updates = updates;
     return BISBM_OK;
 }
 
@@ -215,6 +284,52 @@ int bisbm_tempering_run(bisbm_handle h, uint64_t sweeps, uint32_t exchange_every
     }
     h->temper.round = h->devs[0]->temper.round;
     return rc;
+}
+
+int bisbm_tempering_run_rounds(bisbm_handle h, uint64_t rounds, const bisbm_round_recipe* recipe, int exchange) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->temper.L) return fail(h, BISBM_ERR_STATE, "replica exchange is off: call bisbm_tempering_set first");
+    if (!recipe) return fail(h, BISBM_ERR_INVALID_ARG, "recipe is NULL");
+    if (int rc = mixed_shapes(h)) return rc;
+    const bisbm_round_recipe r = *recipe;
+    if (!r.mh_sweeps && !r.heatbath_sweeps && !r.reshuffles)
+        return fail(h, BISBM_ERR_INVALID_ARG, "the recipe runs nothing: mh_sweeps, heatbath_sweeps and reshuffles are all 0");
+    if ((r.heatbath_sweeps || r.reshuffles) && any_wide(h))
+        return fail(h, BISBM_ERR_UNSUPPORTED, "heat-bath sweeps and pair reshuffles serve byte labels only (at most 256 blocks): this recipe (heatbath_sweeps = %u, reshuffles = %u) needs them; merge the blocks down first",
+                    r.heatbath_sweeps, r.reshuffles);
+    for (bisbm_engine* e : leaves(h))
+        if (!e->state_ready) return fail(h, BISBM_ERR_STATE, "call bisbm_init or bisbm_shuffle before bisbm_tempering_run_rounds");
+    if (r.reshuffles)
+        if (int rc = reshuffle_check_scans(h, r.reshuffle_scans)) return rc;
+    DeviceGuard keep;
+    if (h->devs.empty()) return rounds_leaf(h, rounds, r, exchange != 0);
+    const int rc = on_devices(h, [&](bisbm_engine* d, size_t) { return rounds_leaf(d, rounds, r, exchange != 0); });
+    h->last_kernel_ms = 0;
+    h->last_updates = 0;
+    for (bisbm_engine* d : h->devs) {  // (as bisbm_tempering_run)
+        h->last_kernel_ms = std::max(h->last_kernel_ms, d->last_kernel_ms);
+        h->last_updates += d->last_updates;
+        h->last_pass_steps = std::max(d == h->devs[0] ? 0u : h->last_pass_steps, d->last_pass_steps);
+    }
+    h->temper.round = h->devs[0]->temper.round;
+    return rc;
+}
+
+int bisbm_tempering_rung_stats(bisbm_handle h, uint64_t* out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->temper.L) return fail(h, BISBM_ERR_STATE, "replica exchange is off");
+    if (!out) return fail(h, BISBM_ERR_INVALID_ARG, "out is NULL");
+    const size_t cells = 6 * (size_t)h->temper.L;
+    std::vector<uint64_t> part(cells);
+    std::fill(out, out + cells, 0);
+    DeviceGuard keep;
+    for (bisbm_engine* e : device_entries(h)) {
+        HIPCHK(h, hipSetDevice(e->device));
+        HIPCHK(h, hipStreamSynchronize(e->stream));
+        HIPCHK(h, hipMemcpy(part.data(), e->temper.d_rung_stats.get(), sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < cells; ++i) out[i] += part[i];
+    }
+    return BISBM_OK;
 }
 
 int bisbm_tempering_get(bisbm_handle h, uint32_t* rung_of_chain, float* T_of_chain) {

@@ -266,6 +266,16 @@ public:
         accepted.assign(L - 1, 0);
         check(bisbm_tempering_stats(h_, attempted.data(), accepted.data(), &rounds));
     }
+    // rounds of mixed moves under replica exchange (include/bisbm.h): per round the recipe's MH sweeps, heat-bath sweeps and pair
+    // reshuffles of every chain at its rung's temperature, then one exchange; what each move did per rung (L rows of 6 counts)
+    void tempering_rounds(uint64_t rounds, const bisbm_round_recipe& recipe, bool exchange = true) {
+        check(bisbm_tempering_run_rounds(h_, rounds, &recipe, exchange ? 1 : 0));
+    }
+    std::vector<uint64_t> tempering_rung_stats(size_t L) {
+        std::vector<uint64_t> out(6 * L);
+        check(bisbm_tempering_rung_stats(h_, out.data()));
+        return out;
+    }
     // population annealing (include/bisbm.h): one resampling step (the parent of every slot, the step's log ratio); a run over
     // non-increasing temperatures (log ratio and distinct ancestors per step, acceptance rate per chain); the genealogy
     std::vector<uint32_t> population_resample(double beta_from, double beta_to, double& log_ratio) {
@@ -280,6 +290,14 @@ public:
         distinct.assign(steps, 0);
         rates.assign(n_chains_, 0.);
         check(bisbm_population_run(h_, (uint32_t)temps.size(), temps.data(), sweeps_per_step, log_ratio.data(), distinct.data(), rates.data()));
+    }
+    void population_rounds(const std::vector<float>& temps, uint64_t rounds_per_step, const bisbm_round_recipe& recipe, std::vector<double>& log_ratio,
+                           std::vector<uint32_t>& distinct, std::vector<double>& rates) {
+        const size_t steps = temps.empty() ? 0 : temps.size() - 1;
+        log_ratio.assign(steps, 0.);
+        distinct.assign(steps, 0);
+        rates.assign(n_chains_, 0.);
+        check(bisbm_rounds_population_run(h_, (uint32_t)temps.size(), temps.data(), rounds_per_step, &recipe, log_ratio.data(), distinct.data(), rates.data()));
     }
     std::vector<uint32_t> population_state(uint64_t& rounds, double& log_ratio_total) {
         std::vector<uint32_t> ancestor(n_chains_);

@@ -6,7 +6,7 @@
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
 // --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
-// --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace.
+// --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace, --rung_moves, --population_moves.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -60,6 +60,7 @@ const option_spec kOptions[] = {
     {"polish", 0, 1},           {"heatbath", 0, 0},
     {"reshuffle", 0, 1},        {"reshuffle_scans", 0, 1},
     {"trace", 0, 2},
+    {"rung_moves", 0, 2},       {"population_moves", 0, 2},
 };
 
 const option_spec* find_long(const std::string& name) {
@@ -191,6 +192,11 @@ void print_help(const char* argv0) {
                  "                                        temperatures, and only the chains at T0 are sampled.  The swap\n"
                  "                                        acceptance of every rung pair is reported on stderr.\n"
                  "  --exchange_every arg (=1)             With --tempering: sweeps between exchange rounds.\n"
+                 "  --rung_moves MH HB RS SCANS           With --tempering: burn-in and the gaps between samples run as ROUNDS of MH\n"
+                 "                                        Metropolis-Hastings sweeps, HB heat-bath sweeps and RS pair reshuffles (SCANS\n"
+                 "                                        scans each) of every chain at its rung's temperature, then one exchange;\n"
+                 "                                        -b and -f, divided by the node count as always, then count rounds instead\n"
+                 "                                        of sweeps.  What each move did per rung is reported on stderr.\n"
                  "  --population arg                      Population annealing over temperatures T0 >= ... >= TL (at least 2, each\n"
                  "                                        > 0; Philox mode) in place of the -c / -a schedule: every chain runs\n"
                  "                                        --population_sweeps sweeps at T0; then, for every further temperature,\n"
@@ -200,6 +206,9 @@ void print_help(const char* argv0) {
                  "                                        log ratio ln Z(1/T_k) / Z(1/T_{k-1}) and the distinct ancestors of every\n"
                  "                                        step, and the total, are reported on stderr.\n"
                  "  --population_sweeps arg (=1)          With --population: sweeps per temperature.\n"
+                 "  --population_moves MH HB RS SCANS     With --population: every temperature after the first runs --population_sweeps\n"
+                 "                                        ROUNDS of MH Metropolis-Hastings sweeps, HB heat-bath sweeps and RS pair\n"
+                 "                                        reshuffles (SCANS scans each) instead of that many sweeps.\n"
                  "  --polish N                            After the annealing run or the merges and before the labels are printed:\n"
                  "                                        up to N greedy sweeps (every node to its block of least description\n"
                  "                                        length, only strictly downhill; Philox mode) until a whole sweep moves\n"
@@ -522,7 +531,7 @@ int main(int argc, char const* argv[]) {
         return 1;
     }
     if (count("heatbath") && count("tempering")) {
-        std::cerr << "--heatbath cannot be combined with --tempering: replica exchange runs Metropolis-Hastings sweeps.\n";
+        std::cerr << "--heatbath cannot be combined with --tempering: heat-bath sweeps inside replica exchange are asked for with --rung_moves MH HB RS SCANS.\n";
         return 1;
     }
     uint64_t reshuffle_moves = 0;
@@ -537,7 +546,7 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
         if (count("tempering")) {
-            std::cerr << "--reshuffle cannot be combined with --tempering: the library refuses pair reshuffles while replica exchange is on.\n";
+            std::cerr << "--reshuffle cannot be combined with --tempering: pair reshuffles inside replica exchange are asked for with --rung_moves MH HB RS SCANS.\n";
             return 1;
         }
         const std::string v = single("reshuffle", ""), t = single("reshuffle_scans", "3");
@@ -552,6 +561,33 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
         reshuffle_moves = k, reshuffle_scans = (uint32_t)sc;
+    }
+    // the moves of a round (--rung_moves with --tempering, --population_moves with --population): four integers MH HB RS SCANS
+    bisbm_round_recipe rung_moves{}, population_moves{};
+    bool have_rung_moves = false, have_population_moves = false;
+    for (const char* name : {"rung_moves", "population_moves"}) {
+        if (!count(name)) continue;
+        const bool pop = std::string(name) == "population_moves";
+        const char* needs = pop ? "population" : "tempering";
+        if (!count(needs)) {
+            std::cerr << "--" << name << " sets the moves of a round of --" << needs << ": it needs --" << needs << ".\n";
+            return 1;
+        }
+        uint32_t v[4] = {0, 0, 0, 0};
+        bool ok = var_map[name].size() == 4;
+        for (size_t i = 0; ok && i < 4; ++i) {
+            const std::string& tok = var_map[name][i];
+            char* end = nullptr;
+            const unsigned long long k = std::strtoull(tok.c_str(), &end, 10);
+            ok = !tok.empty() && tok[0] >= '0' && tok[0] <= '9' && *end == '\0' && k < (1ull << 32);
+            v[i] = (uint32_t)k;
+        }
+        if (!ok || (!v[0] && !v[1] && !v[2])) {
+            std::cerr << "Invalid --" << name << ". Four integers >= 0, MH HB RS SCANS, not all of MH HB RS zero, e.g. --" << name << " 1 0 2 3.\n";
+            return 1;
+        }
+        (pop ? population_moves : rung_moves) = bisbm_round_recipe{v[0], v[1], v[2], v[3]};
+        (pop ? have_population_moves : have_rung_moves) = true;
     }
     // population annealing: the temperatures and the sweeps per temperature are checked before anything else runs (one more
     // refusal, an initial partition without the -z block counts, waits below until the partition has been read: before the
@@ -1219,7 +1255,9 @@ int main(int argc, char const* argv[]) {
             if (!ladder.empty()) blockmodel.tempering_set(ladder);
             uint64_t reshuffles_proposed = 0, reshuffles_accepted = 0;
             auto advance = [&](size_t sweeps) {
-                if (!ladder.empty())
+                if (have_rung_moves)  // (`sweeps` counts rounds)
+                    blockmodel.tempering_rounds(sweeps, rung_moves);
+                else if (!ladder.empty())
                     blockmodel.tempering_run(sweeps, exchange_every);
                 else if (count("heatbath"))
                     blockmodel.heatbath_sweeps(sweeps, 1.0);
@@ -1333,6 +1371,17 @@ int main(int argc, char const* argv[]) {
                     std::clog << " " << ladder[i] << "<->" << ladder[i + 1] << " " << acc[i] << "/" << att[i] << " ("
                               << (att[i] ? (double)acc[i] / (double)att[i] : 0.) << ")";
                 std::clog << "\n";
+                if (have_rung_moves) {
+                    const std::vector<uint64_t> rs = blockmodel.tempering_rung_stats(ladder.size());
+                    std::clog << "rung moves: rounds of " << rung_moves.mh_sweeps << " MH sweep(s), " << rung_moves.heatbath_sweeps << " heat-bath sweep(s), "
+                              << rung_moves.reshuffles << " reshuffle(s) of " << rung_moves.reshuffle_scans << " scan(s); per rung:";
+                    for (size_t i = 0; i < ladder.size(); ++i) {
+                        const uint64_t* r = rs.data() + 6 * i;
+                        std::clog << " T=" << ladder[i] << " mh " << r[1] << "/" << r[0] << " heatbath " << r[3] << "/" << r[2] << " reshuffle " << r[5] << "/" << r[4]
+                                  << " (" << (r[4] ? (double)r[5] / (double)r[4] : 0.) << ")";
+                    }
+                    std::clog << "\n";
+                }
             }
             if (count("align") && !per_mode)
                 std::clog << "align: labels matched to chain " << blockmodel.marginals_reference_chain() << " (lowest description length)\n";
@@ -1619,7 +1668,10 @@ int main(int argc, char const* argv[]) {
             if (population_sweeps) algorithm.anneal(blockmodel, &constant_schedule, t0, population_sweeps * (NA + NB), (size_t)1 << 60);
             std::vector<double> log_ratio, rates;
             std::vector<uint32_t> distinct;
-            blockmodel.population_run(population, population_sweeps, log_ratio, distinct, rates);
+            if (have_population_moves)
+                blockmodel.population_rounds(population, population_sweeps, population_moves, log_ratio, distinct, rates);
+            else
+                blockmodel.population_run(population, population_sweeps, log_ratio, distinct, rates);
             char line[160];
             for (size_t k = 0; k < log_ratio.size(); ++k) {
                 std::snprintf(line, sizeof(line), "population step %zu: T %g -> %g, log ratio %.17g, distinct ancestors %u\n", k + 1,

@@ -18,7 +18,7 @@ import numpy as np
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
-                similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None):
+                similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None, rung_moves=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -64,11 +64,16 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     (prob, terms) -- is appended after the stats.  The chains of this rank only.
     `sampler`: "mh" (the default: model.run_sweeps) or "heatbath" -- burn-in and the gaps between samples run through
     model.heatbath_sweeps(sweeps, 1.0) (include/bisbm.h, "Heat-bath sweeps and greedy polishing"); with `tempering` a ValueError
-    (the library refuses heat-bath sweeps while replica exchange is on).
+    (heat-bath sweeps inside replica exchange are asked for with `rung_moves`).
     `reshuffles`: m > 0 runs model.reshuffle(m, reshuffle_scans, 1.0) after every block of sweeps -- the burn-in and every gap
     between samples (include/bisbm.h, "Pair reshuffles"; 3 scans are the convention of the literature, not a measurement); with
-    `tempering` a ValueError.  model.reshuffle_stats = {"proposed", "accepted"} (totals over the chains of this rank) reports
+    `tempering` a ValueError (`rung_moves` is the keyword for that).  model.reshuffle_stats = {"proposed", "accepted"} (totals over the chains of this rank) reports
     the acceptance afterwards.
+    `rung_moves`: with `tempering` only (ValueError without): a dict with some of the keys "mh" (default 1), "heatbath" (0),
+    "reshuffles" (0), "scans" (3).  Burn-in and the gaps between samples then run as ROUNDS of model.tempering_rounds -- per round
+    that many MH sweeps, heat-bath sweeps and pair reshuffles of every chain at its rung's temperature, then one exchange --
+    and `burn_in_sweeps` and `sampling_frequency_sweeps` count rounds; `exchange_every` is not used.
+    model.tempering_rung_stats() reports what each move did per rung afterwards.
     `trace`: depth > 0 (include/bisbm.h, "Chain traces"): a ring of that many snapshots per chain is set, with everything
     forgotten, before the first sample, and every sample is followed by one model.trace_record().  The return value does not
     change: model.trace_lags() / model.trace_series() give the lag curves and the series afterwards (lags in units of
@@ -77,7 +82,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
         return_counts = not multi
-    advance = _advance(model, tempering, exchange_every, sampler, reshuffles, reshuffle_scans)
+    advance = _advance(model, tempering, exchange_every, sampler, reshuffles, reshuffle_scans, rung_moves)
     if burn_in_sweeps > 0:
         advance(burn_in_sweeps)
     if score_pairs is not None:
@@ -184,7 +189,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
 
 
 def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,
-                      reassign=False, tempering=None, exchange_every=1, sampler="mh", trace=None):
+                      reassign=False, tempering=None, exchange_every=1, sampler="mh", trace=None, rung_moves=None):
     """Mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): the chains are grouped into posterior modes and
     every mode gets an aligned histogram and a MAP of its own, in the numbering of its own reference.
     Exactly one of `threshold` and `mode_of_chain`: with `threshold` the grouping is model.partition_modes(threshold) taken
@@ -208,6 +213,7 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     throughout.  `tempering` (with `reassign` only; ValueError otherwise): a temperature ladder as in marginalize(); burn-in
     and the gaps between samples run through model.tempering_run(sweeps, exchange_every), the grouping and every sample take
     the chains on rung 0.  `mode_of_chain` with `reassign` is a ValueError: the anchors come from a grouping.
+    `rung_moves` (with `tempering` only): the moves of a round, as in marginalize(); burn-in and gaps count rounds then.
     `sampler`: "mh" or "heatbath", as in marginalize().  `trace`: a depth, as in marginalize() -- one model.trace_record() after
     every sample; the dict does not change.
     Chains spread over ranks (`shard`, or model.shard, with world_size > 1) raise ValueError: pooling modes across ranks is
@@ -224,7 +230,7 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     from . import mode_assignment
     if mode_of_chain is not None:
         moc, n_modes = mode_assignment(mode_of_chain, model.n_chains)
-    advance = _advance(model, tempering, exchange_every, sampler)
+    advance = _advance(model, tempering, exchange_every, sampler, rung_moves=rung_moves)
     if burn_in_sweeps > 0:
         advance(burn_in_sweeps)
     if threshold is not None:
@@ -276,17 +282,20 @@ def _trace_start(model, trace):
     model.trace_reset()
 
 
-def _advance(model, tempering, exchange_every, sampler, reshuffles=0, reshuffle_scans=3):
+def _advance(model, tempering, exchange_every, sampler, reshuffles=0, reshuffle_scans=3, rung_moves=None):
     """The call that runs the sweeps of the burn-in and between samples: MH at T = 1, heat-bath sweeps at beta = 1, or -- with
     a ladder, which is set here -- replica exchange.  reshuffles > 0: every such block of sweeps is followed by that many pair
-    reshuffles at beta = 1."""
+    reshuffles at beta = 1.  rung_moves (with a ladder only): the blocks are rounds of model.tempering_rounds."""
+    if rung_moves is not None and tempering is None:
+        raise ValueError("rung_moves describes the rounds of replica exchange: it needs tempering=ladder")
     if sampler not in ("mh", "heatbath"):
         raise ValueError("sampler must be \"mh\" or \"heatbath\", not %r" % (sampler,))
     if int(reshuffles) < 0 or int(reshuffle_scans) < 0:
         raise ValueError("reshuffles and reshuffle_scans must not be negative")
     if int(reshuffles) > 0:
         if tempering is not None:
-            raise ValueError("reshuffles cannot be combined with tempering: the library refuses them while replica exchange is on")
+            raise ValueError("reshuffles cannot be combined with tempering: pair reshuffles inside replica exchange are asked for with "
+                             "rung_moves={\"mh\": 1, \"reshuffles\": m, \"scans\": t}")
         sweeps_only = _advance(model, None, exchange_every, sampler)
         model.reshuffle_stats = {"proposed": 0, "accepted": 0}
 
@@ -298,7 +307,13 @@ def _advance(model, tempering, exchange_every, sampler, reshuffles=0, reshuffle_
         return block
     if tempering is not None:
         if sampler == "heatbath":
-            raise ValueError("sampler=\"heatbath\" cannot be combined with tempering: replica exchange runs MH sweeps")
+            raise ValueError("sampler=\"heatbath\" cannot be combined with tempering: heat-bath sweeps inside replica exchange are asked "
+                             "for with rung_moves={\"mh\": 0, \"heatbath\": k}")
+        if rung_moves is not None:
+            from . import rung_moves_recipe
+            recipe = rung_moves_recipe(rung_moves)
+            model.set_tempering(tempering)
+            return lambda rounds: model.tempering_rounds(rounds, **recipe)
         model.set_tempering(tempering)
         return lambda sweeps: model.tempering_run(sweeps, exchange_every)
     if sampler == "heatbath":

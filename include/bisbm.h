@@ -29,7 +29,8 @@ extern "C" {
  *    anchored modes (bisbm_marginals_set_mode_anchors, bisbm_marginals_get_mode_assignment), query scores
  *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*), population annealing
  *    (bisbm_population_*), node conditionals (bisbm_conditionals_*), heat-bath sweeps and greedy polishing
- *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp), chain traces (bisbm_trace_*).  Additions only. */
+ *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp), chain traces (bisbm_trace_*), round recipes
+ *    (bisbm_tempering_run_rounds, bisbm_tempering_rung_stats, bisbm_rounds_population_run).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -238,6 +239,33 @@ int bisbm_tempering_get(bisbm_handle h, uint32_t *rung_of_chain, float *T_of_cha
  * may be NULL. */
 int bisbm_tempering_stats(bisbm_handle h, uint64_t *attempted, uint64_t *accepted, uint64_t *rounds);
 
+/* Heat-bath sweeps and pair reshuffles inside replica exchange.  Under a round recipe every chain runs the two moves (defined
+ * under "Heat-bath sweeps and greedy polishing" and "Pair reshuffles" below, unchanged: the same counters sweeps_total and
+ * reshuffles_total, purposes 9 and 10, every stated order) at its own beta_c = 1.0 / (double)T_c, the correctly rounded f64
+ * quotient of its rung's float temperature as the host computes it at bisbm_tempering_set.  Each of the three moves leaves
+ * exp(-S / T_c) invariant for the chain it runs on, so does their sequence, and the exchange leaves the joint distribution
+ * invariant.  Greedy polishing (beta = +inf) is not available per chain. */
+typedef struct bisbm_round_recipe {
+    uint32_t mh_sweeps;        /* MH sweeps per round, each chain at T_c (the segment of bisbm_tempering_run) */
+    uint32_t heatbath_sweeps;  /* then heat-bath sweeps at beta_c (no early stop) */
+    uint32_t reshuffles;       /* then pair reshuffles per chain at beta_c */
+    uint32_t reshuffle_scans;  /* launch scans of every reshuffle */
+} bisbm_round_recipe;
+/* `rounds` rounds; a round runs, in this order: the MH sweeps, the heat-bath sweeps, the reshuffles, the per-rung tally
+ * (bisbm_tempering_rung_stats) and, if `exchange` is not 0, one exchange round as defined above (the same Philox index
+ * round * L + i, the same round counter and statistics).  So bisbm_tempering_run_rounds(R, {k, 0, 0, .}, 1) is
+ * bisbm_tempering_run(R * k, k) bit for bit, and chain c is the chain a one-chain handle of its global id runs through
+ * bisbm_anneal, bisbm_heatbath_run and bisbm_reshuffle_run at the temperatures chain c held.  Refused: replica exchange off and
+ * chains grouped by shape (BISBM_ERR_STATE), a NULL recipe or one of all zeros (BISBM_ERR_INVALID_ARG), a recipe with heat-bath
+ * sweeps or reshuffles on a wide handle (BISBM_ERR_UNSUPPORTED).  bisbm_heatbath_run and bisbm_reshuffle_run themselves stay
+ * refused while replica exchange is on.  bisbm_reshuffle_get_last reports the last round's last move afterwards. */
+int bisbm_tempering_run_rounds(bisbm_handle h, uint64_t rounds, const bisbm_round_recipe *recipe, int exchange);
+/* out[L * 6]: per rung i, out[6 i + ...] = MH steps, MH steps accepted, heat-bath steps (sweeps * n), heat-bath moves,
+ * reshuffles proposed, reshuffles accepted since bisbm_tempering_set, summed over ensembles and device entries.  What a chain
+ * does in a round (or in a segment of bisbm_tempering_run, which feeds the MH columns) is added to the rung it held during it,
+ * before that round's exchange -- on the device, with integer adds. */
+int bisbm_tempering_rung_stats(bisbm_handle h, uint64_t *out /* L * 6 */);
+
 /* Population annealing (Hukushima & Iba 2003, Machta 2010; no reference counterpart: the reference runs one chain).  The
  * population is all C chains of the handle, over every device of it, all at one temperature; between temperature steps it is
  * resampled by description length, and sweeps at the new temperature then decorrelate the copies.  One resampling step from
@@ -286,6 +314,14 @@ int bisbm_population_resample(bisbm_handle h, double beta_from, double beta_to,
 int bisbm_population_run(bisbm_handle h, uint32_t n_temps, const float *temps, uint64_t sweeps_per_step,
                          double *log_ratio_out /* n_temps-1 */, uint32_t *distinct_out /* n_temps-1 */,
                          double *acc_rate_out /* n_chains, may be NULL */);
+/* bisbm_population_run with, after every resampling step, rounds_per_step rounds of the recipe at the common temperature
+ * temps[k]: mh_sweeps sweeps of bisbm_anneal (BISBM_SCHED_CONSTANT, no early stop), then bisbm_heatbath_run(heatbath_sweeps,
+ * beta, 0), then bisbm_reshuffle_run(reshuffles, reshuffle_scans, beta) with beta = 1.0 / (double)temps[k].  There is no
+ * exchange.  acc_rate_out[c]: accepted MH steps / MH steps of the run.  Refused as bisbm_population_run, and a NULL recipe or one
+ * of all zeros with rounds_per_step > 0 (BISBM_ERR_INVALID_ARG). */
+int bisbm_rounds_population_run(bisbm_handle h, uint32_t n_temps, const float *temps, uint64_t rounds_per_step,
+                                const bisbm_round_recipe *recipe, double *log_ratio_out /* n_temps-1 */,
+                                uint32_t *distinct_out /* n_temps-1 */, double *acc_rate_out /* n_chains, may be NULL */);
 /* The genealogy and the totals since the last reset (ancestor_out: n_chains entries; any pointer may be NULL). */
 int bisbm_population_get(bisbm_handle h, uint32_t *ancestor_out, uint64_t *rounds_out, double *log_ratio_total_out);
 /* ancestor = the identity, rounds = 0, log_ratio_total = 0.  The chains are not touched. */
@@ -569,7 +605,8 @@ int bisbm_conditionals_get_last(bisbm_handle h, uint32_t query_index, uint32_t s
  * Refused, with a message and nothing changed: BISBM_RNG_MT19937_COMPAT and two-byte labels BISBM_ERR_UNSUPPORTED; replica
  * exchange on BISBM_ERR_STATE (as bisbm_anneal); before bisbm_init / bisbm_shuffle BISBM_ERR_STATE; beta NaN, <= 0 or -inf
  * BISBM_ERR_INVALID_ARG.  sweeps = 0 is a no-op that returns BISBM_OK (the outputs are zeroed).
- * Out of scope: a temperature per chain or per rung, heat-bath sweeps inside bisbm_tempering_run / bisbm_population_run,
+ * Inside replica exchange and population annealing the sweeps run through bisbm_tempering_run_rounds /
+ * bisbm_rounds_population_run, under replica exchange at a beta per chain.  Out of scope: greedy polishing per chain,
  * mt19937-compat arithmetic, wide handles.  A move of many nodes at once is bisbm_reshuffle_run below. */
 int bisbm_heatbath_run(bisbm_handle h, uint64_t sweeps, double beta, int stop_when_settled,
                        uint64_t *moved_out /* n_chains, may be NULL */, uint64_t *sweeps_out /* n_chains, may be NULL */);
@@ -628,8 +665,9 @@ int bisbm_heatbath_run(bisbm_handle h, uint64_t sweeps, double beta, int stop_wh
  * allocated at the first call and freed with the handle; an allocation failure is BISBM_ERR_HIP with the size in the message.
  * get_last: the last move of the last call of every chain (r, s: global labels); BISBM_ERR_STATE while a chain has none (no
  * call yet, or its group was formed by a merge since).
- * Out of scope: moves that change Ka or Kb, reshuffles inside bisbm_tempering_run / bisbm_population_run, a temperature per
- * chain, mt19937-compat arithmetic, wide handles, choosing the pair by the state. */
+ * Inside replica exchange and population annealing the moves run through bisbm_tempering_run_rounds /
+ * bisbm_rounds_population_run, under replica exchange at a beta per chain.  Out of scope: moves that change Ka or Kb,
+ * mt19937-compat arithmetic, wide handles, choosing the pair by the state. */
 #define BISBM_RESHUFFLE_NONE 0xffffffffu
 typedef struct bisbm_reshuffle_record {
     uint32_t type;     /* 0: a, 1: b, BISBM_RESHUFFLE_NONE: no pair (everything else 0) */
