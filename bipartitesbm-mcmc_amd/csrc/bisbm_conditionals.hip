@@ -18,6 +18,7 @@
 // add each.  Soft kernel: one workgroup per query, lane <-> block s; a chain's permutation is a bijection, so the lanes of one
 // chain write different columns and every column sees the chains in ascending order.
 #include "bisbm_engine.hpp"
+#include "bisbm_wave_chain.hpp"
 
 using namespace bisbm;
 
@@ -30,7 +31,7 @@ constexpr uint32_t kMaxChunk = 65535;            // chains of one launch: the gr
 __device__ __forceinline__ double nan_row() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 __device__ __forceinline__ double logq_of(const Tables& tab, int n, int k) {
-    return log_q<true>(tab, n, k, (n > 0 && (uint64_t)n < tab.lg_size) ? tab.logtab[n] : 0.);
+    return log_q<true>(tab, n, k, log_n_of(tab, n));
 }
 
 // kLanes: 64 where neither type has more than 64 blocks (one wave: four times as many workgroups fit a CU, and the barriers cost

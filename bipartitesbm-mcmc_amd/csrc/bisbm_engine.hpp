@@ -20,7 +20,8 @@
 //   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block, top-k; kernels and C ABI
 //   bisbm_foldin.hip     fold-in queries: block posterior, recommendations and peers of a node that is not in the graph; kernels and C ABI
 //   bisbm_conditionals.hip  node conditionals: dS of every target block of a node, the conditional and its pooled terms, soft marginals; kernels and C ABI
-//   bisbm_heatbath.hip   heat-bath sweeps and greedy polishing: nodes moved by their conditionals; kernel and C ABI
+//   bisbm_heatbath.hip   heat-bath sweeps and greedy polishing: nodes moved by their conditionals; kernel and C ABI (and the host
+//                        side of the chain state it shares with the reshuffle kernel: bisbm_wave_chain.hpp)
 //   bisbm_reshuffle.hip  pair reshuffles: two blocks' nodes divided afresh in one accepted or rejected move; kernel and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
@@ -669,6 +670,11 @@ void entropy_terms(const bisbm_engine* h, double t[8]);
 // bisbm_anneal on a kernel-running engine with a temperature per chain (T_chain: device pointer, NULL: none); bisbm_anneal.hip
 int anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t duration_steps, uint64_t steps_await,
                   double* acc_rate_out, const float* T_chain);
+// A launch of a wave-chain move kernel (bisbm_wave_chain.hpp) on a kernel-running engine: the fields every such kernel takes
+// (per_rung as below), then where eta goes -- LDS when the kernel's own arrays (own_bytes) and the chain state with eta stay
+// within 40 KiB -- and the LDS bytes to launch with, BISBM_ERR_UNSUPPORTED when they exceed kLdsPerCu; bisbm_heatbath.hip
+void wave_chain_fill(const bisbm_engine* h, double beta, bool per_rung, WaveChainParams& p);
+int wave_chain_plan(bisbm_engine* h, size_t own_bytes, WaveChainParams& p, size_t& lds);
 // `sweeps` heat-bath sweeps of a kernel-running engine on its stream; per_rung: every chain at the beta of its rung
 // (TemperState::d_beta, d_rung) instead of `beta`; sync: wait for the stream before returning; bisbm_heatbath.hip
 int heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_settled, bool per_rung, bool sync);

@@ -4,22 +4,21 @@
 // "Node conditionals": the same f64 operations in the same order as cond_rows_kernel of bisbm_conditionals.hip, restated here
 // because this kernel reads the block state from LDS and keeps the list and the row in LDS arrays of its own.
 //
-// Kernel: one wave per chain, persistent over all sweeps of the call, like the generic sweep_kernel.  The chain's quadrant of m
-// (odd row stride), m_r, n_r, the k_v histogram and eta (when it fits, template parameter EL) live in LDS, loaded at the start
-// and stored at the end; labels stay in HBM.  A sweep is two phases, type a then type b, each walked through TiledOrder in
-// chunks of 64 positions that never straddle the two.  The visited class is an independent set: no step of a phase changes a
-// label that another step of the phase reads, so a chunk's header fetches everything the chunk needs from HBM at once -- lane q
-// the node, row extent and own label of position q, then the first 64 neighbour labels of all 64 rows, eight rows' id loads
-// and eight rows' label gathers in flight together -- and parks the labels in LDS as bytes.  Nothing of it is ever invalidated.
-// A step then touches HBM only for rows longer than 64, the lgamma / log_q tables and the label it writes.
+// Kernel: one wave per chain, persistent over all sweeps of the call, like the generic sweep_kernel.  The chain state in LDS, its
+// load and store-back, the chunk header's parked neighbour labels, the list of the non-zero (t, k_t) and the move are the
+// WaveChain of bisbm_wave_chain.hpp, shared with reshuffle_kernel; this file holds the visit order, the row and the choice.  A
+// sweep is two phases, type a then type b, each walked through TiledOrder in chunks of 64 positions that never straddle the
+// two; the visited class is an independent set.  A step touches HBM only for rows longer than 64, the lgamma / log_q tables
+// and the label it writes.
 //
-// Step: the k_v histogram (integer LDS atomics), the non-zero (t, k_t) compacted in ascending t by ballots with the r side's two
-// table values, then lane <-> target block s (a type with more than 64 blocks is walked in chunks of 64 lanes): per list entry
+// Step: the list, with the r side's two table values per entry in LDS arrays of this kernel's own, then lane <-> target block s
+// (a type with more than 64 blocks is walked in chunks of 64 lanes): per list entry
 // two table gathers and one f64 add in list order, eight entries in flight together, then the three tails, whose gathers are
 // issued before the list is walked.  min, Z and the running sum C_s are sequential in ascending s over k_own terms: the lane of
 // block s holds its value and every lane adds them one v_readlane at a time.  A node that is not free (a one-
 // block type, or alone in its block) is skipped before any of this: its conditional is the point mass on r.
 #include "bisbm_engine.hpp"
+#include "bisbm_wave_chain.hpp"
 
 using namespace bisbm;
 
@@ -27,24 +26,15 @@ namespace bisbm {
 
 namespace {
 
-__device__ __forceinline__ void hb_fence() {  // (one wave: LDS operations execute in issue order; this only stops code motion)
-    __builtin_amdgcn_wave_barrier();
-    __asm__ volatile("" ::: "memory");
-}
-
-// log n from the host table, as the caller of log_q<true> hands it over (bisbm_conditionals.hip: logq_of)
-__device__ __forceinline__ double hb_logn(const Tables& tab, int n) { return (n > 0 && (uint64_t)n < tab.lg_size) ? tab.logtab[n] : 0.; }
-
 template <bool EL>
 __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const uint32_t chain = blockIdx.x;
     if (chain >= p.n_chains) return;
     const uint32_t lane = (uint32_t)lane_id();
-    const uint32_t K = p.ka + p.kb, D = p.maxdeg + 1, S = p.kb | 1u;
     const uint32_t kmax = p.ka > p.kb ? p.ka : p.kb;
 
-    // carve LDS (heatbath_lds_bytes restates the sizes)
+    // this kernel's own arrays, then the chain state
     unsigned char* cur = lds_raw;
     double* s_L1 = (double*)cur;  // lg(m_rt + 1) per list entry
     cur += sizeof(double) * kmax;
@@ -54,40 +44,10 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
     cur += sizeof(double) * kmax;
     double* s_x = (double*)cur;   // w, then P per target
     cur += sizeof(double) * kmax;
-    int32_t* mq = (int32_t*)cur;  // ka * S
-    cur += sizeof(int32_t) * p.ka * S;
-    int32_t* mr = (int32_t*)cur;
-    cur += sizeof(int32_t) * K;
-    int32_t* nr = (int32_t*)cur;
-    cur += sizeof(int32_t) * K;
-    int32_t* hist = (int32_t*)cur;
-    cur += sizeof(int32_t) * kmax;
-    uint32_t* s_t = (uint32_t*)cur;  // the non-zero t, ascending
-    cur += sizeof(uint32_t) * kmax;
-    int32_t* s_kt = (int32_t*)cur;   // their k_t
-    cur += sizeof(int32_t) * kmax;
-    uint8_t* lab_lds = (uint8_t*)cur;  // 64 rows x the labels of their first 64 neighbours
-    cur += kWave * kWave;
-    uint32_t* eta_l = (uint32_t*)cur;  // K * D when EL
-    uint32_t* eta_g = p.eta + (size_t)chain * K * D;
-    auto eta_at = [&](uint32_t idx) -> uint32_t* {
-        if constexpr (EL)
-            return eta_l + idx;
-        else
-            return eta_g + idx;
-    };
-
-    uint8_t* labels = p.labels + (size_t)chain * p.label_stride;
-    int32_t* m_g = p.m + (size_t)chain * p.ka * p.kb;
-    int32_t* mr_g = p.m_r + (size_t)chain * K;
-    int32_t* nr_g = p.n_r + (size_t)chain * K;
-    for (uint32_t i = lane; i < p.ka * p.kb; i += kWave) mq[(i / p.kb) * S + (i % p.kb)] = m_g[i];
-    for (uint32_t i = lane; i < K; i += kWave) {
-        mr[i] = mr_g[i];
-        nr[i] = nr_g[i];
-    }
-    if (EL)
-        for (uint32_t i = lane; i < K * D; i += kWave) eta_l[i] = eta_g[i];
+    WaveChain<EL> wc;
+    wc.load(cur, p, chain);
+    int32_t *const mr = wc.mr, *const nr = wc.nr;  // (the names the row's code below reads the state by)
+    const uint32_t D = wc.D;
     ChainScalars* sc = p.scalars + chain;
     double cum_dS = sc->cum_dS;
     uint64_t sweeps_total = sc->sweeps_total;
@@ -97,16 +57,15 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
     const uint32_t chain_gid = chain_gid_of(p, chain);
     const double beta = chain_beta_of(p, chain);  // (the launch's, or under replica exchange the chain's own)
     uint64_t moved = 0, sweeps_run = 0;
-    for (uint64_t sweep = 0; sweep < p.sweeps; ++sweep) {
+    for (uint64_t sweep = 0; sweep < p.rounds; ++sweep) {
         uint64_t moved_sweep = 0;
         for (uint32_t phase = 0; phase < 2; ++phase) {
             const bool tb = phase != 0;
-            const uint32_t n_cls = tb ? p.nb : p.na, v0 = tb ? p.na : 0u;
-            const uint32_t k_own = tb ? p.kb : p.ka, k_oth = tb ? p.ka : p.kb, own0 = tb ? p.ka : 0u, oth0 = tb ? 0u : p.ka;
+            const TypeView ty = type_view(p, tb);
+            const uint32_t n_cls = ty.n_cls, v0 = ty.v0, k_own = ty.k_own, own0 = ty.own0;
             if (k_own <= 1u) continue;  // (nobody of a one-block type is free)
             TiledOrder order;
             order.init(phx_draw(p.seed, chain_gid, PHX_SWEEP_KEY, 2 * sweeps_total + phase), n_cls);
-            auto Mq = [&](uint32_t i_own, uint32_t j_oth) -> int32_t& { return tb ? mq[j_oth * S + i_own] : mq[i_own * S + j_oth]; };
             for (uint32_t vi0 = 0; vi0 < n_cls; vi0 += kWave) {
                 // ---- chunk header: lane q holds the node, row extent and own label of position vi0 + q ----
                 const uint32_t cnt = n_cls - vi0 < (uint32_t)kWave ? n_cls - vi0 : (uint32_t)kWave;
@@ -115,23 +74,9 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                     v_l = v0 + order(vi0 + lane);
                     beg_l = p.rowptr[v_l];
                     deg_l = p.rowptr[v_l + 1] - beg_l;
-                    r_l = labels[v_l];
+                    r_l = wc.labels[v_l];
                 }
-                // the first 64 neighbour labels of the chunk's rows, eight rows at a time (idle lanes read node 0)
-                hb_fence();
-                for (uint32_t q0 = 0; q0 < cnt; q0 += 8) {
-                    uint32_t id[8], lb[8];
-#pragma unroll
-                    for (uint32_t j = 0; j < 8; ++j) {
-                        const uint32_t b0 = readlane(beg_l, q0 + j), d0 = readlane(deg_l, q0 + j);  // (rows past cnt: deg 0)
-                        id[j] = lane < d0 ? p.col[b0 + lane] : 0u;
-                    }
-#pragma unroll
-                    for (uint32_t j = 0; j < 8; ++j) lb[j] = labels[id[j]];
-#pragma unroll
-                    for (uint32_t j = 0; j < 8; ++j) lab_lds[(q0 + j) * kWave + lane] = (uint8_t)lb[j];
-                }
-                hb_fence();
+                wc.park_rows(cnt, beg_l, deg_l);
 
                 for (uint32_t q = 0; q < cnt; ++q) {
                     const uint32_t v = readlane(v_l, q), beg = readlane(beg_l, q), deg = readlane(deg_l, q);
@@ -139,38 +84,16 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                     if (r_loc >= k_own) continue;  // (a valid label: never)
                     const int n0r = nr[r];
                     if (n0r <= 1) continue;  // not free: the node stays, and no draw is used
-                    // 1. k_v: the histogram of the neighbours' labels
-                    for (uint32_t t = lane; t < k_oth; t += kWave) hist[t] = 0;
-                    hb_fence();
-                    if (lane < deg) {
-                        const uint32_t t = (uint32_t)lab_lds[q * kWave + lane] - oth0;
-                        if (t < k_oth) atomicAdd(&hist[t], 1);
-                    }
-                    for (uint32_t j = kWave + lane; j < deg; j += kWave) {  // rows longer than one wave
-                        const uint32_t t = (uint32_t)labels[p.col[beg + j]] - oth0;
-                        if (t < k_oth) atomicAdd(&hist[t], 1);
-                    }
-                    hb_fence();
-                    // 2. the non-zero (t, k_t) in ascending t, with the r side's two table values
-                    uint32_t nnz = 0;
-                    for (uint32_t c0 = 0; c0 < k_oth; c0 += kWave) {
-                        const uint32_t t = c0 + lane;
-                        const int kt = t < k_oth ? hist[t] : 0;
-                        const unsigned long long bal = __ballot(kt != 0);
-                        if (kt != 0) {
-                            const uint32_t pos = nnz + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-                            const int32_t m_rt = Mq(r_loc, t);
-                            s_t[pos] = t, s_kt[pos] = kt;
-                            s_L1[pos] = lgamma_fast(tab, (long long)m_rt + 1);
-                            s_L3[pos] = lgamma_fast(tab, (long long)m_rt - kt + 1);
-                        }
-                        nnz += (uint32_t)__popcll(bal);
-                    }
-                    hb_fence();
+                    // 1., 2. k_v and the non-zero (t, k_t) in ascending t, with the r side's two table values
+                    const uint32_t nnz = wc.neighbour_list(q, beg, deg, ty, [&](uint32_t pos, uint32_t t, int kt) {
+                        const int32_t m_rt = wc.M(tb, r_loc, t);
+                        s_L1[pos] = lgamma_fast(tab, (long long)m_rt + 1);
+                        s_L3[pos] = lgamma_fast(tab, (long long)m_rt - kt + 1);
+                    });
                     // 3. dS of target s = tid (steps 1 of "Node conditionals")
                     const int ideg = (int)deg;
                     const int m0r = mr[r];
-                    const long long eta_r = *eta_at(r * D + deg);
+                    const long long eta_r = *wc.eta_at(r * D + deg);
                     // the r side of the tails is the same for every target
                     const double tail1_r = lgamma_fast(tab, (long long)m0r - ideg + 1) - lgamma_fast(tab, (long long)m0r + 1);
                     const double tail2_r = lgamma_fast(tab, eta_r + 1) - lgamma_fast(tab, eta_r);
@@ -180,11 +103,11 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                         const int m0s = mr[s], n0s = nr[s];
                         // every table gather of the tails is issued before the list is walked: the s side's four lgamma values
                         // and the log n of the three log_q evaluations below
-                        const long long eta_s = *eta_at(s * D + deg);
+                        const long long eta_s = *wc.eta_at(s * D + deg);
                         const double lg_s1 = lgamma_fast(tab, (long long)m0s + ideg + 1), lg_s0 = lgamma_fast(tab, (long long)m0s + 1);
                         const double lg_e1 = lgamma_fast(tab, eta_s + 1), lg_e2 = lgamma_fast(tab, eta_s + 2);
                         const int qn_r = (lane & 1u) ? m0r : m0r - ideg, qk_r = (lane & 1u) ? n0r : n0r - 1;
-                        const double ln_s1 = hb_logn(tab, m0s + ideg), ln_s0 = hb_logn(tab, m0s), ln_r = hb_logn(tab, qn_r);
+                        const double ln_s1 = log_n_of(tab, m0s + ideg), ln_s0 = log_n_of(tab, m0s), ln_r = log_n_of(tab, qn_r);
                         double acc = 0.;
                         // eight list entries at a time: their reads of m and the sixteen table gathers are in flight together;
                         // the adds keep the list order (past the end of the list the last entry is read again and not added)
@@ -192,11 +115,11 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                             int32_t m_st[8];
                             double a[8], b[8];
 #pragma unroll
-                            for (uint32_t j = 0; j < 8; ++j) m_st[j] = Mq(tid < k_own ? tid : r_loc, s_t[i + j < nnz ? i + j : nnz - 1u]);
+                            for (uint32_t j = 0; j < 8; ++j) m_st[j] = wc.M(tb, tid < k_own ? tid : r_loc, wc.s_t[i + j < nnz ? i + j : nnz - 1u]);
 #pragma unroll
                             for (uint32_t j = 0; j < 8; ++j) {
                                 a[j] = lgamma_fast(tab, (long long)m_st[j] + 1);
-                                b[j] = lgamma_fast(tab, (long long)m_st[j] + s_kt[i + j < nnz ? i + j : nnz - 1u] + 1);
+                                b[j] = lgamma_fast(tab, (long long)m_st[j] + wc.s_kt[i + j < nnz ? i + j : nnz - 1u] + 1);
                             }
 #pragma unroll
                             for (uint32_t j = 0; j < 8; ++j)
@@ -222,7 +145,7 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                         const double tail3 = (readlane(lq_r, 0u) - readlane(lq_r, 1u)) + (lq_s1 - lq_s0);
                         if (tid < k_own) s_dS[tid] = tid == r_loc ? 0. : ((acc + tail1) + tail2) + tail3;
                     }
-                    hb_fence();
+                    wave_fence();
                     // The passes that are sequential in ascending s by definition -- dS_min, Z, C_s -- run on registers: the lane of
                     // block s holds its value, and every lane adds the values one v_readlane at a time (64 blocks per trip).
                     // dS_min (the 0 at r included)
@@ -260,7 +183,7 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                             }
                             for (uint32_t s = 0; s < cn; ++s) Z = Z + readlane(w, s);
                         }
-                        hb_fence();
+                        wave_fence();
                         // ... then P = w / Z and C_s = P_0 + ... + P_s: the first s with u < C_s, else the largest s with P_s > 0
                         const uint64_t pos = (uint64_t)v0 + vi0 + q;  // position in the sweep
                         const U4 A = phx_draw(p.seed, chain_gid, PHX_HEATBATH, sweeps_total * (uint64_t)p.n + pos);
@@ -288,31 +211,9 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                     // 5. apply_mcmc_moves, as mh_step does
                     const double dS_new = s_dS[s_new];
                     const uint32_t s_glob = own0 + s_new;
-                    hb_fence();  // all lanes have read nr / mr / eta before lane 0 rewrites them
-                    // eta in HBM (EL = false) and the label are written by lane 0 with a vector store and atomics that return
-                    // nothing, and read by all lanes of later steps with plain loads; hb_fence only stops code motion.  This
-                    // rests on a property of the hardware: the vector memory operations of ONE wave go through one L1 and
-                    // reach the L2 in issue order, so a load issued after a store or atomic of the same wave to the same
-                    // address sees it (the generic sweep_kernel relies on the same for its labels and its eta in HBM).  No other
-                    // wave reads or writes a chain's arrays during the call.
-                    if (lane == 0) {
-                        atomicSub(&nr[r], 1);
-                        atomicAdd(&nr[s_glob], 1);
-                        atomicSub(eta_at(r * D + deg), 1u);
-                        atomicAdd(eta_at(s_glob * D + deg), 1u);
-                        atomicSub(&mr[r], (int)deg);
-                        atomicAdd(&mr[s_glob], (int)deg);
-                        labels[v] = (uint8_t)s_glob;
-                    }
-                    for (uint32_t i = lane; i < nnz; i += kWave) {
-                        const uint32_t t = s_t[i];
-                        const int k = s_kt[i];
-                        atomicSub(&Mq(r_loc, t), k);
-                        atomicAdd(&Mq(s_new, t), k);
-                    }
+                    wc.apply_move(v, deg, r, s_glob, r_loc, s_new, tb, nnz);
                     cum_dS = cum_dS + dS_new;
                     ++moved_sweep;
-                    hb_fence();
                 }
             }
             __threadfence_block();  // the labels this phase wrote are read by the next phase's headers
@@ -323,15 +224,7 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
         if (p.stop_when_settled && moved_sweep == 0) break;
     }
 
-    // store the chain back
-    __syncthreads();
-    for (uint32_t i = lane; i < p.ka * p.kb; i += kWave) m_g[i] = mq[(i / p.kb) * S + (i % p.kb)];
-    for (uint32_t i = lane; i < K; i += kWave) {
-        mr_g[i] = mr[i];
-        nr_g[i] = nr[i];
-    }
-    if (EL)
-        for (uint32_t i = lane; i < K * D; i += kWave) eta_g[i] = eta_l[i];
+    wc.store();
     if (lane == 0) {
         sc->cum_dS = cum_dS;
         sc->sweeps_total = sweeps_total;
@@ -342,27 +235,9 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
 
 }  // namespace
 
-size_t heatbath_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds) {
-    const size_t K = (size_t)ka + kb, S = kb | 1u, kmax = std::max(ka, kb);
-    size_t lds = sizeof(double) * 4 * kmax + sizeof(int32_t) * ((size_t)ka * S + 2 * K + 3 * kmax) + (size_t)kWave * kWave;
-    if (eta_in_lds) lds += sizeof(uint32_t) * K * ((size_t)maxdeg + 1);
-    return (lds + 15) & ~(size_t)15;
-}
-
-hipError_t launch_heatbath(const HeatbathParams& p, size_t lds_bytes, hipStream_t stream) {
-    if (p.n_chains == 0 || p.sweeps == 0) return hipSuccess;
-    auto kern = p.eta_in_lds ? heatbath_kernel<true> : heatbath_kernel<false>;
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(p.n_chains), dim3(kWave), lds_bytes, stream, p);
-    return hipGetLastError();
-}
-
 }  // namespace bisbm
 
-int bisbm::heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_settled, bool per_rung, bool sync) {
-    HIPCHK(h, hipSetDevice(h->device));
-    HeatbathParams p{};
+void bisbm::wave_chain_fill(const bisbm_engine* h, double beta, bool per_rung, WaveChainParams& p) {
     p.rowptr = h->d_rowptr, p.col = h->d_col;
     p.n = (uint32_t)h->n, p.na = (uint32_t)h->na, p.nb = (uint32_t)h->nb;
     p.ka = h->ka, p.kb = h->kb, p.maxdeg = h->maxdeg;
@@ -372,17 +247,29 @@ int bisbm::heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int st
     p.scalars = h->d_scalars;
     p.lgamma_tab = h->d_lgamma, p.lgamma_size = h->tab->lg.size(), p.q_tab = h->d_q, p.q_stride = h->q_stride, p.log_tab = h->d_logtab;
     p.seed = h->seed;
-    p.sweeps = sweeps;
-    p.greedy = !per_rung && std::isinf(beta) ? 1u : 0u;
-    p.beta = p.greedy ? 0. : beta;
+    p.beta = beta;
     if (per_rung) p.beta_rung = h->temper.d_beta.get(), p.rung = h->temper.d_rung.get();
-    p.stop_when_settled = stop_when_settled ? 1u : 0u;
+}
+
+int bisbm::wave_chain_plan(bisbm_engine* h, size_t own_bytes, WaveChainParams& p, size_t& lds) {
     // eta goes to LDS when that still leaves room for four chains per CU, as in the generic sweep kernel's plan
-    p.eta_in_lds = heatbath_lds_bytes(h->ka, h->kb, h->maxdeg, true) <= 40 * 1024 ? 1 : 0;
-    const size_t lds = heatbath_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0);
+    p.eta_in_lds = own_bytes + wave_chain_lds_bytes(h->ka, h->kb, h->maxdeg, true) <= 40 * 1024 ? 1 : 0;
+    lds = own_bytes + wave_chain_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0);
     if (lds > kLdsPerCu) return fail(h, BISBM_ERR_UNSUPPORTED, "chain state needs %zu B of LDS (> 160 KiB)", lds);
+    return BISBM_OK;
+}
+
+int bisbm::heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when_settled, bool per_rung, bool sync) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HeatbathParams p{};
+    p.rounds = sweeps;
+    p.greedy = !per_rung && std::isinf(beta) ? 1u : 0u;
+    wave_chain_fill(h, p.greedy ? 0. : beta, per_rung, p);
+    p.stop_when_settled = stop_when_settled ? 1u : 0u;
+    size_t lds;  // (the four double[kmax] arrays of the kernel's own: a multiple of 16 bytes, as the rounded chain state is)
+    if (int rc = wave_chain_plan(h, 4 * sizeof(double) * std::max(h->ka, h->kb), p, lds)) return rc;
     h->ent_prev_valid = false;  // (the block state moves)
-    HIPCHK(h, launch_heatbath(p, lds, h->stream));
+    HIPCHK(h, launch_wave_chain(heatbath_kernel<true>, heatbath_kernel<false>, p, lds, h->stream));
     if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
 }

@@ -390,8 +390,11 @@ constexpr uint32_t PHX_EXCHANGE = 7;  // replica exchange: idx = round * L + low
 constexpr uint32_t PHX_RESAMPLE = 8;  // population annealing: idx = resampling step, chain = the handle's first global id
 constexpr uint32_t PHX_HEATBATH = 9;  // heat-bath sweeps: idx = sweeps_total * n + position in the sweep, chain = the chain's global id
 
-// Heat-bath sweeps and greedy polishing (bisbm_heatbath.hip): `sweeps` sweeps of every chain of one engine, one wave per chain.
-struct HeatbathParams {
+// What a launch of a "one wave owns one chain" move kernel (bisbm_wave_chain.hpp) takes, whatever the move.  The ORDER of the
+// fields is load-bearing: it fixes the offsets in the kernels' argument block, and with them the compiler's scalar register
+// allocation and spills (eta_in_lds in the padding after q_stride and rounds before beta keep heat-bath's offsets and figures;
+// profiles/wave_chain_state.md).  After inserting or moving a field compare libbisbm_hip.resources.json with that table.
+struct WaveChainParams {
     const uint32_t* rowptr;
     const uint32_t* col;
     uint32_t n, na, nb, ka, kb, maxdeg;
@@ -403,56 +406,44 @@ struct HeatbathParams {
     int32_t* m_r;                // [chain][K]
     int32_t* n_r;                // [chain][K]
     uint32_t* eta;               // [chain][K*(maxdeg+1)]
-    ChainScalars* scalars;       // cum_dS, sweeps_total advance; last_accepted = moves, last_sweeps = sweeps run
+    ChainScalars* scalars;       // cum_dS advances, and what the kernel counts
     const double* lgamma_tab;
     uint64_t lgamma_size;
     const double* q_tab;
     uint32_t q_stride;
+    int eta_in_lds;              // (host: which instantiation is launched)
     const double* log_tab;
     uint64_t seed;
-    uint64_t sweeps;
-    double beta;                 // finite, > 0 (unused when greedy)
-    // replica exchange (bisbm_tempering_run_rounds): a beta per chain of the launch (never greedy) -- chain c runs at beta_rung[rung[c]], the
-    // host's quotient 1.0 / (double)T of its rung's temperature (TemperState::d_beta, d_rung); NULL: `beta` for every chain
-    const double* beta_rung;
-    const uint32_t* rung;
-    uint32_t greedy;             // beta = +inf: the lowest argmin of dS, only strictly downhill, no draw
-    uint32_t stop_when_settled;  // a chain stops after the first sweep that moved nothing
-    int eta_in_lds;
-};
-size_t heatbath_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds);
-hipError_t launch_heatbath(const HeatbathParams& p, size_t lds_bytes, hipStream_t stream);
-
-constexpr uint32_t PHX_RESHUFFLE = 10;  // pair reshuffles: idx = (reshuffles_total << 32) | k, chain = the chain's global id
-
-// Pair reshuffles (bisbm_reshuffle.hip): `moves` moves of every chain of one engine, one wave per chain.
-struct ReshuffleParams {
-    const uint32_t* rowptr;
-    const uint32_t* col;
-    uint32_t n, na, nb, ka, kb, maxdeg;
-    uint32_t n_chains, first_chain_id;
-    const uint32_t* chain_gids;  // see SweepParams
-    uint8_t* labels;             // byte labels
-    size_t label_stride;
-    int32_t* m;                  // [chain][ka*kb]
-    int32_t* m_r;                // [chain][K]
-    int32_t* n_r;                // [chain][K]
-    uint32_t* eta;               // [chain][K*(maxdeg+1)]
-    ChainScalars* scalars;       // cum_dS and reshuffles_total advance; nothing else is written
-    const double* lgamma_tab;
-    uint64_t lgamma_size;
-    const double* q_tab;
-    uint32_t q_stride;
-    const double* log_tab;
-    uint64_t seed;
-    uint64_t moves;
-    uint32_t scans;
+    uint64_t rounds;             // sweeps or moves of the call
     double beta;                 // finite, > 0
     // replica exchange (bisbm_tempering_run_rounds): a beta per chain of the launch -- chain c runs at beta_rung[rung[c]], the
     // host's quotient 1.0 / (double)T of its rung's temperature (TemperState::d_beta, d_rung); NULL: `beta` for every chain
     const double* beta_rung;
     const uint32_t* rung;
-    int eta_in_lds;
+};
+// The chain state in LDS: the quadrant of m with an odd row stride, m_r, n_r, the k_v histogram and the list's t and k_t (4
+// bytes an entry), the parked neighbour labels of a chunk, eta when it fits -- WaveChain::load carves exactly these.
+constexpr uint32_t kParkedLabelBytes = kWave * kWave;
+__host__ __device__ constexpr uint32_t wave_chain_stride(uint32_t kb) { return kb | 1u; }
+inline size_t wave_chain_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds) {
+    const size_t K = (size_t)ka + kb, kmax = ka > kb ? ka : kb;
+    size_t lds = sizeof(int32_t) * ((size_t)ka * wave_chain_stride(kb) + 2 * K + 3 * kmax) + kParkedLabelBytes;
+    if (eta_in_lds) lds += sizeof(uint32_t) * K * ((size_t)maxdeg + 1);
+    return (lds + 15) & ~(size_t)15;
+}
+
+// Heat-bath sweeps and greedy polishing (bisbm_heatbath.hip): `rounds` sweeps of every chain of one engine.  Of the scalars
+// sweeps_total advances too; last_accepted = moves, last_sweeps = sweeps run.  `beta` is unused when greedy (never per rung).
+struct HeatbathParams : WaveChainParams {
+    uint32_t greedy;             // beta = +inf: the lowest argmin of dS, only strictly downhill, no draw
+    uint32_t stop_when_settled;  // a chain stops after the first sweep that moved nothing
+};
+
+constexpr uint32_t PHX_RESHUFFLE = 10;  // pair reshuffles: idx = (reshuffles_total << 32) | k, chain = the chain's global id
+
+// Pair reshuffles (bisbm_reshuffle.hip): `rounds` moves of every chain of one engine.  Of the scalars reshuffles_total advances too.
+struct ReshuffleParams : WaveChainParams {
+    uint32_t scans;
     // per-chain scratch, nmax = max(na, nb) entries each: the member ids, their original labels, their launch labels
     uint32_t* member;            // [chain][nmax]
     uint8_t* orig;               // [chain][nmax]
@@ -460,8 +451,6 @@ struct ReshuffleParams {
     bisbm_reshuffle_record* record;  // [chain] the last move of the call
     unsigned long long* accepted;    // [chain] accepted moves of the call
 };
-size_t reshuffle_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds);
-hipError_t launch_reshuffle(const ReshuffleParams& p, size_t lds_bytes, hipStream_t stream);
 hipError_t launch_exp_probe(const double* x, size_t count, double* out, hipStream_t stream);
 
 hipError_t launch_split_rank(const SplitParams& p, hipStream_t stream);

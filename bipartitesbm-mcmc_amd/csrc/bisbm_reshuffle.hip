@@ -4,14 +4,14 @@
 // operations in the same order as cond_rows_kernel of bisbm_conditionals.hip and heatbath_kernel of bisbm_heatbath.hip, restated
 // here because this kernel evaluates ONE target per step.
 //
-// Kernel: one wave per chain, persistent over all moves of the call.  The block state sits in LDS, laid out as
-// heatbath_kernel's (the quadrant of m with an odd row stride, m_r, n_r, the k_v histogram, eta when it fits: template
-// parameter EL); labels stay in HBM.  A move collects its members from the type's label row by ballot compaction into the
+// Kernel: one wave per chain, persistent over all moves of the call.  The chain state in LDS, its load and store-back, the
+// chunk header's parked neighbour labels, the list of the non-zero (t, k_t) and the move are the WaveChain of
+// bisbm_wave_chain.hpp, shared with heatbath_kernel; this file holds the pair, the passes and the one-target dS.  A move
+// collects its members from the type's label row by ballot compaction into the
 // chain's scratch (member id, original label, launch label), then runs its passes -- transit to the launch labels, the launch
 // scans, the reverse pass, transit to L, the forward pass, transit back after a rejection -- through ONE copy of the pass loop,
 // told apart by `kind`.  The members are one type, hence an independent set and their neighbours' labels never change during a
-// move: heat-bath's chunk header applies unchanged (lane q takes the node, row extent and label of member q, the first 64
-// neighbour labels of 64 rows are parked in LDS with nothing ever invalidated).
+// move, which is what the shared chunk header asks for (lane q takes the node, row extent and label of member q).
 //
 // Step: a step has one non-trivial target, so the lanes are mapped to the non-zero (t, k_t) of the list instead of to targets:
 // lane i reads m_ct and m_ot and issues its four table gathers, 64 list entries in flight together, then the terms are added
@@ -19,20 +19,13 @@
 // lanes 0 .. 3 through one copy of log_q's code; the eight lgamma values of tail1 and tail2 are issued before the list is
 // walked.  A transit step builds the list and applies the move, and reads no table.
 #include "bisbm_engine.hpp"
+#include "bisbm_wave_chain.hpp"
 
 using namespace bisbm;
 
 namespace bisbm {
 
 namespace {
-
-__device__ __forceinline__ void rs_fence() {  // (one wave: LDS operations execute in issue order; this only stops code motion)
-    __builtin_amdgcn_wave_barrier();
-    __asm__ volatile("" ::: "memory");
-}
-
-// log n from the host table, as the caller of log_q<true> hands it over (bisbm_conditionals.hip: logq_of)
-__device__ __forceinline__ double rs_logn(const Tables& tab, int n) { return (n > 0 && (uint64_t)n < tab.lg_size) ? tab.logtab[n] : 0.; }
 
 enum : uint32_t { RS_TRANSIT = 0, RS_FREE = 1, RS_FORCED = 2 };
 
@@ -42,48 +35,16 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
     const uint32_t chain = blockIdx.x;
     if (chain >= p.n_chains) return;
     const uint32_t lane = (uint32_t)lane_id();
-    const uint32_t K = p.ka + p.kb, D = p.maxdeg + 1, S = p.kb | 1u;
-    const uint32_t kmax = p.ka > p.kb ? p.ka : p.kb, nmax = p.na > p.nb ? p.na : p.nb;
+    const uint32_t nmax = p.na > p.nb ? p.na : p.nb;
 
-    // carve LDS (reshuffle_lds_bytes restates the sizes)
-    unsigned char* cur = lds_raw;
-    int32_t* mq = (int32_t*)cur;  // ka * S
-    cur += sizeof(int32_t) * p.ka * S;
-    int32_t* mr = (int32_t*)cur;
-    cur += sizeof(int32_t) * K;
-    int32_t* nr = (int32_t*)cur;
-    cur += sizeof(int32_t) * K;
-    int32_t* hist = (int32_t*)cur;
-    cur += sizeof(int32_t) * kmax;
-    uint32_t* s_t = (uint32_t*)cur;  // the non-zero t, ascending
-    cur += sizeof(uint32_t) * kmax;
-    int32_t* s_kt = (int32_t*)cur;   // their k_t
-    cur += sizeof(int32_t) * kmax;
-    uint8_t* lab_lds = (uint8_t*)cur;  // 64 rows x the labels of their first 64 neighbours
-    cur += kWave * kWave;
-    uint32_t* eta_l = (uint32_t*)cur;  // K * D when EL
-    uint32_t* eta_g = p.eta + (size_t)chain * K * D;
-    auto eta_at = [&](uint32_t idx) -> uint32_t* {
-        if constexpr (EL)
-            return eta_l + idx;
-        else
-            return eta_g + idx;
-    };
-
-    uint8_t* labels = p.labels + (size_t)chain * p.label_stride;
-    int32_t* m_g = p.m + (size_t)chain * p.ka * p.kb;
-    int32_t* mr_g = p.m_r + (size_t)chain * K;
-    int32_t* nr_g = p.n_r + (size_t)chain * K;
+    WaveChain<EL> wc;
+    wc.load(lds_raw, p, chain);
+    int32_t *const mr = wc.mr, *const nr = wc.nr;  // (the names the dS code below reads the state by)
+    const uint32_t D = wc.D;
+    uint8_t* const labels = wc.labels;
     uint32_t* member = p.member + (size_t)chain * nmax;
     uint8_t* orig = p.orig + (size_t)chain * nmax;
     uint8_t* launch = p.launch + (size_t)chain * nmax;
-    for (uint32_t i = lane; i < p.ka * p.kb; i += kWave) mq[(i / p.kb) * S + (i % p.kb)] = m_g[i];
-    for (uint32_t i = lane; i < K; i += kWave) {
-        mr[i] = mr_g[i];
-        nr[i] = nr_g[i];
-    }
-    if (EL)
-        for (uint32_t i = lane; i < K * D; i += kWave) eta_l[i] = eta_g[i];
     ChainScalars* sc = p.scalars + chain;
     double cum_dS = sc->cum_dS;
     uint32_t total = sc->reshuffles_total;
@@ -97,7 +58,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
     bisbm_reshuffle_record rec{};
     rec.type = BISBM_RESHUFFLE_NONE;
 
-    for (uint64_t move = 0; move < p.moves; ++move, ++total) {
+    for (uint64_t move = 0; move < p.rounds; ++move, ++total) {
         const uint64_t idx0 = (uint64_t)total << 32;
         rec = bisbm_reshuffle_record{};
         rec.type = BISBM_RESHUFFLE_NONE;
@@ -106,8 +67,8 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
         uint32_t pi = readlane((uint32_t)(((uint64_t)phx_draw(p.seed, chain_gid, PHX_RESHUFFLE, idx0).x * n_pairs) >> 32), 0u);
         const bool tb = pi >= pairs_a;
         if (tb) pi -= pairs_a;
-        const uint32_t n_cls = tb ? p.nb : p.na, v0 = tb ? p.na : 0u;
-        const uint32_t k_own = tb ? p.kb : p.ka, k_oth = tb ? p.ka : p.kb, own0 = tb ? p.ka : 0u, oth0 = tb ? 0u : p.ka;
+        const TypeView ty = type_view(p, tb);
+        const uint32_t n_cls = ty.n_cls, v0 = ty.v0, k_own = ty.k_own, own0 = ty.own0;
         uint32_t r_loc = 0;
         while (pi >= k_own - 1u - r_loc) {
             pi -= k_own - 1u - r_loc;
@@ -115,7 +76,6 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
         }
         const uint32_t s_loc = r_loc + 1u + pi;
         const uint32_t rg = own0 + r_loc, sg = own0 + s_loc;  // global labels
-        auto Mq = [&](uint32_t i_own, uint32_t j_oth) -> int32_t& { return tb ? mq[j_oth * S + i_own] : mq[i_own * S + j_oth]; };
         const U4 acc_draw = phx_draw(p.seed, chain_gid, PHX_RESHUFFLE, idx0 | 1u);
         const double u_acc = u53(acc_draw.x, acc_draw.y);
 
@@ -151,13 +111,13 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
             got_r = got_r || __ballot(i < M && bit == 0) != 0;
         }
         __threadfence_block();
-        rs_fence();
+        wave_fence();
         if (lane == 0) {
             if (!got_r) launch[0] = (uint8_t)rg;
             if (!got_s) launch[M - 1u] = (uint8_t)sg;
         }
         __threadfence_block();  // the scratch this wave wrote is read by other lanes of it in the headers below
-        rs_fence();
+        wave_fence();
 
         // the passes: stage 0 transit to the launch labels; 1 .. scans the launch scans; scans + 1 the reverse pass; scans + 2
         // transit to L; scans + 3 the forward pass; scans + 4 transit back to the original labels after a rejection
@@ -176,7 +136,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
                 // L = the labels the launch scans ended at
                 for (uint32_t i = lane; i < M; i += kWave) launch[i] = labels[member[i]];
                 __threadfence_block();
-                rs_fence();
+                wave_fence();
                 kind = RS_FORCED, tgt = orig;
                 q_m = 0.5, q_e = 1, dsum = 0.;
             } else if (stage == (uint64_t)p.scans + 2u) {
@@ -211,21 +171,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
                     c_l = labels[v_l];
                     want_l = tgt[i0 + lane];
                 }
-                // the first 64 neighbour labels of the chunk's rows, eight rows at a time (idle lanes read node 0)
-                rs_fence();
-                for (uint32_t q0 = 0; q0 < cnt; q0 += 8) {
-                    uint32_t id[8], lb[8];
-#pragma unroll
-                    for (uint32_t j = 0; j < 8; ++j) {
-                        const uint32_t b0 = readlane(beg_l, q0 + j), d0 = readlane(deg_l, q0 + j);  // (rows past cnt: deg 0)
-                        id[j] = lane < d0 ? p.col[b0 + lane] : 0u;
-                    }
-#pragma unroll
-                    for (uint32_t j = 0; j < 8; ++j) lb[j] = labels[id[j]];
-#pragma unroll
-                    for (uint32_t j = 0; j < 8; ++j) lab_lds[(q0 + j) * kWave + lane] = (uint8_t)lb[j];
-                }
-                rs_fence();
+                wc.park_rows(cnt, beg_l, deg_l);
 
                 for (uint32_t q = 0; q < cnt; ++q) {
                     const uint32_t v = readlane(v_l, q), beg = readlane(beg_l, q), deg = readlane(deg_l, q);
@@ -247,37 +193,13 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
                         tables = true;
                     }
                     if (!tables && to == c) continue;
-                    // k_v: the histogram of the neighbours' labels
-                    for (uint32_t t = lane; t < k_oth; t += kWave) hist[t] = 0;
-                    rs_fence();
-                    if (lane < deg) {
-                        const uint32_t t = (uint32_t)lab_lds[q * kWave + lane] - oth0;
-                        if (t < k_oth) atomicAdd(&hist[t], 1);
-                    }
-                    for (uint32_t j = kWave + lane; j < deg; j += kWave) {  // rows longer than one wave
-                        const uint32_t t = (uint32_t)labels[p.col[beg + j]] - oth0;
-                        if (t < k_oth) atomicAdd(&hist[t], 1);
-                    }
-                    rs_fence();
-                    // the non-zero (t, k_t) in ascending t
-                    uint32_t nnz = 0;
-                    for (uint32_t c0 = 0; c0 < k_oth; c0 += kWave) {
-                        const uint32_t t = c0 + lane;
-                        const int kt = t < k_oth ? hist[t] : 0;
-                        const unsigned long long bal = __ballot(kt != 0);
-                        if (kt != 0) {
-                            const uint32_t pos = nnz + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-                            s_t[pos] = t, s_kt[pos] = kt;
-                        }
-                        nnz += (uint32_t)__popcll(bal);
-                    }
-                    rs_fence();
+                    const uint32_t nnz = wc.neighbour_list(q, beg, deg, ty, [](uint32_t, uint32_t, int) {});
                     double dS_o = 0.;
                     if (tables) {
                         // dS_o (step 1 of "Node conditionals" with r = c, s = o)
                         const int ideg = (int)deg;
                         const int m0c = mr[c], m0o = mr[o], n0o = nr[o];
-                        const long long eta_c = *eta_at(c * D + deg), eta_o = *eta_at(o * D + deg);
+                        const long long eta_c = *wc.eta_at(c * D + deg), eta_o = *wc.eta_at(o * D + deg);
                         // every table gather of the tails is issued before the list is walked
                         const double lg_c1 = lgamma_fast(tab, (long long)m0c - ideg + 1), lg_c0 = lgamma_fast(tab, (long long)m0c + 1);
                         const double lg_o1 = lgamma_fast(tab, (long long)m0o + ideg + 1), lg_o0 = lgamma_fast(tab, (long long)m0o + 1);
@@ -287,14 +209,14 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
                         const uint32_t sel = lane & 3u;
                         const int qn = sel == 0 ? m0c - ideg : sel == 1 ? m0c : sel == 2 ? m0o + ideg : m0o;
                         const int qk = sel == 0 ? n0c - 1 : sel == 1 ? n0c : sel == 2 ? n0o + 1 : n0o;
-                        const double ln_q = rs_logn(tab, qn);
+                        const double ln_q = log_n_of(tab, qn);
                         double acc = 0.;
                         for (uint32_t l0 = 0; l0 < nnz; l0 += kWave) {
                             const uint32_t cn = nnz - l0 < (uint32_t)kWave ? nnz - l0 : (uint32_t)kWave;
                             const uint32_t li = l0 + (lane < cn ? lane : cn - 1u);  // (idle lanes read the last entry again)
-                            const uint32_t t = s_t[li];
-                            const int kt = s_kt[li];
-                            const int32_t m_ct = Mq(c_loc, t), m_ot = Mq(o_loc, t);
+                            const uint32_t t = wc.s_t[li];
+                            const int kt = wc.s_kt[li];
+                            const int32_t m_ct = wc.M(tb, c_loc, t), m_ot = wc.M(tb, o_loc, t);
                             const double a1 = lgamma_fast(tab, (long long)m_ct + 1), a2 = lgamma_fast(tab, (long long)m_ot + 1);
                             const double a3 = lgamma_fast(tab, (long long)m_ct - kt + 1), a4 = lgamma_fast(tab, (long long)m_ot + kt + 1);
                             const double term = (a1 + a2) - (a3 + a4);
@@ -330,25 +252,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
                         to = readlane(to, 0u);  // (the same in every lane; this tells the compiler)
                         if (to == c) continue;
                     }
-                    // apply the move c -> o, as a heat-bath move (lane 0 writes eta in HBM and the label; see heatbath_kernel on
-                    // why later loads of this wave see them)
-                    rs_fence();  // all lanes have read nr / mr / eta before lane 0 rewrites them
-                    if (lane == 0) {
-                        atomicSub(&nr[c], 1);
-                        atomicAdd(&nr[o], 1);
-                        atomicSub(eta_at(c * D + deg), 1u);
-                        atomicAdd(eta_at(o * D + deg), 1u);
-                        atomicSub(&mr[c], (int)deg);
-                        atomicAdd(&mr[o], (int)deg);
-                        labels[v] = (uint8_t)o;
-                    }
-                    for (uint32_t i = lane; i < nnz; i += kWave) {
-                        const uint32_t t = s_t[i];
-                        const int k = s_kt[i];
-                        atomicSub(&Mq(c_loc, t), k);
-                        atomicAdd(&Mq(o_loc, t), k);
-                    }
-                    rs_fence();
+                    wc.apply_move(v, deg, c, o, c_loc, o_loc, tb, nnz);
                 }
             }
             __threadfence_block();  // the labels this pass wrote are read by the next pass's headers
@@ -360,15 +264,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
         n_accepted += accepted ? 1u : 0u;
     }
 
-    // store the chain back
-    __syncthreads();
-    for (uint32_t i = lane; i < p.ka * p.kb; i += kWave) m_g[i] = mq[(i / p.kb) * S + (i % p.kb)];
-    for (uint32_t i = lane; i < K; i += kWave) {
-        mr_g[i] = mr[i];
-        nr_g[i] = nr[i];
-    }
-    if (EL)
-        for (uint32_t i = lane; i < K * D; i += kWave) eta_g[i] = eta_l[i];
+    wc.store();
     if (lane == 0) {
         sc->cum_dS = cum_dS;
         sc->reshuffles_total = total;
@@ -383,22 +279,6 @@ __global__ void exp_probe_kernel(const double* x, size_t count, double* out) {
 }
 
 }  // namespace
-
-size_t reshuffle_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds) {
-    const size_t K = (size_t)ka + kb, S = kb | 1u, kmax = std::max(ka, kb);
-    size_t lds = sizeof(int32_t) * ((size_t)ka * S + 2 * K + 3 * kmax) + (size_t)kWave * kWave;
-    if (eta_in_lds) lds += sizeof(uint32_t) * K * ((size_t)maxdeg + 1);
-    return (lds + 15) & ~(size_t)15;
-}
-
-hipError_t launch_reshuffle(const ReshuffleParams& p, size_t lds_bytes, hipStream_t stream) {
-    if (p.n_chains == 0 || p.moves == 0) return hipSuccess;
-    auto kern = p.eta_in_lds ? reshuffle_kernel<true> : reshuffle_kernel<false>;
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(p.n_chains), dim3(kWave), lds_bytes, stream, p);
-    return hipGetLastError();
-}
 
 hipError_t launch_exp_probe(const double* x, size_t count, double* out, hipStream_t stream) {
     if (count == 0) return hipSuccess;
@@ -416,28 +296,17 @@ int bisbm::reshuffle_engine(bisbm_engine* h, uint64_t moves, uint32_t scans, dou
     RESERVE(h, st.d_record, C);
     RESERVE(h, st.d_accepted, C);
     ReshuffleParams p{};
-    p.rowptr = h->d_rowptr, p.col = h->d_col;
-    p.n = (uint32_t)h->n, p.na = (uint32_t)h->na, p.nb = (uint32_t)h->nb;
-    p.ka = h->ka, p.kb = h->kb, p.maxdeg = h->maxdeg;
-    p.n_chains = h->n_chains, p.first_chain_id = h->first_chain_id, p.chain_gids = h->d_gids;
-    p.labels = h->d_labels, p.label_stride = h->label_stride;
-    p.m = h->d_m, p.m_r = h->d_m_r, p.n_r = h->d_n_r, p.eta = h->d_eta;
-    p.scalars = h->d_scalars;
-    p.lgamma_tab = h->d_lgamma, p.lgamma_size = h->tab->lg.size(), p.q_tab = h->d_q, p.q_stride = h->q_stride, p.log_tab = h->d_logtab;
-    p.seed = h->seed;
-    p.moves = moves, p.scans = scans, p.beta = beta;
-    if (per_rung) p.beta_rung = h->temper.d_beta.get(), p.rung = h->temper.d_rung.get();
+    wave_chain_fill(h, beta, per_rung, p);
+    p.rounds = moves, p.scans = scans;
     p.member = (uint32_t*)st.d_scratch.get();
     p.orig = st.d_scratch.get() + 4 * nmax * C;
     p.launch = st.d_scratch.get() + 5 * nmax * C;
     p.record = st.d_record.get(), p.accepted = st.d_accepted.get();
-    // eta goes to LDS when that still leaves room for four chains per CU, as in the heat-bath kernel's plan
-    p.eta_in_lds = reshuffle_lds_bytes(h->ka, h->kb, h->maxdeg, true) <= 40 * 1024 ? 1 : 0;
-    const size_t lds = reshuffle_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0);
-    if (lds > kLdsPerCu) return fail(h, BISBM_ERR_UNSUPPORTED, "chain state needs %zu B of LDS (> 160 KiB)", lds);
+    size_t lds;
+    if (int rc = wave_chain_plan(h, 0, p, lds)) return rc;
     h->ent_prev_valid = false;  // (the block state moves)
     st.last.clear();
-    HIPCHK(h, launch_reshuffle(p, lds, h->stream));
+    HIPCHK(h, launch_wave_chain(reshuffle_kernel<true>, reshuffle_kernel<false>, p, lds, h->stream));
     return read_back ? reshuffle_read_back(h) : BISBM_OK;
 }
 

@@ -103,8 +103,13 @@ def main():
             for who, g in order:
                 t["reshuffle_2_moves_3_scans"][who].append(timed(args.limit, "reshuffles (%s)" % who, lambda: g.reshuffle(2, 3, 1.0))[0])
         OUT["existing_calls_vs_parent"] = {call: {who: spread(xs) for who, xs in d.items()} for call, d in t.items()}
+        # one start, the same calls: every chain's labels, cum_dS bit for bit, and what the last call of each kind left behind
+        same = m.get_entropy().tobytes() == p.get_entropy().tobytes() and all(np.array_equal(m.get_memberships(c), p.get_memberships(c)) for c in range(C))
+        equal = {"heatbath_sweep": same and all(np.array_equal(x, y) for x, y in zip(m.last_counts(), p.last_counts())),
+                 "reshuffle_2_moves_3_scans": same and repr(m.reshuffle_last()) == repr(p.reshuffle_last())}
         for call, d in OUT["existing_calls_vs_parent"].items():
             d["this_over_parent_median"] = d["this"]["median_ms"] / d["parent"]["median_ms"]
+            d["equal_to_parent"] = bool(equal[call])
         write_out()
 
     # (c) MH-only rounds against the parent's tempering_run
