@@ -58,6 +58,8 @@ PHILOX_PURPOSE_RESHUFFLE = 10
 RESHUFFLE_NONE = 0xFFFFFFFF
 # bisbm_trace_get_series: which series (BISBM_TRACE_S, BISBM_TRACE_H)
 TRACE_S, TRACE_H = 0, 1
+# bisbm_block_sums_set: keep the sums; also keep every counted chain's aligned tables of the last sample
+BLOCK_SUMS, BLOCK_KEEP_LAST = 1, 2
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -173,6 +175,9 @@ ABI = {
     "bisbm_trace_get_lags": (C.c_int, [C.c_void_p, _f64p, _u64p, _f64p, _u64p, _u64p]),
     "bisbm_trace_get_series": (C.c_int, [C.c_void_p, C.c_int, _f64p]),
     "bisbm_trace_summary": (C.c_int, [C.c_uint64, C.c_uint32, _f64p, C.c_double, _f64p, _u32p, _f64p]),
+    "bisbm_block_sums_set": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "bisbm_block_sums_get": (C.c_int, [C.c_void_p, C.c_uint32, _u64p, _u64p, _u64p, _u64p]),
+    "bisbm_block_sums_get_last": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _i32p, _i32p, _i32p]),
     "bisbm_get_ka_kb": (C.c_int, [C.c_void_p, _u32p, _u32p]),
     "bisbm_get_ka_kb_chain": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "bisbm_agg_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -1296,6 +1301,52 @@ class BlockModel:
         self._check(self._L.bisbm_trace_get_series(self._h, TRACE_S if what == "S" else TRACE_H, _p(out, _f64p)))
         return out
 
+    # -- block summaries (include/bisbm.h, "Block summaries")
+    def block_sums_set(self, on=True, keep_last=False):
+        """Every aligned sample of marginals_accumulate also sums the counted chains' block states -- the ka x kb edge-count
+        quadrant, the block sizes and the block degrees -- through the sample's permutations, per mode (mode 0: the pooled
+        histogram).  `keep_last`: every counted chain's aligned tables of the last sample are kept too (block_last).  Every
+        call zeroes the sums; on=False frees them."""
+        what = (BLOCK_SUMS | (BLOCK_KEEP_LAST if keep_last else 0)) if on else 0
+        self._check(self._L.bisbm_block_sums_set(self._h, what))
+
+    def block_sums(self, mode=None):
+        """The raw words of one mode (None: the pooled histogram's) as a dict: `terms` (chain samples), `e` uint64 [3, KA, KB],
+        `n` and `d` uint64 [3, KA + KB]; plane 0 is the sum, 1 and 2 the low and high word of the sum of squares
+        (sum x^2 = sq_hi * 2^32 + sq_lo)."""
+        ka, kb = self.ka_kb(0)
+        e = np.zeros((3, ka, kb), dtype=np.uint64)
+        n = np.zeros((3, ka + kb), dtype=np.uint64)
+        d = np.zeros((3, ka + kb), dtype=np.uint64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_block_sums_get(self._h, 0 if mode is None else int(mode), C.byref(terms), _p(e, _u64p), _p(n, _u64p), _p(d, _u64p)))
+        return {"terms": int(terms.value), "e": e, "n": n, "d": d}
+
+    def block_summary(self, mode=None):
+        """Means and standard deviations over the counted chain samples of one mode (None: the pooled histogram's), in the
+        numbering of the node marginals of the same samples, as a dict: `terms`, `e_mean` / `e_sd` [KA, KB] (edges between
+        type-a block R and type-b block KA + S), `n_mean` / `n_sd` and `m_r_mean` / `m_r_sd` [KA + KB] (block sizes and
+        degrees), `share` = e_mean / e_mean.sum().  block_moments says how the moments are taken; terms = 0 gives NaN."""
+        w = self.block_sums(mode)
+        out = {"terms": w["terms"]}
+        for key, name in (("e", "e"), ("n", "n"), ("d", "m_r")):
+            mean, var = block_moments(w[key][0], w[key][1], w[key][2], w["terms"])
+            out[name + "_mean"], out[name + "_sd"] = mean, np.sqrt(var)
+        tot = out["e_mean"].sum()
+        out["share"] = out["e_mean"] / tot if tot > 0 else np.full_like(out["e_mean"], np.nan)
+        return out
+
+    def block_last(self, chain):
+        """(mode, e int32 [KA, KB], n_r int32 [KA + KB], m_r int32 [KA + KB]): the aligned tables of `chain` at the last sample
+        and the mode it was counted into (block_sums_set(keep_last=True)); BISBM_ERR_STATE for a chain it did not count."""
+        ka, kb = self.ka_kb(chain)
+        e = np.zeros((ka, kb), dtype=np.int32)
+        n_r = np.zeros(ka + kb, dtype=np.int32)
+        m_r = np.zeros(ka + kb, dtype=np.int32)
+        mode = C.c_uint32()
+        self._check(self._L.bisbm_block_sums_get_last(self._h, int(chain), C.byref(mode), _p(e, _i32p), _p(n_r, _i32p), _p(m_r, _i32p)))
+        return mode.value, e, n_r, m_r
+
     def device_layout(self):
         """(device ordinals, first chain of each device) behind this handle."""
         nd = C.c_int()
@@ -1352,6 +1403,54 @@ def mode_assignment(mode_of_chain, n_chains, n_modes=None):
     if int(n_modes) < 1:
         raise ValueError("no chain is given a mode")
     return moc, int(n_modes)
+
+
+def numpy_block_sums(perms, quads, n_rs, m_rs, modes, n_modes, ka, kb):
+    """The literal model of the block summaries (include/bisbm.h, "Block summaries"); needs no device.  For every chain c with
+    modes[c] = g != MODE_NONE, pi = perms[c] (global-label form, uint [ka + kb]), quads[c] [ka, kb], n_rs[c] and m_rs[c]
+    [ka + kb]:
+        E[g][pi(a)][pi(ka + b) - ka] += quads[c][a][b];  N[g][pi(r)] += n_rs[c][r];  D[g][pi(r)] += m_rs[c][r];  terms[g] += 1
+    where adding x to a cell adds x to its plane 0, (x * x) & 0xffffffff to plane 1 and (x * x) >> 32 to plane 2.  Returns a dict
+    `terms` uint64 [n_modes], `e` uint64 [n_modes, 3, ka, kb], `n` and `d` uint64 [n_modes, 3, ka + kb]."""
+    K = ka + kb
+    out = {"terms": np.zeros(n_modes, dtype=np.uint64), "e": np.zeros((n_modes, 3, ka, kb), dtype=np.uint64),
+           "n": np.zeros((n_modes, 3, K), dtype=np.uint64), "d": np.zeros((n_modes, 3, K), dtype=np.uint64)}
+
+    def add(planes, index, x):
+        x = int(x)
+        planes[(0,) + index] += np.uint64(x)
+        planes[(1,) + index] += np.uint64((x * x) & 0xFFFFFFFF)
+        planes[(2,) + index] += np.uint64((x * x) >> 32)
+    for c in range(len(modes)):
+        g = int(modes[c])
+        if g == MODE_NONE:
+            continue
+        pi = [int(v) for v in perms[c]]
+        for a in range(ka):
+            for b in range(kb):
+                add(out["e"][g], (pi[a], pi[ka + b] - ka), quads[c][a][b])
+        for r in range(K):
+            add(out["n"][g], (pi[r],), n_rs[c][r])
+            add(out["d"][g], (pi[r],), m_rs[c][r])
+        out["terms"][g] += np.uint64(1)
+    return out
+
+
+def block_moments(sum, sq_lo, sq_hi, terms):
+    """(mean, variance) float64 arrays of the cells whose three accumulators are given (arrays of one shape), over `terms`
+    samples.  mean = sum / terms.  With S2 = sq_hi * 2^32 + sq_lo (the exact sum of squares), variance =
+    (S2 * terms - sum^2) / terms^2: numerator and denominator are taken in Python integers and divided once, so the (population)
+    variance is never negative and is exactly 0.0 when all samples agree.  terms = 0 gives NaN.  Needs no device."""
+    s, lo, hi = (np.asarray(a, dtype=np.uint64) for a in (sum, sq_lo, sq_hi))
+    t = int(terms)
+    mean = np.full(s.shape, np.nan)
+    var = np.full(s.shape, np.nan)
+    if t > 0:
+        for i in np.ndindex(*s.shape):
+            x, s2 = int(s[i]), (int(hi[i]) << 32) + int(lo[i])
+            mean[i] = x / t
+            var[i] = (s2 * t - x * x) / (t * t)
+    return mean, var
 
 
 def partition_modes(vi, threshold):

@@ -416,6 +416,8 @@ int aligned_sample(bisbm_engine* e, AlignScratch& s, const AlignPlan& plan, uint
     } else {
         HIPCHK(e, launch_marginals_aligned<false>(cp, M, e->stream));
     }
+    if (plan.block_what)  // block summaries: the chains' block states through the same list, ranges and permutations
+        if (int rc = block_sums_sample(e, s, plan, Y)) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     s.have_perm = true, s.perm_ka = ka, s.perm_kb = kb;
     return BISBM_OK;
@@ -488,7 +490,20 @@ int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     plan.refs = &a.ref;
     plan.ref_serial = a.serial;
     plan.cold_only = h->temper.L != 0;
-    return each_leaf(h, [&](bisbm_engine* e) { return aligned_sample(e, e->align.scratch, plan, 0, device_counts ? device_counts : (e->root ? e->root : e)->d_counts); });
+    std::vector<uint32_t> mode_now;  // block summaries: the chains this sample counts (all; under replica exchange those on rung 0)
+    if (h->blocks.what) {
+        mode_now.assign(h->n_chains, 0u);
+        if (h->temper.L) {
+            std::vector<uint32_t> rung(h->n_chains, 0);
+            if (int rc = bisbm_tempering_get(h, rung.data(), nullptr)) return rc;
+            for (uint32_t c = 0; c < h->n_chains; ++c)
+                if (rung[c] != 0u) mode_now[c] = BISBM_MODE_NONE;
+        }
+        if (int rc = block_sums_prepare(h, ka, kb, mode_now, plan)) return rc;
+    }
+    const int rc = each_leaf(h, [&](bisbm_engine* e) { return aligned_sample(e, e->align.scratch, plan, 0, device_counts ? device_counts : (e->root ? e->root : e)->d_counts); });
+    if (rc == BISBM_OK) block_sums_commit(h, mode_now, plan);
+    return rc;
 }
 
 }  // namespace bisbm

@@ -25,6 +25,8 @@
 //   bisbm_reshuffle.hip  pair reshuffles: two blocks' nodes divided afresh in one accepted or rejected move; kernel and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
+//   bisbm_block_sums.hip  block summaries: the aligned block matrix, sizes and degrees summed over the counted chains of an
+//                        aligned sample; kernel and C ABI
 //   bisbm_trace.hip      chain traces: a ring of each chain's own snapshots, lagged distances to them, the S / H series, tau and R-hat
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
@@ -381,6 +383,24 @@ struct ModeState {
     DeviceBuf<uint32_t> d_top;       // map_mode: winning counts
 };
 
+// Block summaries (bisbm_block_sums.hip).  What is kept, the shape, the terms and the last sample's assignment belong to the
+// handle the caller holds; the sums belong to every device entry (a plain handle, an entry of `devs`: the groups of an entry add
+// into its buffer as they do into its histogram), the last sample's tables to the engines that run the kernels.
+struct BlockSumState {
+    uint32_t what = 0;               // BISBM_BLOCK_SUMS | BISBM_BLOCK_KEEP_LAST; 0: off
+    uint32_t ka = 0, kb = 0;         // the shape the sums were started with
+    uint64_t serial = 1;             // bumped whenever the sums start afresh (it never goes back: a buffer zeroed for an older one is stale)
+    std::vector<uint64_t> terms;     // [modes] chain samples in every mode's sums (empty: no sample since they started)
+    std::vector<uint32_t> last_mode; // [n_chains] the mode the last sample counted every chain into, BISBM_MODE_NONE: none (empty: no sample)
+    // device entry
+    DeviceBuf<unsigned long long> d_sums;  // [slices][3][ka*kb + 2 K] sum, sq_lo, sq_hi of the cells E, N, D
+    uint64_t zeroed = 0;             // the serial d_sums was zeroed for
+    uint32_t slices = 0;
+    // kernel-running engine
+    DeviceBuf<int32_t> d_last;       // [list position][ka*kb + 2 K] the aligned tables of the last sample (KEEP_LAST)
+    uint64_t last_serial = 0;        // the serial d_last was written under
+};
+
 }  // namespace bisbm
 
 // ------------------------------------------------------------------------------------------
@@ -477,6 +497,7 @@ struct bisbm_engine {
     bisbm::PartitionState partition;
     bisbm::ModeState modes;
     bisbm::TraceState trace;
+    bisbm::BlockSumState blocks;
 };
 
 namespace bisbm {
@@ -711,6 +732,8 @@ struct AlignPlan {
     const uint32_t* of_chain = nullptr;  // [chains of the handle] mode of every chain, BISBM_MODE_NONE: not counted; NULL: all in mode 0
     const AlignRef* refs = nullptr;      // [n_modes]
     uint64_t list_serial = 0, ref_serial = 0;  // move with of_chain / with a reference
+    uint32_t block_what = 0;    // block summaries (bisbm_block_sums.hip): what the sample also keeps, 0: nothing
+    uint64_t block_serial = 0;  // BlockSumState::serial of the sums it adds to
     bool cold_only = false;  // the list is the identity and the counting kernel skips the chains off rung 0 (pooled plan under
                              // replica exchange; an anchored plan lists the cold chains itself)
 };
@@ -718,6 +741,17 @@ struct AlignPlan {
 // three steps over e's list of counted chains.  plan.cold_only: the counting kernel takes list position y for chain y and
 // counts it while it is on rung 0.
 int aligned_sample(bisbm_engine* e, AlignScratch& s, const AlignPlan& plan, uint32_t first, uint32_t* counts);
+// ---- block summaries; bisbm_block_sums.hip ----
+// Before an aligned sample of the handle counts anything: mode_now[c] is the mode the sample counts chain c into
+// (BISBM_MODE_NONE: none).  Sums of another shape or mode count start afresh, BISBM_ERR_STATE when a mode's terms would pass
+// 2^32; the plan is told what to keep.  Nothing happens while the sums are off.
+int block_sums_prepare(bisbm_engine* h, uint32_t ka, uint32_t kb, const std::vector<uint32_t>& mode_now, AlignPlan& plan);
+// ... and after it succeeded: the terms and the last sample's assignment
+void block_sums_commit(bisbm_engine* h, const std::vector<uint32_t>& mode_now, const AlignPlan& plan);
+// the sums start afresh (with the histograms they accompany)
+void block_sums_restart(bisbm_engine* h);
+// the kernel of one aligned sample of engine e, on e's stream after the counting kernel: list positions [0, n_pos) of s
+int block_sums_sample(bisbm_engine* e, AlignScratch& s, const AlignPlan& plan, uint32_t n_pos);
 // BISBM_ERR_UNSUPPORTED while some leaf holds two-byte labels
 int refuse_wide_labels(bisbm_engine* h, uint32_t ka, uint32_t kb);
 // BISBM_ERR_INVALID_ARG unless every label of a caller's reference is a block of its node's type

@@ -35,6 +35,7 @@ extern "C" {
 int bisbm_marginals_reset(bisbm_handle h) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     h->align.samples = false;
+    block_sums_restart(h);  // (the block summaries live and die with the histogram they accompany)
     if (h->align.ref.has && h->align.ref.chain >= 0) h->align.ref.has = false;  // (a caller's reference stays)
     if (h->modes.n_modes) return mode_reset(h);  // (one histogram per mode instead of the pooled one)
     if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_marginals_reset(d); });
@@ -99,6 +100,8 @@ extern "C" {
 int bisbm_marginals_accumulate(bisbm_handle h, uint32_t* device_counts) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (int rc = refuse_rungs_over_groups(h)) return rc;
+    if (h->blocks.what && !h->modes.n_modes && h->align.mode != BISBM_ALIGN_REFERENCE)
+        return fail(h, BISBM_ERR_STATE, "block sums are on and this sample is not aligned: raw labels of several chains share no numbering (bisbm_marginals_set_alignment with BISBM_ALIGN_REFERENCE, or modes, first)");
     const int rc = h->modes.n_modes ? mode_accumulate(h, device_counts) : h->align.mode == BISBM_ALIGN_REFERENCE ? align_accumulate(h, device_counts) : accumulate_plain(h, device_counts);
     if (rc == BISBM_OK && !device_counts) h->align.samples = true;
     return rc;

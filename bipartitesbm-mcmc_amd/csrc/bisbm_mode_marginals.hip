@@ -68,6 +68,7 @@ int assign_to_anchors(bisbm_engine* h) {
 
 // the modes are off again: the histograms, the anchors and the scratch go back
 void drop_mode_buffers(bisbm_engine* h, bool off) {
+    block_sums_restart(h);  // (block summaries of another assignment are gone with the histograms)
     for (bisbm_engine* d : device_entries(h)) {
         d->modes.slices = 0;
         d->modes.scratch.have_perm = false;
@@ -153,10 +154,12 @@ int mode_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     plan.of_chain = m.of_chain.data();
     plan.refs = m.refs.data();
     plan.list_serial = m.list_serial, plan.ref_serial = m.ref_serial;
+    if (int rc = block_sums_prepare(h, ka, kb, m.of_chain, plan)) return rc;
     // (device entry i holds the chains dev_first[i] .. of the handle; a plain handle is its own only entry)
     auto sample = [&](bisbm_engine* d, size_t i) { return aligned_sample(d, d->modes.scratch, plan, h->devs.empty() ? 0u : h->dev_first[i], d->modes.d_counts.get()); };
     const int rc = h->devs.empty() ? sample(h, 0) : on_devices(h, sample);
     if (rc) return rc;
+    block_sums_commit(h, m.of_chain, plan);
     for (uint32_t c = 0; c < h->n_chains; ++c)
         if (m.of_chain[c] != kNone) {
             m.terms[m.of_chain[c]] += 1;
@@ -261,6 +264,7 @@ int bisbm_marginals_set_mode_anchors(bisbm_handle h, uint32_t n_modes, const uin
             RESERVE(h, d->modes.d_anchor, rows.size());
             HIPCHK(h, hipMemcpy(d->modes.d_anchor.get(), rows.data(), rows.size(), hipMemcpyHostToDevice));
         }
+        block_sums_restart(h);
         m.n_modes = n_modes;
         m.of_chain.assign(h->n_chains, kNone);
         m.refs.assign(n_modes, AlignRef());

@@ -258,6 +258,24 @@ public:
         check(bisbm_marginals_get_reference(h_, nullptr, &chain));
         return chain;
     }
+    // block summaries (include/bisbm.h): what every aligned sample also keeps (0: off), one mode's raw words (three planes
+    // each: sum, sq_lo, sq_hi) with its terms, a counted chain's aligned tables of the last sample with its mode
+    void block_sums_set(uint32_t what) { check(bisbm_block_sums_set(h_, what)); }
+    uint64_t block_sums(uint32_t mode, std::vector<uint64_t>& e, std::vector<uint64_t>& n, std::vector<uint64_t>& d) {
+        uint32_t ka = 0, kb = 0;
+        check(bisbm_get_ka_kb(h_, &ka, &kb));
+        e.assign((size_t)3 * ka * kb, 0), n.assign((size_t)3 * (ka + kb), 0), d.assign((size_t)3 * (ka + kb), 0);
+        uint64_t terms = 0;
+        check(bisbm_block_sums_get(h_, mode, &terms, e.data(), n.data(), d.data()));
+        return terms;
+    }
+    uint32_t block_sums_last(uint32_t chain, std::vector<int32_t>& e, std::vector<int32_t>& n_r, std::vector<int32_t>& m_r) {
+        uint32_t ka = 0, kb = 0, mode = 0;
+        check(bisbm_get_ka_kb_chain(h_, chain, &ka, &kb));
+        e.assign((size_t)ka * kb, 0), n_r.assign((size_t)ka + kb, 0), m_r.assign((size_t)ka + kb, 0);
+        check(bisbm_block_sums_get_last(h_, chain, &mode, e.data(), n_r.data(), m_r.data()));
+        return mode;
+    }
     // replica exchange (include/bisbm.h): the ladder, sweeps with an exchange round every `every` sweeps, swaps per rung pair
     void tempering_set(const std::vector<float>& ladder) { check(bisbm_tempering_set(h_, (uint32_t)ladder.size(), ladder.data())); }
     void tempering_run(uint64_t sweeps, uint32_t every) { check(bisbm_tempering_run(h_, sweeps, every, nullptr)); }

@@ -59,9 +59,36 @@ const option_spec kOptions[] = {
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
     {"polish", 0, 1},           {"heatbath", 0, 0},
     {"reshuffle", 0, 1},        {"reshuffle_scans", 0, 1},
-    {"trace", 0, 2},
+    {"trace", 0, 2},            {"block_summary", 0, 1},
     {"rung_moves", 0, 2},       {"population_moves", 0, 2},
 };
+
+// a / b of two integers (b > 0) as the nearest double, ties to even: a quotient of 55 or 56 bits with the remainder folded
+// into its lowest bit rounds once, in the conversion
+double exact_quotient(unsigned __int128 a, unsigned __int128 b) {
+    if (a == 0) return 0.;
+    auto bits = [](unsigned __int128 x) {
+        int n = 0;
+        for (; x; x >>= 1) ++n;
+        return n;
+    };
+    const int shift = 55 - (bits(a) - bits(b));
+    if (shift >= 0)
+        a <<= shift;
+    else
+        b <<= -shift;
+    const unsigned __int128 q = a / b;
+    const uint64_t folded = (uint64_t)q | (a % b ? 1u : 0u);
+    return std::ldexp((double)folded, -shift);
+}
+// the moments of a block-summary cell (include/bisbm.h, "Block summaries") from its three words: sum / terms, and
+// (sum of squares * terms - sum^2) / terms^2 in integers with one division at the end; NaN without terms
+double block_mean(uint64_t sum, uint64_t terms) { return terms ? exact_quotient(sum, terms) : std::nan(""); }
+double block_variance(uint64_t sum, uint64_t sq_lo, uint64_t sq_hi, uint64_t terms) {
+    if (!terms) return std::nan("");
+    const unsigned __int128 s2 = ((unsigned __int128)sq_hi << 32) + sq_lo;
+    return exact_quotient(s2 * terms - (unsigned __int128)sum * sum, (unsigned __int128)terms * terms);
+}
 
 const option_spec* find_long(const std::string& name) {
     for (auto const& o : kOptions)
@@ -285,6 +312,13 @@ void print_help(const char* argv0) {
                  "                                        time of the description length, in samples, Sokal's window with c = 5;\n"
                  "                                        window = samples / 2 means the run was too short), then one line with\n"
                  "                                        rhat_S, the split R-hat of the description length over the chains.\n"
+                 "  --block_summary OUT                   With --marginalize --align, or with --modes ... --mode_marginals ...\n"
+                 "                                        (--reassign included): every sample also sums the counted chains' block\n"
+                 "                                        states in the numbering of the node marginals.  OUT receives one section\n"
+                 "                                        per mode (the pooled histogram is mode 0): `mode g terms T ka KA kb KB`,\n"
+                 "                                        then the lines n_mean, n_sd, m_r_mean, m_r_sd (KA + KB values each: block\n"
+                 "                                        sizes and degrees) and e_mean R, e_sd R for every type-a block R (KB\n"
+                 "                                        values each: edges to every type-b block), all printed with %.17g.\n"
                  "  --csr_cache                           Keep a binary CSR beside the edge list (<path>.bisbm_csr, checked\n"
                  "                                        against the file's size and mtime); the text file stays the input.\n";
 }
@@ -461,6 +495,11 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
         trace_depth = (uint32_t)d;
+    }
+    if (count("block_summary") && !(count("marginalize") && (count("align") || count("mode_marginals")))) {
+        std::cerr << "--block_summary sums the chains' block states in the numbering of aligned samples: it needs --marginalize with --align, or with --modes "
+                     "and --mode_marginals.\n";
+        return 1;
     }
     if (count("mode_marginals") && !var_map.count("modes")) {
         std::cerr << "--mode_marginals counts one histogram per mode: it needs --modes (with --marginalize) for the grouping.\n";
@@ -1338,6 +1377,7 @@ int main(int argc, char const* argv[]) {
                 blockmodel.trace_set(trace_depth);
                 blockmodel.trace_reset();
             }
+            if (count("block_summary")) blockmodel.block_sums_set(BISBM_BLOCK_SUMS);
             for (size_t sample = 0; sample < n_samples; ++sample) {
                 advance(sweeps_between);
                 blockmodel.marginals_accumulate();
@@ -1553,6 +1593,47 @@ int main(int argc, char const* argv[]) {
                 }
                 std::clog << "conditionals: " << conditional_queries.size() << " query node(s), beta " << conditionals_beta << ", " << st.terms
                           << " chain term(s) per sum" << (soft ? ", soft marginals" : "") << " -> " << out_path << "\n";
+            }
+            if (count("block_summary")) {
+                // one section per mode: terms, then the means and standard deviations of the sizes, the degrees and the edge counts
+                const std::string out_path = var_map["block_summary"][0];
+                std::ofstream out(out_path);
+                uint32_t n_modes = 1;
+                if (per_mode) {
+                    std::vector<uint32_t> of_chain;
+                    std::vector<int64_t> ref_chain;
+                    std::vector<uint64_t> terms;
+                    n_modes = blockmodel.marginals_modes(of_chain, ref_chain, terms);
+                }
+                char num[40];
+                for (uint32_t g = 0; g < n_modes; ++g) {
+                    std::vector<uint64_t> e, n, d;
+                    const uint64_t terms = blockmodel.block_sums(g, e, n, d);
+                    out << "mode " << g << " terms " << terms << " ka " << KA << " kb " << KB << "\n";
+                    // what = 0: the mean, 1: the standard deviation of `count` cells whose planes are `cells` apart
+                    auto row = [&](const char* name, const uint64_t* w, size_t cells, size_t count, int what) {
+                        out << name;
+                        for (size_t i = 0; i < count; ++i) {
+                            const double v = what == 0 ? block_mean(w[i], terms) : std::sqrt(block_variance(w[i], w[cells + i], w[2 * cells + i], terms));
+                            std::snprintf(num, sizeof(num), " %.17g", v);
+                            out << num;
+                        }
+                        out << "\n";
+                    };
+                    const size_t K = KA + KB;
+                    row("n_mean", n.data(), K, K, 0);
+                    row("n_sd", n.data(), K, K, 1);
+                    row("m_r_mean", d.data(), K, K, 0);
+                    row("m_r_sd", d.data(), K, K, 1);
+                    for (size_t R = 0; R < KA; ++R) row(("e_mean " + std::to_string(R)).c_str(), e.data() + R * KB, KA * KB, KB, 0);
+                    for (size_t R = 0; R < KA; ++R) row(("e_sd " + std::to_string(R)).c_str(), e.data() + R * KB, KA * KB, KB, 1);
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --block_summary: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "block_summary: " << n_modes << " mode(s) -> " << out_path << "\n";
             }
             uint_vec_t heaviest_labels;
             if (per_mode) {

@@ -18,7 +18,7 @@ import numpy as np
 
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
-                similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None, rung_moves=None):
+                similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None, rung_moves=None, blocks=False):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -77,7 +77,13 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     `trace`: depth > 0 (include/bisbm.h, "Chain traces"): a ring of that many snapshots per chain is set, with everything
     forgotten, before the first sample, and every sample is followed by one model.trace_record().  The return value does not
     change: model.trace_lags() / model.trace_series() give the lag curves and the series afterwards (lags in units of
-    sampling_frequency_sweeps), trace_summary() tau and R-hat.  The chains of this rank only."""
+    sampling_frequency_sweeps), trace_summary() tau and R-hat.  The chains of this rank only.
+    `blocks`: with `align` only (ValueError without, before any sweep: raw labels of several chains share no numbering)
+    (include/bisbm.h, "Block summaries"): the block sums are turned on, zeroed, before the first sample (after the reset), and
+    every sample also sums the counted chains' aligned block matrices, sizes and degrees.  The return value does not change:
+    model.block_summary() gives the means and standard deviations afterwards.  The chains of this rank only."""
+    if blocks and not align:
+        raise ValueError("blocks=True needs align=True: the block sums are taken in the numbering of the aligned histogram")
     n = model.n
     multi = shard is not None and shard.world_size > 1
     if return_counts is None:
@@ -129,6 +135,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         model.marginals_reset()
         if align:
             model.marginals_set_alignment(True)
+        if blocks:
+            model.block_sums_set(True)
         for _ in range(int(n_samples)):
             if sampling_frequency_sweeps > 0:
                 advance(sampling_frequency_sweeps)
@@ -163,6 +171,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             model.marginals_set_reference(shard.lowest_chain_labels(model)[1])
         else:
             _drop_library_reference(model)
+    if blocks:
+        model.block_sums_set(True)
     for _ in range(int(n_samples)):
         if sampling_frequency_sweeps > 0:
             advance(sampling_frequency_sweeps)
@@ -189,7 +199,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
 
 
 def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,
-                      reassign=False, tempering=None, exchange_every=1, sampler="mh", trace=None, rung_moves=None):
+                      reassign=False, tempering=None, exchange_every=1, sampler="mh", trace=None, rung_moves=None, blocks=False):
     """Mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): the chains are grouped into posterior modes and
     every mode gets an aligned histogram and a MAP of its own, in the numbering of its own reference.
     Exactly one of `threshold` and `mode_of_chain`: with `threshold` the grouping is model.partition_modes(threshold) taken
@@ -216,6 +226,8 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     `rung_moves` (with `tempering` only): the moves of a round, as in marginalize(); burn-in and gaps count rounds then.
     `sampler`: "mh" or "heatbath", as in marginalize().  `trace`: a depth, as in marginalize() -- one model.trace_record() after
     every sample; the dict does not change.
+    `blocks`: the block sums (include/bisbm.h, "Block summaries") are turned on, zeroed, before the first sample; the dict does
+    not change, model.block_summary(g) gives mode g's block matrix, sizes and degrees with their spread afterwards.
     Chains spread over ranks (`shard`, or model.shard, with world_size > 1) raise ValueError: pooling modes across ranks is
     not done here."""
     if (threshold is None) == (mode_of_chain is None):
@@ -244,6 +256,8 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         model.marginals_set_mode_anchors(anchors, threshold)
     else:
         model.marginals_set_modes(moc, n_modes)
+    if blocks:
+        model.block_sums_set(True)
     _trace_start(model, trace)
     for _ in range(int(n_samples)):
         if sampling_frequency_sweeps > 0:

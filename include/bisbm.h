@@ -835,6 +835,58 @@ int bisbm_marginals_get_mode_assignment(bisbm_handle h, double *vi_out /* n_chai
                                         uint64_t *visits_out /* n_chains * n_modes */, uint64_t *unassigned_out,
                                         uint64_t *samples_out);
 
+/* Block summaries (no reference counterpart): the block-level companion of the aligned node marginals.  Which groups of type-a
+ * nodes attach to which groups of type-b nodes, how large every group is and how firmly the pool agrees on it: the mean and
+ * the exact spread, over the counted chain samples, of the ka x kb edge-count matrix, the block sizes and the block degrees,
+ * in the numbering of the node marginals taken in the same samples.  Off (the default) nothing is launched and nothing else
+ * in this file behaves differently.
+ *
+ * A chain's block state on the device is d_m, the ka x kb quadrant (m_c[a][b] = edges between type-a block a and type-b block
+ * ka + b; bisbm_get_block_state returns it mirrored into K x K), and n_r_c, m_r_c of K = ka + kb entries, all int32.
+ * With the sums on, every ALIGNED sample of bisbm_marginals_accumulate also adds, for every chain c the sample counts into
+ * mode g (mode 0: the pooled histogram) with pi the global-label permutation the sample just computed for c onto g's
+ * reference (bisbm_marginals_get_alignment returns it):
+ *     E[g][pi(a)][pi(ka + b) - ka] += m_c[a][b]   for a < ka, b < kb     edges between the aligned blocks
+ *     N[g][pi(r)] += n_r_c[r]                     for r < K              block sizes
+ *     D[g][pi(r)] += m_r_c[r]                     for r < K              block degrees
+ *     terms[g] += 1
+ * Every cell keeps three uint64 accumulators: sum adds x, sq_lo adds (x*x) & 0xffffffff, sq_hi adds (x*x) >> 32.  x < 2^31,
+ * so the sum of squares is sq_hi * 2^32 + sq_lo exactly, with no carry between the words, and nothing overflows while a mode
+ * holds at most 2^32 chain samples: the accumulate call is BISBM_ERR_STATE, before anything is counted, once a mode's terms
+ * would pass 2^32.  Everything is an integer and every add is associative: the words depend on no thread order, on no split
+ * of the chains over workgroups, on no number of device entries and on no atomics; a plain loop reproduces every word.
+ * The counted chains are exactly those the node histogram of the same sample counts: all chains; under replica exchange the
+ * chains on rung 0 now; with static modes a mode's members (BISBM_MODE_NONE chains are in none); with anchored modes the
+ * chains within the threshold, each in its nearest anchor's mode (unassigned chains add nowhere).
+ *
+ * set: what = 0 turns the feature off and frees its buffers; BISBM_BLOCK_SUMS keeps the sums; BISBM_BLOCK_SUMS |
+ *   BISBM_BLOCK_KEEP_LAST also keeps every counted chain's aligned tables of the last sample (4 bytes per counted chain and
+ *   cell).  Every call zeroes the sums.  Anything else: BISBM_ERR_INVALID_ARG.
+ * The sums live and die with the histogram they accompany: bisbm_marginals_reset zeroes them, and whatever starts the
+ *   histograms afresh starts them afresh too (a merge or split that changes the block counts, bisbm_marginals_set_modes,
+ *   bisbm_marginals_set_mode_anchors).  They are always the library's own: a caller's device_counts does not move them.
+ * get: mode 0 for the pooled histogram, the mode otherwise.  terms, and the planes sum, sq_lo, sq_hi one after the other:
+ *   e[3 * ka * kb] (cell (R, S) at R * kb + S), n[3 * K], d[3 * K]; any pointer may be NULL.  All zero before the first sample
+ *   and after a change of the block counts.  BISBM_ERR_STATE while the sums are off, BISBM_ERR_INVALID_ARG for a mode that does
+ *   not exist.  Several devices: every device keeps the sums of its own chains and the getter adds them on the host; integers
+ *   make that the bits of one handle with all the chains.
+ * get_last: the aligned tables of `chain` at the last sample, e[ka * kb], n_r[K], m_r[K], and the mode it was counted into.
+ *   BISBM_ERR_STATE without BISBM_BLOCK_KEEP_LAST, before a sample, and for a chain the last sample did not count.
+ * A sample that is not aligned (BISBM_ALIGN_NONE and no modes) while the sums are on: bisbm_marginals_accumulate is
+ *   BISBM_ERR_STATE with a message that names bisbm_marginals_set_alignment, before anything is counted -- raw labels of
+ *   several chains share no numbering.  What the aligned sample itself refuses stays refused by it: a wide handle, chains of
+ *   different shapes, grouped chains under modes.
+ * Memory per device: 24 bytes per mode and cell (ka * kb + 2 K cells), plus the kept tables.
+ * Out of scope: unaligned samples, two-byte labels, pooling over processes, quantiles (KEEP_LAST hands a caller the per-chain
+ *   tables for that), cross-moments between cells, eta. */
+#define BISBM_BLOCK_SUMS 1u      /* keep the sums */
+#define BISBM_BLOCK_KEEP_LAST 2u /* also keep every counted chain's aligned tables of the last sample */
+int bisbm_block_sums_set(bisbm_handle h, uint32_t what);
+int bisbm_block_sums_get(bisbm_handle h, uint32_t mode, uint64_t *terms, uint64_t *e /* 3*ka*kb: sum, sq_lo, sq_hi planes */,
+                         uint64_t *n /* 3*K */, uint64_t *d /* 3*K */);
+int bisbm_block_sums_get_last(bisbm_handle h, uint32_t chain, uint32_t *mode_out, int32_t *e /* ka*kb */, int32_t *n_r /* K */,
+                              int32_t *m_r /* K */);
+
 /* Chain traces (no reference counterpart: the reference keeps no history).  Every other analysis here compares chains with each
  * other or with a reference; this one compares a chain with its own past.  How many sweeps until the partition has forgotten
  * where it was, how many independent samples did a run give, do the chains agree on the description length: every chain keeps a
