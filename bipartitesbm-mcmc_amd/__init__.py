@@ -164,6 +164,8 @@ ABI = {
     "bisbm_reshuffle_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, _u64p]),
     "bisbm_reshuffle_get_last": (C.c_int, [C.c_void_p, C.POINTER(ReshuffleRecord)]),
     "bisbm_reshuffle_get_total": (C.c_int, [C.c_void_p, _u64p]),
+    "bisbm_clamp_set": (C.c_int, [C.c_void_p, _u8p]),
+    "bisbm_clamp_get": (C.c_int, [C.c_void_p, _u8p, _u64p]),
     "bisbm_debug_exp": (C.c_int, [C.c_void_p, _f64p, C.c_size_t, _f64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
@@ -189,6 +191,7 @@ ABI = {
     "bisbm_debug_log_q": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_size_t, C.c_int, _f64p]),
     "bisbm_io_read_edge_list": (C.c_long, [C.c_char_p, C.POINTER(_u64p), C.POINTER(_u64p)]),
     "bisbm_io_read_memberships": (C.c_long, [C.c_char_p, C.POINTER(_u32p)]),
+    "bisbm_io_read_clamp": (C.c_long, [C.c_char_p, C.c_uint64, C.POINTER(_u8p), C.c_char_p, C.c_size_t]),
     "bisbm_io_edges_to_csr": (C.c_int, [_u64p, _u64p, C.c_size_t, C.c_uint64, _u64p, _u32p]),
     "bisbm_io_load_csr": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(_u64p), C.POINTER(_u32p), _u64p,
                                     C.POINTER(C.c_int)]),
@@ -290,6 +293,22 @@ def load_memberships(path):
     if n < 0:
         raise FileNotFoundError(path)
     out = np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].copy()
+    L.bisbm_io_free(p)
+    return out
+
+
+def load_clamp(path, n):
+    """The clamp file of ``mcmc --clamp`` (include/bisbm_io.h): node ids < n separated by white space, any order, repeats
+    allowed, an empty file an empty clamp -> bool mask [n].  ValueError, with the token named, for a token that is no node id."""
+    L = lib()
+    p = _u8p()
+    err = C.create_string_buffer(512)
+    count = L.bisbm_io_read_clamp(os.fsencode(path), int(n), C.byref(p), err, len(err))
+    if count == -1:
+        raise FileNotFoundError(path)
+    if count < 0:
+        raise ValueError(err.value.decode())
+    out = np.ctypeslib.as_array(p, shape=(max(int(n), 1),))[:int(n)].astype(bool)
     L.bisbm_io_free(p)
     return out
 
@@ -612,7 +631,7 @@ class BlockModel:
         """Greedy sweeps (beta = +inf: every free node to the lowest block of least dS, only strictly downhill) until a whole
         sweep moves nothing, at most `max_sweeps`.  Returns (moved, sweeps) per chain; a chain has settled -- it is a local
         minimum of the description length under single-node moves -- when its last sweep moved nothing, which
-        sweeps < max_sweeps implies."""
+        sweeps < max_sweeps implies.  Under a clamp() the minimum is over the moves of the open nodes only."""
         return self._heatbath(max_sweeps, float("inf"), True)
 
     # -- pair reshuffles (include/bisbm.h, "Pair reshuffles")
@@ -639,6 +658,35 @@ class BlockModel:
         out = np.zeros(self.n_chains, dtype=np.uint64)
         self._check(self._L.bisbm_reshuffle_get_total(self._h, _p(out, _u64p)))
         return out
+
+    # -- clamped nodes (include/bisbm.h, "Clamped nodes")
+    def clamp(self, nodes_or_mask):
+        """Holds nodes at the labels every chain has for them now: no sampler changes a clamped node's label, in any chain (MH
+        sweeps, heat-bath sweeps and polish(), reshuffles, shuffle_bisbm(), the rounds of replica exchange and population
+        annealing).  `nodes_or_mask`: an array of node ids, or a boolean / uint8 array of length n (non-zero: held).  A new call
+        replaces the mask; an empty one is unclamp().  polish() then certifies a local minimum over the moves of the open
+        nodes only.  While a clamp is set MH sweeps run the generic kernel (slower; README.md), and agg_merge is refused."""
+        a = np.asarray(nodes_or_mask)
+        if a.dtype == np.bool_ or (a.dtype == np.uint8 and a.ndim == 1 and len(a) == self.n):
+            if a.shape != (self.n,):
+                raise ValueError("a clamp mask has one entry per node (%d), not %s" % (self.n, a.shape))
+            mask = np.ascontiguousarray(a != 0, dtype=np.uint8)
+        else:
+            if a.size and (a.dtype.kind not in "iu" or a.min() < 0 or a.max() >= self.n):
+                raise ValueError("clamped node ids must be integers in [0, %d)" % self.n)
+            mask = np.zeros(self.n, dtype=np.uint8)
+            mask[a.astype(np.int64).ravel()] = 1
+        self._check(self._L.bisbm_clamp_set(self._h, _p(mask, _u8p)))
+
+    def unclamp(self):
+        """Clears the clamp: from here on every call is bit for bit what a model that never had one does."""
+        self._check(self._L.bisbm_clamp_set(self._h, None))
+
+    def clamped(self):
+        """The clamp as a bool mask of length n (all False: none)."""
+        mask = np.zeros(self.n, dtype=np.uint8)
+        self._check(self._L.bisbm_clamp_get(self._h, _p(mask, _u8p), None))
+        return mask.astype(bool)
 
     def debug_exp(self, x):
         """exp(x) as the device evaluates it (the host replays of the pair reshuffles take their exponentials from here)"""

@@ -28,6 +28,7 @@
 //   bisbm_block_sums.hip  block summaries: the aligned block matrix, sizes and degrees summed over the counted chains of an
 //                        aligned sample; kernel and C ABI
 //   bisbm_trace.hip      chain traces: a ring of each chain's own snapshots, lagged distances to them, the S / H series, tau and R-hat
+//   bisbm_clamp.hip      clamped nodes: the mask, the lists of the open nodes, the clamped shuffle kernel; C ABI
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -401,6 +402,18 @@ struct BlockSumState {
     uint64_t last_serial = 0;        // the serial d_last was written under
 };
 
+// Clamped nodes (bisbm_clamp.hip).  The mask as the caller gave it belongs to the handle the caller holds; the device copy and
+// the lists of the open nodes belong to every device entry (a plain handle, an entry of `devs`: chains grouped by shape are refused).
+struct ClampState {
+    uint64_t n_clamped = 0;        // non-zero bytes of the mask; 0: no clamp, and no kernel is handed the mask
+    std::vector<uint8_t> mask;     // [n] 0 / 1 (empty: no clamp)
+    // device entry
+    uint32_t open_a = 0, open_b = 0;  // open nodes of type a / of type b
+    DeviceBuf<uint8_t> d_mask;     // [n]
+    DeviceBuf<uint32_t> d_open;    // [open_a + open_b] the open nodes of type a, then of type b, each ascending
+    const uint8_t* mask_or_null() const { return n_clamped ? d_mask.get() : nullptr; }
+};
+
 }  // namespace bisbm
 
 // ------------------------------------------------------------------------------------------
@@ -498,6 +511,7 @@ struct bisbm_engine {
     bisbm::ModeState modes;
     bisbm::TraceState trace;
     bisbm::BlockSumState blocks;
+    bisbm::ClampState clamp;
 };
 
 namespace bisbm {

@@ -48,6 +48,7 @@ void free_all(bisbm_engine* h) {
     // (the buffers of these go here, with the device current and before the stream and the events)
     h->align = AlignState(), h->temper = TemperState(), h->population = PopulationState(), h->pairs = PairScoreState(), h->partition = PartitionState();
     h->queries = QueryScoreState(), h->coassign = CoassignState(), h->foldin = FoldinState(), h->cond = ConditionalState();
+    h->clamp = ClampState();
     h->d_T.reset();
     if (h->root) {  // a sub-engine: the graph and the tables belong to the handle it serves
         h->d_rowptr = nullptr, h->d_col = nullptr, h->d_lgamma = nullptr, h->d_logtab = nullptr, h->d_q = nullptr;
@@ -442,6 +443,7 @@ int shuffle_leaf(bisbm_engine* h) {
     sp.scalars = h->d_scalars;
     sp.mt_engine = h->d_mt_engine;
     sp.wide = h->wide ? 1u : 0u;
+    if (h->clamp.n_clamped) sp.open = h->clamp.d_open.get(), sp.open_a = h->clamp.open_a, sp.open_b = h->clamp.open_b;
     if (h->rng_mode == BISBM_RNG_PHILOX)
         HIPCHK(h, hipMemcpyAsync(h->d_labels_tmp, h->d_labels, (size_t)h->n_chains * h->label_stride * h->lbytes(),
                                  hipMemcpyDeviceToDevice, h->stream));

@@ -16,7 +16,8 @@
 // two table gathers and one f64 add in list order, eight entries in flight together, then the three tails, whose gathers are
 // issued before the list is walked.  min, Z and the running sum C_s are sequential in ascending s over k_own terms: the lane of
 // block s holds its value and every lane adds them one v_readlane at a time.  A node that is not free (a one-
-// block type, or alone in its block) is skipped before any of this: its conditional is the point mass on r.
+// block type, or alone in its block) is skipped before any of this: its conditional is the point mass on r.  A clamped node
+// (include/bisbm.h, "Clamped nodes") is skipped in the chunk header already: the loop over a chunk walks its open positions.
 #include "bisbm_engine.hpp"
 #include "bisbm_wave_chain.hpp"
 
@@ -26,7 +27,9 @@ namespace bisbm {
 
 namespace {
 
-template <bool EL>
+// CL: the launch has a clamp (p.clamp is not NULL).  Without one the instance reads no mask and counts through the chunk as it
+// always did: an unclamped handle runs the code it ran before the clamp existed.
+template <bool EL, bool CL>
 __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const uint32_t chain = blockIdx.x;
@@ -69,16 +72,26 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
             for (uint32_t vi0 = 0; vi0 < n_cls; vi0 += kWave) {
                 // ---- chunk header: lane q holds the node, row extent and own label of position vi0 + q ----
                 const uint32_t cnt = n_cls - vi0 < (uint32_t)kWave ? n_cls - vi0 : (uint32_t)kWave;
-                uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0;
+                uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0, held_l = 0;
                 if (lane < cnt) {
                     v_l = v0 + order(vi0 + lane);
                     beg_l = p.rowptr[v_l];
                     deg_l = p.rowptr[v_l + 1] - beg_l;
                     r_l = wc.labels[v_l];
+                    if (CL) held_l = p.clamp[v_l];
                 }
-                wc.park_rows(cnt, beg_l, deg_l);
+                // under a clamp, the open positions of the chunk: a clamped node stays as a node that is not free does, its row
+                // is not parked (extent 0), a chunk without an open position reads no row at all, and the loop walks the ballot
+                unsigned long long open = CL ? __ballot(lane < cnt && held_l == 0u) : 0ull;
+                if (CL && open == 0ull) continue;
+                wc.park_rows(cnt, beg_l, CL && held_l ? 0u : deg_l);
 
-                for (uint32_t q = 0; q < cnt; ++q) {
+                for (uint32_t qi = 0; CL ? open != 0ull : qi < cnt; ++qi) {
+                    uint32_t q = qi;
+                    if (CL) {
+                        q = (uint32_t)__ffsll((long long)open) - 1u;
+                        open &= open - 1ull;
+                    }
                     const uint32_t v = readlane(v_l, q), beg = readlane(beg_l, q), deg = readlane(deg_l, q);
                     const uint32_t r = readlane(r_l, q), r_loc = r - own0;
                     if (r_loc >= k_own) continue;  // (a valid label: never)
@@ -266,10 +279,14 @@ int bisbm::heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int st
     p.greedy = !per_rung && std::isinf(beta) ? 1u : 0u;
     wave_chain_fill(h, p.greedy ? 0. : beta, per_rung, p);
     p.stop_when_settled = stop_when_settled ? 1u : 0u;
+    p.clamp = h->clamp.mask_or_null();
     size_t lds;  // (the four double[kmax] arrays of the kernel's own: a multiple of 16 bytes, as the rounded chain state is)
     if (int rc = wave_chain_plan(h, 4 * sizeof(double) * std::max(h->ka, h->kb), p, lds)) return rc;
     h->ent_prev_valid = false;  // (the block state moves)
-    HIPCHK(h, launch_wave_chain(heatbath_kernel<true>, heatbath_kernel<false>, p, lds, h->stream));
+    if (p.clamp)
+        HIPCHK(h, launch_wave_chain(heatbath_kernel<true, true>, heatbath_kernel<false, true>, p, lds, h->stream));
+    else
+        HIPCHK(h, launch_wave_chain(heatbath_kernel<true, false>, heatbath_kernel<false, false>, p, lds, h->stream));
     if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
 }

@@ -134,6 +134,62 @@ long bisbm_io_read_memberships(const char* path, uint32_t** labels) {
     return (long)out.size();
 }
 
+long bisbm_io_read_clamp(const char* path, uint64_t n, uint8_t** mask, char* err, size_t err_cap) {
+    if (err && err_cap) err[0] = 0;
+    if (mask) *mask = nullptr;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) {
+        if (err) std::snprintf(err, err_cap, "cannot open %s", path);
+        return -1;
+    }
+    LineReader rd(f);
+    std::vector<uint8_t> held((size_t)n, 0);
+    long count = 0;
+    std::string tok;
+    auto take = [&]() -> bool {  // the token read so far: false when it is no node id
+        if (tok.empty()) return true;
+        uint64_t v = 0;
+        bool ok = true, past = false;  // past: a number of 2^64 or more
+        for (char ch : tok) {
+            if (ch < '0' || ch > '9') {
+                ok = false;
+                break;
+            }
+            if (past || v > (UINT64_MAX - (uint64_t)(ch - '0')) / 10)
+                past = true;
+            else
+                v = v * 10 + (uint64_t)(ch - '0');
+        }
+        if (ok && (past || v >= n)) {
+            if (err) std::snprintf(err, err_cap, "%s: node id '%s' is out of range (the graph has %llu nodes)", path, tok.c_str(), (unsigned long long)n);
+            return false;
+        }
+        if (!ok) {
+            if (err) std::snprintf(err, err_cap, "%s: '%s' is not a node id", path, tok.c_str());
+            return false;
+        }
+        count += held[(size_t)v] ? 0 : 1;
+        held[(size_t)v] = 1;
+        tok.clear();
+        return true;
+    };
+    for (int ch = rd.get();; ch = rd.get()) {
+        const bool blank = ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v';
+        if (ch >= 0 && !blank) {
+            tok.push_back((char)ch);
+            continue;
+        }
+        if (!take()) {
+            std::fclose(f);
+            return -2;
+        }
+        if (ch < 0) break;
+    }
+    std::fclose(f);
+    if (mask) *mask = to_malloc(held);
+    return count;
+}
+
 int bisbm_io_edges_to_csr(const uint64_t* a, const uint64_t* b, size_t n_edges, uint64_t n, uint64_t* rowptr,
                           uint32_t* col) {
     std::memset(rowptr, 0, sizeof(uint64_t) * (n + 1));

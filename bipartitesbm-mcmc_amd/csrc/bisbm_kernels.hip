@@ -582,19 +582,29 @@ __global__ __launch_bounds__(kWave) void sweep_kernel(SweepParams p) {
             // lane q: node, row extent and own label of position vi0 + q.  A node is visited once per
             // sweep, so its own label cannot change before its step.
             const uint32_t cnt = (num_nodes - vi0) < (uint64_t)kWave ? (uint32_t)(num_nodes - vi0) : (uint32_t)kWave;
-            uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0;
+            // Clamped nodes (include/bisbm.h; Philox mode only, p.clamp NULL otherwise): the mask byte comes with the header.  A
+            // clamped position stages no row and gathers no labels -- stage_l, the row length the staging and the label pipeline
+            // go by, is 0 there -- and its step is skipped in do_step.
+            uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0, stage_l = 0;
+            unsigned long long held = 0;
             if ((uint32_t)lane < cnt) {
                 const uint32_t pos = (uint32_t)(vi0 + lane);
                 v_l = (RNG == RNG_COMPAT) ? vl[pos] : (pos < p.na ? order_a(pos) : p.na + order_b(pos - p.na));
                 beg_l = p.rowptr[v_l];
                 deg_l = p.rowptr[v_l + 1] - beg_l;
                 r_l = lab_at<W>(c, v_l);
+                stage_l = deg_l;
+            }
+            if (RNG == RNG_PHILOX && !W && p.clamp) {
+                const bool is_held = (uint32_t)lane < cnt && p.clamp[v_l] != 0;
+                held = __ballot(is_held);
+                if (is_held) stage_l = 0;
             }
             // CSR staging: the chunk's 64 adjacency rows (first 64 ids of each) go HBM -> LDS by
             // LDS-DMA, one 256-B row slot per instruction, all of them in flight together
             wave_fence();
             for (uint32_t q = 0; q < cnt; ++q) {
-                const uint32_t b0 = readlane(beg_l, q), d0 = readlane(deg_l, q);
+                const uint32_t b0 = readlane(beg_l, q), d0 = readlane(stage_l, q);
                 if ((uint32_t)lane < d0)
                     __builtin_amdgcn_global_load_lds(p.col + b0 + lane, ids_lds + q * kWave, 4, 0, 0);
             }
@@ -607,7 +617,7 @@ __global__ __launch_bounds__(kWave) void sweep_kernel(SweepParams p) {
             // not also be written by VALU code, or the compiler drains vmcnt before that write.
             auto gather = [&](uint32_t qq, uint32_t& nb, int& lab) {
                 if (qq < cnt) {
-                    const uint32_t d = readlane(deg_l, qq);
+                    const uint32_t d = readlane(stage_l, qq);
                     const uint32_t id = ids_lds[qq * kWave + lane];
                     const bool on = (uint32_t)lane < d;
                     nb = on ? id : 0xFFFFFFFFu;
@@ -640,8 +650,10 @@ __global__ __launch_bounds__(kWave) void sweep_kernel(SweepParams p) {
                 const double T = temperature_of(p, current_step + vi);  // :84
                 uint32_t s = r;
                 prefetch();
-                const bool ok = mh_step<RNG, EL, W>(p, tab, c, engine, gen, v, beg, deg, r, nbC, labC, T,
-                                                 sweeps_total * num_nodes + vi, chain_gid, &s);
+                // (a clamped node: the ring is rotated and refilled as for any step, the step itself is one that was not accepted)
+                const bool ok = ((held >> q) & 1ull) == 0ull &&
+                                mh_step<RNG, EL, W>(p, tab, c, engine, gen, v, beg, deg, r, nbC, labC, T,
+                                                    sweeps_total * num_nodes + vi, chain_gid, &s);
                 mv_v1 = mv_v2;
                 mv_s1 = mv_s2;
                 mv_v2 = mv_v3;
@@ -826,6 +838,23 @@ __global__ void shuffle_philox_kernel(ShuffleParams p) {
     fb.init(phx_draw(p.seed, gid, PHX_INIT_SHUFFLE, ((uint64_t)1 << 32) | epoch), p.nb);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += gridDim.x * blockDim.x)
         dst[i] = i < p.na ? src[fa(i)] : src[p.na + fb(i - p.na)];
+}
+
+// ... under a clamp (include/bisbm.h, "Clamped nodes", 4.; byte labels): the same keyed permutations on the domains |F_a| and
+// |F_b| of the open nodes, applied to the compacted label vectors -- dst[F[i]] = src[F[f(i)]].  dst holds the labels before the
+// shuffle, so the clamped nodes keep theirs.  A domain of 0 has no position, and Feistel maps a domain of 1 to 0.
+__global__ void shuffle_philox_clamped_kernel(ShuffleParams p) {
+    const uint32_t chain = blockIdx.y;
+    const uint8_t* src = p.labels_old + (size_t)chain * p.label_stride;
+    uint8_t* dst = p.labels + (size_t)chain * p.label_stride;
+    const uint32_t gid = chain_gid_of(p, chain);
+    const uint32_t epoch = p.scalars[chain].shuffle_epoch;
+    Feistel fa, fb;
+    fa.init(phx_draw(p.seed, gid, PHX_INIT_SHUFFLE, ((uint64_t)0 << 32) | epoch), p.open_a);
+    fb.init(phx_draw(p.seed, gid, PHX_INIT_SHUFFLE, ((uint64_t)1 << 32) | epoch), p.open_b);
+    const uint32_t n_open = p.open_a + p.open_b;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_open; i += gridDim.x * blockDim.x)
+        dst[p.open[i]] = src[p.open[i < p.open_a ? fa(i) : p.open_a + fb(i - p.open_a)]];
 }
 
 __global__ void shuffle_epoch_bump_kernel(ChainScalars* sc, uint32_t n_chains) {
@@ -1338,7 +1367,9 @@ hipError_t launch_shuffle(const ShuffleParams& p, int rng_mode, hipStream_t stre
             hipLaunchKernelGGL(shuffle_compat_kernel<uint8_t>, dim3(p.n_chains), dim3(kWave), 0, stream, p);
     } else {
         const uint32_t tiles = (p.n + 255) / 256 < 1024 ? (p.n + 255) / 256 : 1024;
-        if (p.wide)
+        if (p.open)
+            hipLaunchKernelGGL(shuffle_philox_clamped_kernel, dim3(tiles ? tiles : 1, p.n_chains), dim3(256), 0, stream, p);
+        else if (p.wide)
             hipLaunchKernelGGL(shuffle_philox_kernel<uint16_t>, dim3(tiles ? tiles : 1, p.n_chains), dim3(256), 0, stream, p);
         else
             hipLaunchKernelGGL(shuffle_philox_kernel<uint8_t>, dim3(tiles ? tiles : 1, p.n_chains), dim3(256), 0, stream, p);

@@ -112,6 +112,9 @@ struct SweepParams {
     // modulo n -- a WRONG predicted target, (prediction + 1) mod k_own, so that the passes that start from a predicted target
     // take their miss paths at a known rate (bisbm_predict_skew.hpp).  The chain is the same chain whatever the prediction says.
     uint32_t predict_skew;
+    // clamped nodes (bisbm_clamp.hip), generic kernel in Philox mode only: [n] a non-zero byte holds the node -- its step is not
+    // evaluated and counts as a step that was not accepted; NULL: no clamp
+    const uint8_t* clamp;
 };
 // Accepted fraction of the launch before from which a four-steps launch of 17..32 blocks takes the one-stage kernel
 // (SweepParams::one_stage).  Measured at 32 + 32 blocks (profiles/EXPERIMENTS.md, round 7): the one stage wins by 3.9 % where 0.72
@@ -143,6 +146,10 @@ struct ShuffleParams {
     ChainScalars* scalars;
     uint32_t* mt_engine;
     uint32_t wide;
+    // clamped nodes (Philox mode, byte labels): the open nodes of type a (open_a of them), then of type b (open_b), each
+    // ascending; the labels of a type's open nodes are permuted among themselves.  NULL: no clamp
+    const uint32_t* open;
+    uint32_t open_a, open_b;
 };
 
 struct EntropyParams {
@@ -437,6 +444,7 @@ inline size_t wave_chain_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bo
 struct HeatbathParams : WaveChainParams {
     uint32_t greedy;             // beta = +inf: the lowest argmin of dS, only strictly downhill, no draw
     uint32_t stop_when_settled;  // a chain stops after the first sweep that moved nothing
+    const uint8_t* clamp;        // clamped nodes: [n] a non-zero byte holds the node as a node that is not free is held; NULL: no clamp
 };
 
 constexpr uint32_t PHX_RESHUFFLE = 10;  // pair reshuffles: idx = (reshuffles_total << 32) | k, chain = the chain's global id
@@ -450,6 +458,7 @@ struct ReshuffleParams : WaveChainParams {
     uint8_t* launch;             // [chain][nmax]
     bisbm_reshuffle_record* record;  // [chain] the last move of the call
     unsigned long long* accepted;    // [chain] accepted moves of the call
+    const uint8_t* clamp;            // clamped nodes: [n] a node with a non-zero byte is no member of any move; NULL: no clamp
 };
 hipError_t launch_exp_probe(const double* x, size_t count, double* out, hipStream_t stream);
 

@@ -79,12 +79,12 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
         const U4 acc_draw = phx_draw(p.seed, chain_gid, PHX_RESHUFFLE, idx0 | 1u);
         const double u_acc = u53(acc_draw.x, acc_draw.y);
 
-        // 3. the members, ascending id, by ballot compaction
+        // 3. the members, ascending id, by ballot compaction: the nodes of r and s that are not clamped
         uint32_t M = 0;
         for (uint32_t i0 = 0; i0 < n_cls; i0 += kWave) {
             const uint32_t i = i0 + lane;
             const uint32_t lab = i < n_cls ? (uint32_t)labels[v0 + i] : 0xffffffffu;
-            const bool is = lab == rg || lab == sg;
+            const bool is = (lab == rg || lab == sg) && !(p.clamp && p.clamp[v0 + i] != 0);
             const unsigned long long bal = __ballot(is);
             if (is) {
                 const uint32_t pos = M + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
@@ -93,7 +93,10 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
             }
             M += (uint32_t)__popcll(bal);
         }
-        if (M < 2u) continue;  // (no block is ever empty: never)
+        if (M < 2u) {  // (no block is ever empty: only under a clamp) a counted no-op; the record keeps the pair and M
+            rec.type = tb ? 1u : 0u, rec.r = rg, rec.s = sg, rec.M = M;
+            continue;
+        }
         // 4. the launch labels
         const uint32_t W = (M + 127u) >> 7;
         bool got_r = false, got_s = false;
@@ -302,6 +305,7 @@ int bisbm::reshuffle_engine(bisbm_engine* h, uint64_t moves, uint32_t scans, dou
     p.orig = st.d_scratch.get() + 4 * nmax * C;
     p.launch = st.d_scratch.get() + 5 * nmax * C;
     p.record = st.d_record.get(), p.accepted = st.d_accepted.get();
+    p.clamp = h->clamp.mask_or_null();
     size_t lds;
     if (int rc = wave_chain_plan(h, 0, p, lds)) return rc;
     h->ent_prev_valid = false;  // (the block state moves)

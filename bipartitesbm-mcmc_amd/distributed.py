@@ -392,6 +392,23 @@ def numpy_reshuffle_accept(dS_fwd, dS_rev, q_fwd, q_rev, beta, u_acc):
     return A, float(u_acc) < A
 
 
+def numpy_clamped_shuffle(labels, mask, na, perm_a, perm_b):
+    """The shuffle under a clamp (include/bisbm.h, "Clamped nodes", 4.) on the host, given the two permutations of the
+    compacted label vectors: with F the ascending list of the open (mask == 0) nodes of a type and f its permutation of
+    range(len(F)), new[F[i]] = old[F[f[i]]]; the clamped nodes keep their labels.  perm_a / perm_b: f of type a (nodes
+    0 .. na-1) and of type b, of lengths |F_a| and |F_b| (0 and 1 included: nothing moves)."""
+    labels = np.asarray(labels)
+    held = np.asarray(mask) != 0
+    out = labels.copy()
+    for lo, hi, perm in ((0, int(na), perm_a), (int(na), len(labels), perm_b)):
+        F = lo + np.flatnonzero(~held[lo:hi])
+        perm = np.asarray(perm, dtype=np.int64)
+        if len(perm) != len(F) or sorted(perm.tolist()) != list(range(len(F))):
+            raise ValueError("a permutation of the %d open nodes of the type is needed" % len(F))
+        out[F] = labels[F[perm]]
+    return out
+
+
 def numpy_foldin_posterior(labels, m, m_r, n_r, ka, qtype, neighbours, alpha):
     """Host statement of steps 1 and 2 of the fold-in queries (include/bisbm.h, "Fold-in queries") for one chain and one virtual
     node: the posterior P[K_own] over the blocks of its type, bit for bit what the device computes.  `labels`, `m`, `m_r`, `n_r`:

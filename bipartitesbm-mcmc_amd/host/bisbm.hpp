@@ -61,6 +61,20 @@ inline bool load_memberships(uint_vec_t& memberships, const std::string& path) {
     return true;
 }
 
+// The clamp file of --clamp (include/bisbm_io.h): node ids separated by white space -> a mask of n bytes, 1 = listed.  On a
+// failure `error` names the file, and the token where one is at fault.
+inline bool load_clamp(std::vector<uint8_t>& mask, const std::string& path, size_t n, std::string& error) {
+    uint8_t* p = nullptr;
+    char msg[512];
+    if (bisbm_io_read_clamp(path.c_str(), n, &p, msg, sizeof(msg)) < 0) {
+        error = msg;
+        return false;
+    }
+    mask.assign(p, p + n);
+    bisbm_io_free(p);
+    return true;
+}
+
 inline adj_list_t edge_to_adj(const edge_list_t& edge_list, size_t num_vertices = 0) {
     size_t n = num_vertices;
     for (auto const& e : edge_list) n = std::max(n, std::max(e.first, e.second) + 1);  // graph_utilities.cc:39-44
@@ -335,6 +349,18 @@ public:
         moved.assign(n_chains_, 0);
         sweeps.assign(n_chains_, 0);
         check(bisbm_heatbath_run(h_, max_sweeps, std::numeric_limits<double>::infinity(), 1, moved.data(), sweeps.data()));
+    }
+    // clamped nodes (include/bisbm.h): a non-zero byte of the mask (n bytes) holds the node at the label every chain has for it,
+    // through every sampler; an empty or all-zero mask clears the clamp.  The mask in place and how many nodes it holds.
+    void clamp(const std::vector<uint8_t>& mask) {
+        if (!mask.empty() && mask.size() != n_) throw std::runtime_error("clamp: the mask has one byte per node");
+        check(bisbm_clamp_set(h_, mask.empty() ? nullptr : mask.data()));
+    }
+    void unclamp() { check(bisbm_clamp_set(h_, nullptr)); }
+    std::vector<uint8_t> clamped(uint64_t* n_clamped = nullptr) {
+        std::vector<uint8_t> mask(n_);
+        check(bisbm_clamp_get(h_, mask.data(), n_clamped));
+        return mask;
     }
     // pair reshuffles (include/bisbm.h): `moves` moves per chain in which the nodes of two blocks of one type are divided afresh
     // and accepted or rejected as a whole (the accepted moves per chain); the record of every chain's last move.  The default

@@ -6,7 +6,8 @@
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
 // --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
-// --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace, --rung_moves, --population_moves.
+// --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace, --rung_moves, --population_moves,
+// --clamp.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -61,6 +62,7 @@ const option_spec kOptions[] = {
     {"reshuffle", 0, 1},        {"reshuffle_scans", 0, 1},
     {"trace", 0, 2},            {"block_summary", 0, 1},
     {"rung_moves", 0, 2},       {"population_moves", 0, 2},
+    {"clamp", 0, 1},
 };
 
 // a / b of two integers (b > 0) as the nearest double, ties to even: a quotient of 55 or 56 bits with the remainder folded
@@ -249,6 +251,11 @@ void print_help(const char* argv0) {
                  "                                        --tempering).  The acceptance is reported on stderr.\n"
                  "  --reshuffle_scans arg (=3)            With --reshuffle: restricted Gibbs scans before the proposal (3 is the\n"
                  "                                        convention of the literature, not a measurement).\n"
+                 "  --clamp PATH                          PATH holds node ids separated by white space (any order, repeats allowed):\n"
+                 "                                        these nodes keep the labels of --membership_path (required) through every\n"
+                 "                                        sweep, reshuffle and exchange round of the run, in every chain; the other\n"
+                 "                                        nodes are sampled as always.  Philox mode (--rng philox); not with --merge,\n"
+                 "                                        --nature or a -z that differs from the block counts of the membership file.\n"
                  "  --score_pairs IN OUT                  With --marginalize: IN holds one pair `u v` per line (u of type a, v of\n"
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
@@ -910,6 +917,16 @@ int main(int argc, char const* argv[]) {
     // mcmc_main.cc:219-226 tests var_map.count("epsilon"), which is always 1 because of the default value
     bool randomize = count("randomize") > 0;
     const bool merge = count("merge") > 0, nature = count("nature") > 0;
+    if (count("clamp")) {  // (what can be refused before anything is loaded)
+        if (!count("membership_path")) {
+            std::cerr << "--clamp holds the listed nodes at the labels of a membership file: it needs --membership_path.\n";
+            return 1;
+        }
+        if (merge || nature) {
+            std::cerr << "--clamp cannot be combined with " << (merge ? "--merge" : "--nature") << ": a merge renumbers the blocks whose labels the clamp holds.\n";
+            return 1;
+        }
+    }
     size_t seed;
     if (count("seed") == 0)
         seed = (size_t)std::chrono::high_resolution_clock::now().time_since_epoch().count();  // :236-239
@@ -1009,6 +1026,30 @@ int main(int argc, char const* argv[]) {
         output_vec<uint_vec_t>(mine, std::cout);
     };
     const adj_list_t& adj_list = adj_list_loaded;
+    // --clamp: the mask, in the engine's numbering (--reorder: the engine knows node v by new_id[v])
+    std::vector<uint8_t> clamp_mask;
+    if (count("clamp")) {
+        if (!prepared) {
+            std::cerr << "--clamp holds the listed nodes at the labels of --membership_path, which could not be read.\n";
+            return 1;
+        }
+        if (z.size() >= 2 && (z[0] != KA || z[1] != KB)) {
+            std::cerr << "--clamp: -z " << z[0] << " " << z[1] << " differs from the " << KA << " + " << KB
+                      << " blocks of the membership file, and the merge or split that would follow renumbers blocks.\n";
+            return 1;
+        }
+        std::string why;
+        if (!load_clamp(clamp_mask, single("clamp", ""), N, why)) {
+            std::cerr << "[error] --clamp: " << why << "\n";
+            return 1;
+        }
+        if (!new_id.empty()) {
+            std::vector<uint8_t> moved(clamp_mask.size());
+            for (size_t v = 0; v < clamp_mask.size(); ++v) moved[new_id[v]] = clamp_mask[v];
+            clamp_mask.swap(moved);
+        }
+        std::clog << "clamp: " << std::count(clamp_mask.begin(), clamp_mask.end(), (uint8_t)1) << " of " << N << " nodes held\n";
+    }
 
     // K implied by the initial labels vs. requested (mcmc_main.cc:406-419)
     size_t ka = 0, kb = 0;
@@ -1056,6 +1097,10 @@ int main(int argc, char const* argv[]) {
         return 1;
     }
     opt.rng_mode = rng == "philox" ? BISBM_RNG_PHILOX : BISBM_RNG_MT19937_COMPAT;
+    if (count("clamp") && opt.rng_mode != BISBM_RNG_PHILOX) {
+        std::cerr << "--clamp runs in Philox mode only (mt19937-compat is the reference's verification path, and the reference has no clamp): add --rng philox.\n";
+        return 1;
+    }
     if ((polish_sweeps || count("heatbath") || reshuffle_moves) && opt.rng_mode != BISBM_RNG_PHILOX) {
         std::cerr << (polish_sweeps ? "--polish" : count("heatbath") ? "--heatbath" : "--reshuffle")
                   << " runs in Philox mode only (mt19937-compat is the reference's verification path): add --rng philox.\n";
@@ -1245,6 +1290,11 @@ int main(int argc, char const* argv[]) {
         return 0;
     }
     if (ka != KA || kb != KB) {  // the initial partition has other block counts than asked for (:419-450)
+        if (count("clamp")) {
+            std::cerr << "--clamp: the initial partition has " << ka << " + " << kb << " blocks, not " << KA << " + " << KB
+                      << ", and the merge or split that would follow renumbers blocks.\n";
+            return 1;
+        }
         if (!population.empty()) {
             std::cerr << "--population replaces the cooling schedule of the annealing run: the initial partition must have the -z block counts.\n";
             return 1;
@@ -1283,6 +1333,7 @@ int main(int argc, char const* argv[]) {
             const size_t sweeps_between = std::max<size_t>(1, freq / N);
             const size_t n_samples = sampling_steps / (sweeps_between * N);
             blockmodel_t blockmodel(memberships_init, types_init, KA + KB, KA, KB, epsilon, &adj_list, opt);
+            if (!clamp_mask.empty()) blockmodel.clamp(clamp_mask);
             if (randomize)
                 blockmodel.shuffle_bisbm();
             else
@@ -1737,6 +1788,7 @@ int main(int argc, char const* argv[]) {
 
     try {
         blockmodel_t blockmodel(memberships_init, types_init, KA + KB, KA, KB, epsilon, &adj_list, opt);  // :453
+        if (!clamp_mask.empty()) blockmodel.clamp(clamp_mask);
         if (randomize)
             blockmodel.shuffle_bisbm();
         else

@@ -685,6 +685,52 @@ int bisbm_reshuffle_get_last(bisbm_handle h, bisbm_reshuffle_record *out /* n_ch
 /* The chains' reshuffles_total. */
 int bisbm_reshuffle_get_total(bisbm_handle h, uint64_t *out /* n_chains */);
 
+/* Clamped nodes (no reference counterpart): one mask per handle, one byte per node; a non-zero byte means the node is CLAMPED
+ * and no sampler changes its label, in any chain.  Partial labels, one side of a bipartite graph held, an incremental refit, or
+ * a seed per block with the same label in every chain, which pins the block numbering (the raw histogram of the marginals is
+ * then a marginal over chains without an alignment).  Only the nodes are held, not the edges: a clamped node counts in m, m_r,
+ * n_r and eta and in every dS of its neighbours.  The other nodes are OPEN.  Philox mode and byte labels only.
+ * set: the mask is copied to every device of the handle, beside the ascending lists of the open nodes of each type (n bytes
+ * plus 4 bytes per open node and device); NULL or an all-zero mask clears the clamp.  Setting or clearing touches no chain
+ * state: the clamp holds whatever labels every chain has at the time, and bisbm_set_memberships stays allowed under a clamp
+ * (the caller's own act).  After a clear every call is bit for bit what a handle that never had a clamp does, and MH sweeps
+ * run the production kernel again.  get: the mask as 0 / 1 bytes and the number of clamped nodes.
+ *   1. MH SWEEPS (bisbm_anneal, bisbm_tempering_run, the MH part of the rounds): the step of a clamped node is not evaluated
+ *      and the node stays.  In every counter it is a step that was not accepted: it counts in the n steps of the sweep and in
+ *      the count of T < 1 steps of the early stop, never in `accepted`, and adds nothing to the running sum.  The Philox draws
+ *      of a step are keyed by its position in the sweep, so no other step's draws move: the clamped chain equals the unclamped
+ *      chain up to the first step at which the unclamped chain moves a clamped node.  Skipping is legal because a sweep is a
+ *      composition of single-node kernels each of which leaves exp(-beta S) invariant; leaving some out leaves a composition
+ *      of kernels that keep the distribution restricted to the states that agree with the clamped labels.  While a non-empty
+ *      clamp is set the sweeps run the generic kernel (a handle the production kernel would serve runs slower: README.md).
+ *   2. HEAT-BATH SWEEPS AND POLISHING (bisbm_heatbath_run): a clamped node is a node that is not free: it stays, no draw is
+ *      used, and it is counted as such a node is.  The position in the sweep of every other node, and with it its draw, is
+ *      unchanged.  With beta = +inf and stop_when_settled the end state is a local minimum over the moves of the OPEN nodes
+ *      only.  The work of a sweep follows the open nodes: a chunk of 64 positions without an open node reads no row.
+ *   3. PAIR RESHUFFLES (bisbm_reshuffle_run): step 3 becomes "the nodes of that type whose label is r or s and that are not
+ *      clamped, in ascending id"; everything indexed by the member number -- the launch bits, the uniforms of the scans, the
+ *      forced first and last launch label, M < 2 a counted no-op (now possible: the record holds the pair and M, everything
+ *      else 0) -- is unchanged in form.  The pair is still drawn without a look at the state.  The clamped nodes of r and s
+ *      stay in n_r, m_r and m, so a member's dS sees them and its FREE test (n_r[c] > 1) counts them.  Detailed balance holds
+ *      as before: which nodes are members does not depend on how the members are divided.
+ *   4. SHUFFLE (bisbm_shuffle): the labels of the open nodes of each type are permuted among themselves.  For type t with F the
+ *      ascending list of its open nodes: f = the keyed Feistel permutation of bisbm_shuffle (same purpose 3, same index
+ *      (t << 32) | epoch, same chain key) on the domain |F|, and new[F[i]] = old[F[f(i)]] -- the unclamped shuffle of the
+ *      compacted label vector, so block sizes are preserved.  |F| <= 1 leaves the type as it is.  The epoch advances as always.
+ *   5. REPLICA EXCHANGE, ROUNDS, POPULATION ANNEALING: the mask is the handle's, so every kernel of a round is handed it; chain c
+ *      stays, bit for bit, the chain that a one-chain handle of its global id with the same mask runs through the same moves at
+ *      the temperatures it held.  bisbm_population_resample copies whole chains, so the clamped labels of the source travel
+ *      with the copy: a population is meant to share its clamped labels.
+ * The analysis calls, the traces, the partition distances and the block summaries only read chain state and are unchanged.
+ * Served: several devices behind one handle.  Refused, with a message and nothing changed: BISBM_RNG_MT19937_COMPAT (that
+ * mode exists for parity with the reference, which has no clamp) and two-byte labels BISBM_ERR_UNSUPPORTED; chains grouped by
+ * shape BISBM_ERR_STATE; mask_out and n_clamped_out both NULL is allowed.  While a non-empty clamp is set bisbm_agg_merge and
+ * bisbm_agg_merge_total are BISBM_ERR_STATE (a merge or split renumbers blocks; bisbm_clamp_set(h, NULL) first).
+ * Out of scope: a mask per chain, mt19937-compat arithmetic, wide handles, chains grouped by shape, clamped MH sweeps in the
+ * production kernel, constraints other than "stays". */
+int bisbm_clamp_set(bisbm_handle h, const uint8_t *mask /* n; non-zero = held; NULL clears */);
+int bisbm_clamp_get(bisbm_handle h, uint8_t *mask_out /* n, may be NULL */, uint64_t *n_clamped_out /* may be NULL */);
+
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
  * chains' partitions on the device, and a small deterministic grouping on the host.

@@ -23,6 +23,13 @@ long bisbm_io_read_edge_list(const char *path, uint64_t **a, uint64_t **b);
 /* load_memberships (graph_utilities.cc:5-18): one label per line.  Returns the count or -1. */
 long bisbm_io_read_memberships(const char *path, uint32_t **labels);
 
+/* The clamp file of `mcmc --clamp` (no reference counterpart; include/bisbm.h, "Clamped nodes"): node ids as decimal numbers
+ * separated by white space (blanks, tabs, line ends), in any order, repeats allowed; an empty file is an empty clamp.  *mask
+ * gets n malloc'ed bytes, 1 for every listed node.  Returns the number of distinct nodes listed, -1 when the file cannot be
+ * opened, -2 for a token that is not a number of decimal digits alone (a sign, a letter) or an id >= n (a number past 2^64
+ * included); `err` (err_cap bytes, may be NULL) then holds a message that names the token, and *mask is NULL. */
+long bisbm_io_read_clamp(const char *path, uint64_t n, uint8_t **mask, char *err, size_t err_cap);
+
 /* edge_to_adj (graph_utilities.cc:36-49) as CSR: undirected, duplicates kept, each row in edge-file
  * order.  rowptr has n+1 entries, col has 2*n_edges.  Returns 0, or -1 when an id is >= n. */
 int bisbm_io_edges_to_csr(const uint64_t *a, const uint64_t *b, size_t n_edges, uint64_t n,
