@@ -16,9 +16,12 @@
 //                        heat-bath sweeps and pair reshuffles at a beta per chain, the per-rung tally
 //   bisbm_population.hip  population annealing: offspring counts on the host, the kernel that copies chain states between slots
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
-//   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains, top-k on the device; kernels and C ABI
-//   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block, top-k; kernels and C ABI
+//   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains; kernels and C ABI
+//   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block; kernels and C ABI
 //   bisbm_foldin.hip     fold-in queries: block posterior, recommendations and peers of a node that is not in the graph; kernels and C ABI
+//   bisbm_topk.hip       the best k candidates of every query, for the three units above: the mask, select and add kernels, the
+//                        host driver of the *_topk calls and the reader of the *_get_row calls (bisbm_cand_lanes.hpp: how the
+//                        three accumulate kernels lay candidates over lanes)
 //   bisbm_conditionals.hip  node conditionals: dS of every target block of a node, the conditional and its pooled terms, soft marginals; kernels and C ABI
 //   bisbm_heatbath.hip   heat-bath sweeps and greedy polishing: nodes moved by their conditionals; kernel and C ABI (and the host
 //                        side of the chain state it shares with the reshuffle kernel: bisbm_wave_chain.hpp)
@@ -47,6 +50,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <queue>
 #include <random>
 #include <set>
@@ -206,9 +210,18 @@ struct PairScoreState {
     std::vector<uint32_t> order;  // sorted position -> index in the caller's arrays
 };
 
+// What topk_select (bisbm_topk.hip) needs of device memory for one chunk of queries, T: the cell type of the rows.  It is on the
+// engine whose device selects (a plain handle, the first device entry).
+template <class T>
+struct TopkScratch {
+    DeviceBuf<uint8_t> d_mask;     // one byte per cell: the candidates that are not eligible
+    DeviceBuf<T> d_rows, d_stage;  // several devices: the chunk's rows added in device order, one device's part
+    DeviceBuf<uint32_t> d_node;    // [chunk][k] selected nodes
+    DeviceBuf<T> d_val;            // [chunk][k] their cells
+};
+
 // Query scores (bisbm_query_scores.hip).  The sums belong to the engine that owns the graph on a device (a plain handle, the
-// container of shape groups, a device entry); the container of device entries keeps the host side (n, q, off) only.  The scratch
-// of bisbm_query_scores_topk is on the engine whose device selects (a plain handle, the first device entry).
+// container of shape groups, a device entry); the container of device entries keeps the host side (n, q, off) only.
 struct QueryScoreState {
     uint32_t n = 0;               // queries set (0: none)
     uint32_t n_a = 0;             // ... of type a
@@ -219,15 +232,12 @@ struct QueryScoreState {
     DeviceBuf<uint64_t> d_off;    // [n + 1] `off`
     DeviceBuf<uint32_t> d_list;   // [n] indices of the type-a queries, then of the type-b queries, each ascending
     DeviceBuf<double> d_sum;      // [off[n]] running sums, query by query, candidates in id order
-    DeviceBuf<uint8_t> d_mask;    // topk: neighbour mask of one chunk of queries
-    DeviceBuf<double> d_rows, d_stage;  // topk over several devices: the chunk's rows added in device order, one device's part
-    DeviceBuf<uint32_t> d_node;   // topk: [chunk][k] selected nodes
-    DeviceBuf<double> d_val;      // topk: [chunk][k] their sums
+    DeviceBuf<TopkCand> d_cand;   // [n] topk: every query's first candidate (the other type's first node), no self
+    TopkScratch<double> topk;
 };
 
 // Co-assignment (bisbm_coassign.hip).  As QueryScoreState: the counts belong to the engine that owns the graph on a device, the
-// container of device entries keeps the host side (n, q, off) only, the scratch of bisbm_coassign_topk is on the engine whose
-// device selects.
+// container of device entries keeps the host side (n, q, off) only.
 struct CoassignState {
     uint32_t n = 0;               // queries set (0: none)
     uint32_t n_a = 0;             // ... of type a
@@ -241,14 +251,13 @@ struct CoassignState {
     DeviceBuf<uint32_t> d_slot;   // [q_slots] query index of every slot of d_qlab, 0xffffffff: padding
     DeviceBuf<uint32_t> d_qlab;   // [chains of the engine sampled][q_slots] the queries' labels of one sample
     DeviceBuf<uint32_t> d_count;  // [off[n]] counts, query by query, candidates in id order
-    DeviceBuf<uint32_t> d_rows, d_stage;  // topk over several devices: the chunk's rows added up, one device's part
-    DeviceBuf<uint32_t> d_node;   // topk: [chunk][k] selected nodes
-    DeviceBuf<uint32_t> d_val;    // topk: [chunk][k] their counts
+    DeviceBuf<TopkCand> d_cand;   // [n] topk: every query's first candidate (its own type's first node) and its own cell
+    TopkScratch<uint32_t> topk;
 };
 
 // Fold-in queries (bisbm_foldin.hip).  As QueryScoreState: the sums, the tables and the posteriors of the last sample belong to
-// the engine that owns the graph on a device, the container of device entries keeps the host side only, the scratch of
-// bisbm_foldin_topk is on the engine whose device selects.  A row kind that is not kept has no cells (its `off` is all 0).
+// the engine that owns the graph on a device, the container of device entries keeps the host side only.  A row kind that is not
+// kept has no cells (its `off` is all 0).
 struct FoldinState {
     uint32_t n = 0;               // virtual nodes set (0: none)
     uint32_t n_a = 0;             // ... of type a
@@ -260,7 +269,7 @@ struct FoldinState {
     std::vector<uint32_t> list;   // the lists
     std::vector<uint32_t> slot;   // [n] slot of every virtual node: the type-a ones in order, then the type-b ones
     std::vector<uint64_t> off[2]; // [n + 1] first cell of every node's recommend / similar row
-    DeviceBuf<uint8_t> d_type;    // [n] `type`
+    DeviceBuf<TopkCand> d_cand[2];  // [n] topk: the first candidate of every node's recommend / similar row, no self
     DeviceBuf<uint64_t> d_ptr;    // [n + 1] `ptr`
     DeviceBuf<uint32_t> d_nbr;    // `list`
     DeviceBuf<uint32_t> d_order;  // [n] caller's index of every slot
@@ -275,10 +284,7 @@ struct FoldinState {
         std::vector<uint32_t> chain;
     };
     std::vector<Segment> segments;
-    DeviceBuf<uint8_t> d_mask;    // topk: mask of the listed nodes of one chunk
-    DeviceBuf<double> d_rows, d_stage;  // topk over several devices: the chunk's rows added in device order, one device's part
-    DeviceBuf<uint32_t> d_node;   // topk: [chunk][k] selected nodes
-    DeviceBuf<double> d_val;      // topk: [chunk][k] their sums
+    TopkScratch<double> topk;
 };
 
 // Node conditionals (bisbm_conditionals.hip).  As FoldinState: the sums, the soft marginals and the rows of the last sample belong
@@ -527,14 +533,16 @@ int fail(bisbm_engine* h, int code, const char* fmt, ...) __attribute__((format(
     } while (0)
 
 // room for `count` elements in a DeviceBuf, or the call fails with the function, the buffer and the size in the message
-#define RESERVE(h, buf, count)                                                                                                \
-    do {                                                                                                                      \
-        const size_t n_ = (count);                                                                                            \
-        hipError_t e_ = (buf).reserve(n_);                                                                                    \
-        if (e_ != hipSuccess)                                                                                                 \
-            return fail((h), BISBM_ERR_HIP, "%s: %zu bytes of device memory for " #buf " could not be allocated: %s", __func__, \
-                        n_ * sizeof(*(buf).get()), hipGetErrorString(e_));                                                    \
+// (RESERVE_AS: the function is the C call a shared helper works for)
+#define RESERVE_AS(h, fn, buf, count)                                                                                       \
+    do {                                                                                                                    \
+        const size_t n_ = (count);                                                                                          \
+        hipError_t e_ = (buf).reserve(n_);                                                                                  \
+        if (e_ != hipSuccess)                                                                                               \
+            return fail((h), BISBM_ERR_HIP, "%s: %zu bytes of device memory for " #buf " could not be allocated: %s", (fn), \
+                        n_ * sizeof(*(buf).get()), hipGetErrorString(e_));                                                  \
     } while (0)
+#define RESERVE(h, buf, count) RESERVE_AS(h, __func__, buf, count)
 
 void free_chain_arrays(bisbm_engine* h);
 void free_all(bisbm_engine* h);
@@ -673,6 +681,41 @@ std::vector<bisbm_engine*> device_entries(bisbm_engine* h);
 // the engines that run kernels under the handle (a plain handle; its groups; the device entries and their groups), in device
 // order, then group order
 std::vector<bisbm_engine*> leaves(bisbm_engine* h);
+// f(device entry) of every device entry, in device order
+template <class F>
+auto per_device(bisbm_engine* h, F f) {
+    std::vector<decltype(f(h))> out;
+    for (bisbm_engine* d : device_entries(h)) out.push_back(f(d));
+    return out;
+}
+// the chain terms all device entries have added since the last set / reset of the feature whose state is `state`
+template <class S>
+uint64_t total_terms(bisbm_engine* h, S bisbm_engine::*state) {
+    uint64_t t = 0;
+    for (bisbm_engine* d : device_entries(h)) t += (d->*state).terms;
+    return t;
+}
+// the indices of the type-a queries (q[i] < na), then of the type-b ones, each ascending, into `list`; returns how many are type a
+inline uint32_t partition_by_type(const std::vector<uint32_t>& q, uint64_t na, std::vector<uint32_t>& list) {
+    list.resize(q.size());
+    std::iota(list.begin(), list.end(), 0u);
+    return (uint32_t)(std::stable_partition(list.begin(), list.end(), [&](uint32_t i) { return q[i] < na; }) - list.begin());
+}
+
+// ---- rows of cells per query, one set per device entry (bisbm_topk.hip; T: uint32_t, double) ------------------------------
+// `cells`: every device entry's cells, in device order (per_device).  `len` cells from cell `at` on into `out`: over several
+// devices the entries' cells added on the host in device order.
+template <class T>
+int read_row(bisbm_engine* h, const std::vector<const T*>& cells, uint64_t at, size_t len, T* out);
+// The tail of the three *_topk calls (`fn`: the call's name, for the messages): the best k candidates of every query into
+// node_out / val_out ([queries][k]; val_out may be NULL).  off: the host's first cell of every query's row; w, d_off, d_cand:
+// the scratch and the tables of the first device entry, which selects; lists: what to mask, NULL: nothing.  Walks the queries in
+// chunks of at most kTopkChunkCells cells (BISBM_TOPK_CHUNK_CELLS=<n> in the environment, read at every call: n instead, for the
+// tests), never less than one query.
+template <class T>
+int topk_select(bisbm_engine* h, const char* fn, const std::vector<const T*>& cells, const std::vector<uint64_t>& off, TopkScratch<T>& w,
+                const uint64_t* d_off, const TopkCand* d_cand, const TopkMaskLists* lists, uint32_t k, uint32_t* node_out, T* val_out);
+
 bool any_grouped(bisbm_engine* h);  // does the handle, or one of its device entries, keep its chains grouped by shape?
 bool any_wide(bisbm_engine* h);     // does some leaf hold two-byte labels?
 // the leaf that runs chain `chain` of the handle, and the chain's index there

@@ -1,8 +1,8 @@
 // bisbm_foldin.hip -- fold-in queries: a node that is NOT in the graph, given by its type and a list of neighbours of the other
 // type, gets a block posterior per chain by the naive-Bayes rule the engine draws its proposals with, and from it an expected
 // edge count to every node of the other type (recommend rows) and a soft co-assignment with every node of its own type (similar
-// rows), pooled over the chains; the best k of a row are selected on the device (no reference counterpart; include/bisbm.h,
-// "Fold-in queries", states every f64 operation and its order: a sequential host loop gives the same bits).
+// rows), pooled over the chains; the best k of a row are selected on the device by bisbm_topk.hip (no reference counterpart;
+// include/bisbm.h, "Fold-in queries", states every f64 operation and its order: a sequential host loop gives the same bits).
 //
 // Table kernel: one workgroup per (chain, virtual node), lane <-> block.  The factor loop runs over the list in list order
 // inside every lane (the order is part of the definition), the neighbours' labels gathered 256 at a time into LDS.  The chain's
@@ -11,15 +11,16 @@
 // workgroups are neighbours in the grid, and 64 KiB of LDS per workgroup would leave two workgroups per CU.  The max, Z and the
 // table's sums keep their ascending-block order: Z is added by one lane, every lane adds its own table entry.
 //
-// Rows kernel: the shape of query_scores_kernel.  A workgroup owns kFoldinCandTile candidates (a lane reads its four labels as
-// one word of the chain's label row) x kFoldinTile virtual nodes of one type and row kind, keeps the running sums in registers
-// and walks the chains of the launch in ascending order: per chain the tile's table rows (g or P, at most 255 doubles each) go
-// to LDS (two buffers: one barrier per chain), a cell is one LDS lookup, for a recommend row one multiply, and one f64 add.
+// Rows kernel: the shape of query_scores_kernel.  A workgroup owns kFoldinCandTile candidates x kFoldinTile virtual nodes of one
+// type and row kind (bisbm_cand_lanes.hpp), keeps the running sums in registers and walks the chains of the launch in ascending
+// order: per chain the tile's table rows (g or P, at most 255 doubles each) go to LDS (two buffers: one barrier per chain), a cell
+// is one LDS lookup, for a recommend row one multiply, and one f64 add.
 //
-// Top-k: the selection of bisbm_query_scores.hip (exact radix select on the bit patterns of the non-negative sums, ordered
-// compaction, rank sort), written again here because a virtual node has no id to derive its candidate range from.
+// Top-k: the selection of bisbm_topk.hip on the bit patterns of the sums, one table of first candidates per row kind; with the
+// listed nodes left out, a virtual node's list is the list that masks.
 #include <climits>
 
+#include "bisbm_cand_lanes.hpp"
 #include "bisbm_engine.hpp"
 
 using namespace bisbm;
@@ -120,21 +121,13 @@ template <bool REC>
 __global__ __launch_bounds__(256) void foldin_rows_kernel(FoldinRowsParams p) {
     __shared__ double tabs[2][kFoldinTile * kRowStride];
     __shared__ double q_deg[kFoldinTile];
-    const uint32_t first = p.first, n_cand = p.n_cand;
     const uint32_t cand_tile = blockIdx.x % p.cand_tiles, q0 = (p.q_tile0 + blockIdx.x / p.cand_tiles) * kFoldinTile;
     const uint32_t nq = min(kFoldinTile, p.n_list - q0);
 
-    // lane t holds the four nodes of label word w; the ones outside the candidates are never looked up or stored
-    const uint32_t w = (first >> 2) + cand_tile * kLanes + threadIdx.x;
-    const bool any = (uint64_t)w * 4 < (uint64_t)first + n_cand;
-    bool valid[4];
+    const CandLanes cl = cand_lanes(p.first, p.n_cand, cand_tile);
     double dv[4];
 #pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) {
-        const uint64_t v = (uint64_t)w * 4 + j;
-        valid[j] = v >= first && v < (uint64_t)first + n_cand;
-        dv[j] = (REC && valid[j]) ? (double)(p.rowptr[v + 1] - p.rowptr[v]) : 0.;
-    }
+    for (uint32_t j = 0; j < 4; ++j) dv[j] = (REC && cl.valid[j]) ? (double)(p.rowptr[cl.node(j) + 1] - p.rowptr[cl.node(j)]) : 0.;
     if (threadIdx.x < nq) {
         const uint32_t qi = p.order[p.slot0 + q0 + threadIdx.x];
         q_deg[threadIdx.x] = (double)(p.ptr[qi + 1] - p.ptr[qi]);
@@ -144,7 +137,7 @@ __global__ __launch_bounds__(256) void foldin_rows_kernel(FoldinRowsParams p) {
     for (uint32_t i = 0; i < kFoldinTile; ++i) {
         const double* row = i < nq ? p.sum + p.off[p.order[p.slot0 + q0 + i]] : nullptr;
 #pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) acc[i][j] = (i < nq && valid[j]) ? row[(uint64_t)w * 4 + j - first] : 0.;
+        for (uint32_t j = 0; j < 4; ++j) acc[i][j] = (i < nq && cl.valid[j]) ? row[cl.node(j) - p.first] : 0.;
     }
     __syncthreads();
 
@@ -161,10 +154,10 @@ __global__ __launch_bounds__(256) void foldin_rows_kernel(FoldinRowsParams p) {
         }
         __syncthreads();
         buf ^= 1u;
-        const uint32_t word = any ? *(const uint32_t*)(lab + (size_t)w * 4) : 0u;
+        const uint32_t word = cl.any ? *(const uint32_t*)(lab + (size_t)cl.w * 4) : 0u;
         uint32_t bv[4];
 #pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) bv[j] = valid[j] ? ((word >> (8 * j)) & 255u) - p.lab0 : 0u;
+        for (uint32_t j = 0; j < 4; ++j) bv[j] = cl.valid[j] ? ((word >> (8 * j)) & 255u) - p.lab0 : 0u;
 #pragma unroll
         for (uint32_t i = 0; i < kFoldinTile; ++i) {
             if (i >= nq) break;  // (the same for every lane)
@@ -183,113 +176,7 @@ __global__ __launch_bounds__(256) void foldin_rows_kernel(FoldinRowsParams p) {
         double* row = p.sum + p.off[p.order[p.slot0 + q0 + i]];
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j)
-            if (valid[j]) row[(uint64_t)w * 4 + j - first] = acc[i][j];
-    }
-}
-
-__device__ __forceinline__ void candidates_of(const FoldinSelectParams& p, uint32_t qi, uint32_t* first, uint32_t* n_cand) {
-    const bool cand_b = p.similar ? p.type[qi] != 0 : p.type[qi] == 0;
-    *first = cand_b ? p.na : 0u;
-    *n_cand = cand_b ? p.n - p.na : p.na;
-}
-
-// one workgroup per virtual node of the chunk: every entry of its list marks its cell (a repeated entry marks it again)
-__global__ __launch_bounds__(256) void foldin_mask_kernel(FoldinSelectParams p, uint8_t* mask) {
-    const uint32_t qi = p.q0 + blockIdx.x;
-    uint32_t first, n_cand;
-    candidates_of(p, qi, &first, &n_cand);
-    uint8_t* row = mask + (p.off[qi] - p.off[p.q0]);
-    for (uint64_t e = p.ptr[qi] + threadIdx.x; e < p.ptr[qi + 1]; e += blockDim.x) {
-        const uint32_t x = p.nbr[e] - first;
-        if (x < n_cand) row[x] = 1;
-    }
-}
-
-__global__ __launch_bounds__(256) void foldin_select_kernel(FoldinSelectParams p) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t wsum[2][2][kLanes / 64];
-    __shared__ unsigned long long s_key[kQueryMaxK];
-    __shared__ uint32_t s_id[kQueryMaxK];
-    __shared__ unsigned long long s_prefix;
-    __shared__ uint32_t s_remaining, s_eligible;
-    const uint32_t qi = p.q0 + blockIdx.x;
-    uint32_t first, n_cand;
-    candidates_of(p, qi, &first, &n_cand);
-    const uint64_t cell0 = p.off[qi] - p.off[p.q0];
-    const unsigned long long* key = (const unsigned long long*)(p.rows + cell0);
-    const uint8_t* mask = p.mask ? p.mask + cell0 : nullptr;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t* node_out = p.node_out + (size_t)blockIdx.x * p.k;
-    double* sum_out = p.sum_out + (size_t)blockIdx.x * p.k;
-
-    if (tid == 0) s_eligible = 0;
-    __syncthreads();
-    uint32_t mine = 0;
-    for (uint32_t i = tid; i < n_cand; i += kLanes) mine += !(mask && mask[i]);
-    if (mine) atomicAdd(&s_eligible, mine);
-    __syncthreads();
-    const uint32_t kk = min(p.k, s_eligible);
-    for (uint32_t e = kk + tid; e < p.k; e += kLanes) node_out[e] = 0xffffffffu, sum_out[e] = 0.;
-    if (kk == 0) return;
-
-    // the kk-th largest eligible key, byte by byte from the top: `prefix` holds the bytes found, `remaining` the rank within them
-    if (tid == 0) s_prefix = 0, s_remaining = kk;
-    for (int b = 7; b >= 0; --b) {
-        hist[tid] = 0;
-        __syncthreads();
-        const unsigned long long prefix = s_prefix;
-        for (uint32_t i = tid; i < n_cand; i += kLanes) {
-            if (mask && mask[i]) continue;
-            const unsigned long long x = key[i];
-            if (b == 7 || (x >> (8 * (b + 1))) == (prefix >> (8 * (b + 1)))) atomicAdd(&hist[(x >> (8 * b)) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t rem = s_remaining, bin = 255;
-            while (bin > 0 && hist[bin] < rem) rem -= hist[bin], --bin;  // (the bins hold at least `rem` keys in all)
-            s_remaining = rem;
-            s_prefix = prefix | ((unsigned long long)bin << (8 * b));
-        }
-        __syncthreads();
-    }
-    const unsigned long long kth = s_prefix;
-    const uint32_t n_ties = s_remaining, n_greater = kk - n_ties;  // ties to take (>= 1), keys above the k-th
-
-    // ordered compaction: the larger keys into [0, n_greater), the first n_ties ties in id order behind them
-    uint32_t g_base = 0, t_base = 0, it = 0;
-    for (uint32_t s = 0; s < n_cand && (g_base < n_greater || t_base < n_ties); s += kLanes, it ^= 1u) {
-        const uint32_t i = s + tid;
-        const bool in = i < n_cand && !(mask && mask[i]);
-        const unsigned long long x = in ? key[i] : 0ull;
-        const bool isg = in && x > kth, ist = in && x == kth;
-        const unsigned long long bg = __ballot(isg), bt = __ballot(ist), below = (1ull << lane) - 1ull;
-        if (lane == 0) wsum[it][0][wave] = (uint32_t)__popcll(bg), wsum[it][1][wave] = (uint32_t)__popcll(bt);
-        __syncthreads();  // (the other buffer is written next: one barrier per chunk)
-        uint32_t g_off = 0, t_off = 0, g_all = 0, t_all = 0;
-        for (uint32_t k = 0; k < kLanes / 64; ++k) {
-            if (k < wave) g_off += wsum[it][0][k], t_off += wsum[it][1][k];
-            g_all += wsum[it][0][k], t_all += wsum[it][1][k];
-        }
-        if (isg) {
-            const uint32_t pos = g_base + g_off + (uint32_t)__popcll(bg & below);
-            if (pos < n_greater) s_key[pos] = x, s_id[pos] = i;
-        }
-        if (ist) {
-            const uint32_t pos = t_base + t_off + (uint32_t)__popcll(bt & below);
-            if (pos < n_ties) s_key[n_greater + pos] = x, s_id[n_greater + pos] = i;
-        }
-        g_base += g_all, t_base += t_all;
-    }
-    __syncthreads();
-
-    // rank of every entry among the kk: (key descending, id ascending); the ids differ, so the ranks are a permutation
-    for (uint32_t e = tid; e < kk; e += kLanes) {
-        const unsigned long long x = s_key[e];
-        const uint32_t id = s_id[e];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < kk; ++j) rank += (s_key[j] > x) || (s_key[j] == x && s_id[j] < id);
-        node_out[rank] = first + id;
-        sum_out[rank] = __longlong_as_double((long long)x);
+            if (cl.valid[j]) row[cl.node(j) - p.first] = acc[i][j];
     }
 }
 
@@ -306,39 +193,19 @@ hipError_t launch_foldin_tables(const FoldinTableParams& p, hipStream_t stream) 
 hipError_t launch_foldin_rows(const FoldinRowsParams& p_in, bool recommend, hipStream_t stream) {
     FoldinRowsParams p = p_in;
     if (p.n_list == 0 || p.n_cand == 0 || p.n_chains == 0) return hipSuccess;
-    const uint64_t first = p.first, words = ((first + p.n_cand - 1) >> 2) - (first >> 2) + 1;
-    p.cand_tiles = (uint32_t)((words + kLanes - 1) / kLanes);
-    // workgroup = candidate tile + cand_tiles * tile of virtual nodes, as many of the latter per launch as a one-dimensional grid holds
-    const uint32_t q_tiles = (p.n_list + kFoldinTile - 1) / kFoldinTile, per_launch = std::max(1u, (1u << 30) / p.cand_tiles);
-    for (p.q_tile0 = 0; p.q_tile0 < q_tiles; p.q_tile0 += per_launch) {
-        const dim3 grid(p.cand_tiles * std::min(per_launch, q_tiles - p.q_tile0));
+    return for_cand_grids(p.first, p.n_cand, p.n_list, kFoldinTile, [&](uint32_t cand_tiles, uint32_t q_tile0, dim3 grid) {
+        p.cand_tiles = cand_tiles, p.q_tile0 = q_tile0;
         if (recommend)
             hipLaunchKernelGGL(foldin_rows_kernel<true>, grid, dim3(kLanes), 0, stream, p);
         else
             hipLaunchKernelGGL(foldin_rows_kernel<false>, grid, dim3(kLanes), 0, stream, p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t launch_foldin_mask(const FoldinSelectParams& p, uint8_t* mask, hipStream_t stream) {
-    if (p.n_q == 0) return hipSuccess;
-    hipLaunchKernelGGL(foldin_mask_kernel, dim3(p.n_q), dim3(256), 0, stream, p, mask);
-    return hipGetLastError();
-}
-
-hipError_t launch_foldin_select(const FoldinSelectParams& p, hipStream_t stream) {
-    if (p.n_q == 0) return hipSuccess;
-    hipLaunchKernelGGL(foldin_select_kernel, dim3(p.n_q), dim3(kLanes), 0, stream, p);
-    return hipGetLastError();
+    });
 }
 
 }  // namespace bisbm
 
 namespace {
 
-constexpr uint64_t kTopkChunkCells = 1ull << 24;  // cells of one chunk of virtual nodes in bisbm_foldin_topk (at least one node)
 constexpr uint32_t kKinds = BISBM_FOLDIN_RECOMMEND | BISBM_FOLDIN_SIMILAR;
 
 const char* kNoQueries = "no virtual nodes: call bisbm_foldin_set first";
@@ -392,10 +259,9 @@ int add_sample(bisbm_engine* h, bisbm_engine* e, const FoldinState::Segment& seg
     return BISBM_OK;
 }
 
-uint64_t total_terms(bisbm_engine* h) {
-    uint64_t t = 0;
-    for (bisbm_engine* d : device_entries(h)) t += d->foldin.terms;
-    return t;
+// every device entry's rows of one kind
+std::vector<const double*> sums_of(bisbm_engine* h, int kind) {
+    return per_device(h, [kind](bisbm_engine* d) { return (const double*)d->foldin.d_sum[kind].get(); });
 }
 
 // which of the two row kinds `what` names: 0 recommend, 1 similar; refusals as BISBM_ERR_INVALID_ARG
@@ -463,6 +329,9 @@ int bisbm_foldin_set(bisbm_handle h, uint32_t n_queries, const uint8_t* type, co
         f.slot[i] = type[i] ? at_b++ : at_a++;
         order[f.slot[i]] = i;
     }
+    std::vector<TopkCand> cand[2];  // a row's first candidate, every candidate eligible: type b's first node where `off` counted nb
+    for (int kind = 0; kind < 2; ++kind)
+        for (uint32_t i = 0; i < n_queries; ++i) cand[kind].push_back(TopkCand{(type[i] != 0) == (kind == 1) ? (uint32_t)h->na : 0u, 0xffffffffu});
     hipError_t e = hipSuccess;
     for (int kind = 0; kind < 2 && e == hipSuccess; ++kind) {
         const size_t cells = (size_t)f.off[kind][n_queries];
@@ -473,20 +342,21 @@ int bisbm_foldin_set(bisbm_handle h, uint32_t n_queries, const uint8_t* type, co
                         cells * sizeof(double), kind ? "similar" : "recommend", n_queries, hipGetErrorString(e));
         e = hipMemsetAsync(f.d_sum[kind].get(), 0, sizeof(double) * cells, h->stream);
     }
-    if (e == hipSuccess) e = f.d_type.reserve(n_queries);
     if (e == hipSuccess) e = f.d_ptr.reserve((size_t)n_queries + 1);
     if (e == hipSuccess) e = f.d_nbr.reserve(f.list.size());
     if (e == hipSuccess) e = f.d_order.reserve(n_queries);
     if (e == hipSuccess) e = f.d_off[0].reserve((size_t)n_queries + 1);
     if (e == hipSuccess) e = f.d_off[1].reserve((size_t)n_queries + 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(f.d_type.get(), f.type.data(), n_queries, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(f.d_ptr.get(), f.ptr.data(), sizeof(uint64_t) * ((size_t)n_queries + 1), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(f.d_nbr.get(), f.list.data(), sizeof(uint32_t) * f.list.size(), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(f.d_order.get(), order.data(), sizeof(uint32_t) * n_queries, hipMemcpyHostToDevice, h->stream);
-    for (int kind = 0; kind < 2; ++kind)
+    for (int kind = 0; kind < 2; ++kind) {
+        if (e == hipSuccess) e = f.d_cand[kind].reserve(n_queries);
         if (e == hipSuccess)
             e = hipMemcpyAsync(f.d_off[kind].get(), f.off[kind].data(), sizeof(uint64_t) * ((size_t)n_queries + 1), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (`order` and f's vectors are read until here)
+        if (e == hipSuccess) e = hipMemcpyAsync(f.d_cand[kind].get(), cand[kind].data(), sizeof(TopkCand) * n_queries, hipMemcpyHostToDevice, h->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (`order`, `cand` and f's vectors are read until here)
     if (e != hipSuccess) return fail(h, BISBM_ERR_HIP, "bisbm_foldin_set: %s", hipGetErrorString(e));
     h->foldin = std::move(f);
     return BISBM_OK;
@@ -587,23 +457,10 @@ int bisbm_foldin_get_row(bisbm_handle h, uint32_t what, uint32_t query_index, do
     int kind = 0;
     if (int rc = kind_of(h, what, &kind)) return rc;
     if (query_index >= s.n) return fail(h, BISBM_ERR_INVALID_ARG, "query index %u: %u virtual nodes are set", query_index, s.n);
-    if (terms_out) *terms_out = total_terms(h);
+    if (terms_out) *terms_out = total_terms(h, &bisbm_engine::foldin);
     if (!sum_out) return BISBM_OK;
     const std::vector<uint64_t>& off = s.off[kind];
-    const size_t len = (size_t)(off[query_index + 1] - off[query_index]);
-    DeviceGuard keep;
-    std::vector<double> part(h->devs.empty() ? 0 : len);
-    bool first = true;
-    for (bisbm_engine* d : device_entries(h)) {  // (several devices: the device rows are added on the host in device order)
-        HIPCHK(h, hipSetDevice(d->device));
-        HIPCHK(h, hipStreamSynchronize(d->stream));
-        double* dst = h->devs.empty() ? sum_out : part.data();
-        HIPCHK(h, hipMemcpy(dst, d->foldin.d_sum[kind].get() + off[query_index], sizeof(double) * len, hipMemcpyDeviceToHost));
-        if (!h->devs.empty())
-            for (size_t i = 0; i < len; ++i) sum_out[i] = first ? part[i] : sum_out[i] + part[i];
-        first = false;
-    }
-    return BISBM_OK;
+    return read_row(h, sums_of(h, kind), off[query_index], (size_t)(off[query_index + 1] - off[query_index]), sum_out);
 }
 
 int bisbm_foldin_topk(bisbm_handle h, uint32_t what, uint32_t k, int exclude_listed, uint32_t* node_out, double* sum_out, uint64_t* terms_out) {
@@ -617,55 +474,13 @@ int bisbm_foldin_topk(bisbm_handle h, uint32_t what, uint32_t k, int exclude_lis
     if (k == 0) return fail(h, BISBM_ERR_INVALID_ARG, "k is 0");
     if (k > kQueryMaxK) return fail(h, BISBM_ERR_UNSUPPORTED, "k = %u: bisbm_foldin_topk selects at most %u candidates per virtual node", k, kQueryMaxK);
     if (!node_out) return fail(h, BISBM_ERR_INVALID_ARG, "node_out is NULL");
-    const uint64_t terms = total_terms(h);
+    const uint64_t terms = total_terms(h, &bisbm_engine::foldin);
     if (!terms) return fail(h, BISBM_ERR_STATE, "no sample yet: call bisbm_foldin_accumulate before bisbm_foldin_topk");
     if (terms_out) *terms_out = terms;
-    const std::vector<bisbm_engine*> entries = device_entries(h);
-    bisbm_engine* e = entries[0];  // the device that selects
-    FoldinState& w = e->foldin;
-    const std::vector<uint64_t>& off = s.off[kind];
-    DeviceGuard keep;
-    for (bisbm_engine* d : entries) {  // (the sums of every device are complete)
-        HIPCHK(h, hipSetDevice(d->device));
-        HIPCHK(h, hipStreamSynchronize(d->stream));
-    }
-    HIPCHK(h, hipSetDevice(e->device));
-    for (uint32_t q0 = 0; q0 < s.n;) {
-        uint32_t q1 = q0 + 1;
-        while (q1 < s.n && off[q1 + 1] - off[q0] <= kTopkChunkCells) ++q1;
-        const size_t cells = (size_t)(off[q1] - off[q0]), n_q = q1 - q0;
-        FoldinSelectParams p{};
-        p.n = (uint32_t)h->n, p.na = (uint32_t)h->na, p.q0 = q0, p.n_q = (uint32_t)n_q, p.k = k, p.similar = kind == 1;
-        p.type = w.d_type.get(), p.off = w.d_off[kind].get(), p.ptr = w.d_ptr.get(), p.nbr = w.d_nbr.get();
-        p.rows = w.d_sum[kind].get() + off[q0];
-        if (entries.size() > 1) {  // the other devices' rows are added onto a copy of the first device's, in device order
-            RESERVE(h, w.d_rows, cells);
-            RESERVE(h, w.d_stage, cells);
-            HIPCHK(h, hipMemcpyAsync(w.d_rows.get(), p.rows, sizeof(double) * cells, hipMemcpyDeviceToDevice, e->stream));
-            for (size_t j = 1; j < entries.size(); ++j) {
-                HIPCHK(h, hipMemcpyPeerAsync(w.d_stage.get(), e->device, entries[j]->foldin.d_sum[kind].get() + off[q0], entries[j]->device,
-                                             sizeof(double) * cells, e->stream));
-                HIPCHK(h, launch_query_rows_add(w.d_rows.get(), w.d_stage.get(), cells, e->stream));
-            }
-            p.rows = w.d_rows.get();
-        }
-        if (exclude_listed) {
-            RESERVE(h, w.d_mask, cells);
-            HIPCHK(h, hipMemsetAsync(w.d_mask.get(), 0, cells, e->stream));
-            HIPCHK(h, launch_foldin_mask(p, w.d_mask.get(), e->stream));
-            p.mask = w.d_mask.get();
-        }
-        RESERVE(h, w.d_node, n_q * k);
-        RESERVE(h, w.d_val, n_q * k);
-        p.node_out = w.d_node.get();
-        p.sum_out = w.d_val.get();
-        HIPCHK(h, launch_foldin_select(p, e->stream));
-        HIPCHK(h, hipMemcpyAsync(node_out + (size_t)q0 * k, w.d_node.get(), sizeof(uint32_t) * n_q * k, hipMemcpyDeviceToHost, e->stream));
-        if (sum_out) HIPCHK(h, hipMemcpyAsync(sum_out + (size_t)q0 * k, w.d_val.get(), sizeof(double) * n_q * k, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(h, hipStreamSynchronize(e->stream));  // (the scratch is reused by the next chunk)
-        q0 = q1;
-    }
-    return BISBM_OK;
+    FoldinState& w = device_entries(h)[0]->foldin;  // the device that selects
+    const TopkMaskLists listed{nullptr, w.d_ptr.get(), nullptr, w.d_nbr.get()};  // a virtual node's list
+    return topk_select(h, __func__, sums_of(h, kind), s.off[kind], w.topk, w.d_off[kind].get(), w.d_cand[kind].get(), exclude_listed ? &listed : nullptr,
+                       k, node_out, sum_out);
 }
 
 }  // extern "C"

@@ -214,15 +214,31 @@ struct QueryScoreParams {
 constexpr uint32_t kQueryCandTile = 1024;  // candidates per workgroup: 256 lanes, one word of 4 labels each
 constexpr uint32_t kQueryTile = 8;         // queries per workgroup
 constexpr uint32_t kQueryMaxK = 1024;      // bisbm_query_scores_topk: the largest k (the selection is kept in LDS)
-// Selection of one chunk of queries (q0 .. q0 + n_q - 1): rows / mask hold the chunk's cells from cell off[q0] on.
-struct QuerySelectParams {
-    uint32_t n, na, q0, n_q, k;
-    const uint32_t* queries;
-    const uint64_t* off;
-    const double* rows;
-    const uint8_t* mask;  // 1: not eligible; NULL: every candidate is
-    uint32_t* node_out;   // [n_q][k] global node ids in rank order, 0xffffffff past the eligible ones
-    double* sum_out;      // [n_q][k]
+
+// Top-k selection (bisbm_topk.hip): the best k candidates of every query of one chunk (q0 .. q0 + n_q - 1), for query scores,
+// co-assignment and fold-in rows alike.  The candidates of query qi are the off[qi + 1] - off[qi] cells of its row, in id order;
+// rows / mask hold the chunk's cells from cell off[q0] on.  A candidate is eligible iff it is not masked and is not `self`.
+struct TopkCand {
+    uint32_t first;  // node id of the query's first candidate (0 or na)
+    uint32_t self;   // index within the row of the one candidate that is never eligible (the query's own node); 0xffffffff: none
+};
+template <class Key>  // the bit pattern of a cell: uint32_t counts, unsigned long long for the non-negative f64 sums
+struct TopkSelectParams {
+    uint32_t q0, n_q, k;
+    const uint64_t* off;   // [n_queries + 1]
+    const TopkCand* cand;  // [n_queries]
+    const Key* rows;
+    const uint8_t* mask;   // 1: not eligible; NULL: no candidate is masked
+    uint32_t* node_out;    // [n_q][k] global node ids in rank order, 0xffffffff past the eligible ones
+    Key* val_out;          // [n_q][k] their cells, 0 past the eligible ones
+};
+// The lists whose entries are masked (device pointers): query qi's are col[ptr[i]] .. col[ptr[i + 1] - 1] with i = at[qi], or
+// i = qi where `at` is NULL.  The graph's CSR rows have uint32 offsets (ptr32), the lists of virtual nodes uint64 ones (ptr64).
+struct TopkMaskLists {
+    const uint32_t* ptr32;
+    const uint64_t* ptr64;
+    const uint32_t* at;
+    const uint32_t* col;
 };
 
 // Co-assignment (bisbm_coassign.hip): one sample of the chains of one engine into the rows of the queries of one type.  A
@@ -255,16 +271,6 @@ struct CoassignGatherParams {
     const uint8_t* labels;
     size_t label_stride;
     uint32_t* qlab;
-};
-// Selection of one chunk of queries (q0 .. q0 + n_q - 1): rows holds the chunk's cells from cell off[q0] on.  The query's own
-// node is the one candidate that is not eligible.
-struct CoassignSelectParams {
-    uint32_t n, na, q0, n_q, k;
-    const uint32_t* queries;
-    const uint64_t* off;
-    const uint32_t* rows;
-    uint32_t* node_out;   // [n_q][k] global node ids in rank order, 0xffffffff past the eligible ones
-    uint32_t* count_out;  // [n_q][k]
 };
 
 // Fold-in queries (bisbm_foldin.hip): virtual nodes given by a type and a list of neighbours of the other type.  The table kernel
@@ -309,20 +315,6 @@ struct FoldinRowsParams {
 };
 constexpr uint32_t kFoldinCandTile = 1024;  // candidates per workgroup: 256 lanes, one word of 4 labels each
 constexpr uint32_t kFoldinTile = 8;         // virtual nodes per workgroup
-// Selection of one chunk of virtual nodes (q0 .. q0 + n_q - 1, caller's order) of one row kind: rows / mask hold the chunk's
-// cells from cell off[q0] on.
-struct FoldinSelectParams {
-    uint32_t n, na, q0, n_q, k;
-    uint32_t similar;         // the candidates are the nodes of the virtual node's own type (else: of the other type)
-    const uint8_t* type;      // [n_queries] 0: a, 1: b
-    const uint64_t* off;
-    const uint64_t* ptr;      // [n_queries + 1] by caller's index (the mask kernel's)
-    const uint32_t* nbr;
-    const double* rows;
-    const uint8_t* mask;      // 1: not eligible; NULL: every candidate is
-    uint32_t* node_out;       // [n_q][k] global node ids in rank order, 0xffffffff past the eligible ones
-    double* sum_out;          // [n_q][k]
-};
 
 // Node conditionals (bisbm_conditionals.hip).  The rows kernel turns every (chain of the launch, query) into the node's rows dS[k_own]
 // and P[k_own] and the chain's four terms (stay, entropy, margin, free as 0.0 / 1.0); a chain that is not counted gets NaN.  One
@@ -566,18 +558,18 @@ hipError_t launch_pair_scores(const PairScoreParams& p, hipStream_t stream);
 hipError_t launch_pair_scores_fold(double* sum, const double* part, uint32_t slabs, uint32_t n_pairs, hipStream_t stream);
 uint32_t pair_score_slabs(uint64_t n_pairs, uint32_t n_chains);
 hipError_t launch_query_scores(const QueryScoreParams& p, hipStream_t stream);
-// mask[cell of (query, neighbour)] = 1 for every entry of the CSR rows of queries q0 .. q0 + n_q - 1 (mask: the chunk's, zeroed)
-hipError_t launch_query_mask(const uint32_t* rowptr, const uint32_t* col, const QuerySelectParams& p, uint8_t* mask, hipStream_t stream);
-hipError_t launch_query_select(const QuerySelectParams& p, hipStream_t stream);
-hipError_t launch_query_rows_add(double* a, const double* b, uint64_t count, hipStream_t stream);  // a += b
 hipError_t launch_coassign_gather(const CoassignGatherParams& p, bool wide, hipStream_t stream);
 hipError_t launch_coassign_count(const CoassignParams& p, bool wide, hipStream_t stream);
-hipError_t launch_coassign_select(const CoassignSelectParams& p, hipStream_t stream);
-hipError_t launch_coassign_rows_add(uint32_t* a, const uint32_t* b, uint64_t count, hipStream_t stream);  // a += b
 hipError_t launch_foldin_tables(const FoldinTableParams& p, hipStream_t stream);
 hipError_t launch_foldin_rows(const FoldinRowsParams& p, bool recommend, hipStream_t stream);
-hipError_t launch_foldin_mask(const FoldinSelectParams& p, uint8_t* mask, hipStream_t stream);  // the listed nodes of a chunk (mask: zeroed)
-hipError_t launch_foldin_select(const FoldinSelectParams& p, hipStream_t stream);
+// bisbm_topk.hip: mask[cell of (query, entry)] = 1 for every entry of the lists of queries q0 .. q0 + n_q - 1 (mask: the
+// chunk's, zeroed; off / cand as TopkSelectParams); the selection; a += b over `count` cells (Key / T: uint32_t and the 64-bit type)
+hipError_t launch_topk_mask(const TopkMaskLists& lists, uint32_t q0, uint32_t n_q, const uint64_t* off, const TopkCand* cand, uint8_t* mask,
+                            hipStream_t stream);
+template <class Key>
+hipError_t launch_topk_select(const TopkSelectParams<Key>& p, hipStream_t stream);
+template <class T>
+hipError_t launch_rows_add(T* a, const T* b, uint64_t count, hipStream_t stream);
 hipError_t launch_cond_rows(const CondRowsParams& p, hipStream_t stream);
 // the terms of n_chains chains ([chain][n_q][4]) onto stat[3][n_q] and free_cnt[n_q], chain by chain in ascending order
 hipError_t launch_cond_pool(const double* terms, uint32_t n_q, uint32_t n_chains, double* stat, unsigned long long* free_cnt, hipStream_t stream);
