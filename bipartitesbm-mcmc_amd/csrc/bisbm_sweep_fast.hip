@@ -43,6 +43,7 @@
 // Diagnostic hooks (BISBM_STAMPS, BISBM_ABLATE) are compiled out of the product build.
 #include "bisbm_kernels.hpp"
 #include "bisbm_move_word.hpp"
+#include "bisbm_pair_word.hpp"
 #include "bisbm_stand_rule.hpp"
 
 #include <algorithm>
@@ -166,7 +167,9 @@ __device__ unsigned long long g_pass_counts[kPassCounts];
 #define BISBM_PREDICT_TARGET 1
 #endif
 constexpr uint32_t kHistStride = 68;  // bytes per k_v row: 64 counters + pad (17 dwords: odd, conflict-free)
-constexpr uint32_t kHandWords = 9;    // v, row begin, degree, own label, pivot label, proposal word, packed hot-step inputs, accept uniform (2)
+// v, row begin, degree, own label, pivot label, proposal word, packed hot-step inputs, accept uniform (2), pair word (the one-stage
+// four-steps kernels: the step's clash tests against the three steps before it, bisbm_pair_word.hpp; unused elsewhere)
+constexpr uint32_t kHandWords = 10;
 constexpr uint32_t kRowCap = 255;     // longest row the feeder walks (a k_v counter is a byte); longer rows: per-step side path
 
 // a double constant held in a vector register pair for the whole kernel (64-bit literals are not encodable
@@ -216,9 +219,18 @@ __device__ __forceinline__ uint32_t rows4(unsigned long long b) {
 // The commit chain of a four-steps pass (step_quad, step_quad32).  nst: steps that exist; clash_bits: bit 4 i + j, step i, if it
 // moves, touches what step j read; mv4: steps that would move.  commit: bit j, steps 0..j all stand; moved: the moved bits of
 // committed steps only.
-__device__ __forceinline__ void commit_four(uint32_t nst, uint32_t clash_bits, uint32_t mv4, uint32_t& moved, uint32_t& commit) {
-    const uint32_t c01 = (clash_bits >> 1) & 1u, c02 = (clash_bits >> 2) & 1u, c03 = (clash_bits >> 3) & 1u;
-    const uint32_t c12 = (clash_bits >> 6) & 1u, c13 = (clash_bits >> 7) & 1u, c23 = (clash_bits >> 11) & 1u;
+// The pair (i, j) sits at bit 4 i + j of a word (PairsByLane4: lane 4 i + j tests it, clash_pairs) or at bit 16 j + (j - i - 1)
+// of the wave's ballot (PairsByRow: lane j - i - 1 of row j tests it, on the row's own pair word).
+struct PairsByLane4 {
+    static constexpr uint32_t p01 = 1, p02 = 2, p03 = 3, p12 = 6, p13 = 7, p23 = 11;
+};
+struct PairsByRow {
+    static constexpr uint32_t p01 = 16, p02 = 33, p03 = 50, p12 = 32, p13 = 49, p23 = 48;
+};
+template <class At, class Bits>
+__device__ __forceinline__ void commit_four(At, uint32_t nst, Bits clash_bits, uint32_t mv4, uint32_t& moved, uint32_t& commit) {
+    const uint32_t c01 = (uint32_t)(clash_bits >> At::p01) & 1u, c02 = (uint32_t)(clash_bits >> At::p02) & 1u, c03 = (uint32_t)(clash_bits >> At::p03) & 1u;
+    const uint32_t c12 = (uint32_t)(clash_bits >> At::p12) & 1u, c13 = (uint32_t)(clash_bits >> At::p13) & 1u, c23 = (uint32_t)(clash_bits >> At::p23) & 1u;
     const uint32_t m0 = mv4 & 1u;
     const uint32_t k1 = sflag(nst - 1u) & ((m0 & c01) ^ 1u);  // (nst >= 2)
     const uint32_t m1 = k1 & (mv4 >> 1) & 1u;
@@ -255,6 +267,13 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
     // the two-steps passes (step_pair, step_pair64) and the four-steps pass of the one-stage kernels (step_quad32 with OS) start
     // from a predicted inverse-CDF target (see prepare, step_pair and step_quad32)
     constexpr bool kPredictTarget = !K16 && (!Q32 || OS) && (BISBM_PREDICT_TARGET != 0);
+    // ... and there the feeder hands the four-steps pass its pair tests too (see prepare and step_quad32; the diagnostic build
+    // with pass counters keeps clash_pairs, which its counters read)
+#ifdef BISBM_PASS_COUNTS
+    constexpr bool kPairWord = false;
+#else
+    constexpr bool kPairWord = kPredictTarget && Q32 && OS;
+#endif
     const uint32_t row_cap = p.maxdeg < kRowCap ? p.maxdeg : kRowCap;  // neighbours walked per row by the feeder
     // LDS layout, dword offsets
     const uint32_t o_mq = 0, o_eta = ka * S;
@@ -618,6 +637,29 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                 // degree (<= 255 in the hot step), own block, pivot block and predicted target in one word (one cross-lane move per pass)
                 hand[6 * kWave + lane] = (deg_l & 255u) | ((rloc_l & 63u) << 8) | (tloc_l << 16) | (spred_l << 24);
                 *(double*)&hand[7 * kWave + 2 * lane] = ud_acc;  // (words 7, 8: the 64 accept uniforms as doubles)
+                // The pair word (bisbm_pair_word.hpp), for the four-steps pass that commits a row only on this prediction: whether the
+                // step d = 1, 2, 3 places ahead in the chunk, if it moves, touches what this step reads -- their blocks and predicted
+                // targets against this step's, and how many edges it would move in this step's column, a byte of the k_v row built
+                // above -- up to the step's own margins, which the pass has from its scan.  Steps on the general path, lanes past cnt
+                // and d > lane hold anything (blocks masked into range): no pass tests a pair that spans them.
+                if constexpr (kPairWord) {
+                    wfence();  // (the rows' counter bumps)
+                    const uint32_t rs_l = (rloc_l & 31u) | ((spred_l & 31u) << 8);
+                    // (the neighbours' addresses are worked out here, from an opaque copy of the lane number: left to the compiler they
+                    // are loop invariants of the whole kernel, held in registers the stepping wave does not have -- without the copy the
+                    // four one-stage kernels spill 12 to 130 vector registers, with it none)
+                    uint32_t lane_o = lane;
+                    __asm__ volatile("" : "+v"(lane_o));
+                    uint32_t f[3];
+#pragma unroll
+                    for (uint32_t d = 1; d <= 3u; ++d) {
+                        const uint32_t src = (lane_o - d) & 63u;
+                        const uint32_t rs_i = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)rs_l);
+                        const uint32_t k_i_tj = ((const uint8_t*)hist8w)[src * kHistStride + tloc_l];
+                        f[d - 1u] = pair_word_field(rs_i & 31u, rs_i >> 8, rloc_l & 31u, spred_l & 31u, k_i_tj);
+                    }
+                    hand[9 * kWave + lane] = pair_word(f[0], f[1], f[2]);
+                }
                 wfence();
             };
 
@@ -1647,7 +1689,7 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     const unsigned long long b_acc = accept_rows(dS, accu0, accu1, u_acc, qs, m_warm, b_can);  // per row
                     const uint32_t mv4 = rows4(b_can & b_acc), selfok4 = rows4(b_selfok);
                     uint32_t moved, commit;
-                    commit_four(nst, clash_bits, mv4, moved, commit);
+                    commit_four(PairsByLane4{}, nst, clash_bits, mv4, moved, commit);
 #ifdef BISBM_PASS_COUNTS
                     count_pairs((lane >> 2) & 3u, lane & 3u, lane < 16u, moved, commit, nst);
 #endif
@@ -1757,15 +1799,28 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     const double accu0 = butterfly_rows16(a0);  // every lane of a row: the row's sum
                     const double accu1 = butterfly_rows16(a1);
                     const double lq = hot_log_q(std::false_type{}, t.qn, t.qk, t.logn);
-                    // lane 4 i + j, any row: steps i and j, as in step_quad
-                    const uint32_t clash_bits =
-                        (uint32_t)clash_pairs(Four{}, r_loc, s_loc, t_loc, margins,
-                                              (int)(((lane >> 2) & 3u) << 6), (int)((lane & 3u) << 6), [&](int li, uint32_t t_j) {
+                    // The pair tests.  The one-stage kernels: every row still in the pass has the target the feeder predicted, so the
+                    // feeder has worked each pair out up to the later step's margins (the pair word of the row's own step,
+                    // bisbm_pair_word.hpp): lane d - 1 of row j tests steps j - d and j on the margins of the lane that holds s_j --
+                    // one LDS read, one cross-lane move; bit 16 j + d - 1 of the ballot.  (Rows past a wrong prediction carry pair
+                    // data of a wrong target: they are past nst and commit_four does not look at them.)
+                    // The per-mover kernel has no verified prediction -- lane 4 i + j, any row: steps i and j, as in step_quad.
+                    unsigned long long clash_bits;
+                    if constexpr (kPairWord) {
+                        uint32_t m_c = margins;
+                        __asm__ volatile("" : "+v"(m_c)::"memory");
+                        const uint32_t pairs = hand[9 * kWave + qs];
+                        const uint32_t margins_j = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((lane & 48u) | (s_loc & 15u)) << 2), (int)m_c);
+                        clash_bits = __builtin_amdgcn_ballot_w64(pair_clash<4u>(pairs >> ((kPairFieldBits * l16) & 31u), margins_j) != 0u);
+                    } else {
+                        clash_bits = clash_pairs(Four{}, r_loc, s_loc, t_loc, margins,
+                                                 (int)(((lane >> 2) & 3u) << 6), (int)((lane & 3u) << 6), [&](int li, uint32_t t_j) {
                             const int src = li + (int)((t_j & 15u) << 2);  // k of step i at block t_j: leaf t_j >> 4 of lane t_j & 15 of row i
                             const uint32_t k_lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk0);
                             const uint32_t k_hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)kk1);
                             return k_lo ^ ((k_lo ^ k_hi) & (0u - (t_j >> 4)));
-                        }) & 0xffffu;
+                        }) & 0xffffull;
+                    }
                     // (what the row's step adds to m_r / n_r of the two blocks of the lane's column if it moves: rows 0 / 2 hold block
                     // l16 of the register copies, rows 1 / 3 block l16 + 16 -- worked out in the gathers' shadow and pinned there)
                     int zw_lo = 0, zw_hi = 0;
@@ -1781,7 +1836,10 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     const unsigned long long b_acc = accept_rows(dS, accu0, accu1, u_acc, qs, m_warm, b_can);  // per row
                     const uint32_t mv4 = rows4(b_can & b_acc), selfok4 = rows4(b_selfok);
                     uint32_t moved, commit;
-                    commit_four(nst, clash_bits, mv4, moved, commit);
+                    if constexpr (kPairWord)
+                        commit_four(PairsByRow{}, nst, clash_bits, mv4, moved, commit);
+                    else
+                        commit_four(PairsByLane4{}, nst, (uint32_t)clash_bits, mv4, moved, commit);
 #ifdef BISBM_PASS_COUNTS
                     count_pairs((lane >> 2) & 3u, lane & 3u, lane < 16u, moved, commit, nst);
 #endif
