@@ -166,6 +166,8 @@ ABI = {
     "bisbm_reshuffle_get_total": (C.c_int, [C.c_void_p, _u64p]),
     "bisbm_clamp_set": (C.c_int, [C.c_void_p, _u8p]),
     "bisbm_clamp_get": (C.c_int, [C.c_void_p, _u8p, _u64p]),
+    "bisbm_constraints_set": (C.c_int, [C.c_void_p, C.c_uint32, _u8p, _u8p]),
+    "bisbm_constraints_get": (C.c_int, [C.c_void_p, _u32p, _u8p, _u8p]),
     "bisbm_debug_exp": (C.c_int, [C.c_void_p, _f64p, C.c_size_t, _f64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
@@ -192,6 +194,8 @@ ABI = {
     "bisbm_io_read_edge_list": (C.c_long, [C.c_char_p, C.POINTER(_u64p), C.POINTER(_u64p)]),
     "bisbm_io_read_memberships": (C.c_long, [C.c_char_p, C.POINTER(_u32p)]),
     "bisbm_io_read_clamp": (C.c_long, [C.c_char_p, C.c_uint64, C.POINTER(_u8p), C.c_char_p, C.c_size_t]),
+    "bisbm_io_read_constraints": (C.c_long, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_u8p), C.POINTER(_u8p),
+                                             C.c_char_p, C.c_size_t]),
     "bisbm_io_edges_to_csr": (C.c_int, [_u64p, _u64p, C.c_size_t, C.c_uint64, _u64p, _u32p]),
     "bisbm_io_load_csr": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(_u64p), C.POINTER(_u32p), _u64p,
                                     C.POINTER(C.c_int)]),
@@ -310,6 +314,83 @@ def load_clamp(path, n):
         raise ValueError(err.value.decode())
     out = np.ctypeslib.as_array(p, shape=(max(int(n), 1),))[:int(n)].astype(bool)
     L.bisbm_io_free(p)
+    return out
+
+
+def load_constraints(path, na, nb, ka, kb):
+    """The constraints file of ``mcmc --constraints`` (include/bisbm_io.h): one line per constrained node, its id and then its
+    allowed blocks -> (class_of_node uint8 [n], allowed bool [n_classes, ka + kb]) for BlockModel.constrain; class 0 allows
+    everything and holds the unlisted nodes.  ValueError, with the token named, for a malformed line."""
+    L = lib()
+    pc, pa = _u8p(), _u8p()
+    err = C.create_string_buffer(512)
+    n = int(na) + int(nb)
+    count = L.bisbm_io_read_constraints(os.fsencode(path), n, int(na), int(ka), int(kb), C.byref(pc), C.byref(pa), err, len(err))
+    if count == -1:
+        raise FileNotFoundError(path)
+    if count < 0:
+        raise ValueError(err.value.decode())
+    K = int(ka) + int(kb)
+    cls = np.ctypeslib.as_array(pc, shape=(max(n, 1),))[:n].copy()
+    allowed = np.ctypeslib.as_array(pa, shape=(count * K,)).reshape(count, K).astype(bool)
+    L.bisbm_io_free(pc)
+    L.bisbm_io_free(pa)
+    return cls, allowed
+
+
+def constraints_from_lists(n, K, lists, na=None, ka=None):
+    """(class_of_node uint8 [n], allowed bool [n_classes, K]) from {node: [allowed blocks]}: unlisted nodes get class 0, which
+    allows everything, and every distinct list (as a set) gets the next class -- at most 255 of them beside class 0, so that a
+    class id is one byte; more is a ValueError.  With `na` and `ka` (the type-a nodes are 0 .. na-1, the type-a blocks
+    0 .. ka-1) the columns of the other type are set, as the loader of the command line sets them, and a list that names a
+    block of the other type is a ValueError; without them the row is the list as given (the engine ignores the other type)."""
+    n, K = int(n), int(K)
+    cls = np.zeros(n, dtype=np.uint8)
+    rows, index = [np.ones(K, dtype=bool)], {}
+    for v in sorted(lists):
+        blocks = sorted(set(int(s) for s in lists[v]))
+        if not 0 <= int(v) < n:
+            raise ValueError("node %r is not in [0, %d)" % (v, n))
+        if not blocks or blocks[0] < 0 or blocks[-1] >= K:
+            raise ValueError("node %r: a non-empty list of blocks in [0, %d) is needed" % (v, K))
+        row = np.zeros(K, dtype=bool)
+        row[blocks] = True
+        if na is not None:
+            tb = int(v) >= int(na)
+            if any((s >= int(ka)) != tb for s in blocks):
+                raise ValueError("node %r: a block of the other type is listed" % (v,))
+            row[:int(ka)] |= tb
+            row[int(ka):] |= not tb
+        key = row.tobytes()
+        if key == rows[0].tobytes():
+            continue
+        if key not in index:
+            if len(rows) == 256:
+                raise ValueError("more than 255 distinct lists beside class 0: a class id is one byte")
+            index[key] = len(rows)
+            rows.append(row)
+        cls[int(v)] = index[key]
+    return cls, np.array(rows)
+
+
+def admissible_start(na, nb, ka, kb, class_of_node, allowed):
+    """A label vector that the constraints admit: the nodes of each (type, class), in ascending id, are dealt round-robin over
+    the allowed blocks of their type in ascending order.  ValueError when a class allows a node nothing, or when a block ends
+    up empty (no sampler ever empties a block, so such a start could not be left)."""
+    na, nb, ka, kb = int(na), int(nb), int(ka), int(kb)
+    cls = np.asarray(class_of_node)
+    allowed = np.asarray(allowed) != 0
+    out = np.zeros(na + nb, dtype=np.uint32)
+    for lo, hi, b0, b1 in ((0, na, 0, ka), (na, na + nb, ka, ka + kb)):
+        for c in np.unique(cls[lo:hi]):
+            blocks = b0 + np.flatnonzero(allowed[c, b0:b1])
+            nodes = lo + np.flatnonzero(cls[lo:hi] == c)
+            if not len(blocks):
+                raise ValueError("class %d allows node %d no block of its type" % (c, nodes[0]))
+            out[nodes] = blocks[np.arange(len(nodes)) % len(blocks)]
+    empty = np.flatnonzero(np.bincount(out, minlength=ka + kb) == 0)
+    if len(empty):
+        raise ValueError("block %d ends up empty" % empty[0])
     return out
 
 
@@ -687,6 +768,41 @@ class BlockModel:
         mask = np.zeros(self.n, dtype=np.uint8)
         self._check(self._L.bisbm_clamp_get(self._h, _p(mask, _u8p), None))
         return mask.astype(bool)
+
+    # -- block constraints (include/bisbm.h, "Block constraints")
+    def constrain(self, class_of_node, allowed):
+        """Restricts every node to the blocks its class allows, in every chain and through every sampler: `class_of_node` is
+        an array of n class ids (at most 256 classes), `allowed` a [n_classes, KA + KB] table, non-zero meaning allowed (the
+        entries for blocks of the other type are ignored).  Every chain's current labels must be admissible
+        (admissible_start gives such a start); a new call replaces the constraints, and a table that allows every node every
+        block of its type is unconstrain().  May be combined with clamp().  While constraints are set MH sweeps run the
+        generic kernel (slower; README.md), polish() certifies a minimum over the admissible moves, and agg_merge is refused."""
+        cls = np.asarray(class_of_node)
+        table = np.asarray(allowed)
+        if cls.shape != (self.n,) or cls.dtype.kind not in "iub":
+            raise ValueError("class_of_node has one integer per node (%d), not %s %s" % (self.n, cls.dtype, cls.shape))
+        if table.ndim != 2 or table.shape[1] != self.K or not 1 <= table.shape[0] <= 256:
+            raise ValueError("allowed is a [n_classes <= 256, %d] table, not %s" % (self.K, table.shape))
+        if cls.size and (cls.min() < 0 or cls.max() >= table.shape[0]):
+            raise ValueError("class ids must be in [0, %d)" % table.shape[0])
+        cls8 = np.ascontiguousarray(cls, dtype=np.uint8)
+        tab8 = np.ascontiguousarray(table != 0, dtype=np.uint8)
+        self._check(self._L.bisbm_constraints_set(self._h, int(table.shape[0]), _p(cls8, _u8p), _p(tab8, _u8p)))
+
+    def unconstrain(self):
+        """Clears the constraints: from here on every call is bit for bit what a model that never had any does."""
+        self._check(self._L.bisbm_constraints_set(self._h, 0, None, None))
+
+    def constraints(self):
+        """(class_of_node uint8 [n], allowed bool [n_classes, KA + KB]) as set; without constraints (None, None)."""
+        k = np.zeros(1, dtype=np.uint32)
+        self._check(self._L.bisbm_constraints_get(self._h, _p(k, _u32p), None, None))
+        if not int(k[0]):
+            return None, None
+        cls = np.zeros(self.n, dtype=np.uint8)
+        table = np.zeros((int(k[0]), self.K), dtype=np.uint8)
+        self._check(self._L.bisbm_constraints_get(self._h, None, _p(cls, _u8p), _p(table, _u8p)))
+        return cls, table.astype(bool)
 
     def debug_exp(self, x):
         """exp(x) as the device evaluates it (the host replays of the pair reshuffles take their exponentials from here)"""

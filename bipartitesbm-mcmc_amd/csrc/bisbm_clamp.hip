@@ -17,7 +17,7 @@ int clamp_upload(bisbm_engine* e, const std::vector<uint8_t>& mask, uint64_t n_c
     HIPCHK(e, hipStreamSynchronize(e->stream));  // (no kernel of this entry reads the old mask any more)
     if (n_clamped == 0) {
         st = ClampState();
-        return BISBM_OK;
+        return constraints_rebuild_open(e, mask);  // (the shuffle's list under block constraints follows the clamp)
     }
     std::vector<uint32_t> open;
     open.reserve((size_t)(e->n - n_clamped));
@@ -33,7 +33,7 @@ int clamp_upload(bisbm_engine* e, const std::vector<uint8_t>& mask, uint64_t n_c
     if (!open.empty()) HIPCHK(e, hipMemcpy(st.d_open.get(), open.data(), sizeof(uint32_t) * open.size(), hipMemcpyHostToDevice));
     st.open_a = open_a, st.open_b = (uint32_t)open.size() - open_a;
     st.n_clamped = n_clamped;
-    return BISBM_OK;
+    return constraints_rebuild_open(e, mask);
 }
 
 }  // namespace

@@ -281,6 +281,27 @@ __device__ __forceinline__ uint32_t mix32(uint32_t h) {
     return h;
 }
 
+// Block constraints (include/bisbm.h, "Block constraints"): the bit table keeps eight 32-bit words per class, bit s of a class's
+// row set where block s (a global label, below 256) is allowed.
+constexpr uint32_t kCnWords = 8;
+constexpr uint64_t kCnClassKey = 0x9E3779B97F4A7C15ull;  // the shuffle of class c is keyed by seed + c * this (mod 2^64)
+__device__ __forceinline__ bool cn_allows(const uint32_t* bits, uint32_t cls, uint32_t s) {
+    return ((bits[cls * kCnWords + (s >> 5)] >> (s & 31u)) & 1u) != 0u;
+}
+// how many blocks of [own0, own0 + k_own) the class allows
+__device__ __forceinline__ uint32_t cn_count(const uint32_t* bits, uint32_t cls, uint32_t own0, uint32_t k_own) {
+    uint32_t cnt = 0;
+    for (uint32_t w = 0; w < kCnWords; ++w) {
+        const uint32_t lo = w * 32u, hi = lo + 32u;
+        if (hi <= own0 || lo >= own0 + k_own) continue;
+        uint32_t msk = 0xffffffffu;
+        if (own0 > lo) msk &= 0xffffffffu << (own0 - lo);
+        if (own0 + k_own < hi) msk &= 0xffffffffu >> (hi - (own0 + k_own));
+        cnt += (uint32_t)__popc(bits[cls * kCnWords + w] & msk);
+    }
+    return cnt;
+}
+
 // Keyed bijection of [0,n): 4-round alternating Feistel network on max(2, bitlen(n-1)) bits with
 // cycle walking.  Gives the per-sweep visit order (and the label shuffle) without storing a
 // permutation: position i is evaluated on the fly, any lane can evaluate any position.

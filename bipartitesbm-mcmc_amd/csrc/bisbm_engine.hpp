@@ -32,6 +32,8 @@
 //                        aligned sample; kernel and C ABI
 //   bisbm_trace.hip      chain traces: a ring of each chain's own snapshots, lagged distances to them, the S / H series, tau and R-hat
 //   bisbm_clamp.hip      clamped nodes: the mask, the lists of the open nodes, the clamped shuffle kernel; C ABI
+//   bisbm_constraints.hip  block constraints: a class per node and a table of allowed blocks per class; the validation kernel,
+//                        the list of the open nodes by (type, class); C ABI
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -420,6 +422,26 @@ struct ClampState {
     const uint8_t* mask_or_null() const { return n_clamped ? d_mask.get() : nullptr; }
 };
 
+// Block constraints (bisbm_constraints.hip).  The class bytes and the table belong to the handle the caller holds and, with
+// the device copies, to every device entry (chains grouped by shape are refused).  n_classes == 0: no constraints, and no kernel
+// is handed a pointer -- a table under which every node may sit in every block of its type is stored as that.
+struct ConstraintState {
+    uint32_t n_classes = 0;
+    std::vector<uint8_t> cls;      // [n] class of every node
+    std::vector<uint8_t> allowed;  // [n_classes][K] 0 / 1 as given
+    std::vector<uint32_t> bits;    // [n_classes][8] the bit table
+    // device entry
+    DeviceBuf<uint8_t> d_class;    // [n]
+    DeviceBuf<uint32_t> d_bits;    // [n_classes][8]
+    // the shuffle's list: the nodes that are open under the clamp in place, sorted by (type, class, id); segment g holds
+    // d_open[seg[g] .. seg[g + 1]) and has the key (type << 8) | class.  Rebuilt when the clamp or the constraints change.
+    DeviceBuf<uint32_t> d_open, d_seg, d_seg_key;
+    uint32_t n_segs = 0;
+    const uint8_t* class_or_null() const { return n_classes ? d_class.get() : nullptr; }
+    const uint32_t* bits_or_null() const { return n_classes ? d_bits.get() : nullptr; }
+    bool allows(uint64_t v, uint32_t s) const { return ((bits[(size_t)cls[v] * 8 + (s >> 5)] >> (s & 31u)) & 1u) != 0u; }
+};
+
 }  // namespace bisbm
 
 // ------------------------------------------------------------------------------------------
@@ -518,6 +540,7 @@ struct bisbm_engine {
     bisbm::TraceState trace;
     bisbm::BlockSumState blocks;
     bisbm::ClampState clamp;
+    bisbm::ConstraintState constraints;
 };
 
 namespace bisbm {
@@ -761,6 +784,10 @@ int heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when
 // `last` is emptied; bisbm_reshuffle.hip
 int reshuffle_engine(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta, bool per_rung, bool read_back);
 int reshuffle_read_back(bisbm_engine* h);  // ... the copy alone, after a wait for the stream
+// block constraints: the shuffle's list of a device entry (ConstraintState::d_open) from the entry's constraints and the clamp
+// mask given (0 / 1 bytes, empty: none); nothing to do without constraints.  bisbm_clamp_set calls it for every mask it puts in
+// place; bisbm_constraints.hip
+int constraints_rebuild_open(bisbm_engine* e, const std::vector<uint8_t>& clamp_mask);
 // BISBM_ERR_INVALID_ARG when a move of up to max(na, nb) members with `scans` launch scans could use 2^32 draws or more
 int reshuffle_check_scans(bisbm_engine* h, uint32_t scans);
 // bisbm_marginals_accumulate with the alignment on; bisbm_align.hip

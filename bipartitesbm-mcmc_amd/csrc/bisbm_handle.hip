@@ -49,6 +49,7 @@ void free_all(bisbm_engine* h) {
     h->align = AlignState(), h->temper = TemperState(), h->population = PopulationState(), h->pairs = PairScoreState(), h->partition = PartitionState();
     h->queries = QueryScoreState(), h->coassign = CoassignState(), h->foldin = FoldinState(), h->cond = ConditionalState();
     h->clamp = ClampState();
+    h->constraints = ConstraintState();
     h->d_T.reset();
     if (h->root) {  // a sub-engine: the graph and the tables belong to the handle it serves
         h->d_rowptr = nullptr, h->d_col = nullptr, h->d_lgamma = nullptr, h->d_logtab = nullptr, h->d_q = nullptr;
@@ -408,6 +409,10 @@ int bisbm_set_memberships(bisbm_handle h, int64_t chain, const uint32_t* labels)
         const bool ok = v < h->na ? b < h->ka : (b >= h->ka && b < h->K);
         if (!ok) return fail(h, BISBM_ERR_INVALID_ARG, "label %u of node %llu is not a block of the node's type", b, (unsigned long long)v);
     }
+    for (uint64_t v = 0; h->constraints.n_classes && v < h->n; ++v)  // (block constraints: a vector that violates them is refused)
+        if (!h->constraints.allows(v, labels[v]))
+            return fail(h, BISBM_ERR_INVALID_ARG, "label %u of node %llu is not allowed by the block constraints (class %u of bisbm_constraints_set)", labels[v],
+                        (unsigned long long)v, (unsigned)h->constraints.cls[v]);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(h->d_stage_u32, labels, sizeof(uint32_t) * h->n, hipMemcpyHostToDevice, h->stream));
     const uint32_t first = chain == BISBM_ALL_CHAINS ? 0 : (uint32_t)chain;
@@ -444,6 +449,10 @@ int shuffle_leaf(bisbm_engine* h) {
     sp.mt_engine = h->d_mt_engine;
     sp.wide = h->wide ? 1u : 0u;
     if (h->clamp.n_clamped) sp.open = h->clamp.d_open.get(), sp.open_a = h->clamp.open_a, sp.open_b = h->clamp.open_b;
+    if (h->constraints.n_classes) {  // (the list by (type, class) serves the clamp as well: launch_shuffle takes it first)
+        const bisbm::ConstraintState& cn = h->constraints;
+        sp.cn_open = cn.d_open.get(), sp.cn_seg = cn.d_seg.get(), sp.cn_seg_key = cn.d_seg_key.get(), sp.cn_segs = cn.n_segs;
+    }
     if (h->rng_mode == BISBM_RNG_PHILOX)
         HIPCHK(h, hipMemcpyAsync(h->d_labels_tmp, h->d_labels, (size_t)h->n_chains * h->label_stride * h->lbytes(),
                                  hipMemcpyDeviceToDevice, h->stream));

@@ -18,6 +18,8 @@
 // block s holds its value and every lane adds them one v_readlane at a time.  A node that is not free (a one-
 // block type, or alone in its block) is skipped before any of this: its conditional is the point mass on r.  A clamped node
 // (include/bisbm.h, "Clamped nodes") is skipped in the chunk header already: the loop over a chunk walks its open positions.
+// Under block constraints (include/bisbm.h, "Block constraints") a node with one allowed block is skipped the same way, and the
+// row of every other node is restricted to its allowed blocks: they alone enter the minimum, and the others have weight 0.0.
 #include "bisbm_engine.hpp"
 #include "bisbm_wave_chain.hpp"
 
@@ -29,7 +31,9 @@ namespace {
 
 // CL: the launch has a clamp (p.clamp is not NULL).  Without one the instance reads no mask and counts through the chunk as it
 // always did: an unclamped handle runs the code it ran before the clamp existed.
-template <bool EL, bool CL>
+// CN: the launch has block constraints (p.cn_bits is not NULL; p.clamp may be set as well): the one instance that walks the
+// chunk as a clamped launch does and restricts the rows.  The two instances without it hold none of its code.
+template <bool EL, bool CL, bool CN>
 __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const uint32_t chain = blockIdx.x;
@@ -72,13 +76,17 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
             for (uint32_t vi0 = 0; vi0 < n_cls; vi0 += kWave) {
                 // ---- chunk header: lane q holds the node, row extent and own label of position vi0 + q ----
                 const uint32_t cnt = n_cls - vi0 < (uint32_t)kWave ? n_cls - vi0 : (uint32_t)kWave;
-                uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0, held_l = 0;
+                uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0, held_l = 0, cls_l = 0;
                 if (lane < cnt) {
                     v_l = v0 + order(vi0 + lane);
                     beg_l = p.rowptr[v_l];
                     deg_l = p.rowptr[v_l + 1] - beg_l;
                     r_l = wc.labels[v_l];
-                    if (CL) held_l = p.clamp[v_l];
+                    if (CL && !CN) held_l = p.clamp[v_l];
+                    if (CN) {  // (held: clamped, or a class with one allowed block of the type)
+                        cls_l = p.cn_class[v_l];
+                        held_l = ((p.clamp && p.clamp[v_l] != 0) || cn_count(p.cn_bits, cls_l, own0, k_own) <= 1u) ? 1u : 0u;
+                    }
                 }
                 // under a clamp, the open positions of the chunk: a clamped node stays as a node that is not free does, its row
                 // is not parked (extent 0), a chunk without an open position reads no row at all, and the loop walks the ballot
@@ -95,6 +103,9 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                     const uint32_t v = readlane(v_l, q), beg = readlane(beg_l, q), deg = readlane(deg_l, q);
                     const uint32_t r = readlane(r_l, q), r_loc = r - own0;
                     if (r_loc >= k_own) continue;  // (a valid label: never)
+                    const uint32_t cls = CN ? readlane(cls_l, q) : 0u;  // (wave-uniform: the table reads below are of one row)
+                    // is block tid of the type in A_v (the node's own block always is)?
+                    auto admits = [&](uint32_t tid) { return !CN || tid == r_loc || cn_allows(p.cn_bits, cls, own0 + tid); };
                     const int n0r = nr[r];
                     if (n0r <= 1) continue;  // not free: the node stays, and no draw is used
                     // 1., 2. k_v and the non-zero (t, k_t) in ascending t, with the r side's two table values
@@ -165,7 +176,7 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                     double mn = 0.;
                     for (uint32_t c0 = 0; c0 < k_own; c0 += kWave) {
                         const uint32_t tid = c0 + lane, cn = k_own - c0 < (uint32_t)kWave ? k_own - c0 : (uint32_t)kWave;
-                        const double x = tid < k_own ? s_dS[tid] : 0.;
+                        const double x = tid < k_own && admits(tid) ? s_dS[tid] : 0.;  // (the minimum is over A_v, the 0 at r included)
                         for (uint32_t s = 0; s < cn; ++s) {
                             const double y = readlane(x, s);
                             mn = y < mn ? y : mn;
@@ -177,7 +188,7 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                         if (!(mn < 0.)) continue;
                         for (uint32_t c0 = 0; c0 < k_own; c0 += kWave) {
                             const uint32_t tid = c0 + lane;
-                            const unsigned long long hit = __ballot(tid < k_own && tid != r_loc && s_dS[tid] == mn);
+                            const unsigned long long hit = __ballot(tid < k_own && tid != r_loc && admits(tid) && s_dS[tid] == mn);
                             if (hit) {
                                 s_new = c0 + (uint32_t)__ffsll((long long)hit) - 1u;
                                 break;
@@ -191,7 +202,7 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                             double w = 0.;
                             if (tid < k_own) {
                                 const double x = beta * (s_dS[tid] - mn);
-                                w = x > 700. ? 0. : exp(-x);
+                                w = x > 700. || !admits(tid) ? 0. : exp(-x);  // (exactly 0.0 outside A_v)
                                 s_x[tid] = w;
                             }
                             for (uint32_t s = 0; s < cn; ++s) Z = Z + readlane(w, s);
@@ -280,13 +291,16 @@ int bisbm::heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int st
     wave_chain_fill(h, p.greedy ? 0. : beta, per_rung, p);
     p.stop_when_settled = stop_when_settled ? 1u : 0u;
     p.clamp = h->clamp.mask_or_null();
+    p.cn_class = h->constraints.class_or_null(), p.cn_bits = h->constraints.bits_or_null();
     size_t lds;  // (the four double[kmax] arrays of the kernel's own: a multiple of 16 bytes, as the rounded chain state is)
     if (int rc = wave_chain_plan(h, 4 * sizeof(double) * std::max(h->ka, h->kb), p, lds)) return rc;
     h->ent_prev_valid = false;  // (the block state moves)
-    if (p.clamp)
-        HIPCHK(h, launch_wave_chain(heatbath_kernel<true, true>, heatbath_kernel<false, true>, p, lds, h->stream));
+    if (p.cn_bits)
+        HIPCHK(h, launch_wave_chain(heatbath_kernel<true, true, true>, heatbath_kernel<false, true, true>, p, lds, h->stream));
+    else if (p.clamp)
+        HIPCHK(h, launch_wave_chain(heatbath_kernel<true, true, false>, heatbath_kernel<false, true, false>, p, lds, h->stream));
     else
-        HIPCHK(h, launch_wave_chain(heatbath_kernel<true, false>, heatbath_kernel<false, false>, p, lds, h->stream));
+        HIPCHK(h, launch_wave_chain(heatbath_kernel<true, false, false>, heatbath_kernel<false, false, false>, p, lds, h->stream));
     if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
 }

@@ -133,7 +133,9 @@ __device__ __forceinline__ void wave_fence() {
     __asm__ volatile("" ::: "memory");
 }
 
-template <int RNG, bool EL, bool W>
+// CN: the launch has block constraints (p.cn_bits is not NULL; Philox mode and byte labels only).  Without them the instance holds
+// no look-up: a handle without constraints runs the code it ran before they existed.
+template <int RNG, bool EL, bool W, bool CN = false>
 __device__ __forceinline__ bool mh_step(const SweepParams& p, const Tables& tab, ChainCtx& c, Mt& engine, Mt& gen,
                                         uint32_t v, uint32_t beg, uint32_t deg, uint32_t r, uint32_t nb_reg,
                                         int lab_reg, double T, uint64_t gstep, uint32_t chain_gid, uint32_t* s_out) {
@@ -268,7 +270,12 @@ __device__ __forceinline__ bool mh_step(const SweepParams& p, const Tables& tab,
     double dS;
     double phx_accu0 = 1., phx_accu1 = 1.;
     const bool same = (r == s);
-    const bool cross = !same && ((r < c.ka) != (s < c.ka));
+    // Block constraints (include/bisbm.h; the CN instance alone): a target of the node's type that its class does not allow gets
+    // the verdict of a target of the other type -- not evaluated, not accepted.  v and s are wave-uniform, so the two reads are
+    // uniform loads.
+    bool barred = false;
+    if (CN && !same && (r < c.ka) == (s < c.ka)) barred = !cn_allows(p.cn_bits, p.cn_class[v], s);
+    const bool cross = !same && (((r < c.ka) != (s < c.ka)) || (CN && barred));
     if (same) {
         c.accu_r = 1.;  // :109-112
         dS = 0.;
@@ -460,7 +467,7 @@ __device__ __forceinline__ bool mh_step(const SweepParams& p, const Tables& tab,
 //   * the neighbour ids of step q+2 and the neighbour labels of step q+1 are in flight while step q
 //     computes (labels fetched early are patched when step q moves one of those neighbours).
 // ------------------------------------------------------------------------------------------
-template <int RNG, bool EL, bool W>
+template <int RNG, bool EL, bool W, bool CN = false>
 __global__ __launch_bounds__(kWave) void sweep_kernel(SweepParams p) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const uint32_t chain = blockIdx.x;
@@ -652,7 +659,7 @@ __global__ __launch_bounds__(kWave) void sweep_kernel(SweepParams p) {
                 prefetch();
                 // (a clamped node: the ring is rotated and refilled as for any step, the step itself is one that was not accepted)
                 const bool ok = ((held >> q) & 1ull) == 0ull &&
-                                mh_step<RNG, EL, W>(p, tab, c, engine, gen, v, beg, deg, r, nbC, labC, T,
+                                mh_step<RNG, EL, W, CN>(p, tab, c, engine, gen, v, beg, deg, r, nbC, labC, T,
                                                     sweeps_total * num_nodes + vi, chain_gid, &s);
                 mv_v1 = mv_v2;
                 mv_s1 = mv_s2;
@@ -751,6 +758,8 @@ template __global__ void sweep_kernel<RNG_COMPAT, true, false>(SweepParams);
 template __global__ void sweep_kernel<RNG_COMPAT, false, false>(SweepParams);
 template __global__ void sweep_kernel<RNG_PHILOX, false, true>(SweepParams);  // wide mode: eta stays in HBM as well
 template __global__ void sweep_kernel<RNG_COMPAT, false, true>(SweepParams);
+template __global__ void sweep_kernel<RNG_PHILOX, true, false, true>(SweepParams);  // block constraints
+template __global__ void sweep_kernel<RNG_PHILOX, false, false, true>(SweepParams);
 
 // ------------------------------------------------------------------------------------------
 // state build: init_bisbm (blockmodel.cc:682-688, compute_n_r :740-746, compute_m :702-714,
@@ -855,6 +864,33 @@ __global__ void shuffle_philox_clamped_kernel(ShuffleParams p) {
     const uint32_t n_open = p.open_a + p.open_b;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_open; i += gridDim.x * blockDim.x)
         dst[p.open[i]] = src[p.open[i < p.open_a ? fa(i) : p.open_a + fb(i - p.open_a)]];
+}
+
+// ... under block constraints (include/bisbm.h, "Block constraints", 4.; byte labels): the open nodes of every (type, class) are
+// permuted among themselves -- equal class means equal allowed blocks -- by the same keyed permutation on the domain of the
+// segment, the class entering through the Philox key: seed + class * kCnClassKey.  Class 0 has today's key, so one class is the
+// clamped or unclamped shuffle.  Position i finds its segment by bisection over the (at most 512) segment offsets.
+__global__ void shuffle_philox_constrained_kernel(ShuffleParams p) {
+    const uint32_t chain = blockIdx.y;
+    const uint8_t* src = p.labels_old + (size_t)chain * p.label_stride;
+    uint8_t* dst = p.labels + (size_t)chain * p.label_stride;
+    const uint32_t gid = chain_gid_of(p, chain);
+    const uint32_t epoch = p.scalars[chain].shuffle_epoch;
+    const uint32_t n_open = p.cn_seg[p.cn_segs];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_open; i += gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = p.cn_segs;  // the segment g with cn_seg[g] <= i < cn_seg[g + 1]
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (p.cn_seg[mid] <= i)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const uint32_t beg = p.cn_seg[lo], len = p.cn_seg[lo + 1] - beg, key = p.cn_seg_key[lo];
+        Feistel f;
+        f.init(phx_draw(p.seed + (uint64_t)(key & 255u) * kCnClassKey, gid, PHX_INIT_SHUFFLE, ((uint64_t)(key >> 8) << 32) | epoch), len);
+        dst[p.cn_open[i]] = src[p.cn_open[beg + f(i - beg)]];
+    }
 }
 
 __global__ void shuffle_epoch_bump_kernel(ChainScalars* sc, uint32_t n_chains) {
@@ -979,12 +1015,12 @@ __global__ void log_q_probe_kernel(Tables tab, const int32_t* n, const int32_t* 
 // ------------------------------------------------------------------------------------------
 // launchers (called from the host runtime)
 // ------------------------------------------------------------------------------------------
-template <int RNG, bool EL, bool W = false>
+template <int RNG, bool EL, bool W = false, bool CN = false>
 static hipError_t launch_sweep_variant(const SweepParams& p, size_t lds_bytes, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)sweep_kernel<RNG, EL, W>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipError_t e = hipFuncSetAttribute((const void*)sweep_kernel<RNG, EL, W, CN>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((sweep_kernel<RNG, EL, W>), dim3(p.n_chains), dim3(kWave), lds_bytes, stream, p);
+    hipLaunchKernelGGL((sweep_kernel<RNG, EL, W, CN>), dim3(p.n_chains), dim3(kWave), lds_bytes, stream, p);
     return hipGetLastError();
 }
 
@@ -996,6 +1032,9 @@ hipError_t launch_sweep(const SweepParams& p, int rng_mode, size_t lds_bytes, hi
     else if (rng_mode == RNG_COMPAT)
         e = p.eta_in_lds ? launch_sweep_variant<RNG_COMPAT, true>(p, lds_bytes, stream)
                          : launch_sweep_variant<RNG_COMPAT, false>(p, lds_bytes, stream);
+    else if (p.cn_bits)  // (block constraints: the instances that look the target up)
+        e = p.eta_in_lds ? launch_sweep_variant<RNG_PHILOX, true, false, true>(p, lds_bytes, stream)
+                         : launch_sweep_variant<RNG_PHILOX, false, false, true>(p, lds_bytes, stream);
     else
         e = p.eta_in_lds ? launch_sweep_variant<RNG_PHILOX, true>(p, lds_bytes, stream)
                          : launch_sweep_variant<RNG_PHILOX, false>(p, lds_bytes, stream);
@@ -1367,7 +1406,9 @@ hipError_t launch_shuffle(const ShuffleParams& p, int rng_mode, hipStream_t stre
             hipLaunchKernelGGL(shuffle_compat_kernel<uint8_t>, dim3(p.n_chains), dim3(kWave), 0, stream, p);
     } else {
         const uint32_t tiles = (p.n + 255) / 256 < 1024 ? (p.n + 255) / 256 : 1024;
-        if (p.open)
+        if (p.cn_open)
+            hipLaunchKernelGGL(shuffle_philox_constrained_kernel, dim3(tiles ? tiles : 1, p.n_chains), dim3(256), 0, stream, p);
+        else if (p.open)
             hipLaunchKernelGGL(shuffle_philox_clamped_kernel, dim3(tiles ? tiles : 1, p.n_chains), dim3(256), 0, stream, p);
         else if (p.wide)
             hipLaunchKernelGGL(shuffle_philox_kernel<uint16_t>, dim3(tiles ? tiles : 1, p.n_chains), dim3(256), 0, stream, p);

@@ -115,6 +115,11 @@ struct SweepParams {
     // clamped nodes (bisbm_clamp.hip), generic kernel in Philox mode only: [n] a non-zero byte holds the node -- its step is not
     // evaluated and counts as a step that was not accepted; NULL: no clamp
     const uint8_t* clamp;
+    // block constraints (bisbm_constraints.hip), generic kernel in Philox mode only: the class byte of every node [n] and the bit
+    // table of eight 32-bit words per class (bit s of a class's row: block s allowed) -- a proposal of another block of the node's
+    // type outside its class's row is not evaluated and counts as a step that was not accepted; NULL: no constraints
+    const uint8_t* cn_class;
+    const uint32_t* cn_bits;
 };
 // Accepted fraction of the launch before from which a four-steps launch of 17..32 blocks takes the one-stage kernel
 // (SweepParams::one_stage).  Measured at 32 + 32 blocks (profiles/EXPERIMENTS.md, round 7): the one stage wins by 3.9 % where 0.72
@@ -150,6 +155,14 @@ struct ShuffleParams {
     // ascending; the labels of a type's open nodes are permuted among themselves.  NULL: no clamp
     const uint32_t* open;
     uint32_t open_a, open_b;
+    // block constraints (Philox mode, byte labels; launch_shuffle takes this list first -- it serves a clamp set beside the
+    // constraints as well, whose own `open` may be set too): the open nodes sorted by (type, class, id) in `cn_open`,
+    // segment g = (type, class) holds cn_open[cn_seg[g] .. cn_seg[g + 1]) and is permuted among itself under the key of its
+    // class, cn_seg_key[g] = (type << 8) | class.  NULL: no constraints
+    const uint32_t* cn_open;
+    const uint32_t* cn_seg;      // [cn_segs + 1]
+    const uint32_t* cn_seg_key;  // [cn_segs]
+    uint32_t cn_segs;
 };
 
 struct EntropyParams {
@@ -437,6 +450,10 @@ struct HeatbathParams : WaveChainParams {
     uint32_t greedy;             // beta = +inf: the lowest argmin of dS, only strictly downhill, no draw
     uint32_t stop_when_settled;  // a chain stops after the first sweep that moved nothing
     const uint8_t* clamp;        // clamped nodes: [n] a non-zero byte holds the node as a node that is not free is held; NULL: no clamp
+    // block constraints: the class byte per node and the bit table (SweepParams::cn_bits) -- the row of a node is restricted to the
+    // allowed blocks of its type, a node with one allowed block is held as a clamped node is; NULL: no constraints
+    const uint8_t* cn_class;
+    const uint32_t* cn_bits;
 };
 
 constexpr uint32_t PHX_RESHUFFLE = 10;  // pair reshuffles: idx = (reshuffles_total << 32) | k, chain = the chain's global id
@@ -451,6 +468,9 @@ struct ReshuffleParams : WaveChainParams {
     bisbm_reshuffle_record* record;  // [chain] the last move of the call
     unsigned long long* accepted;    // [chain] accepted moves of the call
     const uint8_t* clamp;            // clamped nodes: [n] a node with a non-zero byte is no member of any move; NULL: no clamp
+    // block constraints: a node whose class does not allow BOTH blocks of the pair is no member either; NULL: no constraints
+    const uint8_t* cn_class;
+    const uint32_t* cn_bits;
 };
 hipError_t launch_exp_probe(const double* x, size_t count, double* out, hipStream_t stream);
 

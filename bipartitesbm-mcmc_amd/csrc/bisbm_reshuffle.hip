@@ -29,7 +29,9 @@ namespace {
 
 enum : uint32_t { RS_TRANSIT = 0, RS_FREE = 1, RS_FORCED = 2 };
 
-template <bool EL>
+// CN: the launch has block constraints (p.cn_bits is not NULL).  Without them the instance holds no look-up and is the code a
+// handle ran before they existed.
+template <bool EL, bool CN>
 __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const uint32_t chain = blockIdx.x;
@@ -79,12 +81,17 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
         const U4 acc_draw = phx_draw(p.seed, chain_gid, PHX_RESHUFFLE, idx0 | 1u);
         const double u_acc = u53(acc_draw.x, acc_draw.y);
 
-        // 3. the members, ascending id, by ballot compaction: the nodes of r and s that are not clamped
+        // 3. the members, ascending id, by ballot compaction: the nodes of r and s that are not clamped and, under block
+        //    constraints, may sit in both
         uint32_t M = 0;
         for (uint32_t i0 = 0; i0 < n_cls; i0 += kWave) {
             const uint32_t i = i0 + lane;
             const uint32_t lab = i < n_cls ? (uint32_t)labels[v0 + i] : 0xffffffffu;
-            const bool is = (lab == rg || lab == sg) && !(p.clamp && p.clamp[v0 + i] != 0);
+            bool is = (lab == rg || lab == sg) && !(p.clamp && p.clamp[v0 + i] != 0);
+            if (CN && is) {  // (block constraints: a member's class allows both blocks of the pair)
+                const uint32_t cls = p.cn_class[v0 + i];
+                is = cn_allows(p.cn_bits, cls, rg) && cn_allows(p.cn_bits, cls, sg);
+            }
             const unsigned long long bal = __ballot(is);
             if (is) {
                 const uint32_t pos = M + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
@@ -93,7 +100,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
             }
             M += (uint32_t)__popcll(bal);
         }
-        if (M < 2u) {  // (no block is ever empty: only under a clamp) a counted no-op; the record keeps the pair and M
+        if (M < 2u) {  // (no block is ever empty: only under a clamp or block constraints) a counted no-op; the record keeps the pair and M
             rec.type = tb ? 1u : 0u, rec.r = rg, rec.s = sg, rec.M = M;
             continue;
         }
@@ -306,11 +313,15 @@ int bisbm::reshuffle_engine(bisbm_engine* h, uint64_t moves, uint32_t scans, dou
     p.launch = st.d_scratch.get() + 5 * nmax * C;
     p.record = st.d_record.get(), p.accepted = st.d_accepted.get();
     p.clamp = h->clamp.mask_or_null();
+    p.cn_class = h->constraints.class_or_null(), p.cn_bits = h->constraints.bits_or_null();
     size_t lds;
     if (int rc = wave_chain_plan(h, 0, p, lds)) return rc;
     h->ent_prev_valid = false;  // (the block state moves)
     st.last.clear();
-    HIPCHK(h, launch_wave_chain(reshuffle_kernel<true>, reshuffle_kernel<false>, p, lds, h->stream));
+    if (p.cn_bits)
+        HIPCHK(h, launch_wave_chain(reshuffle_kernel<true, true>, reshuffle_kernel<false, true>, p, lds, h->stream));
+    else
+        HIPCHK(h, launch_wave_chain(reshuffle_kernel<true, false>, reshuffle_kernel<false, false>, p, lds, h->stream));
     return read_back ? reshuffle_read_back(h) : BISBM_OK;
 }
 

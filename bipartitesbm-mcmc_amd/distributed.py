@@ -259,14 +259,36 @@ def _foldin_blocks(m, m_r, n_r, ka, qtype):
     return quad, m_r[a], n_r[a], m_r[b]
 
 
-def numpy_conditional_row(dS_row, r_local, free, beta):
+def numpy_conditional_row(dS_row, r_local, free, beta, allowed=None):
     """Host statement of steps 3 and 4 of the node conditionals (include/bisbm.h, "Node conditionals") for one chain and one
     query: (P [K_own], stay, entropy, margin) from the row dS_s over the blocks of the node's type, the node's block within its
     type, whether the node is free (K_own > 1 and it is not alone in its block) and beta, with the operations in the order the
     header states.  margin is None for a node that is not free.  The exponential and the logarithm are numpy's: the device's may
-    differ from them in the last bits, everything else is bit for bit."""
+    differ from them in the last bits, everything else is bit for bit.  `allowed` (None: every block): a 0 / 1 vector over the
+    blocks of the type, the node's A_v of the block constraints (include/bisbm.h, "Block constraints", 2.) -- the row is then
+    the restricted one of the heat-bath sweeps: the minimum is over A_v (r included), a block outside A_v has weight exactly 0.0,
+    the margin is over the other blocks of A_v (None when there is none), and a node with one allowed block is not free."""
     dS = np.asarray(dS_row, dtype=np.float64)
     K, r, beta = len(dS), int(r_local), float(beta)
+    if allowed is not None:
+        A = np.asarray(allowed) != 0
+        A[r] = True  # (the node's own block is always allowed)
+        free = bool(free) and int(A.sum()) > 1
+        if free:
+            x = beta * (dS - dS[A].min())
+            w = np.where((x > 700.0) | ~A, 0.0, np.exp(-np.minimum(x, 700.0)))
+            Z = float(w[0])
+            for y in w[1:]:
+                Z = Z + float(y)
+            P = w / Z
+            others = A.copy()
+            others[r] = False
+            margin = float(dS[others].min())
+            acc = 0.0
+            for y in P:
+                if y != 0.0:
+                    acc = acc + float(y) * float(np.log(y))
+            return P, float(P[r]), 0.0 - acc, margin
     if not free:
         P = np.zeros(K, dtype=np.float64)
         P[r] = 1.0
@@ -286,16 +308,33 @@ def numpy_conditional_row(dS_row, r_local, free, beta):
     return P, float(P[r]), 0.0 - acc, margin
 
 
-def numpy_heatbath_choice(dS_row, P_row, r, free, u, greedy):
+def numpy_heatbath_choice(dS_row, P_row, r, free, u, greedy, allowed=None):
     """Host statement of steps 3 and 4 of the heat-bath sweeps (include/bisbm.h, "Heat-bath sweeps and greedy polishing") for one
     visited node: the node's new block within its type from its rows dS_s and P(s), its current block r within its type, whether
     it is free, the uniform u of the step and whether the call is greedy (beta = +inf; u and P_row are not looked at then).  A
-    node that is not free stays.  Bit for bit the device's choice when the rows are the device's."""
+    node that is not free stays.  Bit for bit the device's choice when the rows are the device's.  `allowed` (None: every
+    block): the node's A_v of the block constraints as a 0 / 1 vector over the blocks of the type -- a node with one allowed block
+    stays, the greedy choice is the lowest block of A_v that attains the minimum over A_v (r's 0 included), and the drawn choice
+    walks P_row, which is then the restricted row (0.0 outside A_v), as always."""
     r = int(r)
+    if allowed is not None:
+        A = [bool(x) for x in allowed]
+        A[r] = True
+        free = bool(free) and sum(A) > 1
     if not free:
         return r
     if greedy:
         dS = [float(x) for x in dS_row]
+        if allowed is not None:
+            mn = 0.0
+            for s in range(len(dS)):
+                if A[s] and s != r and dS[s] < mn:
+                    mn = dS[s]
+            if not mn < 0.0:
+                return r
+            for s in range(len(dS)):
+                if A[s] and s != r and dS[s] == mn:
+                    return s
         best = 0
         for s in range(1, len(dS)):
             if dS[s] < dS[best]:
@@ -406,6 +445,27 @@ def numpy_clamped_shuffle(labels, mask, na, perm_a, perm_b):
         if len(perm) != len(F) or sorted(perm.tolist()) != list(range(len(F))):
             raise ValueError("a permutation of the %d open nodes of the type is needed" % len(F))
         out[F] = labels[F[perm]]
+    return out
+
+
+def numpy_constrained_shuffle(labels, mask, na, class_of_node, perms):
+    """The shuffle under block constraints (include/bisbm.h, "Block constraints", 4.) on the host, given the permutation of
+    every (type, class): with F the ascending list of the open (mask == 0; mask None: all) nodes of type t and class c and
+    f = perms[(t, c)] a permutation of range(len(F)), new[F[i]] = old[F[f[i]]]; every other node keeps its label.  A (type,
+    class) without an open node needs no entry, one with a single open node may have [0] or none."""
+    labels = np.asarray(labels)
+    cls = np.asarray(class_of_node)
+    held = np.zeros(len(labels), dtype=bool) if mask is None else np.asarray(mask) != 0
+    out = labels.copy()
+    for t, (lo, hi) in enumerate(((0, int(na)), (int(na), len(labels)))):
+        for c in np.unique(cls[lo:hi]):
+            F = lo + np.flatnonzero(~held[lo:hi] & (cls[lo:hi] == c))
+            if len(F) <= 1 and (t, int(c)) not in perms:
+                continue
+            perm = np.asarray(perms[(t, int(c))], dtype=np.int64)
+            if len(perm) != len(F) or sorted(perm.tolist()) != list(range(len(F))):
+                raise ValueError("a permutation of the %d open nodes of type %d and class %d is needed" % (len(F), t, c))
+            out[F] = labels[F[perm]]
     return out
 
 

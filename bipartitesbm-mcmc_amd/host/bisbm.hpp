@@ -75,6 +75,26 @@ inline bool load_clamp(std::vector<uint8_t>& mask, const std::string& path, size
     return true;
 }
 
+// The constraints file of --constraints (include/bisbm_io.h): one line per constrained node, its id and its allowed blocks ->
+// the class of every node (n bytes) and the table of n_classes x (ka + kb) bytes for constrain().  On a failure `error` names the
+// file, and the token where one is at fault.
+inline bool load_constraints(uint32_t& n_classes, std::vector<uint8_t>& class_of_node, std::vector<uint8_t>& allowed, const std::string& path,
+                             size_t n, size_t na, size_t ka, size_t kb, std::string& error) {
+    uint8_t *pc = nullptr, *pa = nullptr;
+    char msg[512];
+    const long classes = bisbm_io_read_constraints(path.c_str(), n, na, (uint32_t)ka, (uint32_t)kb, &pc, &pa, msg, sizeof(msg));
+    if (classes < 0) {
+        error = msg;
+        return false;
+    }
+    n_classes = (uint32_t)classes;
+    class_of_node.assign(pc, pc + n);
+    allowed.assign(pa, pa + (size_t)classes * (ka + kb));
+    bisbm_io_free(pc);
+    bisbm_io_free(pa);
+    return true;
+}
+
 inline adj_list_t edge_to_adj(const edge_list_t& edge_list, size_t num_vertices = 0) {
     size_t n = num_vertices;
     for (auto const& e : edge_list) n = std::max(n, std::max(e.first, e.second) + 1);  // graph_utilities.cc:39-44
@@ -361,6 +381,23 @@ public:
         std::vector<uint8_t> mask(n_);
         check(bisbm_clamp_get(h_, mask.data(), n_clamped));
         return mask;
+    }
+    // block constraints (include/bisbm.h): node v may sit in block s iff allowed[class_of_node[v] * (KA + KB) + s] is set (and s is
+    // of v's type), through every sampler and in every chain; every chain's labels must satisfy them when they are set
+    void constrain(uint32_t n_classes, const std::vector<uint8_t>& class_of_node, const std::vector<uint8_t>& allowed) {
+        if (class_of_node.size() != n_) throw std::runtime_error("constrain: class_of_node has one byte per node");
+        check(bisbm_constraints_set(h_, n_classes, class_of_node.data(), allowed.data()));
+    }
+    void unconstrain() { check(bisbm_constraints_set(h_, 0, nullptr, nullptr)); }
+    uint32_t constraints(std::vector<uint8_t>& class_of_node, std::vector<uint8_t>& allowed) {
+        uint32_t n_classes = 0;
+        check(bisbm_constraints_get(h_, &n_classes, nullptr, nullptr));
+        uint32_t ka = 0, kb = 0;
+        check(bisbm_get_ka_kb(h_, &ka, &kb));
+        class_of_node.assign(n_, 0);
+        allowed.assign((size_t)n_classes * (ka + kb), 0);
+        check(bisbm_constraints_get(h_, nullptr, class_of_node.data(), allowed.data()));
+        return n_classes;
     }
     // pair reshuffles (include/bisbm.h): `moves` moves per chain in which the nodes of two blocks of one type are divided afresh
     // and accepted or rejected as a whole (the accepted moves per chain); the record of every chain's last move.  The default

@@ -7,7 +7,7 @@
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
 // --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
 // --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace, --rung_moves, --population_moves,
-// --clamp.
+// --clamp, --constraints.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -62,7 +62,7 @@ const option_spec kOptions[] = {
     {"reshuffle", 0, 1},        {"reshuffle_scans", 0, 1},
     {"trace", 0, 2},            {"block_summary", 0, 1},
     {"rung_moves", 0, 2},       {"population_moves", 0, 2},
-    {"clamp", 0, 1},
+    {"clamp", 0, 1},            {"constraints", 0, 1},
 };
 
 // a / b of two integers (b > 0) as the nearest double, ties to even: a quotient of 55 or 56 bits with the remainder folded
@@ -256,6 +256,12 @@ void print_help(const char* argv0) {
                  "                                        sweep, reshuffle and exchange round of the run, in every chain; the other\n"
                  "                                        nodes are sampled as always.  Philox mode (--rng philox); not with --merge,\n"
                  "                                        --nature or a -z that differs from the block counts of the membership file.\n"
+                 "  --constraints PATH                    PATH holds one line per constrained node: the node id, then the blocks it\n"
+                 "                                        may sit in (global labels, blocks of its own type).  Through every sweep,\n"
+                 "                                        reshuffle and exchange round of the run a listed node stays inside its\n"
+                 "                                        list, in every chain; the labels of --membership_path (required) must\n"
+                 "                                        satisfy the lists.  Philox mode (--rng philox); not with --merge, --nature\n"
+                 "                                        or a -z that differs from the block counts of the membership file.\n"
                  "  --score_pairs IN OUT                  With --marginalize: IN holds one pair `u v` per line (u of type a, v of\n"
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
@@ -927,6 +933,16 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
     }
+    if (count("constraints")) {
+        if (!count("membership_path")) {
+            std::cerr << "--constraints needs a start that satisfies the lists: it needs --membership_path.\n";
+            return 1;
+        }
+        if (merge || nature) {
+            std::cerr << "--constraints cannot be combined with " << (merge ? "--merge" : "--nature") << ": a merge renumbers the blocks that the lists name.\n";
+            return 1;
+        }
+    }
     size_t seed;
     if (count("seed") == 0)
         seed = (size_t)std::chrono::high_resolution_clock::now().time_since_epoch().count();  // :236-239
@@ -1050,6 +1066,32 @@ int main(int argc, char const* argv[]) {
         }
         std::clog << "clamp: " << std::count(clamp_mask.begin(), clamp_mask.end(), (uint8_t)1) << " of " << N << " nodes held\n";
     }
+    // --constraints: the class of every node, in the engine's numbering, and the table of allowed blocks per class
+    uint32_t cn_classes = 0;
+    std::vector<uint8_t> cn_class, cn_allowed;
+    if (count("constraints")) {
+        if (!prepared) {
+            std::cerr << "--constraints needs the labels of --membership_path as a start that satisfies the lists, and the file could not be read.\n";
+            return 1;
+        }
+        if (z.size() >= 2 && (z[0] != KA || z[1] != KB)) {
+            std::cerr << "--constraints: -z " << z[0] << " " << z[1] << " differs from the " << KA << " + " << KB
+                      << " blocks of the membership file, and the merge or split that would follow renumbers blocks.\n";
+            return 1;
+        }
+        std::string why;
+        if (!load_constraints(cn_classes, cn_class, cn_allowed, single("constraints", ""), N, NA, KA, KB, why)) {
+            std::cerr << "[error] --constraints: " << why << "\n";
+            return 1;
+        }
+        if (!new_id.empty()) {
+            std::vector<uint8_t> moved(cn_class.size());
+            for (size_t v = 0; v < cn_class.size(); ++v) moved[new_id[v]] = cn_class[v];
+            cn_class.swap(moved);
+        }
+        std::clog << "constraints: " << (N - (size_t)std::count(cn_class.begin(), cn_class.end(), (uint8_t)0)) << " of " << N << " nodes listed, "
+                  << cn_classes << " class(es)\n";
+    }
 
     // K implied by the initial labels vs. requested (mcmc_main.cc:406-419)
     size_t ka = 0, kb = 0;
@@ -1097,6 +1139,10 @@ int main(int argc, char const* argv[]) {
         return 1;
     }
     opt.rng_mode = rng == "philox" ? BISBM_RNG_PHILOX : BISBM_RNG_MT19937_COMPAT;
+    if (count("constraints") && opt.rng_mode != BISBM_RNG_PHILOX) {
+        std::cerr << "--constraints runs in Philox mode only (mt19937-compat is the reference's verification path, and the reference has no constraints): add --rng philox.\n";
+        return 1;
+    }
     if (count("clamp") && opt.rng_mode != BISBM_RNG_PHILOX) {
         std::cerr << "--clamp runs in Philox mode only (mt19937-compat is the reference's verification path, and the reference has no clamp): add --rng philox.\n";
         return 1;
@@ -1290,6 +1336,11 @@ int main(int argc, char const* argv[]) {
         return 0;
     }
     if (ka != KA || kb != KB) {  // the initial partition has other block counts than asked for (:419-450)
+        if (count("constraints")) {
+            std::cerr << "--constraints: the initial partition has " << ka << " + " << kb << " blocks, not " << KA << " + " << KB
+                      << ", and the merge or split that would follow renumbers blocks.\n";
+            return 1;
+        }
         if (count("clamp")) {
             std::cerr << "--clamp: the initial partition has " << ka << " + " << kb << " blocks, not " << KA << " + " << KB
                       << ", and the merge or split that would follow renumbers blocks.\n";
@@ -1334,6 +1385,7 @@ int main(int argc, char const* argv[]) {
             const size_t n_samples = sampling_steps / (sweeps_between * N);
             blockmodel_t blockmodel(memberships_init, types_init, KA + KB, KA, KB, epsilon, &adj_list, opt);
             if (!clamp_mask.empty()) blockmodel.clamp(clamp_mask);
+            if (cn_classes) blockmodel.constrain(cn_classes, cn_class, cn_allowed);
             if (randomize)
                 blockmodel.shuffle_bisbm();
             else
@@ -1789,6 +1841,7 @@ int main(int argc, char const* argv[]) {
     try {
         blockmodel_t blockmodel(memberships_init, types_init, KA + KB, KA, KB, epsilon, &adj_list, opt);  // :453
         if (!clamp_mask.empty()) blockmodel.clamp(clamp_mask);
+        if (cn_classes) blockmodel.constrain(cn_classes, cn_class, cn_allowed);
         if (randomize)
             blockmodel.shuffle_bisbm();
         else

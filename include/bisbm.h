@@ -731,6 +731,66 @@ int bisbm_reshuffle_get_total(bisbm_handle h, uint64_t *out /* n_chains */);
 int bisbm_clamp_set(bisbm_handle h, const uint8_t *mask /* n; non-zero = held; NULL clears */);
 int bisbm_clamp_get(bisbm_handle h, uint8_t *mask_out /* n, may be NULL */, uint64_t *n_clamped_out /* may be NULL */);
 
+/* Block constraints (no reference counterpart; graph-tool's pclabel / bfield): where a clamp says "this node stays", a
+ * constraint says "this node is in one of these blocks".  A taxonomy for some nodes, one side of a partly curated graph, the
+ * refinement of a coarse fit inside its own blocks (every block gets children, a node chooses among the children of its
+ * parent).  One set per handle: a class id per node, class_of_node[n], one byte each, at most 256 classes, and a table
+ * allowed[n_classes][ka + kb], one byte per cell, non-zero meaning allowed.  Node v may sit in block s iff
+ * allowed[class_of_node[v]][s] is set and s is of v's type; A_v is the set of those blocks, and the table's entries for blocks
+ * of the other type are ignored.  Classes that allow disjoint sets break the label symmetry between those sets in every chain
+ * without pinning a node.  Philox mode and byte labels only.
+ * set: validates before anything changes.  n_classes <= 256 and every class id < n_classes, else BISBM_ERR_INVALID_ARG.  Then,
+ * on every device of the handle, a kernel looks at every node's current label in every chain: a label outside A_v is
+ * BISBM_ERR_STATE with a message naming the global chain id, the node and the label of the first offender.  A refusal leaves
+ * the constraints that were in place on every device.  Each device keeps the class bytes (n bytes), the table as eight 32-bit
+ * words per class (at most 8 KiB) and one list of the open nodes sorted by (type, class, id) (4 bytes per open node), which is
+ * rebuilt whenever the clamp or the constraints change.  n_classes = 0 or a NULL pointer clears.  A table under which every
+ * A_v is all blocks of v's type IS "no constraints" and is stored as a clear: the kernels are handed no table, MH sweeps run
+ * the production kernel, every call is bit for bit that of a handle that never had constraints, and get reports 0 classes.
+ * get: n_classes, the class bytes and the table as 0 / 1 bytes (each pointer may be NULL; without constraints 0 classes, all
+ * class bytes 0, allowed_out untouched).
+ *   1. MH SWEEPS: the proposal is drawn exactly as always.  If its target s is of the node's type, is not the node's own
+ *      block and is not in A_v, the step is not evaluated; in every counter it is a step that was not accepted, as the step of
+ *      a clamped node is: it counts in the n steps of the sweep and in the early stop's count of T < 1 steps, never in
+ *      `accepted`, and adds nothing to the running sum.  A proposal of the node's own block is always allowed.  The Hastings
+ *      ratio of a move inside A_v is unchanged: refusing the proposals that leave the admissible set restricts a chain that is
+ *      in detailed balance with exp(-beta S) to that set, and a restriction of a reversible chain to a subset, with the refused
+ *      mass put on staying, is reversible with respect to the restricted distribution.  The draws of a
+ *      step are keyed by its position, so a refusal moves nobody else's draws: the constrained chain equals the unconstrained
+ *      one up to the first step at which the unconstrained chain accepts a target outside A_v.  While constraints are set the
+ *      sweeps run the generic kernel (README.md).
+ *   2. HEAT-BATH SWEEPS AND POLISHING: a node with |A_v| = 1 is held exactly as a clamped node is -- in the chunk header, no
+ *      row read, no draw used.  Otherwise the row is restricted to A_v: mn = the minimum of dS_s over s in A_v (the 0 at r
+ *      included), w_s = exp(-beta (dS_s - mn)) for s in A_v and exactly 0.0 for s outside; Z, P, C_s and the choice are as
+ *      without constraints, in the same order (a +0.0 term keeps every bit).  Greedy: the lowest s in A_v that attains mn, and
+ *      only if mn < 0.  With stop_when_settled the end state is a local minimum over the admissible moves.
+ *   3. PAIR RESHUFFLES: a member is an open node of r or s whose class allows BOTH r and s.  Everything indexed by the member
+ *      number is unchanged in form.  A non-member is treated exactly as a clamped node: it stays in n_r, m_r and m, the FREE
+ *      test counts it, and M < 2 is the counted no-op.  The member set depends on the union of the two blocks and on the
+ *      constraints, not on how the union is divided, so the move and its reverse see the same members: detailed balance holds
+ *      as under a clamp.
+ *   4. SHUFFLE: the labels of the open nodes of each (type, class) are permuted among themselves (equal class: equal A_v, so
+ *      every label stays admissible and block sizes are preserved).  For type t and class c with F the ascending list of the
+ *      open nodes of that type and class: f = the keyed Feistel permutation of bisbm_shuffle on the domain |F| -- same
+ *      purpose 3, same index (t << 32) | epoch, same chain id -- under the Philox key seed + c * 0x9E3779B97F4A7C15 (mod
+ *      2^64), and new[F[i]] = old[F[f(i)]].  Class 0 has the key of the plain shuffle: with one class this is the clamped or
+ *      unclamped shuffle, bit for bit.
+ *   5. REPLICA EXCHANGE, ROUNDS, POPULATION ANNEALING: the constraints are the handle's, so every kernel of a round is handed
+ *      them; chain c stays, bit for bit, the chain that a one-chain handle of its global id with the same constraints runs.  A
+ *      resampled slot carries its ancestor's labels, which were admissible.
+ * Constraints and a clamp are independent and may both be set.  bisbm_set_memberships under constraints refuses a vector
+ * that violates them (BISBM_ERR_INVALID_ARG, naming the first node).  The analysis calls only read state and are unchanged;
+ * bisbm_conditionals_* keeps reporting the UNRESTRICTED row.  Refused, with a message and nothing changed:
+ * BISBM_RNG_MT19937_COMPAT and two-byte labels BISBM_ERR_UNSUPPORTED; chains grouped by shape BISBM_ERR_STATE.  While
+ * constraints are set bisbm_agg_merge and bisbm_agg_merge_total are BISBM_ERR_STATE (bisbm_constraints_set(h, 0, NULL, NULL)
+ * first).
+ * Out of scope: a table per chain, constraints in the production kernel (DESIGN.md section 26's follow-up serves both),
+ * restricted rows in bisbm_conditionals_*, mt19937-compat arithmetic, wide handles, chains grouped by shape, merges or splits
+ * under constraints, soft priors over blocks. */
+int bisbm_constraints_set(bisbm_handle h, uint32_t n_classes, const uint8_t *class_of_node /* n */,
+                          const uint8_t *allowed /* n_classes * (ka + kb) */);   /* 0 / NULL clears */
+int bisbm_constraints_get(bisbm_handle h, uint32_t *n_classes_out, uint8_t *class_of_node_out, uint8_t *allowed_out);
+
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the
  * chains' partitions on the device, and a small deterministic grouping on the host.

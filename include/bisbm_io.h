@@ -30,6 +30,19 @@ long bisbm_io_read_memberships(const char *path, uint32_t **labels);
  * included); `err` (err_cap bytes, may be NULL) then holds a message that names the token, and *mask is NULL. */
 long bisbm_io_read_clamp(const char *path, uint64_t n, uint8_t **mask, char *err, size_t err_cap);
 
+/* The constraints file of `mcmc --constraints` (no reference counterpart; include/bisbm.h, "Block constraints"): one line per
+ * constrained node -- the node id, then its allowed blocks as global labels (type a: 0 .. ka-1, type b: ka .. ka+kb-1), all
+ * decimal numbers separated by blanks or tabs.  Lines in any order; a node may be repeated with the same blocks; blank lines
+ * are skipped; an empty file constrains nobody.  The lists become classes: class 0 allows everything and holds the unlisted
+ * nodes, every distinct list (as a set, per type) gets the next class, at most 255 of them.  *class_of_node gets n malloc'ed
+ * bytes and *allowed a malloc'ed table of classes x (ka + kb) bytes, 1 = allowed (the columns of the other type are 1: they
+ * are ignored).  Returns the number of classes (>= 1), -1 when the file cannot be opened, -2 for a malformed line: a token
+ * that is not a number of decimal digits alone, a node id >= n or a block >= ka + kb (a number past 2^64 included), a block of
+ * the other type, a node without a block, a node repeated with other blocks, a 256th distinct list; `err` (err_cap bytes, may
+ * be NULL) then holds a message that names the offending token, and both outputs are NULL. */
+long bisbm_io_read_constraints(const char *path, uint64_t n, uint64_t na, uint32_t ka, uint32_t kb, uint8_t **class_of_node,
+                               uint8_t **allowed, char *err, size_t err_cap);
+
 /* edge_to_adj (graph_utilities.cc:36-49) as CSR: undirected, duplicates kept, each row in edge-file
  * order.  rowptr has n+1 entries, col has 2*n_edges.  Returns 0, or -1 when an id is >= n. */
 int bisbm_io_edges_to_csr(const uint64_t *a, const uint64_t *b, size_t n_edges, uint64_t n,

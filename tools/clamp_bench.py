@@ -33,15 +33,15 @@ OUT, timed, write_out = hb.OUT, hb.timed, hb.write_out
 NEW_SYMBOLS = ("bisbm_clamp_set", "bisbm_clamp_get", "bisbm_io_read_clamp")
 
 
-def parent_package(lib_path):
-    """The Python package a second time, bound to the parent commit's library (which lacks this feature's symbols)."""
+def parent_package(lib_path, drop=NEW_SYMBOLS):
+    """The Python package a second time, bound to the parent commit's library (which lacks this feature's symbols, `drop`)."""
     pkg = os.path.join(ROOT, "bipartitesbm-mcmc_amd")
     spec = importlib.util.spec_from_file_location("bisbm_parent", os.path.join(pkg, "__init__.py"), submodule_search_locations=[pkg])
     mod = importlib.util.module_from_spec(spec)
     sys.modules["bisbm_parent"] = mod
     spec.loader.exec_module(mod)
     mod.LIB_PATH = os.path.abspath(lib_path)
-    for name in NEW_SYMBOLS:
+    for name in drop:
         mod.ABI.pop(name, None)
     mod.lib()
     return mod
