@@ -168,6 +168,9 @@ ABI = {
     "bisbm_clamp_get": (C.c_int, [C.c_void_p, _u8p, _u64p]),
     "bisbm_constraints_set": (C.c_int, [C.c_void_p, C.c_uint32, _u8p, _u8p]),
     "bisbm_constraints_get": (C.c_int, [C.c_void_p, _u32p, _u8p, _u8p]),
+    "bisbm_fields_set": (C.c_int, [C.c_void_p, C.c_uint32, _u8p, _f64p]),
+    "bisbm_fields_get": (C.c_int, [C.c_void_p, _u32p, _u8p, _f64p]),
+    "bisbm_fields_energy": (C.c_int, [C.c_void_p, _f64p]),
     "bisbm_debug_exp": (C.c_int, [C.c_void_p, _f64p, C.c_size_t, _f64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
@@ -196,6 +199,8 @@ ABI = {
     "bisbm_io_read_clamp": (C.c_long, [C.c_char_p, C.c_uint64, C.POINTER(_u8p), C.c_char_p, C.c_size_t]),
     "bisbm_io_read_constraints": (C.c_long, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_u8p), C.POINTER(_u8p),
                                              C.c_char_p, C.c_size_t]),
+    "bisbm_io_read_fields": (C.c_long, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_u8p), C.POINTER(_f64p),
+                                        C.c_char_p, C.c_size_t]),
     "bisbm_io_edges_to_csr": (C.c_int, [_u64p, _u64p, C.c_size_t, C.c_uint64, _u64p, _u32p]),
     "bisbm_io_load_csr": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(_u64p), C.POINTER(_u32p), _u64p,
                                     C.POINTER(C.c_int)]),
@@ -391,6 +396,102 @@ def admissible_start(na, nb, ka, kb, class_of_node, allowed):
     empty = np.flatnonzero(np.bincount(out, minlength=ka + kb) == 0)
     if len(empty):
         raise ValueError("block %d ends up empty" % empty[0])
+    return out
+
+
+def load_fields(path, na, nb, ka, kb):
+    """The fields file of ``mcmc --fields`` (include/bisbm_io.h): one line per node with a prior, its id and then block:weight
+    pairs -> (class_of_node uint8 [n], field float64 [n_classes, ka + kb]) for BlockModel.set_fields; phi = -ln weight, class 0
+    is the zero row and holds the unlisted nodes.  A node repeated with another row is an error.  ValueError, with the token
+    named, for a malformed line."""
+    L = lib()
+    pc, pf = _u8p(), _f64p()
+    err = C.create_string_buffer(512)
+    n = int(na) + int(nb)
+    count = L.bisbm_io_read_fields(os.fsencode(path), n, int(na), int(ka), int(kb), C.byref(pc), C.byref(pf), err, len(err))
+    if count == -1:
+        raise FileNotFoundError(path)
+    if count < 0:
+        raise ValueError(err.value.decode())
+    K = int(ka) + int(kb)
+    cls = np.ctypeslib.as_array(pc, shape=(max(n, 1),))[:n].copy()
+    field = np.ctypeslib.as_array(pf, shape=(max(count * K, 1),))[:count * K].reshape(count, K).copy()
+    L.bisbm_io_free(pc)
+    L.bisbm_io_free(pf)
+    return cls, field
+
+
+def fields_from_weights(n, K, weights, na=None, ka=None):
+    """(class_of_node uint8 [n], field float64 [n_classes, K]) from {node: {block: weight}}: the energy of a listed block is
+    phi = -ln weight, an unlisted block has weight 1 (phi = 0), an unlisted node gets class 0, whose row is zero.  Every distinct
+    row gets the next class -- at most 255 of them beside class 0, so that a class id is one byte; more is a ValueError.  A weight
+    that is <= 0 or not finite is a ValueError (0 would forbid the block: that is what constraints are for).  With `na` and `ka`
+    (the type-a nodes are 0 .. na-1, the type-a blocks 0 .. ka-1) a block of the other type is a ValueError; without them the
+    row is taken as given (the engine ignores the other type's entries)."""
+    import math
+    n, K = int(n), int(K)
+    cls = np.zeros(n, dtype=np.uint8)
+    rows, index = [np.zeros(K, dtype=np.float64)], {}
+    index[rows[0].tobytes()] = 0
+    for v in sorted(weights):
+        if not 0 <= int(v) < n:
+            raise ValueError("node %r is not in [0, %d)" % (v, n))
+        row = np.zeros(K, dtype=np.float64)
+        for s, w in weights[v].items():
+            s, w = int(s), float(w)
+            if not 0 <= s < K:
+                raise ValueError("node %r: block %d is not in [0, %d)" % (v, s, K))
+            if na is not None and (s >= int(ka)) != (int(v) >= int(na)):
+                raise ValueError("node %r: block %d is a block of the other type" % (v, s))
+            if w == 0.0:
+                raise ValueError("node %r, block %d: a weight of 0 forbids the block; use constraints (BlockModel.constrain) for that" % (v, s))
+            if not (w > 0.0) or not math.isfinite(w):
+                raise ValueError("node %r, block %d: weight %r is not finite and above 0" % (v, s, w))
+            row[s] = 0.0 - math.log(w)
+        key = row.tobytes()
+        if key not in index:
+            if len(rows) == 256:
+                raise ValueError("more than 255 distinct rows beside class 0: a class id is one byte")
+            index[key] = len(rows)
+            rows.append(row)
+        cls[int(v)] = index[key]
+    return cls, np.array(rows)
+
+
+def numpy_field_energy(labels, class_of_node, field, na, ka):
+    """Phi of one label vector as bisbm_fields_energy defines it (include/bisbm.h, "Block fields", 7.), bit for bit: the integer
+    histogram count[class][block] over the nodes, then the sum over (class ascending, block ascending, the own type's range of
+    the nodes counted) of float(count) * phi, added sequentially from 0.0 with zero counts skipped."""
+    labels = np.asarray(labels).astype(np.int64)
+    cls = np.asarray(class_of_node).astype(np.int64)
+    field = np.asarray(field, dtype=np.float64)
+    n_classes, K = field.shape
+    na, ka = int(na), int(ka)
+    count = np.zeros((n_classes, K), dtype=np.int64)
+    for v in range(len(labels)):
+        b = int(labels[v])
+        if (b >= ka) != (v >= na):
+            raise ValueError("label %d of node %d is not a block of the node's type" % (b, v))
+        count[cls[v], b] += 1
+    phi = 0.0
+    for c in range(n_classes):
+        for b in range(K):
+            if count[c, b]:
+                phi = phi + float(count[c, b]) * float(field[c, b])
+    return phi
+
+
+def numpy_field_row(row, r_loc, f_own):
+    """The heat-bath row under block fields (include/bisbm.h, "Block fields", 2.) from the model's row dS_s over the blocks of
+    the node's type (BlockModel.conditionals_last), the node's block within its type and the entries of its class's field row
+    over the same blocks: row[s] + (f[s] - f[r]) for s != r, and 0 at r.  Bit for bit the device's row."""
+    row = np.asarray(row, dtype=np.float64)
+    f = np.asarray(f_own, dtype=np.float64)
+    r = int(r_loc)
+    out = np.zeros(len(row), dtype=np.float64)
+    for s in range(len(row)):
+        if s != r:
+            out[s] = float(row[s]) + (float(f[s]) - float(f[r]))
     return out
 
 
@@ -803,6 +904,49 @@ class BlockModel:
         table = np.zeros((int(k[0]), self.K), dtype=np.uint8)
         self._check(self._L.bisbm_constraints_get(self._h, None, _p(cls, _u8p), _p(table, _u8p)))
         return cls, table.astype(bool)
+
+    # -- block fields (include/bisbm.h, "Block fields")
+    def set_fields(self, class_of_node, field):
+        """Gives every node a soft prior over blocks, in every chain and through every sampler: `class_of_node` is an array of n
+        class ids (at most 256 classes), `field` a [n_classes, KA + KB] table of finite energies phi in nats (the entries for
+        blocks of the other type are ignored).  With Phi = the sum of phi[class(v)][b_v] over the nodes every sampler targets
+        exp(-beta (S + Phi)): a node's prior weight for block s is exp(-phi_s) (fields_from_weights builds the pair from
+        weights).  A new call replaces the fields, a table of zeros is clear_fields().  Independent of clamp() and constrain().
+        While fields are set MH sweeps run the generic kernel (slower; README.md), get_entropy() advances by dS + dPhi, polish()
+        certifies a minimum of S + Phi, replica exchange and population annealing weigh S + Phi, and agg_merge is refused;
+        entropy() stays the description length."""
+        cls = np.asarray(class_of_node)
+        table = np.asarray(field, dtype=np.float64)
+        if cls.shape != (self.n,) or cls.dtype.kind not in "iub":
+            raise ValueError("class_of_node has one integer per node (%d), not %s %s" % (self.n, cls.dtype, cls.shape))
+        if table.ndim != 2 or table.shape[1] != self.K or not 1 <= table.shape[0] <= 256:
+            raise ValueError("field is a [n_classes <= 256, %d] table, not %s" % (self.K, table.shape))
+        if cls.size and (cls.min() < 0 or cls.max() >= table.shape[0]):
+            raise ValueError("class ids must be in [0, %d)" % table.shape[0])
+        cls8 = np.ascontiguousarray(cls, dtype=np.uint8)
+        tab = np.ascontiguousarray(table, dtype=np.float64)
+        self._check(self._L.bisbm_fields_set(self._h, int(table.shape[0]), _p(cls8, _u8p), _p(tab, _f64p)))
+
+    def clear_fields(self):
+        """Clears the fields: from here on every call is bit for bit what a model that never had any does."""
+        self._check(self._L.bisbm_fields_set(self._h, 0, None, None))
+
+    def fields(self):
+        """(class_of_node uint8 [n], field float64 [n_classes, KA + KB]) as set; without fields (None, None)."""
+        k = np.zeros(1, dtype=np.uint32)
+        self._check(self._L.bisbm_fields_get(self._h, _p(k, _u32p), None, None))
+        if not int(k[0]):
+            return None, None
+        cls = np.zeros(self.n, dtype=np.uint8)
+        table = np.zeros((int(k[0]), self.K), dtype=np.float64)
+        self._check(self._L.bisbm_fields_get(self._h, None, _p(cls, _u8p), _p(table, _f64p)))
+        return cls, table
+
+    def field_energy(self):
+        """Phi per chain (bisbm_fields_energy; numpy_field_energy is its host statement); zeros without fields."""
+        out = np.zeros(self.n_chains, dtype=np.float64)
+        self._check(self._L.bisbm_fields_energy(self._h, _p(out, _f64p)))
+        return out
 
     def debug_exp(self, x):
         """exp(x) as the device evaluates it (the host replays of the pair reshuffles take their exponentials from here)"""

@@ -104,7 +104,9 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     // ... and while block constraints are set: it is the one that looks a proposal's target up ("Block constraints")
     p.clamp = h->clamp.mask_or_null();
     p.cn_class = h->constraints.class_or_null(), p.cn_bits = h->constraints.bits_or_null();
-    const bool fast = h->rng_mode == BISBM_RNG_PHILOX && h->ka <= 64 && h->kb <= 64 && !h->wide && !(force && force[0] == '1') && !p.clamp && !p.cn_bits;
+    // ... and while block fields are set: it is the one that adds the field to a step's dS ("Block fields")
+    p.fl_class = h->fields.class_or_null(), p.fl_field = h->fields.field_or_null();
+    const bool fast = h->rng_mode == BISBM_RNG_PHILOX && h->ka <= 64 && h->kb <= 64 && !h->wide && !(force && force[0] == '1') && !p.clamp && !p.cn_bits && !p.fl_field;
     // Temperatures of the pow / log schedules are evaluated with the host libm (the reference's own values) into a table of
     // at most kTabCap steps.  The generic kernel evaluates pow / log itself beyond it; the production kernel holds no
     // pow / log at all: a longer call runs as several launches of whole sweeps, each with the slice of the table it covers

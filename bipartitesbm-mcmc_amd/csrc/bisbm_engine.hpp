@@ -34,6 +34,8 @@
 //   bisbm_clamp.hip      clamped nodes: the mask, the lists of the open nodes, the clamped shuffle kernel; C ABI
 //   bisbm_constraints.hip  block constraints: a class per node and a table of allowed blocks per class; the validation kernel,
 //                        the list of the open nodes by (type, class); C ABI
+//   bisbm_fields.hip     block fields: a class per node and a table of f64 energies per class and block; the kernel of a
+//                        chain's field energy Phi; C ABI
 //
 // Reference lines cited as <file>:<line> relative to /root/reference/src.
 #pragma once
@@ -442,6 +444,21 @@ struct ConstraintState {
     bool allows(uint64_t v, uint32_t s) const { return ((bits[(size_t)cls[v] * 8 + (s >> 5)] >> (s & 31u)) & 1u) != 0u; }
 };
 
+// Block fields (bisbm_fields.hip).  The class bytes and the table belong to the handle the caller holds and, with the device
+// copies, to every device entry (chains grouped by shape are refused).  n_classes == 0: no fields, and no kernel is handed a
+// pointer -- a table of zeros is stored as that.
+struct FieldState {
+    uint32_t n_classes = 0;
+    std::vector<uint8_t> cls;    // [n] field class of every node
+    std::vector<double> field;   // [n_classes][K] as given
+    // device entry
+    DeviceBuf<uint8_t> d_class;  // [n]
+    DeviceBuf<double> d_field;   // [n_classes][K]
+    DeviceBuf<double> d_phi;     // [n_chains] Phi of every chain (fields_energy_device)
+    const uint8_t* class_or_null() const { return n_classes ? d_class.get() : nullptr; }
+    const double* field_or_null() const { return n_classes ? d_field.get() : nullptr; }
+};
+
 }  // namespace bisbm
 
 // ------------------------------------------------------------------------------------------
@@ -541,6 +558,7 @@ struct bisbm_engine {
     bisbm::BlockSumState blocks;
     bisbm::ClampState clamp;
     bisbm::ConstraintState constraints;
+    bisbm::FieldState fields;
 };
 
 namespace bisbm {
@@ -788,6 +806,9 @@ int reshuffle_read_back(bisbm_engine* h);  // ... the copy alone, after a wait f
 // mask given (0 / 1 bytes, empty: none); nothing to do without constraints.  bisbm_clamp_set calls it for every mask it puts in
 // place; bisbm_constraints.hip
 int constraints_rebuild_open(bisbm_engine* e, const std::vector<uint8_t>& clamp_mask);
+// block fields: Phi of every chain of a kernel-running engine that has fields, into its FieldState::d_phi on its stream (no
+// wait); what bisbm_fields_energy, the exchange round and the resampling step all read.  bisbm_fields.hip
+int fields_energy_device(bisbm_engine* e);
 // BISBM_ERR_INVALID_ARG when a move of up to max(na, nb) members with `scans` launch scans could use 2^32 draws or more
 int reshuffle_check_scans(bisbm_engine* h, uint32_t scans);
 // bisbm_marginals_accumulate with the alignment on; bisbm_align.hip

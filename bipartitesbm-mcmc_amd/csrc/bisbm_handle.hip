@@ -50,6 +50,7 @@ void free_all(bisbm_engine* h) {
     h->queries = QueryScoreState(), h->coassign = CoassignState(), h->foldin = FoldinState(), h->cond = ConditionalState();
     h->clamp = ClampState();
     h->constraints = ConstraintState();
+    h->fields = FieldState();
     h->d_T.reset();
     if (h->root) {  // a sub-engine: the graph and the tables belong to the handle it serves
         h->d_rowptr = nullptr, h->d_col = nullptr, h->d_lgamma = nullptr, h->d_logtab = nullptr, h->d_q = nullptr;

@@ -33,7 +33,10 @@ namespace {
 // always did: an unclamped handle runs the code it ran before the clamp existed.
 // CN: the launch has block constraints (p.cn_bits is not NULL; p.clamp may be set as well): the one instance that walks the
 // chunk as a clamped launch does and restricts the rows.  The two instances without it hold none of its code.
-template <bool EL, bool CL, bool CN>
+// FL: the launch has block fields (p.fl_field is not NULL; include/bisbm.h, "Block fields"): the one instance per EL that adds the
+// field to the row.  It is compiled with CL and CN and serves a clamp and constraints beside the field by testing their pointers
+// at run time; the instances without it hold none of its code.
+template <bool EL, bool CL, bool CN, bool FL = false>
 __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const uint32_t chain = blockIdx.x;
@@ -76,16 +79,21 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
             for (uint32_t vi0 = 0; vi0 < n_cls; vi0 += kWave) {
                 // ---- chunk header: lane q holds the node, row extent and own label of position vi0 + q ----
                 const uint32_t cnt = n_cls - vi0 < (uint32_t)kWave ? n_cls - vi0 : (uint32_t)kWave;
-                uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0, held_l = 0, cls_l = 0;
+                uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0, held_l = 0, cls_l = 0, fcls_l = 0;
                 if (lane < cnt) {
                     v_l = v0 + order(vi0 + lane);
                     beg_l = p.rowptr[v_l];
                     deg_l = p.rowptr[v_l + 1] - beg_l;
                     r_l = wc.labels[v_l];
                     if (CL && !CN) held_l = p.clamp[v_l];
-                    if (CN) {  // (held: clamped, or a class with one allowed block of the type)
+                    if (CN && !FL) {  // (held: clamped, or a class with one allowed block of the type)
                         cls_l = p.cn_class[v_l];
                         held_l = ((p.clamp && p.clamp[v_l] != 0) || cn_count(p.cn_bits, cls_l, own0, k_own) <= 1u) ? 1u : 0u;
+                    }
+                    if (FL) {  // (the same with the constraints' pointers tested; the field class of the node)
+                        if (p.cn_bits) cls_l = p.cn_class[v_l];
+                        held_l = ((p.clamp && p.clamp[v_l] != 0) || (p.cn_bits && cn_count(p.cn_bits, cls_l, own0, k_own) <= 1u)) ? 1u : 0u;
+                        fcls_l = p.fl_class[v_l];
                     }
                 }
                 // under a clamp, the open positions of the chunk: a clamped node stays as a node that is not free does, its row
@@ -105,7 +113,10 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                     if (r_loc >= k_own) continue;  // (a valid label: never)
                     const uint32_t cls = CN ? readlane(cls_l, q) : 0u;  // (wave-uniform: the table reads below are of one row)
                     // is block tid of the type in A_v (the node's own block always is)?
-                    auto admits = [&](uint32_t tid) { return !CN || tid == r_loc || cn_allows(p.cn_bits, cls, own0 + tid); };
+                    auto admits = [&](uint32_t tid) { return !CN || (FL && !p.cn_bits) || tid == r_loc || cn_allows(p.cn_bits, cls, own0 + tid); };
+                    // block fields: the row of the node's class (wave-uniform), f[r] for every lane
+                    const double* f_row = FL ? p.fl_field + (size_t)readlane(fcls_l, q) * (p.ka + p.kb) : nullptr;
+                    const double f_r = FL ? f_row[r] : 0.;
                     const int n0r = nr[r];
                     if (n0r <= 1) continue;  // not free: the node stays, and no draw is used
                     // 1., 2. k_v and the non-zero (t, k_t) in ascending t, with the r side's two table values
@@ -167,7 +178,10 @@ __global__ __launch_bounds__(kWave) void heatbath_kernel(HeatbathParams p) {
                         const double tail1 = tail1_r + (lg_s1 - lg_s0);
                         const double tail2 = tail2_r + (lg_e1 - lg_e2);
                         const double tail3 = (readlane(lq_r, 0u) - readlane(lq_r, 1u)) + (lq_s1 - lq_s0);
-                        if (tid < k_own) s_dS[tid] = tid == r_loc ? 0. : ((acc + tail1) + tail2) + tail3;
+                        if (FL) {  // (one coalesced read of the row; idle lanes do not index the table: the last row ends the allocation)
+                            if (tid < k_own) s_dS[tid] = tid == r_loc ? 0. : (((acc + tail1) + tail2) + tail3) + (f_row[own0 + tid] - f_r);
+                        } else if (tid < k_own)
+                            s_dS[tid] = tid == r_loc ? 0. : ((acc + tail1) + tail2) + tail3;
                     }
                     wave_fence();
                     // The passes that are sequential in ascending s by definition -- dS_min, Z, C_s -- run on registers: the lane of
@@ -292,10 +306,13 @@ int bisbm::heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int st
     p.stop_when_settled = stop_when_settled ? 1u : 0u;
     p.clamp = h->clamp.mask_or_null();
     p.cn_class = h->constraints.class_or_null(), p.cn_bits = h->constraints.bits_or_null();
+    p.fl_class = h->fields.class_or_null(), p.fl_field = h->fields.field_or_null();
     size_t lds;  // (the four double[kmax] arrays of the kernel's own: a multiple of 16 bytes, as the rounded chain state is)
     if (int rc = wave_chain_plan(h, 4 * sizeof(double) * std::max(h->ka, h->kb), p, lds)) return rc;
     h->ent_prev_valid = false;  // (the block state moves)
-    if (p.cn_bits)
+    if (p.fl_field)
+        HIPCHK(h, launch_wave_chain(heatbath_kernel<true, true, true, true>, heatbath_kernel<false, true, true, true>, p, lds, h->stream));
+    else if (p.cn_bits)
         HIPCHK(h, launch_wave_chain(heatbath_kernel<true, true, true>, heatbath_kernel<false, true, true>, p, lds, h->stream));
     else if (p.clamp)
         HIPCHK(h, launch_wave_chain(heatbath_kernel<true, true, false>, heatbath_kernel<false, true, false>, p, lds, h->stream));

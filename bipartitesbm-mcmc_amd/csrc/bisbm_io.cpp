@@ -278,6 +278,108 @@ long bisbm_io_read_constraints(const char* path, uint64_t n, uint64_t na, uint32
     return (long)rows.size();
 }
 
+long bisbm_io_read_fields(const char* path, uint64_t n, uint64_t na, uint32_t ka, uint32_t kb, uint8_t** class_of_node, double** field,
+                          char* err, size_t err_cap) {
+    if (err && err_cap) err[0] = 0;
+    if (class_of_node) *class_of_node = nullptr;
+    if (field) *field = nullptr;
+    const uint32_t K = ka + kb;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) {
+        if (err) std::snprintf(err, err_cap, "cannot open %s", path);
+        return -1;
+    }
+    LineReader rd(f);
+    // a token as a number: 0 it is one (below 2^64), 1 it holds something that is no decimal digit (or nothing), 2 it is 2^64 or more
+    auto number = [](const std::string& tok, uint64_t& v) -> int {
+        v = 0;
+        bool past = false;
+        if (tok.empty()) return 1;
+        for (char ch : tok) {
+            if (ch < '0' || ch > '9') return 1;
+            if (past || v > (UINT64_MAX - (uint64_t)(ch - '0')) / 10)
+                past = true;
+            else
+                v = v * 10 + (uint64_t)(ch - '0');
+        }
+        return past ? 2 : 0;
+    };
+    std::vector<std::vector<double>> rows;  // row c of the table: class 0 is the zero row
+    rows.emplace_back((size_t)K, 0.);
+    std::vector<uint8_t> cls((size_t)n, 0), listed((size_t)n, 0);
+    std::vector<std::string> toks;
+    std::string tok;
+    bool bad = false;
+    auto fail_with = [&](const std::string& what) {
+        if (err) std::snprintf(err, err_cap, "%s: %s", path, what.c_str());
+        bad = true;
+    };
+    auto take_line = [&]() {  // the tokens of one line: a node id, then block:weight pairs
+        if (toks.empty()) return;
+        uint64_t v = 0;
+        const int kind = number(toks[0], v);
+        if (kind == 1) return fail_with("'" + toks[0] + "' is not a node id");
+        if (kind == 2 || v >= n) return fail_with("node id '" + toks[0] + "' is out of range (the graph has " + std::to_string(n) + " nodes)");
+        if (toks.size() == 1) return fail_with("node '" + toks[0] + "' has no block:weight on its line");
+        const bool tb = v >= na;
+        std::vector<double> row((size_t)K, 0.);
+        std::vector<uint8_t> seen((size_t)K, 0);
+        for (size_t i = 1; i < toks.size(); ++i) {
+            const size_t colon = toks[i].find(':');
+            if (colon == std::string::npos) return fail_with("'" + toks[i] + "' is not block:weight");
+            const std::string bt = toks[i].substr(0, colon), wt = toks[i].substr(colon + 1);
+            uint64_t s = 0;
+            const int ks = number(bt, s);
+            if (ks == 1) return fail_with("'" + toks[i] + "': '" + bt + "' is not a block");
+            if (ks == 2 || s >= K) return fail_with("'" + toks[i] + "': block '" + bt + "' is out of range (there are " + std::to_string(K) + " blocks)");
+            if ((s >= ka) != tb) return fail_with("'" + toks[i] + "': block '" + bt + "' is not a block of the type of node " + std::to_string(v));
+            if (seen[(size_t)s]) return fail_with("'" + toks[i] + "': block '" + bt + "' is listed twice for node " + std::to_string(v));
+            // the weight: a decimal or scientific number, nothing else in the token (no "inf", "nan", hex or blanks)
+            bool plain = !wt.empty();
+            for (char ch : wt) plain = plain && ((ch >= '0' && ch <= '9') || ch == '.' || ch == 'e' || ch == 'E' || ch == '+' || ch == '-');
+            char* end = nullptr;
+            const double w = plain ? std::strtod(wt.c_str(), &end) : 0.;
+            if (!plain || end != wt.c_str() + wt.size()) return fail_with("'" + toks[i] + "': '" + wt + "' is not a weight");
+            if (w == 0.) return fail_with("'" + toks[i] + "': a weight of 0 forbids the block, which is what --constraints is for");
+            if (!(w > 0.) || !std::isfinite(w)) return fail_with("'" + toks[i] + "': a weight is finite and above 0");
+            row[(size_t)s] = 0. - std::log(w);  // (weight 1: +0.0, the bits of an unlisted block)
+            seen[(size_t)s] = 1;
+        }
+        size_t c = 0;
+        while (c < rows.size() && std::memcmp(rows[c].data(), row.data(), sizeof(double) * K) != 0) ++c;
+        if (listed[(size_t)v]) {
+            if (cls[(size_t)v] != c) fail_with("node '" + toks[0] + "' is listed twice with different weights");
+            return;
+        }
+        if (c == rows.size()) {
+            if (rows.size() == 256) return fail_with("the line of node '" + toks[0] + "' holds the 256th distinct row: a class id is one byte, at most 255 rows beside class 0");
+            rows.push_back(row);
+        }
+        cls[(size_t)v] = (uint8_t)c, listed[(size_t)v] = 1;
+    };
+    for (int ch = rd.get(); !bad; ch = rd.get()) {
+        const bool eol = ch < 0 || ch == '\n';
+        const bool blank = ch == ' ' || ch == '\t' || ch == '\r' || ch == '\f' || ch == '\v';
+        if (!eol && !blank) {
+            tok.push_back((char)ch);
+            continue;
+        }
+        if (!tok.empty()) toks.push_back(tok), tok.clear();
+        if (eol) {
+            take_line();
+            toks.clear();
+        }
+        if (ch < 0) break;
+    }
+    std::fclose(f);
+    if (bad) return -2;
+    std::vector<double> table;
+    for (const auto& row : rows) table.insert(table.end(), row.begin(), row.end());
+    if (class_of_node) *class_of_node = to_malloc(cls);
+    if (field) *field = to_malloc(table);
+    return (long)rows.size();
+}
+
 int bisbm_io_edges_to_csr(const uint64_t* a, const uint64_t* b, size_t n_edges, uint64_t n, uint64_t* rowptr,
                           uint32_t* col) {
     std::memset(rowptr, 0, sizeof(uint64_t) * (n + 1));

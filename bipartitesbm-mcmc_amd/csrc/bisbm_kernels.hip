@@ -135,7 +135,9 @@ __device__ __forceinline__ void wave_fence() {
 
 // CN: the launch has block constraints (p.cn_bits is not NULL; Philox mode and byte labels only).  Without them the instance holds
 // no look-up: a handle without constraints runs the code it ran before they existed.
-template <int RNG, bool EL, bool W, bool CN = false>
+// FL: the launch has block fields (p.fl_field is not NULL; include/bisbm.h, "Block fields").  The one instance per EL that adds the
+// field; it is compiled with CN and serves constraints beside the field by testing p.cn_bits at run time.
+template <int RNG, bool EL, bool W, bool CN = false, bool FL = false>
 __device__ __forceinline__ bool mh_step(const SweepParams& p, const Tables& tab, ChainCtx& c, Mt& engine, Mt& gen,
                                         uint32_t v, uint32_t beg, uint32_t deg, uint32_t r, uint32_t nb_reg,
                                         int lab_reg, double T, uint64_t gstep, uint32_t chain_gid, uint32_t* s_out) {
@@ -274,7 +276,7 @@ __device__ __forceinline__ bool mh_step(const SweepParams& p, const Tables& tab,
     // the verdict of a target of the other type -- not evaluated, not accepted.  v and s are wave-uniform, so the two reads are
     // uniform loads.
     bool barred = false;
-    if (CN && !same && (r < c.ka) == (s < c.ka)) barred = !cn_allows(p.cn_bits, p.cn_class[v], s);
+    if (CN && (!FL || p.cn_bits) && !same && (r < c.ka) == (s < c.ka)) barred = !cn_allows(p.cn_bits, p.cn_class[v], s);
     const bool cross = !same && (((r < c.ka) != (s < c.ka)) || (CN && barred));
     if (same) {
         c.accu_r = 1.;  // :109-112
@@ -400,6 +402,12 @@ __device__ __forceinline__ bool mh_step(const SweepParams& p, const Tables& tab,
             c.accu_r = (deg == 0) ? 1. : accu1 / accu0;  // :185-189
             dS = entropy1 - entropy0;
         }
+        // Block fields (the FL instance alone): dE = dS + (f[s] - f[r]) of the row of v's class, the difference first, then one
+        // add.  v, r and s are wave-uniform: three uniform loads.  `same` keeps 0 and `cross` / `barred` keep infinity above.
+        if (FL) {
+            const double* f = p.fl_field + (size_t)p.fl_class[v] * K;
+            dS = dS + (f[s] - f[r]);
+        }
     }
 
     GSTAMP(c, 5);
@@ -467,7 +475,7 @@ __device__ __forceinline__ bool mh_step(const SweepParams& p, const Tables& tab,
 //   * the neighbour ids of step q+2 and the neighbour labels of step q+1 are in flight while step q
 //     computes (labels fetched early are patched when step q moves one of those neighbours).
 // ------------------------------------------------------------------------------------------
-template <int RNG, bool EL, bool W, bool CN = false>
+template <int RNG, bool EL, bool W, bool CN = false, bool FL = false>
 __global__ __launch_bounds__(kWave) void sweep_kernel(SweepParams p) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const uint32_t chain = blockIdx.x;
@@ -659,7 +667,7 @@ __global__ __launch_bounds__(kWave) void sweep_kernel(SweepParams p) {
                 prefetch();
                 // (a clamped node: the ring is rotated and refilled as for any step, the step itself is one that was not accepted)
                 const bool ok = ((held >> q) & 1ull) == 0ull &&
-                                mh_step<RNG, EL, W, CN>(p, tab, c, engine, gen, v, beg, deg, r, nbC, labC, T,
+                                mh_step<RNG, EL, W, CN, FL>(p, tab, c, engine, gen, v, beg, deg, r, nbC, labC, T,
                                                     sweeps_total * num_nodes + vi, chain_gid, &s);
                 mv_v1 = mv_v2;
                 mv_s1 = mv_s2;
@@ -760,6 +768,8 @@ template __global__ void sweep_kernel<RNG_PHILOX, false, true>(SweepParams);  //
 template __global__ void sweep_kernel<RNG_COMPAT, false, true>(SweepParams);
 template __global__ void sweep_kernel<RNG_PHILOX, true, false, true>(SweepParams);  // block constraints
 template __global__ void sweep_kernel<RNG_PHILOX, false, false, true>(SweepParams);
+template __global__ void sweep_kernel<RNG_PHILOX, true, false, true, true>(SweepParams);  // block fields
+template __global__ void sweep_kernel<RNG_PHILOX, false, false, true, true>(SweepParams);
 
 // ------------------------------------------------------------------------------------------
 // state build: init_bisbm (blockmodel.cc:682-688, compute_n_r :740-746, compute_m :702-714,
@@ -1015,12 +1025,12 @@ __global__ void log_q_probe_kernel(Tables tab, const int32_t* n, const int32_t* 
 // ------------------------------------------------------------------------------------------
 // launchers (called from the host runtime)
 // ------------------------------------------------------------------------------------------
-template <int RNG, bool EL, bool W = false, bool CN = false>
+template <int RNG, bool EL, bool W = false, bool CN = false, bool FL = false>
 static hipError_t launch_sweep_variant(const SweepParams& p, size_t lds_bytes, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)sweep_kernel<RNG, EL, W, CN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipError_t e = hipFuncSetAttribute((const void*)sweep_kernel<RNG, EL, W, CN, FL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((sweep_kernel<RNG, EL, W, CN>), dim3(p.n_chains), dim3(kWave), lds_bytes, stream, p);
+    hipLaunchKernelGGL((sweep_kernel<RNG, EL, W, CN, FL>), dim3(p.n_chains), dim3(kWave), lds_bytes, stream, p);
     return hipGetLastError();
 }
 
@@ -1032,6 +1042,9 @@ hipError_t launch_sweep(const SweepParams& p, int rng_mode, size_t lds_bytes, hi
     else if (rng_mode == RNG_COMPAT)
         e = p.eta_in_lds ? launch_sweep_variant<RNG_COMPAT, true>(p, lds_bytes, stream)
                          : launch_sweep_variant<RNG_COMPAT, false>(p, lds_bytes, stream);
+    else if (p.fl_field)  // (block fields: the instances that add the field, and look the target up where constraints are set too)
+        e = p.eta_in_lds ? launch_sweep_variant<RNG_PHILOX, true, false, true, true>(p, lds_bytes, stream)
+                         : launch_sweep_variant<RNG_PHILOX, false, false, true, true>(p, lds_bytes, stream);
     else if (p.cn_bits)  // (block constraints: the instances that look the target up)
         e = p.eta_in_lds ? launch_sweep_variant<RNG_PHILOX, true, false, true>(p, lds_bytes, stream)
                          : launch_sweep_variant<RNG_PHILOX, false, false, true>(p, lds_bytes, stream);

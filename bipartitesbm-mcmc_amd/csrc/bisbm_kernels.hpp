@@ -120,6 +120,10 @@ struct SweepParams {
     // type outside its class's row is not evaluated and counts as a step that was not accepted; NULL: no constraints
     const uint8_t* cn_class;
     const uint32_t* cn_bits;
+    // block fields (bisbm_fields.hip), generic kernel in Philox mode only: the field class byte of every node [n] and the table of
+    // f64 energies [class][ka + kb] -- a step that is evaluated adds (f[s] - f[r]) of the node's row to its dS; NULL: no fields
+    const uint8_t* fl_class;
+    const double* fl_field;
 };
 // Accepted fraction of the launch before from which a four-steps launch of 17..32 blocks takes the one-stage kernel
 // (SweepParams::one_stage).  Measured at 32 + 32 blocks (profiles/EXPERIMENTS.md, round 7): the one stage wins by 3.9 % where 0.72
@@ -454,6 +458,10 @@ struct HeatbathParams : WaveChainParams {
     // allowed blocks of its type, a node with one allowed block is held as a clamped node is; NULL: no constraints
     const uint8_t* cn_class;
     const uint32_t* cn_bits;
+    // block fields: the field class byte per node and the table (SweepParams::fl_field) -- the row entry of a target s != r gets
+    // (f[s] - f[r]) of the node's row added; NULL: no fields
+    const uint8_t* fl_class;
+    const double* fl_field;
 };
 
 constexpr uint32_t PHX_RESHUFFLE = 10;  // pair reshuffles: idx = (reshuffles_total << 32) | k, chain = the chain's global id
@@ -471,6 +479,9 @@ struct ReshuffleParams : WaveChainParams {
     // block constraints: a node whose class does not allow BOTH blocks of the pair is no member either; NULL: no constraints
     const uint8_t* cn_class;
     const uint32_t* cn_bits;
+    // block fields: a member's dS_o gets (f[o] - f[c]) of its row added before it enters the weights and the pass's sum; NULL: no fields
+    const uint8_t* fl_class;
+    const double* fl_field;
 };
 hipError_t launch_exp_probe(const double* x, size_t count, double* out, hipStream_t stream);
 

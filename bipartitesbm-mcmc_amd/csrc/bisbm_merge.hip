@@ -875,6 +875,8 @@ int bisbm_agg_merge(bisbm_handle h, int diff_a, int diff_b, int nm) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (h->constraints.n_classes)  // (a merge or split renumbers blocks: the table's columns would change their meaning)
         return fail(h, BISBM_ERR_STATE, "block constraints are set: a merge renumbers blocks, clear them first with bisbm_constraints_set(h, 0, NULL, NULL)");
+    if (h->fields.n_classes)  // (... and so would the field table's)
+        return fail(h, BISBM_ERR_STATE, "block fields are set: a merge renumbers blocks, clear them first with bisbm_fields_set(h, 0, NULL, NULL)");
     if (h->clamp.n_clamped)  // (a merge or split renumbers blocks: the labels a clamp holds would change their meaning)
         return fail(h, BISBM_ERR_STATE, "%llu node(s) are clamped: a merge renumbers blocks, clear the clamp first with bisbm_clamp_set(h, NULL)", (unsigned long long)h->clamp.n_clamped);
     if (h->devs.empty() && h->groups.empty()) return run_merges(h, 0, diff_a, diff_b, nm);
@@ -895,6 +897,8 @@ int bisbm_agg_merge_total(bisbm_handle h, int diff, int nm) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (h->constraints.n_classes)  // (a merge or split renumbers blocks: the table's columns would change their meaning)
         return fail(h, BISBM_ERR_STATE, "block constraints are set: a merge renumbers blocks, clear them first with bisbm_constraints_set(h, 0, NULL, NULL)");
+    if (h->fields.n_classes)  // (... and so would the field table's)
+        return fail(h, BISBM_ERR_STATE, "block fields are set: a merge renumbers blocks, clear them first with bisbm_fields_set(h, 0, NULL, NULL)");
     if (h->clamp.n_clamped)  // (a merge or split renumbers blocks: the labels a clamp holds would change their meaning)
         return fail(h, BISBM_ERR_STATE, "%llu node(s) are clamped: a merge renumbers blocks, clear the clamp first with bisbm_clamp_set(h, NULL)", (unsigned long long)h->clamp.n_clamped);
     if (!h->devs.empty()) {

@@ -270,6 +270,11 @@ int bisbm_population_resample(bisbm_handle h, double beta_from, double beta_to, 
     const uint32_t C = h->n_chains;
     std::vector<double> S(C);
     if (int rc = bisbm_entropy(h, S.data())) return rc;
+    if (h->fields.n_classes) {  // (block fields: the weights and the ln Z increment are those of E = S + Phi, the tilted target)
+        std::vector<double> phi(C);
+        if (int rc = bisbm_fields_energy(h, phi.data())) return rc;
+        for (uint32_t c = 0; c < C; ++c) S[c] = S[c] + phi[c];
+    }
     uint32_t U[4];
     philox_host(h->seed, h->first_chain_id, PHX_RESAMPLE, s.rounds, U);
     std::vector<uint32_t> parent(C);

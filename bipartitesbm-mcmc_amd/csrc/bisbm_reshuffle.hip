@@ -31,7 +31,9 @@ enum : uint32_t { RS_TRANSIT = 0, RS_FREE = 1, RS_FORCED = 2 };
 
 // CN: the launch has block constraints (p.cn_bits is not NULL).  Without them the instance holds no look-up and is the code a
 // handle ran before they existed.
-template <bool EL, bool CN>
+// FL: the launch has block fields (p.fl_field is not NULL): the one instance per EL that adds the field to a member's dS_o.  It is
+// compiled with CN and serves constraints beside the field by testing p.cn_bits at run time.
+template <bool EL, bool CN, bool FL = false>
 __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const uint32_t chain = blockIdx.x;
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
             const uint32_t i = i0 + lane;
             const uint32_t lab = i < n_cls ? (uint32_t)labels[v0 + i] : 0xffffffffu;
             bool is = (lab == rg || lab == sg) && !(p.clamp && p.clamp[v0 + i] != 0);
-            if (CN && is) {  // (block constraints: a member's class allows both blocks of the pair)
+            if (CN && (!FL || p.cn_bits) && is) {  // (block constraints: a member's class allows both blocks of the pair)
                 const uint32_t cls = p.cn_class[v0 + i];
                 is = cn_allows(p.cn_bits, cls, rg) && cn_allows(p.cn_bits, cls, sg);
             }
@@ -237,6 +239,10 @@ __global__ __launch_bounds__(kWave) void reshuffle_kernel(ReshuffleParams p) {
                         const double tail2 = (lg_ec1 - lg_ec0) + (lg_eo1 - lg_eo2);
                         const double tail3 = (readlane(lq, 0u) - readlane(lq, 1u)) + (readlane(lq, 2u) - readlane(lq, 3u));
                         dS_o = ((acc + tail1) + tail2) + tail3;
+                        if (FL) {  // (block fields: the move under E = S + Phi; v, c and o are wave-uniform)
+                            const double* f = p.fl_field + (size_t)p.fl_class[v] * (p.ka + p.kb);
+                            dS_o = dS_o + (f[o] - f[c]);
+                        }
                         // the two weights, Z = w_r + w_s, the choice and its factor
                         const double mn = dS_o < 0. ? dS_o : 0.;
                         const double x_c = beta * (0. - mn), x_o = beta * (dS_o - mn);
@@ -314,11 +320,14 @@ int bisbm::reshuffle_engine(bisbm_engine* h, uint64_t moves, uint32_t scans, dou
     p.record = st.d_record.get(), p.accepted = st.d_accepted.get();
     p.clamp = h->clamp.mask_or_null();
     p.cn_class = h->constraints.class_or_null(), p.cn_bits = h->constraints.bits_or_null();
+    p.fl_class = h->fields.class_or_null(), p.fl_field = h->fields.field_or_null();
     size_t lds;
     if (int rc = wave_chain_plan(h, 0, p, lds)) return rc;
     h->ent_prev_valid = false;  // (the block state moves)
     st.last.clear();
-    if (p.cn_bits)
+    if (p.fl_field)
+        HIPCHK(h, launch_wave_chain(reshuffle_kernel<true, true, true>, reshuffle_kernel<false, true, true>, p, lds, h->stream));
+    else if (p.cn_bits)
         HIPCHK(h, launch_wave_chain(reshuffle_kernel<true, true>, reshuffle_kernel<false, true>, p, lds, h->stream));
     else
         HIPCHK(h, launch_wave_chain(reshuffle_kernel<true, false>, reshuffle_kernel<false, false>, p, lds, h->stream));

@@ -22,6 +22,7 @@ struct ExchangeParams {
     uint32_t* rung;              // [chain] rung of the chain
     uint32_t* at;                // [ensemble][L] chain on every rung
     unsigned long long* stats;   // [2][L - 1] attempted, accepted
+    const double* phi;           // [chain] block fields: Phi of every chain, the swap test is on E = S + Phi; NULL: no fields
 };
 
 __device__ __forceinline__ double description_length(const ExchangeParams& p, uint32_t c) {
@@ -29,6 +30,12 @@ __device__ __forceinline__ double description_length(const ExchangeParams& p, ui
     s += p.part[c];
     for (int i = 1; i < 8; ++i) s += p.terms[i];
     return s;
+}
+
+// E of chain c: the description length, under block fields plus Phi (one add; without fields the description length's own bits)
+__device__ __forceinline__ double chain_energy(const ExchangeParams& p, uint32_t c) {
+    const double s = description_length(p, c);
+    return p.phi ? s + p.phi[c] : s;
 }
 
 // One lane per (ensemble, lower rung i of this round's parity).  The pairs of a round are disjoint, so every lane owns the
@@ -40,7 +47,7 @@ __global__ __launch_bounds__(256) void tempering_exchange_kernel(ExchangeParams 
     const uint32_t i = (uint32_t)(p.round & 1u) + 2u * (t % p.pairs);  // i + 1 < L by the choice of `pairs`
     uint32_t* at = p.at + (size_t)g * p.L;
     const uint32_t a = at[i], b = at[i + 1];
-    const double delta = (1.0 / (double)p.ladder[i] - 1.0 / (double)p.ladder[i + 1]) * (description_length(p, a) - description_length(p, b));
+    const double delta = (1.0 / (double)p.ladder[i] - 1.0 / (double)p.ladder[i + 1]) * (chain_energy(p, a) - chain_energy(p, b));
     const U4 U = phx_draw(p.seed, p.first_gid + g * p.L, PHX_EXCHANGE, p.round * p.L + i);
     const bool accept = delta >= 0. || u53(U.x, U.y) < exp(delta);
     atomicAdd(&p.stats[i], 1ull);
@@ -141,6 +148,10 @@ int exchange_round(bisbm_engine* e) {
     p.rung = t.d_rung.get();
     p.at = t.d_at.get();
     p.stats = t.d_stats.get();
+    if (e->fields.n_classes) {  // (block fields: the swap test is on E = S + Phi)
+        if (int rc = fields_energy_device(e)) return rc;
+        p.phi = e->fields.d_phi.get();
+    }
     const uint32_t lanes = p.n_ens * p.pairs;
     if (lanes) {
         hipLaunchKernelGGL(tempering_exchange_kernel, dim3((lanes + 255) / 256), dim3(256), 0, e->stream, p);

@@ -95,6 +95,27 @@ inline bool load_constraints(uint32_t& n_classes, std::vector<uint8_t>& class_of
     return true;
 }
 
+// The fields file of --fields (include/bisbm_io.h): one line per node with a prior, its id and block:weight pairs -> the field
+// class of every node (n bytes) and the table of n_classes x (ka + kb) energies (-ln weight) for set_fields().  On a failure
+// `error` names the file, and the token where one is at fault.
+inline bool load_fields(uint32_t& n_classes, std::vector<uint8_t>& class_of_node, std::vector<double>& field, const std::string& path, size_t n,
+                        size_t na, size_t ka, size_t kb, std::string& error) {
+    uint8_t* pc = nullptr;
+    double* pf = nullptr;
+    char msg[512];
+    const long classes = bisbm_io_read_fields(path.c_str(), n, na, (uint32_t)ka, (uint32_t)kb, &pc, &pf, msg, sizeof(msg));
+    if (classes < 0) {
+        error = msg;
+        return false;
+    }
+    n_classes = (uint32_t)classes;
+    class_of_node.assign(pc, pc + n);
+    field.assign(pf, pf + (size_t)classes * (ka + kb));
+    bisbm_io_free(pc);
+    bisbm_io_free(pf);
+    return true;
+}
+
 inline adj_list_t edge_to_adj(const edge_list_t& edge_list, size_t num_vertices = 0) {
     size_t n = num_vertices;
     for (auto const& e : edge_list) n = std::max(n, std::max(e.first, e.second) + 1);  // graph_utilities.cc:39-44
@@ -398,6 +419,30 @@ public:
         allowed.assign((size_t)n_classes * (ka + kb), 0);
         check(bisbm_constraints_get(h_, nullptr, class_of_node.data(), allowed.data()));
         return n_classes;
+    }
+    // block fields (include/bisbm.h): node v has the prior weight exp(-field[class_of_node[v] * (KA + KB) + s]) for block s of its
+    // type, through every sampler and in every chain: the target is exp(-beta (S + Phi))
+    void set_fields(uint32_t n_classes, const std::vector<uint8_t>& class_of_node, const std::vector<double>& field) {
+        if (class_of_node.size() != n_) throw std::runtime_error("set_fields: class_of_node has one byte per node");
+        check(bisbm_fields_set(h_, n_classes, class_of_node.data(), field.data()));
+    }
+    void clear_fields() { check(bisbm_fields_set(h_, 0, nullptr, nullptr)); }
+    uint32_t fields(std::vector<uint8_t>& class_of_node, std::vector<double>& field) {
+        uint32_t n_classes = 0;
+        check(bisbm_fields_get(h_, &n_classes, nullptr, nullptr));
+        uint32_t ka = 0, kb = 0;
+        check(bisbm_get_ka_kb(h_, &ka, &kb));
+        class_of_node.assign(n_, 0);
+        field.assign((size_t)n_classes * (ka + kb), 0.);
+        check(bisbm_fields_get(h_, nullptr, class_of_node.data(), field.data()));
+        return n_classes;
+    }
+    std::vector<double> field_energy() {  // Phi per chain
+        uint32_t chains = 0;
+        check(bisbm_get_sizes(h_, nullptr, nullptr, nullptr, &chains));
+        std::vector<double> out(chains);
+        check(bisbm_fields_energy(h_, out.data()));
+        return out;
     }
     // pair reshuffles (include/bisbm.h): `moves` moves per chain in which the nodes of two blocks of one type are divided afresh
     // and accepted or rejected as a whole (the accepted moves per chain); the record of every chain's last move.  The default

@@ -7,7 +7,7 @@
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
 // --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
 // --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace, --rung_moves, --population_moves,
-// --clamp, --constraints.
+// --clamp, --constraints, --fields.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -63,6 +63,7 @@ const option_spec kOptions[] = {
     {"trace", 0, 2},            {"block_summary", 0, 1},
     {"rung_moves", 0, 2},       {"population_moves", 0, 2},
     {"clamp", 0, 1},            {"constraints", 0, 1},
+    {"fields", 0, 1},
 };
 
 // a / b of two integers (b > 0) as the nearest double, ties to even: a quotient of 55 or 56 bits with the remainder folded
@@ -262,6 +263,13 @@ void print_help(const char* argv0) {
                  "                                        list, in every chain; the labels of --membership_path (required) must\n"
                  "                                        satisfy the lists.  Philox mode (--rng philox); not with --merge, --nature\n"
                  "                                        or a -z that differs from the block counts of the membership file.\n"
+                 "  --fields PATH                         PATH holds one line per node with a prior: the node id, then block:weight\n"
+                 "                                        pairs (global labels, blocks of its own type, weights above 0; an unlisted\n"
+                 "                                        block has weight 1).  Every sweep, reshuffle, exchange round and resampling\n"
+                 "                                        step of the run then targets the posterior times these weights, in every\n"
+                 "                                        chain: a preference, not a rule (--constraints forbids).  The blocks are\n"
+                 "                                        those of --membership_path (required).  Philox mode (--rng philox); not with\n"
+                 "                                        --merge, --nature or a -z that differs from the membership file's counts.\n"
                  "  --score_pairs IN OUT                  With --marginalize: IN holds one pair `u v` per line (u of type a, v of\n"
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
@@ -943,6 +951,16 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
     }
+    if (count("fields")) {
+        if (!count("membership_path")) {
+            std::cerr << "--fields names the blocks of a membership file: it needs --membership_path.\n";
+            return 1;
+        }
+        if (merge || nature) {
+            std::cerr << "--fields cannot be combined with " << (merge ? "--merge" : "--nature") << ": a merge renumbers the blocks that the file names.\n";
+            return 1;
+        }
+    }
     size_t seed;
     if (count("seed") == 0)
         seed = (size_t)std::chrono::high_resolution_clock::now().time_since_epoch().count();  // :236-239
@@ -1092,6 +1110,33 @@ int main(int argc, char const* argv[]) {
         std::clog << "constraints: " << (N - (size_t)std::count(cn_class.begin(), cn_class.end(), (uint8_t)0)) << " of " << N << " nodes listed, "
                   << cn_classes << " class(es)\n";
     }
+    // --fields: the field class of every node, in the engine's numbering, and the table of energies per class
+    uint32_t fl_classes = 0;
+    std::vector<uint8_t> fl_class;
+    std::vector<double> fl_field;
+    if (count("fields")) {
+        if (!prepared) {
+            std::cerr << "--fields names the blocks of --membership_path, which could not be read.\n";
+            return 1;
+        }
+        if (z.size() >= 2 && (z[0] != KA || z[1] != KB)) {
+            std::cerr << "--fields: -z " << z[0] << " " << z[1] << " differs from the " << KA << " + " << KB
+                      << " blocks of the membership file, and the merge or split that would follow renumbers blocks.\n";
+            return 1;
+        }
+        std::string why;
+        if (!load_fields(fl_classes, fl_class, fl_field, single("fields", ""), N, NA, KA, KB, why)) {
+            std::cerr << "[error] --fields: " << why << "\n";
+            return 1;
+        }
+        if (!new_id.empty()) {
+            std::vector<uint8_t> moved(fl_class.size());
+            for (size_t v = 0; v < fl_class.size(); ++v) moved[new_id[v]] = fl_class[v];
+            fl_class.swap(moved);
+        }
+        std::clog << "fields: " << (N - (size_t)std::count(fl_class.begin(), fl_class.end(), (uint8_t)0)) << " of " << N << " nodes listed, "
+                  << fl_classes << " class(es)\n";
+    }
 
     // K implied by the initial labels vs. requested (mcmc_main.cc:406-419)
     size_t ka = 0, kb = 0;
@@ -1139,6 +1184,10 @@ int main(int argc, char const* argv[]) {
         return 1;
     }
     opt.rng_mode = rng == "philox" ? BISBM_RNG_PHILOX : BISBM_RNG_MT19937_COMPAT;
+    if (count("fields") && opt.rng_mode != BISBM_RNG_PHILOX) {
+        std::cerr << "--fields runs in Philox mode only (mt19937-compat is the reference's verification path, and the reference has no fields): add --rng philox.\n";
+        return 1;
+    }
     if (count("constraints") && opt.rng_mode != BISBM_RNG_PHILOX) {
         std::cerr << "--constraints runs in Philox mode only (mt19937-compat is the reference's verification path, and the reference has no constraints): add --rng philox.\n";
         return 1;
@@ -1336,6 +1385,11 @@ int main(int argc, char const* argv[]) {
         return 0;
     }
     if (ka != KA || kb != KB) {  // the initial partition has other block counts than asked for (:419-450)
+        if (count("fields")) {
+            std::cerr << "--fields: the initial partition has " << ka << " + " << kb << " blocks, not " << KA << " + " << KB
+                      << ", and the merge or split that would follow renumbers blocks.\n";
+            return 1;
+        }
         if (count("constraints")) {
             std::cerr << "--constraints: the initial partition has " << ka << " + " << kb << " blocks, not " << KA << " + " << KB
                       << ", and the merge or split that would follow renumbers blocks.\n";
@@ -1386,6 +1440,7 @@ int main(int argc, char const* argv[]) {
             blockmodel_t blockmodel(memberships_init, types_init, KA + KB, KA, KB, epsilon, &adj_list, opt);
             if (!clamp_mask.empty()) blockmodel.clamp(clamp_mask);
             if (cn_classes) blockmodel.constrain(cn_classes, cn_class, cn_allowed);
+            if (fl_classes) blockmodel.set_fields(fl_classes, fl_class, fl_field);
             if (randomize)
                 blockmodel.shuffle_bisbm();
             else
@@ -1842,6 +1897,7 @@ int main(int argc, char const* argv[]) {
         blockmodel_t blockmodel(memberships_init, types_init, KA + KB, KA, KB, epsilon, &adj_list, opt);  // :453
         if (!clamp_mask.empty()) blockmodel.clamp(clamp_mask);
         if (cn_classes) blockmodel.constrain(cn_classes, cn_class, cn_allowed);
+        if (fl_classes) blockmodel.set_fields(fl_classes, fl_class, fl_field);
         if (randomize)
             blockmodel.shuffle_bisbm();
         else

@@ -19,7 +19,7 @@ import numpy as np
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
                 similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None, rung_moves=None, blocks=False,
-                clamp=None, constraints=None):
+                clamp=None, constraints=None, fields=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -89,11 +89,15 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     chain the block numbering is pinned, and the pooled histogram is a marginal over chains without `align`.
     `constraints`: (class_of_node, allowed) as model.constrain takes them (include/bisbm.h, "Block constraints"): set before the
     burn-in and left set, so every node stays inside the blocks its class allows through the whole run, whatever the sampler.
-    Classes that allow disjoint sets of blocks keep those sets apart in every chain."""
+    Classes that allow disjoint sets of blocks keep those sets apart in every chain.
+    `fields`: (class_of_node, field) as model.set_fields takes them (include/bisbm.h, "Block fields"): set before the burn-in and
+    left set, so every sampler of the run targets exp(-beta (S + Phi)); the marginals are those of the tilted posterior."""
     if clamp is not None:
         model.clamp(clamp)
     if constraints is not None:
         model.constrain(*constraints)
+    if fields is not None:
+        model.set_fields(*fields)
     if blocks and not align:
         raise ValueError("blocks=True needs align=True: the block sums are taken in the numbering of the aligned histogram")
     n = model.n
@@ -212,7 +216,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
 
 def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,
                       reassign=False, tempering=None, exchange_every=1, sampler="mh", trace=None, rung_moves=None, blocks=False, clamp=None,
-                      constraints=None):
+                      constraints=None, fields=None):
     """Mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): the chains are grouped into posterior modes and
     every mode gets an aligned histogram and a MAP of its own, in the numbering of its own reference.
     Exactly one of `threshold` and `mode_of_chain`: with `threshold` the grouping is model.partition_modes(threshold) taken
@@ -243,6 +247,7 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     not change, model.block_summary(g) gives mode g's block matrix, sizes and degrees with their spread afterwards.
     `clamp`: node ids or a mask, as in marginalize(): set before the burn-in and left set.
     `constraints`: (class_of_node, allowed), as in marginalize(): set before the burn-in and left set.
+    `fields`: (class_of_node, field), as in marginalize(): set before the burn-in and left set.
     Chains spread over ranks (`shard`, or model.shard, with world_size > 1) raise ValueError: pooling modes across ranks is
     not done here."""
     if (threshold is None) == (mode_of_chain is None):
@@ -261,6 +266,8 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         model.clamp(clamp)
     if constraints is not None:
         model.constrain(*constraints)
+    if fields is not None:
+        model.set_fields(*fields)
     advance = _advance(model, tempering, exchange_every, sampler, rung_moves=rung_moves)
     if burn_in_sweeps > 0:
         advance(burn_in_sweeps)

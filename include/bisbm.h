@@ -786,10 +786,60 @@ int bisbm_clamp_get(bisbm_handle h, uint8_t *mask_out /* n, may be NULL */, uint
  * first).
  * Out of scope: a table per chain, constraints in the production kernel (DESIGN.md section 26's follow-up serves both),
  * restricted rows in bisbm_conditionals_*, mt19937-compat arithmetic, wide handles, chains grouped by shape, merges or splits
- * under constraints, soft priors over blocks. */
+ * under constraints.  (Soft priors over blocks: "Block fields" below.) */
 int bisbm_constraints_set(bisbm_handle h, uint32_t n_classes, const uint8_t *class_of_node /* n */,
                           const uint8_t *allowed /* n_classes * (ka + kb) */);   /* 0 / NULL clears */
 int bisbm_constraints_get(bisbm_handle h, uint32_t *n_classes_out, uint8_t *class_of_node_out, uint8_t *allowed_out);
+
+/* Block fields (no reference counterpart; graph-tool's bfield): soft per-node priors over blocks.  Where constraints forbid, a
+ * field prefers: labels that are partly wrong, a taxonomy that is a tendency, node metadata, the children of a coarse fit a node
+ * should prefer but may leave.  One set per handle, shaped like the constraints and independent of them and of the clamp (all
+ * three may be set at once): a class byte per node, class_of_node[n] (its own vector, at most 256 classes), and a table
+ * field[n_classes][ka + kb] of f64 energies phi in nats; a row's entries for blocks of the other type are ignored.  With
+ * Phi(b) = sum_v phi[class(v)][b_v] and E = S + Phi every sampler targets exp(-beta E) instead of exp(-beta S): a node's prior
+ * weight for block s is exp(-phi_s), and beta tempers the field together with the description length.  Philox mode and byte
+ * labels only.
+ * set: validates before anything changes.  n_classes <= 256, every class id < n_classes and every entry finite, else
+ * BISBM_ERR_INVALID_ARG naming class and block (for +inf the message names bisbm_constraints_set, the way to forbid a block).  A
+ * refusal leaves the fields that were in place on every device.  n_classes = 0 or a NULL pointer clears, and a table whose
+ * entries are all +-0.0 IS "no fields" and is stored as a clear: the kernels are handed null pointers, MH sweeps run the
+ * production kernel again, every call is bit for bit that of a handle that never had fields, and get reports 0 classes.  Each
+ * device keeps the n class bytes and the table in global memory (at most 512 KiB of table).
+ * get: n_classes, the class bytes and the table as given (each pointer may be NULL; without fields 0 classes, all class bytes 0,
+ * field_out untouched).
+ * Wherever a sampler uses a node's dS(v: r -> s) it uses dE = dS + (f[s] - f[r]), f the row of v's class: the difference is
+ * formed first, then there is exactly one f64 add onto the dS the kernel already has.  No draw, no Philox index and no order of
+ * any sum changes.
+ *   1. MH SWEEPS: the add follows the evaluation of the step's dS, before the accept line, whose form stays.  A proposal of the
+ *      node's own block keeps 0, a target of the other type or barred by the constraints keeps its verdict.  Proposal and
+ *      Hastings factor are untouched: the step is the Metropolis-Hastings step for exp(-beta E) with the same q.  While fields
+ *      are set the sweeps run the generic kernel (README.md).
+ *   2. HEAT-BATH SWEEPS AND POLISHING: the row entry of target s != r is (((acc + tail1) + tail2) + tail3) + (f[s] - f[r]) and
+ *      stays 0 at r; minimum, weights, Z, C_s, the greedy rule and the constraints' restriction follow as they are.  Polishing
+ *      certifies a minimum of E over the open admissible moves.
+ *   3. PAIR RESHUFFLES: a member's dS_o gets the same add before it enters the scan's weights and the pass's sum, so Q, dS_fwd,
+ *      dS_rev, A and the record are those of the move under E; the record's layout does not change.
+ *   4. RUNNING SUM: while fields are set bisbm_get_cum_dS advances by the dE of what was accepted, so between two reads
+ *      delta cum = delta S + delta Phi.  Setting or clearing fields does not touch the sum.
+ *   5. REPLICA EXCHANGE: the swap test uses E_a - E_b, E = the description length + Phi (one add per chain).
+ *   6. POPULATION ANNEALING: the resampling weights and the ln Z increment use E per chain, S[c] + Phi[c] added on the host before
+ *      bisbm_population_offspring, which is unchanged: the reported evidence is that of the tilted target exp(-beta E).
+ *   7. bisbm_fields_energy: Phi of every chain, defined so that a host loop gives the same bits: the integer histogram
+ *      count[class][block] over the nodes, then Phi = the sum over (class ascending, block ascending) of (double) count * phi,
+ *      added sequentially from 0.0, zero counts skipped (a label is a block of its node's type, so only a node's own type's
+ *      range is ever counted).  Without fields every Phi is 0.0.  The exchange and the resampling use this same code.
+ * Unchanged: bisbm_entropy stays the description length, and every "lowest description length" choice with it (alignment
+ * reference, a mode's best chain); every analysis call; bisbm_conditionals_* keeps reporting the model's row (the heat-bath row
+ * is that row plus the field); the shuffle (an initialiser, not a sampler); bisbm_set_memberships.  Refused, with a message and
+ * nothing changed: BISBM_RNG_MT19937_COMPAT and two-byte labels BISBM_ERR_UNSUPPORTED; chains grouped by shape BISBM_ERR_STATE.
+ * While fields are set bisbm_agg_merge and bisbm_agg_merge_total are BISBM_ERR_STATE (bisbm_fields_set(h, 0, NULL, NULL) first).
+ * Out of scope: fields in the production kernel, a table per chain, more than 256 distinct rows, mt19937-compat arithmetic,
+ * wide handles, chains grouped by shape, merges or splits under fields, the field inside bisbm_conditionals_* and the fold-in
+ * posteriors, learning the field from metadata. */
+int bisbm_fields_set(bisbm_handle h, uint32_t n_classes, const uint8_t *class_of_node /* n */,
+                     const double *field /* n_classes * (ka + kb) */);   /* 0 / NULL clears */
+int bisbm_fields_get(bisbm_handle h, uint32_t *n_classes_out, uint8_t *class_of_node_out, double *field_out);
+int bisbm_fields_energy(bisbm_handle h, double *out /* n_chains */);
 
 /* Partition distances and posterior modes (no reference counterpart: the reference keeps one partition).  How many different
  * answers did the chains find, which chains agree, how much of the pool sits in each answer: the all-pairs comparison of the

@@ -43,6 +43,21 @@ long bisbm_io_read_clamp(const char *path, uint64_t n, uint8_t **mask, char *err
 long bisbm_io_read_constraints(const char *path, uint64_t n, uint64_t na, uint32_t ka, uint32_t kb, uint8_t **class_of_node,
                                uint8_t **allowed, char *err, size_t err_cap);
 
+/* The fields file of `mcmc --fields` (no reference counterpart; include/bisbm.h, "Block fields"): one line per node with a
+ * prior -- the node id, then block:weight pairs, the block a global label of the node's type, the weight a finite decimal or
+ * scientific number above 0; tokens separated by blanks or tabs.  The energy of a listed block is phi = -ln weight (the host
+ * libm's log), an unlisted block has weight 1, phi = 0.  Lines in any order; a node may be repeated with the same row (a
+ * repeat with another row is an error, not "the last line wins"); blank lines are skipped; an empty file gives nobody a field.
+ * The rows become classes: class 0 is the zero row and holds the unlisted nodes, every distinct row gets the next class, at most
+ * 255 of them.  *class_of_node gets n malloc'ed bytes and *field a malloc'ed table of classes x (ka + kb) doubles.  Returns the
+ * number of classes (>= 1), -1 when the file cannot be opened, -2 for a malformed line: a node id or block that is not a number
+ * of decimal digits alone, a node id >= n or a block >= ka + kb, a block of the other type, a block twice on a line, a token
+ * without ':', a weight that is not a number, is 0 (the message names --constraints), negative or not finite, a node without a
+ * pair, a node repeated with another row, a 256th distinct row; `err` (err_cap bytes, may be NULL) then holds a message that
+ * names the offending token, and both outputs are NULL. */
+long bisbm_io_read_fields(const char *path, uint64_t n, uint64_t na, uint32_t ka, uint32_t kb, uint8_t **class_of_node,
+                          double **field, char *err, size_t err_cap);
+
 /* edge_to_adj (graph_utilities.cc:36-49) as CSR: undirected, duplicates kept, each row in edge-file
  * order.  rowptr has n+1 entries, col has 2*n_edges.  Returns 0, or -1 when an id is >= n. */
 int bisbm_io_edges_to_csr(const uint64_t *a, const uint64_t *b, size_t n_edges, uint64_t n,
