@@ -17,7 +17,7 @@ SOURCES = ["bisbm_kernels.hip", "bisbm_sweep_fast.hip", "bisbm_handle.hip", "bis
            "bisbm_query_scores.hip", "bisbm_coassign.hip", "bisbm_foldin.hip", "bisbm_topk.hip", "bisbm_conditionals.hip", "bisbm_heatbath.hip", "bisbm_reshuffle.hip",
            "bisbm_mode_marginals.hip", "bisbm_trace.hip", "bisbm_block_sums.hip", "bisbm_clamp.hip", "bisbm_constraints.hip", "bisbm_fields.hip",
            "bisbm_tables.cpp", "bisbm_io.cpp"]
-HEADERS = ["bisbm_device.hpp", "bisbm_partition_device.hpp", "bisbm_kernels.hpp", "bisbm_stand_rule.hpp", "bisbm_pair_word.hpp", "bisbm_move_word.hpp", "bisbm_predict_skew.hpp", "bisbm_engine.hpp", "bisbm_pass_policy.hpp", "bisbm_wave_chain.hpp", "bisbm_cand_lanes.hpp", os.path.join("..", "host", "bisbm.hpp"),
+HEADERS = ["bisbm_device.hpp", "bisbm_partition_device.hpp", "bisbm_kernels.hpp", "bisbm_stand_rule.hpp", "bisbm_pair_word.hpp", "bisbm_move_word.hpp", "bisbm_held_word.hpp", "bisbm_predict_skew.hpp", "bisbm_engine.hpp", "bisbm_pass_policy.hpp", "bisbm_wave_chain.hpp", "bisbm_cand_lanes.hpp", os.path.join("..", "host", "bisbm.hpp"),
            os.path.join("..", "host", "mcmc_main.cpp"), os.path.join("..", "..", "include", "bisbm.h"),
            os.path.join("..", "..", "include", "bisbm_io.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-pthread",
@@ -94,12 +94,13 @@ def compile_library(out, extra=(), verbose=False, jobs=None):
     cc = hipcc()
     objdir = tempfile.mkdtemp(prefix="bisbm_obj_")
     try:
-        # the production kernel's 20 variants: four units of five kernels + the dispatch (BISBM_FAST_PART, bisbm_sweep_fast.hip);
-        # a build with in-kernel stamps or pass counts keeps them in one unit (its counters are one device symbol)
+        # the production kernel's variants: four units of six kernels (parts 0 .. 3), the dispatch (4) and four units of the two
+        # held kernels each (5 .. 8) (BISBM_FAST_PART, bisbm_sweep_fast.hip); a build with in-kernel stamps or pass counts keeps
+        # them in one unit (its counters are one device symbol)
         units = []
         for src in SOURCES:
             if src == "bisbm_sweep_fast.hip" and not any("BISBM_STAMPS" in f or "BISBM_PASS_COUNTS" in f for f in extra):
-                units += [(src, ["-DBISBM_FAST_PART=%d" % part], "%s.part%d.o" % (src, part)) for part in range(5)]
+                units += [(src, ["-DBISBM_FAST_PART=%d" % part], "%s.part%d.o" % (src, part)) for part in range(9)]
             else:
                 units.append((src, [], src + ".o"))
 

@@ -100,13 +100,20 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     // the production kernel covers Philox mode with both block counts <= 64; mt19937-compat mode and
     // wider partitions run the generic kernel (BISBM_FORCE_GENERIC=1 forces it, for A/B checks)
     const char* force = getenv("BISBM_FORCE_GENERIC");
-    // while a non-empty clamp is set the generic kernel runs too: it is the one that reads the mask (include/bisbm.h, "Clamped nodes")
-    // ... and while block constraints are set: it is the one that looks a proposal's target up ("Block constraints")
+    // A clamp (include/bisbm.h, "Clamped nodes") and block constraints ("Block constraints") run on the production kernel too: its
+    // held instances take the mask and the table as one allowed word per step (bisbm_held_word.hpp), two steps per pass at most.
+    // A handle that is mostly clamped is better off on the generic kernel, which skips a clamped step outright where the
+    // production kernel walks its row all the same: the share of clamped nodes against kHeldFastMaxClampShare decides
+    // (BISBM_HELD_FAST=1 / =0 pins the production / the generic kernel for held handles: tests, A/B runs).  Constraints without a
+    // clamp always take the production kernel.
     p.clamp = h->clamp.mask_or_null();
     p.cn_class = h->constraints.class_or_null(), p.cn_bits = h->constraints.bits_or_null();
-    // ... and while block fields are set: it is the one that adds the field to a step's dS ("Block fields")
+    // While block fields are set the generic kernel runs: it is the one that adds the field to a step's dS ("Block fields")
     p.fl_class = h->fields.class_or_null(), p.fl_field = h->fields.field_or_null();
-    const bool fast = h->rng_mode == BISBM_RNG_PHILOX && h->ka <= 64 && h->kb <= 64 && !h->wide && !(force && force[0] == '1') && !p.clamp && !p.cn_bits && !p.fl_field;
+    const bool held = p.clamp != nullptr || p.cn_bits != nullptr;
+    bool held_fast = (double)h->clamp.n_clamped <= kHeldFastMaxClampShare * (double)h->n;
+    if (const char* hf = getenv("BISBM_HELD_FAST")) held_fast = hf[0] == '1' ? true : hf[0] == '0' ? false : held_fast;
+    const bool fast = h->rng_mode == BISBM_RNG_PHILOX && h->ka <= 64 && h->kb <= 64 && !h->wide && !(force && force[0] == '1') && (!held || held_fast) && !p.fl_field;
     // Temperatures of the pow / log schedules are evaluated with the host libm (the reference's own values) into a table of
     // at most kTabCap steps.  The generic kernel evaluates pow / log itself beyond it; the production kernel holds no
     // pow / log at all: a longer call runs as several launches of whole sweeps, each with the slice of the table it covers
@@ -145,7 +152,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     p.vlist_in_lds = 0;
     p.eta_w = p.eta_lo_a = p.eta_lo_b = 0;
     if (fast) {
-        lds = sweep_fast_lds_bytes(h->ka, h->kb, h->maxdeg, false, 0);
+        lds = sweep_fast_lds_bytes(h->ka, h->kb, h->maxdeg, false, 0, held);
         p.eta_in_lds = (lds + eta_bytes <= 40 * 1024) ? 1 : 0;
         if (!p.eta_in_lds) {
             // eta does not fit beside the rest (many blocks and / or long rows): the kernel keeps a window of it in LDS -- the
@@ -168,7 +175,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
                 (type ? p.eta_lo_b : p.eta_lo_a) = best_lo;
             }
         }
-        lds = sweep_fast_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0, p.eta_w);
+        lds = sweep_fast_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0, p.eta_w, held);
     } else {
         // generic kernel: m quadrant (odd row stride), m_r, n_r, k_v histogram, staged rows; compat adds the
         // two mt19937 states and (small graphs) the visit list
@@ -211,7 +218,9 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     // every sixteenth launch tries a neighbouring depth again (a chain leaves its burn-in, a schedule cools down).  The chain
     // is the same chain whatever runs (same Philox counters, bit-equal results).
     // (depth 1 = two steps per pass, 2 = four -- in 16-lane rows, two blocks per lane above 16 blocks of a type --, 3 = eight)
+    // (a held launch: the two-steps pass at most -- the held kernels hold no deeper one)
     const uint32_t max_depth = (!fast || p.pair_steps < 2u || h->ka > 32 || h->kb > 32) ? 0u
+                               : held                                                   ? 1u
                                : std::min<uint32_t>(p.pair_steps, (h->ka <= 8 && h->kb <= 8) ? 3u : 2u);
     // Any schedule, any steps_await: what anneal() carries from sweep to sweep -- entropy_min_, the position of the last
     // minimum, the count of T < 1 steps, "this chain has returned" -- travels in the chain's scalars (SweepParams::resume, as for

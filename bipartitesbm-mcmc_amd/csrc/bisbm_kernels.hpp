@@ -112,10 +112,11 @@ struct SweepParams {
     // modulo n -- a WRONG predicted target, (prediction + 1) mod k_own, so that the passes that start from a predicted target
     // take their miss paths at a known rate (bisbm_predict_skew.hpp).  The chain is the same chain whatever the prediction says.
     uint32_t predict_skew;
-    // clamped nodes (bisbm_clamp.hip), generic kernel in Philox mode only: [n] a non-zero byte holds the node -- its step is not
-    // evaluated and counts as a step that was not accepted; NULL: no clamp
+    // clamped nodes (bisbm_clamp.hip), Philox mode only -- the generic kernel and the held instances of the production kernel:
+    // [n] a non-zero byte holds the node -- its step counts as a step that was not accepted; NULL: no clamp
     const uint8_t* clamp;
-    // block constraints (bisbm_constraints.hip), generic kernel in Philox mode only: the class byte of every node [n] and the bit
+    // block constraints (bisbm_constraints.hip), Philox mode only -- the generic kernel and the held instances of the production
+    // kernel: the class byte of every node [n] and the bit
     // table of eight 32-bit words per class (bit s of a class's row: block s allowed) -- a proposal of another block of the node's
     // type outside its class's row is not evaluated and counts as a step that was not accepted; NULL: no constraints
     const uint8_t* cn_class;
@@ -130,6 +131,15 @@ struct SweepParams {
 // to 0.82 of the steps are accepted (randomised start: two to three movers per pass) and loses 1.6 % at 0.65 (chains on the planted
 // partition: most accepted steps are r == s, a pass has one mover or none).  Between the two nothing is measured: the per-mover loop runs.
 constexpr double kOneStageAccepted = 0.7;
+// Share of clamped nodes up to which a clamped handle's MH sweeps take the production kernel (its held instances); above it the
+// generic kernel runs, which skips a clamped step outright where the production kernel walks the node's row all the same.
+// Measured on the bench graph at 0 / 5 / 10 / 50 / 90 / 97 / 99 % clamped (profiles/held_fast_bench.json): the
+// production kernel wins at every one of them, by 1.29 x still at 99 % -- two barred steps end their pass before anything is
+// evaluated, so its sweep gets cheaper with the share too -- and the two do not cross inside the measured range.  The constant
+// stays at section 26's estimate, which is also a measured share: up to it the production kernel is known to win (1.54 x at 97 %),
+// and a handle clamped beyond it runs the generic kernel, as every clamped handle did before -- slower than it could at 97 .. 99 %
+// (404 against 312 ms at 99 %), never slower than it was.  tests/test_gpu_held_fast.py pins a 98 % clamped handle to that side.
+constexpr double kHeldFastMaxClampShare = 0.97;
 constexpr uint32_t kSimdClaims = 1u << 14;  // index: XCC_ID[3:0] | HW_ID se, sh, cu [15:8] | simd [5:4]
 
 struct BuildParams {
@@ -560,7 +570,8 @@ hipError_t launch_sum_from_entropy(ChainScalars* scalars, const double* before, 
 
 hipError_t launch_sweep(const SweepParams& p, int rng_mode, size_t lds_bytes, hipStream_t stream);
 hipError_t launch_sweep_fast(const SweepParams& p, size_t lds_bytes, hipStream_t stream);
-size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds, uint32_t eta_window);
+// held: a launch with clamped nodes and / or block constraints (two more hand-off words per step: 1 KiB)
+size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds, uint32_t eta_window, bool held = false);
 hipError_t launch_state_build(const BuildParams& p, hipStream_t stream);
 // `labels` is the byte base of the label array; wide: two-byte labels (label_stride counts labels in both cases)
 hipError_t launch_labels_broadcast(const uint32_t* src, uint8_t* labels, bool wide, size_t label_stride, uint32_t n,

@@ -42,6 +42,7 @@
 // No generic pointers (flat loads wait on vmcnt AND lgkmcnt), no workgroup barriers on the step path.
 // Diagnostic hooks (BISBM_STAMPS, BISBM_ABLATE) are compiled out of the product build.
 #include "bisbm_kernels.hpp"
+#include "bisbm_held_word.hpp"
 #include "bisbm_move_word.hpp"
 #include "bisbm_pair_word.hpp"
 #include "bisbm_stand_rule.hpp"
@@ -169,7 +170,8 @@ __device__ unsigned long long g_pass_counts[kPassCounts];
 constexpr uint32_t kHistStride = 68;  // bytes per k_v row: 64 counters + pad (17 dwords: odd, conflict-free)
 // v, row begin, degree, own label, pivot label, proposal word, packed hot-step inputs, accept uniform (2), pair word (the one-stage
 // four-steps kernels: the step's clash tests against the three steps before it, bisbm_pair_word.hpp; unused elsewhere)
-constexpr uint32_t kHandWords = 10;
+// A held launch (clamped nodes, block constraints) adds the step's allowed word (bisbm_held_word.hpp), low and high half.
+constexpr uint32_t hand_words(bool held) { return held ? 12u : 10u; }
 constexpr uint32_t kRowCap = 255;     // longest row the feeder walks (a k_v counter is a byte); longer rows: per-step side path
 
 // a double constant held in a vector register pair for the whole kernel (64-bit literals are not encodable
@@ -203,6 +205,7 @@ struct PairSteps {
     uint32_t selfA, selfB, warmA, warmB;                          // r == s; T > 0 (pair_selfs)
     uint32_t prop, pack_v, deg, r_loc, t_loc;                     // per lane
     double u_acc;
+    uint32_t allow_lo, allow_hi;  // per lane, held launches only: the allowed word of the lane's own step (bisbm_held_word.hpp)
     // what the verdicts will be combined with, in one word (the scalar file is full): bit 0 step q can
     // move, bit 1 step q is an accepted r == s, bits 2, 3 the same for step q + 1, bit 4 the clash
     __device__ __forceinline__ uint32_t flags(uint32_t clash) const {
@@ -249,8 +252,12 @@ __device__ __forceinline__ void commit_four(At, uint32_t nst, Bits clash_bits, u
 // steps per pass in groups of eight lanes (step_oct).  Q32 (with K32, without K16): four steps per pass with up to 32 blocks
 // of a type, two blocks per lane (step_quad32) -- the kernel of a launch whose pass depth the host set to four.  OS (with Q32):
 // step_quad32 updates the register copies of m_r / n_r in one stage per pass, not one mover at a time (sweep_quad32_one_stage_kernel).
-template <bool EL, bool CT, bool K32, bool K16, bool K8, bool Q32, bool OS>
+// HD (without K16, Q32): a held launch -- p.clamp and / or p.cn_bits are set: the feeder hands every step its allowed word and the
+// stepping wave bars the targets it does not hold (sweep_fast_held_kernel; one and two steps per pass).
+template <bool EL, bool CT, bool K32, bool K16, bool K8, bool Q32, bool OS, bool HD = false>
 __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
+    static_assert(!HD || (!K16 && !K8 && !Q32 && !OS), "held launches run the passes of one and two steps");
+    constexpr uint32_t kHandWords = hand_words(HD);
     extern __shared__ __align__(16) uint32_t lds32[];
     const uint32_t chain = blockIdx.x;
     if (chain >= p.n_chains) return;
@@ -530,11 +537,20 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                 uint32_t* const hist8w = hist8_base + (c & 1u) * kWave * (kHistStride / 4);
                 uint32_t* const hand = hand_base + (c & 1u) * kHandWords * kWave;
                 uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0, which_l = 0;
+                [[maybe_unused]] uint64_t allow_l = ~0ull;
                 if (lane < cnt) {
                     v_l = node_base + order(vi0 + lane);
                     beg_l = p.rowptr[v_l];
                     deg_l = p.rowptr[v_l + 1] - beg_l;
                     r_l = labels[v_l];  // own label: stable until the node's own step
+                    if constexpr (HD) {
+                        // the allowed word of the lane's step (bisbm_held_word.hpp): the mask byte, the class byte and the class's
+                        // row of the bit table, beside the row extent and the own label.  Nothing else of the chunk's preparation
+                        // looks at it: a held node's row is walked and its target predicted like any other.
+                        const bool clamped = p.clamp != nullptr && p.clamp[v_l] != 0;
+                        const uint32_t* const row = p.cn_bits != nullptr ? p.cn_bits + (uint32_t)p.cn_class[v_l] * kHeldRowWords : nullptr;
+                        allow_l = held_word(clamped, row, own_base, k_own);
+                    }
                     const U4 A = phx_draw(p.seed, chain_gid, PHX_STEP_A, sweeps_total * (uint64_t)n + node_base + vi0 + lane);
                     which_l = (uint32_t)(u53(A.x, A.y) * (double)deg_l);  // pivot neighbour, blockmodel.cc:619
                     if (which_l >= deg_l) which_l = deg_l ? deg_l - 1 : 0;
@@ -594,6 +610,10 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                 hand[2 * kWave + lane] = deg_l;
                 hand[3 * kWave + lane] = r_l;
                 hand[4 * kWave + lane] = (uint32_t)piv_l;
+                if constexpr (HD) {
+                    hand[10 * kWave + lane] = (uint32_t)allow_l;
+                    hand[11 * kWave + lane] = (uint32_t)(allow_l >> 32);
+                }
                 // Per-lane inputs of the hot step.  Bit 31 of the proposal word sends the step down the general path: uniform
                 // random target, a single own block, empty or over-long rows, T == 0, a degree outside the eta window.
                 // (the other three uniforms of step vi0 + lane are drawn here, after the walk -- counter-based: the draw for the
@@ -772,8 +792,16 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     // ---- transition_ratio, metropolis_hasting.cc:103-192 (production arithmetic) ----
                     // r == s (always accepted at T > 0, :109-112) and cross-type targets (dS = +inf, :121-123):
                     // same straight-line code with s replaced by r, outcome overridden.
-                    const bool same = (r == s);
-                    const bool cross = !same && ((r < ka) != (s < ka));
+                    // HD: a target of the node's own type that its allowed word does not hold (bisbm_held_word.hpp) gets the verdict of
+                    // a target of the other type -- not evaluated, not accepted.  Under constraints the own block is always held,
+                    // so r == s stays what it is; under a clamp the word is 0 and r == s is barred like every other target.
+                    bool barred = false;
+                    if constexpr (HD) {
+                        const unsigned long long allow = ((unsigned long long)handed(11) << 32) | handed(10);
+                        barred = s - own_base < k_own && held_barred(allow, (s - own_base) & 63u) != 0u;
+                    }
+                    const bool same = (r == s) && !barred;
+                    const bool cross = !same && (((r < ka) != (s < ka)) || barred);
                     const uint32_t s_eff = (same || cross) ? r : s;
                     const uint32_t s_loc = s_eff - own_base;
                     const int ideg = (int)deg;
@@ -933,6 +961,11 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     const int32_t m_rt_raw = mq[a_rt];
                     const int w_piv = mq[mq_at(lane, t_loc)];
                     const int n_r_r = readlane(nr_own, r_loc);
+                    [[maybe_unused]] uint32_t allow_lo_v = 0u, allow_hi_v = 0u;  // HD: the step's allowed word, asked for with the early reads
+                    if constexpr (HD) {
+                        allow_lo_v = hand[10 * kWave + q];
+                        if (!K32) allow_hi_v = hand[11 * kWave + q];
+                    }
                     // the two lgamma gathers that only need row r go out now: their latency runs under the proposal
                     // Lanes with k == 0 (idle lanes included) contribute exact zeros to all three sums whatever m is, so
                     // they all read table entry 1: a gather costs per distinct address, not per lane
@@ -952,6 +985,15 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     __asm__("s_ff1_i32_b64 %0, %1" : "=s"(first_hit) : "s"(hit));
                     const uint32_t s_loc = min(first_hit, last_own);
                     FSTAMP_STEP(2);
+                    if constexpr (HD) {  // a barred target (r == s of a clamped node included): a step that was not accepted
+                        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)allow_lo_v);
+                        if constexpr (K32) {
+                            if (held_barred32(lo, s_loc) != 0u) return;
+                        } else {
+                            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)allow_hi_v);
+                            if (held_barred(((unsigned long long)hi << 32) | lo, s_loc) != 0u) return;
+                        }
+                    }
                     if (s_loc == r_loc) {  // r == s: dS = 0, accepted as is unless T == 0; nothing changes (:109-112, :49-50)
                         const bool ok = n_r_r != 1 && (CT || T != 0.);
                         if (ok && lane == 0) acc_l0 += 1;
@@ -1154,6 +1196,10 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     PairSteps P;
                     P.prop = prop_of(qs);
                     P.u_acc = u_acc_of(qs);
+                    if constexpr (HD) {  // (asked for here, with the pass's first reads: the verdict on the targets needs it behind the scan)
+                        P.allow_lo = hand[10 * kWave + qs];
+                        if (!K32) P.allow_hi = hand[11 * kWave + qs];
+                    }
                     const uint32_t packA = readlane(pack_l, q), packB = readlane(pack_l, qB);
                     P.r_locA = (packA >> 8) & 63u, P.r_locB = (packB >> 8) & 63u;
                     P.degA = packA & 255u, P.degB = packB & 255u, P.t_locB = (packB >> 16) & 63u;
@@ -1174,6 +1220,23 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     // T = 0 (the greedy tail of a cooling schedule): r == s is not accepted (dS = 0 is not < 0, :49-50)
                     P.warmA = CT ? 1u : ((uint32_t)(zeroT_mask >> q) & 1u) ^ 1u;
                     P.warmB = CT ? 1u : ((uint32_t)(zeroT_mask >> qB) & 1u) ^ 1u;
+                    // HD: a barred target (bisbm_held_word.hpp; lane 0 holds step q's word, lane 32 step q + 1's).  A barred step is
+                    // a step that does not move and is not accepted -- what the step of a node alone in its block is (liveA / liveB)
+                    // -- and, like an r == s, one whose evaluation nobody needs: with the partner's r == s or barred target the pass
+                    // is done (pair_both_self).  A first step that is barred does not move, so the second step's evaluation stands.
+                    if constexpr (HD) {
+                        const uint32_t loA = readlane(P.allow_lo, 0u), loB = readlane(P.allow_lo, 32u);
+                        uint32_t barA, barB;
+                        if constexpr (K32) {
+                            barA = held_barred32(loA, s_locA), barB = held_barred32(loB, s_locB);
+                        } else {
+                            const uint32_t hiA = readlane(P.allow_hi, 0u), hiB = readlane(P.allow_hi, 32u);
+                            barA = held_barred(((unsigned long long)hiA << 32) | loA, s_locA);
+                            barB = held_barred(((unsigned long long)hiB << 32) | loB, s_locB);
+                        }
+                        P.selfA |= barA, P.selfB |= barB;
+                        P.liveA &= barA ^ 1u, P.liveB &= barB ^ 1u;
+                    }
                 };
                 // both r == s: nothing changes (:109-112); the steps the pass is done with
                 auto pair_both_self = [&](auto tm, const PairSteps& P, uint32_t q, uint32_t qB, uint32_t pairable) -> uint32_t {
@@ -2095,6 +2158,12 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_quad32_one_stage_kernel(Sw
     sweep_fast_body<EL, CT, true, false, false, true, true>(p);
 }
 
+// ... and the passes of one and two steps a third time for held launches (HD: clamped nodes, block constraints)
+template <bool EL, bool CT, bool K32>
+__global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_held_kernel(SweepParams p) {
+    sweep_fast_body<EL, CT, K32, false, false, false, false, true>(p);
+}
+
 template <class Kernel>
 static hipError_t launch_fast_kernel(Kernel kernel, const SweepParams& p, size_t lds_bytes, hipStream_t stream) {
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
@@ -2121,9 +2190,18 @@ hipError_t launch_fast_variant(const SweepParams& p, size_t lds_bytes, hipStream
                                         : launch_fast_variant3<EL, CT, false, false, false>(p, lds_bytes, stream);
 }
 
-// The 20 + 4 kernels compile side by side: the build (build.py) compiles this file once per BISBM_FAST_PART = 0 .. 3 -- the six
-// kernels of one (EL, CT) each -- and once with BISBM_FAST_PART = 4 for the dispatch below; undefined: everything in one unit
-// (diagnostic builds with in-kernel stamps, whose counters are one device symbol).
+// A held launch: two steps per pass at most (the deeper passes rest on the stand rule and the pair words, whose held form does
+// not exist), so one kernel per K32.
+template <bool EL, bool CT>
+hipError_t launch_fast_held(const SweepParams& p, size_t lds_bytes, hipStream_t stream) {
+    return (p.ka <= 32u && p.kb <= 32u) ? launch_fast_kernel(sweep_fast_held_kernel<EL, CT, true>, p, lds_bytes, stream)
+                                        : launch_fast_kernel(sweep_fast_held_kernel<EL, CT, false>, p, lds_bytes, stream);
+}
+
+// The 20 + 4 + 8 kernels compile side by side: the build (build.py) compiles this file once per BISBM_FAST_PART = 0 .. 3 -- the six
+// kernels of one (EL, CT) each --, once per BISBM_FAST_PART = 5 .. 8 -- the two held kernels of one (EL, CT) each -- and once with
+// BISBM_FAST_PART = 4 for the dispatch below; undefined: everything in one unit (diagnostic builds with in-kernel stamps, whose
+// counters are one device symbol).
 #ifndef BISBM_FAST_PART
 #define BISBM_FAST_PART -1
 #endif
@@ -2141,18 +2219,35 @@ template hipError_t launch_fast_variant<true, false>(const SweepParams&, size_t,
 template hipError_t launch_fast_variant<true, true>(const SweepParams&, size_t, hipStream_t);
 #endif
 
+#if BISBM_FAST_HERE(5)
+template hipError_t launch_fast_held<false, false>(const SweepParams&, size_t, hipStream_t);
+#endif
+#if BISBM_FAST_HERE(6)
+template hipError_t launch_fast_held<false, true>(const SweepParams&, size_t, hipStream_t);
+#endif
+#if BISBM_FAST_HERE(7)
+template hipError_t launch_fast_held<true, false>(const SweepParams&, size_t, hipStream_t);
+#endif
+#if BISBM_FAST_HERE(8)
+template hipError_t launch_fast_held<true, true>(const SweepParams&, size_t, hipStream_t);
+#endif
+
 #if BISBM_FAST_HERE(4)
 #if BISBM_FAST_PART == 4
+extern template hipError_t launch_fast_held<false, false>(const SweepParams&, size_t, hipStream_t);
+extern template hipError_t launch_fast_held<false, true>(const SweepParams&, size_t, hipStream_t);
+extern template hipError_t launch_fast_held<true, false>(const SweepParams&, size_t, hipStream_t);
+extern template hipError_t launch_fast_held<true, true>(const SweepParams&, size_t, hipStream_t);
 extern template hipError_t launch_fast_variant<false, false>(const SweepParams&, size_t, hipStream_t);
 extern template hipError_t launch_fast_variant<false, true>(const SweepParams&, size_t, hipStream_t);
 extern template hipError_t launch_fast_variant<true, false>(const SweepParams&, size_t, hipStream_t);
 extern template hipError_t launch_fast_variant<true, true>(const SweepParams&, size_t, hipStream_t);
 #endif
 
-size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds, uint32_t eta_window) {
+size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds, uint32_t eta_window, bool held) {
     const uint32_t K = ka + kb, D = maxdeg + 1, S = kb | 1u;
     const size_t dwords = (size_t)ka * S + (eta_in_lds ? (size_t)K * D : (size_t)std::max(ka, kb) * eta_window) +
-                          2 * (size_t)kWave * (kHistStride / 4) + 2 * (size_t)kHandWords * kWave + kWave + 4 + 10 + 16 + 64 + 128;
+                          2 * (size_t)kWave * (kHistStride / 4) + 2 * (size_t)hand_words(held) * kWave + kWave + 4 + 10 + 16 + 64 + 128;
     // the step reads m[.][lane] for all 64 lanes whatever ka, kb are (idle lanes are masked after the read):
     // dword index <= 63 * S + 63 must be inside the allocation
     const size_t reach = 63 * (size_t)S + 64;
@@ -2161,9 +2256,14 @@ size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_
 
 hipError_t launch_sweep_fast(const SweepParams& p, size_t /*generic_lds_bytes*/, hipStream_t stream) {
     const bool ct = p.schedule == SCHED_CONSTANT;
-    const size_t lds_bytes = sweep_fast_lds_bytes(p.ka, p.kb, p.maxdeg, p.eta_in_lds != 0, p.eta_w);
+    const bool held = p.clamp != nullptr || p.cn_bits != nullptr;  // (the host sends a held launch here only where it means to, bisbm_anneal.hip)
+    const size_t lds_bytes = sweep_fast_lds_bytes(p.ka, p.kb, p.maxdeg, p.eta_in_lds != 0, p.eta_w, held);
     hipError_t e;
-    if (p.eta_in_lds)
+    if (held && p.eta_in_lds)
+        e = ct ? launch_fast_held<true, true>(p, lds_bytes, stream) : launch_fast_held<true, false>(p, lds_bytes, stream);
+    else if (held)
+        e = ct ? launch_fast_held<false, true>(p, lds_bytes, stream) : launch_fast_held<false, false>(p, lds_bytes, stream);
+    else if (p.eta_in_lds)
         e = ct ? launch_fast_variant<true, true>(p, lds_bytes, stream) : launch_fast_variant<true, false>(p, lds_bytes, stream);
     else
         e = ct ? launch_fast_variant<false, true>(p, lds_bytes, stream) : launch_fast_variant<false, false>(p, lds_bytes, stream);

@@ -701,8 +701,9 @@ int bisbm_reshuffle_get_total(bisbm_handle h, uint64_t *out /* n_chains */);
  *      of a step are keyed by its position in the sweep, so no other step's draws move: the clamped chain equals the unclamped
  *      chain up to the first step at which the unclamped chain moves a clamped node.  Skipping is legal because a sweep is a
  *      composition of single-node kernels each of which leaves exp(-beta S) invariant; leaving some out leaves a composition
- *      of kernels that keep the distribution restricted to the states that agree with the clamped labels.  While a non-empty
- *      clamp is set the sweeps run the generic kernel (a handle the production kernel would serve runs slower: README.md).
+ *      of kernels that keep the distribution restricted to the states that agree with the clamped labels.  A handle the
+ *      production kernel serves keeps it under a clamp (its held instances, two steps per pass at most), unless most of its
+ *      nodes are clamped: then the generic kernel, which skips a clamped step outright, is the faster one and runs (README.md).
  *   2. HEAT-BATH SWEEPS AND POLISHING (bisbm_heatbath_run): a clamped node is a node that is not free: it stays, no draw is
  *      used, and it is counted as such a node is.  The position in the sweep of every other node, and with it its draw, is
  *      unchanged.  With beta = +inf and stop_when_settled the end state is a local minimum over the moves of the OPEN nodes
@@ -757,8 +758,8 @@ int bisbm_clamp_get(bisbm_handle h, uint8_t *mask_out /* n, may be NULL */, uint
  *      in detailed balance with exp(-beta S) to that set, and a restriction of a reversible chain to a subset, with the refused
  *      mass put on staying, is reversible with respect to the restricted distribution.  The draws of a
  *      step are keyed by its position, so a refusal moves nobody else's draws: the constrained chain equals the unconstrained
- *      one up to the first step at which the unconstrained chain accepts a target outside A_v.  While constraints are set the
- *      sweeps run the generic kernel (README.md).
+ *      one up to the first step at which the unconstrained chain accepts a target outside A_v.  A handle the production kernel
+ *      serves keeps it under constraints (its held instances, two steps per pass at most: README.md).
  *   2. HEAT-BATH SWEEPS AND POLISHING: a node with |A_v| = 1 is held exactly as a clamped node is -- in the chunk header, no
  *      row read, no draw used.  Otherwise the row is restricted to A_v: mn = the minimum of dS_s over s in A_v (the 0 at r
  *      included), w_s = exp(-beta (dS_s - mn)) for s in A_v and exactly 0.0 for s outside; Z, P, C_s and the choice are as
