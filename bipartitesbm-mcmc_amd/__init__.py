@@ -51,6 +51,9 @@ FOLDIN_RECOMMEND, FOLDIN_SIMILAR = 1, 2
 FOLDIN_CAND_TILE, FOLDIN_TILE = 1024, 8
 # bisbm_conditionals_*: the bit of `what` that keeps the last sample's rows
 COND_KEEP_LAST = 1
+# bisbm_least_settled_topk: the statistic that is ranked (BISBM_SETTLED_BY_ENTROPY, BISBM_SETTLED_BY_STAY); the largest k is
+# QUERY_MAX_K, an entry past the queries QUERY_NONE
+SETTLED_BY_ENTROPY, SETTLED_BY_STAY = 0, 1
 # the Philox purpose of the heat-bath draw (csrc/bisbm_kernels.hpp: PHX_HEATBATH; DESIGN.md section 4 lists them all)
 PHILOX_PURPOSE_HEATBATH = 9
 # ... and of the pair reshuffles (PHX_RESHUFFLE), and the record type of a move without a pair (BISBM_RESHUFFLE_NONE)
@@ -160,6 +163,9 @@ ABI = {
     "bisbm_conditionals_get_stats": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p, _u64p, _u64p]),
     "bisbm_conditionals_get_marginals": (C.c_int, [C.c_void_p, _f64p, _u32p, _u64p]),
     "bisbm_conditionals_get_last": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p, _f64p]),
+    "bisbm_held_conditionals_set": (C.c_int, [C.c_void_p, C.c_int]),
+    "bisbm_held_conditionals_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "bisbm_least_settled_topk": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p, _f64p, _u64p]),
     "bisbm_heatbath_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_int, _u64p, _u64p]),
     "bisbm_reshuffle_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, _u64p]),
     "bisbm_reshuffle_get_last": (C.c_int, [C.c_void_p, C.POINTER(ReshuffleRecord)]),
@@ -172,6 +178,7 @@ ABI = {
     "bisbm_fields_get": (C.c_int, [C.c_void_p, _u32p, _u8p, _f64p]),
     "bisbm_fields_energy": (C.c_int, [C.c_void_p, _f64p]),
     "bisbm_debug_exp": (C.c_int, [C.c_void_p, _f64p, C.c_size_t, _f64p]),
+    "bisbm_debug_log": (C.c_int, [C.c_void_p, _f64p, C.c_size_t, _f64p]),
     "bisbm_partition_distances": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _f64p, _f64p]),
     "bisbm_partition_distances_to": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _f64p, _f64p]),
     "bisbm_partition_contingency": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
@@ -955,6 +962,13 @@ class BlockModel:
         self._check(self._L.bisbm_debug_exp(self._h, _p(x, _f64p), len(x), _p(out, _f64p)))
         return out
 
+    def debug_log(self, x):
+        """log(x) as the device evaluates it (the entropy term of numpy_held_conditional_row on the device's bits)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.zeros(len(x), dtype=np.float64)
+        self._check(self._L.bisbm_debug_log(self._h, _p(x, _f64p), len(x), _p(out, _f64p)))
+        return out
+
     # -- replica exchange (include/bisbm.h, "Replica exchange")
     def set_tempering(self, ladder):
         """Replica exchange over ensembles of L = len(ladder) consecutive chains (chain g L + i starts on rung i); ``None`` or
@@ -1495,6 +1509,36 @@ class BlockModel:
         self._check(self._L.bisbm_conditionals_get_last(self._h, i, stride, _p(dS, _f64p), _p(P, _f64p)))
         return dS, P
 
+    # -- held conditionals and the least settled queries (include/bisbm.h, "Held conditionals", "Least settled")
+    def conditionals_held(self, on=True):
+        """Switch what conditionals_accumulate evaluates: the held row -- the heat-bath kernel's row under the handle's clamp,
+        block constraints and block fields as they are at each sample -- or (on=False) the model's unrestricted row.  A call that
+        changes the switch zeroes the sums and the soft marginals and forgets the last rows; conditionals_set turns it off."""
+        self._check(self._L.bisbm_held_conditionals_set(self._h, 1 if on else 0))
+
+    def conditionals_is_held(self):
+        on = C.c_int()
+        self._check(self._L.bisbm_held_conditionals_get(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def least_settled(self, k, by="entropy"):
+        """(query indices uint32 [k], nodes int64 [k], values float64 [k], terms): the k queries with the largest entropy sum
+        (by="entropy") or the smallest stay sum (by="stay") of conditionals_stats, selected on the device; ties in ascending query
+        index.  Past the queries an index is QUERY_NONE, its node -1 and its value 0.0."""
+        if by not in ("entropy", "stay"):
+            raise ValueError("by = %r: \"entropy\" or \"stay\"" % (by,))
+        k = int(k)
+        idx = np.zeros(max(k, 0), dtype=np.uint32)
+        val = np.zeros(max(k, 0), dtype=np.float64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_least_settled_topk(self._h, SETTLED_BY_STAY if by == "stay" else SETTLED_BY_ENTROPY, k if k >= 0 else 0, _p(idx, _u32p),
+                                                      _p(val, _f64p), C.byref(terms)))
+        q = np.asarray(getattr(self, "conditional_queries", np.zeros(0, dtype=np.uint32)), dtype=np.int64)
+        some = idx != QUERY_NONE
+        nodes = np.full(len(idx), -1, dtype=np.int64)
+        nodes[some] = q[idx[some]]
+        return idx, nodes, val, terms.value
+
     # -- partition distances and posterior modes (include/bisbm.h, "Partition distances and posterior modes")
     def partition_distances(self, chains=None):
         """(vi float64 [m, m], H float64 [m]): the variation of information (nats) between every two of the selected chains'
@@ -1931,6 +1975,6 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice, numpy_reshuffle_accept, numpy_reshuffle_launch, numpy_reshuffle_pair, numpy_reshuffle_q, numpy_reshuffle_step,  # noqa: E402,F401
+from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_held_conditional_row, numpy_least_settled, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice, numpy_reshuffle_accept, numpy_reshuffle_launch, numpy_reshuffle_pair, numpy_reshuffle_q, numpy_reshuffle_step,  # noqa: E402,F401
                           numpy_pair_scores, numpy_query_topk, shard_chains)
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

@@ -36,7 +36,10 @@ __device__ __forceinline__ double logq_of(const Tables& tab, int n, int k) {
 
 // kLanes: 64 where neither type has more than 64 blocks (one wave: four times as many workgroups fit a CU, and the barriers cost
 // nothing), else 256
-template <uint32_t kLanes>
+// HELD: the launch has a clamp, block constraints or block fields and bisbm_held_conditionals_set is on (include/bisbm.h, "Held
+// conditionals"): the row is the heat-bath kernel's -- the field added in the target's lane, the minimum, the margin and the weights
+// restricted to A_v, a clamped node or one with a single allowed block a point mass.  The instances without it hold none of its code.
+template <uint32_t kLanes, bool HELD>
 __global__ __launch_bounds__(kLanes) void cond_rows_kernel(CondRowsParams p) {
     __shared__ int s_k[kLanes];          // k_v histogram over the blocks of the other type
     __shared__ uint32_t s_t[kLanes];     // the non-zero t, ascending
@@ -68,6 +71,22 @@ __global__ __launch_bounds__(kLanes) void cond_rows_kernel(CondRowsParams p) {
     const uint32_t* eta_g = p.eta + (size_t)c * K * D;
     const uint32_t beg = p.rowptr[v], deg = p.rowptr[v + 1] - beg;
     const uint32_t r_loc = min((uint32_t)lab[v] - own0, k_own - 1u), r = own0 + r_loc;  // (a valid label: the min never binds)
+    // held rows: the node's mask byte, class and field row (v is the workgroup's: one read each), and its own entry of A_v
+    bool held_shut = false, ok = true;  // clamped or |A_v| = 1; block tid is in A_v (the node's own block always is)
+    const double* f_row = nullptr;
+    uint8_t* s_ok = nullptr;
+    if constexpr (HELD) {
+        __shared__ uint8_t s_ok_[kLanes];
+        s_ok = s_ok_;
+        held_shut = p.clamp && p.clamp[v] != 0;
+        if (p.cn_bits) {
+            const uint32_t cls = p.cn_class[v];
+            held_shut = held_shut || cn_count(p.cn_bits, cls, own0, k_own) <= 1u;
+            ok = tid == r_loc || (tid < k_own && cn_allows(p.cn_bits, cls, own0 + tid));
+        }
+        s_ok[tid] = ok ? 1 : 0;  // (read behind the barriers below)
+        if (p.fl_field) f_row = p.fl_field + (size_t)p.fl_class[v] * K;
+    }
 
     // 1. k_v: the histogram of the neighbours' labels
     s_k[tid] = 0;
@@ -133,18 +152,22 @@ __global__ __launch_bounds__(kLanes) void cond_rows_kernel(CondRowsParams p) {
         const double tail2 = (lgamma_fast(tab, eta_r + 1) - lgamma_fast(tab, eta_r)) + (lgamma_fast(tab, eta_s + 1) - lgamma_fast(tab, eta_s + 2));
         const double tail3 = (logq_of(tab, m0r - ideg, n0r - 1) - logq_of(tab, m0r, n0r)) + (logq_of(tab, m0s + ideg, n0s + 1) - logq_of(tab, m0s, n0s));
         dS = ((acc + tail1) + tail2) + tail3;
+        if constexpr (HELD)
+            if (f_row) dS = dS + (f_row[s] - f_row[r]);  // (the difference first, then one add: "Block fields" 2.)
     }
     if (tid < k_own) dS_row[tid] = dS;
     s_x[tid] = dS;
     __syncthreads();
     // 4. the conditional: min, weights, Z in ascending s, P; then the chain's label-free terms
-    const bool free_node = k_own > 1u && n0r > 1;
+    const bool free_node = k_own > 1u && n0r > 1 && !(HELD && held_shut);
     if (tid == 0) {
         double mn = 0., mg = 0.;  // (the 0 at r)
         bool first = true;
 #pragma unroll 8
         for (uint32_t s = 0; s < k_own; ++s) {
             if (s == r_loc) continue;
+            if constexpr (HELD)
+                if (!s_ok[s]) continue;  // (the minimum and the margin are over A_v)
             const double x = s_x[s];
             mn = x < mn ? x : mn;
             mg = (first || x < mg) ? x : mg;
@@ -156,7 +179,7 @@ __global__ __launch_bounds__(kLanes) void cond_rows_kernel(CondRowsParams p) {
     double w = tid == r_loc ? 1. : 0.;
     if (free_node && tid < k_own) {
         const double x = p.beta * (dS - s_min);
-        w = x > 700. ? 0. : exp(-x);
+        w = x > 700. || (HELD && !ok) ? 0. : exp(-x);  // (exactly 0.0 outside A_v)
     }
     __syncthreads();
     s_x[tid] = w;
@@ -222,16 +245,30 @@ __global__ __launch_bounds__(256) void cond_soft_kernel(CondSoftParams p) {
     }
 }
 
+// the device's logarithm for a host that restates the entropy term (bisbm_debug_log)
+__global__ void log_probe_kernel(const double* x, size_t count, double* out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = log(x[i]);
+}
+
 }  // namespace
 
 namespace bisbm {
 
 hipError_t launch_cond_rows(const CondRowsParams& p, hipStream_t stream) {
     if (p.n_q == 0 || p.n_chains == 0) return hipSuccess;
-    if (std::max(p.ka, p.kb) <= 64u)
-        hipLaunchKernelGGL(cond_rows_kernel<64>, dim3(p.n_q, p.n_chains), dim3(64), 0, stream, p);
-    else
-        hipLaunchKernelGGL(cond_rows_kernel<256>, dim3(p.n_q, p.n_chains), dim3(256), 0, stream, p);
+    const bool held = p.clamp || p.cn_bits || p.fl_field;  // (the switch on with nothing held: the plain instances)
+    if (std::max(p.ka, p.kb) <= 64u) {
+        if (held)
+            hipLaunchKernelGGL((cond_rows_kernel<64, true>), dim3(p.n_q, p.n_chains), dim3(64), 0, stream, p);
+        else
+            hipLaunchKernelGGL((cond_rows_kernel<64, false>), dim3(p.n_q, p.n_chains), dim3(64), 0, stream, p);
+    } else {
+        if (held)
+            hipLaunchKernelGGL((cond_rows_kernel<256, true>), dim3(p.n_q, p.n_chains), dim3(256), 0, stream, p);
+        else
+            hipLaunchKernelGGL((cond_rows_kernel<256, false>), dim3(p.n_q, p.n_chains), dim3(256), 0, stream, p);
+    }
     return hipGetLastError();
 }
 
@@ -318,6 +355,11 @@ int add_sample(bisbm_engine* h, bisbm_engine* e, const ConditionalState::Segment
     p.lgamma_tab = e->d_lgamma, p.lgamma_size = e->tab->lg.size(), p.q_tab = e->d_q, p.q_stride = e->q_stride, p.log_tab = e->d_logtab;
     p.dS = s.d_dS.get() + (keep ? seg.base : 0), p.P = s.d_P.get() + (keep ? seg.base : 0);
     p.terms = s.d_terms.get();
+    if (s.held) {  // (the pointers the heat-bath launch takes; holds are refused on grouped handles, so `e` is the handle itself)
+        p.clamp = e->clamp.mask_or_null();
+        p.cn_class = e->constraints.class_or_null(), p.cn_bits = e->constraints.bits_or_null();
+        p.fl_class = e->fields.class_or_null(), p.fl_field = e->fields.field_or_null();
+    }
     CondSoftParams sp{};
     sp.na = p.na, sp.ka = e->ka, sp.kb = e->kb, sp.kmax = std::max(e->ka, e->kb), sp.n_q = s.n, sp.row_total = rt;
     sp.q = p.q, sp.nbb = p.nbb, sp.P = p.P, sp.perm = s.scratch.d_perm.get(), sp.prob = s.d_prob.get();
@@ -595,6 +637,79 @@ int bisbm_conditionals_get_last(bisbm_handle h, uint32_t query_index, uint32_t s
         }
     }
     return BISBM_OK;
+}
+
+int bisbm_debug_log(bisbm_handle h, const double* x, size_t count, double* out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->devs.empty()) {
+        const int rc = bisbm_debug_log(h->devs[0], x, count, out);
+        if (rc) h->err = h->devs[0]->err;
+        return rc;
+    }
+    if (!x || !out) return fail(h, BISBM_ERR_INVALID_ARG, "NULL argument");
+    if (count == 0) return BISBM_OK;
+    DeviceGuard keep;
+    HIPCHK(h, hipSetDevice(h->device));
+    DeviceBuf<double> dx, dout;
+    RESERVE(h, dx, count);
+    RESERVE(h, dout, count);
+    HIPCHK(h, hipMemcpy(dx.get(), x, sizeof(double) * count, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(log_probe_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, (const double*)dx.get(), count, dout.get());
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(out, dout.get(), sizeof(double) * count, hipMemcpyDeviceToHost));
+    return BISBM_OK;
+}
+
+int bisbm_held_conditionals_set(bisbm_handle h, int on) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->cond.n) return fail(h, BISBM_ERR_STATE, "%s", kNoQueries);
+    const bool held = on != 0;
+    if (!h->devs.empty())
+        if (int rc = on_devices(h, [&](bisbm_engine* d, size_t) { return bisbm_held_conditionals_set(d, on); })) return rc;
+    if (h->cond.held == held) return BISBM_OK;  // (not a switch: the sums stay)
+    h->cond.held = held;
+    if (!h->devs.empty()) return BISBM_OK;
+    return bisbm_conditionals_reset(h);  // a sum over two definitions means nothing: the sums, prob and the last rows go
+}
+
+int bisbm_held_conditionals_get(bisbm_handle h, int* on_out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (!h->cond.n) return fail(h, BISBM_ERR_STATE, "%s", kNoQueries);
+    if (!on_out) return fail(h, BISBM_ERR_INVALID_ARG, "on_out is NULL");
+    *on_out = h->cond.held ? 1 : 0;
+    return BISBM_OK;
+}
+
+int bisbm_least_settled_topk(bisbm_handle h, uint32_t by, uint32_t k, uint32_t* query_out, double* value_out, uint64_t* terms_out) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    const ConditionalState& s = h->cond;
+    if (!s.n) return fail(h, BISBM_ERR_STATE, "%s", kNoQueries);
+    if (by != BISBM_SETTLED_BY_ENTROPY && by != BISBM_SETTLED_BY_STAY)
+        return fail(h, BISBM_ERR_INVALID_ARG, "by = %u: BISBM_SETTLED_BY_ENTROPY (0) or BISBM_SETTLED_BY_STAY (1)", by);
+    if (k == 0) return fail(h, BISBM_ERR_INVALID_ARG, "k is 0");
+    if (k > kQueryMaxK) return fail(h, BISBM_ERR_UNSUPPORTED, "k = %u: bisbm_least_settled_topk selects at most %u queries", k, kQueryMaxK);
+    if (!query_out) return fail(h, BISBM_ERR_INVALID_ARG, "query_out is NULL");
+    const uint64_t terms = total_terms(h, &bisbm_engine::cond);
+    if (!terms) return fail(h, BISBM_ERR_STATE, "no sample yet: call bisbm_conditionals_accumulate before bisbm_least_settled_topk");
+    if (terms_out) *terms_out = terms;
+    // one row: the n entries of the statistic (d_stat holds stay, entropy, margin, n each), the candidates the query indices
+    bisbm_engine* e = device_entries(h)[0];  // the device that selects
+    ConditionalState& w = e->cond;
+    const std::vector<uint64_t> off{0, s.n};
+    {  // (24 bytes, written at every call)
+        const TopkCand cand{0u, 0xffffffffu};
+        DeviceGuard keep;
+        HIPCHK(h, hipSetDevice(e->device));
+        RESERVE(h, w.d_sel_off, 2);
+        RESERVE(h, w.d_sel_cand, 1);
+        HIPCHK(h, hipMemcpy(w.d_sel_off.get(), off.data(), sizeof(uint64_t) * 2, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(w.d_sel_cand.get(), &cand, sizeof(cand), hipMemcpyHostToDevice));
+    }
+    const size_t at = by == BISBM_SETTLED_BY_STAY ? 0 : (size_t)s.n;
+    const auto stat_of = [at](bisbm_engine* d) { return (const double*)d->cond.d_stat.get() + at; };
+    return topk_select(h, __func__, per_device(h, stat_of), off, w.topk, w.d_sel_off.get(), w.d_sel_cand.get(), nullptr, k, query_out, value_out,
+                       by == BISBM_SETTLED_BY_STAY);
 }
 
 }  // extern "C"

@@ -300,6 +300,7 @@ struct ConditionalState {
     uint32_t n_b = 0;             // ... of type b
     uint32_t what = 0;            // BISBM_COND_KEEP_LAST
     double beta = 0;
+    bool held = false;            // bisbm_held_conditionals_set: the rows are the held ones (on every engine of the handle)
     uint64_t terms = 0;           // chain terms added to the label-free sums since the last set / reset
     uint64_t prob_terms = 0;      // ... to the soft marginals (they start afresh whenever the reference is set)
     std::vector<uint32_t> q;      // [n] node of every query, caller's order
@@ -322,6 +323,10 @@ struct ConditionalState {
     };
     std::vector<Segment> segments;
     AlignScratch scratch;         // (its own: the permutations of a conditional sample are not the marginal histogram's)
+    // bisbm_least_settled_topk, on the device that selects: one row of n cells -- its bounds {0, n}, its TopkCand {0, none}
+    DeviceBuf<uint64_t> d_sel_off;
+    DeviceBuf<TopkCand> d_sel_cand;
+    TopkScratch<double> topk;
 };
 
 // Pair reshuffles (bisbm_reshuffle.hip).  Everything belongs to the engine that runs the kernel (a plain handle, a group, a
@@ -752,10 +757,11 @@ int read_row(bisbm_engine* h, const std::vector<const T*>& cells, uint64_t at, s
 // node_out / val_out ([queries][k]; val_out may be NULL).  off: the host's first cell of every query's row; w, d_off, d_cand:
 // the scratch and the tables of the first device entry, which selects; lists: what to mask, NULL: nothing.  Walks the queries in
 // chunks of at most kTopkChunkCells cells (BISBM_TOPK_CHUNK_CELLS=<n> in the environment, read at every call: n instead, for the
-// tests), never less than one query.
+// tests), never less than one query.  ascending: the smallest cells first (f64 rows without a mask only).
 template <class T>
 int topk_select(bisbm_engine* h, const char* fn, const std::vector<const T*>& cells, const std::vector<uint64_t>& off, TopkScratch<T>& w,
-                const uint64_t* d_off, const TopkCand* d_cand, const TopkMaskLists* lists, uint32_t k, uint32_t* node_out, T* val_out);
+                const uint64_t* d_off, const TopkCand* d_cand, const TopkMaskLists* lists, uint32_t k, uint32_t* node_out, T* val_out,
+                bool ascending = false);
 
 bool any_grouped(bisbm_engine* h);  // does the handle, or one of its device entries, keep its chains grouped by shape?
 bool any_wide(bisbm_engine* h);     // does some leaf hold two-byte labels?

@@ -372,6 +372,12 @@ struct CondRowsParams {
     double* dS;                 // [chain - buf_chain0][row_total]
     double* P;
     double* terms;              // [chain - chain0][n_q][4]
+    // held rows (bisbm_held_conditionals_set; all NULL: the model's row): the heat-bath launch's pointers (HeatbathParams)
+    const uint8_t* clamp;       // [n] mask bytes
+    const uint8_t* cn_class;    // [n] class of every node
+    const uint32_t* cn_bits;    // [classes][8]
+    const uint8_t* fl_class;    // [n] field class of every node
+    const double* fl_field;     // [classes][ka + kb]
 };
 // prob[query][perm[chain][block] - type base] += P[chain][query][block], chains in ascending order
 struct CondSoftParams {
@@ -609,7 +615,7 @@ hipError_t launch_foldin_rows(const FoldinRowsParams& p, bool recommend, hipStre
 hipError_t launch_topk_mask(const TopkMaskLists& lists, uint32_t q0, uint32_t n_q, const uint64_t* off, const TopkCand* cand, uint8_t* mask,
                             hipStream_t stream);
 template <class Key>
-hipError_t launch_topk_select(const TopkSelectParams<Key>& p, hipStream_t stream);
+hipError_t launch_topk_select(const TopkSelectParams<Key>& p, hipStream_t stream, bool ascending = false);
 template <class T>
 hipError_t launch_rows_add(T* a, const T* b, uint64_t count, hipStream_t stream);
 hipError_t launch_cond_rows(const CondRowsParams& p, hipStream_t stream);

@@ -36,7 +36,9 @@ __global__ __launch_bounds__(256) void topk_mask_kernel(const P* ptr, const uint
 }
 
 // MASKED: p.mask is given (a kernel of its own: the loops over a row without a mask test nothing per cell but `self`)
-template <class Key, bool MASKED>
+// ASC: the smallest cells first -- every key is read complemented, which turns the order of the unsigned keys round and leaves the
+// id order of the ties; val_out gets the cells themselves (bisbm_least_settled_topk by stay; the other instances hold none of it)
+template <class Key, bool MASKED, bool ASC = false>
 __global__ __launch_bounds__(256) void topk_select_kernel(TopkSelectParams<Key> p) {
     constexpr int kTop = (int)sizeof(Key) - 1;  // the highest byte of a key
     __shared__ uint32_t hist[256];
@@ -48,7 +50,8 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkSelectParams<Key> 
     const uint32_t qi = p.q0 + blockIdx.x;
     const uint32_t first = p.cand[qi].first, self = p.cand[qi].self, n_cand = (uint32_t)(p.off[qi + 1] - p.off[qi]);
     const uint64_t cell0 = p.off[qi] - p.off[p.q0];
-    const Key* key = p.rows + cell0;
+    const Key* cells = p.rows + cell0;
+    const auto key = [&](uint32_t i) -> Key { return ASC ? (Key)~cells[i] : cells[i]; };
     const uint8_t* mask = MASKED ? p.mask + cell0 : nullptr;
     const auto eligible = [&](uint32_t i) { return !(MASKED && mask[i]) && i != self; };
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkSelectParams<Key> 
         const Key prefix = s_prefix;
         for (uint32_t i = tid; i < n_cand; i += kLanes) {
             if (!eligible(i)) continue;
-            const Key x = key[i];
+            const Key x = key(i);
             if (b == kTop || (x >> (8 * (b + 1))) == (prefix >> (8 * (b + 1)))) atomicAdd(&hist[(x >> (8 * b)) & 255u], 1u);
         }
         __syncthreads();
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkSelectParams<Key> 
     for (uint32_t s = 0; s < n_cand && (g_base < n_greater || t_base < n_ties); s += kLanes, it ^= 1u) {
         const uint32_t i = s + tid;
         const bool in = i < n_cand && eligible(i);
-        const Key x = in ? key[i] : 0;
+        const Key x = in ? key(i) : 0;
         const bool isg = in && x > kth, ist = in && x == kth;
         const unsigned long long bg = __ballot(isg), bt = __ballot(ist), below = (1ull << lane) - 1ull;
         if (lane == 0) wsum[it][0][wave] = (uint32_t)__popcll(bg), wsum[it][1][wave] = (uint32_t)__popcll(bt);
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkSelectParams<Key> 
         uint32_t rank = 0;
         for (uint32_t j = 0; j < kk; ++j) rank += (s_key[j] > x) || (s_key[j] == x && s_id[j] < id);
         node_out[rank] = first + id;
-        val_out[rank] = x;
+        val_out[rank] = ASC ? (Key)~x : x;
     }
 }
 
@@ -165,16 +168,22 @@ hipError_t launch_topk_mask(const TopkMaskLists& l, uint32_t q0, uint32_t n_q, c
 }
 
 template <class Key>
-hipError_t launch_topk_select(const TopkSelectParams<Key>& p, hipStream_t stream) {
+hipError_t launch_topk_select(const TopkSelectParams<Key>& p, hipStream_t stream, bool ascending) {
     if (p.n_q == 0) return hipSuccess;
-    if (p.mask)
+    if (ascending) {  // (the f64 sums without a mask: the one caller)
+        if constexpr (sizeof(Key) == 8) {
+            if (p.mask) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((topk_select_kernel<Key, false, true>), dim3(p.n_q), dim3(kLanes), 0, stream, p);
+        } else
+            return hipErrorInvalidValue;
+    } else if (p.mask)
         hipLaunchKernelGGL((topk_select_kernel<Key, true>), dim3(p.n_q), dim3(kLanes), 0, stream, p);
     else
         hipLaunchKernelGGL((topk_select_kernel<Key, false>), dim3(p.n_q), dim3(kLanes), 0, stream, p);
     return hipGetLastError();
 }
-template hipError_t launch_topk_select(const TopkSelectParams<uint32_t>&, hipStream_t);
-template hipError_t launch_topk_select(const TopkSelectParams<unsigned long long>&, hipStream_t);
+template hipError_t launch_topk_select(const TopkSelectParams<uint32_t>&, hipStream_t, bool);
+template hipError_t launch_topk_select(const TopkSelectParams<unsigned long long>&, hipStream_t, bool);
 
 template <class T>
 hipError_t launch_rows_add(T* a, const T* b, uint64_t count, hipStream_t stream) {
@@ -205,7 +214,7 @@ template int read_row(bisbm_engine*, const std::vector<const double*>&, uint64_t
 
 template <class T>
 int topk_select(bisbm_engine* h, const char* fn, const std::vector<const T*>& cells, const std::vector<uint64_t>& off, TopkScratch<T>& w,
-                const uint64_t* d_off, const TopkCand* d_cand, const TopkMaskLists* lists, uint32_t k, uint32_t* node_out, T* val_out) {
+                const uint64_t* d_off, const TopkCand* d_cand, const TopkMaskLists* lists, uint32_t k, uint32_t* node_out, T* val_out, bool ascending) {
     using Key = std::conditional_t<sizeof(T) == 8, unsigned long long, uint32_t>;
     const std::vector<bisbm_engine*> entries = device_entries(h);
     bisbm_engine* e = entries[0];  // the device that selects
@@ -241,7 +250,7 @@ int topk_select(bisbm_engine* h, const char* fn, const std::vector<const T*>& ce
         RESERVE_AS(h, fn, w.d_val, n_q * k);
         const TopkSelectParams<Key> p{q0, (uint32_t)n_q, k, d_off, d_cand, (const Key*)rows, lists ? w.d_mask.get() : nullptr,
                                       w.d_node.get(), (Key*)w.d_val.get()};
-        HIPCHK(h, launch_topk_select(p, e->stream));
+        HIPCHK(h, launch_topk_select(p, e->stream, ascending));
         HIPCHK(h, hipMemcpyAsync(node_out + (size_t)q0 * k, w.d_node.get(), sizeof(uint32_t) * n_q * k, hipMemcpyDeviceToHost, e->stream));
         if (val_out) HIPCHK(h, hipMemcpyAsync(val_out + (size_t)q0 * k, w.d_val.get(), sizeof(T) * n_q * k, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(h, hipStreamSynchronize(e->stream));  // (the scratch is reused by the next chunk)
@@ -250,8 +259,8 @@ int topk_select(bisbm_engine* h, const char* fn, const std::vector<const T*>& ce
     return BISBM_OK;
 }
 template int topk_select(bisbm_engine*, const char*, const std::vector<const uint32_t*>&, const std::vector<uint64_t>&, TopkScratch<uint32_t>&,
-                         const uint64_t*, const TopkCand*, const TopkMaskLists*, uint32_t, uint32_t*, uint32_t*);
+                         const uint64_t*, const TopkCand*, const TopkMaskLists*, uint32_t, uint32_t*, uint32_t*, bool);
 template int topk_select(bisbm_engine*, const char*, const std::vector<const double*>&, const std::vector<uint64_t>&, TopkScratch<double>&,
-                         const uint64_t*, const TopkCand*, const TopkMaskLists*, uint32_t, uint32_t*, double*);
+                         const uint64_t*, const TopkCand*, const TopkMaskLists*, uint32_t, uint32_t*, double*, bool);
 
 }  // namespace bisbm

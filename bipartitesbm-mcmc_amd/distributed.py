@@ -308,6 +308,64 @@ def numpy_conditional_row(dS_row, r_local, free, beta, allowed=None):
     return P, float(P[r]), 0.0 - acc, margin
 
 
+def numpy_held_conditional_row(dS_row, r_loc, free, beta, clamped=False, allowed_own=None, f_own=None, exp=np.exp, log=np.log):
+    """Host statement of the held row (include/bisbm.h, "Held conditionals") for one chain and one query: (dE [K_own], P [K_own],
+    stay, entropy, margin) from the model's row dS_s over the blocks of the node's type, the node's block within its type,
+    whether the node is free in the model's sense (K_own > 1 and it is not alone in its block) and beta.  clamped: the node's
+    mask byte is non-zero.  allowed_own (None: every block): a 0 / 1 vector over the blocks of the type, the node's A_v (its own
+    block always counts as allowed).  f_own (None: no fields): the entries of its class's field row over the same blocks.
+    `exp`, `log`: the exponential (BlockModel.debug_exp for the device's bits) and the logarithm, each called with an array.
+    margin is None for a node that is not open.  With no hold it is numpy_conditional_row bit for bit."""
+    dS = np.asarray(dS_row, dtype=np.float64)
+    K, r, beta = len(dS), int(r_loc), float(beta)
+    dE = np.zeros(K, dtype=np.float64)
+    for s in range(K):
+        if s != r:
+            dE[s] = float(dS[s]) + (float(f_own[s]) - float(f_own[r])) if f_own is not None else float(dS[s])
+    A = np.ones(K, dtype=bool) if allowed_own is None else np.asarray(allowed_own) != 0
+    A[r] = True
+    is_open = K > 1 and bool(free) and not clamped and int(A.sum()) > 1
+    margin = None
+    if not is_open:
+        P = np.zeros(K, dtype=np.float64)
+        P[r] = 1.0
+    else:
+        mn = 0.0
+        for s in range(K):
+            if A[s] and dE[s] < mn:
+                mn = float(dE[s])
+        x = beta * (dE - mn)
+        w = np.where((x > 700.0) | ~A, 0.0, np.asarray(exp(np.where(A, -np.minimum(x, 700.0), 0.0)), dtype=np.float64))
+        Z = float(w[0])
+        for y in w[1:]:
+            Z = Z + float(y)
+        P = w / Z
+        others = A.copy()
+        others[r] = False
+        margin = float(dE[others].min())
+    acc = 0.0
+    lnP = np.asarray(log(np.where(P != 0.0, P, 1.0)), dtype=np.float64)
+    for y, ln in zip(P, lnP):
+        if y != 0.0:
+            acc = acc + float(y) * float(ln)
+    return dE, P, float(P[r]), 0.0 - acc, margin
+
+
+def numpy_least_settled(values, k, by="entropy"):
+    """Host statement of bisbm_least_settled_topk: (query indices uint32 [k], values float64 [k]) from one statistic of
+    BlockModel.conditionals_stats -- the largest entropy sums first, or (by="stay") the smallest stay sums first, ties in ascending
+    query index; past the entries the index is 0xffffffff and the value 0.0.  The device orders the bit patterns as unsigned keys,
+    which is the order of the values only for sums of non-negative terms: asserted here."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    assert not np.isnan(v).any() and not (v.view(np.uint64) >> np.uint64(63)).any(), "a negative or NaN sum: the bit patterns do not order as unsigned keys"
+    order = np.lexsort((np.arange(len(v)), v if by == "stay" else -v))[:int(k)]
+    idx = np.full(int(k), 0xFFFFFFFF, dtype=np.uint32)
+    val = np.zeros(int(k), dtype=np.float64)
+    idx[:len(order)] = order
+    val[:len(order)] = v[order]
+    return idx, val
+
+
 def numpy_heatbath_choice(dS_row, P_row, r, free, u, greedy, allowed=None):
     """Host statement of steps 3 and 4 of the heat-bath sweeps (include/bisbm.h, "Heat-bath sweeps and greedy polishing") for one
     visited node: the node's new block within its type from its rows dS_s and P(s), its current block r within its type, whether

@@ -583,6 +583,19 @@ public:
         dS.assign((size_t)n_chains_ * stride, 0.), p.assign((size_t)n_chains_ * stride, 0.);
         check(bisbm_conditionals_get_last(h_, query_index, stride, dS.data(), p.data()));
     }
+    // held conditionals and the least settled queries (include/bisbm.h, "Held conditionals", "Least settled"): the switch between
+    // the held row (the heat-bath kernel's, under the handle's clamp, constraints and fields) and the model's row; the k queries
+    // with the largest entropy sum (BISBM_SETTLED_BY_ENTROPY) or the smallest stay sum (BISBM_SETTLED_BY_STAY), as query indices
+    void conditionals_held(bool on = true) { check(bisbm_held_conditionals_set(h_, on ? 1 : 0)); }
+    bool conditionals_is_held() {
+        int on = 0;
+        check(bisbm_held_conditionals_get(h_, &on));
+        return on != 0;
+    }
+    void least_settled(uint32_t by, uint32_t k, std::vector<uint32_t>& queries, std::vector<double>& values, uint64_t& terms) {
+        queries.assign(k, 0), values.assign(k, 0.);
+        check(bisbm_least_settled_topk(h_, by, k, queries.data(), values.data(), &terms));
+    }
     // rung of every chain under replica exchange (bisbm_tempering_get)
     std::vector<uint32_t> tempering_rungs() {
         std::vector<uint32_t> rung(n_chains_);

@@ -57,6 +57,7 @@ const option_spec kOptions[] = {
     {"similar", 0, 2},
     {"foldin", 0, 2},           {"foldin_alpha", 0, 1},
     {"conditionals", 0, 2},     {"conditionals_beta", 0, 1},
+    {"conditionals_held", 0, 0}, {"least_settled", 0, 2},
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
     {"polish", 0, 1},           {"heatbath", 0, 0},
     {"reshuffle", 0, 1},        {"reshuffle_scans", 0, 1},
@@ -308,6 +309,12 @@ void print_help(const char* argv0) {
                  "                                        the blocks of its type (the conditionals averaged through the alignment).\n"
                  "  --conditionals_beta B                 With --conditionals: the inverse temperature of the conditional, B > 0\n"
                  "                                        (default 1).\n"
+                 "  --conditionals_held                   With --conditionals: evaluate the held row instead -- the conditional the\n"
+                 "                                        samplers sample under --clamp, --constraints and --fields (a clamped node\n"
+                 "                                        is a point mass, a barred block has probability 0, the field is added).\n"
+                 "  --least_settled OUT K [entropy|stay]  With --conditionals: OUT receives `query node value` for the K lines of\n"
+                 "                                        QUERIES (counted from 0) with the largest mean entropy (the default) or\n"
+                 "                                        the smallest mean stay, selected on the device, %.17g; ties in line order.\n"
                  "  --modes OUT THRESHOLD                 With --marginalize: after the last sample the sampled chains' partitions\n"
                  "                                        are compared (variation of information, nats) and grouped into modes:\n"
                  "                                        chains joined by a path of pairs with VI <= THRESHOLD share a mode.  OUT\n"
@@ -433,6 +440,27 @@ int main(int argc, char const* argv[]) {
     if (count("conditionals_beta") && !count("conditionals")) {
         std::cerr << "--conditionals_beta sets the inverse temperature of the node conditionals: it needs --conditionals.\n";
         return 1;
+    }
+    if (count("conditionals_held") && !count("conditionals")) {
+        std::cerr << "--conditionals_held evaluates the node conditionals under the clamp, the constraints and the fields: it needs --conditionals.\n";
+        return 1;
+    }
+    if (count("least_settled") && !count("conditionals")) {
+        std::cerr << "--least_settled ranks the query nodes of the node conditionals: it needs --conditionals.\n";
+        return 1;
+    }
+    uint32_t least_settled_k = 0, least_settled_by = BISBM_SETTLED_BY_ENTROPY;
+    if (var_map.count("least_settled")) {
+        const std::vector<std::string>& a = var_map["least_settled"];
+        char* end = nullptr;
+        const unsigned long long k = a.size() >= 2 ? std::strtoull(a[1].c_str(), &end, 10) : 0;
+        if (a.size() < 2 || a.size() > 3 || a[1].empty() || a[1][0] == '-' || *end != '\0' || k == 0 || k > 1024 ||
+            (a.size() == 3 && a[2] != "entropy" && a[2] != "stay")) {
+            std::cerr << "Invalid --least_settled. The file to write, K in [1, 1024] and optionally entropy or stay, e.g. --least_settled out.txt 10 stay.\n";
+            return 1;
+        }
+        least_settled_k = (uint32_t)k;
+        if (a.size() == 3 && a[2] == "stay") least_settled_by = BISBM_SETTLED_BY_STAY;
     }
     double conditionals_beta = 1.;
     if (var_map.count("conditionals")) {
@@ -1530,6 +1558,7 @@ int main(int argc, char const* argv[]) {
                 std::vector<uint32_t> q;
                 for (uint32_t v : conditional_queries) q.push_back(new_id.empty() ? v : new_id[v]);
                 blockmodel.conditionals_set(q, conditionals_beta);
+                if (count("conditionals_held")) blockmodel.conditionals_held(true);
             }
             if (trace_depth) {
                 blockmodel.trace_set(trace_depth);
@@ -1750,7 +1779,28 @@ int main(int argc, char const* argv[]) {
                     return 1;
                 }
                 std::clog << "conditionals: " << conditional_queries.size() << " query node(s), beta " << conditionals_beta << ", " << st.terms
-                          << " chain term(s) per sum" << (soft ? ", soft marginals" : "") << " -> " << out_path << "\n";
+                          << " chain term(s) per sum" << (soft ? ", soft marginals" : "") << (count("conditionals_held") ? ", held rows" : "") << " -> " << out_path
+                          << "\n";
+            }
+            if (var_map.count("least_settled")) {
+                const std::string out_path = var_map["least_settled"][0];
+                std::ofstream out(out_path);
+                std::vector<uint32_t> ranked;
+                std::vector<double> values;
+                uint64_t terms = 0;
+                if (!conditional_queries.empty()) blockmodel.least_settled(least_settled_by, least_settled_k, ranked, values, terms);
+                char num[64];
+                for (size_t i = 0; i < ranked.size() && ranked[i] != 0xffffffffu; ++i) {
+                    std::snprintf(num, sizeof(num), " %.17g", values[i] / (double)terms);
+                    out << ranked[i] << " " << conditional_queries[ranked[i]] << num << "\n";
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --least_settled: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "least_settled: " << least_settled_k << " of " << conditional_queries.size() << " query node(s) by "
+                          << (least_settled_by == BISBM_SETTLED_BY_STAY ? "stay" : "entropy") << " -> " << out_path << "\n";
             }
             if (count("block_summary")) {
                 // one section per mode: terms, then the means and standard deviations of the sizes, the degrees and the edge counts

@@ -19,7 +19,7 @@ import numpy as np
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
                 similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None, rung_moves=None, blocks=False,
-                clamp=None, constraints=None, fields=None):
+                clamp=None, constraints=None, fields=None, conditionals_held=False, least_settled=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -91,7 +91,14 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     burn-in and left set, so every node stays inside the blocks its class allows through the whole run, whatever the sampler.
     Classes that allow disjoint sets of blocks keep those sets apart in every chain.
     `fields`: (class_of_node, field) as model.set_fields takes them (include/bisbm.h, "Block fields"): set before the burn-in and
-    left set, so every sampler of the run targets exp(-beta (S + Phi)); the marginals are those of the tilted posterior."""
+    left set, so every sampler of the run targets exp(-beta (S + Phi)); the marginals are those of the tilted posterior.
+    `conditionals_held`: with `conditionals` only (ValueError without, before anything is set): the conditional samples evaluate
+    the held row (include/bisbm.h, "Held conditionals"), the conditional the run's samplers sample under the clamp, the
+    constraints and the fields as they are at each sample.
+    `least_settled`: (k, by) or (k,) with `conditionals` only (ValueError without), by = "entropy" (the default) or "stay"
+    (include/bisbm.h, "Least settled"): model.least_settled(k, by) -- (query indices, nodes, values, terms) -- is appended after
+    the conditionals' stats (and their soft marginals)."""
+    _check_conditional_extras(conditionals, conditionals_held, least_settled)
     if clamp is not None:
         model.clamp(clamp)
     if constraints is not None:
@@ -120,6 +127,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         model.foldin_set(foldin[0], foldin[2] if len(foldin) > 2 else None)
     if conditionals is not None:
         model.conditionals_set(conditionals[0], conditionals[1] if len(conditionals) > 1 else 1.0)
+        if conditionals_held:
+            model.conditionals_held(True)
     _trace_start(model, trace)
     taken = [0]
 
@@ -145,6 +154,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             out += (model.conditionals_stats(),)
             if align:
                 out += (model.conditionals_marginals(),)
+            if least_settled is not None:
+                out += (model.least_settled(int(least_settled[0]), least_settled[1] if len(least_settled) > 1 else "entropy"),)
         return out
     if device_counts is None and not multi:
         # one rank, no caller buffer: the library's own histogram
@@ -216,7 +227,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
 
 def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,
                       reassign=False, tempering=None, exchange_every=1, sampler="mh", trace=None, rung_moves=None, blocks=False, clamp=None,
-                      constraints=None, fields=None):
+                      constraints=None, fields=None, conditionals=None, conditionals_held=False, least_settled=None):
     """Mode-resolved marginals (include/bisbm.h, "Mode-resolved marginals"): the chains are grouped into posterior modes and
     every mode gets an aligned histogram and a MAP of its own, in the numbering of its own reference.
     Exactly one of `threshold` and `mode_of_chain`: with `threshold` the grouping is model.partition_modes(threshold) taken
@@ -248,6 +259,11 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
     `clamp`: node ids or a mask, as in marginalize(): set before the burn-in and left set.
     `constraints`: (class_of_node, allowed), as in marginalize(): set before the burn-in and left set.
     `fields`: (class_of_node, field), as in marginalize(): set before the burn-in and left set.
+    `conditionals`: (nodes, beta) or (nodes,), as in marginalize(): the queries are set before the first sample, every sample
+    also takes one conditional sample of every counted chain (pooled over the modes: per-mode conditionals are not kept, and
+    there are no soft marginals), and the dict gets "conditionals": model.conditionals_stats().  `conditionals_held` and
+    `least_settled` = (k, by), both with `conditionals` only (ValueError without), as in marginalize(): the held row, and
+    "least_settled": model.least_settled(k, by) in the dict.
     Chains spread over ranks (`shard`, or model.shard, with world_size > 1) raise ValueError: pooling modes across ranks is
     not done here."""
     if (threshold is None) == (mode_of_chain is None):
@@ -256,6 +272,7 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         raise ValueError("tempering needs reassign=True: chains that trade temperatures have no fixed mode")
     if reassign and mode_of_chain is not None:
         raise ValueError("reassign takes its anchors from a grouping: give threshold, not mode_of_chain")
+    _check_conditional_extras(conditionals, conditionals_held, least_settled)
     shard = shard if shard is not None else getattr(model, "shard", None)
     if shard is not None and getattr(shard, "world_size", 1) > 1:
         raise ValueError("marginalize_modes serves the chains of one rank: pooling modes across ranks is not done here")
@@ -284,6 +301,10 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         model.marginals_set_modes(moc, n_modes)
     if blocks:
         model.block_sums_set(True)
+    if conditionals is not None:
+        model.conditionals_set(conditionals[0], conditionals[1] if len(conditionals) > 1 else 1.0)
+        if conditionals_held:
+            model.conditionals_held(True)
     _trace_start(model, trace)
     for _ in range(int(n_samples)):
         if sampling_frequency_sweeps > 0:
@@ -291,6 +312,13 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         model.marginals_accumulate(None)
         if trace:
             model.trace_record()
+        if conditionals is not None:
+            model.conditionals_accumulate()
+    extras = {}
+    if conditionals is not None:
+        extras["conditionals"] = model.conditionals_stats()
+        if least_settled is not None:
+            extras["least_settled"] = model.least_settled(int(least_settled[0]), least_settled[1] if len(least_settled) > 1 else "entropy")
     state = model.marginals_modes()
     labels = np.zeros((n_modes, model.n), dtype=np.uint32)
     top = np.zeros((n_modes, model.n), dtype=np.uint32)
@@ -303,13 +331,25 @@ def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweep
         visits = model.marginals_mode_assignment()["visits"]
         return {"modes": modes, "labels": labels, "top": top, "counts": counts, "terms": state["terms"], "weights": state["weights"],
                 "ref_chain": state["ref_chain"], "moved": int(((visits > 0).sum(axis=1) > 1).sum()), "unassigned": state["unassigned"],
-                "visits": visits}
+                "visits": visits, **extras}
     moved = 0
     if threshold is not None:
         after = model.partition_modes(threshold, chains=modes["chains"])
         moved = int(sum(_co_members(modes, c) != _co_members(after, c) for c in range(len(modes["chains"]))))
     return {"modes": modes, "labels": labels, "top": top, "counts": counts, "terms": state["terms"], "weights": state["weights"],
-            "ref_chain": state["ref_chain"], "moved": moved}
+            "ref_chain": state["ref_chain"], "moved": moved, **extras}
+
+
+def _check_conditional_extras(conditionals, conditionals_held, least_settled):
+    """conditionals_held / least_settled of marginalize() / marginalize_modes(): refused without `conditionals`, and a malformed
+    `least_settled`, before anything is set or run."""
+    if conditionals is None and conditionals_held:
+        raise ValueError("conditionals_held=True switches the row of the node conditionals: it needs conditionals=(nodes, beta)")
+    if conditionals is None and least_settled is not None:
+        raise ValueError("least_settled ranks the queries of the node conditionals: it needs conditionals=(nodes, beta)")
+    if least_settled is not None:
+        if not 1 <= len(least_settled) <= 2 or (len(least_settled) > 1 and least_settled[1] not in ("entropy", "stay")):
+            raise ValueError("least_settled must be (k, by) or (k,), by = \"entropy\" or \"stay\"")
 
 
 def _trace_start(model, trace):

@@ -30,7 +30,8 @@ extern "C" {
  *    (bisbm_query_scores_*), co-assignment (bisbm_coassign_*), fold-in queries (bisbm_foldin_*), population annealing
  *    (bisbm_population_*), node conditionals (bisbm_conditionals_*), heat-bath sweeps and greedy polishing
  *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp), chain traces (bisbm_trace_*), round recipes
- *    (bisbm_tempering_run_rounds, bisbm_tempering_rung_stats, bisbm_rounds_population_run).  Additions only. */
+ *    (bisbm_tempering_run_rounds, bisbm_tempering_rung_stats, bisbm_rounds_population_run), held conditionals and the least
+ *    settled queries (bisbm_held_conditionals_*, bisbm_least_settled_topk, bisbm_debug_log).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -560,8 +561,8 @@ int bisbm_foldin_topk(bisbm_handle h, uint32_t what, uint32_t k, int exclude_lis
  *   row for a chain that was not counted, a stride below some chain's K_own BISBM_ERR_INVALID_ARG); BISBM_ERR_STATE without
  *   KEEP_LAST or before the first sample; dS_out or p_out may be NULL.
  * Out of scope: conditionals in mt19937-compat arithmetic, two-byte labels, pooling over processes, a library-chosen
- * reference, per-mode soft histograms, top-k of the least settled nodes on the device (with n doubles per statistic the host
- * sorts them).  Moving nodes by these rows is bisbm_heatbath_run below. */
+ * reference, per-mode soft histograms.  (Top-k of the least settled nodes on the device: "Least settled" below; the row under a
+ * clamp, constraints and fields: "Held conditionals" below.)  Moving nodes by these rows is bisbm_heatbath_run below. */
 #define BISBM_COND_KEEP_LAST 1u
 int bisbm_conditionals_set(bisbm_handle h, uint32_t n_queries, const uint32_t *queries /* NULL: all n nodes */, double beta,
                            uint32_t what);
@@ -574,6 +575,51 @@ int bisbm_conditionals_get_marginals(bisbm_handle h, double *prob_out /* n_queri
                                      uint64_t *terms_out);
 int bisbm_conditionals_get_last(bisbm_handle h, uint32_t query_index, uint32_t stride, double *dS_out,
                                 double *p_out /* n_chains * stride each, either may be NULL */);
+
+/* Held conditionals: the sampler's own conditional, returned (no reference counterpart).  The calls above evaluate the model's
+ * unrestricted row whatever is held.  With the switch on, bisbm_conditionals_accumulate evaluates instead the HELD ROW: the row
+ * the heat-bath kernel forms under the handle's clamp ("Clamped nodes" 2.), block constraints ("Block constraints" 2.) and
+ * block fields ("Block fields" 2.), the same f64 operations in the same order -- a heat-bath replay fed these rows needs no
+ * host-side restriction and no field add.  The holds are read as they are at each sample; no copy is taken at switch time.
+ * For query v in counted chain c, with r = b_v, clamped = v's mask byte is non-zero, A_v = the blocks of v's type that its class
+ * allows (all of them without constraints; r is in A_v, because setting constraints validates the labels) and f = the field row
+ * of v's class over v's type (absent without fields), in f64 with no fused multiply-add:
+ *   1. dE_r = 0.0; for s != r, dE_s = dS_s + (f[s] - f[r]) with fields (the difference first, then one add) and dE_s = dS_s
+ *      without, dS_s exactly as in "Node conditionals" 1.  Evaluated and reported for EVERY s of the type, inside A_v or not:
+ *      dS_out of bisbm_conditionals_get_last holds dE.
+ *   2. OPEN iff K_own > 1 and n_r[r] > 1 and not clamped and |A_v| > 1.
+ *   3. Not open: the point mass on r.  Open: mn = min over s in A_v of dE_s (the 0 at r included); x_s = beta (dE_s - mn);
+ *      w_s = (x_s > 700.0) ? 0.0 : exp(-x_s) for s in A_v and exactly 0.0 outside; Z = the w_s added in ascending s over all s
+ *      (a +0.0 term keeps every bit); P(s) = w_s / Z.
+ *   4. Per-chain terms: stay = P(r); entropy = 0.0 - sum P ln P in ascending s, zero terms skipped; margin = min over s in
+ *      A_v, s != r, of dE_s, taken only when the node is open; `free` counts the chains in which the node is open.
+ *   5. Everything downstream is unchanged and is fed these rows: pooling over chains, soft marginals through the alignment,
+ *      last rows, rung-0 counting, several devices, shape groups.
+ * set: on != 0 switches to the held row, 0 back to the model's row.  A call that changes the switch zeroes the label-free sums,
+ *   prob and their terms and forgets the last rows (a sum over two definitions means nothing); queries, beta, `what` and the
+ *   reference stay.  A call that does not change it changes nothing.  bisbm_conditionals_set puts the switch back to off, as it
+ *   forgets the reference.  BISBM_ERR_STATE without queries.  Allowed wherever the conditionals are allowed; holds themselves
+ *   are refused on compat, wide and shape-grouped handles, where the switch therefore changes nothing.  On with no clamp, no
+ *   constraints and no fields the plain kernel runs: the plain call bit for bit.
+ * Out of scope: the field and the lists inside the fold-in posteriors, a mask or a table per chain, pooling over processes,
+ * per-mode soft histograms. */
+int bisbm_held_conditionals_set(bisbm_handle h, int on);
+int bisbm_held_conditionals_get(bisbm_handle h, int *on_out);
+
+/* Least settled: the k queries whose pooled conditional is the least decided, selected on the device (no reference
+ * counterpart).  One statistic of the current sums of bisbm_conditionals_get_stats (held rows or plain rows alike) is ranked over
+ * the n_queries entries by the exact radix select of the other top-k calls: by entropy, the largest entropy_sum first; by stay,
+ * the smallest stay_sum first; ties in ascending query index.  query_out holds query INDICES (queries may repeat), value_out[i]
+ * the entry bisbm_conditionals_get_stats returns for query_out[i], bit for bit -- over several devices the device sums are added
+ * in device order, as get_stats adds them.  Both statistics are sums of non-negative terms (stay is in [0, 1], an entropy term
+ * is 0.0 - a sum of terms <= 0), so their bit patterns order as unsigned keys.  k follows bisbm_coassign_topk: k = 0
+ * BISBM_ERR_INVALID_ARG, k > 1024 BISBM_ERR_UNSUPPORTED, past the n_queries entries query_out is 0xffffffff and value_out 0.0.
+ * BISBM_ERR_STATE without queries or before the first sample; BISBM_ERR_INVALID_ARG for an unknown `by`.
+ * Out of scope: a mean-margin ranking (`free` differs per query: a division per key). */
+#define BISBM_SETTLED_BY_ENTROPY 0u   /* largest entropy_sum first */
+#define BISBM_SETTLED_BY_STAY    1u   /* smallest stay_sum first */
+int bisbm_least_settled_topk(bisbm_handle h, uint32_t by, uint32_t k, uint32_t *query_out /* k query indices */,
+                             double *value_out /* k, may be NULL */, uint64_t *terms_out);
 
 /* Heat-bath sweeps and greedy polishing: nodes moved by their conditionals (no reference counterpart).  Where the MH step draws
  * one target block and accepts or rejects it, a heat-bath (Gibbs) update draws the node's new block from its exact conditional
@@ -781,12 +827,13 @@ int bisbm_clamp_get(bisbm_handle h, uint8_t *mask_out /* n, may be NULL */, uint
  *      resampled slot carries its ancestor's labels, which were admissible.
  * Constraints and a clamp are independent and may both be set.  bisbm_set_memberships under constraints refuses a vector
  * that violates them (BISBM_ERR_INVALID_ARG, naming the first node).  The analysis calls only read state and are unchanged;
- * bisbm_conditionals_* keeps reporting the UNRESTRICTED row.  Refused, with a message and nothing changed:
+ * bisbm_conditionals_* keeps reporting the UNRESTRICTED row
+ * (unless bisbm_held_conditionals_set is on: "Held conditionals").  Refused, with a message and nothing changed:
  * BISBM_RNG_MT19937_COMPAT and two-byte labels BISBM_ERR_UNSUPPORTED; chains grouped by shape BISBM_ERR_STATE.  While
  * constraints are set bisbm_agg_merge and bisbm_agg_merge_total are BISBM_ERR_STATE (bisbm_constraints_set(h, 0, NULL, NULL)
  * first).
  * Out of scope: a table per chain, constraints in the production kernel (DESIGN.md section 26's follow-up serves both),
- * restricted rows in bisbm_conditionals_*, mt19937-compat arithmetic, wide handles, chains grouped by shape, merges or splits
+ * restricted rows in the plain bisbm_conditionals_* row (the opt-in is "Held conditionals"), mt19937-compat arithmetic, wide handles, chains grouped by shape, merges or splits
  * under constraints.  (Soft priors over blocks: "Block fields" below.) */
 int bisbm_constraints_set(bisbm_handle h, uint32_t n_classes, const uint8_t *class_of_node /* n */,
                           const uint8_t *allowed /* n_classes * (ka + kb) */);   /* 0 / NULL clears */
@@ -831,12 +878,12 @@ int bisbm_constraints_get(bisbm_handle h, uint32_t *n_classes_out, uint8_t *clas
  *      range is ever counted).  Without fields every Phi is 0.0.  The exchange and the resampling use this same code.
  * Unchanged: bisbm_entropy stays the description length, and every "lowest description length" choice with it (alignment
  * reference, a mode's best chain); every analysis call; bisbm_conditionals_* keeps reporting the model's row (the heat-bath row
- * is that row plus the field); the shuffle (an initialiser, not a sampler); bisbm_set_memberships.  Refused, with a message and
+ * is that row plus the field) (unless bisbm_held_conditionals_set is on: "Held conditionals"); the shuffle (an initialiser, not a sampler); bisbm_set_memberships.  Refused, with a message and
  * nothing changed: BISBM_RNG_MT19937_COMPAT and two-byte labels BISBM_ERR_UNSUPPORTED; chains grouped by shape BISBM_ERR_STATE.
  * While fields are set bisbm_agg_merge and bisbm_agg_merge_total are BISBM_ERR_STATE (bisbm_fields_set(h, 0, NULL, NULL) first).
  * Out of scope: fields in the production kernel, a table per chain, more than 256 distinct rows, mt19937-compat arithmetic,
- * wide handles, chains grouped by shape, merges or splits under fields, the field inside bisbm_conditionals_* and the fold-in
- * posteriors, learning the field from metadata. */
+ * wide handles, chains grouped by shape, merges or splits under fields, the field inside the plain bisbm_conditionals_* row (the
+ * opt-in is "Held conditionals") and inside the fold-in posteriors, learning the field from metadata. */
 int bisbm_fields_set(bisbm_handle h, uint32_t n_classes, const uint8_t *class_of_node /* n */,
                      const double *field /* n_classes * (ka + kb) */);   /* 0 / NULL clears */
 int bisbm_fields_get(bisbm_handle h, uint32_t *n_classes_out, uint8_t *class_of_node_out, double *field_out);
@@ -1165,6 +1212,8 @@ int bisbm_debug_log_q(bisbm_handle h, const int32_t *n, const int32_t *k, size_t
 
 /* Device numerics probe (tests, host replays of "Pair reshuffles"): out[i] = exp(x[i]) as the device evaluates it. */
 int bisbm_debug_exp(bisbm_handle h, const double *x, size_t count, double *out);
+/* ... and out[i] = log(x[i]): the logarithm of the entropy term of the node conditionals (host statements of "Held conditionals"). */
+int bisbm_debug_log(bisbm_handle h, const double *x, size_t count, double *out);
 
 const char *bisbm_last_error(bisbm_handle h); /* h may be NULL: error of the last failed create */
 int bisbm_abi_version(void);
