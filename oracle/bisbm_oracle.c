@@ -682,6 +682,13 @@ struct orc_model {
     size_t cap_K;           /* blocks the state arrays are allocated for */
     double last_split_dS;   /* dS of the cut the last agg_split applied */
     uint64_t last_accepted, last_sweeps;
+    /* the holds of include/bisbm.h (Philox mode): NULL = not set */
+    uint8_t *clamp;                  /* n bytes */
+    uint8_t *cn_class, *cn_allowed;  /* n bytes; n_classes * K bytes */
+    uint8_t *fl_class;               /* n bytes */
+    double *fl_field;                /* n_classes * K */
+    double last_margin;              /* orc_last_margin */
+    uint64_t hold_counts[4];         /* orc_hold_counts */
 };
 
 size_t orc_n(const orc_model *m) { return m->n; }
@@ -739,6 +746,7 @@ orc_model *orc_create(size_t n, size_t na, size_t nb, const uint64_t *rowptr, co
     m->kv = (int *)calloc(K, sizeof(int));
     m->cap_K = K;
     m->entropy_min = INFINITY;
+    m->last_margin = INFINITY; /* no orc_anneal call yet: no accept test was made */
     m->accu_r = 0.;
     m->rng_mode = ORC_RNG_COMPAT;
     orc_mt_seed(&m->engine, 5489u);
@@ -763,8 +771,46 @@ void orc_destroy(orc_model *m) {
     free(m->n_r);
     free(m->eta);
     free(m->kv);
+    free(m->clamp);
+    free(m->cn_class);
+    free(m->cn_allowed);
+    free(m->fl_class);
+    free(m->fl_field);
     free(m);
 }
+
+static void *dup_bytes(const void *src, size_t bytes) {
+    void *p = malloc(bytes ? bytes : 1);
+    memcpy(p, src, bytes);
+    return p;
+}
+
+void orc_set_clamp(orc_model *m, const uint8_t *mask) {
+    free(m->clamp);
+    m->clamp = mask ? (uint8_t *)dup_bytes(mask, m->n) : NULL;
+}
+
+void orc_set_constraints(orc_model *m, size_t n_classes, const uint8_t *class_of_node, const uint8_t *allowed) {
+    free(m->cn_class);
+    free(m->cn_allowed);
+    m->cn_class = m->cn_allowed = NULL;
+    if (n_classes == 0 || !class_of_node || !allowed) return;
+    m->cn_class = (uint8_t *)dup_bytes(class_of_node, m->n);
+    m->cn_allowed = (uint8_t *)dup_bytes(allowed, n_classes * m->K);
+}
+
+void orc_set_fields(orc_model *m, size_t n_classes, const uint8_t *class_of_node, const double *field) {
+    free(m->fl_class);
+    free(m->fl_field);
+    m->fl_class = NULL;
+    m->fl_field = NULL;
+    if (n_classes == 0 || !class_of_node || !field) return;
+    m->fl_class = (uint8_t *)dup_bytes(class_of_node, m->n);
+    m->fl_field = (double *)dup_bytes(field, sizeof(double) * n_classes * m->K);
+}
+
+double orc_last_margin(const orc_model *m) { return m->last_margin; }
+void orc_hold_counts(const orc_model *m, uint64_t out[4]) { memcpy(out, m->hold_counts, sizeof(m->hold_counts)); }
 
 void orc_seed_compat(orc_model *m, uint64_t engine_seed, uint64_t gen_seed) {
     m->rng_mode = ORC_RNG_COMPAT;
@@ -1117,7 +1163,15 @@ static int step_compat(orc_model *m, size_t v, double temperature) {
     return 0;
 }
 
+/* The holds follow include/bisbm.h to the letter: a clamped node is a step that was not accepted ("Clamped nodes" 1.); the
+ * proposal is drawn as always; a target of the node's type that is not its own block and not in A_v is not evaluated ("Block
+ * constraints" 1.); under fields dE = dS + (f[s] - f[r]), the difference first, stands where dS stood, in the T = 0 test, in the
+ * accept line and in the running sum ("Block fields" 1. and 4.).  With nothing set this is the step it always was. */
 static int step_philox(orc_model *m, size_t v, double temperature, uint64_t gstep) {
+    if (m->clamp && m->clamp[v]) {
+        m->hold_counts[0]++;
+        return 0;
+    }
     uint32_t A[4], B[4];
     phx_draw(m->phx_seed, m->phx_chain, PHX_STEP_A, gstep, A);
     phx_draw(m->phx_seed, m->phx_chain, PHX_STEP_B, gstep, B);
@@ -1125,16 +1179,35 @@ static int step_philox(orc_model *m, size_t v, double temperature, uint64_t gste
     double u_tgt = u53(B[0], B[1]), u_acc = u53(B[2], B[3]);
     size_t s = propose_philox(m, v, u_idx, u_R, u_tgt);
     size_t r = m->labels[v];
+    if (m->cn_allowed && s != r && (r < m->ka) == (s < m->ka) && !m->cn_allowed[(size_t)m->cn_class[v] * m->K + s]) {
+        m->hold_counts[1]++;
+        return 0;
+    }
     compute_kv(m, v);
     double dS = transition_ratio(m, v, r, s);
     int cross = (r != s) && ((r < m->ka) != (s < m->ka));
     if (cross) return 0; /* dS = +inf: never accepted (:121-123) */
+    double dE = dS;
+    int fielded = m->fl_field && s != r;
+    if (fielded) {
+        const double *f = m->fl_field + (size_t)m->fl_class[v] * m->K;
+        dE = dS + (f[s] - f[r]);
+        m->hold_counts[2]++;
+    }
     if (temperature == 0.) {
-        if (dS < 0) return apply_mcmc_move(m, v, r, s, dS);
+        if (fielded && (dE < 0) != (dS < 0)) m->hold_counts[3]++;
+        if (dE < 0) return apply_mcmc_move(m, v, r, s, dE);
         return 0;
     }
     /* u < exp(-dS/T) accu1/accu0 (:54-57) written without the log and the quotient */
-    if (u_acc * m->phx_accu0 < m->phx_accu1 * exp(-dS * (1.0 / temperature))) return apply_mcmc_move(m, v, r, s, dS);
+    double lhs = u_acc * m->phx_accu0, rhs = m->phx_accu1 * exp(-dE * (1.0 / temperature));
+    if (s != r) {
+        double big = lhs > rhs ? lhs : rhs;
+        double margin = big == 0. ? 0. : (isinf(big) ? 1. : fabs(lhs - rhs) / big);
+        if (margin < m->last_margin) m->last_margin = margin;
+        if (fielded && (lhs < rhs) != (lhs < m->phx_accu1 * exp(-dS * (1.0 / temperature)))) m->hold_counts[3]++;
+    }
+    if (lhs < rhs) return apply_mcmc_move(m, v, r, s, dE);
     return 0;
 }
 
@@ -1315,6 +1388,8 @@ double orc_anneal(orc_model *m, int schedule, float kw0, float kw1, uint64_t dur
     uint64_t all_sweeps = duration / num_nodes;
     double temperature = 1;
     m->last_sweeps = 0;
+    m->last_margin = INFINITY;
+    memset(m->hold_counts, 0, sizeof(m->hold_counts));
     for (uint64_t sweep = 0; sweep < all_sweeps; ++sweep) {
         uint32_t keys_a[4], keys_b[4];
         if (m->rng_mode == ORC_RNG_COMPAT)

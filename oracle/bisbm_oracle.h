@@ -121,6 +121,20 @@ uint64_t orc_last_accepted(const orc_model *m);
 uint64_t orc_last_sweeps(const orc_model *m);
 uint64_t orc_total_sweeps(const orc_model *m);
 
+/* The three holds of include/bisbm.h ("Clamped nodes" 1., "Block constraints" 1., "Block fields" 1. and 4.) in the Philox-mode MH
+ * step, restated literally: bytes per node and a byte / f64 table, copied on set.  NULL or 0 classes clears.  Nothing here is
+ * validated: the caller hands admissible tables.  Merges and splits do not know the holds (clear them first, as the library asks). */
+void orc_set_clamp(orc_model *m, const uint8_t *mask /* n, non-zero = clamped */);
+void orc_set_constraints(orc_model *m, size_t n_classes, const uint8_t *class_of_node /* n */,
+                         const uint8_t *allowed /* n_classes * K, non-zero = allowed */);
+void orc_set_fields(orc_model *m, size_t n_classes, const uint8_t *class_of_node /* n */, const double *field /* n_classes * K */);
+/* over the last orc_anneal call: the smallest |lhs - rhs| / max(lhs, rhs) of the two sides of the accept line
+ * u accu0 < accu1 exp(-dE / T) over the steps that reached it with s != r (+inf when none did) */
+double orc_last_margin(const orc_model *m);
+/* over the last orc_anneal call: out[0] steps of clamped nodes, out[1] proposals of a same-type target outside A_v, out[2] steps
+ * whose dS got a field difference added, out[3] of those the ones whose decision differs from the one dS alone gives */
+void orc_hold_counts(const orc_model *m, uint64_t out[4]);
+
 /* agglomerative merges between anneals (blockmodel.cc:109-288,335-372,567-611,639-669); see the .c file */
 size_t orc_ka(const orc_model *m);
 size_t orc_kb(const orc_model *m);

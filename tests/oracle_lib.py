@@ -15,6 +15,7 @@ SCHEDULES = {"exponential": 0, "linear": 1, "logarithmic": 2, "constant": 3, "ab
 
 _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
+_u8p = C.POINTER(C.c_uint8)
 _i32p = C.POINTER(C.c_int32)
 _f64p = C.POINTER(C.c_double)
 
@@ -104,6 +105,12 @@ def lib():
     for name in ("orc_last_accepted", "orc_last_sweeps", "orc_total_sweeps"):
         getattr(L, name).restype = C.c_uint64
         getattr(L, name).argtypes = [C.c_void_p]
+    L.orc_set_clamp.argtypes = [C.c_void_p, _u8p]
+    L.orc_set_constraints.argtypes = [C.c_void_p, C.c_size_t, _u8p, _u8p]
+    L.orc_set_fields.argtypes = [C.c_void_p, C.c_size_t, _u8p, _f64p]
+    L.orc_last_margin.restype = C.c_double
+    L.orc_last_margin.argtypes = [C.c_void_p]
+    L.orc_hold_counts.argtypes = [C.c_void_p, _u64p]
     L.orc_get_memberships.argtypes = [C.c_void_p, _u32p]
     L.orc_get_m.argtypes = [C.c_void_p, _i32p]
     L.orc_get_m_r.argtypes = [C.c_void_p, _i32p]
@@ -237,6 +244,46 @@ class OracleModel:
     def anneal(self, schedule, kwargs, duration, steps_await):
         kw = list(kwargs) + [0.0, 0.0]
         return self.L.orc_anneal(self.h, SCHEDULES[schedule], kw[0], kw[1], duration, steps_await)
+
+    # the holds of include/bisbm.h in the Philox-mode MH step (oracle/bisbm_oracle.h); the tables are copied
+    def clamp(self, mask=None):
+        """mask: n entries, non-zero = clamped; None clears"""
+        if mask is None:
+            self.L.orc_set_clamp(self.h, None)
+            return
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        assert mask.shape == (self.n,)
+        self.L.orc_set_clamp(self.h, _p(mask, _u8p))
+
+    def constrain(self, class_of_node=None, allowed=None):
+        """class_of_node: n class ids; allowed: [n_classes][K], non-zero = allowed; None clears"""
+        if class_of_node is None or allowed is None or len(allowed) == 0:
+            self.L.orc_set_constraints(self.h, 0, None, None)
+            return
+        cls = np.ascontiguousarray(class_of_node, dtype=np.uint8)
+        tab = np.ascontiguousarray(np.asarray(allowed) != 0, dtype=np.uint8)
+        assert cls.shape == (self.n,) and tab.ndim == 2 and tab.shape[1] == self.K and int(cls.max()) < tab.shape[0]
+        self.L.orc_set_constraints(self.h, tab.shape[0], _p(cls, _u8p), _p(tab, _u8p))
+
+    def set_fields(self, class_of_node=None, field=None):
+        """class_of_node: n class ids; field: [n_classes][K] of f64; None clears"""
+        if class_of_node is None or field is None or len(field) == 0:
+            self.L.orc_set_fields(self.h, 0, None, None)
+            return
+        cls = np.ascontiguousarray(class_of_node, dtype=np.uint8)
+        tab = np.ascontiguousarray(field, dtype=np.float64)
+        assert cls.shape == (self.n,) and tab.ndim == 2 and tab.shape[1] == self.K and int(cls.max()) < tab.shape[0]
+        self.L.orc_set_fields(self.h, tab.shape[0], _p(cls, _u8p), _p(tab, _f64p))
+
+    @property
+    def last_margin(self):
+        return self.L.orc_last_margin(self.h)
+
+    def hold_counts(self):
+        """over the last anneal: dict(clamped steps, barred same-type targets, fielded steps, decisions the field turned)"""
+        out = (C.c_uint64 * 4)()
+        self.L.orc_hold_counts(self.h, out)
+        return dict(clamped=out[0], barred=out[1], fielded=out[2], turned=out[3])
 
     def _refresh_k(self):
         self.ka, self.kb = self.L.orc_ka(self.h), self.L.orc_kb(self.h)

@@ -16,6 +16,7 @@ import oracle_lib as O
 import test_gpu_constraints as TC
 from test_gpu_constraints import ENUM_LISTS, FIRST_ID, INF, LOW_T, SEED, _code, _enumeration, _one_start, _pair_rows, _same_state, _state
 from test_gpu_heatbath import _assert_state_is_a_rebuild, _bits, _case, _model, _refused
+from mh_replay import mh_replay_sweep as _mh_replay_sweep  # (the shared host replay of one held MH sweep)
 from test_tempering import exchange_round, philox, u53
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -310,42 +311,6 @@ MH_BASE = 3
 
 def _mh_field(na, nb, ka, kb):
     return np.arange(na + nb) % 4, _table(4, ka + kb, 7, scale=1.5)
-
-
-def _mh_replay_sweep(probe, lab, cls, field, gid, sweep, T, na, nb, ka, seed, exp):
-    """One MH sweep under fields on the host, from the oracle's pieces: the proposal from propose_philox with the step's draws,
-    dS and the Hastings factor from transition_ratio, dE = dS + (f[s] - f[r]), the accept uniform of the step.  `probe` is an
-    oracle model used for its state alone.  Returns (labels, accepted, the smallest relative distance of the two sides of an accept
-    test, whether some decision differs from the one dS alone gives)."""
-    n = na + nb
-    lab = lab.copy()
-    Tf = float(np.float32(T))
-    probe.set_memberships(lab.astype(np.uint32))
-    probe.init_bisbm()
-    accepted, margin, differs = 0, INF, False
-    for p, v in enumerate(_visit(gid, sweep, na, nb, seed)):
-        A, Bw = philox(seed, gid, 0, sweep * n + p), philox(seed, gid, 1, sweep * n + p)
-        s = int(probe.propose_philox(v, u53(A[0], A[1]), u53(A[2], A[3]), u53(Bw[0], Bw[1])))
-        r = int(lab[v])
-        u_acc = u53(Bw[2], Bw[3])
-        if s == r:
-            accepted += int(probe.n_r()[r] > 1)  # (u < 1: accepted unless the veto of a node alone in its block)
-            continue
-        if (s < ka) != (r < ka):
-            continue
-        dS, accu_r = probe.transition_ratio(v, s)
-        f = field[cls[v]]
-        dE = dS + (float(f[s]) - float(f[r]))
-        rhs = accu_r * exp(-dE * (1.0 / Tf))
-        plain = u_acc < accu_r * exp(-dS * (1.0 / Tf))
-        margin = min(margin, abs(u_acc - rhs) / max(u_acc, rhs))
-        differs = differs or (plain != (u_acc < rhs))
-        if u_acc < rhs and probe.n_r()[r] > 1:
-            lab[v] = s
-            accepted += 1
-            probe.set_memberships(lab.astype(np.uint32))
-            probe.init_bisbm()
-    return lab, accepted, margin, differs
 
 
 def _mh_replay(exp, device=None):

@@ -2,12 +2,13 @@
 
 A handle with clamped nodes and / or block constraints runs its MH sweeps on the held instances of the production kernel: the
 feeder wave hands every step an allowed word (csrc/bisbm_held_word.hpp) and the stepping wave bars the targets it does not hold,
-one or two steps per pass.  The chain is the chain the generic kernel runs for the same clamp and constraints -- the tie to the
-oracle is tests/test_gpu_clamp.py and tests/test_gpu_constraints.py, which force no kernel; here the two kernels are tied to each
-other.  Every comparison: handle A with nothing forced, handle B under BISBM_FORCE_GENERIC=1, three chains with first chain id
-5, the same start, hold and calls; per chain the labels, m, m_r, n_r, eta and both columns of last_counts() are equal integer
-for integer, the running sum of accepted dS (BISBM_KEEP_SUM=1) agrees as tests/test_gpu_parity.py asks of the production kernel
-(1e-9 of the sum plus 1e-12 of the description length), and A reports two steps per pass where B reports one."""
+one or two steps per pass.  The chain is the chain the generic kernel runs for the same clamp and constraints -- the tie of either
+kernel to the oracle is tests/test_gpu_held_oracle.py (tests/test_gpu_clamp.py and tests/test_gpu_constraints.py, which force no
+kernel, check the prefix property on the device); here the two kernels are tied to each other under every switch.  Every
+comparison: handle A with nothing forced, handle B under BISBM_FORCE_GENERIC=1, three chains with first chain id 5, the same
+start, hold and calls; per chain the labels, m, m_r, n_r, eta and both columns of last_counts() are equal integer for integer, the
+running sum of accepted dS (BISBM_KEEP_SUM=1) agrees as tests/test_gpu_parity.py asks of the production kernel (1e-9 of the sum
+plus 1e-12 of the description length), and A reports two steps per pass where B reports one."""
 import importlib
 import os
 
@@ -94,26 +95,30 @@ def _half_lists(name, seed):
     raise AssertionError("no admissible start for %s" % name)
 
 
-def _handle(name, hold, mask=None, warm=0):
+def _handle(name, hold, mask=None, warm=0, seed=SEED, fields=None):
     """hold: "clamp" -- shuffle_bisbm (and `warm` unheld sweeps), then a random 30 % clamp (or `mask`); "constraints" -- the
-    round-robin start of _half_lists under its table; "both" -- that start and table, and the clamp on top"""
+    round-robin start of _half_lists under its table; "both" -- that start and table, and the clamp on top; "none" -- the start of
+    "clamp" without the clamp.  seed: the handle's Philox seed.  fields: (class_of_node, field), set after everything else
+    (tests/test_gpu_held_oracle.py)"""
     (rowptr, col), na, nb, ka, kb, eps = _case(name)
     n = na + nb
     if mask is None:
         mask = np.random.default_rng(77).random(n) < 0.3
-    if hold == "clamp":
-        m = _model(name, CHAINS, first_chain_id=FIRST_ID)
+    if hold in ("clamp", "none"):
+        m = _model(name, CHAINS, seed=seed, first_chain_id=FIRST_ID)
         m.shuffle_bisbm()
         if warm:
             m.run_sweeps(warm)
     else:
         cls, allowed, start = _half_lists(name, 3)
-        m = _model(name, CHAINS, first_chain_id=FIRST_ID, labels=start)
+        m = _model(name, CHAINS, seed=seed, first_chain_id=FIRST_ID, labels=start)
         m.init_bisbm()
         m.constrain(cls, allowed)
     if hold in ("clamp", "both"):
         m.clamp(mask)
         assert int(m.clamped().sum()) == int(mask.sum())
+    if fields is not None:
+        m.set_fields(*fields)
     return m
 
 
