@@ -200,6 +200,7 @@ ABI = {
     "bisbm_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bisbm_last_sweep_timing": (C.c_int, [C.c_void_p, _f64p, _u64p]),
     "bisbm_last_pass_steps": (C.c_int, [C.c_void_p, _u32p]),
+    "bisbm_last_eta_plan": (C.c_int, [C.c_void_p, _u32p]),
     "bisbm_debug_log_q": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_size_t, C.c_int, _f64p]),
     "bisbm_io_read_edge_list": (C.c_long, [C.c_char_p, C.POINTER(_u64p), C.POINTER(_u64p)]),
     "bisbm_io_read_memberships": (C.c_long, [C.c_char_p, C.POINTER(_u32p)]),
@@ -794,6 +795,13 @@ class BlockModel:
         k = C.c_uint32()
         self._check(self._L.bisbm_last_pass_steps(self._h, C.byref(k)))
         return k.value
+
+    def last_eta_plan(self):
+        """(eta_in_lds, eta_w, eta_lo_a, eta_lo_b) of the last MH launch: all of eta in LDS, or the production kernel's window of
+        eta_w degrees from eta_lo_a / eta_lo_b per type (rows of 1 to 255 entries inside it take the hot step); never changes the chain."""
+        out = (C.c_uint32 * 4)()
+        self._check(self._L.bisbm_last_eta_plan(self._h, out))
+        return tuple(int(x) for x in out)
 
     # -- marginals (README.md:49-53)
     @property

@@ -49,6 +49,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
             h->last_kernel_ms = std::max(h->last_kernel_ms, g->last_kernel_ms);
             h->last_updates += g->last_updates;
             h->last_pass_steps = gi == 0 ? g->last_pass_steps : std::max(h->last_pass_steps, g->last_pass_steps);
+            if (gi == 0) std::copy(g->last_eta_plan, g->last_eta_plan + 4, h->last_eta_plan);
             if (acc_rate_out)
                 for (size_t j = 0; j < rates[gi].size(); ++j) acc_rate_out[g->ridx[j]] = rates[gi][j];
         }
@@ -192,6 +193,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
         lds = (lds + 15) & ~(size_t)15;
     }
     if (lds > 160 * 1024) return fail(h, BISBM_ERR_UNSUPPORTED, "chain state needs %zu B of LDS (> 160 KiB)", lds);
+    h->last_eta_plan[0] = p.eta_in_lds, h->last_eta_plan[1] = p.eta_w, h->last_eta_plan[2] = p.eta_lo_a, h->last_eta_plan[3] = p.eta_lo_b;
 
     p.simd_claims = nullptr;
     p.fixed_stepping_wave = 0;

@@ -593,6 +593,12 @@ int bisbm_last_pass_steps(bisbm_handle h, uint32_t* steps_per_pass) {
     return BISBM_OK;
 }
 
+int bisbm_last_eta_plan(bisbm_handle h, uint32_t out[4]) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (out) std::copy(h->last_eta_plan, h->last_eta_plan + 4, out);
+    return BISBM_OK;
+}
+
 int bisbm_debug_log_q(bisbm_handle h, const int32_t* n, const int32_t* k, size_t count, int fast, double* out) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (!h->devs.empty()) {

@@ -9,6 +9,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <iostream>
@@ -703,6 +704,12 @@ public:
         std::vector<uint32_t> lab(n_);
         check(bisbm_marginals_map(h_, lab.data()));
         return uint_vec_t(lab.begin(), lab.end());
+    }
+    // {eta_in_lds, eta_w, eta_lo_a, eta_lo_b} of the last MH launch (include/bisbm.h, bisbm_last_eta_plan)
+    std::array<uint32_t, 4> last_eta_plan() const {
+        std::array<uint32_t, 4> out{};
+        check(bisbm_last_eta_plan(h_, out.data()));
+        return out;
     }
     bisbm_handle handle() const { return h_; }
     uint32_t n_chains() const { return n_chains_; }

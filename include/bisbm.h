@@ -31,7 +31,8 @@ extern "C" {
  *    (bisbm_population_*), node conditionals (bisbm_conditionals_*), heat-bath sweeps and greedy polishing
  *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp), chain traces (bisbm_trace_*), round recipes
  *    (bisbm_tempering_run_rounds, bisbm_tempering_rung_stats, bisbm_rounds_population_run), held conditionals and the least
- *    settled queries (bisbm_held_conditionals_*, bisbm_least_settled_topk, bisbm_debug_log).  Additions only. */
+ *    settled queries (bisbm_held_conditionals_*, bisbm_least_settled_topk, bisbm_debug_log), the eta plan of the last launch
+ *    (bisbm_last_eta_plan).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -1203,6 +1204,15 @@ int bisbm_last_sweep_timing(bisbm_handle h, double *kernel_ms, uint64_t *node_up
  * measured speed of earlier launches; the chain does not depend on it.  Diagnostic: no
  * counterpart in the reference. */
 int bisbm_last_pass_steps(bisbm_handle h, uint32_t *steps_per_pass);
+
+/* Where the last Metropolis-Hastings launch kept eta: out = {eta_in_lds, eta_w, eta_lo_a, eta_lo_b}.  eta_in_lds = 1: all of eta
+ * was in LDS (eta_w = 0), and on the production kernel no row of 1 to 255 entries left the hot step for eta's sake.  Otherwise the production
+ * kernel kept a window of eta_w consecutive degrees per type in LDS, [eta_lo_a, eta_lo_a + eta_w) for type a and the same from
+ * eta_lo_b for type b; a row of 1 to 255 entries took the hot step if its degree lay inside its type's window and the general
+ * step otherwise.  The generic kernel has no window: its eta_in_lds and three zeros.  A handle over several devices or shape
+ * groups reports its first member's plan.  Diagnostic (tests tell from it which route a row took): no counterpart in the
+ * reference; the chain does not depend on it. */
+int bisbm_last_eta_plan(bisbm_handle h, uint32_t out[4]);
 
 /* Device numerics probe (tests): evaluates log_q(n[i], k[i]) on the device (int_part.hh:27-37).
  * fast = 0: the literal evaluation (mt19937-compat mode, entropy()); fast = 1: the Philox-mode

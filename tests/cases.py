@@ -95,6 +95,138 @@ HEATBATH_CASES = {c[0]: c for c in [
     ("hb_eta_in_hbm", 300, 200, 3000, 10, 10, 1.0, 1, 0),
 ]}
 
+# ------------------------------------------------------------------ row shapes (tests/test_row_shapes.py, tests/test_gpu_row_shapes.py)
+# The production sweep kernel's edges along the length and the make-up of an adjacency row (kRowCap = 255, byte k_v counters, ids
+# read four at a time and sixteen a round, the eta window).  Outside CASES, so the GPU-vs-oracle matrix does not grow by them.
+ROW_LADDER = (1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 254, 255, 256, 257, 300)
+ROW_ISOLATED = 2  # rows of no entries per type, as random_graph makes them
+ROW_BAND = tuple(range(128, 192, 4))  # 20 + 27, sparse graph: rows of 128 .. 188 entries in one block, side by side in the ids (below)
+ROW_BALLAST = 8   # rows of 250 entries per type in the dense graphs: with them more rows lie in a window that ends at 255 than in one that ends below
+# id: na, nb, ka, kb, graph seed, the last rows of col[] in the sparse and in the dense graph, the dense graph's plain degrees.
+# The dense graph exists where the production kernel keeps a window of eta in LDS (every shape but 8 + 7): its plain degrees are
+# chosen so that the window, which is placed where most nodes are, ends at 255.
+ROW_SHAPES = {
+    "8+7": (331, 299, 8, 7, 41, "255", None, None),
+    "16+13": (601, 549, 16, 13, 42, "1", "3", (36, 44)),
+    "20+27": (843, 811, 20, 27, 43, "3", "255", (160, 230)),
+    "40+33": (1211, 1109, 40, 33, 44, "1", "255", (140, 200)),
+    "64+50": (1223, 1217, 64, 50, 45, "3", "255", (212, 228)),
+}
+
+
+def _matched_edges(rng, ids_a, deg_a, block_a, ids_b, deg_b, block_b, ka, kb, p_in):
+    """Edges between two node lists with exactly the given degrees (the sums are equal): every stub of a type-a node asks for a
+    type-b block -- the partner a_block * kb // ka of its own with probability p_in, else a uniform one -- and gets a stub of it
+    while the block has one; the stubs left over on both sides are paired at random.  Multi-edges are kept."""
+    pa, pb = rng.permutation(int(deg_a.sum())), rng.permutation(int(deg_b.sum()))
+    sa, own = np.repeat(ids_a, deg_a)[pa], np.repeat(block_a, deg_a)[pa]
+    want = np.where(rng.random(len(sa)) < p_in, own * kb // ka, rng.integers(0, kb, len(sa)))
+    sb, sb_blk = np.repeat(ids_b, deg_b)[pb], np.repeat(block_b, deg_b)[pb]
+    out_b = np.full(len(sa), -1, dtype=np.int64)
+    left = []
+    for t in range(kb):
+        asks, has = np.flatnonzero(want == t), sb[sb_blk == t]
+        k = min(len(asks), len(has))
+        out_b[asks[:k]] = has[:k]
+        left.append(has[k:])
+    rest = np.flatnonzero(out_b < 0)
+    out_b[rest] = rng.permutation(np.concatenate(left))
+    return sa.astype(np.uint64), out_b.astype(np.uint64)
+
+
+def row_shape_graph(sid, dense=False):
+    """The graph of a row of ROW_SHAPES.  Plain nodes form a planted graph with prescribed degrees (1 + Poisson(5): mean about 6;
+    dense: uniform over the shape's range); every special node of one type lies apart from the others (all but the band) and its edges go to plain
+    nodes of the other type only, so it keeps its degree exactly:
+      * the ladder: one node of every degree of ROW_LADDER (dense: up to 255), to uniform plain nodes;
+      * concentrated rows, whose neighbours are dealt out over the plain nodes of planted blocks of the other type (local block
+        numbers): "one_block" 255 entries in the other type's last block, "half" 128 entries in block 2, "split" 128 + 127 in
+        blocks 4 and 5, which share a word of the kernel's byte counters, and "copies": the type-a node and the type-b node of this
+        name share one edge 255 times (the one special row whose neighbour is no plain node);
+      * 20 + 27, sparse graph: the band, one row of every length of ROW_BAND with all its entries in block 3, at the end of each type's
+        ids: bytes with the top bit set and every pattern of the bits below it, in rows that the sweep's visit order (local in the
+        ids) often puts into one pass -- under the planted labels a mover with 128 .. 188 edges in a column is followed within the
+        pass by a step that reads that column;
+      * ROW_ISOLATED rows of no entries, and in the dense graph ROW_BALLAST rows of 250 entries to uniform plain nodes;
+      * type b ends with a row of 1, 3 or 255 entries ("255": behind a row of 2), the last row of col[].
+    Returns dict(rowptr, col, labels, na, nb, ka, kb, special={type: {name: node}}, ladder=the degrees)."""
+    na, nb, ka, kb, seed, end_sparse, end_dense, plain_range = ROW_SHAPES[sid]
+    end = end_dense if dense else end_sparse
+    rng = np.random.default_rng(seed + (500 if dense else 0))
+    ladder = tuple(d for d in ROW_LADDER if d <= 255 or not dense)
+    labels = O.contiguous_labels(na, nb, ka, kb).astype(np.int64)
+    names = ["ladder%d" % d for d in ladder] + ["one_block", "half", "split", "copies"] + ["isolated%d" % i for i in range(ROW_ISOLATED)]
+    names += ["ballast%d" % i for i in range(ROW_BALLAST if dense else 0)]
+    band = ROW_BAND if sid == "20+27" and not dense else ()
+    special, plain = {}, {}
+    for t, (first, size) in enumerate(((0, na), (na, nb))):
+        tail = ["band%d" % d for d in band] + {"a": [], "1": ["end"], "3": ["end"], "255": ["before_end", "end"]}["a" if t == 0 else end]
+        spread = size - len(tail) - 1
+        order = rng.permutation(len(names))  # (which special sits where: no run of the ladder along the ids)
+        special[t] = {names[j]: first + 1 + (i * spread) // len(names) for i, j in enumerate(order)}
+        for i, name in enumerate(tail):
+            special[t][name] = first + size - len(tail) + i
+        assert len(set(special[t].values())) == len(special[t])
+        plain[t] = np.setdiff1d(np.arange(first, first + size), np.array(list(special[t].values())))
+    deg = {}
+    for t in (0, 1):
+        if dense:
+            deg[t] = rng.integers(plain_range[0], plain_range[1] + 1, len(plain[t]))
+        else:
+            deg[t] = 1 + rng.poisson(5.0, len(plain[t]))
+    diff = int(deg[0].sum() - deg[1].sum())  # the two sums made equal on the longer side, one edge a node
+    t_fix = 1 if diff > 0 else 0
+    deg[t_fix] = deg[t_fix] + abs(diff) // len(deg[t_fix]) + (np.arange(len(deg[t_fix])) < abs(diff) % len(deg[t_fix]))
+    a, b = _matched_edges(rng, plain[0], deg[0], labels[plain[0]], plain[1], deg[1], labels[plain[1]] - ka, ka, kb, 0.8)
+    ea, eb = [a], [b]
+
+    def add(node, others):
+        others = np.asarray(others, dtype=np.uint64)
+        mine = np.full(len(others), node, dtype=np.uint64)
+        ea.append(mine if node < na else others)
+        eb.append(others if node < na else mine)
+
+    for t in (0, 1):
+        oth, k_oth, base_oth = plain[1 - t], (kb, ka)[t], (ka, 0)[t]
+        in_block = lambda blk: oth[labels[oth] - base_oth == blk]
+        deal = lambda blk, count: np.resize(rng.permutation(in_block(blk)), count)
+        for d in ladder:
+            add(special[t]["ladder%d" % d], rng.choice(oth, d))
+        for i in range(ROW_BALLAST if dense else 0):
+            add(special[t]["ballast%d" % i], rng.choice(oth, 250))
+        for d in band:
+            add(special[t]["band%d" % d], deal(3, d))
+        add(special[t]["one_block"], deal(k_oth - 1, 255))
+        add(special[t]["half"], deal(2, 128))
+        add(special[t]["split"], np.concatenate([deal(4, 128), deal(5, 127)]))
+        if "end" in special[t]:
+            add(special[t]["end"], rng.choice(oth, int(end)))
+        if "before_end" in special[t]:
+            add(special[t]["before_end"], rng.choice(oth, 2))
+    add(special[0]["copies"], np.full(255, special[1]["copies"]))
+    rowptr, col = O.edge_to_csr(np.concatenate(ea), np.concatenate(eb), na + nb)
+    return dict(rowptr=rowptr, col=col, labels=labels.astype(np.uint32), na=na, nb=nb, ka=ka, kb=kb, special=special, ladder=ladder,
+                end=end, dense=dense)
+
+
+def row_shape_rows(g):
+    """[(type, name, node, degree)] of the ladder, the concentrated rows and the last rows of col[] of a row-shape graph: the rows the tests ask about"""
+    out = []
+    for t in (0, 1):
+        for name, v in sorted(g["special"][t].items(), key=lambda kv: kv[1]):
+            if not name.startswith(("isolated", "ballast", "band")):
+                out.append((t, name, v, int(g["rowptr"][v + 1] - g["rowptr"][v])))
+    return out
+
+
+def row_k_v(g, v, labels=None):
+    """k_v of node v in numpy: how many entries of its row lie in every block of the other type"""
+    labels = g["labels"] if labels is None else labels
+    k_oth, base = (g["kb"], g["ka"]) if v < g["na"] else (g["ka"], 0)
+    row = g["col"][int(g["rowptr"][v]):int(g["rowptr"][v + 1])]
+    return np.bincount(np.asarray(labels)[row].astype(np.int64) - base, minlength=k_oth)
+
+
 LOG_Q_TIERS = ("table", "closed", "closed2", "mid", "low", "literal")
 
 
