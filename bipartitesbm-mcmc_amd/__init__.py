@@ -63,6 +63,8 @@ RESHUFFLE_NONE = 0xFFFFFFFF
 TRACE_S, TRACE_H = 0, 1
 # bisbm_block_sums_set: keep the sums; also keep every counted chain's aligned tables of the last sample
 BLOCK_SUMS, BLOCK_KEEP_LAST = 1, 2
+# bisbm_last_sweep_route (BISBM_ROUTE_*): the production kernel ran; the launch carried a clamp or constraints; it carried fields
+ROUTE_PRODUCTION, ROUTE_HELD, ROUTE_FIELDS = 1, 2, 4
 _RNG = {"philox": RNG_PHILOX, "mt19937-compat": RNG_MT19937_COMPAT, "compat": RNG_MT19937_COMPAT}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -201,6 +203,7 @@ ABI = {
     "bisbm_last_sweep_timing": (C.c_int, [C.c_void_p, _f64p, _u64p]),
     "bisbm_last_pass_steps": (C.c_int, [C.c_void_p, _u32p]),
     "bisbm_last_eta_plan": (C.c_int, [C.c_void_p, _u32p]),
+    "bisbm_last_sweep_route": (C.c_int, [C.c_void_p, _u32p]),
     "bisbm_debug_log_q": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_size_t, C.c_int, _f64p]),
     "bisbm_io_read_edge_list": (C.c_long, [C.c_char_p, C.POINTER(_u64p), C.POINTER(_u64p)]),
     "bisbm_io_read_memberships": (C.c_long, [C.c_char_p, C.POINTER(_u32p)]),
@@ -796,6 +799,13 @@ class BlockModel:
         self._check(self._L.bisbm_last_pass_steps(self._h, C.byref(k)))
         return k.value
 
+    def last_route(self):
+        """ROUTE_* bits of the last MH launch: ROUTE_PRODUCTION (the production kernel ran, not the generic one), ROUTE_HELD (it
+        carried a clamp or constraints), ROUTE_FIELDS (it carried block fields); 0 before any launch.  Never changes the chain."""
+        r = C.c_uint32()
+        self._check(self._L.bisbm_last_sweep_route(self._h, C.byref(r)))
+        return r.value
+
     def last_eta_plan(self):
         """(eta_in_lds, eta_w, eta_lo_a, eta_lo_b) of the last MH launch: all of eta in LDS, or the production kernel's window of
         eta_w degrees from eta_lo_a / eta_lo_b per type (rows of 1 to 255 entries inside it take the hot step); never changes the chain."""
@@ -927,7 +937,7 @@ class BlockModel:
         blocks of the other type are ignored).  With Phi = the sum of phi[class(v)][b_v] over the nodes every sampler targets
         exp(-beta (S + Phi)): a node's prior weight for block s is exp(-phi_s) (fields_from_weights builds the pair from
         weights).  A new call replaces the fields, a table of zeros is clear_fields().  Independent of clamp() and constrain().
-        While fields are set MH sweeps run the generic kernel (slower; README.md), get_entropy() advances by dS + dPhi, polish()
+        While fields are set MH sweeps run the production kernel's fielded instances, one step per pass (README.md), get_entropy() advances by dS + dPhi, polish()
         certifies a minimum of S + Phi, replica exchange and population annealing weigh S + Phi, and agg_merge is refused;
         entropy() stays the description length."""
         cls = np.asarray(class_of_node)

@@ -35,6 +35,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
          "-falign-loops=64"]
 
 
+# the units bisbm_sweep_fast.hip is compiled as (BISBM_FAST_PART): 0 .. 3 the production kernels, 4 the dispatch, 5 .. 8 the held
+# kernels, 9 .. 12 the fielded kernels
+FAST_PARTS = tuple(range(13))
+
+
 def hipcc():
     for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
         if cand and os.path.exists(cand):
@@ -94,13 +99,13 @@ def compile_library(out, extra=(), verbose=False, jobs=None):
     cc = hipcc()
     objdir = tempfile.mkdtemp(prefix="bisbm_obj_")
     try:
-        # the production kernel's variants: four units of six kernels (parts 0 .. 3), the dispatch (4) and four units of the two
-        # held kernels each (5 .. 8) (BISBM_FAST_PART, bisbm_sweep_fast.hip); a build with in-kernel stamps or pass counts keeps
+        # the production kernel's variants: four units of six kernels (parts 0 .. 3), the dispatch (4), four units of the two
+        # held kernels each (5 .. 8) and four of the two fielded kernels each (9 .. 12) (BISBM_FAST_PART, bisbm_sweep_fast.hip); a build with in-kernel stamps or pass counts keeps
         # them in one unit (its counters are one device symbol)
         units = []
         for src in SOURCES:
             if src == "bisbm_sweep_fast.hip" and not any("BISBM_STAMPS" in f or "BISBM_PASS_COUNTS" in f for f in extra):
-                units += [(src, ["-DBISBM_FAST_PART=%d" % part], "%s.part%d.o" % (src, part)) for part in range(9)]
+                units += [(src, ["-DBISBM_FAST_PART=%d" % part], "%s.part%d.o" % (src, part)) for part in FAST_PARTS]
             else:
                 units.append((src, [], src + ".o"))
 

@@ -49,7 +49,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
             h->last_kernel_ms = std::max(h->last_kernel_ms, g->last_kernel_ms);
             h->last_updates += g->last_updates;
             h->last_pass_steps = gi == 0 ? g->last_pass_steps : std::max(h->last_pass_steps, g->last_pass_steps);
-            if (gi == 0) std::copy(g->last_eta_plan, g->last_eta_plan + 4, h->last_eta_plan);
+            if (gi == 0) std::copy(g->last_eta_plan, g->last_eta_plan + 4, h->last_eta_plan), h->last_route = g->last_route;
             if (acc_rate_out)
                 for (size_t j = 0; j < rates[gi].size(); ++j) acc_rate_out[g->ridx[j]] = rates[gi][j];
         }
@@ -109,12 +109,19 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     // clamp always take the production kernel.
     p.clamp = h->clamp.mask_or_null();
     p.cn_class = h->constraints.class_or_null(), p.cn_bits = h->constraints.bits_or_null();
-    // While block fields are set the generic kernel runs: it is the one that adds the field to a step's dS ("Block fields")
+    // Block fields ("Block fields") run on the production kernel as well: its fielded instances add f[s] - f[r] to a step's finished
+    // dS, one step per pass, and take a clamp and constraints beside the field through the same allowed word (the clamp-share rule
+    // above holds for them as it stands).  BISBM_FIELD_FAST=0 pins the generic kernel for fielded handles only, =1 the production
+    // kernel (A/B runs, tests).
     p.fl_class = h->fields.class_or_null(), p.fl_field = h->fields.field_or_null();
     const bool held = p.clamp != nullptr || p.cn_bits != nullptr;
+    const bool fielded = p.fl_field != nullptr;
     bool held_fast = (double)h->clamp.n_clamped <= kHeldFastMaxClampShare * (double)h->n;
     if (const char* hf = getenv("BISBM_HELD_FAST")) held_fast = hf[0] == '1' ? true : hf[0] == '0' ? false : held_fast;
-    const bool fast = h->rng_mode == BISBM_RNG_PHILOX && h->ka <= 64 && h->kb <= 64 && !h->wide && !(force && force[0] == '1') && (!held || held_fast) && !p.fl_field;
+    bool field_fast = true;
+    if (const char* ff = getenv("BISBM_FIELD_FAST")) field_fast = ff[0] != '0';
+    const bool fast = h->rng_mode == BISBM_RNG_PHILOX && h->ka <= 64 && h->kb <= 64 && !h->wide && !(force && force[0] == '1') && (!held || held_fast) &&
+                      (!fielded || field_fast);
     // Temperatures of the pow / log schedules are evaluated with the host libm (the reference's own values) into a table of
     // at most kTabCap steps.  The generic kernel evaluates pow / log itself beyond it; the production kernel holds no
     // pow / log at all: a longer call runs as several launches of whole sweeps, each with the slice of the table it covers
@@ -153,7 +160,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     p.vlist_in_lds = 0;
     p.eta_w = p.eta_lo_a = p.eta_lo_b = 0;
     if (fast) {
-        lds = sweep_fast_lds_bytes(h->ka, h->kb, h->maxdeg, false, 0, held);
+        lds = sweep_fast_lds_bytes(h->ka, h->kb, h->maxdeg, false, 0, held, fielded);
         p.eta_in_lds = (lds + eta_bytes <= 40 * 1024) ? 1 : 0;
         if (!p.eta_in_lds) {
             // eta does not fit beside the rest (many blocks and / or long rows): the kernel keeps a window of it in LDS -- the
@@ -176,7 +183,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
                 (type ? p.eta_lo_b : p.eta_lo_a) = best_lo;
             }
         }
-        lds = sweep_fast_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0, p.eta_w, held);
+        lds = sweep_fast_lds_bytes(h->ka, h->kb, h->maxdeg, p.eta_in_lds != 0, p.eta_w, held, fielded);
     } else {
         // generic kernel: m quadrant (odd row stride), m_r, n_r, k_v histogram, staged rows; compat adds the
         // two mt19937 states and (small graphs) the visit list
@@ -200,6 +207,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     {
         const char* single = getenv("BISBM_SINGLE_STEPS");  // =1: one step per pass in every variant (A/B checks, tests)
         p.pair_steps = !single ? 3u : single[0] == '1' ? 0u : single[0] == '2' ? 1u : single[0] == '4' ? 2u : 3u;  // =2 / =4: at most two / four per pass
+        if (fast && fielded) p.pair_steps = 0u;  // (the fielded instances hold the one-step pass only)
     }
     p.predict_skew = predict_skew_from_env(getenv("BISBM_PREDICT_SKEW"));  // =n: every n-th step of a chunk gets a wrong predicted target (tests)
     if (fast) {
@@ -235,6 +243,10 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
     // (BISBM_KEEP_SUM=1: every launch keeps the sum of its own dS values, for the tests that compare exactly that with the change
     // of the description length)
     p.keep_sum = (getenv("BISBM_KEEP_SUM") && getenv("BISBM_KEEP_SUM")[0] == '1') ? 1u : 0u;
+    // A fielded production launch always keeps the sum in the kernel: under fields it follows S + Phi ("Block fields" 4.), so every
+    // accepted dE is added where it is made -- the same additions in the same order as the generic kernel's, and no second
+    // evaluation of Phi around the call.
+    if (fast && fielded) p.keep_sum = 1u;
     const bool sum_from_entropy = fast && p.keep_sum == 0u && !sweep_fast_tracks_minimum(schedule, p.kw0, steps_await, duration_steps);
     if (sum_from_entropy) {
         if (!h->d_ent_prev) HIPCHK(h, dalloc(&h->d_ent_prev, h->n_chains));
@@ -311,6 +323,7 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
                                  : (h->ka <= 8 && h->kb <= 8 && d >= 3u) ? 8u
                                  : (h->ka <= 32 && h->kb <= 32 && d >= 2u) ? 4u
                                  : p.pair_steps != 0u ? 2u : 1u;
+            h->last_route = (fast ? BISBM_ROUTE_PRODUCTION : 0u) | (held ? BISBM_ROUTE_HELD : 0u) | (fielded ? BISBM_ROUTE_FIELDS : 0u);
         }
         HIPCHK(h, hipEventRecord(h->ev0, h->stream));
         if (fast)
@@ -343,8 +356,8 @@ int bisbm::anneal_engine(bisbm_engine* h, int schedule, const float kwargs[2], u
             const uint32_t incumbent = h->passes.current();
             h->passes.record(depth, speed, acc_frac);
             if (getenv("BISBM_PASS_LOG"))
-                fprintf(stderr, "[bisbm passes] depth %u%s: %.3e updates/ms, accepted %.3f (before the launch: two %.3e, four %.3e, eight %.3e; incumbent %u -> %u)\n",
-                        depth, depth != incumbent && incumbent != 0u && h->passes.settled() ? " (a look)" : "", speed, acc_frac, before[0], before[1], before[2],
+                fprintf(stderr, "[bisbm passes] route %u, depth %u%s: %.3e updates/ms, accepted %.3f (before the launch: two %.3e, four %.3e, eight %.3e; incumbent %u -> %u)\n",
+                        h->last_route, depth, depth != incumbent && incumbent != 0u && h->passes.settled() ? " (a look)" : "", speed, acc_frac, before[0], before[1], before[2],
                         incumbent, h->passes.current());
         }
         if (segmented && fast && all_stopped) {  // every chain has returned (:96-98)

@@ -525,6 +525,7 @@ struct bisbm_engine {
     double last_kernel_ms = 0;
     uint64_t last_updates = 0;
     uint32_t last_pass_steps = 0;  // steps per pass of the last sweep launch (1, 2, 4, 8)
+    uint32_t last_route = 0;       // BISBM_ROUTE_* bits of the last MH sweep launch (a container: its first member's); 0: none yet
     uint32_t last_eta_plan[4] = {0, 0, 0, 0};  // {eta_in_lds, eta_w, eta_lo_a, eta_lo_b} of the last sweep launch (a container: its first member's)
     // which depth of pass (two / four / eight steps) the next production launch runs: chosen from the timed launches so far
     // (bisbm_pass_policy.hpp); belongs to a partition: init / shuffle / merges / splits reset it

@@ -593,6 +593,12 @@ int bisbm_last_pass_steps(bisbm_handle h, uint32_t* steps_per_pass) {
     return BISBM_OK;
 }
 
+int bisbm_last_sweep_route(bisbm_handle h, uint32_t* route) {
+    if (!h) return BISBM_ERR_INVALID_ARG;
+    if (route) *route = h->last_route;
+    return BISBM_OK;
+}
+
 int bisbm_last_eta_plan(bisbm_handle h, uint32_t out[4]) {
     if (!h) return BISBM_ERR_INVALID_ARG;
     if (out) std::copy(h->last_eta_plan, h->last_eta_plan + 4, out);

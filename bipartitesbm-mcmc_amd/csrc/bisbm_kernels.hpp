@@ -576,8 +576,9 @@ hipError_t launch_sum_from_entropy(ChainScalars* scalars, const double* before, 
 
 hipError_t launch_sweep(const SweepParams& p, int rng_mode, size_t lds_bytes, hipStream_t stream);
 hipError_t launch_sweep_fast(const SweepParams& p, size_t lds_bytes, hipStream_t stream);
-// held: a launch with clamped nodes and / or block constraints (two more hand-off words per step: 1 KiB)
-size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds, uint32_t eta_window, bool held = false);
+// held: a launch with clamped nodes and / or block constraints (two more hand-off words per step: 1 KiB); fielded: a launch with block
+// fields (the two held words and the field class: 1.5 KiB).  Unfielded launches get the bytes they always got.
+size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds, uint32_t eta_window, bool held = false, bool fielded = false);
 hipError_t launch_state_build(const BuildParams& p, hipStream_t stream);
 // `labels` is the byte base of the label array; wide: two-byte labels (label_stride counts labels in both cases)
 hipError_t launch_labels_broadcast(const uint32_t* src, uint8_t* labels, bool wide, size_t label_stride, uint32_t n,

@@ -185,7 +185,7 @@ int multi_anneal(bisbm_engine* h, int schedule, const float kwargs[2], uint64_t 
         h->last_kernel_ms = std::max(h->last_kernel_ms, d->last_kernel_ms);
         h->last_updates += d->last_updates;
         h->last_pass_steps = std::max(d == h->devs[0] ? 0u : h->last_pass_steps, d->last_pass_steps);
-        if (d == h->devs[0]) std::copy(d->last_eta_plan, d->last_eta_plan + 4, h->last_eta_plan);
+        if (d == h->devs[0]) std::copy(d->last_eta_plan, d->last_eta_plan + 4, h->last_eta_plan), h->last_route = d->last_route;
     }
     return rc;
 }

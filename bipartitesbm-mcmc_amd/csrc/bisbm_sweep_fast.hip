@@ -170,8 +170,9 @@ __device__ unsigned long long g_pass_counts[kPassCounts];
 constexpr uint32_t kHistStride = 68;  // bytes per k_v row: 64 counters + pad (17 dwords: odd, conflict-free)
 // v, row begin, degree, own label, pivot label, proposal word, packed hot-step inputs, accept uniform (2), pair word (the one-stage
 // four-steps kernels: the step's clash tests against the three steps before it, bisbm_pair_word.hpp; unused elsewhere)
-// A held launch (clamped nodes, block constraints) adds the step's allowed word (bisbm_held_word.hpp), low and high half.
-constexpr uint32_t hand_words(bool held) { return held ? 12u : 10u; }
+// A held launch (clamped nodes, block constraints) adds the step's allowed word (bisbm_held_word.hpp), low and high half; a fielded
+// launch (block fields) carries the allowed word too and adds the node's field class.
+constexpr uint32_t hand_words(bool held, bool fielded = false) { return fielded ? 13u : held ? 12u : 10u; }
 constexpr uint32_t kRowCap = 255;     // longest row the feeder walks (a k_v counter is a byte); longer rows: per-step side path
 
 // a double constant held in a vector register pair for the whole kernel (64-bit literals are not encodable
@@ -254,10 +255,15 @@ __device__ __forceinline__ void commit_four(At, uint32_t nst, Bits clash_bits, u
 // step_quad32 updates the register copies of m_r / n_r in one stage per pass, not one mover at a time (sweep_quad32_one_stage_kernel).
 // HD (without K16, Q32): a held launch -- p.clamp and / or p.cn_bits are set: the feeder hands every step its allowed word and the
 // stepping wave bars the targets it does not hold (sweep_fast_held_kernel; one and two steps per pass).
-template <bool EL, bool CT, bool K32, bool K16, bool K8, bool Q32, bool OS, bool HD = false>
+// FL (with HD): a fielded launch -- p.fl_field is set (include/bisbm.h, "Block fields"): the feeder hands every step its node's field
+// class too, and the step adds f[s] - f[r] of that class's row to its finished dS (sweep_fast_fielded_kernel).  One step per pass:
+// the hot step and the general step are all these instances hold.  A clamp and constraints beside the field come through the
+// allowed word, which is all ones where neither is set.
+template <bool EL, bool CT, bool K32, bool K16, bool K8, bool Q32, bool OS, bool HD = false, bool FL = false>
 __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
     static_assert(!HD || (!K16 && !K8 && !Q32 && !OS), "held launches run the passes of one and two steps");
-    constexpr uint32_t kHandWords = hand_words(HD);
+    static_assert(!FL || HD, "fielded launches carry the allowed word");
+    constexpr uint32_t kHandWords = hand_words(HD, FL);
     extern __shared__ __align__(16) uint32_t lds32[];
     const uint32_t chain = blockIdx.x;
     if (chain >= p.n_chains) return;
@@ -273,7 +279,8 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
     const uint32_t D = p.maxdeg + 1, S = kb | 1u;
     // the two-steps passes (step_pair, step_pair64) and the four-steps pass of the one-stage kernels (step_quad32 with OS) start
     // from a predicted inverse-CDF target (see prepare, step_pair and step_quad32)
-    constexpr bool kPredictTarget = !K16 && (!Q32 || OS) && (BISBM_PREDICT_TARGET != 0);
+    // (FL: one step per pass, which scans before it reads anything of its target -- nothing to predict)
+    constexpr bool kPredictTarget = !K16 && (!Q32 || OS) && !FL && (BISBM_PREDICT_TARGET != 0);
     // ... and there the feeder hands the four-steps pass its pair tests too (see prepare and step_quad32; the diagnostic build
     // with pass counters keeps clash_pairs, which its counters read)
 #ifdef BISBM_PASS_COUNTS
@@ -392,7 +399,8 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
     const bool quad32_mode = (uint32_t)__builtin_amdgcn_readfirstlane((Q32 && (!CT || T_const > 0.) && p.pair_steps > 1u) ? 1 : 0) != 0u;
     const bool oct_mode = (uint32_t)__builtin_amdgcn_readfirstlane((K8 && (!CT || T_const > 0.) && p.pair_steps > 2u) ? 1 : 0) != 0u;
     const uint32_t track_min =
-        (uint32_t)__builtin_amdgcn_readfirstlane((sweep_fast_tracks_minimum(p.schedule, p.kw0, p.steps_await, p.call_duration) || p.keep_sum != 0u) ? 1 : 0);
+        (uint32_t)__builtin_amdgcn_readfirstlane((sweep_fast_tracks_minimum(p.schedule, p.kw0, p.steps_await, p.call_duration) || p.keep_sum != 0u || FL) ? 1 : 0);
+    // (FL: a fielded launch always keeps its own sum -- it follows S + Phi, which the change of the description length does not give)
     // constants of the hot step (log_q closed form, accept filter)
     BISBM_PIN(c_l2e, 0x1.71547652b82fep+0);        // log2(e)
     double c_tol = 1e-5;                           // accept filter margin
@@ -538,6 +546,7 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                 uint32_t* const hand = hand_base + (c & 1u) * kHandWords * kWave;
                 uint32_t v_l = 0, beg_l = 0, deg_l = 0, r_l = 0, which_l = 0;
                 [[maybe_unused]] uint64_t allow_l = ~0ull;
+                [[maybe_unused]] uint32_t fcls_l = 0u;  // FL: the node's field class (idle lanes: class 0, a row that exists)
                 if (lane < cnt) {
                     v_l = node_base + order(vi0 + lane);
                     beg_l = p.rowptr[v_l];
@@ -550,6 +559,7 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                         const bool clamped = p.clamp != nullptr && p.clamp[v_l] != 0;
                         const uint32_t* const row = p.cn_bits != nullptr ? p.cn_bits + (uint32_t)p.cn_class[v_l] * kHeldRowWords : nullptr;
                         allow_l = held_word(clamped, row, own_base, k_own);
+                        if constexpr (FL) fcls_l = p.fl_class[v_l];
                     }
                     const U4 A = phx_draw(p.seed, chain_gid, PHX_STEP_A, sweeps_total * (uint64_t)n + node_base + vi0 + lane);
                     which_l = (uint32_t)(u53(A.x, A.y) * (double)deg_l);  // pivot neighbour, blockmodel.cc:619
@@ -613,6 +623,7 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                 if constexpr (HD) {
                     hand[10 * kWave + lane] = (uint32_t)allow_l;
                     hand[11 * kWave + lane] = (uint32_t)(allow_l >> 32);
+                    if constexpr (FL) hand[12 * kWave + lane] = fcls_l;
                 }
                 // Per-lane inputs of the hot step.  Bit 31 of the proposal word sends the step down the general path: uniform
                 // random target, a single own block, empty or over-long rows, T == 0, a degree outside the eta window.
@@ -697,6 +708,8 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                 // proposal word, the accept uniform and 1 / T are read from LDS at a per-half / per-row address by every pass.)
                 new_lab[lane] = 0xffu;
                 const uint32_t pack_l = hand[6 * kWave + lane];
+                [[maybe_unused]] uint32_t fcls_l = 0u;  // FL: the field classes of the chunk's nodes, lane = step (read per step with v_readlane)
+                if constexpr (FL) fcls_l = hand[12 * kWave + lane];
                 unsigned long long gen_mask = __builtin_amdgcn_ballot_w64((int32_t)hand[5 * kWave + lane] < 0);  // steps that need the general path
                 auto prop_of = [&](uint32_t step) -> uint32_t { return hand[5 * kWave + step]; };
                 auto u_acc_of = [&](uint32_t step) -> double { return *(const double*)&hand[7 * kWave + 2 * step]; };
@@ -847,6 +860,15 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     d = d + tail_lg * sign_tail1_of();
                     d = d + lq * sign_q1_of();
                     double dS = k_oth <= 32u ? butterfly_sum_low32(d) : butterfly_sum(d);
+                    // FL: dE = dS + (f[s] - f[r]) of the row of the node's class -- the difference first, then one add onto the finished
+                    // dS ("Block fields" 1.).  r == s keeps 0, a cross-type or barred target keeps its verdict: nothing is added there.
+                    // (the rare path: the two entries straight from the table, as mh_step of the generic kernel reads them)
+                    if constexpr (FL) {
+                        if (!same && !cross) {
+                            const double* const f = p.fl_field + (size_t)handed(12) * K;
+                            dS = dS + (f[s] - f[r]);
+                        }
+                    }
                     // accept (:47-61): T == 0: dS < 0;  else u < exp(-dS/T) accu1/accu0
                     bool accept;
                     if (T == 0.)
@@ -966,6 +988,15 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                         allow_lo_v = hand[10 * kWave + q];
                         if (!K32) allow_hi_v = hand[11 * kWave + q];
                     }
+                    // FL: the own-type part of the field row of the node's class, lane l <-> own block l: one coalesced read of at most
+                    // 512 B (the table stays in L2) that goes out first, so that nothing waits for it alone; f[s] and f[r] are then
+                    // cross-lane reads at scalar indices -- no memory access between the target and the accept line.  Lanes past
+                    // k_own do not index the table (the last class's row ends the allocation).
+                    [[maybe_unused]] double f_l = 0.;
+                    if constexpr (FL) {
+                        const double* const f_own = p.fl_field + (size_t)readlane(fcls_l, q) * K + own_base;
+                        if (lane < k_own) f_l = f_own[lane];
+                    }
                     // the two lgamma gathers that only need row r go out now: their latency runs under the proposal
                     // Lanes with k == 0 (idle lanes included) contribute exact zeros to all three sums whatever m is, so
                     // they all read table entry 1: a gather costs per distinct address, not per lane
@@ -1044,7 +1075,9 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     double d = (L1 + L2) - (L3 + L4);
                     d = d + tail_lg * sign_tail1_of();  // scalar terms folded into leaves 0..7 / 0..3, see step_general
                     d = d + lq * sign_q1_of();
-                    const double dS = K32 ? butterfly_sum_low32(d) : butterfly_sum(d);
+                    double dS = K32 ? butterfly_sum_low32(d) : butterfly_sum(d);
+                    // FL: dE = dS + (f[s] - f[r]), the difference first, then one add; dE stands where dS stood from here on
+                    if constexpr (FL) dS = dS + (readlane(f_l, s_loc) - readlane(f_l, r_loc));
                     FSTAMP_STEP(6);
                     if (!CT && T == 0.) {  // the greedy tail of a cooling schedule (:49-50): dS < 0 decides
                         if (!(dS < 0.) || n_r_r == 1) return;
@@ -2023,7 +2056,9 @@ __device__ __forceinline__ void sweep_fast_body(const SweepParams& p) {
                     }
                     acc_l0 += (unsigned long long)acc_chunk;
                 };
-                if constexpr (!K32) {  // more than 32 blocks of a type: step_pair64 is the only hot step this variant holds (registers)
+                if constexpr (FL) {  // one step per pass, and the sum is always kept (see track_min)
+                    for (uint32_t q = 0; q < cnt; ++q) step(std::true_type{}, q);
+                } else if constexpr (!K32) {  // more than 32 blocks of a type: step_pair64 is the only hot step this variant holds (registers)
                     if (track_min != 0u)
                         pair_loop(std::true_type{});
                     else
@@ -2164,6 +2199,12 @@ __global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_held_kernel(SweepPara
     sweep_fast_body<EL, CT, K32, false, false, false, false, true>(p);
 }
 
+// ... and the pass of one step a fourth time for fielded launches (FL: block fields, with or without a clamp and constraints)
+template <bool EL, bool CT, bool K32>
+__global__ __launch_bounds__(2 * kWave, 2) void sweep_fast_fielded_kernel(SweepParams p) {
+    sweep_fast_body<EL, CT, K32, false, false, false, false, true, true>(p);
+}
+
 template <class Kernel>
 static hipError_t launch_fast_kernel(Kernel kernel, const SweepParams& p, size_t lds_bytes, hipStream_t stream) {
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
@@ -2198,8 +2239,15 @@ hipError_t launch_fast_held(const SweepParams& p, size_t lds_bytes, hipStream_t 
                                         : launch_fast_kernel(sweep_fast_held_kernel<EL, CT, false>, p, lds_bytes, stream);
 }
 
-// The 20 + 4 + 8 kernels compile side by side: the build (build.py) compiles this file once per BISBM_FAST_PART = 0 .. 3 -- the six
-// kernels of one (EL, CT) each --, once per BISBM_FAST_PART = 5 .. 8 -- the two held kernels of one (EL, CT) each -- and once with
+// A fielded launch: one step per pass, one kernel per K32.
+template <bool EL, bool CT>
+hipError_t launch_fast_fielded(const SweepParams& p, size_t lds_bytes, hipStream_t stream) {
+    return (p.ka <= 32u && p.kb <= 32u) ? launch_fast_kernel(sweep_fast_fielded_kernel<EL, CT, true>, p, lds_bytes, stream)
+                                        : launch_fast_kernel(sweep_fast_fielded_kernel<EL, CT, false>, p, lds_bytes, stream);
+}
+
+// The 20 + 4 + 8 + 8 kernels compile side by side: the build (build.py) compiles this file once per BISBM_FAST_PART = 0 .. 3 -- the six
+// kernels of one (EL, CT) each --, once per BISBM_FAST_PART = 5 .. 8 -- the two held kernels of one (EL, CT) each --, once per BISBM_FAST_PART = 9 .. 12 -- the two fielded kernels of one (EL, CT) each -- and once with
 // BISBM_FAST_PART = 4 for the dispatch below; undefined: everything in one unit (diagnostic builds with in-kernel stamps, whose
 // counters are one device symbol).
 #ifndef BISBM_FAST_PART
@@ -2232,8 +2280,25 @@ template hipError_t launch_fast_held<true, false>(const SweepParams&, size_t, hi
 template hipError_t launch_fast_held<true, true>(const SweepParams&, size_t, hipStream_t);
 #endif
 
+#if BISBM_FAST_HERE(9)
+template hipError_t launch_fast_fielded<false, false>(const SweepParams&, size_t, hipStream_t);
+#endif
+#if BISBM_FAST_HERE(10)
+template hipError_t launch_fast_fielded<false, true>(const SweepParams&, size_t, hipStream_t);
+#endif
+#if BISBM_FAST_HERE(11)
+template hipError_t launch_fast_fielded<true, false>(const SweepParams&, size_t, hipStream_t);
+#endif
+#if BISBM_FAST_HERE(12)
+template hipError_t launch_fast_fielded<true, true>(const SweepParams&, size_t, hipStream_t);
+#endif
+
 #if BISBM_FAST_HERE(4)
 #if BISBM_FAST_PART == 4
+extern template hipError_t launch_fast_fielded<false, false>(const SweepParams&, size_t, hipStream_t);
+extern template hipError_t launch_fast_fielded<false, true>(const SweepParams&, size_t, hipStream_t);
+extern template hipError_t launch_fast_fielded<true, false>(const SweepParams&, size_t, hipStream_t);
+extern template hipError_t launch_fast_fielded<true, true>(const SweepParams&, size_t, hipStream_t);
 extern template hipError_t launch_fast_held<false, false>(const SweepParams&, size_t, hipStream_t);
 extern template hipError_t launch_fast_held<false, true>(const SweepParams&, size_t, hipStream_t);
 extern template hipError_t launch_fast_held<true, false>(const SweepParams&, size_t, hipStream_t);
@@ -2244,10 +2309,10 @@ extern template hipError_t launch_fast_variant<true, false>(const SweepParams&, 
 extern template hipError_t launch_fast_variant<true, true>(const SweepParams&, size_t, hipStream_t);
 #endif
 
-size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds, uint32_t eta_window, bool held) {
+size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_in_lds, uint32_t eta_window, bool held, bool fielded) {
     const uint32_t K = ka + kb, D = maxdeg + 1, S = kb | 1u;
     const size_t dwords = (size_t)ka * S + (eta_in_lds ? (size_t)K * D : (size_t)std::max(ka, kb) * eta_window) +
-                          2 * (size_t)kWave * (kHistStride / 4) + 2 * (size_t)hand_words(held) * kWave + kWave + 4 + 10 + 16 + 64 + 128;
+                          2 * (size_t)kWave * (kHistStride / 4) + 2 * (size_t)hand_words(held, fielded) * kWave + kWave + 4 + 10 + 16 + 64 + 128;
     // the step reads m[.][lane] for all 64 lanes whatever ka, kb are (idle lanes are masked after the read):
     // dword index <= 63 * S + 63 must be inside the allocation
     const size_t reach = 63 * (size_t)S + 64;
@@ -2257,9 +2322,14 @@ size_t sweep_fast_lds_bytes(uint32_t ka, uint32_t kb, uint32_t maxdeg, bool eta_
 hipError_t launch_sweep_fast(const SweepParams& p, size_t /*generic_lds_bytes*/, hipStream_t stream) {
     const bool ct = p.schedule == SCHED_CONSTANT;
     const bool held = p.clamp != nullptr || p.cn_bits != nullptr;  // (the host sends a held launch here only where it means to, bisbm_anneal.hip)
-    const size_t lds_bytes = sweep_fast_lds_bytes(p.ka, p.kb, p.maxdeg, p.eta_in_lds != 0, p.eta_w, held);
+    const bool fielded = p.fl_field != nullptr;  // (likewise; a clamp and constraints beside the field ride in the fielded kernels)
+    const size_t lds_bytes = sweep_fast_lds_bytes(p.ka, p.kb, p.maxdeg, p.eta_in_lds != 0, p.eta_w, held, fielded);
     hipError_t e;
-    if (held && p.eta_in_lds)
+    if (fielded && p.eta_in_lds)
+        e = ct ? launch_fast_fielded<true, true>(p, lds_bytes, stream) : launch_fast_fielded<true, false>(p, lds_bytes, stream);
+    else if (fielded)
+        e = ct ? launch_fast_fielded<false, true>(p, lds_bytes, stream) : launch_fast_fielded<false, false>(p, lds_bytes, stream);
+    else if (held && p.eta_in_lds)
         e = ct ? launch_fast_held<true, true>(p, lds_bytes, stream) : launch_fast_held<true, false>(p, lds_bytes, stream);
     else if (held)
         e = ct ? launch_fast_held<false, true>(p, lds_bytes, stream) : launch_fast_held<false, false>(p, lds_bytes, stream);

@@ -292,7 +292,7 @@ int bisbm_tempering_run(bisbm_handle h, uint64_t sweeps, uint32_t exchange_every
         h->last_kernel_ms = std::max(h->last_kernel_ms, d->last_kernel_ms);
         h->last_updates += d->last_updates;
         h->last_pass_steps = std::max(d == h->devs[0] ? 0u : h->last_pass_steps, d->last_pass_steps);
-        if (d == h->devs[0]) std::copy(d->last_eta_plan, d->last_eta_plan + 4, h->last_eta_plan);
+        if (d == h->devs[0]) std::copy(d->last_eta_plan, d->last_eta_plan + 4, h->last_eta_plan), h->last_route = d->last_route;
     }
     h->temper.round = h->devs[0]->temper.round;
     return rc;
@@ -322,7 +322,7 @@ int bisbm_tempering_run_rounds(bisbm_handle h, uint64_t rounds, const bisbm_roun
         h->last_kernel_ms = std::max(h->last_kernel_ms, d->last_kernel_ms);
         h->last_updates += d->last_updates;
         h->last_pass_steps = std::max(d == h->devs[0] ? 0u : h->last_pass_steps, d->last_pass_steps);
-        if (d == h->devs[0]) std::copy(d->last_eta_plan, d->last_eta_plan + 4, h->last_eta_plan);
+        if (d == h->devs[0]) std::copy(d->last_eta_plan, d->last_eta_plan + 4, h->last_eta_plan), h->last_route = d->last_route;
     }
     h->temper.round = h->devs[0]->temper.round;
     return rc;

@@ -711,6 +711,12 @@ public:
         check(bisbm_last_eta_plan(h_, out.data()));
         return out;
     }
+    // BISBM_ROUTE_* bits of the last MH launch: which kernel ran, and whether it carried a hold or fields (bisbm_last_sweep_route)
+    uint32_t last_route() const {
+        uint32_t route = 0;
+        check(bisbm_last_sweep_route(h_, &route));
+        return route;
+    }
     bisbm_handle handle() const { return h_; }
     uint32_t n_chains() const { return n_chains_; }
 

@@ -33,12 +33,16 @@ start = np.concatenate([np.arange(na) % ka, ka + np.arange(nb) % kb]).astype(np.
 start[hinted] = hint[hinted]
 
 
+routes = []  # (BlockModel.last_route() of each fit's MH sweeps)
+
+
 def fit(prepare):
     """a short anneal, then greedy polishing; the labels of the chain with the lowest description length"""
     model = bisbm.BlockModel(start.astype(np.uint32), types, ka + kb, ka, kb, 1.0, adj, n_chains=CHAINS, rng="philox", seed=3)
     model.init_bisbm()
     prepare(model)
     model.run_sweeps(40, temperature=1.0)
+    routes.append(model.last_route())
     model.polish(50)
     best = int(np.argmin(model.entropy()))
     labels = model.get_memberships(best).astype(np.int64)
@@ -57,3 +61,7 @@ mask[hinted] = True
 print("%d of %d nodes hinted, %d of the hints wrong; weight of a hinted block %g (%d field classes)" % (len(hinted), n, len(wrong), WEIGHT, len(field)))
 report("hints as weights", fit(lambda model: model.set_fields(class_of_node, field)))
 report("hints clamped", fit(lambda model: model.clamp(mask)))
+# which kernel ran the sweeps: both fits take the production kernel, the fielded one its one-step pass
+print("MH sweeps ran the %s" % ", ".join("%s kernel (%s)" % ("production" if r & bisbm.ROUTE_PRODUCTION else "generic",
+                                                            "fields" if r & bisbm.ROUTE_FIELDS else "a clamp" if r & bisbm.ROUTE_HELD else "nothing held")
+                                         for r in routes))

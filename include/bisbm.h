@@ -32,7 +32,7 @@ extern "C" {
  *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp), chain traces (bisbm_trace_*), round recipes
  *    (bisbm_tempering_run_rounds, bisbm_tempering_rung_stats, bisbm_rounds_population_run), held conditionals and the least
  *    settled queries (bisbm_held_conditionals_*, bisbm_least_settled_topk, bisbm_debug_log), the eta plan of the last launch
- *    (bisbm_last_eta_plan).  Additions only. */
+ *    (bisbm_last_eta_plan), the route of the last launch (bisbm_last_sweep_route).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -852,7 +852,7 @@ int bisbm_constraints_get(bisbm_handle h, uint32_t *n_classes_out, uint8_t *clas
  * BISBM_ERR_INVALID_ARG naming class and block (for +inf the message names bisbm_constraints_set, the way to forbid a block).  A
  * refusal leaves the fields that were in place on every device.  n_classes = 0 or a NULL pointer clears, and a table whose
  * entries are all +-0.0 IS "no fields" and is stored as a clear: the kernels are handed null pointers, MH sweeps run the
- * production kernel again, every call is bit for bit that of a handle that never had fields, and get reports 0 classes.  Each
+ * unfielded kernels again, every call is bit for bit that of a handle that never had fields, and get reports 0 classes.  Each
  * device keeps the n class bytes and the table in global memory (at most 512 KiB of table).
  * get: n_classes, the class bytes and the table as given (each pointer may be NULL; without fields 0 classes, all class bytes 0,
  * field_out untouched).
@@ -862,7 +862,10 @@ int bisbm_constraints_get(bisbm_handle h, uint32_t *n_classes_out, uint8_t *clas
  *   1. MH SWEEPS: the add follows the evaluation of the step's dS, before the accept line, whose form stays.  A proposal of the
  *      node's own block keeps 0, a target of the other type or barred by the constraints keeps its verdict.  Proposal and
  *      Hastings factor are untouched: the step is the Metropolis-Hastings step for exp(-beta E) with the same q.  While fields
- *      are set the sweeps run the generic kernel (README.md).
+ *      are set the sweeps of a handle the production kernel serves run its fielded instances, one step per pass
+ *      (bisbm_last_pass_steps reports 1, bisbm_last_sweep_route BISBM_ROUTE_PRODUCTION | BISBM_ROUTE_FIELDS), with a clamp and
+ *      constraints beside the field in the same launch; the chain is, integer for integer, the generic kernel's
+ *      (BISBM_FIELD_FAST=0 in the environment pins that kernel for fielded handles; README.md).
  *   2. HEAT-BATH SWEEPS AND POLISHING: the row entry of target s != r is (((acc + tail1) + tail2) + tail3) + (f[s] - f[r]) and
  *      stays 0 at r; minimum, weights, Z, C_s, the greedy rule and the constraints' restriction follow as they are.  Polishing
  *      certifies a minimum of E over the open admissible moves.
@@ -1213,6 +1216,15 @@ int bisbm_last_pass_steps(bisbm_handle h, uint32_t *steps_per_pass);
  * groups reports its first member's plan.  Diagnostic (tests tell from it which route a row took): no counterpart in the
  * reference; the chain does not depend on it. */
 int bisbm_last_eta_plan(bisbm_handle h, uint32_t out[4]);
+
+/* Which kernel the last Metropolis-Hastings launch ran and what it carried, as BISBM_ROUTE_* bits (0 before any launch).  One step
+ * per pass no longer tells the generic kernel from the production one (a fielded launch runs the production kernel's one-step
+ * pass), so tests and A/B runs read the route here.  A handle over several devices or shape groups reports its first member's
+ * route, as bisbm_last_eta_plan does.  Diagnostic: no counterpart in the reference; the chain does not depend on it. */
+#define BISBM_ROUTE_PRODUCTION 1u /* the production kernel (bisbm_sweep_fast.hip), not the generic one */
+#define BISBM_ROUTE_HELD 2u       /* the launch carried a clamp and / or block constraints */
+#define BISBM_ROUTE_FIELDS 4u     /* the launch carried block fields */
+int bisbm_last_sweep_route(bisbm_handle h, uint32_t *route);
 
 /* Device numerics probe (tests): evaluates log_q(n[i], k[i]) on the device (int_part.hh:27-37).
  * fast = 0: the literal evaluation (mt19937-compat mode, entropy()); fast = 1: the Philox-mode
