@@ -45,6 +45,10 @@ QUERY_NONE = 0xFFFFFFFF
 # bisbm_coassign_*: candidates x queries of one workgroup of the counting kernel (csrc/bisbm_kernels.hpp: kCoassignCandTile,
 # kCoassignTile); the largest k of bisbm_coassign_topk is QUERY_MAX_K, an entry past the eligible nodes QUERY_NONE
 COASSIGN_CAND_TILE, COASSIGN_TILE = 1024, 16
+# bisbm_edge_probs_*: the kinds of a pair (BISBM_EDGE_ADD, BISBM_EDGE_REMOVE), the bit of `what` that keeps the last sample's dS
+# (BISBM_EDGE_KEEP_LAST) and the pairs of one workgroup of the dS kernel (csrc/bisbm_engine.hpp: kEdgeProbsTile)
+EDGE_ADD, EDGE_REMOVE, EDGE_KEEP_LAST = 0, 1, 1
+EDGE_PROBS_TILE = 1024
 # bisbm_foldin_*: the row kinds (BISBM_FOLDIN_RECOMMEND, BISBM_FOLDIN_SIMILAR) and candidates x virtual nodes of one workgroup of
 # the rows kernel (csrc/bisbm_kernels.hpp: kFoldinCandTile, kFoldinTile); the largest k of bisbm_foldin_topk is QUERY_MAX_K
 FOLDIN_RECOMMEND, FOLDIN_SIMILAR = 1, 2
@@ -142,6 +146,11 @@ ABI = {
     "bisbm_pair_scores_accumulate": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_reset": (C.c_int, [C.c_void_p]),
     "bisbm_pair_scores_get": (C.c_int, [C.c_void_p, _f64p, _u64p]),
+    "bisbm_edge_probs_set": (C.c_int, [C.c_void_p, C.c_uint64, _u32p, _u32p, _u8p, C.c_uint32]),
+    "bisbm_edge_probs_accumulate": (C.c_int, [C.c_void_p]),
+    "bisbm_edge_probs_reset": (C.c_int, [C.c_void_p]),
+    "bisbm_edge_probs_get": (C.c_int, [C.c_void_p, _f64p, _f64p, _u32p, _u64p]),
+    "bisbm_edge_probs_get_last": (C.c_int, [C.c_void_p, C.c_uint64, _f64p]),
     "bisbm_query_scores_set": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
     "bisbm_query_scores_accumulate": (C.c_int, [C.c_void_p]),
     "bisbm_query_scores_reset": (C.c_int, [C.c_void_p]),
@@ -1264,6 +1273,62 @@ class BlockModel:
         self._check(self._L.bisbm_pair_scores_get(self._h, _p(out, _f64p), C.byref(terms)))
         return out, terms.value
 
+    # -- edge probabilities (include/bisbm.h, "Edge probabilities")
+    def edge_probs_set(self, pairs, kinds=None, keep_last=False):
+        """The edges to weigh: an integer array [P, 2] of (type-a node, type-b node) and per pair EDGE_ADD (0; also "+") or
+        EDGE_REMOVE (1; "-"), None: all ADD; replaces earlier pairs and zeroes the sums.  keep_last: keep every chain's dS of the
+        last sample for edge_probs_last (n_chains x P doubles on the device).  An empty array frees everything."""
+        pr = np.asarray(pairs)
+        if pr.size == 0:
+            pr = np.zeros((0, 2), dtype=np.uint32)
+        if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+            raise ValueError("pairs must be an integer array of shape (P, 2)")
+        if len(pr) and (pr.min() < 0 or pr.max() > 0xFFFFFFFF):
+            raise ValueError("a node id of a pair is outside [0, 2^32)")
+        u = np.ascontiguousarray(pr[:, 0], dtype=np.uint32)
+        v = np.ascontiguousarray(pr[:, 1], dtype=np.uint32)
+        kd = None
+        if kinds is not None:
+            kd = np.array([{"+": EDGE_ADD, "-": EDGE_REMOVE}.get(k, k) for k in kinds] if len(kinds) else [], dtype=np.int64)
+            if kd.shape != (len(u),) or (len(kd) and (kd.min() < 0 or kd.max() > 255)):
+                raise ValueError("kinds must hold one of EDGE_ADD / EDGE_REMOVE per pair")
+            kd = np.ascontiguousarray(kd, dtype=np.uint8)
+        self._check(self._L.bisbm_edge_probs_set(self._h, len(u), _p(u, _u32p), _p(v, _u32p), _p(kd, _u8p) if kd is not None else None,
+                                                 EDGE_KEEP_LAST if keep_last else 0))
+        self.n_edge_pairs = len(u)
+
+    def edge_probs_accumulate(self):
+        """One sample: every counted chain's dS and exp(-dS) are added to every pair's sums (with replica exchange on, the
+        chains on rung 0 only)."""
+        self._check(self._L.bisbm_edge_probs_accumulate(self._h))
+
+    def edge_probs_reset(self):
+        self._check(self._L.bisbm_edge_probs_reset(self._h))
+
+    def edge_probs(self):
+        """A dict, arrays [P] in the order of edge_probs_set: dS_sum, w_sum (float64), mult (uint32: the present multiplicity),
+        terms, and the estimates mean_dS = dS_sum / terms and log_prob = ln(w_sum / terms), the log posterior-predictive odds of
+        the edited graph (NaN before the first sample, -inf where every counted chain's exp(-dS) is 0)."""
+        P = getattr(self, "n_edge_pairs", 0)
+        ds, w, mult = np.zeros(P, dtype=np.float64), np.zeros(P, dtype=np.float64), np.zeros(P, dtype=np.uint32)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_edge_probs_get(self._h, _p(ds, _f64p), _p(w, _f64p), _p(mult, _u32p), C.byref(terms)))
+        if not terms.value:
+            mean = logp = np.full(P, np.nan)
+        else:  # (math.log: the C library's logarithm, the one the command line prints)
+            import math
+            t = float(terms.value)
+            mean = ds / t
+            logp = np.array([math.log(x) if x > 0 else (-math.inf if x == 0 else math.nan) for x in (w / t).tolist()], dtype=np.float64)
+        return {"dS_sum": ds, "w_sum": w, "mult": mult, "terms": terms.value, "mean_dS": mean, "log_prob": logp}
+
+    def edge_probs_last(self, i):
+        """float64 [n_chains]: dS of pair i (in the order of edge_probs_set) in every chain at the last sample, NaN where the
+        chain was not counted; needs keep_last."""
+        out = np.zeros(self.n_chains, dtype=np.float64)
+        self._check(self._L.bisbm_edge_probs_get_last(self._h, int(i), _p(out, _f64p)))
+        return out
+
     # -- query scores (include/bisbm.h, "Query scores")
     def query_scores_set(self, queries):
         """The nodes to rank candidates for: an integer array [Q] of node ids of either type (they may repeat); replaces earlier
@@ -1994,5 +2059,5 @@ metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
 from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_held_conditional_row, numpy_least_settled, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice, numpy_reshuffle_accept, numpy_reshuffle_launch, numpy_reshuffle_pair, numpy_reshuffle_q, numpy_reshuffle_step,  # noqa: E402,F401
-                          numpy_pair_scores, numpy_query_topk, shard_chains)
+                          numpy_edge_dS, numpy_edge_multiplicity, numpy_pair_scores, numpy_query_topk, shard_chains)
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

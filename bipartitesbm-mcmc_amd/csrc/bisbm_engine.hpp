@@ -16,6 +16,7 @@
 //                        heat-bath sweeps and pair reshuffles at a beta per chain, the per-rung tally
 //   bisbm_population.hip  population annealing: offspring counts on the host, the kernel that copies chain states between slots
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
+//   bisbm_edge_probs.hip   exact edge probabilities: dS of adding or removing a listed edge, pooled over chains; kernels and C ABI
 //   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains; kernels and C ABI
 //   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block; kernels and C ABI
 //   bisbm_foldin.hip     fold-in queries: block posterior, recommendations and peers of a node that is not in the graph; kernels and C ABI
@@ -212,6 +213,28 @@ struct PairScoreState {
     DeviceBuf<double> d_sum;      // [n] running sums, sorted order
     DeviceBuf<double> d_part;     // [slabs][n] partial sums of one sample
     std::vector<uint32_t> order;  // sorted position -> index in the caller's arrays
+};
+
+// Edge probabilities (bisbm_edge_probs.hip).  As PairScoreState: the buffers belong to the engine that owns the graph on a device,
+// the container of device entries keeps only `n`; the pairs are held sorted by (u, v).
+constexpr uint32_t kEdgeProbsTile = 1024;  // pairs per workgroup of the dS kernel: 256 lanes, 4 pairs each
+struct EdgeProbState {
+    uint64_t n = 0;               // pairs listed (0: none)
+    uint64_t terms = 0;           // chain terms added to every sum since the last set / reset
+    uint32_t what = 0;            // BISBM_EDGE_KEEP_LAST
+    bool have_last = false;       // d_last holds a sample
+    DeviceBuf<uint32_t> d_u, d_v;         // [n] type-a node, type-b node of every pair, sorted order
+    DeviceBuf<uint32_t> d_du, d_dv;       // [n] their degrees
+    DeviceBuf<uint8_t> d_kind;            // [n] BISBM_EDGE_ADD / BISBM_EDGE_REMOVE
+    DeviceBuf<double> d_tdeg, d_tmult;    // [n] the chain-independent terms of dS, in the form of the pair's kind
+    DeviceBuf<double> d_dS_sum, d_w_sum;  // [n] running sums, sorted order
+    DeviceBuf<double> d_blk;      // [chains of a launch][K][4] block terms
+    DeviceBuf<double> d_etat;     // [chains of a launch][K][max_degree + 1][2] eta terms
+    DeviceBuf<uint32_t> d_row;    // KEEP_LAST over shape groups: [chains of a launch] row of d_last of every chain
+    DeviceBuf<double> d_last;     // KEEP_LAST: [chains of the engine][n] dS of the last sample, NaN: not counted
+    std::vector<uint32_t> order;  // sorted position -> index in the caller's arrays
+    std::vector<uint32_t> pos;    // index in the caller's arrays -> sorted position
+    std::vector<uint32_t> mult;   // [n] present multiplicity of every pair, sorted order
 };
 
 // What topk_select (bisbm_topk.hip) needs of device memory for one chunk of queries, T: the cell type of the rows.  It is on the
@@ -554,6 +577,7 @@ struct bisbm_engine {
     bisbm::TemperState temper;
     bisbm::PopulationState population;
     bisbm::PairScoreState pairs;
+    bisbm::EdgeProbState edges;
     bisbm::QueryScoreState queries;
     bisbm::CoassignState coassign;
     bisbm::FoldinState foldin;

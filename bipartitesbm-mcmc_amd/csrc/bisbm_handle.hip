@@ -49,6 +49,7 @@ void free_all(bisbm_engine* h) {
     h->align = AlignState(), h->temper = TemperState(), h->population = PopulationState(), h->pairs = PairScoreState(), h->partition = PartitionState();
     h->queries = QueryScoreState(), h->coassign = CoassignState(), h->foldin = FoldinState(), h->cond = ConditionalState();
     h->clamp = ClampState();
+    h->edges = EdgeProbState();
     h->constraints = ConstraintState();
     h->fields = FieldState();
     h->d_T.reset();
@@ -295,6 +296,8 @@ int bisbm_create(bisbm_handle* out, uint64_t n, uint64_t na, uint64_t nb, const 
 
     // tables: lgamma covers every index the sweep and entropy() can touch
     // (cache.cc:86-91 sizes it 2E+1 and grows on demand; the values are lgamma(i) either way)
+    // The three sizes also cover every index of the edge probabilities (bisbm_edge_probs.hip): m_rs + 2 and m_r + 2 <= E + 2 and
+    // mu + 2 <= E + 2 lie below 2E + 2 (E >= 1), d + 2 and eta + 2 <= n + 2 below n + 3, ka kb + E + 1 below ka kb + E + 2.
     uint64_t lg_size = 2 * h->num_edges + 2;
     lg_size = std::max<uint64_t>(lg_size, n + 3);
     lg_size = std::max<uint64_t>(lg_size, (uint64_t)ka * kb + h->num_edges + 2);

@@ -209,6 +209,55 @@ def numpy_pair_scores(labels_by_chain, m_by_chain, m_r_by_chain, deg, pairs):
     return total
 
 
+def numpy_edge_multiplicity(rowptr, col, pairs):
+    """mu of every pair (u, v): the number of entries of u's CSR row equal to v (include/bisbm.h, "Edge probabilities")."""
+    pairs = np.asarray(pairs).reshape(-1, 2).astype(np.int64)
+    rowptr, col = np.asarray(rowptr).astype(np.int64), np.asarray(col).astype(np.int64)
+    return np.array([int((col[rowptr[u]:rowptr[u + 1]] == v).sum()) for u, v in pairs], dtype=np.uint32)
+
+
+def numpy_edge_dS(m, m_r, n_r, eta, deg, labels, ka, kb, E, u, v, kind, mult, lg, logq):
+    """Host statement of one chain's dS of one pair (include/bisbm.h, "Edge probabilities"): the seven terms in the stated order,
+    Python floats (f64, no fused multiply-add).  m, m_r, n_r, eta: the chain's block state as get_m / get_m_r / get_n_r /
+    get_eta_rk_ return it (global labels, the full K x K matrix, eta [K, max_degree + 1]); deg: the degree of every node;
+    labels: the chain's; E: the number of edges; kind 0: ADD, 1: REMOVE; mult: the pair's present multiplicity.  lg(i): the
+    lgamma table's entry (lg(0) = +inf); logq(edges of the block, nodes of the block): the log_q of the description length, in
+    the argument order the entropy kernel calls it with."""
+    r, s = int(labels[u]), int(labels[v])
+    du, dv, mu = int(deg[u]), int(deg[v]), int(mult)
+    mrs, mr, ms, nr, ns = int(m[r][s]), int(m_r[r]), int(m_r[s]), int(n_r[r]), int(n_r[s])
+    D = len(eta[0])
+
+    def eta_at(x, d):
+        return int(eta[x][d]) if 0 <= d < D else 0
+
+    def lbinom(N, k):
+        if N == 0 or k == 0 or k > N:
+            return 0.0
+        return (lg(N + 1) - lg(k + 1)) - lg(N - k + 1)
+    cells = int(ka) * int(kb)
+    E = int(E)
+    if int(kind) == 0:
+        t_deg = (lg(du + 1) - lg(du + 2)) + (lg(dv + 1) - lg(dv + 2))
+        t_m = lg(mrs + 1) - lg(mrs + 2)
+        t_mr = (lg(mr + 2) - lg(mr + 1)) + (lg(ms + 2) - lg(ms + 1))
+        du2, dv2, mr2, ms2 = du + 1, dv + 1, mr + 1, ms + 1
+        t_mult = lg(mu + 2) - lg(mu + 1)
+        t_E = lbinom(cells + E, E + 1) - lbinom(cells + E - 1, E)
+    else:
+        t_deg = (lg(du + 1) - lg(du)) + (lg(dv + 1) - lg(dv))
+        t_m = lg(mrs + 1) - lg(mrs)
+        t_mr = (lg(mr) - lg(mr + 1)) + (lg(ms) - lg(ms + 1))
+        du2, dv2, mr2, ms2 = du - 1, dv - 1, mr - 1, ms - 1
+        t_mult = lg(mu) - lg(mu + 1)
+        t_E = lbinom(cells + E - 2, E - 1) - lbinom(cells + E - 1, E)
+    eu0, eu1, ev0, ev1 = eta_at(r, du), eta_at(r, du2), eta_at(s, dv), eta_at(s, dv2)
+    t_eta = (((lg(eu0 + 1) - lg(eu0)) + (lg(eu1 + 1) - lg(eu1 + 2)))
+             + ((lg(ev0 + 1) - lg(ev0)) + (lg(ev1 + 1) - lg(ev1 + 2))))
+    t_q = (logq(mr2, nr) - logq(mr, nr)) + (logq(ms2, ns) - logq(ms, ns))
+    return (((((t_deg + t_m) + t_mr) + t_eta) + t_q) + t_mult) + t_E
+
+
 QUERY_NONE = 0xFFFFFFFF  # bisbm_query_scores_topk: an entry past the eligible candidates
 
 

@@ -472,6 +472,19 @@ public:
         check(bisbm_pair_scores_get(h_, sum.data(), &terms));
         return sum;
     }
+    // edge probabilities (include/bisbm.h): the pairs with their kinds (BISBM_EDGE_ADD / BISBM_EDGE_REMOVE), a sample of every
+    // counted chain, the sums of dS and exp(-dS), the present multiplicities and the number of chain terms in the sums
+    void edge_probs_set(const std::vector<uint32_t>& u, const std::vector<uint32_t>& v, const std::vector<uint8_t>& kind, bool keep_last = false) {
+        if (u.size() != v.size() || u.size() != kind.size()) throw std::runtime_error("edge_probs_set: u, v and kind differ in length");
+        check(bisbm_edge_probs_set(h_, u.size(), u.data(), v.data(), kind.data(), keep_last ? BISBM_EDGE_KEEP_LAST : 0u));
+        n_edge_pairs_ = u.size();
+    }
+    void edge_probs_accumulate() { check(bisbm_edge_probs_accumulate(h_)); }
+    void edge_probs_reset() { check(bisbm_edge_probs_reset(h_)); }
+    void edge_probs(std::vector<double>& dS_sum, std::vector<double>& w_sum, std::vector<uint32_t>& mult, uint64_t& terms) {
+        dS_sum.assign(n_edge_pairs_, 0.), w_sum.assign(n_edge_pairs_, 0.), mult.assign(n_edge_pairs_, 0u);
+        check(bisbm_edge_probs_get(h_, dS_sum.data(), w_sum.data(), mult.data(), &terms));
+    }
     // query scores (include/bisbm.h): the query nodes (either type), a sample of every counted chain, one query's row over its
     // candidates (all nodes of the other type, in id order), and every query's k best candidates selected on the device
     // (nodes / sums [queries * k], 0xffffffff / 0.0 past the eligible ones; the estimate of an entry is sum / terms)
@@ -731,7 +744,7 @@ private:
         KB_ = kb;
     }
     bisbm_handle h_ = nullptr;
-    size_t KA_, KB_, n_ = 0, na_ = 0, n_pairs_ = 0;
+    size_t KA_, KB_, n_ = 0, na_ = 0, n_pairs_ = 0, n_edge_pairs_ = 0;
     std::vector<uint32_t> queries_, coassign_queries_;
     std::vector<uint8_t> foldin_types_;
     uint32_t n_conditionals_ = 0;

@@ -5,12 +5,13 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
+// --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --edge_probs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
 // --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace, --rung_moves, --population_moves,
 // --clamp, --constraints, --fields.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
+#include <algorithm>
 #include <chrono>
 #include <limits>
 #include <cmath>
@@ -52,6 +53,7 @@ const option_spec kOptions[] = {
     {"chains", 0, 1},           {"device", 0, 1},          {"devices", 0, 1},          {"rng", 0, 1},          {"gen_seed", 0, 1},
     {"csr_cache", 0, 0},        {"reorder", 0, 0},         {"marginalize", 0, 0},      {"align", 0, 0},
     {"tempering", 0, 2},        {"exchange_every", 0, 1},  {"score_pairs", 0, 2},
+    {"edge_probs", 0, 2},
     {"population", 0, 2},       {"population_sweeps", 0, 1},
     {"recommend", 0, 2},        {"include_edges", 0, 0},
     {"similar", 0, 2},
@@ -275,6 +277,12 @@ void print_help(const char* argv0) {
                  "                                        type b); every sample adds every sampled chain's expected edge count\n"
                  "                                        between the two, and OUT receives `u v score` per pair in input order\n"
                  "                                        (score = the mean over samples and chains, printed with %.17g).\n"
+                 "  --edge_probs IN OUT                   With --marginalize: IN holds one line `u v`, `u v +` or `u v -` per pair (u of\n"
+                 "                                        type a, v of type b; + or nothing: add one edge u - v, -: remove one, which\n"
+                 "                                        must be there); every sample adds every sampled chain's exact change dS of\n"
+                 "                                        the description length under that edit and exp(-dS), and OUT receives\n"
+                 "                                        `u v kind mult mean_dS log_prob` per pair in input order (mult: the edge's\n"
+                 "                                        present multiplicity, log_prob = ln mean exp(-dS); %.17g).\n"
                  "  --recommend QUERIES OUT K             With --marginalize: QUERIES holds one node id per line (either type);\n"
                  "                                        every sample adds every sampled chain's expected edge count between the\n"
                  "                                        node and EVERY node of the other type, and OUT receives the K best\n"
@@ -377,6 +385,14 @@ int main(int argc, char const* argv[]) {
     }
     if (count("score_pairs") && var_map["score_pairs"].size() != 2) {
         std::cerr << "Invalid --score_pairs. Two paths: the file of pairs to read and the file of scores to write.\n";
+        return 1;
+    }
+    if (count("edge_probs") && !count("marginalize")) {
+        std::cerr << "--edge_probs weighs edges over the samples of the chains: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("edge_probs") && var_map["edge_probs"].size() != 2) {
+        std::cerr << "Invalid --edge_probs. Two paths: the file of pairs to read and the file of results to write.\n";
         return 1;
     }
     if ((count("recommend") || count("include_edges")) && !count("marginalize")) {
@@ -758,6 +774,38 @@ int main(int argc, char const* argv[]) {
                 return 1;
             }
     }
+    // --edge_probs: the pairs are read and checked before any device is touched (ids as in the edge list file); that every `-`
+    // names an edge of the graph is checked once the graph is loaded, below
+    edge_list_t edge_prob_pairs;
+    std::vector<uint8_t> edge_prob_kinds;
+    if (count("edge_probs")) {
+        const std::string in = var_map["edge_probs"][0];
+        std::ifstream file(in);
+        if (!file) {
+            std::cerr << "[error] --edge_probs: cannot read " << in << "\n";
+            return 1;
+        }
+        std::string text;
+        for (size_t line_no = 1; std::getline(file, text); ++line_no) {
+            std::istringstream fields(text);
+            std::vector<std::string> tok;
+            for (std::string t; fields >> t;) tok.push_back(t);
+            if (tok.empty()) continue;
+            auto is_id = [](const std::string& t) { return !t.empty() && t.size() <= 18 && t.find_first_not_of("0123456789") == std::string::npos; };
+            if (tok.size() < 2 || tok.size() > 3 || !is_id(tok[0]) || !is_id(tok[1]) || (tok.size() == 3 && tok[2] != "+" && tok[2] != "-")) {
+                std::cerr << "[error] --edge_probs: line " << line_no << " of " << in << " is not `u v`, `u v +` or `u v -`: " << text << "\n";
+                return 1;
+            }
+            edge_prob_pairs.emplace_back((size_t)std::stoull(tok[0]), (size_t)std::stoull(tok[1]));
+            edge_prob_kinds.push_back(tok.size() == 3 && tok[2] == "-" ? BISBM_EDGE_REMOVE : BISBM_EDGE_ADD);
+        }
+        for (size_t i = 0; i < edge_prob_pairs.size(); ++i)
+            if (edge_prob_pairs[i].first >= NA || edge_prob_pairs[i].second < NA || edge_prob_pairs[i].second >= NA + NB) {
+                std::cerr << "[error] --edge_probs: pair " << i << " (" << edge_prob_pairs[i].first << " " << edge_prob_pairs[i].second
+                          << ") must name a type-a node [0, " << NA << ") and a type-b node [" << NA << ", " << NA + NB << ")\n";
+                return 1;
+            }
+    }
     // --recommend: the queries are read and checked before any device is touched (ids as in the edge list file)
     std::vector<uint32_t> recommend_queries;
     if (var_map.count("recommend")) {
@@ -1068,6 +1116,15 @@ int main(int argc, char const* argv[]) {
         edge_list_t edge_list;
         load_edge_list(edge_list, single("edge_list_path", ""));
         adj_list_loaded = edge_to_adj(edge_list, N);
+    }
+    for (size_t i = 0; i < edge_prob_pairs.size(); ++i) {  // --edge_probs: a `-` needs its edge (still no device touched)
+        if (edge_prob_kinds[i] != BISBM_EDGE_REMOVE) continue;
+        const size_t u = edge_prob_pairs[i].first, v = edge_prob_pairs[i].second;
+        const uint32_t* row = adj_list_loaded.col.data();
+        if (std::find(row + adj_list_loaded.rowptr[u], row + adj_list_loaded.rowptr[u + 1], (uint32_t)v) == row + adj_list_loaded.rowptr[u + 1]) {
+            std::cerr << "[error] --edge_probs: pair " << i << " (" << u << " " << v << " -) removes an edge the graph does not hold\n";
+            return 1;
+        }
     }
     // --reorder: the engine works on a renumbered graph; memberships go in and come out in the caller's numbering
     std::vector<uint32_t> new_id;
@@ -1536,6 +1593,14 @@ int main(int argc, char const* argv[]) {
                 }
                 blockmodel.pair_scores_set(pu, pv);
             }
+            if (!edge_prob_pairs.empty()) {  // (--reorder: the engine knows the nodes by their new ids)
+                std::vector<uint32_t> pu, pv;
+                for (auto const& pr : edge_prob_pairs) {
+                    pu.push_back(new_id.empty() ? (uint32_t)pr.first : new_id[pr.first]);
+                    pv.push_back(new_id.empty() ? (uint32_t)pr.second : new_id[pr.second]);
+                }
+                blockmodel.edge_probs_set(pu, pv, edge_prob_kinds);
+            }
             if (!recommend_queries.empty()) {  // (--reorder: the engine knows the nodes by their new ids)
                 std::vector<uint32_t> q;
                 for (uint32_t v : recommend_queries) q.push_back(new_id.empty() ? v : new_id[v]);
@@ -1575,6 +1640,7 @@ int main(int argc, char const* argv[]) {
                 }
                 if (!foldin_types.empty()) blockmodel.foldin_accumulate();
                 if (!score_pairs.empty()) blockmodel.pair_scores_accumulate();
+                if (!edge_prob_pairs.empty()) blockmodel.edge_probs_accumulate();
                 if (!recommend_queries.empty()) blockmodel.query_scores_accumulate();
                 if (!similar_queries.empty()) blockmodel.coassign_accumulate();
             }
@@ -1662,6 +1728,26 @@ int main(int argc, char const* argv[]) {
                     return 1;
                 }
                 std::clog << "score_pairs: " << score_pairs.size() << " pair(s), " << terms << " chain term(s) each -> " << out_path << "\n";
+            }
+            if (count("edge_probs")) {
+                const std::string out_path = var_map["edge_probs"][1];
+                std::ofstream out(out_path);
+                uint64_t terms = 0;
+                std::vector<double> dS_sum, w_sum;
+                std::vector<uint32_t> mult;
+                if (!edge_prob_pairs.empty()) blockmodel.edge_probs(dS_sum, w_sum, mult, terms);
+                char line[192];
+                for (size_t i = 0; i < edge_prob_pairs.size(); ++i) {
+                    std::snprintf(line, sizeof(line), "%zu %zu %c %u %.17g %.17g\n", edge_prob_pairs[i].first, edge_prob_pairs[i].second,
+                                  edge_prob_kinds[i] == BISBM_EDGE_REMOVE ? '-' : '+', mult[i], dS_sum[i] / (double)terms, std::log(w_sum[i] / (double)terms));
+                    out << line;
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --edge_probs: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "edge_probs: " << edge_prob_pairs.size() << " pair(s), " << terms << " chain term(s) each -> " << out_path << "\n";
             }
             if (var_map.count("recommend")) {
                 const std::string out_path = var_map["recommend"][1];

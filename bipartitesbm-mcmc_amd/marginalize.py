@@ -19,7 +19,7 @@ import numpy as np
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
                 similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None, rung_moves=None, blocks=False,
-                clamp=None, constraints=None, fields=None, conditionals_held=False, least_settled=None):
+                clamp=None, constraints=None, fields=None, conditionals_held=False, least_settled=None, edge_probs=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -47,6 +47,10 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     scores"): set, with zeroed sums, before the first sample, and every sample also adds every counted chain's term to every
     pair's sum (with `tempering` the chains on rung 0 only).  The return value does not change: model.pair_scores() gives
     (sum, terms) afterwards, shard.pooled_pair_scores(model) the same over ranks.
+    `edge_probs`: (pairs, kinds) or (pairs,) as model.edge_probs_set takes them (include/bisbm.h, "Edge probabilities"): set, with
+    zeroed sums, before the first sample, and every sample also adds every counted chain's dS and exp(-dS) to every pair's sums
+    -- wherever `score_pairs` takes a sample.  The return value does not change: model.edge_probs() gives the sums and the
+    estimates afterwards.  The chains of this rank only.
     `recommend`: (queries, k) or (queries, k, exclude_edges) (include/bisbm.h, "Query scores"): the queries are set, with zeroed
     sums, before the first sample, every sample also adds every counted chain's term to every (query, candidate) sum, and the
     return value becomes (labels, counts, model.recommend(k, exclude_edges)) -- the chains of this rank only.
@@ -117,6 +121,9 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     if score_pairs is not None:
         model.pair_scores_set(score_pairs)
         model.pair_scores_reset()
+    if edge_probs is not None:
+        model.edge_probs_set(edge_probs[0], edge_probs[1] if len(edge_probs) > 1 else None)
+        model.edge_probs_reset()
     if recommend is not None:
         model.query_scores_set(recommend[0])
         model.query_scores_reset()
@@ -170,6 +177,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             model.marginals_accumulate(None)
             if score_pairs is not None:
                 model.pair_scores_accumulate()
+            if edge_probs is not None:
+                model.edge_probs_accumulate()
             if recommend is not None:
                 model.query_scores_accumulate()
             if similar is not None:
@@ -206,6 +215,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         model.marginals_accumulate(device_counts.data_ptr())  # adds into the tensor, on the device
         if score_pairs is not None:
             model.pair_scores_accumulate()
+        if edge_probs is not None:
+            model.edge_probs_accumulate()
         if recommend is not None:
             model.query_scores_accumulate()
         if similar is not None:

@@ -32,7 +32,8 @@ extern "C" {
  *    (bisbm_heatbath_run), pair reshuffles (bisbm_reshuffle_*, bisbm_debug_exp), chain traces (bisbm_trace_*), round recipes
  *    (bisbm_tempering_run_rounds, bisbm_tempering_rung_stats, bisbm_rounds_population_run), held conditionals and the least
  *    settled queries (bisbm_held_conditionals_*, bisbm_least_settled_topk, bisbm_debug_log), the eta plan of the last launch
- *    (bisbm_last_eta_plan), the route of the last launch (bisbm_last_sweep_route).  Additions only. */
+ *    (bisbm_last_eta_plan), the route of the last launch (bisbm_last_sweep_route), edge probabilities
+ *    (bisbm_edge_probs_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -360,6 +361,57 @@ int bisbm_pair_scores_set(bisbm_handle h, uint64_t n_pairs, const uint32_t *u, c
 int bisbm_pair_scores_accumulate(bisbm_handle h);
 int bisbm_pair_scores_reset(bisbm_handle h);
 int bisbm_pair_scores_get(bisbm_handle h, double *sum_out /* n_pairs, host */, uint64_t *terms_out);
+
+/* Edge probabilities: the exact change of the description length when one listed edge is added or removed, pooled over chains (no
+ * reference counterpart; graph-tool's get_edges_prob gives the same quantity).  For a chain with partition b,
+ *     P(G +- e | b) / P(G | b) = exp(-dS_e),   dS_e = S(G +- e, b) - S(G, b),
+ * S the full description length bisbm_entropy returns.  Pooled over chains it is the posterior-predictive odds of the edited graph.
+ * An edge changes no label, so the field energy Phi, a clamp and constraints do not enter.
+ * A PAIR is (u, v, kind): u of type a (u < na), v of type b (na <= v < n), kind BISBM_EDGE_ADD (one more edge u - v) or
+ * BISBM_EDGE_REMOVE (one edge u - v less).  mu: the number of CSR entries of u equal to v, the present multiplicity.  For a chain
+ * r = b_u, s = b_v; d_u, d_v: the CSR row lengths; E: the number of edges; eta_x[d] = eta[x][d] for 0 <= d <= max_degree and 0
+ * outside; lg: the engine's lgamma table; lbinom: lbinom_fast; logq(k, n): the log_q bisbm_entropy uses for a block of k edge
+ * ends and n nodes -- the non-fast instance in both RNG modes, the one bisbm_debug_log_q(..., fast = 0) probes.  All f64, no fused
+ * multiply-add, in this order.  ADD:
+ *     t_deg  = (lg(d_u+1) - lg(d_u+2)) + (lg(d_v+1) - lg(d_v+2))
+ *     t_m    = lg(m_rs+1) - lg(m_rs+2)
+ *     t_mr   = (lg(m_r[r]+2) - lg(m_r[r]+1)) + (lg(m_r[s]+2) - lg(m_r[s]+1))
+ *     t_eta  = ((lg(eta_r[d_u]+1) - lg(eta_r[d_u])) + (lg(eta_r[d_u+1]+1) - lg(eta_r[d_u+1]+2)))
+ *            + ((lg(eta_s[d_v]+1) - lg(eta_s[d_v])) + (lg(eta_s[d_v+1]+1) - lg(eta_s[d_v+1]+2)))
+ *     t_q    = (logq(m_r[r]+1, n_r[r]) - logq(m_r[r], n_r[r])) + (logq(m_r[s]+1, n_r[s]) - logq(m_r[s], n_r[s]))
+ *     t_mult = lg(mu+2) - lg(mu+1)
+ *     t_E    = lbinom(ka kb + E, E+1) - lbinom(ka kb + E - 1, E)
+ *     dS     = (((((t_deg + t_m) + t_mr) + t_eta) + t_q) + t_mult) + t_E
+ * REMOVE: the same seven terms in the same order with d+2 -> d in t_deg, t_m = lg(m_rs+1) - lg(m_rs), t_mr = (lg(m_r[r]) -
+ * lg(m_r[r]+1)) + ..., the second eta index d-1 instead of d+1, logq(m_r-1, n_r), t_mult = lg(mu) - lg(mu+1) and t_E =
+ * lbinom(ka kb + E - 2, E-1) - lbinom(ka kb + E - 1, E).  w = (dS > 700.0) ? 0.0 : exp(-dS) with the device's exp
+ * (bisbm_debug_exp).  A SAMPLE (accumulate) adds, for every pair and every counted chain, dS to dS_sum[pair] and w to
+ * w_sum[pair], one f64 add each, the chains one at a time in ascending chain index (chains grouped by shape: group by group,
+ * each with its own t_E), and the number of counted chains to `terms`; counted = every chain, or with replica exchange on only
+ * the chains on rung 0.  There are no floating-point atomics and the result does not depend on tiles or launch geometry: a
+ * sequential host loop gives the same bits.  The estimates: the mean dS = dS_sum / terms, and ln P = ln(w_sum / terms), the log
+ * posterior-predictive odds.  Both RNG modes, byte and two-byte labels, chains grouped by shape, several devices and handles with
+ * a clamp, constraints or fields are served; replica exchange over chains grouped by shape is BISBM_ERR_STATE, as for the pair
+ * scores.  Chain state is only read.  Sums and `terms` survive merges, splits, label-width switches and regrouping.
+ * set: uploads the pairs (they may repeat), replacing earlier ones and zeroing sums and terms; kind NULL: all ADD; what: 0 or
+ *   BISBM_EDGE_KEEP_LAST (keep every chain's dS of the last sample for get_last: n_chains * n_pairs doubles); n_pairs = 0 frees
+ *   everything.  BISBM_ERR_INVALID_ARG for a u outside [0, na), a v outside [na, n), an unknown kind, an unknown bit of `what`,
+ *   a REMOVE with mu = 0: bisbm_last_error names the first offending index and the earlier pairs and sums stay in place.
+ * accumulate: one sample; BISBM_ERR_STATE before bisbm_init / bisbm_shuffle or without pairs.
+ * reset: zeroes sums and terms, keeps the pairs.
+ * get: dS_sum[n_pairs], w_sum[n_pairs], mult_out[n_pairs] (mu) in the caller's order (several devices: the per-device sums added
+ *   on the host in device order) and terms; any pointer may be NULL.
+ * get_last: dS of pair `pair_index` (caller's order) in every chain at the last sample, NaN where the chain was not counted;
+ *   BISBM_ERR_STATE without BISBM_EDGE_KEEP_LAST or before the first sample. */
+#define BISBM_EDGE_ADD 0u
+#define BISBM_EDGE_REMOVE 1u
+#define BISBM_EDGE_KEEP_LAST 1u
+int bisbm_edge_probs_set(bisbm_handle h, uint64_t n_pairs, const uint32_t *u, const uint32_t *v,
+                         const uint8_t *kind /* NULL: all ADD */, uint32_t what);
+int bisbm_edge_probs_accumulate(bisbm_handle h);
+int bisbm_edge_probs_reset(bisbm_handle h);
+int bisbm_edge_probs_get(bisbm_handle h, double *dS_sum, double *w_sum, uint32_t *mult_out, uint64_t *terms);
+int bisbm_edge_probs_get_last(bisbm_handle h, uint64_t pair_index, double *dS_out /* n_chains, NaN where not counted */);
 
 /* Query scores: for one node, every node of the other type scored and ranked (no reference counterpart).  A QUERY is a node q of
  * either type; its CANDIDATES are all nodes of the other type in id order: na .. n-1 for q < na, 0 .. na-1 for q >= na
