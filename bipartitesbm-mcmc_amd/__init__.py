@@ -49,6 +49,9 @@ COASSIGN_CAND_TILE, COASSIGN_TILE = 1024, 16
 # (BISBM_EDGE_KEEP_LAST) and the pairs of one workgroup of the dS kernel (csrc/bisbm_engine.hpp: kEdgeProbsTile)
 EDGE_ADD, EDGE_REMOVE, EDGE_KEEP_LAST = 0, 1, 1
 EDGE_PROBS_TILE = 1024
+# bisbm_edge_queries_*: candidates x queries of one workgroup of the accumulate kernel (csrc/bisbm_kernels.hpp: kEdgeQueryCandTile,
+# kEdgeQueryTile); the largest k of bisbm_edge_queries_topk is QUERY_MAX_K, an entry past the eligible candidates QUERY_NONE
+EDGE_QUERY_CAND_TILE, EDGE_QUERY_TILE = 1024, 8
 # bisbm_foldin_*: the row kinds (BISBM_FOLDIN_RECOMMEND, BISBM_FOLDIN_SIMILAR) and candidates x virtual nodes of one workgroup of
 # the rows kernel (csrc/bisbm_kernels.hpp: kFoldinCandTile, kFoldinTile); the largest k of bisbm_foldin_topk is QUERY_MAX_K
 FOLDIN_RECOMMEND, FOLDIN_SIMILAR = 1, 2
@@ -151,6 +154,11 @@ ABI = {
     "bisbm_edge_probs_reset": (C.c_int, [C.c_void_p]),
     "bisbm_edge_probs_get": (C.c_int, [C.c_void_p, _f64p, _f64p, _u32p, _u64p]),
     "bisbm_edge_probs_get_last": (C.c_int, [C.c_void_p, C.c_uint64, _f64p]),
+    "bisbm_edge_queries_set": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
+    "bisbm_edge_queries_accumulate": (C.c_int, [C.c_void_p]),
+    "bisbm_edge_queries_reset": (C.c_int, [C.c_void_p]),
+    "bisbm_edge_queries_get_row": (C.c_int, [C.c_void_p, C.c_uint32, _f64p, _u32p, _u64p]),
+    "bisbm_edge_queries_topk": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, _u32p, _f64p, _u64p]),
     "bisbm_query_scores_set": (C.c_int, [C.c_void_p, C.c_uint32, _u32p]),
     "bisbm_query_scores_accumulate": (C.c_int, [C.c_void_p]),
     "bisbm_query_scores_reset": (C.c_int, [C.c_void_p]),
@@ -1382,6 +1390,73 @@ class BlockModel:
         nodes, sums, terms = self.query_topk(k, exclude_edges)
         return nodes, sums / terms, terms
 
+    # -- edge queries (include/bisbm.h, "Edge queries")
+    def edge_queries_set(self, queries):
+        """The nodes whose candidate edges are weighed: an integer array [Q] of node ids of either type (they may repeat);
+        replaces earlier queries and zeroes the sums.  Every query gets a row of one f64 per node of the other type on the
+        device.  An empty array frees everything."""
+        q = np.asarray(queries)
+        if q.size == 0:
+            q = np.zeros(0, dtype=np.uint32)
+        if q.ndim != 1 or not np.issubdtype(q.dtype, np.integer):
+            raise ValueError("queries must be a one-dimensional integer array")
+        if len(q) and (q.min() < 0 or q.max() > 0xFFFFFFFF):
+            raise ValueError("a query is outside [0, 2^32)")
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        self._check(self._L.bisbm_edge_queries_set(self._h, len(q), _p(q, _u32p)))
+        self.edge_query_nodes = q.copy()
+
+    def edge_queries_accumulate(self):
+        """One sample: every counted chain's exp(-dS) of adding the edge is added to the sum of every (query, candidate), chain
+        by chain in ascending order (with replica exchange on, the chains on rung 0 only)."""
+        self._check(self._L.bisbm_edge_queries_accumulate(self._h))
+
+    def edge_queries_reset(self):
+        self._check(self._L.bisbm_edge_queries_reset(self._h))
+
+    @staticmethod
+    def _log_odds(w_sum, terms):
+        """ln(w_sum / terms) with the C library's logarithm (the one the command line prints): NaN before the first sample,
+        -inf where every counted chain's exp(-dS) is 0"""
+        import math
+        w = np.asarray(w_sum, dtype=np.float64)
+        if not terms:
+            return np.full(w.shape, np.nan)
+        flat = [math.log(x) if x > 0 else (-math.inf if x == 0 else math.nan) for x in (w / float(terms)).ravel().tolist()]
+        return np.array(flat, dtype=np.float64).reshape(w.shape)
+
+    def edge_queries(self, i):
+        """A dict for the i-th query, arrays [n_other] over its candidates in id order (candidate j of a type-a query is node
+        na + j, of a type-b query node j): w_sum (float64), mult (uint32: the present multiplicity of the edge to the candidate),
+        terms, and log_prob = ln(w_sum / terms), the log posterior-predictive odds of the graph with the edge added."""
+        queries = getattr(self, "edge_query_nodes", np.zeros(0, dtype=np.uint32))
+        i = int(i)
+        if not 0 <= i < len(queries):
+            raise IndexError("query index %d: %d queries are set" % (i, len(queries)))
+        n_other = self.n - self.na if queries[i] < self.na else self.na
+        w, mult = np.zeros(n_other, dtype=np.float64), np.zeros(n_other, dtype=np.uint32)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_edge_queries_get_row(self._h, i, _p(w, _f64p), _p(mult, _u32p), C.byref(terms)))
+        return {"w_sum": w, "mult": mult, "terms": terms.value, "log_prob": self._log_odds(w, terms.value)}
+
+    def edge_queries_topk(self, k, exclude_edges=True):
+        """(nodes uint32 [Q, k], w_sum float64 [Q, k], terms): every query's k best candidates by pooled w_sum, descending, ties
+        to the lowest node id, selected on the device.  exclude_edges: the query's neighbours are not eligible.  Entries past
+        the eligible candidates are 0xffffffff / 0.0."""
+        Q = len(getattr(self, "edge_query_nodes", ()))
+        nodes = np.zeros((Q, int(k)), dtype=np.uint32)
+        sums = np.zeros((Q, int(k)), dtype=np.float64)
+        terms = C.c_uint64()
+        self._check(self._L.bisbm_edge_queries_topk(self._h, int(k), 1 if exclude_edges else 0, _p(nodes, _u32p), _p(sums, _f64p), C.byref(terms)))
+        return nodes, sums, terms.value
+
+    def recommend_edges(self, k, exclude_edges=True):
+        """(nodes uint32 [Q, k], w_sum float64 [Q, k], log_prob float64 [Q, k]): edge_queries_topk with log_prob =
+        ln(w_sum / terms), the log odds of adding the edge between the query and the node (entries past the eligible
+        candidates: node 0xffffffff, w_sum 0.0, log_prob -inf); edge_queries_topk gives the terms."""
+        nodes, sums, terms = self.edge_queries_topk(k, exclude_edges)
+        return nodes, sums, self._log_odds(sums, terms)
+
     # -- co-assignment (include/bisbm.h, "Co-assignment")
     def coassign_set(self, queries):
         """The nodes to find similar nodes for: an integer array [Q] of node ids of either type (they may repeat); replaces
@@ -2059,5 +2134,5 @@ metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
 from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_held_conditional_row, numpy_least_settled, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice, numpy_reshuffle_accept, numpy_reshuffle_launch, numpy_reshuffle_pair, numpy_reshuffle_q, numpy_reshuffle_step,  # noqa: E402,F401
-                          numpy_edge_dS, numpy_edge_multiplicity, numpy_pair_scores, numpy_query_topk, shard_chains)
+                          numpy_edge_dS, numpy_edge_multiplicity, numpy_edge_query_rows, numpy_pair_scores, numpy_query_topk, shard_chains)
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

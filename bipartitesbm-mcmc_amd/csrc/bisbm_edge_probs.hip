@@ -31,6 +31,9 @@
 // floating-point atomics, and a sequential host loop gives the same bits.  With BISBM_EDGE_KEEP_LAST every dS is also stored to
 // the chain's row of `last` (NaN for a chain that is not counted).  The pairs are held sorted by (u, v), so the b_u gather of a
 // tile walks a short stretch of the label array.
+//
+// The edge queries (bisbm_edge_queries.hip) take the block terms and the eta terms of a range from the same two kernels
+// (launch_edge_terms) and size their ranges by the same rule (edge_range_chains).
 #include "bisbm_device.hpp"
 #include "bisbm_engine.hpp"
 
@@ -197,14 +200,20 @@ __global__ __launch_bounds__(256) void edge_probs_kernel(EdgeProbParams p) {
     }
 }
 
-hipError_t launch_edge_probs(const EdgeProbParams& p, bool wide, hipStream_t stream) {
+// the block terms and the eta terms of the range of `p` (of p: the shape, the range, m_r, n_r, eta, rung, tab, blk, etat)
+hipError_t launch_terms(const EdgeProbParams& p, hipStream_t stream) {
     const uint32_t K = p.ka + p.kb;
     hipLaunchKernelGGL(edge_block_terms_kernel, dim3((p.n_range * K + 255) / 256), dim3(256), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const size_t cells = (size_t)p.n_range * K * (p.maxdeg + 1);
     hipLaunchKernelGGL(edge_eta_terms_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, p);
-    e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_edge_probs(const EdgeProbParams& p, bool wide, hipStream_t stream) {
+    const uint32_t K = p.ka + p.kb;
+    hipError_t e = launch_terms(p, stream);
     if (e != hipSuccess) return e;
     const dim3 grid((p.n_pairs + kEdgeProbsTile - 1) / kEdgeProbsTile), block(kLanes);
     if (wide) {
@@ -226,10 +235,7 @@ int add_sample(bisbm_engine* h, bisbm_engine* e) {
     if (!e->state_ready) return fail(h, BISBM_ERR_STATE, "call bisbm_init or bisbm_shuffle before bisbm_edge_probs_accumulate");
     const uint32_t K = e->ka + e->kb;
     const size_t eta_cells = (size_t)K * (e->maxdeg + 1);  // per chain
-    // chains per launch (BISBM_EDGE_RANGE_CHAINS=<n> in the environment, read at every call: n instead, for the tests)
-    size_t range = kEtaTermBytes / (2 * sizeof(double) * eta_cells);
-    if (const char* env = std::getenv("BISBM_EDGE_RANGE_CHAINS")) range = std::strtoull(env, nullptr, 10);
-    const uint32_t per = (uint32_t)std::min<size_t>(std::max<size_t>(range, 1), e->n_chains);
+    const uint32_t per = edge_range_chains(e);
     RESERVE(h, s.d_blk, (size_t)per * K * 4);
     RESERVE(h, s.d_etat, (size_t)per * eta_cells * 2);
     const HostTables& tab = *h->tab;
@@ -268,6 +274,25 @@ int add_sample(bisbm_engine* h, bisbm_engine* e) {
 }
 
 }  // namespace
+
+namespace bisbm {
+
+// chains per launch (BISBM_EDGE_RANGE_CHAINS=<n> in the environment, read at every call: n instead, for the tests)
+uint32_t edge_range_chains(const bisbm_engine* e) {
+    size_t range = kEtaTermBytes / (2 * sizeof(double) * (size_t)(e->ka + e->kb) * (e->maxdeg + 1));
+    if (const char* env = std::getenv("BISBM_EDGE_RANGE_CHAINS")) range = std::strtoull(env, nullptr, 10);
+    return (uint32_t)std::min<size_t>(std::max<size_t>(range, 1), e->n_chains);
+}
+
+hipError_t launch_edge_terms(const EdgeTermParams& t, hipStream_t stream) {
+    EdgeProbParams p{};
+    p.ka = t.ka, p.kb = t.kb, p.maxdeg = t.maxdeg, p.c0 = t.c0, p.n_range = t.n_range;
+    p.m_r = t.m_r, p.n_r = t.n_r, p.eta = t.eta, p.rung = t.rung, p.tab = t.tab;
+    p.blk = t.blk, p.etat = t.etat;
+    return launch_terms(p, stream);
+}
+
+}  // namespace bisbm
 
 extern "C" {
 

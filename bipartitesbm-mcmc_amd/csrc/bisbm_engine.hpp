@@ -18,6 +18,7 @@
 //   bisbm_pair_scores.hip  posterior-predictive pair scores pooled over chains: its kernels and its part of the C ABI
 //   bisbm_edge_probs.hip   exact edge probabilities: dS of adding or removing a listed edge, pooled over chains; kernels and C ABI
 //   bisbm_query_scores.hip  query scores: every candidate of a node scored over the chains; kernels and C ABI
+//   bisbm_edge_queries.hip  edge queries: every candidate of a node weighed by the exact dS of adding the edge; kernel and C ABI
 //   bisbm_coassign.hip   co-assignment: how often every node of a query's own type shares its block; kernels and C ABI
 //   bisbm_foldin.hip     fold-in queries: block posterior, recommendations and peers of a node that is not in the graph; kernels and C ABI
 //   bisbm_topk.hip       the best k candidates of every query, for the three units above: the mask, select and add kernels, the
@@ -259,6 +260,31 @@ struct QueryScoreState {
     DeviceBuf<uint64_t> d_off;    // [n + 1] `off`
     DeviceBuf<uint32_t> d_list;   // [n] indices of the type-a queries, then of the type-b queries, each ascending
     DeviceBuf<double> d_sum;      // [off[n]] running sums, query by query, candidates in id order
+    DeviceBuf<TopkCand> d_cand;   // [n] topk: every query's first candidate (the other type's first node), no self
+    TopkScratch<double> topk;
+};
+
+// Edge queries (bisbm_edge_queries.hip).  As QueryScoreState: the sums belong to the engine that owns the graph on a device, the
+// container of device entries keeps the host side (n, q, off, nbr_ptr, nbr, mult) only.
+struct EdgeQueryState {
+    uint32_t n = 0;               // queries set (0: none)
+    uint32_t n_a = 0;             // ... of type a
+    uint64_t terms = 0;           // chain terms added to every sum since the last set / reset
+    std::vector<uint32_t> q;      // [n] node of every query, caller's order
+    std::vector<uint64_t> off;    // [n + 1] first cell of every query's row; off[n]: cells in all
+    std::vector<uint64_t> nbr_ptr;  // [n + 1] first entry of every query's distinct neighbours
+    std::vector<uint32_t> nbr;    // the distinct neighbours of every query, ascending
+    std::vector<uint32_t> mult;   // ... and how many CSR entries of the query each has
+    DeviceBuf<uint32_t> d_q;      // [n] `q`
+    DeviceBuf<uint64_t> d_off;    // [n + 1] `off`
+    DeviceBuf<uint32_t> d_list;   // [n] indices of the type-a queries, then of the type-b queries, each ascending
+    DeviceBuf<uint64_t> d_nbr_ptr;  // `nbr_ptr`
+    DeviceBuf<uint32_t> d_nbr;    // `nbr`
+    DeviceBuf<double> d_nbr_tmult;  // lg(mu + 2) - lg(mu + 1) of every entry of `nbr`, from the host's table
+    DeviceBuf<double> d_sum;      // [off[n]] running sums of w, query by query, candidates in id order
+    DeviceBuf<double> d_blk;      // [chains of a launch][K][4] block terms
+    DeviceBuf<double> d_etat;     // [chains of a launch][K][max_degree + 1][2] eta terms
+    DeviceBuf<double> d_tm;       // [chains of a launch][ka*kb] t_m terms
     DeviceBuf<TopkCand> d_cand;   // [n] topk: every query's first candidate (the other type's first node), no self
     TopkScratch<double> topk;
 };
@@ -579,6 +605,7 @@ struct bisbm_engine {
     bisbm::PairScoreState pairs;
     bisbm::EdgeProbState edges;
     bisbm::QueryScoreState queries;
+    bisbm::EdgeQueryState edge_queries;
     bisbm::CoassignState coassign;
     bisbm::FoldinState foldin;
     bisbm::ConditionalState cond;
@@ -788,6 +815,10 @@ template <class T>
 int topk_select(bisbm_engine* h, const char* fn, const std::vector<const T*>& cells, const std::vector<uint64_t>& off, TopkScratch<T>& w,
                 const uint64_t* d_off, const TopkCand* d_cand, const TopkMaskLists* lists, uint32_t k, uint32_t* node_out, T* val_out,
                 bool ascending = false);
+
+// edge probabilities and edge queries: how many consecutive chains of `e` one launch serves -- as many as keep the eta terms
+// under the byte cap of a launch; bisbm_edge_probs.hip
+uint32_t edge_range_chains(const bisbm_engine* e);
 
 bool any_grouped(bisbm_engine* h);  // does the handle, or one of its device entries, keep its chains grouped by shape?
 bool any_wide(bisbm_engine* h);     // does some leaf hold two-byte labels?

@@ -50,6 +50,7 @@ void free_all(bisbm_engine* h) {
     h->queries = QueryScoreState(), h->coassign = CoassignState(), h->foldin = FoldinState(), h->cond = ConditionalState();
     h->clamp = ClampState();
     h->edges = EdgeProbState();
+    h->edge_queries = EdgeQueryState();
     h->constraints = ConstraintState();
     h->fields = FieldState();
     h->d_T.reset();

@@ -242,6 +242,52 @@ constexpr uint32_t kQueryCandTile = 1024;  // candidates per workgroup: 256 lane
 constexpr uint32_t kQueryTile = 8;         // queries per workgroup
 constexpr uint32_t kQueryMaxK = 1024;      // bisbm_query_scores_topk: the largest k (the selection is kept in LDS)
 
+// Edge queries (bisbm_edge_queries.hip): every candidate of a node weighed by the exact dS of adding the edge.
+// The terms of dS that belong to (chain, block) and to (chain, block, degree) for chains c0 .. c0 + n_range - 1 of one engine:
+// what the two term kernels of bisbm_edge_probs.hip fill, for the listed call and for this one alike.
+struct EdgeTermParams {
+    uint32_t ka, kb, maxdeg, c0, n_range;
+    const int32_t *m_r, *n_r;  // [chain][K]
+    const uint32_t* eta;       // [chain][K][maxdeg + 1]
+    const uint32_t* rung;      // replica exchange: only chains with rung[c] == 0 are filled; NULL: every chain
+    Tables tab;
+    double* blk;               // [n_range][K][4] {t_mr half, t_q half} of ADD, of REMOVE
+    double* etat;              // [n_range][K][maxdeg + 1][2] {lg(eta+1) - lg(eta), lg(eta+1) - lg(eta+2)}
+};
+hipError_t launch_edge_terms(const EdgeTermParams& p, hipStream_t stream);
+// One range of chains of one engine into the rows of the queries of one type.  A workgroup owns kEdgeQueryCandTile candidates x
+// kEdgeQueryTile queries of the list and adds w = exp(-dS) of the counted chains of the range onto its cells of `sum` one at a
+// time, in ascending chain order; the ranges of a sample follow each other on the stream.
+struct EdgeQueryParams {
+    uint32_t n, na, ka, kb, maxdeg, c0, n_range;
+    uint32_t type;            // 0: type-a queries (candidates na .. n-1), 1: type-b queries (candidates 0 .. na-1)
+    uint32_t n_list;          // queries of this type
+    uint32_t cand_tiles, q_tile0;  // the launcher's: candidate tiles of the type, first query tile of the launch
+    const uint32_t* list;     // [n_list] their indices in the caller's order
+    const uint32_t* queries;  // [n_queries] node of every query
+    const uint64_t* off;      // [n_queries + 1] first cell of every query's row in `sum`
+    const uint32_t* rowptr;
+    // the present edges of every query: its distinct neighbours ascending, nbr[nbr_ptr[i]] .. nbr[nbr_ptr[i + 1] - 1], and
+    // t_mult = lg(mu + 2) - lg(mu + 1) of each
+    const uint64_t* nbr_ptr;  // [n_queries + 1]
+    const uint32_t* nbr;
+    const double* nbr_tmult;
+    const uint8_t* labels;    // byte labels
+    size_t label_stride;      // (a multiple of 4: a lane reads four candidates' labels as one word)
+    const int32_t* m;         // [chain][ka*kb]
+    const uint32_t* rung;     // replica exchange: only chains with rung[c] == 0 are counted; NULL: every chain
+    const double* lg;         // the lgamma table (t_deg, t_m)
+    uint64_t lg_size;
+    double tE;                // t_E of ADD for this shape
+    const double* blk;        // [n_range][K][4] block terms of the range
+    const double* etat;       // [n_range][K][maxdeg + 1][2] eta terms of the range
+    double* tm;               // [n_range][ka*kb] t_m = lg(m+1) - lg(m+2) of every cell of the quadrant, of the range
+    double* sum;
+};
+constexpr uint32_t kEdgeQueryCandTile = 1024;  // candidates per workgroup: 256 lanes, one word of 4 labels each
+constexpr uint32_t kEdgeQueryTile = 8;         // queries per workgroup
+hipError_t launch_edge_queries(const EdgeQueryParams& p, hipStream_t stream);
+
 // Top-k selection (bisbm_topk.hip): the best k candidates of every query of one chunk (q0 .. q0 + n_q - 1), for query scores,
 // co-assignment and fold-in rows alike.  The candidates of query qi are the off[qi + 1] - off[qi] cells of its row, in id order;
 // rows / mask hold the chunk's cells from cell off[q0] on.  A candidate is eligible iff it is not masked and is not `self`.

@@ -258,6 +258,70 @@ def numpy_edge_dS(m, m_r, n_r, eta, deg, labels, ka, kb, E, u, v, kind, mult, lg
     return (((((t_deg + t_m) + t_mr) + t_eta) + t_q) + t_mult) + t_E
 
 
+def numpy_edge_query_mult(rowptr, col, na, queries):
+    """mu of every (query, candidate) of the edge queries (include/bisbm.h, "Edge queries"): one uint32 row per query over the
+    nodes of the other type in id order -- how many entries of the query's CSR row name the candidate."""
+    rowptr, col = np.asarray(rowptr).astype(np.int64), np.asarray(col).astype(np.int64)
+    n, na = len(rowptr) - 1, int(na)
+    rows = []
+    for q in np.asarray(queries, dtype=np.int64).tolist():
+        first, n_other = (na, n - na) if q < na else (0, na)
+        rows.append(np.bincount(col[rowptr[q]:rowptr[q + 1]] - first, minlength=n_other).astype(np.uint32))
+    return rows
+
+
+def numpy_edge_query_rows(m, m_r, n_r, eta, deg, labels, na, ka, kb, E, queries, mult, lg, logq):
+    """Host statement of one chain's rows of the edge queries (include/bisbm.h, "Edge queries"): for every query the ADD dS of
+    numpy_edge_dS for all its candidates (the nodes of the other type in id order) at once -- the same seven terms from the same
+    f64 operations in the same order, elementwise over the candidates, so every entry carries the bits of numpy_edge_dS for the
+    pair (type-a node, type-b node) that query and candidate form.  Arguments as numpy_edge_dS; `queries`: node ids of either
+    type; `mult`: the rows of numpy_edge_query_mult.  Returns a list of float64 rows; w is (dS > 700.0) ? 0.0 : exp(-dS)."""
+    m, m_r, n_r, eta = np.asarray(m), np.asarray(m_r), np.asarray(n_r), np.asarray(eta)
+    deg, labels = np.asarray(deg).astype(np.int64), np.asarray(labels).astype(np.int64)
+    n, na, ka, kb, E = len(labels), int(na), int(ka), int(kb), int(E)
+    K, D = ka + kb, eta.shape[1]
+
+    def lbinom(N, k):
+        if N == 0 or k == 0 or k > N:
+            return 0.0
+        return (lg(N + 1) - lg(k + 1)) - lg(N - k + 1)
+
+    def table(keys, f):
+        """f over the distinct keys, spread back: a float64 array shaped like `keys` (the last axis holds a key's parts)"""
+        keys = np.asarray(keys, dtype=np.int64)
+        flat = keys.reshape(-1, keys.shape[-1])
+        uniq, inv = np.unique(flat, axis=0, return_inverse=True)
+        vals = np.array([f(*row) for row in uniq.tolist()], dtype=np.float64)
+        return vals[np.asarray(inv).reshape(-1)].reshape(keys.shape[:-1])
+    # per block: the halves of t_mr and t_q
+    h_mr = table(np.stack([m_r], axis=-1), lambda a: lg(a + 2) - lg(a + 1))
+    h_q = table(np.stack([m_r, n_r], axis=-1), lambda a, b: logq(a + 1, b) - logq(a, b))
+    # per node: the halves of t_deg and t_eta
+    h_deg = table(np.stack([deg], axis=-1), lambda d: lg(d + 1) - lg(d + 2))
+    e0 = eta[labels, deg].astype(np.int64)
+    e1 = np.where(deg + 1 < D, eta[labels, np.minimum(deg + 1, D - 1)], 0).astype(np.int64)
+    h_eta = table(np.stack([e0, e1], axis=-1), lambda a, b: (lg(a + 1) - lg(a)) + (lg(b + 1) - lg(b + 2)))
+    # per cell of the quadrant: t_m
+    t_m = table(np.stack([m[:ka, ka:K]], axis=-1), lambda a: lg(a + 1) - lg(a + 2))
+    cells = ka * kb
+    t_E = lbinom(cells + E, E + 1) - lbinom(cells + E - 1, E)
+    rows = []
+    for q, mu in zip(np.asarray(queries, dtype=np.int64).tolist(), mult):
+        if q < na:  # the query is u, the candidates are the v
+            u, v = np.full(n - na, q, dtype=np.int64), np.arange(na, n)
+        else:
+            u, v = np.arange(na), np.full(na, q, dtype=np.int64)
+        r, s = labels[u], labels[v]
+        t_mult = table(np.stack([np.asarray(mu)], axis=-1), lambda a: lg(a + 2) - lg(a + 1))
+        dS = (h_deg[u] + h_deg[v]) + t_m[r, s - ka]
+        dS = dS + (h_mr[r] + h_mr[s])
+        dS = dS + (h_eta[u] + h_eta[v])
+        dS = dS + (h_q[r] + h_q[s])
+        dS = dS + t_mult
+        rows.append(dS + t_E)
+    return rows
+
+
 QUERY_NONE = 0xFFFFFFFF  # bisbm_query_scores_topk: an entry past the eligible candidates
 
 

@@ -505,6 +505,27 @@ public:
         sums.assign(queries_.size() * (size_t)k, 0.);
         check(bisbm_query_scores_topk(h_, k, exclude_neighbours ? 1 : 0, nodes.data(), sums.data(), &terms));
     }
+    // edge queries (include/bisbm.h): the query nodes (either type), a sample of every counted chain, one query's row of
+    // w_sum = sum of exp(-dS) over its candidates with their present multiplicities, and every query's k best candidates selected
+    // on the device (nodes / w_sums [queries * k], 0xffffffff / 0.0 past the eligible ones; the log odds of an entry are
+    // ln(w_sum / terms))
+    void edge_queries_set(const std::vector<uint32_t>& queries) {
+        check(bisbm_edge_queries_set(h_, (uint32_t)queries.size(), queries.data()));
+        edge_queries_ = queries;
+    }
+    void edge_queries_accumulate() { check(bisbm_edge_queries_accumulate(h_)); }
+    void edge_queries_reset() { check(bisbm_edge_queries_reset(h_)); }
+    void edge_queries_row(uint32_t query_index, std::vector<double>& w_sum, std::vector<uint32_t>& mult, uint64_t& terms) {
+        if (query_index >= edge_queries_.size()) throw std::runtime_error("edge_queries_row: no such query");
+        const size_t len = edge_queries_[query_index] < na_ ? n_ - na_ : na_;
+        w_sum.assign(len, 0.), mult.assign(len, 0u);
+        check(bisbm_edge_queries_get_row(h_, query_index, w_sum.data(), mult.data(), &terms));
+    }
+    void edge_queries_topk(uint32_t k, bool exclude_neighbours, std::vector<uint32_t>& nodes, std::vector<double>& w_sums, uint64_t& terms) {
+        nodes.assign(edge_queries_.size() * (size_t)k, 0);
+        w_sums.assign(edge_queries_.size() * (size_t)k, 0.);
+        check(bisbm_edge_queries_topk(h_, k, exclude_neighbours ? 1 : 0, nodes.data(), w_sums.data(), &terms));
+    }
     // co-assignment (include/bisbm.h): the query nodes (either type), a sample of every counted chain, one query's row over the
     // nodes of its own type in id order, and every query's k most often co-assigned nodes selected on the device (nodes / counts
     // [queries * k], 0xffffffff / 0 past the eligible ones; the estimate of an entry is count / terms)
@@ -745,7 +766,7 @@ private:
     }
     bisbm_handle h_ = nullptr;
     size_t KA_, KB_, n_ = 0, na_ = 0, n_pairs_ = 0, n_edge_pairs_ = 0;
-    std::vector<uint32_t> queries_, coassign_queries_;
+    std::vector<uint32_t> queries_, edge_queries_, coassign_queries_;
     std::vector<uint8_t> foldin_types_;
     uint32_t n_conditionals_ = 0;
     uint32_t n_chains_;

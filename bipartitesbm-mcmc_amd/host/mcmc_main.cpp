@@ -5,7 +5,7 @@
 // newline), "acceptance ratio" and summary() on clog (:483-485).  Boost.program_options is replaced by a
 // small parser with the same surface (long/short names, `--opt=value`, multitoken options).
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
-// --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --edge_probs, --recommend, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
+// --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --edge_probs, --recommend, --recommend_edges, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
 // --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace, --rung_moves, --population_moves,
 // --clamp, --constraints, --fields.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
@@ -56,6 +56,7 @@ const option_spec kOptions[] = {
     {"edge_probs", 0, 2},
     {"population", 0, 2},       {"population_sweeps", 0, 1},
     {"recommend", 0, 2},        {"include_edges", 0, 0},
+    {"recommend_edges", 0, 2},
     {"similar", 0, 2},
     {"foldin", 0, 2},           {"foldin_alpha", 0, 1},
     {"conditionals", 0, 2},     {"conditionals_beta", 0, 1},
@@ -289,7 +290,15 @@ void print_help(const char* argv0) {
                  "                                        candidates of every query that are not its neighbours already, as\n"
                  "                                        `query candidate score` lines in rank order (score descending, ties to\n"
                  "                                        the lowest id; score = the mean over samples and chains, %.17g).\n"
-                 "  --include_edges                       With --recommend: the query's neighbours are ranked as well.\n"
+                 "  --recommend_edges QUERIES OUT K       With --marginalize: QUERIES as for --recommend; every sample adds, for the\n"
+                 "                                        node and EVERY node of the other type, every sampled chain's exp(-dS) of\n"
+                 "                                        the exact change dS of the description length when the edge between the\n"
+                 "                                        two is added (the quantity of --edge_probs), and OUT receives the K best\n"
+                 "                                        candidates of every query that are not its neighbours already, as\n"
+                 "                                        `query candidate score log_prob` lines in rank order (score = mean\n"
+                 "                                        exp(-dS) descending, ties to the lowest id; log_prob = ln score; %.17g).\n"
+                 "  --include_edges                       With --recommend or --recommend_edges: the query's neighbours are ranked\n"
+                 "                                        as well.\n"
                  "  --similar QUERIES OUT K               With --marginalize: QUERIES holds one node id per line (either type);\n"
                  "                                        every sample counts, for EVERY node of the query's own type, the\n"
                  "                                        sampled chains in which it shares the query's block, and OUT receives\n"
@@ -399,7 +408,11 @@ int main(int argc, char const* argv[]) {
         std::cerr << "--recommend ranks the candidates of nodes over the samples of the chains: it needs --marginalize.\n";
         return 1;
     }
-    if (count("include_edges") && !count("recommend")) {
+    if (count("recommend_edges") && !count("marginalize")) {
+        std::cerr << "--recommend_edges ranks the candidates of nodes over the samples of the chains: it needs --marginalize.\n";
+        return 1;
+    }
+    if (count("include_edges") && !count("recommend") && !count("recommend_edges")) {
         std::cerr << "--include_edges keeps a query's neighbours among its candidates: it needs --recommend.\n";
         return 1;
     }
@@ -417,6 +430,21 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
         recommend_k = (uint32_t)k;
+    }
+    uint32_t recommend_edges_k = 0;
+    if (var_map.count("recommend_edges")) {
+        if (var_map["recommend_edges"].size() != 3) {
+            std::cerr << "Invalid --recommend_edges. Three arguments: the file of query nodes to read, the file to write and K.\n";
+            return 1;
+        }
+        const std::string tok = var_map["recommend_edges"][2];
+        char* end = nullptr;
+        const unsigned long k = std::strtoul(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0' || tok[0] == '-' || tok[0] == '+' || k == 0 || k > 0xffffffffUL) {
+            std::cerr << "Invalid --recommend_edges. K must be a positive integer, e.g. --recommend_edges queries.txt out.txt 10.\n";
+            return 1;
+        }
+        recommend_edges_k = (uint32_t)k;
     }
     if (count("similar") && !count("marginalize")) {
         std::cerr << "--similar counts the chains in which nodes share a block over the samples of the chains: it needs --marginalize.\n";
@@ -828,6 +856,31 @@ int main(int argc, char const* argv[]) {
                 return 1;
             }
             recommend_queries.push_back((uint32_t)id);
+        }
+    }
+    // --recommend_edges: likewise
+    std::vector<uint32_t> recommend_edges_queries;
+    if (var_map.count("recommend_edges")) {
+        const std::string in = var_map["recommend_edges"][0];
+        std::ifstream file(in);
+        if (!file) {
+            std::cerr << "[error] --recommend_edges: cannot read " << in << "\n";
+            return 1;
+        }
+        std::string text;
+        for (size_t line_no = 1; std::getline(file, text); ++line_no) {
+            const size_t b = text.find_first_not_of(" \t\r");
+            if (b == std::string::npos) continue;  // (an empty line)
+            const size_t e = text.find_last_not_of(" \t\r");
+            const std::string tok = text.substr(b, e - b + 1);
+            char* end = nullptr;
+            const unsigned long long id = std::strtoull(tok.c_str(), &end, 10);
+            if (*end != '\0' || tok[0] == '-' || tok[0] == '+' || id >= NA + NB) {
+                std::cerr << "[error] --recommend_edges: line " << line_no << " of " << in << " (" << tok << ") must name a node [0, " << NA + NB
+                          << ")\n";
+                return 1;
+            }
+            recommend_edges_queries.push_back((uint32_t)id);
         }
     }
     // --similar: likewise
@@ -1606,6 +1659,11 @@ int main(int argc, char const* argv[]) {
                 for (uint32_t v : recommend_queries) q.push_back(new_id.empty() ? v : new_id[v]);
                 blockmodel.query_scores_set(q);
             }
+            if (!recommend_edges_queries.empty()) {
+                std::vector<uint32_t> q;
+                for (uint32_t v : recommend_edges_queries) q.push_back(new_id.empty() ? v : new_id[v]);
+                blockmodel.edge_queries_set(q);
+            }
             if (!similar_queries.empty()) {
                 std::vector<uint32_t> q;
                 for (uint32_t v : similar_queries) q.push_back(new_id.empty() ? v : new_id[v]);
@@ -1642,6 +1700,7 @@ int main(int argc, char const* argv[]) {
                 if (!score_pairs.empty()) blockmodel.pair_scores_accumulate();
                 if (!edge_prob_pairs.empty()) blockmodel.edge_probs_accumulate();
                 if (!recommend_queries.empty()) blockmodel.query_scores_accumulate();
+                if (!recommend_edges_queries.empty()) blockmodel.edge_queries_accumulate();
                 if (!similar_queries.empty()) blockmodel.coassign_accumulate();
             }
             std::clog << "marginalize: burn-in " << burn_in / N << " sweeps, " << n_samples << " samples " << sweeps_between
@@ -1774,6 +1833,33 @@ int main(int argc, char const* argv[]) {
                 }
                 std::clog << "recommend: " << recommend_queries.size() << " query node(s), " << recommend_k << " candidate(s) each, " << terms
                           << " chain term(s) per score -> " << out_path << "\n";
+            }
+            if (var_map.count("recommend_edges")) {
+                const std::string out_path = var_map["recommend_edges"][1];
+                std::ofstream out(out_path);
+                uint64_t terms = 0;
+                std::vector<uint32_t> nodes;
+                std::vector<double> sums;
+                if (!recommend_edges_queries.empty()) blockmodel.edge_queries_topk(recommend_edges_k, !count("include_edges"), nodes, sums, terms);
+                std::vector<uint32_t> old_id(new_id.size());
+                for (size_t v = 0; v < new_id.size(); ++v) old_id[new_id[v]] = (uint32_t)v;
+                char line[160];
+                for (size_t i = 0; i < recommend_edges_queries.size(); ++i)
+                    for (size_t r = 0; r < recommend_edges_k; ++r) {
+                        const uint32_t node = nodes[i * recommend_edges_k + r];
+                        if (node == 0xffffffffu) continue;  // (fewer than K candidates are eligible)
+                        const double score = sums[i * recommend_edges_k + r] / (double)terms;
+                        std::snprintf(line, sizeof(line), "%u %u %.17g %.17g\n", recommend_edges_queries[i], new_id.empty() ? node : old_id[node], score,
+                                      score > 0 ? std::log(score) : -INFINITY);
+                        out << line;
+                    }
+                out.close();
+                if (!out) {
+                    std::cerr << "[error] --recommend_edges: cannot write " << out_path << "\n";
+                    return 1;
+                }
+                std::clog << "recommend_edges: " << recommend_edges_queries.size() << " query node(s), " << recommend_edges_k << " candidate(s) each, "
+                          << terms << " chain term(s) per score -> " << out_path << "\n";
             }
             if (var_map.count("similar")) {
                 const std::string out_path = var_map["similar"][1];

@@ -19,7 +19,8 @@ import numpy as np
 def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, shard=None, device_counts=None,
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
                 similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None, rung_moves=None, blocks=False,
-                clamp=None, constraints=None, fields=None, conditionals_held=False, least_settled=None, edge_probs=None):
+                clamp=None, constraints=None, fields=None, conditionals_held=False, least_settled=None, edge_probs=None,
+                recommend_edges=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -54,6 +55,10 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     `recommend`: (queries, k) or (queries, k, exclude_edges) (include/bisbm.h, "Query scores"): the queries are set, with zeroed
     sums, before the first sample, every sample also adds every counted chain's term to every (query, candidate) sum, and the
     return value becomes (labels, counts, model.recommend(k, exclude_edges)) -- the chains of this rank only.
+    `recommend_edges`: (queries, k) or (queries, k, exclude_edges) (include/bisbm.h, "Edge queries"): the queries are set, with
+    zeroed sums, before the first sample, every sample also adds every counted chain's exp(-dS) of adding the edge to every (query,
+    candidate) sum, and model.recommend_edges(k, exclude_edges) -- (nodes, w_sum, log_prob) -- is appended to the return
+    value, after `recommend`'s element when both are asked for.  The chains of this rank only.
     `similar`: (queries, k) (include/bisbm.h, "Co-assignment"): the queries are set, with zeroed counts, before the first sample,
     every sample also counts in which chains every node of a query's own type shares its block, and model.similar(k) -- (nodes,
     count / terms, terms) -- is appended as the last element of the return value.  The chains of this rank only: pooling over
@@ -127,6 +132,9 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     if recommend is not None:
         model.query_scores_set(recommend[0])
         model.query_scores_reset()
+    if recommend_edges is not None:
+        model.edge_queries_set(recommend_edges[0])
+        model.edge_queries_reset()
     if similar is not None:
         model.coassign_set(similar[0])
         model.coassign_reset()
@@ -153,6 +161,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
         out = (labels, counts)
         if recommend is not None:
             out += (model.recommend(int(recommend[1]), bool(recommend[2]) if len(recommend) > 2 else True),)
+        if recommend_edges is not None:
+            out += (model.recommend_edges(int(recommend_edges[1]), bool(recommend_edges[2]) if len(recommend_edges) > 2 else True),)
         if similar is not None:
             out += (model.similar(int(similar[1])),)
         if foldin is not None:
@@ -181,6 +191,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
                 model.edge_probs_accumulate()
             if recommend is not None:
                 model.query_scores_accumulate()
+            if recommend_edges is not None:
+                model.edge_queries_accumulate()
             if similar is not None:
                 model.coassign_accumulate()
             if foldin is not None:
@@ -219,6 +231,8 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
             model.edge_probs_accumulate()
         if recommend is not None:
             model.query_scores_accumulate()
+        if recommend_edges is not None:
+            model.edge_queries_accumulate()
         if similar is not None:
             model.coassign_accumulate()
         if foldin is not None:

@@ -33,7 +33,7 @@ extern "C" {
  *    (bisbm_tempering_run_rounds, bisbm_tempering_rung_stats, bisbm_rounds_population_run), held conditionals and the least
  *    settled queries (bisbm_held_conditionals_*, bisbm_least_settled_topk, bisbm_debug_log), the eta plan of the last launch
  *    (bisbm_last_eta_plan), the route of the last launch (bisbm_last_sweep_route), edge probabilities
- *    (bisbm_edge_probs_*).  Additions only. */
+ *    (bisbm_edge_probs_*), edge queries (bisbm_edge_queries_*).  Additions only. */
 #define BISBM_ABI_VERSION 3
 
 typedef struct bisbm_engine *bisbm_handle;
@@ -451,6 +451,46 @@ int bisbm_query_scores_reset(bisbm_handle h);
 int bisbm_query_scores_get_row(bisbm_handle h, uint32_t query_index, double *sum_out /* n_other, host */, uint64_t *terms_out);
 int bisbm_query_scores_topk(bisbm_handle h, uint32_t k, int exclude_neighbours, uint32_t *node_out /* n_queries * k, host */,
                             double *sum_out /* n_queries * k, host, may be NULL */, uint64_t *terms_out);
+
+/* Edge queries: for one node, every node of the other type weighed by the exact odds of the edge to it, and ranked (no reference
+ * counterpart).  Queries and candidates are those of the query scores above: a QUERY is a node q of either type, its CANDIDATES
+ * are all nodes of the other type in id order, na .. n-1 for q < na, 0 .. na-1 for q >= na (n_other of them).  One chain's term
+ * for (query, candidate) is
+ *     w = (dS > 700.0) ? 0.0 : exp(-dS)
+ * with dS the ADD dS of "Edge probabilities" above for the pair (type-a node u, type-b node v) the two form: its seven terms in
+ * its order, with the pair's present multiplicity mu, the same f64 operations -- bit-equal to what bisbm_edge_probs_* gives that
+ * chain for the listed pair (u, v, BISBM_EDGE_ADD), also where the candidate is a neighbour of the query already, by one edge or
+ * by several.  (Every two-sided term of dS is (half of u) + (half of v), and IEEE addition commutes: which of the two is the query
+ * changes no bit.)  A SAMPLE (bisbm_edge_queries_accumulate) adds w of every counted chain to w_sum[query][candidate] and the
+ * number of counted chains to `terms`; counted = every chain, or with replica exchange on only the chains on rung 0.  The order
+ * of the additions is that of the query scores and the edge probabilities: per device one f64 add per counted chain in
+ * ascending chain index (chains grouped by shape: group by group in group order, each with its own t_E), no floating-point
+ * atomics, no partial sums; the result does not depend on tiles, ranges of chains or launch geometry and a sequential loop on
+ * the host reproduces it bit for bit.  Several devices: each keeps the sums of its own chains, added in device order when read.
+ * ln(w_sum / terms) is the posterior-predictive log odds of the graph with the edge added.  Only w_sum is kept (sums of dS can
+ * be negative and are no radix keys; the mean dS stays with bisbm_edge_probs_*): 8 bytes per (query, candidate) per device.
+ * Both RNG modes, chains grouped by shape, several devices, replica exchange and handles with a clamp, constraints or fields
+ * are served (an edge changes no label); replica exchange over chains grouped by shape is BISBM_ERR_STATE, as for the pair
+ * scores.  Chain state is only read.  Sums and terms survive merges, splits and regrouping by shape.
+ * set: as bisbm_query_scores_set -- uploads n_queries nodes (they may repeat, both types may be mixed), replacing earlier ones,
+ *   allocates and zeroes the sums; a query >= n is BISBM_ERR_INVALID_ARG, bisbm_last_error names the first offending index and
+ *   the earlier queries and sums stay in place; n_queries = 0 frees everything.  It also finds, per query, its distinct
+ *   neighbours and their mu in the CSR.
+ * accumulate: one sample; BISBM_ERR_STATE before bisbm_init / bisbm_shuffle or without queries; BISBM_ERR_UNSUPPORTED on a
+ *   handle with two-byte labels (KA + KB > 256): bisbm_edge_probs_* serves it, list the pairs there.
+ * reset: zeroes sums and terms, keeps the queries.
+ * get_row: the row of query `query_index` (its position in the array given to set) in candidate-id order: w_sum_out[n_other],
+ *   mult_out[n_other] (mu of every candidate, 0 where there is no edge) and terms; every pointer may be NULL.
+ * topk: the contract of bisbm_query_scores_topk on w_sum -- descending, ties to the lowest node id, with exclude_neighbours != 0
+ *   the nodes of the query's CSR row are not eligible, 0xffffffff / 0.0 past the eligible candidates, values bit-equal to
+ *   get_row's; k = 0 is BISBM_ERR_INVALID_ARG, k > 1024 BISBM_ERR_UNSUPPORTED, terms == 0 BISBM_ERR_STATE. */
+int bisbm_edge_queries_set(bisbm_handle h, uint32_t n_queries, const uint32_t *queries);
+int bisbm_edge_queries_accumulate(bisbm_handle h);
+int bisbm_edge_queries_reset(bisbm_handle h);
+int bisbm_edge_queries_get_row(bisbm_handle h, uint32_t query_index, double *w_sum_out /* n_other, host */,
+                               uint32_t *mult_out /* n_other, host */, uint64_t *terms_out);
+int bisbm_edge_queries_topk(bisbm_handle h, uint32_t k, int exclude_neighbours, uint32_t *node_out /* n_queries * k, host */,
+                            double *w_sum_out /* n_queries * k, host, may be NULL */, uint64_t *terms_out);
 
 /* Co-assignment: for one node, how often every node of its OWN type shares its block (no reference counterpart).  The posterior
  * co-assignment probability P(b_v = b_q | graph) is one row of the consensus (co-classification) matrix; the full n x n matrix
