@@ -66,6 +66,11 @@ PHILOX_PURPOSE_HEATBATH = 9
 # ... and of the pair reshuffles (PHX_RESHUFFLE), and the record type of a move without a pair (BISBM_RESHUFFLE_NONE)
 PHILOX_PURPOSE_RESHUFFLE = 10
 RESHUFFLE_NONE = 0xFFFFFFFF
+# ... of the split and merge moves (bisbm_split_merge.hip: PHX_SPLIT_MERGE), the kinds of a move (BISBM_SM_SPLIT, BISBM_SM_MERGE) and
+# why a proposal was refused without an evaluation (BISBM_SM_EVALUATED: it was not)
+PHILOX_PURPOSE_SPLIT_MERGE = 11
+SM_SPLIT, SM_MERGE = 0, 1
+SM_EVALUATED, SM_SINGLETON, SM_AT_K_MAX, SM_AT_K_MIN, SM_NO_PAIR = 0, 1, 2, 3, 4
 # bisbm_trace_get_series: which series (BISBM_TRACE_S, BISBM_TRACE_H)
 TRACE_S, TRACE_H = 0, 1
 # bisbm_block_sums_set: keep the sums; also keep every counted chain's aligned tables of the last sample
@@ -93,6 +98,14 @@ class ReshuffleRecord(C.Structure):
                 ("dS_fwd", C.c_double), ("dS_rev", C.c_double), ("q_fwd_mant", C.c_double), ("q_rev_mant", C.c_double),
                 ("q_fwd_exp", C.c_int32), ("q_rev_exp", C.c_int32), ("u_acc", C.c_double), ("A", C.c_double),
                 ("accepted", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SplitMergeRecord(C.Structure):
+    """bisbm_split_merge_record (include/bisbm.h, "Split and merge moves")"""
+    _fields_ = [("kind", C.c_uint32), ("type", C.c_uint32), ("r", C.c_uint32), ("s", C.c_uint32), ("M", C.c_uint32), ("refused", C.c_uint32),
+                ("q_mant", C.c_double), ("q_exp", C.c_int32), ("accepted", C.c_uint32),
+                ("dS", C.c_double), ("lnA", C.c_double), ("A", C.c_double), ("u_acc", C.c_double),
+                ("ka_before", C.c_uint32), ("kb_before", C.c_uint32), ("ka_after", C.c_uint32), ("kb_after", C.c_uint32)]
 
 
 # every symbol include/bisbm.h and include/bisbm_io.h declare: (restype, argtypes)
@@ -189,6 +202,12 @@ ABI = {
     "bisbm_reshuffle_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, _u64p]),
     "bisbm_reshuffle_get_last": (C.c_int, [C.c_void_p, C.POINTER(ReshuffleRecord)]),
     "bisbm_reshuffle_get_total": (C.c_int, [C.c_void_p, _u64p]),
+    "bisbm_split_merge_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, _u32p, _u32p, _u64p]),
+    "bisbm_split_merge_get_last": (C.c_int, [C.c_void_p, C.POINTER(SplitMergeRecord)]),
+    "bisbm_split_merge_get_total": (C.c_int, [C.c_void_p, _u64p]),
+    "bisbm_split_merge_get_groups": (C.c_int, [C.c_void_p, _u32p]),
+    "bisbm_split_merge_get_timing": (C.c_int, [C.c_void_p, _f64p, _f64p]),
+    "bisbm_split_merge_shape_term": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f64p]),
     "bisbm_clamp_set": (C.c_int, [C.c_void_p, _u8p]),
     "bisbm_clamp_get": (C.c_int, [C.c_void_p, _u8p, _u64p]),
     "bisbm_constraints_set": (C.c_int, [C.c_void_p, C.c_uint32, _u8p, _u8p]),
@@ -882,6 +901,60 @@ class BlockModel:
         out = np.zeros(self.n_chains, dtype=np.uint64)
         self._check(self._L.bisbm_reshuffle_get_total(self._h, _p(out, _u64p)))
         return out
+
+    # -- split and merge moves (include/bisbm.h, "Split and merge moves")
+    def split_merge(self, moves, scans=3, beta=1.0, k_min=(1, 1), k_max=None):
+        """`moves` split or merge moves per chain: one block divided in two by `scans` restricted Gibbs scans from a random
+        launch state and one more that is the proposal, or two blocks of one type made one, accepted or rejected as a whole, so
+        that exp(-beta S) stays exactly invariant over the unlabelled partitions of every shape with k_min <= (Ka, Kb) <= k_max
+        (k_max None: min(n_t, 127) per type).  An accepted move changes the chain's shape: the chains are kept grouped by shape
+        (ka_kb(chain)), and traces, marginal histograms and every sum indexed by block labels must be reset by the caller, exactly
+        as after agg_merge.  Returns the accepted moves per chain (uint64 [n_chains])."""
+        acc = np.zeros(self.n_chains, dtype=np.uint64)
+        lo = np.ascontiguousarray(k_min, dtype=np.uint32)
+        hi = None if k_max is None else np.ascontiguousarray(k_max, dtype=np.uint32)
+        if lo.shape != (2,) or (hi is not None and hi.shape != (2,)):
+            raise ValueError("k_min and k_max are pairs (type a, type b)")
+        self._check(self._L.bisbm_split_merge_run(self._h, int(moves), int(scans), float(beta), _p(lo, _u32p),
+                                                  None if hi is None else _p(hi, _u32p), _p(acc, _u64p)))
+        self._refresh_k()
+        return acc
+
+    def split_merge_last(self):
+        """The last split or merge move of every chain: a list of dicts with kind (SM_SPLIT / SM_MERGE), type, r, s (global labels
+        before the move; a split's s: the label the new block takes), M, refused (SM_EVALUATED, or why nothing was evaluated),
+        q as (mantissa, exponent), dS, lnA, A, u_acc, accepted, before and after as (ka, kb)."""
+        rec = (SplitMergeRecord * self.n_chains)()
+        self._check(self._L.bisbm_split_merge_get_last(self._h, rec))
+        return [{"kind": x.kind, "type": x.type, "r": x.r, "s": x.s, "M": x.M, "refused": x.refused, "q": (x.q_mant, x.q_exp),
+                 "dS": x.dS, "lnA": x.lnA, "A": x.A, "u_acc": x.u_acc, "accepted": bool(x.accepted),
+                 "before": (x.ka_before, x.kb_before), "after": (x.ka_after, x.kb_after)} for x in rec]
+
+    def split_merge_total(self):
+        """Per chain, over the handle's lifetime: uint64 [n_chains][4] -- splits proposed, splits accepted, merges proposed,
+        merges accepted; a row's proposals add up to the index of the chain's next move's Philox draws."""
+        out = np.zeros((self.n_chains, 4), dtype=np.uint64)
+        self._check(self._L.bisbm_split_merge_get_total(self._h, _p(out, _u64p)))
+        return out
+
+    def chain_groups(self):
+        """The shape group of its device entry that every chain lives in (uint32 [n_chains]; all 0 while an entry's chains are
+        not grouped): chains of one device entry with the same shape share a group."""
+        out = np.zeros(self.n_chains, dtype=np.uint32)
+        self._check(self._L.bisbm_split_merge_get_groups(self._h, _p(out, _u32p)))
+        return out
+
+    def split_merge_timing(self):
+        """(ms of the last split_merge() call by the host clock, ms of it spent forming the groups again) -- diagnostic"""
+        a, b = np.zeros(1, dtype=np.float64), np.zeros(1, dtype=np.float64)
+        self._check(self._L.bisbm_split_merge_get_timing(self._h, _p(a, _f64p), _p(b, _f64p)))
+        return float(a[0]), float(b[0])
+
+    def split_merge_shape_term(self, ka, kb):
+        """T(ka, kb), the part of the description length that depends on the shape alone, as the library evaluates it."""
+        out = np.zeros(1, dtype=np.float64)
+        self._check(self._L.bisbm_split_merge_shape_term(self._h, int(ka), int(kb), _p(out, _f64p)))
+        return float(out[0])
 
     # -- clamped nodes (include/bisbm.h, "Clamped nodes")
     def clamp(self, nodes_or_mask):
@@ -2133,6 +2206,6 @@ class MetropolisHasting:
 metropolis_hasting = MetropolisHasting
 blockmodel_t = BlockModel
 
-from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_held_conditional_row, numpy_least_settled, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice, numpy_reshuffle_accept, numpy_reshuffle_launch, numpy_reshuffle_pair, numpy_reshuffle_q, numpy_reshuffle_step,  # noqa: E402,F401
+from .distributed import (ChainShard, numpy_coassign, numpy_conditional_row, numpy_held_conditional_row, numpy_least_settled, numpy_foldin_posterior, numpy_foldin_rows, numpy_foldin_tables, numpy_heatbath_choice, numpy_reshuffle_accept, numpy_reshuffle_launch, numpy_reshuffle_pair, numpy_reshuffle_q, numpy_reshuffle_step, numpy_split_merge_accept, numpy_split_merge_choice, numpy_split_merge_launch, numpy_split_merge_dS, numpy_split_merge_step, numpy_split_merge_renumber, numpy_split_merge_roles, numpy_split_merge_pairs,  # noqa: E402,F401
                           numpy_edge_dS, numpy_edge_multiplicity, numpy_edge_query_rows, numpy_pair_scores, numpy_query_topk, shard_chains)
 from .marginalize import marginalize, marginalize_modes  # noqa: E402,F401

@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libbisbm_hip.so")
 # (bisbm_engine.hpp describes which unit holds what), plain C++ for the tables and the text / CSR ingest
 SOURCES = ["bisbm_kernels.hip", "bisbm_sweep_fast.hip", "bisbm_handle.hip", "bisbm_anneal.hip", "bisbm_marginals.hip",
            "bisbm_multi.hip", "bisbm_merge.hip", "bisbm_align.hip", "bisbm_tempering.hip", "bisbm_population.hip", "bisbm_pair_scores.hip", "bisbm_edge_probs.hip", "bisbm_partition.hip",
-           "bisbm_query_scores.hip", "bisbm_edge_queries.hip", "bisbm_coassign.hip", "bisbm_foldin.hip", "bisbm_topk.hip", "bisbm_conditionals.hip", "bisbm_heatbath.hip", "bisbm_reshuffle.hip",
+           "bisbm_query_scores.hip", "bisbm_edge_queries.hip", "bisbm_coassign.hip", "bisbm_foldin.hip", "bisbm_topk.hip", "bisbm_conditionals.hip", "bisbm_heatbath.hip", "bisbm_reshuffle.hip", "bisbm_split_merge.hip",
            "bisbm_mode_marginals.hip", "bisbm_trace.hip", "bisbm_block_sums.hip", "bisbm_clamp.hip", "bisbm_constraints.hip", "bisbm_fields.hip",
            "bisbm_tables.cpp", "bisbm_io.cpp"]
 HEADERS = ["bisbm_device.hpp", "bisbm_partition_device.hpp", "bisbm_kernels.hpp", "bisbm_stand_rule.hpp", "bisbm_pair_word.hpp", "bisbm_move_word.hpp", "bisbm_held_word.hpp", "bisbm_predict_skew.hpp", "bisbm_engine.hpp", "bisbm_pass_policy.hpp", "bisbm_wave_chain.hpp", "bisbm_cand_lanes.hpp", os.path.join("..", "host", "bisbm.hpp"),

@@ -28,6 +28,7 @@
 //   bisbm_heatbath.hip   heat-bath sweeps and greedy polishing: nodes moved by their conditionals; kernel and C ABI (and the host
 //                        side of the chain state it shares with the reshuffle kernel: bisbm_wave_chain.hpp)
 //   bisbm_reshuffle.hip  pair reshuffles: two blocks' nodes divided afresh in one accepted or rejected move; kernel and C ABI
+//   bisbm_split_merge.hip  split and merge moves: a block divided in two or two made one, the chains regrouped by shape; kernels and C ABI
 //   bisbm_partition.hip  chain-by-chain partition distances (contingency tables, VI, entropies), grouping into modes
 //   bisbm_mode_marginals.hip  mode-resolved marginals, host side: the chains' modes, a reference and a histogram slice per mode
 //   bisbm_block_sums.hip  block summaries: the aligned block matrix, sizes and degrees summed over the counted chains of an
@@ -388,6 +389,23 @@ struct ReshuffleState {
     std::vector<unsigned long long> accepted;
 };
 
+// Split and merge moves (bisbm_split_merge.hip).  Everything belongs to the device entry (a plain handle, an entry of `devs`),
+// indexed by the entry's own chain order whatever the grouping by shape of the moment: the groups come and go with the moves.
+struct SplitMergeState {
+    std::vector<uint32_t> proposed;                 // [chains] j: split / merge moves proposed so far (empty: none yet)
+    std::vector<uint64_t> totals;                   // [chains][4] splits proposed, accepted, merges proposed, accepted
+    std::vector<bisbm_split_merge_record> last;     // [chains] (empty: no call yet)
+    double call_ms = 0, regroup_ms = 0;             // host clock of the last call on this entry, and its part spent forming groups
+    // scratch of one launch over all groups of the entry, each group a slice: the chains' state with a spare block per type
+    DeviceBuf<uint8_t> d_labels;                    // [chains][label_stride]
+    DeviceBuf<int32_t> d_m, d_m_r, d_n_r;
+    DeviceBuf<uint32_t> d_eta;
+    DeviceBuf<uint8_t> d_scratch;                   // as ReshuffleState::d_scratch
+    DeviceBuf<bisbm_split_merge_record> d_record;   // [chains]
+    DeviceBuf<uint32_t> d_proposed;                 // [chains] `proposed` in launch order
+    DeviceBuf<uint8_t> d_jobs;                      // the regrouping's copy jobs (the unit's ChainCopy, as bytes)
+};
+
 // Partition distances (bisbm_partition.hip).  The scratch of the calls, on the engine whose device computes (a plain handle, the
 // container of shape groups, the first device entry); nothing of it outlives a call in meaning, it is only kept to be reused.
 struct PartitionState {
@@ -610,6 +628,7 @@ struct bisbm_engine {
     bisbm::FoldinState foldin;
     bisbm::ConditionalState cond;
     bisbm::ReshuffleState reshuffle;
+    bisbm::SplitMergeState split_merge;
     bisbm::PartitionState partition;
     bisbm::ModeState modes;
     bisbm::TraceState trace;
@@ -865,6 +884,11 @@ int heatbath_engine(bisbm_engine* h, uint64_t sweeps, double beta, int stop_when
 // `last` is emptied; bisbm_reshuffle.hip
 int reshuffle_engine(bisbm_engine* h, uint64_t moves, uint32_t scans, double beta, bool per_rung, bool read_back);
 int reshuffle_read_back(bisbm_engine* h);  // ... the copy alone, after a wait for the stream
+// chains of one handle in different shapes (bisbm_merge.hip): a sub-engine of `root` for `count` chains of shape (ka, kb) with its
+// own per-chain arrays, stream and events, graph and tables borrowed (NULL and `err` when an allocation fails); and root->where
+// from the groups' ridx.  The split and merge moves regroup with them.
+bisbm_engine* new_group(bisbm_engine* root, uint32_t ka, uint32_t kb, uint32_t count, std::string& err);
+void remap_groups(bisbm_engine* root);
 // block constraints: the shuffle's list of a device entry (ConstraintState::d_open) from the entry's constraints and the clamp
 // mask given (0 / 1 bytes, empty: none); nothing to do without constraints.  bisbm_clamp_set calls it for every mask it puts in
 // place; bisbm_constraints.hip

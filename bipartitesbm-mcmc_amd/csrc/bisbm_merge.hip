@@ -708,10 +708,8 @@ int run_merges(bisbm_engine* h, int which, int diff_a, int diff_b, int nm, std::
 // ---------------------------------------------------------------------------------------------
 // chains with different block counts: sub-engines per shape (see bisbm_engine::groups)
 // ---------------------------------------------------------------------------------------------
-namespace {
-
 // a sub-engine of `root` for `count` chains of shape (ka, kb): own per-chain arrays, stream and events; graph and tables borrowed
-bisbm_engine* new_group(bisbm_engine* root, uint32_t ka, uint32_t kb, uint32_t count, std::string& err) {
+bisbm_engine* bisbm::new_group(bisbm_engine* root, uint32_t ka, uint32_t kb, uint32_t count, std::string& err) {
     std::unique_ptr<bisbm_engine> gp(new bisbm_engine());
     bisbm_engine* g = gp.get();
     g->root = root;
@@ -754,6 +752,14 @@ bisbm_engine* new_group(bisbm_engine* root, uint32_t ka, uint32_t kb, uint32_t c
     }
     return gp.release();
 }
+
+void bisbm::remap_groups(bisbm_engine* root) {
+    root->where.assign(root->n_chains, {0u, 0u});
+    for (size_t gi = 0; gi < root->groups.size(); ++gi)
+        for (size_t j = 0; j < root->groups[gi]->ridx.size(); ++j) root->where[root->groups[gi]->ridx[j]] = {(uint32_t)gi, (uint32_t)j};
+}
+
+namespace {
 
 // The chains of `src` (labels already in each chain's own new numbering, shapes in `ends`) go to new sub-engines of
 // `root`, one per distinct shape in order of first appearance; every chain keeps its generator state, counters and
@@ -798,12 +804,6 @@ int split_by_shape(bisbm_engine* root, bisbm_engine* src, const std::vector<std:
         if (rc) return fail(root, rc, "%s", g->err.c_str());
     }
     return BISBM_OK;
-}
-
-void remap_groups(bisbm_engine* root) {
-    root->where.assign(root->n_chains, {0u, 0u});
-    for (size_t gi = 0; gi < root->groups.size(); ++gi)
-        for (size_t j = 0; j < root->groups[gi]->ridx.size(); ++j) root->where[root->groups[gi]->ridx[j]] = {(uint32_t)gi, (uint32_t)j};
 }
 
 // agg_merge(engine, diff, nm) on a handle whose chains may end (or already live) in different shapes

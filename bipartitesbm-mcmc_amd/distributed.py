@@ -602,6 +602,118 @@ def numpy_reshuffle_accept(dS_fwd, dS_rev, q_fwd, q_rev, beta, u_acc):
     return A, float(u_acc) < A
 
 
+def numpy_split_merge_choice(x, y, ka, kb, k_min=(1, 1), k_max=None, size_of=None):
+    """Host statement of step 2 of the split and merge moves (include/bisbm.h, "Split and merge moves"): (kind, type, r, s,
+    refused) from the first two words x, y of the move's draw 0 and the shape -- kind 0: a split of global label r (s: the
+    label the new block takes), kind 1: a merge of the pair r < s, global labels; refused: 0, or 4 (a merge without a pair;
+    type, r, s are 0 then), 3 (a merge of a type at k_min), 2 (a split of a type at k_max), 1 (a split of a block of fewer than
+    two nodes; only when `size_of`, a function of the global label, is given), tested in this order.  k_max None: no bound."""
+    ka, kb = int(ka), int(kb)
+    K = ka + kb
+    if int(x) & 1:
+        pair = numpy_reshuffle_pair(y, ka, kb)
+        if pair is None:
+            return 1, 0, 0, 0, 4
+        t, r, s = pair
+        k = kb if t else ka
+        return 1, t, r + t * ka, s + t * ka, 3 if k <= int(k_min[t]) else 0
+    b = (int(y) * K) >> 32
+    t = 1 if b >= ka else 0
+    k = kb if t else ka
+    refused = 0
+    if k_max is not None and k >= int(k_max[t]):
+        refused = 2
+    elif size_of is not None and int(size_of(b)) < 2:
+        refused = 1
+    return 0, t, b, (K if t else ka), refused
+
+
+def numpy_split_merge_roles(member_labels):
+    """Host statement of step 3: (home label, away mask) of the present division of the members (ascending id) -- home is the
+    block of member 0, whatever its label, so every unordered division has exactly one description."""
+    lab = [int(l) for l in member_labels]
+    return lab[0], [l != lab[0] for l in lab]
+
+
+def numpy_split_merge_launch(bits):
+    """Host statement of the first half of step 4: which of the M members are launched away -- member 0 never (its bit is not
+    looked at), member i >= 1 iff its launch bit is set, and member M - 1 if that left nobody away."""
+    away = [False] + [bool(b) for b in list(bits)[1:]]
+    if not any(away):
+        away[-1] = True
+    return away
+
+
+def numpy_split_merge_step(dS_o, in_home, free, beta, u=None, forced_home=None, exp=np.exp):
+    """Host statement of one restricted step of step 4, 6 or 7 for a member i >= 1: (goes home?, factor, dead) -- the step of
+    numpy_reshuffle_step with (home, away) in the place of (r, s): Z = w_home + w_away, home iff u < P_home.  Only the sole
+    member of away can be not free."""
+    return numpy_reshuffle_step(dS_o, in_home, free, beta, u=u, forced_to_r=forced_home, exp=exp)
+
+
+def numpy_split_merge_dS(m_h, m_a, eta_h, eta_a, mr_h, mr_a, nr_h, nr_a, T_merged, T_divided, lgamma, log_q):
+    """Host statement of step 5: merge_dS = S(blocks h and a made one) - S(as they are), from their rows of m over the other
+    type's blocks (ascending), their eta rows over the degrees 0 .. max_degree, their m_r and n_r and the shape terms T of the
+    two shapes; lgamma(i) and log_q(n, k) are the tables' (callables)."""
+    acc_m = 0.0
+    for x, y in zip(m_h, m_a):
+        x, y = int(x), int(y)
+        acc_m = acc_m + ((lgamma(x + 1) + lgamma(y + 1)) - lgamma(x + y + 1))
+    acc_e = 0.0
+    for x, y in zip(eta_h, eta_a):
+        x, y = int(x), int(y)
+        acc_e = acc_e + ((lgamma(x + 1) + lgamma(y + 1)) - lgamma(x + y + 1))
+    mr_h, mr_a, nr_h, nr_a = int(mr_h), int(mr_a), int(nr_h), int(nr_a)
+    tail1 = lgamma(mr_h + mr_a + 1) - (lgamma(mr_h + 1) + lgamma(mr_a + 1))
+    tail2 = log_q(mr_h + mr_a, nr_h + nr_a) - (log_q(mr_h, nr_h) + log_q(mr_a, nr_a))
+    return (((acc_m + acc_e) + tail1) + tail2) + (float(T_merged) - float(T_divided))
+
+
+def numpy_split_merge_pairs(ka, kb):
+    """N(ka, kb) = C(ka, 2) + C(kb, 2)"""
+    return int(ka) * (int(ka) - 1) // 2 + int(kb) * (int(kb) - 1) // 2
+
+
+def numpy_split_merge_accept(kind, merge_dS, q, beta, u_acc, ka, kb, t, exp=np.exp, log=np.log):
+    """Host statement of steps 6 to 8: (dS, ln A, A, accepted) of a split (kind 0; merge_dS of the proposal, q = Q_fwd) or a
+    merge (kind 1; merge_dS of the present division, q = Q_rev) of type t from the shape (ka, kb) BEFORE the move.  q is
+    (mantissa, exponent); a dead forced pass (mantissa 0.0) is ln A = -inf, A = 0.0 and a rejection."""
+    ka, kb, beta = int(ka), int(kb), float(beta)
+    K = ka + kb
+    if kind == 1 and float(q[0]) == 0.0:
+        return float(merge_dS), -np.inf, 0.0, False
+    ln_q = float(log(np.float64(q[0]))) + float(int(q[1])) * 0.6931471805599453
+    if kind == 1:
+        dS = float(merge_dS)
+        lnA = ((0.0 - beta * dS) + (float(log(np.float64(numpy_split_merge_pairs(ka, kb)))) - float(log(np.float64(K - 1))))) + ln_q
+    else:
+        dS = 0.0 - float(merge_dS)
+        after = numpy_split_merge_pairs(ka + (1 - t), kb + t)
+        lnA = ((0.0 - beta * dS) + (float(log(np.float64(K))) - float(log(np.float64(after))))) - ln_q
+    with np.errstate(over="ignore"):
+        A = float(exp(np.float64(lnA)))
+    return dS, lnA, A, float(u_acc) < A
+
+
+def numpy_split_merge_renumber(labels, kind, t, r, s, ka, kb, away_nodes=None):
+    """Host statement of the numbering after an accepted move (step 8): (labels, ka, kb).  Split (kind 0) of block r of type t
+    with the nodes `away_nodes` leaving it: of type a, away becomes label ka and every type-b label moves up by one; of type b,
+    away becomes label ka + kb.  Merge (kind 1) of r < s: the nodes of s take r, the labels of that type above s move down by
+    one, and for a type-a merge every type-b label moves down by one as well."""
+    lab = np.array(labels, dtype=np.int64)
+    ka, kb = int(ka), int(kb)
+    if kind == 0:
+        if t == 0:
+            lab[lab >= ka] += 1
+            lab[np.asarray(away_nodes, dtype=np.int64)] = ka
+            return lab, ka + 1, kb
+        lab[np.asarray(away_nodes, dtype=np.int64)] = ka + kb
+        return lab, ka, kb + 1
+    lab[lab == int(s)] = int(r)
+    lab[lab > int(s)] -= 1
+    return (lab, ka - 1, kb) if t == 0 else (lab, ka, kb - 1)
+
+
 def numpy_clamped_shuffle(labels, mask, na, perm_a, perm_b):
     """The shuffle under a clamp (include/bisbm.h, "Clamped nodes", 4.) on the host, given the two permutations of the
     compacted label vectors: with F the ascending list of the open (mask == 0) nodes of a type and f its permutation of

@@ -458,6 +458,27 @@ public:
         check(bisbm_reshuffle_get_last(h_, rec.data()));
         return rec;
     }
+    // split and merge moves (include/bisbm.h): `moves` moves per chain in which one block is divided in two or two blocks of one
+    // type are made one, accepted or rejected as a whole (the accepted moves per chain) -- the chains then differ in shape
+    // (ka_kb(chain)) and everything indexed by block labels is reset by the caller, as after agg_merge; k_max {0, 0}: min(n_t, 127)
+    std::vector<uint64_t> split_merge(uint64_t moves, uint32_t scans = 3, double beta = 1.0, std::array<uint32_t, 2> k_min = {1, 1},
+                                      std::array<uint32_t, 2> k_max = {0, 0}) {
+        std::vector<uint64_t> accepted(n_chains_);
+        check(bisbm_split_merge_run(h_, moves, scans, beta, k_min.data(), k_max[0] || k_max[1] ? k_max.data() : nullptr, accepted.data()));
+        refresh_k();
+        return accepted;
+    }
+    std::vector<bisbm_split_merge_record> split_merge_last() {
+        std::vector<bisbm_split_merge_record> rec(n_chains_);
+        check(bisbm_split_merge_get_last(h_, rec.data()));
+        return rec;
+    }
+    // ... per chain {splits proposed, splits accepted, merges proposed, merges accepted}
+    std::vector<uint64_t> split_merge_total() {
+        std::vector<uint64_t> out(4 * (size_t)n_chains_);
+        check(bisbm_split_merge_get_total(h_, out.data()));
+        return out;
+    }
     // pair scores (include/bisbm.h): the pairs (u of type a, v of type b), a sample of every counted chain, the sums and the
     // number of chain terms in them (the estimate of a pair is sum / terms)
     void pair_scores_set(const std::vector<uint32_t>& u, const std::vector<uint32_t>& v) {

@@ -7,7 +7,7 @@
 // Extra flags: --chains, --device, --devices, --rng {mt19937-compat,philox}, --gen_seed, --csr_cache, --reorder, --marginalize, --align,
 // --tempering, --exchange_every, --population, --population_sweeps, --score_pairs, --edge_probs, --recommend, --recommend_edges, --include_edges, --modes, --mode_marginals, --reassign, --similar, --foldin, --foldin_alpha,
 // --conditionals, --conditionals_beta, --polish, --heatbath, --reshuffle, --reshuffle_scans, --trace, --rung_moves, --population_moves,
-// --clamp, --constraints, --fields.
+// --clamp, --constraints, --fields, --split_merge, --split_merge_scans, --k_min, --k_max, --shape_counts.
 // The agglomerative drivers (:349-451) run through bisbm_agg_merge.  --merge starts at one block per node: while
 // KA + KB > 256 the library runs its wide mode (two-byte labels, generic kernel), up to about 14 000 blocks (bisbm_check_shape).
 // Negative diffs (agg_split) run through the same call (blockmodel.cc:110-117).
@@ -64,6 +64,7 @@ const option_spec kOptions[] = {
     {"modes", 0, 2},            {"mode_marginals", 0, 1},  {"reassign", 0, 0},
     {"polish", 0, 1},           {"heatbath", 0, 0},
     {"reshuffle", 0, 1},        {"reshuffle_scans", 0, 1},
+    {"split_merge", 0, 1},      {"split_merge_scans", 0, 1}, {"k_min", 0, 2},       {"k_max", 0, 2},       {"shape_counts", 0, 1},
     {"trace", 0, 2},            {"block_summary", 0, 1},
     {"rung_moves", 0, 2},       {"population_moves", 0, 2},
     {"clamp", 0, 1},            {"constraints", 0, 1},
@@ -256,6 +257,16 @@ void print_help(const char* argv0) {
                  "                                        --tempering).  The acceptance is reported on stderr.\n"
                  "  --reshuffle_scans arg (=3)            With --reshuffle: restricted Gibbs scans before the proposal (3 is the\n"
                  "                                        convention of the literature, not a measurement).\n"
+                 "  --split_merge M                       With --marginalize and --shape_counts: M split or merge moves per chain after\n"
+                 "                                        the burn-in and after every block of sweeps between samples (one block\n"
+                 "                                        divided in two, or two blocks of one type made one, accepted or rejected as\n"
+                 "                                        a whole), so the chains sample (Ka, Kb) with the partition; Philox mode.\n"
+                 "                                        Standard output: the labels of the lowest description length seen.\n"
+                 "  --split_merge_scans arg (=3)          With --split_merge: restricted Gibbs scans before the proposal.\n"
+                 "  --k_min A B (=1 1)                    With --split_merge: the fewest blocks of type a and of type b.\n"
+                 "  --k_max A B                           With --split_merge: the most blocks per type (default: min(n_t, 127)).\n"
+                 "  --shape_counts OUT                    With --split_merge: OUT gets one line per visited shape, `ka kb visits S`:\n"
+                 "                                        the visits over samples and chains, the lowest description length seen.\n"
                  "  --clamp PATH                          PATH holds node ids separated by white space (any order, repeats allowed):\n"
                  "                                        these nodes keep the labels of --membership_path (required) through every\n"
                  "                                        sweep, reshuffle and exchange round of the run, in every chain; the other\n"
@@ -693,6 +704,70 @@ int main(int argc, char const* argv[]) {
             return 1;
         }
         reshuffle_moves = k, reshuffle_scans = (uint32_t)sc;
+    }
+    // --split_merge M [--split_merge_scans T] [--k_min A B] [--k_max A B] --shape_counts OUT
+    uint64_t split_merge_moves = 0;
+    uint32_t split_merge_scans = 3;
+    std::array<uint32_t, 2> sm_k_min{1, 1}, sm_k_max{0, 0};  // (k_max {0, 0}: the library's default)
+    std::string shape_counts_path;
+    for (const char* name : {"split_merge_scans", "k_min", "k_max", "shape_counts"})
+        if (count(name) && !count("split_merge")) {
+            std::cerr << "--" << name << " belongs to the split and merge moves: it needs --split_merge.\n";
+            return 1;
+        }
+    if (count("split_merge")) {
+        if (!count("marginalize")) {
+            std::cerr << "--split_merge runs split and merge moves between the sweeps of the marginalization mode: it needs --marginalize.\n";
+            return 1;
+        }
+        if (!count("shape_counts")) {
+            std::cerr << "--split_merge changes the chains' block counts, so there is no pooled label histogram: it needs --shape_counts OUT for the histogram of visited shapes.\n";
+            return 1;
+        }
+        for (const char* other : {"tempering", "population", "align", "reshuffle", "clamp", "constraints", "fields", "modes", "mode_marginals", "block_summary",
+                                  "trace", "recommend", "recommend_edges", "score_pairs", "edge_probs", "similar", "foldin", "conditionals", "polish"})
+            if (count(other)) {
+                std::cerr << "--split_merge cannot be combined with --" << other
+                          << ": the moves renumber blocks and change the chains' block counts (marginalize(split_merges=) of the Python package keeps the numbering-free sums).\n";
+                return 1;
+            }
+        const std::string v = single("split_merge", ""), t = single("split_merge_scans", "3");
+        char *end = nullptr, *end2 = nullptr;
+        const unsigned long long k = std::strtoull(v.c_str(), &end, 10), sc = std::strtoull(t.c_str(), &end2, 10);
+        if (v.empty() || *end != '\0' || v[0] == '-' || k == 0) {
+            std::cerr << "Invalid --split_merge. The moves per chain after every block of sweeps: an integer >= 1, e.g. --split_merge 4.\n";
+            return 1;
+        }
+        if (t.empty() || *end2 != '\0' || t[0] == '-' || sc > 0xffffffffull) {
+            std::cerr << "Invalid --split_merge_scans. An integer >= 0, e.g. --split_merge_scans 3.\n";
+            return 1;
+        }
+        for (const char* name : {"k_min", "k_max"}) {
+            if (!count(name)) continue;
+            auto const& vals = var_map.at(name);
+            std::array<uint32_t, 2>& dst = std::string(name) == "k_min" ? sm_k_min : sm_k_max;
+            bool ok = vals.size() == 2;
+            for (size_t i = 0; ok && i < 2; ++i) {
+                char* e = nullptr;
+                const unsigned long long x = std::strtoull(vals[i].c_str(), &e, 10);
+                ok = !vals[i].empty() && *e == '\0' && vals[i][0] != '-' && x >= 1 && x <= 254;
+                dst[i] = (uint32_t)x;
+            }
+            if (!ok) {
+                std::cerr << "Invalid --" << name << ". Two integers >= 1, the blocks of type a and of type b, e.g. --" << name << " 1 1.\n";
+                return 1;
+            }
+        }
+        if (count("k_max") && (sm_k_min[0] > sm_k_max[0] || sm_k_min[1] > sm_k_max[1] || sm_k_max[0] + sm_k_max[1] > 254)) {
+            std::cerr << "Invalid --k_max. At least --k_min per type and at most 254 blocks in all.\n";
+            return 1;
+        }
+        shape_counts_path = single("shape_counts", "");
+        if (shape_counts_path.empty()) {
+            std::cerr << "Invalid --shape_counts. A path to write, e.g. --shape_counts shapes.txt.\n";
+            return 1;
+        }
+        split_merge_moves = k, split_merge_scans = (uint32_t)sc;
     }
     // the moves of a round (--rung_moves with --tempering, --population_moves with --population): four integers MH HB RS SCANS
     bisbm_round_recipe rung_moves{}, population_moves{};
@@ -1334,8 +1409,8 @@ int main(int argc, char const* argv[]) {
         std::cerr << "--clamp runs in Philox mode only (mt19937-compat is the reference's verification path, and the reference has no clamp): add --rng philox.\n";
         return 1;
     }
-    if ((polish_sweeps || count("heatbath") || reshuffle_moves) && opt.rng_mode != BISBM_RNG_PHILOX) {
-        std::cerr << (polish_sweeps ? "--polish" : count("heatbath") ? "--heatbath" : "--reshuffle")
+    if ((polish_sweeps || count("heatbath") || reshuffle_moves || split_merge_moves) && opt.rng_mode != BISBM_RNG_PHILOX) {
+        std::cerr << (polish_sweeps ? "--polish" : count("heatbath") ? "--heatbath" : reshuffle_moves ? "--reshuffle" : "--split_merge")
                   << " runs in Philox mode only (mt19937-compat is the reference's verification path): add --rng philox.\n";
         return 1;
     }
@@ -1603,6 +1678,52 @@ int main(int argc, char const* argv[]) {
                     reshuffles_proposed += reshuffle_moves * opt.n_chains;
                 }
             };
+            if (split_merge_moves) {
+                // the chains sample (Ka, Kb): no pooled histogram; the visited shapes are counted and the best state of each kept
+                uint64_t proposed = 0, accepted = 0;
+                auto advance_shapes = [&](size_t sweeps) {
+                    advance(sweeps);
+                    for (uint64_t a : blockmodel.split_merge(split_merge_moves, split_merge_scans, 1.0, sm_k_min, sm_k_max)) accepted += a;
+                    proposed += split_merge_moves * opt.n_chains;
+                };
+                if (burn_in >= N) advance_shapes(burn_in / N);
+                struct Best {
+                    uint64_t visits = 0;
+                    bool have = false;
+                    double S = 0;
+                    uint_vec_t labels;
+                };
+                std::map<std::pair<size_t, size_t>, Best> shapes;
+                for (size_t sample = 0; sample < n_samples; ++sample) {
+                    advance_shapes(sweeps_between);
+                    const std::vector<double> dl = blockmodel.entropy_all();
+                    for (uint32_t c = 0; c < opt.n_chains; ++c) {
+                        Best& b = shapes[blockmodel.ka_kb(c)];
+                        b.visits += 1;
+                        if (!b.have || dl[c] < b.S) b.have = true, b.S = dl[c], b.labels = *blockmodel.get_memberships(c);
+                    }
+                }
+                std::clog << "marginalize: burn-in " << burn_in / N << " sweeps, " << n_samples << " samples " << sweeps_between
+                          << " sweep(s) apart, " << opt.n_chains << " chain(s)\n";
+                std::clog << "split_merge: " << accepted << " of " << proposed << " split / merge move(s) accepted (" << split_merge_scans << " scan(s))\n";
+                if (n_samples == 0) {
+                    std::cerr << "[error] --marginalize: -t " << sampling_steps << " steps hold no sample (" << sweeps_between * N << " steps per sample)\n";
+                    return 1;
+                }
+                std::ofstream out(shape_counts_path);
+                out.precision(17);
+                const Best* best = nullptr;
+                for (auto const& kv : shapes) {
+                    out << kv.first.first << " " << kv.first.second << " " << kv.second.visits << " " << kv.second.S << "\n";
+                    if (!best || kv.second.S < best->S) best = &kv.second;
+                }
+                if (!out) {
+                    std::cerr << "[error] --shape_counts: cannot write " << shape_counts_path << "\n";
+                    return 1;
+                }
+                emit_labels(best->labels);
+                return 0;
+            }
             if (burn_in >= N) advance(burn_in / N);
             blockmodel.marginals_reset();
             if (count("align")) blockmodel.marginals_set_alignment(true);

@@ -20,7 +20,7 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
                 return_counts=None, align=False, tempering=None, exchange_every=1, score_pairs=None, recommend=None,
                 similar=None, foldin=None, conditionals=None, sampler="mh", reshuffles=0, reshuffle_scans=3, trace=None, rung_moves=None, blocks=False,
                 clamp=None, constraints=None, fields=None, conditionals_held=False, least_settled=None, edge_probs=None,
-                recommend_edges=None):
+                recommend_edges=None, split_merges=0, split_merge_scans=3, k_min=(1, 1), k_max=None):
     """Runs the chain(s) of `model` (a BlockModel whose state is already initialised by init_bisbm() /
     shuffle_bisbm()) and returns (labels, counts):
       labels  uint32 [n]         MAP block of every node in the reference's numbering
@@ -106,8 +106,32 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     constraints and the fields as they are at each sample.
     `least_settled`: (k, by) or (k,) with `conditionals` only (ValueError without), by = "entropy" (the default) or "stay"
     (include/bisbm.h, "Least settled"): model.least_settled(k, by) -- (query indices, nodes, values, terms) -- is appended after
-    the conditionals' stats (and their soft marginals)."""
+    the conditionals' stats (and their soft marginals).
+    `split_merges`: m > 0 runs model.split_merge(m, split_merge_scans, 1.0, k_min, k_max) after every block of sweeps -- the
+    burn-in and every gap between samples (include/bisbm.h, "Split and merge moves") -- so the chains sample (Ka, Kb) with the
+    partition, and the return value becomes (shape_counts, best): shape_counts {(ka, kb): visits} over samples and chains, best
+    {(ka, kb): (S, labels)} the lowest description length seen at a sample in every visited shape with its labels.  The pooled
+    label histogram needs one common shape and is refused there, with everything that rests on it or on a block numbering
+    (`align`, `blocks`, `device_counts`, `return_counts`, `trace`, `tempering`, `clamp`, `constraints`, `fields`, `recommend`,
+    `recommend_edges`, `reshuffles`, chains spread over ranks: ValueError before anything runs); the numbering-free options
+    `score_pairs`, `edge_probs`, `similar`, `foldin` and `conditionals` stay and then average over the posterior of (Ka, Kb) --
+    the results of `similar`, `foldin` and `conditionals` are appended as above (model.pair_scores() and model.edge_probs() give
+    the sums of the other two, as always).  model.split_merge_stats = {"proposed", "accepted"} reports the acceptance."""
     _check_conditional_extras(conditionals, conditionals_held, least_settled)
+    if int(split_merges) < 0 or int(split_merge_scans) < 0:
+        raise ValueError("split_merges and split_merge_scans must not be negative")
+    if split_merges:
+        refused = {"align": align, "blocks": blocks, "device_counts": device_counts is not None, "return_counts": bool(return_counts),
+                   "trace": bool(trace), "tempering": tempering is not None, "rung_moves": rung_moves is not None, "clamp": clamp is not None,
+                   "constraints": constraints is not None, "fields": fields is not None, "recommend": recommend is not None,
+                   "recommend_edges": recommend_edges is not None, "reshuffles": bool(reshuffles), "conditionals_held": conditionals_held,
+                   "least_settled": least_settled is not None, "shard": shard is not None and shard.world_size > 1}
+        bad = sorted(k for k, v in refused.items() if v)
+        if bad:
+            raise ValueError("split_merges changes the chains' block counts: the pooled label histogram and everything that rests on one "
+                             "block numbering is refused with it (%s)" % ", ".join(bad))
+        return _marginalize_shapes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sampler, int(split_merges), int(split_merge_scans),
+                                   k_min, k_max, score_pairs, edge_probs, similar, foldin, conditionals)
     if clamp is not None:
         model.clamp(clamp)
     if constraints is not None:
@@ -248,6 +272,70 @@ def marginalize(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sha
     labels = shard.map_labels(send, model.na, model.KA).cpu().numpy().astype(np.uint32)
     counts = shard.pooled_marginals(send).cpu().numpy().astype(np.int64) if return_counts else None
     return result(labels, counts)
+
+
+def _marginalize_shapes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, sampler, moves, scans, k_min, k_max, score_pairs, edge_probs,
+                        similar, foldin, conditionals):
+    """marginalize(..., split_merges=moves): see there"""
+    if sampler not in ("mh", "heatbath"):
+        raise ValueError("sampler must be \"mh\" or \"heatbath\"")
+    model.split_merge_stats = {"proposed": 0, "accepted": 0}
+
+    def advance(sweeps):
+        if sampler == "mh":
+            model.run_sweeps(int(sweeps))
+        else:
+            model.heatbath_sweeps(int(sweeps), 1.0)
+        acc = model.split_merge(moves, scans, 1.0, k_min, k_max)
+        model.split_merge_stats["proposed"] += moves * model.n_chains
+        model.split_merge_stats["accepted"] += int(acc.sum())
+    if burn_in_sweeps > 0:
+        advance(burn_in_sweeps)
+    if score_pairs is not None:
+        model.pair_scores_set(score_pairs)
+        model.pair_scores_reset()
+    if edge_probs is not None:
+        model.edge_probs_set(edge_probs[0], edge_probs[1] if len(edge_probs) > 1 else None)
+        model.edge_probs_reset()
+    if similar is not None:
+        model.coassign_set(similar[0])
+        model.coassign_reset()
+    if foldin is not None:
+        model.foldin_set(foldin[0], foldin[2] if len(foldin) > 2 else None)
+    if conditionals is not None:
+        model.conditionals_set(conditionals[0], conditionals[1] if len(conditionals) > 1 else 1.0)
+    shape_counts, best = {}, {}
+    for _ in range(int(n_samples)):
+        if sampling_frequency_sweeps > 0:
+            advance(sampling_frequency_sweeps)
+        S = model.entropy()
+        lowest = {}
+        for c in range(model.n_chains):
+            shape = model.ka_kb(c)
+            shape_counts[shape] = shape_counts.get(shape, 0) + 1
+            if shape not in lowest or S[c] < S[lowest[shape]]:
+                lowest[shape] = c
+        for shape, c in lowest.items():
+            if shape not in best or S[c] < best[shape][0]:
+                best[shape] = (float(S[c]), model.get_memberships(c))
+        if score_pairs is not None:
+            model.pair_scores_accumulate()
+        if edge_probs is not None:
+            model.edge_probs_accumulate()
+        if similar is not None:
+            model.coassign_accumulate()
+        if foldin is not None:
+            model.foldin_accumulate()
+        if conditionals is not None:
+            model.conditionals_accumulate()
+    out = (shape_counts, best)
+    if similar is not None:
+        out += (model.similar(int(similar[1])),)
+    if foldin is not None:
+        out += ((model.foldin_recommend(int(foldin[1])), model.foldin_similar(int(foldin[1]))),)
+    if conditionals is not None:
+        out += (model.conditionals_stats(),)
+    return out
 
 
 def marginalize_modes(model, burn_in_sweeps, n_samples, sampling_frequency_sweeps, threshold=None, mode_of_chain=None, shard=None,

@@ -824,6 +824,105 @@ int bisbm_reshuffle_get_last(bisbm_handle h, bisbm_reshuffle_record *out /* n_ch
 /* The chains' reshuffles_total. */
 int bisbm_reshuffle_get_total(bisbm_handle h, uint64_t *out /* n_chains */);
 
+/* Split and merge moves (no reference counterpart): one block divided in two, or two blocks of one type made one, in ONE accepted
+ * or rejected move, so that the chains sample (Ka, Kb) with the partition.  exp(-beta S), S = bisbm_entropy's full description
+ * length -- which holds lbinom(Ka Kb + E - 1, E), lbinom(na - 1, Ka - 1) and lbinom(nb - 1, Kb - 1) and is therefore comparable
+ * across shapes --, stays exactly invariant over the UNLABELLED partitions of every shape with k_min[t] <= K_t <= k_max[t].  It is
+ * Jain and Neal's split-merge: the pair reshuffle above with one side empty before or after.  Philox mode and byte labels; f64
+ * without a fused multiply-add; exp and log are the device's.  Defined per chain; j = the chain's count of proposed split / merge
+ * moves (a 32-bit counter kept with the chain through every regrouping, one per proposal whatever became of it).
+ *   1. RANDOMNESS: X(k) = Philox(seed; idx = (j << 32) | k, chain = global chain id, purpose 11); U(k) as in "Pair reshuffles".
+ *      k = 0: kind and choice; k = 1: u_acc; launch bits and scan uniforms at the k of "Pair reshuffles" 1. (the forward pass of a
+ *      split is scan t = scans; a merge draws no uniform past the launch scans).
+ *   2. KIND AND CHOICE, from the shape (ka, kb) alone, K = ka + kb: bit 0 of the first word of X(0) clear: SPLIT of block
+ *      (y * K) >> 32, y the second word of X(0), a global label; set: MERGE of pair number (y * N) >> 32 of the N(ka, kb) =
+ *      C(ka, 2) + C(kb, 2) same-type pairs {r < s} in the enumeration of "Pair reshuffles" 2.  With t the type of the block or
+ *      pair, the proposal is REFUSED -- counted as proposed, rejected, nothing evaluated -- when: a merge and N = 0
+ *      (BISBM_SM_NO_PAIR); a merge and k_t <= k_min[t] (BISBM_SM_AT_K_MIN); a split and k_t >= k_max[t] (BISBM_SM_AT_K_MAX); a
+ *      split and the block has fewer than 2 nodes (BISBM_SM_SINGLETON), tested in this order.
+ *   3. MEMBERS AND ROLES: the nodes of r (split) or of r and s (merge), ascending id, M of them.  Member 0 is pinned: the part
+ *      that holds it is HOME, the other AWAY, which counts every unordered division of the set once.  Split: home is r, away
+ *      the new block.  Merge: home is the block of member 0 now.
+ *   4. LAUNCH STATE L: member 0 home; member i >= 1 away iff its launch bit is set; if none is away, member M - 1 goes away;
+ *      then `scans` restricted scans over members 1 .. M - 1 in ascending order.  A step is step 5 of "Pair reshuffles" with
+ *      (home, away) in the place of (r, s): a member alone in its block (only the sole member of away can be) stays with the
+ *      factor 1.0 and no draw; otherwise Z = w_home + w_away, the member goes home iff u < P_home, the factor is the P of where
+ *      it went.  L depends on the member set and the rest of the state, never on the present division.  Getting from the
+ *      present state to the launch labels is transit: no table is read.
+ *   5. merge_dS(D) = S(all members in one block) - S(D) for a division D into blocks h and a of type t, with m_ht, m_at over the
+ *      blocks t' of the other type in ascending order, eta_hk, eta_ak over k = 0 .. max_degree ascending, lg = the lgamma table:
+ *        acc_m = 0.0; acc_m = acc_m + ((lg(m_ht' + 1) + lg(m_at' + 1)) - lg(m_ht' + m_at' + 1)) for every t'
+ *        acc_e = 0.0; acc_e = acc_e + ((lg(eta_hk + 1) + lg(eta_ak + 1)) - lg(eta_hk + eta_ak + 1)) for every k
+ *        tail1 = lg(m_h + m_a + 1) - (lg(m_h + 1) + lg(m_a + 1))
+ *        tail2 = log_q(m_h + m_a, n_h + n_a) - (log_q(m_h, n_h) + log_q(m_a, n_a))     (log_q: bisbm_entropy's)
+ *        merge_dS = (((acc_m + acc_e) + tail1) + tail2) + (T(shape merged) - T(shape of D))
+ *      T(ka, kb) = (lbinom(ka kb + E - 1, E) + lbinom(na - 1, ka - 1)) + lbinom(nb - 1, kb - 1) from the host's tables
+ *      (bisbm_split_merge_shape_term returns it).  An empty block adds exactly 0 to every other term of S.  No pass over the
+ *      members is needed.  The closed form was chosen over two evaluations of the full description length: it costs K + D
+ *      table gathers a move instead of two passes over the whole block state, and it meets the 1e-9 |S| of the tests.
+ *   6. SPLIT: one free scan (t = scans) from L over members 1 .. M - 1 gives the proposal D' and Q_fwd (mantissa, exponent as in
+ *      "Pair reshuffles" 6.).  dS = 0.0 - merge_dS(D');
+ *      ln A = ((0.0 - beta * dS) + (log((double)K) - log((double)N(shape after)))) - (log(mant) + (double)exp * 0.6931471805599453).
+ *   7. MERGE: a forced pass from L to the present division D gives Q_rev; a member that is not free forced to move, or a factor
+ *      of exactly 0.0, makes Q_rev = (0.0, 0) and the move a certain rejection (ln A = -inf, A = 0.0), the members return in
+ *      transit.  dS = merge_dS(D), evaluated at D before anything moves;
+ *      ln A = ((0.0 - beta * dS) + (log((double)N(shape now)) - log((double)(K - 1)))) + (log(mant) + (double)exp * 0.6931471805599453).
+ *   8. ACCEPT: A = exp(ln A); accepted iff u_acc < A.  Accepted: dS goes onto bisbm_get_cum_dS with one add, and the blocks are
+ *      renumbered: split of a type-a block: away becomes label ka, every type-b label moves up by one; split of a type-b
+ *      block: away becomes label K; merge: the merged block takes r, the labels of that type above s move down by one, and for
+ *      a type-a merge every type-b label moves down by one as well.  Rejected (or refused): labels, m, m_r, n_r, eta and the
+ *      running sum are what they were, integer for integer.  The invariance claim concerns the unlabelled partition only.
+ * Why it is exact: a split x -> y of block b and the merge y -> x of the pair it creates share L; the forward path has
+ * probability (1/2)(1/K) p(L) q(y | L), the reverse (1/2)(1/N(shape of y)) p(L) -- the merge is deterministic given the pair --
+ * and the shape of x has K blocks where that of y has K + 1, which is the K - 1 of step 7.
+ * An accepted move changes the chain's shape: the handle keeps its chains GROUPED BY SHAPE as after bisbm_agg_merge_total (a plain
+ * handle becomes a container at the first accepted move), and a chain that reaches a shape another group already holds joins
+ * that group.  Groups are formed again only after a launch in which some chain was accepted, and only the groups that lost or
+ * gained a chain are rebuilt.  Every device entry regroups its own chains; results are keyed by the global chain id and do not
+ * depend on the number of devices or on the grouping.  AFTER ACCEPTED MOVES THE CALLER RESETS traces, marginal histograms and
+ * every analysis sum that is indexed by block labels, exactly as after bisbm_agg_merge; the numbering-free analysis calls (pair
+ * scores, edge probabilities, co-assignment, fold-in, conditionals, partition distances) go on and average over (Ka, Kb).
+ * k_min / k_max: per type, 1 <= k_min[t] <= k_max[t]; k_max NULL: min(n_t, 127); k_min NULL: (1, 1).  A split needs a spare
+ * block of each type beside the chain's own in the kernel's state: k_max[0] + k_max[1] <= 254, and every chain must have ka +
+ * kb <= 254 (BISBM_ERR_INVALID_ARG / BISBM_ERR_UNSUPPORTED).
+ * Refused with a message and nothing changed: BISBM_RNG_MT19937_COMPAT and two-byte labels (BISBM_ERR_UNSUPPORTED); a clamp,
+ * block constraints or block fields being set (a move renumbers blocks, as bisbm_agg_merge), replica exchange on, a population
+ * in progress (bisbm_population_reset ends it), before bisbm_init / bisbm_shuffle (BISBM_ERR_STATE); beta not finite or <= 0,
+ * k_min / k_max out of order (BISBM_ERR_INVALID_ARG).  moves = 0 is a no-op that zeroes accepted_out.
+ * get_last: the last move of every chain (BISBM_ERR_STATE before the first call); get_total: per chain {splits proposed, splits
+ * accepted, merges proposed, merges accepted} over the handle's lifetime. */
+#define BISBM_SM_SPLIT 0u
+#define BISBM_SM_MERGE 1u
+#define BISBM_SM_EVALUATED 0u
+#define BISBM_SM_SINGLETON 1u
+#define BISBM_SM_AT_K_MAX 2u
+#define BISBM_SM_AT_K_MIN 3u
+#define BISBM_SM_NO_PAIR 4u
+typedef struct bisbm_split_merge_record {
+    uint32_t kind;     /* BISBM_SM_SPLIT / BISBM_SM_MERGE */
+    uint32_t type;     /* 0: a, 1: b (BISBM_SM_NO_PAIR: 0) */
+    uint32_t r, s;     /* global labels in the numbering before the move; split: s = the label away takes if accepted */
+    uint32_t M;        /* members (BISBM_SM_SINGLETON: the block's size; other refusals: 0) */
+    uint32_t refused;  /* BISBM_SM_EVALUATED, or why nothing was evaluated */
+    double q_mant;     /* Q_fwd (split) / Q_rev (merge) */
+    int32_t q_exp;
+    uint32_t accepted;
+    double dS, lnA, A, u_acc;
+    uint32_t ka_before, kb_before, ka_after, kb_after;
+} bisbm_split_merge_record;
+int bisbm_split_merge_run(bisbm_handle h, uint64_t moves, uint32_t scans, double beta, const uint32_t *k_min /* 2, may be NULL */,
+                          const uint32_t *k_max /* 2, may be NULL */, uint64_t *accepted_out /* n_chains, may be NULL */);
+int bisbm_split_merge_get_last(bisbm_handle h, bisbm_split_merge_record *out /* n_chains */);
+int bisbm_split_merge_get_total(bisbm_handle h, uint64_t *out /* n_chains x 4 */);
+/* DIAGNOSTIC (tests and host replays; not needed to run the moves).  The group of its device entry that every chain lives in (0
+ * on an entry whose chains are not grouped): two chains of one device entry with the same shape have the same group. */
+int bisbm_split_merge_get_groups(bisbm_handle h, uint32_t *out /* n_chains */);
+/* DIAGNOSTIC.  Host clock of the last bisbm_split_merge_run in ms, and the part of it spent forming the groups again (copying
+ * chains, allocating groups, rebuilding block state); over several device entries the slowest entry's.  Either may be NULL. */
+int bisbm_split_merge_get_timing(bisbm_handle h, double *call_ms, double *regroup_ms);
+/* DIAGNOSTIC.  T(ka, kb) of step 5 as the library evaluates it (for a host that replays a move). */
+int bisbm_split_merge_shape_term(bisbm_handle h, uint32_t ka, uint32_t kb, double *out);
+
 /* Clamped nodes (no reference counterpart): one mask per handle, one byte per node; a non-zero byte means the node is CLAMPED
  * and no sampler changes its label, in any chain.  Partial labels, one side of a bipartite graph held, an incremental refit, or
  * a seed per block with the same label in every chain, which pins the block numbering (the raw histogram of the marginals is
