@@ -460,7 +460,7 @@ int align_accumulate(bisbm_engine* h, uint32_t* device_counts) {
     if (!device_counts) {
         // (as without the alignment: a histogram of other block counts is started afresh)
         bool stale = false;
-        for (bisbm_engine* d : device_entries(h)) stale = stale || !d->d_counts || d->counts_cols != std::max(ka, kb);
+        for (bisbm_engine* d : device_entries(h)) stale = stale || !d->counts_fit(ka, kb);
         if (stale)
             if (int rc = bisbm_marginals_reset(h)) return rc;
     }

@@ -580,6 +580,10 @@ struct bisbm_engine {
     uint32_t* d_counts = nullptr;     // internal marginal buffer n*kmax
     uint32_t counts_kmax = 0;         // columns d_counts was sized for
     uint32_t counts_cols = 0;         // columns of the histogram it currently holds (max(KA, KB) at the last reset)
+    uint32_t counts_ka = 0, counts_kb = 0;  // ... and the block counts it was started for: a column means a block of that numbering
+    // does the internal histogram hold samples of these block counts?  (Not of their maximum alone: 3 + 2 and 3 + 1 blocks share
+    // a row length and no numbering.)
+    bool counts_fit(uint32_t ka_now, uint32_t kb_now) const { return d_counts && counts_ka == ka_now && counts_kb == kb_now; }
     uint32_t cap_ka = 0, cap_kb = 0;  // block counts d_m / d_m_r / d_n_r / d_eta are allocated for
     std::shared_ptr<bisbm::HostTables> tab;
     uint32_t q_stride = 0;

@@ -9,7 +9,7 @@ namespace bisbm {
 // MAP labels from the internal histogram of one engine (no pooling): argmax kernel + copy
 int single_marginals_map(bisbm_engine* h, uint32_t* labels_out) {
     if (int rc = shared_shape(h, nullptr, nullptr)) return rc;
-    if (!h->d_counts || h->counts_cols != std::max(h->ka, h->kb)) return fail(h, BISBM_ERR_STATE, "no marginal histogram of the present block counts yet");
+    if (!h->counts_fit(h->ka, h->kb)) return fail(h, BISBM_ERR_STATE, "no marginal histogram of the present block counts yet");
     HIPCHK(h, hipSetDevice(h->device));
     DeviceBuf<uint16_t> d_lab;
     RESERVE(h, d_lab, (size_t)h->n);
@@ -52,6 +52,7 @@ int bisbm_marginals_reset(bisbm_handle h) {
         h->counts_kmax = kmax;
     }
     h->counts_cols = kmax;
+    h->counts_ka = h->ka, h->counts_kb = h->kb;
     HIPCHK(h, hipMemsetAsync(h->d_counts, 0, sizeof(uint32_t) * cnt, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BISBM_OK;
@@ -68,8 +69,8 @@ int accumulate_plain(bisbm_engine* h, uint32_t* device_counts) {
     if (!h->devs.empty()) return on_devices(h, [](bisbm_engine* d, size_t) { return bisbm_marginals_accumulate(d, nullptr); });
     HIPCHK(h, hipSetDevice(h->device));
     if (!device_counts) {
-        // (a histogram made before a merge / split changed max(KA, KB) has another row length: start afresh)
-        if (!h->d_counts || h->counts_cols != std::max(h->ka, h->kb)) {
+        // (a histogram made before a merge / split changed the block counts holds another numbering: start afresh)
+        if (!h->counts_fit(h->ka, h->kb)) {
             int rc = bisbm_marginals_reset(h);
             if (rc) return rc;
         }
@@ -114,9 +115,9 @@ int bisbm_marginals_get(bisbm_handle h, uint32_t* counts_out) {
     if (!h->devs.empty()) return multi_marginals_get(h, counts_out);
     if (int rc = shared_shape(h, nullptr, nullptr)) return rc;
     if (!h->d_counts) return fail(h, BISBM_ERR_STATE, "no internal marginal buffer yet");
-    if (h->counts_cols != std::max(h->ka, h->kb))
-        return fail(h, BISBM_ERR_STATE, "the block counts changed since the histogram was made (%u columns then, %u now)", h->counts_cols,
-                    std::max(h->ka, h->kb));
+    if (!h->counts_fit(h->ka, h->kb))
+        return fail(h, BISBM_ERR_STATE, "the block counts changed since the histogram was made (%u + %u then, %u + %u now)", h->counts_ka, h->counts_kb,
+                    h->ka, h->kb);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(counts_out, h->d_counts, sizeof(uint32_t) * (size_t)h->n * std::max(h->ka, h->kb), hipMemcpyDeviceToHost));

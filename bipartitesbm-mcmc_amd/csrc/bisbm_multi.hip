@@ -212,7 +212,7 @@ int multi_marginals_map(bisbm_engine* h, uint32_t* labels_out) {
     const uint32_t kmax = std::max(ka, kb);
     const size_t nd = h->devs.size();
     for (bisbm_engine* d : h->devs)
-        if (!d->d_counts || d->counts_cols != kmax) return fail(h, BISBM_ERR_STATE, "no marginal histogram of the present block counts yet");
+        if (!d->counts_fit(ka, kb)) return fail(h, BISBM_ERR_STATE, "no marginal histogram of the present block counts yet");
     DeviceGuard guard;
     if (int rc = pool_prepare(h, kmax)) return rc;
     DevicePool* P = h->pool;

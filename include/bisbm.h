@@ -174,7 +174,14 @@ int bisbm_get_last_counts(bisbm_handle h, uint64_t *accepted, uint64_t *sweeps);
  * the reference partition, into the internal buffer and into a caller's device_counts alike; without it (the default) the raw
  * labels are counted.  A block label means something only inside one chain, so a histogram of more than one chain is a
  * marginal only when aligned.  bisbm_marginals_reset empties the histogram and drops a library-chosen reference (the
- * alignment mode and a caller's reference stay). */
+ * alignment mode and a caller's reference stay).
+ * After a merge or split (bisbm_agg_merge, bisbm_split_merge_run) the caller resets.  Where it does not: while the chains have
+ * different block counts accumulate, get and map are BISBM_ERR_STATE and nothing changes.  The internal histogram of a plain
+ * handle is dropped when its chains are grouped by shape (bisbm_agg_merge_total, the first accepted split or merge).  Once the
+ * chains share (ka, kb) again, get and map are BISBM_ERR_STATE while there is no histogram of these block counts -- none at
+ * all, or one started for OTHER counts, either of them, also where max(ka, kb) and with it the row length is the same: 3 + 3
+ * and 3 + 2 blocks share no numbering --, and the next accumulate into the internal buffer, raw or aligned, starts afresh and
+ * holds that sample alone (the block sums start afresh with it, a library-chosen reference is taken afresh). */
 int bisbm_marginals_accumulate(bisbm_handle h, uint32_t *device_counts);
 int bisbm_marginals_reset(bisbm_handle h);
 int bisbm_marginals_get(bisbm_handle h, uint32_t *counts_out /* n*kmax, host */);

@@ -18,7 +18,7 @@ import pytest
 
 import cases
 import oracle_lib as O
-from test_gpu_heatbath import _assert_state_is_a_rebuild, _bits, _case, _model, _refused
+from test_gpu_heatbath import _GRAPHS, _assert_state_is_a_rebuild, _bits, _case, _model, _refused
 from test_tempering import philox, u53
 
 B = importlib.import_module("bipartitesbm-mcmc_amd")
@@ -288,6 +288,89 @@ def test_the_replays_saw_accepted_and_rejected_splits_and_merges():
     if not all(SEEN.values()):
         _replay("tiny", 16, 1, beta=0.3)
     assert all(v > 0 for v in SEEN.values()), SEEN
+
+
+# ------------------------------------------------------------------------------------------- 1b. the byte-label edge
+EDGE_NA, EDGE_NB = 262, 264
+EDGE_K_MAX = (127, 127)
+
+
+def _edge_case(ka, kb):
+    """262 + 264 nodes, 2400 edges and a hub of some 600 (node 0), known to _case under a name per creation shape; the start by
+    hand: block 0 of each type holds the type's first nodes (12 at 126 + 127 blocks), every other block two nodes in id order"""
+    name = "sm_byte_edge_%d_%d" % (ka, kb)
+    if name not in _GRAPHS:
+        graph = next((g[0] for k, g in _GRAPHS.items() if k.startswith("sm_byte_edge_")), None)
+        _GRAPHS[name] = (graph or cases.random_graph(11, EDGE_NA, EDGE_NB, 2400, 126, 127, 1, 0), EDGE_NA, EDGE_NB, ka, kb, 1.0)
+    la = np.repeat(np.arange(ka), [EDGE_NA - 2 * (ka - 1)] + [2] * (ka - 1))
+    lb = ka + np.repeat(np.arange(kb), [EDGE_NB - 2 * (kb - 1)] + [2] * (kb - 1))
+    return name, np.concatenate([la, lb]).astype(np.uint32)
+
+
+def _edge_first(ka, kb, lab, want, u_below=0.25):
+    """the lowest first chain id at which move 0 of the replayed chain (the last of three) is the wanted kind and choice, with
+    a u_acc below u_below; the kind and the choice from the oracle's Philox, as the device draws them"""
+    size_of = lambda g: int((lab == g).sum())
+    for first in range(1, 1 << 20):
+        x = _draw(SEED, first + 2, 0, 0)
+        if want(*D.numpy_split_merge_choice(x[0], x[1], ka, kb, (1, 1), EDGE_K_MAX, size_of=size_of)) and u53(*_draw(SEED, first + 2, 0, 1)[:2]) < u_below:
+            return first
+    raise AssertionError("no chain id draws the wanted move")
+
+
+def _replay_edge(ka, kb, want, beta, scans=1):
+    """one move of three chains from the start by hand, the last chain replayed on the host; afterwards every chain's state is a
+    rebuild from its labels and its labels are contiguous per type"""
+    name, lab = _edge_case(ka, kb)
+    (rowptr, col), na, nb, _, _, eps = _case(name)
+    # the padded launch holds (ka + 1) x (kb + 1) blocks: its quadrant fits the LDS, its eta (K + 2 rows of max_degree + 1 words)
+    # is past what the plan keeps there, so the kernel's instantiation with eta in HBM runs (as test_eta_outside_the_lds asserts)
+    deg_max = int(np.diff(rowptr.astype(np.int64)).max())
+    assert 4 * (ka + 1) * (kb + 2) <= 160 * 1024 and 4 * (ka + kb + 2) * (deg_max + 1) > 40 * 1024
+    first = _edge_first(ka, kb, lab, want)
+    chains = 3
+    m = _model(name, chains, first_chain_id=first, labels=lab)
+    m.init_bisbm()
+    helpers = _Helpers(name, beta)
+    out = _replay_move(m, chains - 1, first + chains - 1, name, helpers, scans, beta, (1, 1), EDGE_K_MAX)
+    print("%s: first chain id %d: %s; all chains: %s" % (name, first, out, [(r["kind"], r["type"], r["r"], r["s"], r["M"], r["refused"], r["accepted"]) for r in m.split_merge_last()]))
+    for c in range(chains):
+        _assert_state_is_a_rebuild(m, rowptr, col, c)
+        a, b = m.ka_kb(c)
+        got = m.get_memberships(c)
+        assert sorted(set(got[:na].tolist())) == list(range(a)) and sorted(set(got[na:].tolist())) == list(range(a, a + b)), c
+        assert a <= 127 and b <= 127 and int(got.max()) == a + b - 1
+    helpers.close()
+    m.close()
+    return out
+
+
+def test_a_split_to_127_plus_127_blocks_is_the_host_replay():
+    """126 + 127 blocks, a split of the 12 nodes of type-a block 0 at beta = 0.05: with K = 253 the move carries
+    log(K / N(shape after)) = log(253 / 16002) = -4.1 and -ln Q_fwd of 11 free members is about +7, so it is accepted.  The
+    chain ends at 127 + 127 blocks with labels up to 253.  Observed on an MI355X: first chain id 3294, u_acc = 0.138, the split of 12 members accepted (the two
+    other chains proposed merges of four members at K = 253: one accepted, one rejected)."""
+    out = _replay_edge(126, 127, lambda kind, t, r, s, refused: kind == B.SM_SPLIT and r == 0 and not refused, 0.05)
+    assert out["accepted"] and out["M"] == 12 and out["type"] == 0
+
+
+def test_a_merge_into_the_last_label_at_127_plus_127_blocks_is_the_host_replay():
+    """127 + 127 blocks: the padded launch has 128 + 128, the spare of type b is label 255.  A type-b merge whose s is the last
+    label, 253 -- label 254 of the launch, the upper of the two labels the regrouping takes out -- of two blocks of two nodes.
+    Observed on an MI355X: first chain id 1134, blocks 238 and 253, accepted, as were the type-b merges of the two other chains."""
+    out = _replay_edge(127, 127, lambda kind, t, r, s, refused: kind == B.SM_MERGE and t == 1 and s == 253 and r > 127 and not refused, 0.05)
+    assert out["accepted"] and out["M"] == 4 and (out["type"], out["s"]) == (1, 253)
+
+
+def test_a_type_a_merge_at_127_plus_127_blocks_is_the_host_replay():
+    """every type-b label moves down with the merged type-a block's.  Observed on an MI355X: first chain id 33, blocks 7 and 89, accepted."""
+    out = _replay_edge(127, 127, lambda kind, t, r, s, refused: kind == B.SM_MERGE and t == 0 and r > 0 and not refused, 0.05)
+    assert out["accepted"] and out["M"] == 4 and out["type"] == 0
+
+
+def test_a_split_at_127_plus_127_blocks_is_refused_at_k_max():
+    out = _replay_edge(127, 127, lambda kind, t, r, s, refused: kind == B.SM_SPLIT, 0.05)
+    assert out["refused"] == B.SM_AT_K_MAX and not out["accepted"]
 
 
 # --------------------------------------------------------------------------------------------------------- 2. regrouping
