@@ -95,6 +95,20 @@ HEATBATH_CASES = {c[0]: c for c in [
     ("hb_eta_in_hbm", 300, 200, 3000, 10, 10, 1.0, 1, 0),
 ]}
 
+# Shapes of the held MH sweeps above 64 blocks of a type alone (tests/test_gpu_held_wide.py, pinned on the host by
+# tests/test_oracle_holds.py; the layout of CASES, graphs from random_graph(11, ...)): there the generic kernel is the only MH route.
+# The smallest shapes that reach each edge; outside CASES, so the GPU-vs-oracle matrix does not grow by them.
+HELD_WIDE_CASES = {c[0]: c for c in [
+    # 70 type-a blocks: the proposal's inverse CDF of type a walks two chunks of lanes
+    ("held_k70_k3", 400, 300, 6000, 70, 3, 2.0, 0, 0),
+    # 130 type-b blocks: three chunks; words 0 to 4 of a constraint row; isolated nodes (uniform proposals over 133 blocks)
+    ("held_k3_k130", 300, 400, 6000, 3, 130, 1.0, 0, 4),
+    # 256 blocks, the limit of byte labels: bit 31 of word 7; type b in three chunks, the last of one lane
+    ("held_k127_k129", 400, 400, 6000, 127, 129, 1.0, 2, 0),
+    # a hub of degree above 600 beside 103 blocks: eta stays outside LDS in the generic kernel
+    ("held_k3_k100_hub", 300, 400, 4000, 3, 100, 1.0, 1, 0),
+]}
+
 # ------------------------------------------------------------------ row shapes (tests/test_row_shapes.py, tests/test_gpu_row_shapes.py)
 # The production sweep kernel's edges along the length and the make-up of an adjacency row (kRowCap = 255, byte k_v counters, ids
 # read four at a time and sixteen a round, the eta window).  Outside CASES, so the GPU-vs-oracle matrix does not grow by them.

@@ -416,9 +416,10 @@ def _reshuffle_replay(m, c, gid, name, moves, scans, beta, cls, allowed, mask=No
     return out
 
 
-@pytest.mark.parametrize("name,moves,scans", [("tiny", 4, 1), ("hubs_isolated", 2, 3)])
+@pytest.mark.parametrize("name,moves,scans", [("tiny", 4, 1), ("hubs_isolated", 2, 3), ("wideK", 2, 2)])
 def test_reshuffles_are_the_host_replay_over_the_filtered_members(name, moves, scans):
-    """every third node is unrestricted, the others may sit in their block and the next of its type"""
+    """every third node is unrestricted, the others may sit in their block and the next of its type (wideK: 70 blocks of type a, the
+    membership test of a pair reads the second and the third word of a class's row)"""
     (rowptr, col), na, nb, ka, kb, eps = _case(name)
     chains, c = 3, 2
     m = _model(name, chains, first_chain_id=FIRST_ID)

@@ -46,7 +46,7 @@ _GRAPHS = {}
 
 def _case(name):
     if name not in _GRAPHS:
-        _, na, nb, ne, ka, kb, eps, hubs, iso = cases.HEATBATH_CASES[name] if name in cases.HEATBATH_CASES else cases.CASE[name]
+        _, na, nb, ne, ka, kb, eps, hubs, iso = next(d[name] for d in (cases.HEATBATH_CASES, cases.HELD_WIDE_CASES, cases.CASE) if name in d)
         _GRAPHS[name] = (cases.random_graph(11, na, nb, ne, ka, kb, hubs, iso), na, nb, ka, kb, eps)
     return _GRAPHS[name]
 

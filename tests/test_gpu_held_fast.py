@@ -95,11 +95,12 @@ def _half_lists(name, seed):
     raise AssertionError("no admissible start for %s" % name)
 
 
-def _handle(name, hold, mask=None, warm=0, seed=SEED, fields=None):
+def _handle(name, hold, mask=None, warm=0, seed=SEED, fields=None, lists=None):
     """hold: "clamp" -- shuffle_bisbm (and `warm` unheld sweeps), then a random 30 % clamp (or `mask`); "constraints" -- the
     round-robin start of _half_lists under its table; "both" -- that start and table, and the clamp on top; "none" -- the start of
     "clamp" without the clamp.  seed: the handle's Philox seed.  fields: (class_of_node, field), set after everything else
-    (tests/test_gpu_held_oracle.py)"""
+    (tests/test_gpu_held_oracle.py).  lists: (class_of_node, allowed, start) in the place of _half_lists(name, 3)
+    (tests/test_gpu_held_wide.py, whose shapes have their own recipe)"""
     (rowptr, col), na, nb, ka, kb, eps = _case(name)
     n = na + nb
     if mask is None:
@@ -110,7 +111,7 @@ def _handle(name, hold, mask=None, warm=0, seed=SEED, fields=None):
         if warm:
             m.run_sweeps(warm)
     else:
-        cls, allowed, start = _half_lists(name, 3)
+        cls, allowed, start = _half_lists(name, 3) if lists is None else lists
         m = _model(name, CHAINS, seed=seed, first_chain_id=FIRST_ID, labels=start)
         m.init_bisbm()
         m.constrain(cls, allowed)

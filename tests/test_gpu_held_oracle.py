@@ -58,7 +58,8 @@ _LISTS = {}
 
 def _tables(name, hold, mask=None):
     """The hold of a case: mask (30 % of the nodes unless given), (class_of_node, allowed) and the start of _half_lists(name, 3),
-    (class_of_node, field) of four classes with entries of about 1.5 nats.  None where the hold has no such part."""
+    (class_of_node, field) of four classes with entries of about 1.5 nats.  None where the hold has no such part.  (A module whose
+    shapes need lists of another recipe puts them into _LISTS first: tests/test_gpu_held_wide.py.)"""
     (rowptr, col), na, nb, ka, kb, eps = _case(name)
     n = na + nb
     t = dict(mask=None, cn=None, start=None, fl=None)
@@ -102,7 +103,8 @@ def _oracles(name, t, seed, warm=0):
 def _device(name, t, seed, warm=0):
     """tests/test_gpu_held_fast.py's _handle for the hold of the case, with the seed of the case and the field on top"""
     hold = {(False, False): "none", (True, False): "clamp", (False, True): "constraints", (True, True): "both"}[(t["mask"] is not None, t["cn"] is not None)]
-    return _handle(name, hold, mask=t["mask"], warm=warm, seed=seed, fields=t["fl"])
+    lists = None if t["cn"] is None else t["cn"] + (t["start"],)  # (the table and the start the oracles were given)
+    return _handle(name, hold, mask=t["mask"], warm=warm, seed=seed, fields=t["fl"], lists=lists)
 
 
 # ------------------------------------------------------------------------------------------------------------- the calls

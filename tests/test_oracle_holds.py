@@ -23,7 +23,7 @@ def _bits(x):
 
 def _case(name):
     if name not in _GRAPHS:
-        _, na, nb, ne, ka, kb, eps, hubs, iso = cases.CASE[name]
+        _, na, nb, ne, ka, kb, eps, hubs, iso = cases.HELD_WIDE_CASES[name] if name in cases.HELD_WIDE_CASES else cases.CASE[name]
         _GRAPHS[name] = (cases.random_graph(11, na, nb, ne, ka, kb, hubs, iso), na, nb, ka, kb, eps)
     return _GRAPHS[name]
 
@@ -150,13 +150,14 @@ def _replay_holds(hold, n, na, ka, kb, lab):
 
 
 @pytest.mark.parametrize("hold", ["clamp", "constraints", "fields", "all"])
-def test_orc_anneal_under_holds_is_the_python_replay(hold):
-    """hubs_isolated: three unheld sweeps from the contiguous labels, then 10 sweeps at T = 1 and 10 at the low T under the hold,
-    sweep by sweep: labels and accepted count of orc_anneal equal those of tests/mh_replay.py.  The replay tests
+@pytest.mark.parametrize("name", ["hubs_isolated"] + list(cases.HELD_WIDE_CASES))
+def test_orc_anneal_under_holds_is_the_python_replay(name, hold):
+    """hubs_isolated and the shapes above 64 blocks of a type, where the oracle is the one reference of the device's held sweeps
+    (tests/test_gpu_held_wide.py): three unheld sweeps from the contiguous labels, then 10 sweeps at T = 1 and 10 at the low T under
+    the hold, sweep by sweep: labels and accepted count of orc_anneal equal those of tests/mh_replay.py.  The replay tests
     u < (accu1 / accu0) e where the oracle tests u accu0 < accu1 e: the margin condition (no test within a relative 1e-9, by both
     counts) is what makes the two the same decision, and it is a condition on the seed."""
     import math
-    name = "hubs_isolated"
     (rowptr, col), na, nb, ka, kb, eps = _case(name)
     n = na + nb
     o = _oracle(name, shuffle=False)
@@ -184,7 +185,7 @@ def test_orc_anneal_under_holds_is_the_python_replay(hold):
         for key, v in o.hold_counts().items():
             seen[key] += v
         seen["accepted"] += accepted
-    print("replay under %s: 20 sweeps equal; margin %.3g; %s" % (hold, margin, seen))
+    print("replay of %s under %s: 20 sweeps equal; margin %.3g; %s" % (name, hold, margin, seen))
     assert margin > 1e-9, margin
     assert seen["accepted"] > 0
     assert (seen["clamped"] > 0) == (h["clamp"] is not None) and (seen["barred"] > 0) == (h["constraints"] is not None)
@@ -381,3 +382,19 @@ def test_the_random_sequences_with_holds_cover_what_they_are_for():
     assert total["depth_back"] >= small and total["held_long"] >= long_call
     assert total["held_anneals"] >= small + long_call - 2 and total["fielded_anneals"] >= 2 and total["held_cold"] >= 2
     assert total["cleared_clamps"] >= 1 and total["cleared_lists"] >= 1
+
+
+# ----------------------------------------------------------------- 6. what the held cases above 64 blocks of a type cover
+def test_the_held_cases_above_64_blocks_cover_what_they_are_for():
+    """tests/test_gpu_held_wide.py walked on the host, the oracles' side alone: every case of its matrix (four shapes, five holds)
+    and its four early-stop cases meets the conditions that the device run asserts before it looks at the device -- no accept test
+    within a relative 1e-9 of its threshold, steps of clamped nodes, barred targets, accepted moves and decisions the field turned
+    where the hold has that part, labels up to the last block, bit 255 of the table set in one class and clear in another, a block
+    barred in every word of a row, and a cooling call that one chain leaves early and another runs to its end -- so a case that
+    drifts fails here, without a GPU."""
+    import test_gpu_held_wide as W
+    assert W.NAMES == list(cases.HELD_WIDE_CASES) and len(W.NAMES) == 4 and len(W.HOLDS) == 5
+    for name in W.NAMES:
+        for hold in W.HOLDS:
+            W.matrix_inputs(name, hold)
+        W.early_stop_inputs(name)
